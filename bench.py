@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config hall|hall_plane|bunny|s5|cpu_f64] [--shard strong|weak]
                     [--s5-shard blocks|contiguous] [--repeats R] [--no-s5] [--no-rccl] [--no-cpu-baseline] [--no-fresh-pair]
+                    [--dump-outputs DIR]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* from the environment), or plainly as `python bench.py --gpus N`, in which case this process starts
@@ -14,12 +15,18 @@ A child that does not answer in time is killed (its exact PID), the line is stil
 non-zero: a stuck communicator can neither hold the line back nor end as rc 0.  To profile, put the measuring process
 itself behind the profiler: `rocprofv3 --kernel-trace --stats -- python3 bench.py --leg main [--config ...]`.
 
-What `value` is (round 4).  The K-step region -- EXACTLY K steps between barrier + synchronize on both sides, the max over the
-ranks -- is repeated R times (R >= 25 where a region is short: the driver's `--steps 20` is 0.2 ms of work), each repeat
-between its own barriers; `ms_per_step` is the MEDIAN region / K, `value` = K / median region, the spread beside it
-(`ms_per_step_min` / `_max`, `repeats`).  For N > 1 `value` is the iteration rate of what the ranks compute TOGETHER: K / dt.
+What `value` is.  The K-step region -- EXACTLY K steps between barrier + synchronize on both sides, the max over the ranks --
+is timed once, so `--steps` is the number of timed steps; `ms_per_step` is region / K, `value` = K / region.  `--repeats R`
+times R such regions, each between its own barriers, and reports the MEDIAN region with the spread beside it (`ms_per_step_min`
+/ `_max`, `repeats`).  For N > 1 `value` is the iteration rate of what the ranks compute TOGETHER: K / dt.
 Ranks that shard one cloud (hall, s5) run ONE registration; ranks that run replicas (hall_plane, bunny, cpu_f64) each run
 their own, and the sum over replicas is reported beside it as `aggregate_iterations_per_s`, never as `value`.
+
+`--dump-outputs DIR` (rank 0): after the timed region, what a caller of the loop holds after its last step -- T.npy (the
+composed 4x4 transform), err.npy (the error series of that registration), moved.npy (the moving cloud as moved), idx.npy (the
+correspondences of the last pass), sample_rows.npy (the rows of moved / idx written) -- in float32 / float64.  A moving cloud
+above DUMP_MAX_POINTS points (s5) is written as a fixed sample of rows drawn with a fixed seed.  The inputs depend on the
+arguments alone, so two builds run with the same arguments can be compared file for file.
 
 Workloads (`--config`; every BASELINE.json config has one; each line carries `roofline` and `cpu_baseline`):
   hall        configs[2], the one BASELINE.json's metric is quoted on (default): point-to-point ICP on the hall LiDAR scan,
@@ -650,9 +657,8 @@ def free_port():
 # ======================================================================================================================
 def timed_steps(wl, ranks, K, stride, repeats=None):
     """The K-step region -- EXACTLY K steps between barrier + synchronize on both sides, the max over the ranks -- R times, every
-    repeat between its own barriers.  R: `--repeats`, else at least 25 where a region is short (the driver's `--steps 20` is 0.2 ms
-    of work: ONE such sample says nothing, and the boxes of the pool differ by up to 25 %), as many as make a quarter of a second
-    (at most 400), and 3..7 for regions that are long by themselves (s5: one registration of 30 iterations, 0.15 s).
+    repeat between its own barriers.  R: `--repeats` (or ICP_BENCH_REPEATS), else 1: `--steps` is the number of timed steps, and
+    whoever wants a longer window asks for more of them.
     Returns the R durations (every rank holds the same list) and the loop's event timing summed over all repeats."""
     import torch
     ctx = wl.ctx
@@ -672,13 +678,7 @@ def timed_steps(wl, ranks, K, stride, repeats=None):
     ctx.set_profiling(stride)     # (also restarts the stride: the first launch after this is a timed one)
     dts = [region(stats)]
     if repeats is None or repeats < 1:
-        d0 = dts[0]
-        if d0 < 0.05:
-            repeats = max(25, min(400, int(0.25 / max(d0, 1e-6)) + 1))
-        else:
-            repeats = max(3, min(25, int(1.0 / d0) + 1))
-        if os.environ.get("ICP_BENCH_REPEATS"):
-            repeats = max(1, int(os.environ["ICP_BENCH_REPEATS"]))
+        repeats = max(1, int(os.environ.get("ICP_BENCH_REPEATS") or 1))
     for _ in range(repeats - 1):
         dts.append(region(stats))
     sec, cnt = ctx.loop_timing()
@@ -692,6 +692,27 @@ def region_stats(dts, K):
     med = statistics.median(dts)
     return {"value": K / med, "ms_per_step": 1e3 * med / K, "ms_per_step_min": 1e3 * min(dts) / K, "ms_per_step_max": 1e3 * max(dts) / K,
             "repeats": len(dts), "region_ms_median": 1e3 * med, "region_ms_min": 1e3 * min(dts), "region_ms_max": 1e3 * max(dts)}
+
+
+DUMP_MAX_POINTS = 1 << 20      # --dump-outputs: larger moving clouds are sampled (moved + idx + rows: 42 MB at most, fp64)
+DUMP_SEED = 0
+
+
+def dump_outputs(ctx, out_dir):
+    """--dump-outputs: the loop's state after the timed region's last step, as a caller of icp_loop_* reads it; returns the
+    arrays written.  Indices and rows are written as float64 (exact below 2^53)."""
+    import numpy as np
+    st = ctx.loop_state()
+    moved, idx = ctx.get_moving(), ctx.loop_indices()
+    rows = np.arange(moved.shape[0])
+    if rows.size > DUMP_MAX_POINTS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.size, DUMP_MAX_POINTS, replace=False))
+    arrays = {"T": np.asarray(st["T"], dtype=np.float64), "err": np.asarray(st["err"], dtype=np.float64),
+              "moved": moved[rows], "idx": idx[rows].astype(np.float64), "sample_rows": rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return arrays
 
 
 def roofline_leg(wl, K, passes_full, region, stride):
@@ -876,6 +897,8 @@ def leg_main(args, rank, local_rank, world):
         stride = 7 if (regs_expected >= 70 and not brief) else 0
     dts, stats, sec1, cnt1, passes1 = timed_steps(wl, ranks, K, stride, args.repeats)
     st = ctx.loop_state()
+    if args.dump_outputs and rank == 0 and not brief:
+        dump_outputs(ctx, args.dump_outputs)     # (before the roofline leg: its registrations would overwrite the state)
     out = None
     if rank == 0:
         rs = region_stats(dts, K)
@@ -1089,9 +1112,11 @@ def main():
     ap.add_argument("--s5-shard", dest="s5_shard", choices=("blocks", "contiguous"), default="blocks",
                     help="s5, N > 1: blocks = the cloud dealt to the ranks in blocks of 16 384 points along a Hilbert curve (even loads); "
                          "contiguous = icp_shard_range's ranges (round 3: the eighths take 16 to 30 ms per registration)")
-    ap.add_argument("--repeats", type=int, default=None, help="repeats of the K-step region (default: >= 25 for short regions, see timed_steps)")
+    ap.add_argument("--repeats", type=int, default=None, help="repeats of the K-step region, the median reported (default 1: --steps is the number of timed steps)")
     ap.add_argument("--no-s5", action="store_true", help="hall: skip the brief configs[4] leg beside the line")
     ap.add_argument("--no-fresh-pair", action="store_true")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (rank 0)")
     ap.add_argument("--route", choices=("local", "rccl", "none"), default=None, help="(internal) the iteration's sum over the ranks")
     ap.add_argument("--brief", action="store_true", help="(internal) an auxiliary leg: timed regions only")
     ap.add_argument("--leg", choices=("main",), default=None, help="(internal) run the measurement in this process")
@@ -1103,6 +1128,9 @@ def main():
         args.warmup = DEFAULT_STEPS[args.config][1]
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
         raise SystemExit("--gpus >= 1, --steps >= 1, --warmup >= 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+        os.makedirs(args.dump_outputs, exist_ok=True)     # (a path that cannot be written fails here, before any GPU work)
     if args.leg is None:
         argv = [a for a in sys.argv[1:]]
         sys.exit(supervise(args, argv))

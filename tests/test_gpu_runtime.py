@@ -209,8 +209,8 @@ def test_bench_with_the_drivers_arguments():
     d = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5"])
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["value"] > 0 and d["unit"] == "iterations/s"
     assert abs(d["value"] - 20 / (d["ms_per_step"] * 20e-3)) < 1e-6 * d["value"]
-    # round 4: the 0.2 ms region is repeated (each repeat between its own barriers), the median is the figure, the spread beside it
-    assert d["repeats"] >= 25 and d["ms_per_step_min"] <= d["ms_per_step"] <= d["ms_per_step_max"]
+    # --steps is the number of timed steps: ONE region of exactly K steps unless --repeats asks for more
+    assert d["repeats"] == 1 and d["ms_per_step_min"] == d["ms_per_step"] == d["ms_per_step_max"]
     assert d["config"]["registrations_per_region"] == 2 and d["config"]["registrations_timed"] == 2 * d["repeats"]
     assert "aggregate_iterations_per_s" not in d
     # ... what a pair the context has not seen costs, and the host's model string beside the CPU figure
@@ -232,13 +232,39 @@ def test_bench_with_the_drivers_arguments():
     assert d["final_rms_error"] < 1e-3
 
 
+def test_bench_dump_outputs(tmp_path, orc, golden):
+    """--dump-outputs: the loop's state after the timed region's last step, float32 / float64 only, the same bits from run to
+    run with the same arguments, and a moved cloud that is the dumped transform applied to the hall moving cloud"""
+    args = ["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-s5", "--no-fresh-pair"]
+    runs = []
+    for name in ("a", "b"):
+        d = _bench(args + ["--dump-outputs", str(tmp_path / name)])
+        assert d["steps"] == 20 and d["repeats"] == 1 and d["ms_per_step"] > 0
+        files = sorted(p.name for p in (tmp_path / name).iterdir())
+        assert files == ["T.npy", "err.npy", "idx.npy", "moved.npy", "sample_rows.npy"], files
+        assert sum((tmp_path / name / f).stat().st_size for f in files) <= 64 << 20
+        runs.append({f[:-4]: np.load(tmp_path / name / f) for f in files})
+    a, b = runs
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), (k, a[k].dtype)
+        assert np.array_equal(a[k], b[k]), k
+    P, Q = orc.hall_clouds(golden)
+    assert a["T"].shape == (4, 4) and np.array_equal(a["T"][3], [0, 0, 0, 1])
+    assert a["err"].size >= 2 and a["err"][0] == 0 and np.all(a["err"][1:] > 0)
+    assert a["moved"].shape == P.shape and a["moved"].dtype == np.float32
+    assert np.array_equal(a["sample_rows"], np.arange(P.shape[0]))
+    assert np.array_equal(a["idx"], np.round(a["idx"])) and a["idx"].min() >= 0 and a["idx"].max() < Q.shape[0]
+    want = P.astype(np.float64) @ a["T"][:3, :3].T + a["T"][:3, 3]
+    assert np.abs(a["moved"] - want).max() < 1e-4 * np.abs(P).max()
+
+
 @pytest.mark.parametrize("cfg,extra", [("hall_plane", ["--steps", "40", "--warmup", "10"]), ("bunny", ["--steps", "44", "--warmup", "0"]),
                                        ("s5", ["--points", "600000", "--steps", "8", "--warmup", "2"]), ("cpu_f64", ["--steps", "120", "--warmup", "10"])])
 def test_bench_every_config_carries_roofline_and_cpu_baseline(cfg, extra):
     """BASELINE configs[0], [1], [3], [4] through `bench.py --config ...`: a line with an EXECUTED-work roofline of the config's own
     kernel (frac <= 1, recomputable from its parts) and a CPU baseline timed beside it"""
     d = _bench(["--config", cfg] + extra)
-    assert d["fresh_pair_ms"] > d["setup_ms"] > 0 and d["repeats"] >= 3
+    assert d["fresh_pair_ms"] > d["setup_ms"] > 0 and d["repeats"] == 1
     assert d["value"] > 0 and d["unit"] == "iterations/s" and d["dtype"] == ("f64" if cfg == "cpu_f64" else "f32")
     r = d["roofline"]
     assert r["peak"] == (78.6 if cfg == "cpu_f64" else 157.3) and r["unit"] == "TFLOP/s" and r["bound"] == "valu"

@@ -148,7 +148,7 @@ def test_generators_match_oracle_bitwise(pkg, orc):
     assert np.array_equal(D64, Dc) and np.array_equal(ds.make_model_cpu(D64), Mc)
 
 
-def test_readers_match_fixtures(pkg, golden):
+def test_readers_match_fixtures(pkg, golden, tmp_path):
     ds = pkg.datasets
     for head, full in (("bunny_res_head.csv", "bunny_res_xyz_f32.bin"), ("bunny_head.csv", "bunny_xyz_f32.bin")):
         pts = ds.read_xyz_text(os.path.join(golden, head))
@@ -161,12 +161,9 @@ def test_readers_match_fixtures(pkg, golden):
     assert alt.shape == az.shape == (16,) and abs(alt[0] - 15.379) < 1e-6 and abs(az[15] + 0.857) < 1e-6
     # binary packet form of the same dump
     vals = np.array([int(x) for x in open(os.path.join(golden, "os1_two_packets.csv")).read().split()], dtype=np.uint8)
-    path = os.path.join(golden, "_tmp_packets.bin")
+    path = str(tmp_path / "packets.bin")
     vals.tofile(path)
-    try:
-        r2, enc2 = ds.read_os1_ranges(path)
-    finally:
-        os.remove(path)
+    r2, enc2 = ds.read_os1_ranges(path)
     assert enc2 == enc and np.array_equal(r2, r)
     with pytest.raises(pkg.IcpError) as e:
         ds.read_xyz_text(os.path.join(golden, "does_not_exist.csv"))
@@ -248,7 +245,7 @@ def test_shared_rows_plan_always_fits_the_grid(pkg):
 
 
 def test_bench_region_statistics():
-    """round 4: `value` = K over the MEDIAN of the repeated K-step regions, the spread beside it -- never a single sample"""
+    """`value` = K over the MEDIAN of the K-step regions (one, unless --repeats asks for more), the spread beside it"""
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_mod2", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
@@ -257,3 +254,35 @@ def test_bench_region_statistics():
     assert rs["repeats"] == 5 and abs(rs["value"] - 20 / 0.25e-3) < 1e-6
     assert abs(rs["ms_per_step"] - 0.25 / 20) < 1e-12 and abs(rs["ms_per_step_min"] - 0.21 / 20) < 1e-12 and abs(rs["ms_per_step_max"] - 0.90 / 20) < 1e-12
     assert bench.cpu_model() != ""
+
+
+def test_bench_dump_outputs_samples_a_large_cloud(tmp_path):
+    """--dump-outputs on an s5-sized loop (10 M points): under 64 MB through a sample of rows fixed by the seed, the same rows
+    from call to call, float32 / float64 only"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 10_000_000
+
+    class Ctx:     # what icp_loop_state / icp_get_moving / icp_loop_indices hand back, without a device
+        def loop_state(self):
+            return {"T": np.eye(4), "err": np.array([0.0, 0.5, 0.25])}
+
+        def get_moving(self):
+            return np.repeat(np.arange(n, dtype=np.float32), 3).reshape(n, 3)
+
+        def loop_indices(self):
+            return np.arange(n, dtype=np.int32)[::-1].copy()
+
+    a = bench.dump_outputs(Ctx(), str(tmp_path / "a"))
+    b = bench.dump_outputs(Ctx(), str(tmp_path / "b"))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["T.npy", "err.npy", "idx.npy", "moved.npy", "sample_rows.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64 << 20
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and np.array_equal(np.load(tmp_path / "a" / (k + ".npy")), v), k
+    rows = a["sample_rows"]
+    assert rows.size == bench.DUMP_MAX_POINTS and np.array_equal(rows, b["sample_rows"]) and np.all(np.diff(rows) > 0)
+    assert rows.min() >= 0 and rows.max() < n
+    assert np.array_equal(a["moved"][:, 2], rows) and np.array_equal(a["idx"], n - 1 - rows)
