@@ -1,5 +1,5 @@
 // icp_host_loop.h -- the host half of the ICP driver loop, free of any device call: error series, stop
-// rule, minimisation, transform composition.  The device loop (icp_api.cpp) and the host-only C ABI
+// rule, minimisation, transform composition.  The device loop (icp_loop.cpp) and the host-only C ABI
 // (icp_host_loop_*, used by the multi-rank CPU tests) run this one implementation.
 #pragma once
 #include <vector>

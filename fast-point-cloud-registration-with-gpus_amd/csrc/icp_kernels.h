@@ -118,7 +118,7 @@ enum { ICP_MB64_CMD = 6 };   // (within each part; tags: word 7 of each part)
 // How long a block waits for a message before it gives up (which reads as EXIT), in WALL-CLOCK seconds of the device's
 // constant 100 MHz counter -- the same budget whatever memory the poll goes to.  Blocks that listen to block 0's relay
 // wait twice as long: block 0 decides, and publishes its verdict (message or EXIT) through the relay.  The host side of
-// the contract (icp_api.cpp, kMailLeaseS) never posts a message a block might no longer be waiting for.
+// the contract (icp_loop.cpp, kMailLeaseS) never posts a message a block might no longer be waiting for.
 #define ICP_MAILBOX_BUDGET_S 4
 constexpr long long ICP_MAILBOX_BUDGET_TICKS = (long long)ICP_MAILBOX_BUDGET_S * 100000000ll;
 struct NNFusedTransform {

@@ -802,7 +802,7 @@ def _two_ranks_on_one_device(pkg, golden, metric, dtype, env=None, max_iter=100,
 def test_two_ranks_one_node_local_communicator(pkg, orc, golden, resident):
     """two ranks with a shard of the hall scan each, both on cuda:0: both end with the same bits, and with the run of one rank
     holding the whole cloud up to the association of the fp64 sums.  Ranks that share a DEVICE run one launch per pass by
-    default (two resident kernels need not fit the machine together: the circular wait of icp_api.cpp, can_reside);
+    default (two resident kernels need not fit the machine together: the circular wait of icp_loop.cpp, can_reside);
     ICP_DEBUG=shared_resident -- two hall-sized shards do fit -- keeps each rank's resident kernel, the form two ranks on
     two devices run"""
     got = _two_ranks_on_one_device(pkg, golden, pkg.ICP_POINT_TO_POINT, np.float32, {"ICP_DEBUG": "shared_resident"} if resident else None)
