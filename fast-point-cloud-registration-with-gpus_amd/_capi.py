@@ -23,6 +23,7 @@ ICP_ERR_NOMEM = -8
 ICP_F32, ICP_F64 = 0, 1
 ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1
 ICP_NMOM = 32
+ICP_BATCH_MAX_POINTS = 65536   # per cloud of one pair of a batch
 MOM_ERR, MOM_CNT, MOM_SP, MOM_SQ, MOM_SQP, MOM_SPP, MOM_SQQ, MOM_C, MOM_B = 0, 1, 2, 5, 8, 17, 18, 2, 23
 
 
@@ -40,6 +41,7 @@ class icp_result(C.Structure):
 
 _vp, _i, _pi = C.c_void_p, C.c_int, C.POINTER(C.c_int)
 _pd, _pf, _pi32, _pu32 = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+_pi64 = C.POINTER(C.c_int64)
 
 # name -> (restype, argtypes); every symbol of include/icp_mi355x.h and include/icp_mi355x_diag.h
 SIGNATURES = {
@@ -83,6 +85,16 @@ SIGNATURES = {
     "icp_loop_timing_passes": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "icp_loop_phase_seconds": (_i, [_vp, _pd, _pd]),
     "icp_loop_indices": (_i, [_vp, _vp]),
+    "icp_batch_create": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, _i, C.POINTER(_vp)]),
+    "icp_batch_destroy": (None, [_vp]),
+    "icp_batch_begin": (_i, [_vp, C.POINTER(icp_params)]),
+    "icp_batch_run": (_i, [_vp, _i, _pi, _pi]),
+    "icp_batch_state": (_i, [_vp, _i, _pi, _pi, _pi, _pd, _i, _pd]),
+    "icp_batch_done": (_i, [_vp, _pi32]),
+    "icp_batch_get_moving": (_i, [_vp, _vp]),
+    "icp_batch_get_indices": (_i, [_vp, _pi32]),
+    "icp_batch_loop_indices": (_i, [_vp, _pi32]),
+    "icp_point_to_point_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_comm_unique_id": (_i, [_vp]),
     "icp_comm_init": (_i, [_vp, _vp, _i, _i]),
     "icp_comm_destroy": (_i, [_vp]),

@@ -1,0 +1,407 @@
+// icp_batch.cpp -- batched point-to-point ICP (icp_batch_*, icp_point_to_point_batch): many independent pairs, and per step ONE
+// matching launch + ONE reduction launch + ONE download of ICP_NMOM doubles per pair for every pair still running.
+//
+//   step k:  [R, t + mode of every pair: H2D]  ->  nn_match_batch (transform + error, match, moments per work item)
+//            ->  batch_finalize_kernel (per pair, fixed order)  ->  D2H count x ICP_NMOM  ->  sync
+//            ->  HostLoop::advance per pair that took part (error, stop rule, 3x3 solve)
+//
+// Every pair runs its own icp::HostLoop, the single-pair loop's host half (icp_host_loop.cpp): the same stop rule, the same
+// composition of T, the same err series.  A pass of a pair is what loop_enqueue_body (icp_loop.cpp) makes of it: the motion
+// solved by the previous pass is applied in the front of the launch (note_applied when it is enqueued), and the loop's last,
+// error-only pass matches nothing.  The reference runs that loop once per program (src/ICP_point_to_point.cu:295-423,
+// src/ICP_CPU.c:217-271).
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "icp_ctx.h"
+
+struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header only names it, as icp_ctx)
+    icp_ctx* ctx = nullptr;
+    int count = 0;
+    int prec = ICP_F32;
+    size_t esize = sizeof(float);
+    std::vector<int64_t> moff;               // the caller's moving offsets: the layout of get_moving / get_indices
+    std::vector<icp::BatchPair> pairs;       // where each pair lives on the device
+    int n_items = 0;
+    long long p_plane = 0, q_plane = 0;      // elements per SoA plane of the moving / model clouds
+    DevBuf P, P0, Q, items, pairs_d, ctl, idx[2], partials, mom;   // P0: the moving clouds as uploaded (icp_batch_begin)
+    void* h_ctl = nullptr;                   // pinned: R, t of every pair (12 values of the precision), then its mode (int)
+    double* h_mom = nullptr;                 // pinned: count x ICP_NMOM
+    size_t rt_bytes = 0, ctl_bytes = 0;
+    bool begun = false;                      // a loop is under way (or has ended) and its state is readable
+    long long steps = 0;                     // steps since icp_batch_begin: step k matches into idx[k & 1]
+    std::vector<icp::HostLoop> H;
+    std::vector<int> status;                 // ICP_OK, or the rc that ended the pair's loop
+    std::vector<int> last_match;             // idx buffer of the pair's most recent matching pass
+    std::vector<int> applied_buf;            // idx buffer of the pass whose motion the pair applied last
+};
+
+namespace {
+
+bool running(const icp_batch* b, int p) { return b->begun && !b->H[p].done && b->status[p] == ICP_OK; }
+
+int count_running(const icp_batch* b)
+{
+    int k = 0;
+    for (int p = 0; p < b->count; ++p) k += running(b, p) ? 1 : 0;
+    return k;
+}
+
+// a batch borrows the context's device and stream -- never in the middle of the context's own pass
+int ready(icp_batch* b)
+{
+    if (!b) return fail(ICP_ERR_INVALID, "null batch");
+    if (int rc = use(b->ctx)) return rc;
+    if (b->ctx->loop.pending) return fail(ICP_ERR_STATE, "the context has an enqueued pass that is not completed (icp_loop_complete first)");
+    return ICP_OK;
+}
+
+void release(icp_batch* b)
+{
+    for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom}) d->release();
+    if (b->h_ctl) (void)hipHostFree(b->h_ctl);
+    if (b->h_mom) (void)hipHostFree(b->h_mom);
+    delete b;
+}
+
+int check_offsets(const int64_t* off, int count, const char* what)
+{
+    if (off[0] != 0) return fail(ICP_ERR_INVALID, std::string(what) + " offsets must start at 0");
+    for (int p = 0; p < count; ++p) {
+        const int64_t len = off[p + 1] - off[p];
+        if (len < 1) return fail(ICP_ERR_INVALID, std::string(what) + " offsets must be strictly increasing (every cloud has >= 1 point)");
+        if (len > ICP_BATCH_MAX_POINTS) return fail(ICP_ERR_INVALID, std::string("a ") + what + " cloud has more than ICP_BATCH_MAX_POINTS points");
+    }
+    return ICP_OK;
+}
+
+template <typename F>
+bool all_finite(const void* aos, int64_t points)
+{
+    const F* a = static_cast<const F*>(aos);
+    for (int64_t i = 0; i < 3 * points; ++i)
+        if (!std::isfinite(a[i])) return false;
+    return true;
+}
+
+// the pairs' AoS clouds -> padded SoA planes, every cloud at its offset (the padding is never read)
+template <typename F>
+std::vector<F> to_planes(const void* aos, const int64_t* off, int count, const std::vector<long long>& dst, long long plane)
+{
+    const F* a = static_cast<const F*>(aos);
+    std::vector<F> out((size_t)(3 * plane), F(0));
+    for (int p = 0; p < count; ++p)
+        for (int64_t i = 0; i < off[p + 1] - off[p]; ++i)
+            for (int k = 0; k < 3; ++k) out[(size_t)(k * plane + dst[p] + i)] = a[3 * (off[p] + i) + k];
+    return out;
+}
+
+template <typename F>
+void from_planes(const std::vector<char>& raw, const icp_batch* b, void* aos)
+{
+    const F* s = reinterpret_cast<const F*>(raw.data());
+    F* o = static_cast<F*>(aos);
+    for (int p = 0; p < b->count; ++p)
+        for (int i = 0; i < b->pairs[p].n; ++i)
+            for (int k = 0; k < 3; ++k) o[3 * (b->moff[p] + i) + k] = s[k * b->p_plane + b->pairs[p].p_off + i];
+}
+
+template <typename F>
+void put_rt(void* dst, const double* R, const double* t)
+{
+    F* o = static_cast<F*>(dst);
+    for (int k = 0; k < 9; ++k) o[k] = (F)R[k];
+    for (int k = 0; k < 3; ++k) o[9 + k] = (F)t[k];
+}
+
+int upload(icp_batch* b, const void* moving, const int64_t* moving_off, const void* model, const int64_t* model_off)
+{
+    icp_ctx* c = b->ctx;
+    std::vector<long long> pdst(b->count), qdst(b->count);
+    for (int p = 0; p < b->count; ++p) { pdst[p] = b->pairs[p].p_off; qdst[p] = b->pairs[p].q_off; }
+    const size_t pb = 3 * (size_t)b->p_plane * b->esize, qb = 3 * (size_t)b->q_plane * b->esize;
+    HIP_TRY(b->P.ensure(pb));
+    HIP_TRY(b->P0.ensure(pb));
+    HIP_TRY(b->Q.ensure(qb));
+    if (b->prec == ICP_F64) {
+        const std::vector<double> ps = to_planes<double>(moving, moving_off, b->count, pdst, b->p_plane);
+        const std::vector<double> qs = to_planes<double>(model, model_off, b->count, qdst, b->q_plane);
+        HIP_TRY(hipMemcpyAsync(b->P0.p, ps.data(), pb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(b->Q.p, qs.data(), qb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));   // (before the host vectors go)
+    } else {
+        const std::vector<float> ps = to_planes<float>(moving, moving_off, b->count, pdst, b->p_plane);
+        const std::vector<float> qs = to_planes<float>(model, model_off, b->count, qdst, b->q_plane);
+        HIP_TRY(hipMemcpyAsync(b->P0.p, ps.data(), pb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(b->Q.p, qs.data(), qb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(b->P.p, b->P0.p, pb, hipMemcpyDeviceToDevice, c->stream));
+    std::vector<icp::BatchItem> items;
+    items.reserve((size_t)b->n_items);
+    for (int p = 0; p < b->count; ++p)
+        for (int first = 0; first < b->pairs[p].n; first += icp::BATCH_ITEM)
+            items.push_back(icp::BatchItem{p, first, std::min(icp::BATCH_ITEM, b->pairs[p].n - first), 0});
+    HIP_TRY(b->items.ensure(items.size() * sizeof(icp::BatchItem)));
+    HIP_TRY(b->pairs_d.ensure(b->pairs.size() * sizeof(icp::BatchPair)));
+    HIP_TRY(hipMemcpyAsync(b->items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b->pairs_d.p, b->pairs.data(), b->pairs.size() * sizeof(icp::BatchPair), hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY(b->idx[k].ensure((size_t)b->p_plane * sizeof(int32_t)));
+        HIP_TRY(hipMemsetAsync(b->idx[k].p, 0, (size_t)b->p_plane * sizeof(int32_t), c->stream));
+    }
+    HIP_TRY(b->partials.ensure((size_t)b->n_items * ICP_NMOM * sizeof(double)));
+    HIP_TRY(b->mom.ensure((size_t)b->count * ICP_NMOM * sizeof(double)));
+    b->rt_bytes = (size_t)b->count * 12 * b->esize;
+    b->ctl_bytes = b->rt_bytes + (size_t)b->count * sizeof(int);
+    HIP_TRY(b->ctl.ensure(b->ctl_bytes));
+    HIP_TRY(hipHostMalloc(&b->h_ctl, b->ctl_bytes, hipHostMallocDefault));
+    std::memset(b->h_ctl, 0, b->ctl_bytes);
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_mom), (size_t)b->count * ICP_NMOM * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // (items: a host vector)
+    return ICP_OK;
+}
+
+// one step: enqueue the pass of every running pair, then complete it (loop_enqueue_body + loop_complete_body, per pair)
+int step(icp_batch* b)
+{
+    icp_ctx* c = b->ctx;
+    const int cur = (int)(b->steps & 1);
+    int* mode = reinterpret_cast<int*>(static_cast<char*>(b->h_ctl) + b->rt_bytes);
+    for (int p = 0; p < b->count; ++p) {
+        mode[p] = 0;
+        if (!running(b, p)) continue;
+        icp::HostLoop& H = b->H[p];
+        const bool apply = H.have_rt;
+        const bool final_only = H.next_is_final();   // the loop ends after this error whatever it is: nothing is matched
+        if (apply) {
+            void* rt = static_cast<char*>(b->h_ctl) + (size_t)p * 12 * b->esize;
+            if (b->prec == ICP_F64) put_rt<double>(rt, H.R, H.t);
+            else put_rt<float>(rt, H.R, H.t);
+            b->applied_buf[p] = b->last_match[p];
+            H.note_applied();
+            mode[p] |= icp::BATCH_APPLY;
+        }
+        if (!final_only) {
+            b->last_match[p] = cur;
+            mode[p] |= icp::BATCH_MATCH;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(b->ctl.p, b->h_ctl, b->ctl_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(icp::launch_batch_pass(b->prec, (const icp::BatchItem*)b->items.p, b->n_items, (const icp::BatchPair*)b->pairs_d.p, b->count,
+                                   (const int*)(static_cast<char*>(b->ctl.p) + b->rt_bytes), b->ctl.p, b->P.p, b->p_plane, b->Q.p,
+                                   b->q_plane, (const int32_t*)b->idx[cur ^ 1].p, (int32_t*)b->idx[cur].p, (double*)b->partials.p,
+                                   (double*)b->mom.p, c->stream));
+    HIP_TRY(hipMemcpyAsync(b->h_mom, b->mom.p, (size_t)b->count * ICP_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    b->steps += 1;
+    for (int p = 0; p < b->count; ++p) {
+        if (mode[p] == 0) continue;
+        const int rc = b->H[p].advance(b->h_mom + (size_t)p * ICP_NMOM);
+        if (rc != ICP_OK) {   // a numeric failure ends this pair only; what its completed passes produced stays readable
+            b->status[p] = rc;
+            b->H[p].done = true;
+        }
+    }
+    return ICP_OK;
+}
+
+// the buffer each pair's indices are read from: its most recent matching pass, or the pass whose motion it applied last
+int download_indices(icp_batch* b, bool contributing, int32_t* out)
+{
+    if (int rc = ready(b)) return rc;
+    if (!out) return fail(ICP_ERR_INVALID, "idx_out == NULL");
+    if (!b->begun || b->steps == 0) return fail(ICP_ERR_STATE, "no matching pass since icp_batch_begin");
+    std::vector<int32_t> h[2];
+    for (int k = 0; k < 2; ++k) {
+        h[k].resize((size_t)b->p_plane);
+        HIP_TRY(hipMemcpyAsync(h[k].data(), b->idx[k].p, (size_t)b->p_plane * sizeof(int32_t), hipMemcpyDeviceToHost, b->ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    for (int p = 0; p < b->count; ++p) {
+        const int which = contributing && b->H[p].applied > 0 ? b->applied_buf[p] : b->last_match[p];
+        std::memcpy(out + b->moff[p], h[which].data() + b->pairs[p].p_off, (size_t)b->pairs[p].n * sizeof(int32_t));
+    }
+    return ICP_OK;
+}
+
+}  // namespace
+
+#pragma GCC visibility push(default)   // (the C ABI)
+extern "C" {
+
+int icp_batch_create(icp_ctx* c, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
+                     const int64_t* model_off, int precision, icp_batch** out)
+{
+    if (!out) return fail(ICP_ERR_INVALID, "out == NULL");
+    *out = nullptr;
+    if (!c) return fail(ICP_ERR_INVALID, "null context");
+    if (count < 1) return fail(ICP_ERR_INVALID, "a batch needs at least one pair");
+    if (!moving_aos || !moving_off || !model_aos || !model_off) return fail(ICP_ERR_INVALID, "null cloud or offsets");
+    if (precision != ICP_F32 && precision != ICP_F64) return fail(ICP_ERR_INVALID, "unknown precision");
+    if (int rc = check_offsets(moving_off, count, "moving")) return rc;
+    if (int rc = check_offsets(model_off, count, "model")) return rc;
+    // (icp_set_* refuse a cloud with a NaN or an infinite coordinate; so does a batch, whichever pair holds it)
+    const bool finite = precision == ICP_F64 ? all_finite<double>(moving_aos, moving_off[count]) && all_finite<double>(model_aos, model_off[count])
+                                             : all_finite<float>(moving_aos, moving_off[count]) && all_finite<float>(model_aos, model_off[count]);
+    if (!finite) return fail(ICP_ERR_INVALID, "a cloud of the batch has a NaN or an infinite coordinate");
+    if (int rc = use(c)) return rc;
+    if (c->loop.pending) return fail(ICP_ERR_STATE, "the context has an enqueued pass that is not completed (icp_loop_complete first)");
+    ScopedPin pin(c);
+    icp_batch* b = new (std::nothrow) icp_batch();
+    if (!b) return fail(ICP_ERR_NOMEM, "batch");
+    b->ctx = c;
+    b->count = count;
+    b->prec = precision;
+    b->esize = precision == ICP_F64 ? sizeof(double) : sizeof(float);
+    b->moff.assign(moving_off, moving_off + count + 1);
+    b->pairs.resize((size_t)count);
+    long long items = 0;
+    for (int p = 0; p < count; ++p) {
+        icp::BatchPair& pr = b->pairs[p];
+        pr.n = (int)(moving_off[p + 1] - moving_off[p]);
+        pr.m = (int)(model_off[p + 1] - model_off[p]);
+        pr.p_off = b->p_plane;
+        pr.q_off = b->q_plane;
+        b->p_plane += icp::round_up(pr.n, icp::BATCH_ALIGN);
+        b->q_plane += icp::round_up(pr.m, icp::BATCH_ALIGN);
+        pr.item0 = (int)std::min<long long>(items, INT_MAX);
+        items += (pr.n + icp::BATCH_ITEM - 1) / icp::BATCH_ITEM;
+        pr.item1 = (int)std::min<long long>(items, INT_MAX);
+    }
+    if (items > INT_MAX) {
+        delete b;
+        return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    }
+    b->n_items = (int)items;
+    b->H.resize((size_t)count);
+    b->status.assign((size_t)count, ICP_OK);
+    b->last_match.assign((size_t)count, 0);
+    b->applied_buf.assign((size_t)count, 0);
+    if (int rc = upload(b, moving_aos, moving_off, model_aos, model_off)) {
+        (void)hipStreamSynchronize(c->stream);
+        release(b);
+        return rc;
+    }
+    *out = b;
+    return ICP_OK;
+}
+
+void icp_batch_destroy(icp_batch* b)
+{
+    if (!b) return;
+    (void)hipSetDevice(b->ctx->device);
+    release(b);
+}
+
+int icp_batch_begin(icp_batch* b, const icp_params* prm)
+{
+    if (int rc = ready(b)) return rc;
+    if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
+    if (prm->metric != ICP_POINT_TO_POINT) return fail(ICP_ERR_INVALID, "a batch runs point-to-point only");
+    if (prm->precision != b->prec) return fail(ICP_ERR_INVALID, "params precision differs from the batch's clouds");
+    if (prm->max_iter < 1) return fail(ICP_ERR_INVALID, "max_iter must be >= 1");
+    b->begun = false;
+    for (int p = 0; p < b->count; ++p)
+        if (int rc = b->H[p].begin(*prm)) return fail(rc, "bad loop parameters");
+    b->status.assign((size_t)b->count, ICP_OK);
+    b->last_match.assign((size_t)b->count, 0);
+    b->applied_buf.assign((size_t)b->count, 0);
+    HIP_TRY(hipMemcpyAsync(b->P.p, b->P0.p, 3 * (size_t)b->p_plane * b->esize, hipMemcpyDeviceToDevice, b->ctx->stream));
+    b->steps = 0;
+    b->begun = true;
+    return ICP_OK;
+}
+
+int icp_batch_run(icp_batch* b, int max_steps, int* steps_done, int* active)
+{
+    if (int rc = ready(b)) return rc;
+    if (max_steps < 0) return fail(ICP_ERR_INVALID, "max_steps < 0");
+    if (!b->begun) return fail(ICP_ERR_STATE, "icp_batch_begin first");
+    ScopedPin pin(b->ctx);
+    int k = 0;
+    while (k < max_steps && count_running(b) > 0) {
+        if (int rc = step(b)) {
+            // a device failure leaves the clouds in an unknown state: the loop is discarded
+            (void)hipStreamSynchronize(b->ctx->stream);
+            (void)hipGetLastError();
+            b->begun = false;
+            return rc;
+        }
+        ++k;
+    }
+    if (steps_done) *steps_done = k;
+    if (active) *active = count_running(b);
+    return ICP_OK;
+}
+
+int icp_batch_state(icp_batch* b, int pair, int* status, int* iterations, int* passes, double* err, int err_cap, double* T16)
+{
+    if (!b) return fail(ICP_ERR_INVALID, "null batch");
+    if (pair < 0 || pair >= b->count) return fail(ICP_ERR_INVALID, "pair out of range");
+    if (!b->begun) return fail(ICP_ERR_STATE, "no loop");
+    const icp::HostLoop& H = b->H[pair];
+    if (status) *status = b->status[pair];
+    if (iterations) *iterations = H.iterations;
+    if (passes) *passes = H.applied;
+    if (err) {
+        const int cnt = (int)H.err.size() < err_cap ? (int)H.err.size() : err_cap;
+        for (int i = 0; i < cnt; ++i) err[i] = H.err[i];
+    }
+    if (T16) std::memcpy(T16, H.T, sizeof H.T);
+    return ICP_OK;
+}
+
+int icp_batch_done(icp_batch* b, int32_t* done_out)
+{
+    if (!b || !done_out) return fail(ICP_ERR_INVALID, "null argument");
+    if (!b->begun) return fail(ICP_ERR_STATE, "no loop");
+    for (int p = 0; p < b->count; ++p) done_out[p] = running(b, p) ? 0 : 1;
+    return ICP_OK;
+}
+
+int icp_batch_get_moving(icp_batch* b, void* aos_out)
+{
+    if (int rc = ready(b)) return rc;
+    if (!aos_out) return fail(ICP_ERR_INVALID, "aos_out == NULL");
+    std::vector<char> raw(3 * (size_t)b->p_plane * b->esize);
+    HIP_TRY(hipMemcpyAsync(raw.data(), b->P.p, raw.size(), hipMemcpyDeviceToHost, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    if (b->prec == ICP_F64) from_planes<double>(raw, b, aos_out);
+    else from_planes<float>(raw, b, aos_out);
+    return ICP_OK;
+}
+
+int icp_batch_get_indices(icp_batch* b, int32_t* idx_out) { return download_indices(b, false, idx_out); }
+
+int icp_batch_loop_indices(icp_batch* b, int32_t* idx_out) { return download_indices(b, true, idx_out); }
+
+int icp_point_to_point_batch(icp_ctx* c, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
+                             const int64_t* model_off, const icp_params* prm, double* T16_out, int* iterations_out, int* passes_out,
+                             double* err_out, int32_t* idx_out, void* moved_out, int* status_out)
+{
+    if (!c) return fail(ICP_ERR_INVALID, "null context");
+    if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
+    if (prm->metric != ICP_POINT_TO_POINT) return fail(ICP_ERR_INVALID, "a batch runs point-to-point only");
+    if (prm->max_iter < 1) return fail(ICP_ERR_INVALID, "max_iter must be >= 1");
+    icp_batch* b = nullptr;
+    if (int rc = icp_batch_create(c, count, moving_aos, moving_off, model_aos, model_off, prm->precision, &b)) return rc;
+    ScopedPin pin(c);
+    int rc = icp_batch_begin(b, prm);
+    for (int active = 1; rc == ICP_OK && active > 0;) rc = icp_batch_run(b, 1 << 20, nullptr, &active);
+    const int cap = prm->max_iter + 1;
+    for (int p = 0; rc == ICP_OK && p < count; ++p)
+        rc = icp_batch_state(b, p, status_out ? status_out + p : nullptr, iterations_out ? iterations_out + p : nullptr,
+                             passes_out ? passes_out + p : nullptr, err_out ? err_out + (size_t)p * cap : nullptr, cap,
+                             T16_out ? T16_out + (size_t)p * 16 : nullptr);
+    if (rc == ICP_OK && idx_out) rc = icp_batch_loop_indices(b, idx_out);
+    if (rc == ICP_OK && moved_out) rc = icp_batch_get_moving(b, moved_out);
+    icp_batch_destroy(b);
+    return rc;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -847,4 +847,182 @@ hipError_t launch_dense_v2(const NNPlan& pl, const void* P, const void* Qscan, v
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// batched point-to-point (icp_batch.cpp): the pass of every running pair of a batch in one launch.
+//
+// grid = one block per work item: BATCH_ITEM moving points of one pair, cut from that pair's first point.  All four waves
+// hold the item's points (one per lane); wave w scans the w-th contiguous quarter of the pair's model through its own LDS
+// sub-tile (every lane reads the same address), keeping the running minimum and the first chunk that lowered it, as
+// nn_match_kernel does; the index is recovered inside that chunk, and the quarters are merged in ascending order with a
+// strict <: the lowest index wins ties, as in the reference's ascending scan.
+//   front end (pass >= 1): the pair's previous R, t by apply_rt -- every wave moves its copy of the points with the same
+//     instructions; wave 0 stores them and adds |p_new - q[idx_prev]|^2 in double (transform_error_kernel's arithmetic);
+//   tail: wave 0 stores idx, gathers q[idx] and forms moments_kernel's point-to-point terms in double; block_sum_store
+//     writes the item's row partials[item][0 .. ICP_MOM_SQQ] (error in slot ICP_MOM_ERR).
+// A pair's blocks, their geometry and every sum depend on that pair alone (no atomics): its bits do not depend on the batch.
+// ------------------------------------------------------------------------------------------------
+template <typename F> struct BatchCfg;
+template <> struct BatchCfg<float> { static constexpr int TW = 512; };    // model points per wave and tile: 6 KiB per wave
+template <> struct BatchCfg<double> { static constexpr int TW = 256; };
+static_assert(sizeof(RT<float>) == 12 * sizeof(float) && sizeof(RT<double>) == 12 * sizeof(double), "the host writes R, t as 12 values per pair");
+
+template <typename F>
+__global__ __launch_bounds__(NN_BLOCK) void nn_match_batch(const BatchItem* __restrict__ items, const BatchPair* __restrict__ pairs,
+                                                           const int* __restrict__ mode, const RT<F>* __restrict__ rts,
+                                                           F* __restrict__ P, long long p_plane, const F* __restrict__ Q, long long q_plane,
+                                                           const int32_t* __restrict__ idx_prev, int32_t* __restrict__ idx_cur,
+                                                           double* __restrict__ partials)
+{
+    using V = typename Vec16<F>::type;
+    constexpr int VN = Vec16<F>::N;
+    constexpr int TW = BatchCfg<F>::TW, C = NN_CHUNK;
+    constexpr int NACC = ICP_MOM_SQQ + 1;   // error, count, sum p, sum q, sum q p^T, |p|^2, |q|^2: the slots of the moment vector
+    static_assert(BATCH_ITEM == 64 && NN_BLOCK == 4 * BATCH_ITEM, "one point per lane, four waves per item");
+    __shared__ __attribute__((aligned(16))) F sq[4][3][TW];
+    __shared__ F md[4][BATCH_ITEM];
+    __shared__ int mi[4][BATCH_ITEM];
+
+    const BatchItem it = items[blockIdx.x];
+    const int pm = mode[it.pair];
+    if (pm == 0) return;   // the pair has ended (or takes no part in this pass): the whole block leaves
+    const BatchPair pr = pairs[it.pair];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool live = lane < it.count;
+    const long long gi = pr.p_off + it.first + (live ? lane : 0);   // (lanes past the item's end work on its first point: nothing of theirs is kept)
+    const F* Qx = Q + pr.q_off;
+    const F* Qy = Qx + q_plane;
+    const F* Qz = Qx + 2 * q_plane;
+
+    F x = P[gi], y = P[p_plane + gi], z = P[2 * p_plane + gi];
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    __syncthreads();   // every wave holds its points before wave 0 overwrites them
+
+    if (pm & BATCH_APPLY) {
+        apply_rt<F>(rts[it.pair], x, y, z, x, y, z);
+        if (w == 0 && live) {
+            P[gi] = x;
+            P[p_plane + gi] = y;
+            P[2 * p_plane + gi] = z;
+            const int j = idx_prev[gi];
+            const double dx = (double)Qx[j] - (double)x;
+            const double dy = (double)Qy[j] - (double)y;
+            const double dz = (double)Qz[j] - (double)z;
+            acc[ICP_MOM_ERR] = dx * dx + dy * dy + dz * dz;
+        }
+    }
+
+    if (pm & BATCH_MATCH) {
+        const int m = pr.m;
+        const int wseg = ((m + 3) / 4 + C - 1) / C * C;   // model points per wave, whole chunks
+        const int my0 = w * wseg, my1 = min(my0 + wseg, m);  // may be empty (my1 <= my0)
+        const int ntile = (wseg + TW - 1) / TW;           // the same for every wave: the barriers pair up
+        F best = inf_<F>();
+        int cst = -1;   // first model index of the chunk that last lowered `best`
+        for (int k = 0; k < ntile; ++k) {
+            const int t0 = my0 + k * TW;
+            __syncthreads();
+            // this wave's sub-tile; places past the quarter's end hold +inf, which never lowers a minimum
+            for (int e = lane; e < TW; e += 64) {
+                const int j = t0 + e;
+                F qx = inf_<F>(), qy = inf_<F>(), qz = inf_<F>();
+                if (j < my1) { qx = Qx[j]; qy = Qy[j]; qz = Qz[j]; }
+                sq[w][0][e] = qx;
+                sq[w][1][e] = qy;
+                sq[w][2][e] = qz;
+            }
+            __syncthreads();
+            const int len = min(TW, my1 - t0);   // <= 0: this wave's quarter is exhausted
+            for (int c = 0; c < len; c += C) {
+                const F bo = best;
+#pragma unroll
+                for (int kk = 0; kk < C; kk += VN) {
+                    const V qx = *reinterpret_cast<const V*>(&sq[w][0][c + kk]);
+                    const V qy = *reinterpret_cast<const V*>(&sq[w][1][c + kk]);
+                    const V qz = *reinterpret_cast<const V*>(&sq[w][2][c + kk]);
+#pragma unroll
+                    for (int v = 0; v < VN; ++v) best = fmin_(best, dist2<F>(x, y, z, vget(qx, v), vget(qy, v), vget(qz, v)));
+                }
+                cst = (best < bo) ? t0 + c : cst;
+            }
+        }
+        // the lowest j of the winning chunk with d_j == min (global memory, L2-resident)
+        int bi = 0x7fffffff;
+        if (cst >= 0) {
+            bi = cst;
+            for (int kk = C - 1; kk >= 0; --kk) {
+                const int j = cst + kk;
+                if (j < my1) {
+                    const F d = dist2<F>(x, y, z, Qx[j], Qy[j], Qz[j]);
+                    bi = (d == best) ? j : bi;
+                }
+            }
+        }
+        md[w][lane] = cst >= 0 ? best : inf_<F>();
+        mi[w][lane] = bi;
+        __syncthreads();
+        if (w == 0 && live) {
+            F b = md[0][lane];
+            int j = mi[0][lane];
+#pragma unroll
+            for (int ww = 1; ww < 4; ++ww)
+                if (md[ww][lane] < b) { b = md[ww][lane]; j = mi[ww][lane]; }
+            j = ((unsigned)j < (unsigned)m) ? j : 0;   // (nothing found only if every distance overflowed: idx stays in range)
+            idx_cur[gi] = j;
+            const double px = (double)x, py = (double)y, pz = (double)z;
+            const double qx = (double)Qx[j], qy = (double)Qy[j], qz = (double)Qz[j];
+            acc[ICP_MOM_CNT] = 1.0;
+            acc[ICP_MOM_SP + 0] = px; acc[ICP_MOM_SP + 1] = py; acc[ICP_MOM_SP + 2] = pz;
+            acc[ICP_MOM_SQ + 0] = qx; acc[ICP_MOM_SQ + 1] = qy; acc[ICP_MOM_SQ + 2] = qz;
+            acc[ICP_MOM_SQP + 0] = qx * px; acc[ICP_MOM_SQP + 1] = qx * py; acc[ICP_MOM_SQP + 2] = qx * pz;
+            acc[ICP_MOM_SQP + 3] = qy * px; acc[ICP_MOM_SQP + 4] = qy * py; acc[ICP_MOM_SQP + 5] = qy * pz;
+            acc[ICP_MOM_SQP + 6] = qz * px; acc[ICP_MOM_SQP + 7] = qz * py; acc[ICP_MOM_SQP + 8] = qz * pz;
+            acc[ICP_MOM_SPP] = px * px + py * py + pz * pz;
+            acc[ICP_MOM_SQQ] = qx * qx + qy * qy + qz * qz;
+        }
+    }
+    // (waves 1-3 add zeros: the row is wave 0's 64 lanes, summed in lane order)
+    block_sum_store<NACC, NN_BLOCK>(acc, partials + (size_t)blockIdx.x * ICP_NMOM);
+}
+
+// one block per pair: mom[pair] = the pair's item rows added up in a fixed order (thread (k, part) adds items part, part + 8, ...
+// of slot k; the eight part sums are then added in part order -- finalize_kernel's scheme, over the pair's own items only)
+__global__ __launch_bounds__(256) void batch_finalize_kernel(const BatchPair* __restrict__ pairs, const int* __restrict__ mode,
+                                                             const double* __restrict__ partials, double* __restrict__ mom)
+{
+    __shared__ double red[8][ICP_NMOM];
+    if (mode[blockIdx.x] == 0) return;
+    const int k = threadIdx.x & 31, part = threadIdx.x >> 5;
+    const int i0 = pairs[blockIdx.x].item0, i1 = pairs[blockIdx.x].item1;
+    double s = 0.0;
+    if (k <= ICP_MOM_SQQ)
+        for (int i = i0 + part; i < i1; i += 8) s += partials[(size_t)i * ICP_NMOM + k];
+    red[part][k] = s;
+    __syncthreads();
+    if (threadIdx.x < ICP_NMOM) {
+        double tot = red[0][k];
+#pragma unroll
+        for (int p = 1; p < 8; ++p) tot += red[p][k];
+        mom[(size_t)blockIdx.x * ICP_NMOM + k] = tot;
+    }
+}
+
+hipError_t launch_batch_pass(int precision, const BatchItem* items, int n_items, const BatchPair* pairs, int n_pairs, const int* mode,
+                             const void* rt, void* P, long long p_plane, const void* Q, long long q_plane, const int32_t* idx_prev,
+                             int32_t* idx_cur, double* partials, double* mom, hipStream_t st)
+{
+    if (n_items <= 0 || n_pairs <= 0) return hipSuccess;
+    if (precision == ICP_F64)
+        hipLaunchKernelGGL((nn_match_batch<double>), dim3(n_items), dim3(NN_BLOCK), 0, st, items, pairs, mode, (const RT<double>*)rt,
+                           (double*)P, p_plane, (const double*)Q, q_plane, idx_prev, idx_cur, partials);
+    else
+        hipLaunchKernelGGL((nn_match_batch<float>), dim3(n_items), dim3(NN_BLOCK), 0, st, items, pairs, mode, (const RT<float>*)rt,
+                           (float*)P, p_plane, (const float*)Q, q_plane, idx_prev, idx_cur, partials);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(batch_finalize_kernel, dim3(n_pairs), dim3(256), 0, st, pairs, mode, (const double*)partials, mom);
+    return hipGetLastError();
+}
+
 }  // namespace icp

@@ -365,6 +365,21 @@ hipError_t launch_transform_error(int precision, void* P_soa, int n, int n_pad, 
 hipError_t launch_finalize(double* mom_out, const double* mom_partials, int mom_blocks, const double* err_partials,
                            int err_blocks, int rows_have_err /* slot 0 of the rows carries error shares */, hipStream_t st, double* scratch = nullptr /* >= 256 x ICP_NMOM doubles: many rows are added in two stages */);
 
+// batched point-to-point (icp_batch_*, icp_batch.cpp).  Every cloud of a batch starts at a multiple of BATCH_ALIGN elements in
+// its SoA plane (x at [off], y at [plane + off], z at [2 * plane + off]); the moving clouds' matches use the same offsets.
+// One work item = BATCH_ITEM moving points of one pair, cut from that pair's first point: one block of NN_BLOCK threads,
+// the four waves scanning four contiguous quarters of the pair's model for the same points.
+constexpr int BATCH_ITEM = 64;
+constexpr int BATCH_ALIGN = 64;
+constexpr int BATCH_APPLY = 1, BATCH_MATCH = 2;   // per-pair mode bits of one pass (0: the pair is not part of it)
+struct BatchItem { int pair, first, count, pad_; };
+struct BatchPair { long long p_off, q_off; int n, m, item0, item1; };   // items [item0, item1) belong to the pair, in point order
+// pass over every item whose pair's mode is non-zero: [apply rt[pair] + error against idx_prev] -> [match -> idx_cur, moments]
+// -> partials[item][0..ICP_MOM_SQQ]; then mom[pair][ICP_NMOM] = that pair's items added in item order (pairs of mode 0 untouched)
+hipError_t launch_batch_pass(int precision, const BatchItem* items, int n_items, const BatchPair* pairs, int n_pairs, const int* mode,
+                             const void* rt /* RT<F>[n_pairs] */, void* P_soa, long long p_plane, const void* Q_soa, long long q_plane,
+                             const int32_t* idx_prev, int32_t* idx_cur, double* partials, double* mom, hipStream_t st);
+
 // soa2 (optional): a second copy of the result (the pristine moving cloud); enc (optional, fp32): the cloud's bounding cube as six
 // ordered-integer words {~ord(min xyz), ord(max xyz)}, zero before the launch
 hipError_t launch_aos_to_soa(int precision, const void* aos, int n, int n_pad, void* soa, hipStream_t st, unsigned int* nonfinite = nullptr, void* soa2 = nullptr,

@@ -245,6 +245,33 @@ class Context:
     def point_to_plane(self, D, M, normals=None, max_iter=50, tol=1e-6, fixed_iterations=False):
         return self._run(capi.ICP_POINT_TO_PLANE, D, M, normals, max_iter, tol, fixed_iterations)
 
+    # ---- batched point-to-point (icp_batch_*): many independent pairs, one launch per step ------------
+    def batch(self, pairs):
+        """a Batch of (D, M) pairs of one dtype, uploaded once (see Batch)"""
+        return Batch(self, pairs)
+
+    def point_to_point_batch(self, pairs, max_iter=40, tol=1e-6, fixed_iterations=False):
+        """point_to_point for every (D, M) of `pairs` (one dtype) in one batched registration; a list of Result in pair order,
+        each exactly what point_to_point gives for that pair alone (extra["status"]: ICP_OK or the code that ended its loop)"""
+        Ds, Ms, moff, qoff, dtype = _batch_arrays(pairs)
+        count, cap = len(Ds), int(max_iter) + 1
+        prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(dtype), capi.ICP_POINT_TO_POINT)
+        T = np.zeros((count, 16))
+        it, ps, st = (np.zeros(count, dtype=np.int32) for _ in range(3))
+        err = np.zeros((count, cap))
+        idx = np.zeros(int(moff[-1]), dtype=np.int32)
+        moved = np.zeros((int(moff[-1]), 3), dtype=dtype)
+        D, M = np.concatenate(Ds), np.concatenate(Ms)
+        pi, pd, p64 = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        rc = self._lib.icp_point_to_point_batch(self._h, count, D.ctypes.data, moff.ctypes.data_as(p64), M.ctypes.data, qoff.ctypes.data_as(p64),
+                                                C.byref(prm), T.ctypes.data_as(pd), it.ctypes.data_as(pi), ps.ctypes.data_as(pi),
+                                                err.ctypes.data_as(pd), idx.ctypes.data_as(C.POINTER(C.c_int32)), moved.ctypes.data,
+                                                st.ctypes.data_as(pi))
+        capi.check(rc, "icp_point_to_point_batch")
+        return [Result(T=T[b].reshape(4, 4).copy(), iterations=int(it[b]), passes=int(ps[b]), err=err[b, : ps[b] + 1].copy(),
+                       idx=idx[moff[b]:moff[b + 1]].copy(), moved=moved[moff[b]:moff[b + 1]].copy(), extra={"status": int(st[b])})
+                for b in range(count)]
+
     # ---- step-wise loop (multi-GPU driver, per-iteration parity tests) -------------------------
     def loop_begin(self, metric=capi.ICP_POINT_TO_POINT, max_iter=40, tol=1e-6, fixed_iterations=False):
         prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(self._dtype), metric)
@@ -330,6 +357,102 @@ class Context:
         capi.check(self._lib.icp_os1_packets_to_cartesian(self._h, pk.ctypes.data, npk, alt.ctypes.data_as(pf), az.ctypes.data_as(pf),
                                                           xyz.ctypes.data, rng.ctypes.data), "icp_os1_packets_to_cartesian")
         return xyz, rng
+
+
+def _batch_arrays(pairs):
+    """(D, M) pairs -> the clouds as contiguous arrays of one dtype and the int64 offsets of their concatenation"""
+    pairs = list(pairs)
+    if not pairs:
+        raise ValueError("a batch needs at least one pair")
+    dtype = _as_cloud(pairs[0][0]).dtype
+    Ds = [_as_cloud(D, dtype) for D, _ in pairs]
+    Ms = [_as_cloud(M, dtype) for _, M in pairs]
+    moff = np.concatenate([[0], np.cumsum([D.shape[0] for D in Ds])]).astype(np.int64)
+    qoff = np.concatenate([[0], np.cumsum([M.shape[0] for M in Ms])]).astype(np.int64)
+    return Ds, Ms, moff, qoff, dtype
+
+
+class Batch:
+    """icp_batch: (D, M) pairs of one dtype resident on the context's device; every step runs the pass of every pair still
+    running in one launch.  Each pair's loop is the one Context.point_to_point runs for it alone.  Outputs are split per pair."""
+
+    def __init__(self, ctx, pairs):
+        self._ctx = ctx   # (keeps the context alive: a batch must go before it)
+        self._lib = ctx._lib
+        Ds, Ms, self._moff, qoff, self._dtype = _batch_arrays(pairs)
+        self.count = len(Ds)
+        D, M = np.concatenate(Ds), np.concatenate(Ms)
+        h = C.c_void_p()
+        p64 = C.POINTER(C.c_int64)
+        capi.check(self._lib.icp_batch_create(ctx._h, self.count, D.ctypes.data, self._moff.ctypes.data_as(p64), M.ctypes.data,
+                                              qoff.ctypes.data_as(p64), _prec(self._dtype), C.byref(h)), "icp_batch_create")
+        self._h = h
+        self._max_iter = 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.icp_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _split(self, flat):
+        return [flat[self._moff[b]:self._moff[b + 1]].copy() for b in range(self.count)]
+
+    def begin(self, max_iter=40, tol=1e-6, fixed_iterations=False):
+        """start every pair's registration from the uploaded clouds"""
+        prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(self._dtype), capi.ICP_POINT_TO_POINT)
+        capi.check(self._lib.icp_batch_begin(self._h, C.byref(prm)), "icp_batch_begin")
+        self._max_iter = int(max_iter)
+
+    def run(self, steps):
+        """up to `steps` passes of every running pair; returns (steps_done, pairs still running)"""
+        k, a = C.c_int(0), C.c_int(0)
+        capi.check(self._lib.icp_batch_run(self._h, int(steps), C.byref(k), C.byref(a)), "icp_batch_run")
+        return k.value, a.value
+
+    def state(self, b):
+        st, it, ps = C.c_int(0), C.c_int(0), C.c_int(0)
+        err = np.zeros(self._max_iter + 1)
+        T = np.zeros(16)
+        pd = C.POINTER(C.c_double)
+        capi.check(self._lib.icp_batch_state(self._h, int(b), C.byref(st), C.byref(it), C.byref(ps), err.ctypes.data_as(pd), err.size,
+                                             T.ctypes.data_as(pd)), "icp_batch_state")
+        return dict(status=st.value, iterations=it.value, passes=ps.value, err=err[: ps.value + 1].copy(), T=T.reshape(4, 4))
+
+    def done(self):
+        """(count,) bool: the pairs whose loop has ended"""
+        out = np.zeros(self.count, dtype=np.int32)
+        capi.check(self._lib.icp_batch_done(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))), "icp_batch_done")
+        return out.astype(bool)
+
+    def get_moving(self):
+        out = np.empty((int(self._moff[-1]), 3), dtype=self._dtype)
+        capi.check(self._lib.icp_batch_get_moving(self._h, out.ctypes.data), "icp_batch_get_moving")
+        return self._split(out)
+
+    def _indices(self, fn, where):
+        out = np.empty(int(self._moff[-1]), dtype=np.int32)
+        capi.check(fn(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))), where)
+        return self._split(out)
+
+    def get_indices(self):
+        """each pair's matches of its most recent matching pass"""
+        return self._indices(self._lib.icp_batch_get_indices, "icp_batch_get_indices")
+
+    def loop_indices(self):
+        """each pair's matches of the last pass that contributed to its T"""
+        return self._indices(self._lib.icp_batch_loop_indices, "icp_batch_loop_indices")
 
 
 # ---- host-only helpers (no device) -------------------------------------------------------------

@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-#define ICP_ABI_VERSION 2 /* 2: icp_result gained seconds_host / seconds_setup, icp_loop_phase_seconds */
+#define ICP_ABI_VERSION 2 /* 2: icp_result gained seconds_host / seconds_setup, icp_loop_phase_seconds; later the icp_batch_* entry
+                           * points were added (new symbols only: nothing that existed changed) */
 
 /* return codes */
 #define ICP_OK 0
@@ -201,6 +202,46 @@ int icp_loop_timing_passes(icp_ctx* ctx, long long* passes);
 int icp_loop_phase_seconds(icp_ctx* ctx, double* seconds_nn, double* seconds_host);
 /* correspondences of the last pass that contributed to T (ping-pong buffer), n int32 */
 int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
+
+/* ---- batched point-to-point: many independent small pairs, one launch of every pair's pass per step ----------------
+ * The reference registers one pair per program run (src/ICP_point_to_point.cu:295-423); a loop of icp_point_to_point over
+ * many small pairs pays a whole iteration's launch and round trip per pair.  A batch keeps all its pairs on the device and
+ * runs ONE matching launch + ONE reduction launch + ONE 32-double-per-pair download per step for every pair still running.
+ *   - pair b = moving points [moving_off[b], moving_off[b+1]) and model points [model_off[b], model_off[b+1]) of the
+ *     concatenated AoS arrays, element type = precision (as icp_set_model).  Offsets: count+1 int64, starting at 0, strictly
+ *     increasing (every cloud >= 1 point, <= ICP_BATCH_MAX_POINTS).  Anything else, a NaN or an infinite coordinate
+ *     anywhere, count < 1 or a metric other than ICP_POINT_TO_POINT is refused with ICP_ERR_INVALID, and no batch is made.
+ *   - each pair's loop is exactly what icp_point_to_point computes for that pair alone (same stop rule, iterations, passes,
+ *     err series, composed T, idx of the last contributing pass, final cloud), and a pair's bits do not depend on the other
+ *     pairs of the batch or their order: work is cut relative to each pair's first point, partial sums are added per pair
+ *     in a fixed order, there are no floating-point atomics.  Pairs finish independently; a numeric failure of one pair's
+ *     minimisation ends that pair only (its status), the others go on.
+ *   - a batch uses the context's device and stream and nothing else of it (resident clouds, loop, counters stay as they
+ *     were).  It must be destroyed before its context.  While the context has an enqueued pass that is not completed
+ *     (icp_loop_enqueue without icp_loop_complete) the batch calls return ICP_ERR_STATE.
+ *   - icp_batch_begin starts every pair's registration from the clouds icp_batch_create uploaded. */
+typedef struct icp_batch icp_batch;
+#define ICP_BATCH_MAX_POINTS 65536 /* per cloud of one pair */
+int icp_batch_create(icp_ctx* ctx, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
+                     const int64_t* model_off, int precision, icp_batch** out);
+void icp_batch_destroy(icp_batch* b);
+int icp_batch_begin(icp_batch* b, const icp_params* prm); /* prm->metric must be ICP_POINT_TO_POINT, prm->precision the batch's */
+/* up to max_steps passes for every pair still running; *active (optional) = pairs not yet done */
+int icp_batch_run(icp_batch* b, int max_steps, int* steps_done, int* active);
+/* per pair: status = ICP_OK or the rc that ended this pair's loop; the rest as icp_loop_state */
+int icp_batch_state(icp_batch* b, int pair, int* status, int* iterations, int* passes, double* err, int err_cap, double* T16);
+/* count int32: 1 where that pair's loop has ended (stop rule, max_iter, or a failed minimisation), else 0 */
+int icp_batch_done(icp_batch* b, int32_t* done_out);
+int icp_batch_get_moving(icp_batch* b, void* aos_out);      /* all pairs, concatenated as uploaded, as icp_get_moving */
+int icp_batch_get_indices(icp_batch* b, int32_t* idx_out);  /* each pair's most recent matching pass, as icp_get_indices */
+int icp_batch_loop_indices(icp_batch* b, int32_t* idx_out); /* each pair's last contributing pass, as icp_loop_indices */
+/* one call: create + begin + run to the end + results, then destroy.  Every output pointer may be NULL; per pair:
+ * T16_out 16, iterations_out / passes_out / status_out 1, err_out max_iter+1 doubles; idx_out and moved_out (3 values per
+ * point, precision of the run) concatenated as the moving clouds.  A failed pair is reported in status_out, not in the
+ * return code. */
+int icp_point_to_point_batch(icp_ctx* ctx, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
+                             const int64_t* model_off, const icp_params* prm, double* T16_out, int* iterations_out,
+                             int* passes_out, double* err_out, int32_t* idx_out, void* moved_out, int* status_out);
 
 /* ---- multi-GPU: the loop's single collective issued by the library (RCCL over xGMI, bound at run time) ----
  * One process per GPU.  Rank 0 obtains an id (icp_comm_unique_id), the host application distributes those

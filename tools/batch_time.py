@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Pair-iterations per second of the batched point-to-point loop (Context.point_to_point_batch, one launch per step for all
+pairs) against a loop of Context.point_to_point over the same pairs (GPU box).
+
+  python3 tools/batch_time.py [--reps 5] [--out FILE]
+
+Cases: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids (make_model_gpu, tol 1e-6);
+16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  Both sides are timed end to end (upload included) with a host clock
+around calls that end in a device synchronisation; a pair-iteration is one matching pass of one pair (Result.passes).  The
+sequential side also reports its loops alone (Result.seconds_total, the registration without the upload).  Median of --reps
+after one warm-up of every case.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def cases(pkg, orc):
+    ds = pkg.datasets
+    D64, M64 = orc.synth_icp_cpu(32)
+    G = ds.synthetic_grid(32, np.float32)
+    Gm = ds.make_model_gpu(G, *ds.P2P_GPU)
+    B = np.fromfile(os.path.join(ROOT, "tests", "golden", "bunny_res_xyz_f32.bin"), dtype=np.float32).reshape(-1, 3)
+    rng = np.random.default_rng(5)
+    bunny = [(B, ds.make_model_gpu(B, tuple(np.asarray(ds.BUNNY[0]) + rng.uniform(-0.05, 0.05, 3)), ds.BUNNY[1])) for _ in range(16)]
+    return [
+        ("configs0_fp64_x64", [(D64, M64)] * 64, 200, 1e-5),
+        ("configs0_fp64_x256", [(D64, M64)] * 256, 200, 1e-5),
+        ("grid1024_fp32_x64", [(G, Gm)] * 64, 40, 1e-6),
+        ("bunny_res_fp32_x16", bunny, 100, 1e-6),
+    ]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--profile-case", default="", help="run only this case's batched registration, once after a warm-up (for a kernel trace)")
+    a = ap.parse_args()
+    import torch  # noqa: F401  (torch first: it bundles the HIP runtime)
+    from __graft_entry__ import load_package
+    import oracle_lib
+    pkg = load_package()
+    orc = oracle_lib.Oracle()
+    rows = []
+    with pkg.Context(0) as ctx:
+        for name, pairs, it, tol in cases(pkg, orc):
+            if a.profile_case:
+                if name == a.profile_case:
+                    for _ in range(2):
+                        res = ctx.point_to_point_batch(pairs, max_iter=it, tol=tol)
+                    print(json.dumps(dict(case=name, pairs=len(pairs), pair_iterations=sum(r.passes for r in res),
+                                          steps=max(r.passes for r in res) + 1)), flush=True)
+                continue
+
+            def batched():
+                t0 = time.perf_counter()
+                res = ctx.point_to_point_batch(pairs, max_iter=it, tol=tol)
+                return time.perf_counter() - t0, sum(r.passes for r in res), None
+
+            def sequential():
+                t0 = time.perf_counter()
+                res = [ctx.point_to_point(D, M, max_iter=it, tol=tol) for D, M in pairs]
+                return time.perf_counter() - t0, sum(r.passes for r in res), sum(r.seconds_total for r in res)
+
+            batched()
+            sequential()
+            tb, ts, tl = [], [], []
+            for _ in range(a.reps):   # alternated, so that both see the same box
+                s, pb, _ = batched()
+                tb.append(s)
+                s, ps, loops = sequential()
+                ts.append(s)
+                tl.append(loops)
+            assert pb == ps, (name, pb, ps)   # the same registrations
+            mb, ms, ml = float(np.median(tb)), float(np.median(ts)), float(np.median(tl))
+            row = dict(case=name, pairs=len(pairs), points=int(pairs[0][0].shape[0]), pair_iterations=pb,
+                       batched_s=mb, sequential_s=ms, sequential_loops_s=ml,
+                       batched_pair_it_per_s=pb / mb, sequential_pair_it_per_s=pb / ms,
+                       batched_us_per_pair_it=1e6 * mb / pb, sequential_us_per_pair_it=1e6 * ms / pb,
+                       sequential_loops_us_per_pair_it=1e6 * ml / pb, speedup=ms / mb, speedup_vs_loops=ml / mb)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
