@@ -24,6 +24,9 @@ ICP_F32, ICP_F64 = 0, 1
 ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1
 ICP_NMOM = 32
 ICP_BATCH_MAX_POINTS = 65536   # per cloud of one pair of a batch
+# icp_diag_loop_moments: how the vector came about (include/icp_mi355x_diag.h)
+ROUTE_HOST_ROWS, ROUTE_COMPACT, ROUTE_AVX, ROUTE_FIN_LAUNCH, ROUTE_FIN_PINNED, ROUTE_FIN_KERNEL = 0x001, 0x002, 0x004, 0x008, 0x010, 0x020
+ROUTE_FIN_TWO_STAGE, ROUTE_FUSED_TAIL, ROUTE_MOMENTS_KERNEL, ROUTE_ERROR_ONLY, ROUTE_ARMED, ROUTE_RESIDENT = 0x040, 0x080, 0x100, 0x200, 0x400, 0x800
 MOM_ERR, MOM_CNT, MOM_SP, MOM_SQ, MOM_SQP, MOM_SPP, MOM_SQQ, MOM_C, MOM_B = 0, 1, 2, 5, 8, 17, 18, 2, 23
 
 
@@ -113,6 +116,8 @@ SIGNATURES = {
     "icp_shard_range": (_i, [C.c_int64, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "icp_share_rows_plan": (_i, [_pu32, _i, _i, _i, _i, _pi32, _pu32]),
     "icp_diag_row_roles": (_i, [_vp, _pu32, _i, _i, _i, _i, _pi32]),
+    "icp_diag_loop_moments": (_i, [_vp, _pd, _pi]),
+    "icp_diag_batch_moments": (_i, [_vp, _i, _pd]),
     "icp_eigh3": (_i, [_pd, _pd, _pd]),
     "icp_synthetic_grid_f32": (_i, [_i, C.c_float, C.c_float, _vp]),
     "icp_synthetic_grid_f64": (_i, [_i, C.c_double, C.c_double, _vp]),

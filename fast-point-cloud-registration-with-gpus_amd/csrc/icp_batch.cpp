@@ -16,6 +16,7 @@
 #include <new>
 #include <vector>
 
+#include "../../include/icp_mi355x_diag.h"
 #include "icp_ctx.h"
 
 struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header only names it, as icp_ctx)
@@ -37,6 +38,7 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     std::vector<int> status;                 // ICP_OK, or the rc that ended the pair's loop
     std::vector<int> last_match;             // idx buffer of the pair's most recent matching pass
     std::vector<int> applied_buf;            // idx buffer of the pass whose motion the pair applied last
+    std::vector<char> mom_seen;              // the pair's HostLoop has advanced on its row of h_mom since icp_batch_begin
 };
 
 namespace {
@@ -200,6 +202,7 @@ int step(icp_batch* b)
     b->steps += 1;
     for (int p = 0; p < b->count; ++p) {
         if (mode[p] == 0) continue;
+        b->mom_seen[p] = 1;   // (a pair that takes no part in a later step keeps this row: batch_finalize_kernel skips it)
         const int rc = b->H[p].advance(b->h_mom + (size_t)p * ICP_NMOM);
         if (rc != ICP_OK) {   // a numeric failure ends this pair only; what its completed passes produced stays readable
             b->status[p] = rc;
@@ -281,6 +284,7 @@ int icp_batch_create(icp_ctx* c, int count, const void* moving_aos, const int64_
     b->status.assign((size_t)count, ICP_OK);
     b->last_match.assign((size_t)count, 0);
     b->applied_buf.assign((size_t)count, 0);
+    b->mom_seen.assign((size_t)count, 0);
     if (int rc = upload(b, moving_aos, moving_off, model_aos, model_off)) {
         (void)hipStreamSynchronize(c->stream);
         release(b);
@@ -310,6 +314,7 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
     b->status.assign((size_t)b->count, ICP_OK);
     b->last_match.assign((size_t)b->count, 0);
     b->applied_buf.assign((size_t)b->count, 0);
+    b->mom_seen.assign((size_t)b->count, 0);
     HIP_TRY(hipMemcpyAsync(b->P.p, b->P0.p, 3 * (size_t)b->p_plane * b->esize, hipMemcpyDeviceToDevice, b->ctx->stream));
     b->steps = 0;
     b->begun = true;
@@ -352,6 +357,15 @@ int icp_batch_state(icp_batch* b, int pair, int* status, int* iterations, int* p
         for (int i = 0; i < cnt; ++i) err[i] = H.err[i];
     }
     if (T16) std::memcpy(T16, H.T, sizeof H.T);
+    return ICP_OK;
+}
+
+int icp_diag_batch_moments(icp_batch* b, int pair, double* out32)
+{
+    if (!b || !out32) return fail(ICP_ERR_INVALID, "null argument");
+    if (pair < 0 || pair >= b->count) return fail(ICP_ERR_INVALID, "pair out of range");
+    if (!b->begun || !b->mom_seen[pair] || !b->h_mom) return fail(ICP_ERR_STATE, "no completed pass of this pair");
+    std::memcpy(out32, b->h_mom + (size_t)pair * ICP_NMOM, ICP_NMOM * sizeof(double));
     return ICP_OK;
 }
 

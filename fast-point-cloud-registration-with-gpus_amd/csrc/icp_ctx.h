@@ -95,6 +95,8 @@ struct LoopState {
     icp::NNMailbox* live_mailbox = nullptr;             // a resident kernel is running and listens here
     bool from_pristine = false;  // the loop started from the cloud icp_set_moving uploaded: it can be run again from the copy
     long long steps = 0;         // completed (enqueue + complete) steps of this loop
+    int route = 0;               // ICP_ROUTE_* bits of the pending (then: last completed) pass -- icp_diag_loop_moments
+    bool mom_valid = false;      // c->h_mom holds the vector HostLoop::advance last received in this loop
 };
 
 // the calling thread's affinity, narrowed to the device's NUMA node for the duration of one entry point (see icp_create)

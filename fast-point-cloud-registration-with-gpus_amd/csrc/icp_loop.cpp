@@ -18,6 +18,7 @@
 #include <cstring>
 #include <unistd.h>
 
+#include "../../include/icp_mi355x_diag.h"
 #include "icp_comm.h"
 #include "icp_ctx.h"
 
@@ -263,8 +264,9 @@ icp::NNTailArgs tail_args(const icp_ctx* c, const icp::NNPlan& pl, int32_t* idx_
 // waits for: how many rows, in which format, who adds them up, and under which tag.  slot_written: it leaves its points and
 // matches in slot order, in the other plane of the slot-order points (the next such launch starts from them).
 void set_pending(LoopState& L, int mom_blocks, int err_blocks, bool compact, bool host_reduce, bool final_poll, bool timed, double tag,
-                 bool slot_written)
+                 bool slot_written, int route)
 {
+    L.route = route | (host_reduce ? ICP_ROUTE_HOST_ROWS : 0) | (compact ? ICP_ROUTE_COMPACT : 0);
     L.mom_blocks = mom_blocks;
     L.err_blocks = err_blocks;
     L.rows_compact = compact;
@@ -409,7 +411,8 @@ int wait_host_rows(icp_ctx* c, bool tracing)
 
 // The pending pass's rows (and error rows) added up into c->h_mom, rows in block order: every slot is the same sum whichever
 // adder runs (ICP_MAILBOX=plain keeps the scalar loop: the same bits, for the A/B).
-void sum_host_rows(icp_ctx* c)
+// Returns ICP_ROUTE_AVX when a wide adder ran, else 0.
+int sum_host_rows(icp_ctx* c)
 {
     const LoopState& L = c->loop;
     const bool compact = L.rows_compact;
@@ -418,7 +421,7 @@ void sum_host_rows(icp_ctx* c)
     for (int b = 0; b < L.err_blocks; ++b) mom[ICP_MOM_ERR] += c->h_err_partials[b];
     // (a compact row does not carry its point count: a row of the sparse kernels holds the real points of its slots)
     if (compact) mom[ICP_MOM_CNT] = (double)c->n;
-    if (L.mom_blocks == 0) return;
+    if (L.mom_blocks == 0) return 0;
 #if defined(__x86_64__)
     static const bool have_avx = __builtin_cpu_supports("avx");
     static_assert(icp::NN_CROW == 16 && ICP_NMOM == 32, "the AVX adders take rows of sixteen and of 32 doubles");
@@ -427,13 +430,13 @@ void sum_host_rows(icp_ctx* c)
         add_compact_rows_avx(c->h_mom_partials, L.mom_blocks, kTagMask, sum);
         mom[ICP_MOM_ERR] += sum[0];
         for (int k = 1; k < icp::NN_CROW; ++k) mom[ICP_MOM_SP - 1 + k] += sum[k];
-        return;
+        return ICP_ROUTE_AVX;
     }
     if (have_avx && c->mail_wide) {
         double sum[32];
         add_full_rows_avx(c->h_mom_partials, L.mom_blocks, sum);
         for (int k = 0; k < ICP_NMOM - 1; ++k) mom[k] += sum[k];
-        return;
+        return ICP_ROUTE_AVX;
     }
 #endif
     for (int b = 0; b < L.mom_blocks; ++b) {
@@ -454,6 +457,7 @@ void sum_host_rows(icp_ctx* c)
             for (int k = 0; k < ICP_NMOM - 1; ++k) mom[k] += row[k];  // the last slot is the completion tag
         }
     }
+    return 0;
 }
 
 // the launch itself added its rows up and leaves the vector in pinned memory, the pass's tag in its last slot
@@ -561,8 +565,11 @@ int loop_enqueue_body(icp_ctx* c)
         }
     }
     const bool fin = ta.fin_tickets != nullptr;   // this pass's rows are added up inside its launch
+    int route = final_only ? ICP_ROUTE_ERROR_ONLY : tail ? ICP_ROUTE_FUSED_TAIL : ICP_ROUTE_MOMENTS_KERNEL;
+    if (fin) route |= ICP_ROUTE_FIN_LAUNCH | (fin_to_host(c) ? ICP_ROUTE_FIN_PINNED : 0);
     if (!host_reduce) {
         if (!fin) {
+            route |= ICP_ROUTE_FIN_KERNEL | (mom_blocks > 2048 ? ICP_ROUTE_FIN_TWO_STAGE : 0);
             if (mom_blocks > 2048) HIP_TRY(c->fin_scratch.ensure(256 * ICP_NMOM * sizeof(double)));
             HIP_TRY(icp::launch_finalize(c->mom_dev, (const double*)c->mom_partials.p, mom_blocks,
                                          (const double*)c->err_partials.p, err_blocks, tail ? 1 : 0, c->stream, (double*)c->fin_scratch.p));
@@ -572,7 +579,7 @@ int loop_enqueue_body(icp_ctx* c)
             if (int rc = icp::comm_allreduce_sum_f64(c->comm, c->mom_dev, ICP_NMOM, c->stream, err)) return fail(rc, err);
         }
     }
-    set_pending(L, mom_blocks, err_blocks, ta.compact != 0, host_reduce, fin && fin_to_host(c), timed, (double)c->tag_seq, slots);
+    set_pending(L, mom_blocks, err_blocks, ta.compact != 0, host_reduce, fin && fin_to_host(c), timed, (double)c->tag_seq, slots, route);
     if (c->trace) c->tr_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
     return ICP_OK;
 }
@@ -588,7 +595,7 @@ int loop_complete_body(icp_ctx* c, int* done)
     const auto tr0 = tracing ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point{};
     if (int rc = L.host_reduce ? wait_host_rows(c, tracing) : L.final_poll ? wait_final_vector(c) : copy_back(c)) return rc;
     const auto tr1 = tracing ? std::chrono::steady_clock::now() : tr0;
-    if (L.host_reduce) sum_host_rows(c);
+    if (L.host_reduce) L.route |= sum_host_rows(c);
     const auto tr2 = tracing ? std::chrono::steady_clock::now() : tr1;
     L.pending = false;
     if (L.timed_nn)
@@ -602,6 +609,7 @@ int loop_complete_body(icp_ctx* c, int* done)
     // (the host half of a pass is timed only while profiling is on: two clock reads are 0.5 % of a 9 us iteration)
     const bool time_host = c->profile_stride > 0;
     const auto th0 = time_host ? std::chrono::steady_clock::now() : tr2;
+    L.mom_valid = true;   // (icp_diag_loop_moments: c->h_mom as the host half receives it)
     const int adv = L.H.advance(c->h_mom);
     if (time_host) L.seconds_host += std::chrono::duration<double>(std::chrono::steady_clock::now() - th0).count();
     if (adv != ICP_OK) {
@@ -726,7 +734,8 @@ void loop_release_armed(icp_ctx* c)
     L.H.note_applied();
     L.armed = false;
     const bool host_rows = c->host_reduce();
-    set_pending(L, c->plan.blocks_x, 0, L.armed_compact, host_rows, !host_rows, false, L.armed_tag, c->plan.splits == 1 && c->slot_state.p != nullptr);
+    set_pending(L, c->plan.blocks_x, 0, L.armed_compact, host_rows, !host_rows, false, L.armed_tag, c->plan.splits == 1 && c->slot_state.p != nullptr,
+                ICP_ROUTE_ARMED | ICP_ROUTE_FUSED_TAIL | (host_rows ? 0 : ICP_ROUTE_FIN_LAUNCH | ICP_ROUTE_FIN_PINNED));
 }
 
 // the loop ended (or failed): the waiting kernel exits without touching anything; undo the bookkeeping
@@ -830,7 +839,8 @@ int loop_run_resident(icp_ctx* c, int max_steps, int* k_io, int* d_io, bool* fel
             std::fprintf(stderr, "[icp trace]   host turnaround (last row seen -> next message out): %.2f us\n",
                          1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - c->tr_rows_done).count());
         // (the kernel works in place: no slot-order points are left behind)
-        set_pending(L, rp.blocks_x, 0, ta.compact != 0, true, false, false, base + (double)sent, false);
+        set_pending(L, rp.blocks_x, 0, ta.compact != 0, true, false, false, base + (double)sent, false,
+                    ICP_ROUTE_RESIDENT | (cmd == icp::ICP_CMD_TRANSFORM_ONLY ? ICP_ROUTE_ERROR_ONLY : ICP_ROUTE_FUSED_TAIL));
         ++sent;
         if (c->trace) c->tr_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
         c->posted_at = tr0;
@@ -1106,6 +1116,18 @@ int icp_loop_timing_passes(icp_ctx* c, long long* passes)
 {
     if (!c || !passes) return fail(ICP_ERR_INVALID, "null argument");
     *passes = c->prof_nn_passes;
+    return ICP_OK;
+}
+
+int icp_diag_loop_moments(icp_ctx* c, double* out32, int* route)
+{
+    if (!c || !out32) return fail(ICP_ERR_INVALID, "null argument");
+    const LoopState& L = c->loop;
+    if (!L.active || !L.mom_valid || !c->h_mom) return fail(ICP_ERR_STATE, "no completed pass of a loop");
+    // (an enqueued pass has set its route already while the vector is still the pass's before it: never hand out the two together)
+    if (L.pending) return fail(ICP_ERR_STATE, "an enqueue is in flight (icp_loop_complete first)");
+    std::memcpy(out32, c->h_mom, ICP_NMOM * sizeof(double));
+    if (route) *route = L.route;
     return ICP_OK;
 }
 

@@ -198,6 +198,13 @@ class Context:
                                                 roles.ctypes.data_as(C.POINTER(C.c_int32))), "icp_diag_row_roles")
         return roles, h
 
+    def diag_loop_moments(self):
+        """(the ICP_NMOM vector the loop's host half last received, its ROUTE_* bits): icp_diag_loop_moments"""
+        mom = np.zeros(capi.ICP_NMOM, dtype=np.float64)
+        route = C.c_int(0)
+        capi.check(self._lib.icp_diag_loop_moments(self._h, mom.ctypes.data_as(C.POINTER(C.c_double)), C.byref(route)), "icp_diag_loop_moments")
+        return mom, route.value
+
     def nn_launch_info(self):
         v = [C.c_int(0) for _ in range(5)]
         capi.check(self._lib.icp_nn_launch_info(self._h, *[C.byref(x) for x in v]), "icp_nn_launch_info")
@@ -429,6 +436,12 @@ class Batch:
         capi.check(self._lib.icp_batch_state(self._h, int(b), C.byref(st), C.byref(it), C.byref(ps), err.ctypes.data_as(pd), err.size,
                                              T.ctypes.data_as(pd)), "icp_batch_state")
         return dict(status=st.value, iterations=it.value, passes=ps.value, err=err[: ps.value + 1].copy(), T=T.reshape(4, 4))
+
+    def diag_moments(self, b):
+        """the ICP_NMOM vector pair b's loop last advanced on (icp_diag_batch_moments)"""
+        mom = np.zeros(capi.ICP_NMOM, dtype=np.float64)
+        capi.check(self._lib.icp_diag_batch_moments(self._h, int(b), mom.ctypes.data_as(C.POINTER(C.c_double))), "icp_diag_batch_moments")
+        return mom
 
     def done(self):
         """(count,) bool: the pairs whose loop has ended"""

@@ -53,6 +53,31 @@ int icp_share_rows_plan(const uint32_t* hits, int rows, int blocks, int model_po
 #define ICP_ROLES_EXTRA 4096
 int icp_diag_row_roles(icp_ctx* ctx, uint32_t* hits_io, int rows, int min_part, int total_div, int control, int32_t* roles_out);
 
+/* The ICP_NMOM-double moment vector the loop's host half (HostLoop::advance: error, stop rule, solve) last received -- after the
+ * rows were added up by whoever adds them for this plan and after any exchange between the ranks of a node communicator -- and,
+ * in *route (may be NULL), how it came about: the ICP_ROUTE_* bits below.  Everything a pass gives the host is in this vector;
+ * tests/test_gpu_moments.py holds it against exact sums over (moving cloud, model, correspondences) of the same pass.  Reading it
+ * costs the loop nothing: the flags are set where the pass is issued and completed, the vector is the one the loop keeps anyway.
+ * ICP_ERR_STATE before the first completed pass of a loop, and between icp_loop_enqueue and icp_loop_complete (the vector would
+ * be the previous pass's, the route the pending one's).  (The reference has no such seam: its sums are cublas calls between
+ * the kernels, src/ICP_point_to_point.cu:308-357.) */
+#define ICP_ROUTE_HOST_ROWS 0x001      /* the host added the pass's rows from pinned memory (sum_host_rows) */
+#define ICP_ROUTE_COMPACT 0x002        /* ... rows in the compact 16-double format (tag in the low mantissa bits of slots 0/4/8/12) */
+#define ICP_ROUTE_AVX 0x004            /* ... with the AVX adder (else the scalar loop: ICP_MAILBOX=plain, or no AVX) */
+#define ICP_ROUTE_FIN_LAUNCH 0x008     /* the matching launch added its rows up itself (fin_close) */
+#define ICP_ROUTE_FIN_PINNED 0x010     /* ... and left the vector in pinned memory (else in the device vector, copied back) */
+#define ICP_ROUTE_FIN_KERNEL 0x020     /* rows left on the device and added by finalize_kernel, the vector copied back */
+#define ICP_ROUTE_FIN_TWO_STAGE 0x040  /* ... through finalize_ranges_kernel first (more than 2048 rows) */
+#define ICP_ROUTE_FUSED_TAIL 0x080     /* the rows come from the matching kernel's fused tail */
+#define ICP_ROUTE_MOMENTS_KERNEL 0x100 /* ... or from moments_kernel (the two-kernel form) */
+#define ICP_ROUTE_ERROR_ONLY 0x200     /* the loop's last pass: a transform and its error, nothing matched (only ICP_MOM_ERR means anything) */
+#define ICP_ROUTE_ARMED 0x400          /* the pass was an armed launch released through its mailbox */
+#define ICP_ROUTE_RESIDENT 0x800       /* the pass was a message to the resident kernel */
+int icp_diag_loop_moments(icp_ctx* ctx, double* out32, int* route);
+/* the same for pair `pair` of a batch: the row of the step's download that pair's loop last advanced on (the batch has one route:
+ * nn_match_batch's item rows added by batch_finalize_kernel).  ICP_ERR_STATE before the pair's first completed pass. */
+int icp_diag_batch_moments(icp_batch* b, int pair, double* out32);
+
 #ifdef __cplusplus
 }
 #endif

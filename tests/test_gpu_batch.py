@@ -9,6 +9,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from clouds import ragged_pair   # (one home for the construction: the moment tests use the same clouds)
+
 pytestmark = pytest.mark.gpu
 
 TOL_T = 1e-5
@@ -47,19 +49,6 @@ def fp32_pairs(pkg, golden):
     B = np.fromfile(os.path.join(golden, "bunny_res_xyz_f32.bin"), dtype=np.float32).reshape(-1, 3)
     return [(D, pkg.datasets.make_model_gpu(D, *pkg.datasets.P2P_GPU)), (D, pkg.datasets.make_model_standard(D)),
             (B, pkg.datasets.make_model_gpu(B, *pkg.datasets.BUNNY))]
-
-
-def ragged_pair(rng_seed, n, m):
-    """the construction of test_gpu_parity.test_resident_loop_small_and_ragged_clouds"""
-    rng = np.random.default_rng(rng_seed)
-    M = rng.standard_normal((m, 3)).astype(np.float32)
-    pick = rng.integers(0, m, size=n)
-    ang = np.array([0.05, -0.03, 0.04])
-    cx, sx, cy, sy, cz, sz = np.cos(ang[0]), np.sin(ang[0]), np.cos(ang[1]), np.sin(ang[1]), np.cos(ang[2]), np.sin(ang[2])
-    R = (np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]) @
-         np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]))
-    D = ((M[pick].astype(np.float64) - np.array([0.02, -0.01, 0.03])) @ R).astype(np.float32) + (1e-3 * rng.standard_normal((n, 3))).astype(np.float32)
-    return D, M
 
 
 def same_bits(a, b):
