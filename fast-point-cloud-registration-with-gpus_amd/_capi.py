@@ -91,6 +91,8 @@ SIGNATURES = {
     "icp_batch_create": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, _i, C.POINTER(_vp)]),
     "icp_batch_destroy": (None, [_vp]),
     "icp_batch_begin": (_i, [_vp, C.POINTER(icp_params)]),
+    "icp_batch_set_model_normals": (_i, [_vp, _vp]),
+    "icp_batch_estimate_normals": (_i, [_vp, _vp, _pi32]),
     "icp_batch_run": (_i, [_vp, _i, _pi, _pi]),
     "icp_batch_state": (_i, [_vp, _i, _pi, _pi, _pi, _pd, _i, _pd]),
     "icp_batch_done": (_i, [_vp, _pi32]),
@@ -98,6 +100,7 @@ SIGNATURES = {
     "icp_batch_get_indices": (_i, [_vp, _pi32]),
     "icp_batch_loop_indices": (_i, [_vp, _pi32]),
     "icp_point_to_point_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
+    "icp_point_to_plane_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, _vp, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_comm_unique_id": (_i, [_vp]),
     "icp_comm_init": (_i, [_vp, _vp, _i, _i]),
     "icp_comm_destroy": (_i, [_vp]),

@@ -1,19 +1,25 @@
-// icp_batch.cpp -- batched point-to-point ICP (icp_batch_*, icp_point_to_point_batch): many independent pairs, and per step ONE
-// matching launch + ONE reduction launch + ONE download of ICP_NMOM doubles per pair for every pair still running.
+// icp_batch.cpp -- batched ICP (icp_batch_*, icp_point_to_point_batch, icp_point_to_plane_batch): many independent pairs, and per
+// step ONE matching launch + ONE reduction launch + ONE download of ICP_NMOM doubles per pair for every pair still running.
 //
 //   step k:  [R, t + mode of every pair: H2D]  ->  nn_match_batch (transform + error, match, moments per work item)
 //            ->  batch_finalize_kernel (per pair, fixed order)  ->  D2H count x ICP_NMOM  ->  sync
-//            ->  HostLoop::advance per pair that took part (error, stop rule, 3x3 solve)
+//            ->  HostLoop::advance per pair that took part (error, stop rule, 3x3 solve or 6x6 solve)
+//
+// Point-to-plane needs the model normals of every pair, in planes laid out as the models: given by the caller
+// (icp_batch_set_model_normals) or made on the device by ONE neighbour launch + ONE normals launch for the whole batch
+// (icp_batch_estimate_normals: knn4_batch + normals_batch_kernel, icp_k_plane.hip).  The reference estimates them once per
+// program, before its loop (src/ICP_point_to_plane.cu:391-438).
 //
 // Every pair runs its own icp::HostLoop, the single-pair loop's host half (icp_host_loop.cpp): the same stop rule, the same
 // composition of T, the same err series.  A pass of a pair is what loop_enqueue_body (icp_loop.cpp) makes of it: the motion
 // solved by the previous pass is applied in the front of the launch (note_applied when it is enqueued), and the loop's last,
 // error-only pass matches nothing.  The reference runs that loop once per program (src/ICP_point_to_point.cu:295-423,
-// src/ICP_CPU.c:217-271).
+// src/ICP_CPU.c:217-271; point-to-plane src/ICP_point_to_plane.cu:517-631).
 #include <climits>
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "../../include/icp_mi355x_diag.h"
@@ -25,10 +31,15 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     int prec = ICP_F32;
     size_t esize = sizeof(float);
     std::vector<int64_t> moff;               // the caller's moving offsets: the layout of get_moving / get_indices
+    std::vector<int64_t> qoff;               // the caller's model offsets: the layout of the normals and the neighbours
     std::vector<icp::BatchPair> pairs;       // where each pair lives on the device
     int n_items = 0;
     long long p_plane = 0, q_plane = 0;      // elements per SoA plane of the moving / model clouds
     DevBuf P, P0, Q, items, pairs_d, ctl, idx[2], partials, mom;   // P0: the moving clouds as uploaded (icp_batch_begin)
+    DevBuf N, q_items, nbr;                  // point-to-plane: the model normals (planes as Q), the model's work items, 4 neighbours per model point
+    int n_q_items = 0;
+    bool have_normals = false;
+    int metric = ICP_POINT_TO_POINT;         // of the loop under way
     void* h_ctl = nullptr;                   // pinned: R, t of every pair (12 values of the precision), then its mode (int)
     double* h_mom = nullptr;                 // pinned: count x ICP_NMOM
     size_t rt_bytes = 0, ctl_bytes = 0;
@@ -63,7 +74,8 @@ int ready(icp_batch* b)
 
 void release(icp_batch* b)
 {
-    for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom}) d->release();
+    for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr})
+        d->release();
     if (b->h_ctl) (void)hipHostFree(b->h_ctl);
     if (b->h_mom) (void)hipHostFree(b->h_mom);
     delete b;
@@ -193,10 +205,10 @@ int step(icp_batch* b)
         }
     }
     HIP_TRY(hipMemcpyAsync(b->ctl.p, b->h_ctl, b->ctl_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(icp::launch_batch_pass(b->prec, (const icp::BatchItem*)b->items.p, b->n_items, (const icp::BatchPair*)b->pairs_d.p, b->count,
-                                   (const int*)(static_cast<char*>(b->ctl.p) + b->rt_bytes), b->ctl.p, b->P.p, b->p_plane, b->Q.p,
-                                   b->q_plane, (const int32_t*)b->idx[cur ^ 1].p, (int32_t*)b->idx[cur].p, (double*)b->partials.p,
-                                   (double*)b->mom.p, c->stream));
+    HIP_TRY(icp::launch_batch_pass(b->prec, b->metric, (const icp::BatchItem*)b->items.p, b->n_items, (const icp::BatchPair*)b->pairs_d.p,
+                                   b->count, (const int*)(static_cast<char*>(b->ctl.p) + b->rt_bytes), b->ctl.p, b->P.p, b->p_plane, b->Q.p,
+                                   b->metric == ICP_POINT_TO_PLANE ? b->N.p : nullptr, b->q_plane, (const int32_t*)b->idx[cur ^ 1].p,
+                                   (int32_t*)b->idx[cur].p, (double*)b->partials.p, (double*)b->mom.p, c->stream));
     HIP_TRY(hipMemcpyAsync(b->h_mom, b->mom.p, (size_t)b->count * ICP_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     b->steps += 1;
@@ -261,6 +273,7 @@ int icp_batch_create(icp_ctx* c, int count, const void* moving_aos, const int64_
     b->prec = precision;
     b->esize = precision == ICP_F64 ? sizeof(double) : sizeof(float);
     b->moff.assign(moving_off, moving_off + count + 1);
+    b->qoff.assign(model_off, model_off + count + 1);
     b->pairs.resize((size_t)count);
     long long items = 0;
     for (int p = 0; p < count; ++p) {
@@ -305,10 +318,13 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
 {
     if (int rc = ready(b)) return rc;
     if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
-    if (prm->metric != ICP_POINT_TO_POINT) return fail(ICP_ERR_INVALID, "a batch runs point-to-point only");
+    if (prm->metric != ICP_POINT_TO_POINT && prm->metric != ICP_POINT_TO_PLANE) return fail(ICP_ERR_INVALID, "unknown metric");
+    if (prm->metric == ICP_POINT_TO_PLANE && !b->have_normals)
+        return fail(ICP_ERR_INVALID, "a point-to-plane batch needs the model normals: icp_batch_set_model_normals or icp_batch_estimate_normals first");
     if (prm->precision != b->prec) return fail(ICP_ERR_INVALID, "params precision differs from the batch's clouds");
     if (prm->max_iter < 1) return fail(ICP_ERR_INVALID, "max_iter must be >= 1");
     b->begun = false;
+    b->metric = prm->metric;
     for (int p = 0; p < b->count; ++p)
         if (int rc = b->H[p].begin(*prm)) return fail(rc, "bad loop parameters");
     b->status.assign((size_t)b->count, ICP_OK);
@@ -393,18 +409,100 @@ int icp_batch_get_indices(icp_batch* b, int32_t* idx_out) { return download_indi
 
 int icp_batch_loop_indices(icp_batch* b, int32_t* idx_out) { return download_indices(b, true, idx_out); }
 
-int icp_point_to_point_batch(icp_ctx* c, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
-                             const int64_t* model_off, const icp_params* prm, double* T16_out, int* iterations_out, int* passes_out,
-                             double* err_out, int32_t* idx_out, void* moved_out, int* status_out)
+int icp_batch_set_model_normals(icp_batch* b, const void* nxyz_aos)
 {
-    if (!c) return fail(ICP_ERR_INVALID, "null context");
-    if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
-    if (prm->metric != ICP_POINT_TO_POINT) return fail(ICP_ERR_INVALID, "a batch runs point-to-point only");
-    if (prm->max_iter < 1) return fail(ICP_ERR_INVALID, "max_iter must be >= 1");
+    if (int rc = ready(b)) return rc;
+    if (!nxyz_aos) return fail(ICP_ERR_INVALID, "nxyz_aos == NULL");
+    const int64_t points = b->qoff[b->count];
+    if (!(b->prec == ICP_F64 ? all_finite<double>(nxyz_aos, points) : all_finite<float>(nxyz_aos, points)))
+        return fail(ICP_ERR_INVALID, "a normal of the batch has a NaN or an infinite component");
+    std::vector<long long> qdst(b->count);
+    for (int p = 0; p < b->count; ++p) qdst[p] = b->pairs[p].q_off;
+    const size_t qb = 3 * (size_t)b->q_plane * b->esize;
+    HIP_TRY(b->N.ensure(qb));
+    b->begun = false;   // a loop under way is discarded: its passes so far used other normals (or none)
+    b->have_normals = false;
+    if (b->prec == ICP_F64) {
+        const std::vector<double> ns = to_planes<double>(nxyz_aos, b->qoff.data(), b->count, qdst, b->q_plane);
+        HIP_TRY(hipMemcpyAsync(b->N.p, ns.data(), qb, hipMemcpyHostToDevice, b->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
+    } else {
+        const std::vector<float> ns = to_planes<float>(nxyz_aos, b->qoff.data(), b->count, qdst, b->q_plane);
+        HIP_TRY(hipMemcpyAsync(b->N.p, ns.data(), qb, hipMemcpyHostToDevice, b->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    }
+    b->have_normals = true;
+    return ICP_OK;
+}
+
+int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighbours_out)
+{
+    if (int rc = ready(b)) return rc;
+    for (int p = 0; p < b->count; ++p)
+        if (b->pairs[p].m < 5)
+            return fail(ICP_ERR_INVALID, "normals need at least 5 model points (k = 4 neighbours + self): pair " + std::to_string(p) + " has " +
+                                             std::to_string(b->pairs[p].m));
+    icp_ctx* c = b->ctx;
+    const size_t qb = 3 * (size_t)b->q_plane * b->esize, nb = 4 * (size_t)b->q_plane * sizeof(int32_t);
+    if (b->n_q_items == 0) {   // the model's work items: BATCH_ITEM model points of one pair, cut from that pair's first model point
+        std::vector<icp::BatchItem> items;
+        for (int p = 0; p < b->count; ++p)
+            for (int first = 0; first < b->pairs[p].m; first += icp::BATCH_ITEM)
+                items.push_back(icp::BatchItem{p, first, std::min(icp::BATCH_ITEM, b->pairs[p].m - first), 0});
+        if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+        HIP_TRY(b->q_items.ensure(items.size() * sizeof(icp::BatchItem)));
+        HIP_TRY(hipMemcpyAsync(b->q_items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));   // (items: a host vector)
+        b->n_q_items = (int)items.size();
+    }
+    HIP_TRY(b->nbr.ensure(nb));
+    HIP_TRY(b->N.ensure(qb));
+    b->begun = false;   // a loop under way is discarded
+    b->have_normals = false;
+    HIP_TRY(hipMemsetAsync(b->nbr.p, 0, nb, c->stream));   // (the padding between the clouds: never read, never random)
+    HIP_TRY(hipMemsetAsync(b->N.p, 0, qb, c->stream));
+    HIP_TRY(icp::launch_batch_normals(b->prec, (const icp::BatchItem*)b->q_items.p, b->n_q_items, (const icp::BatchPair*)b->pairs_d.p, b->Q.p,
+                                      b->q_plane, (int32_t*)b->nbr.p, b->N.p, c->stream));
+    std::vector<char> raw;
+    std::vector<int32_t> hn;
+    if (nxyz_aos_out) {
+        raw.resize(qb);
+        HIP_TRY(hipMemcpyAsync(raw.data(), b->N.p, qb, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (neighbours_out) {
+        hn.resize(4 * (size_t)b->q_plane);
+        HIP_TRY(hipMemcpyAsync(hn.data(), b->nbr.p, nb, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int p = 0; p < b->count; ++p) {
+        const icp::BatchPair& pr = b->pairs[p];
+        if (nxyz_aos_out)
+            for (int i = 0; i < pr.m; ++i)
+                for (int k = 0; k < 3; ++k) {
+                    const size_t src = (size_t)(k * b->q_plane + pr.q_off + i), dst = 3 * (size_t)(b->qoff[p] + i) + k;
+                    if (b->prec == ICP_F64) static_cast<double*>(nxyz_aos_out)[dst] = reinterpret_cast<const double*>(raw.data())[src];
+                    else static_cast<float*>(nxyz_aos_out)[dst] = reinterpret_cast<const float*>(raw.data())[src];
+                }
+        if (neighbours_out)
+            std::memcpy(neighbours_out + 4 * b->qoff[p], hn.data() + 4 * (size_t)pr.q_off, 4 * (size_t)pr.m * sizeof(int32_t));
+    }
+    b->have_normals = true;
+    return ICP_OK;
+}
+
+namespace {
+
+// create, [normals], begin, run to the end, results, destroy
+int run_batch(icp_ctx* c, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos, const int64_t* model_off,
+              bool plane, const void* normals_aos, const icp_params* prm, double* T16_out, int* iterations_out, int* passes_out,
+              double* err_out, int32_t* idx_out, void* moved_out, int* status_out)
+{
     icp_batch* b = nullptr;
     if (int rc = icp_batch_create(c, count, moving_aos, moving_off, model_aos, model_off, prm->precision, &b)) return rc;
     ScopedPin pin(c);
-    int rc = icp_batch_begin(b, prm);
+    int rc = ICP_OK;
+    if (plane) rc = normals_aos ? icp_batch_set_model_normals(b, normals_aos) : icp_batch_estimate_normals(b, nullptr, nullptr);
+    if (rc == ICP_OK) rc = icp_batch_begin(b, prm);
     for (int active = 1; rc == ICP_OK && active > 0;) rc = icp_batch_run(b, 1 << 20, nullptr, &active);
     const int cap = prm->max_iter + 1;
     for (int p = 0; rc == ICP_OK && p < count; ++p)
@@ -415,6 +513,32 @@ int icp_point_to_point_batch(icp_ctx* c, int count, const void* moving_aos, cons
     if (rc == ICP_OK && moved_out) rc = icp_batch_get_moving(b, moved_out);
     icp_batch_destroy(b);
     return rc;
+}
+
+}  // namespace
+
+int icp_point_to_point_batch(icp_ctx* c, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
+                             const int64_t* model_off, const icp_params* prm, double* T16_out, int* iterations_out, int* passes_out,
+                             double* err_out, int32_t* idx_out, void* moved_out, int* status_out)
+{
+    if (!c) return fail(ICP_ERR_INVALID, "null context");
+    if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
+    if (prm->metric != ICP_POINT_TO_POINT) return fail(ICP_ERR_INVALID, "icp_point_to_point_batch runs point-to-point only (icp_point_to_plane_batch)");
+    if (prm->max_iter < 1) return fail(ICP_ERR_INVALID, "max_iter must be >= 1");
+    return run_batch(c, count, moving_aos, moving_off, model_aos, model_off, false, nullptr, prm, T16_out, iterations_out, passes_out, err_out,
+                     idx_out, moved_out, status_out);
+}
+
+int icp_point_to_plane_batch(icp_ctx* c, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
+                             const int64_t* model_off, const void* normals_aos, const icp_params* prm, double* T16_out,
+                             int* iterations_out, int* passes_out, double* err_out, int32_t* idx_out, void* moved_out, int* status_out)
+{
+    if (!c) return fail(ICP_ERR_INVALID, "null context");
+    if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
+    if (prm->metric != ICP_POINT_TO_PLANE) return fail(ICP_ERR_INVALID, "icp_point_to_plane_batch: prm->metric must be ICP_POINT_TO_PLANE");
+    if (prm->max_iter < 1) return fail(ICP_ERR_INVALID, "max_iter must be >= 1");
+    return run_batch(c, count, moving_aos, moving_off, model_aos, model_off, true, normals_aos, prm, T16_out, iterations_out, passes_out,
+                     err_out, idx_out, moved_out, status_out);
 }
 
 }  // extern "C"

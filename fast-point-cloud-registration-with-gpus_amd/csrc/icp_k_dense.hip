@@ -848,7 +848,7 @@ hipError_t launch_dense_v2(const NNPlan& pl, const void* P, const void* Qscan, v
 }
 
 // ------------------------------------------------------------------------------------------------
-// batched point-to-point (icp_batch.cpp): the pass of every running pair of a batch in one launch.
+// batched ICP (icp_batch.cpp): the pass of every running pair of a batch in one launch.
 //
 // grid = one block per work item: BATCH_ITEM moving points of one pair, cut from that pair's first point.  All four waves
 // hold the item's points (one per lane); wave w scans the w-th contiguous quarter of the pair's model through its own LDS
@@ -859,6 +859,10 @@ hipError_t launch_dense_v2(const NNPlan& pl, const void* P, const void* Qscan, v
 //     instructions; wave 0 stores them and adds |p_new - q[idx_prev]|^2 in double (transform_error_kernel's arithmetic);
 //   tail: wave 0 stores idx, gathers q[idx] and forms moments_kernel's point-to-point terms in double; block_sum_store
 //     writes the item's row partials[item][0 .. ICP_MOM_SQQ] (error in slot ICP_MOM_ERR).
+//   METRIC == ICP_POINT_TO_PLANE (its own instantiation: the point-to-point one has no branch on the metric): wave 0 gathers
+//     n[idx] too, from the normal planes laid out as the model's, and forms moments_kernel's plane terms statement for
+//     statement -- cn = (p x n, n), bi = (p - q) . n, C += cn cn^T, b -= cn bi -- into slots ICP_MOM_CNT, ICP_MOM_C ..
+//     ICP_MOM_B + 5.  The front end and the error-only last pass are the same code.
 // A pair's blocks, their geometry and every sum depend on that pair alone (no atomics): its bits do not depend on the batch.
 // ------------------------------------------------------------------------------------------------
 template <typename F> struct BatchCfg;
@@ -866,17 +870,19 @@ template <> struct BatchCfg<float> { static constexpr int TW = 512; };    // mod
 template <> struct BatchCfg<double> { static constexpr int TW = 256; };
 static_assert(sizeof(RT<float>) == 12 * sizeof(float) && sizeof(RT<double>) == 12 * sizeof(double), "the host writes R, t as 12 values per pair");
 
-template <typename F>
+template <typename F, int METRIC>
 __global__ __launch_bounds__(NN_BLOCK) void nn_match_batch(const BatchItem* __restrict__ items, const BatchPair* __restrict__ pairs,
                                                            const int* __restrict__ mode, const RT<F>* __restrict__ rts,
-                                                           F* __restrict__ P, long long p_plane, const F* __restrict__ Q, long long q_plane,
+                                                           F* __restrict__ P, long long p_plane, const F* __restrict__ Q,
+                                                           const F* __restrict__ Nrm, long long q_plane,
                                                            const int32_t* __restrict__ idx_prev, int32_t* __restrict__ idx_cur,
                                                            double* __restrict__ partials)
 {
     using V = typename Vec16<F>::type;
     constexpr int VN = Vec16<F>::N;
     constexpr int TW = BatchCfg<F>::TW, C = NN_CHUNK;
-    constexpr int NACC = ICP_MOM_SQQ + 1;   // error, count, sum p, sum q, sum q p^T, |p|^2, |q|^2: the slots of the moment vector
+    // error, count, sum p, sum q, sum q p^T, |p|^2, |q|^2 -- or error, count, C (21), b (6): the slots of the moment vector
+    constexpr int NACC = (METRIC == ICP_POINT_TO_POINT) ? ICP_MOM_SQQ + 1 : ICP_MOM_B + 6;
     static_assert(BATCH_ITEM == 64 && NN_BLOCK == 4 * BATCH_ITEM, "one point per lane, four waves per item");
     __shared__ __attribute__((aligned(16))) F sq[4][3][TW];
     __shared__ F md[4][BATCH_ITEM];
@@ -974,13 +980,31 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_match_batch(const BatchItem* __re
             const double px = (double)x, py = (double)y, pz = (double)z;
             const double qx = (double)Qx[j], qy = (double)Qy[j], qz = (double)Qz[j];
             acc[ICP_MOM_CNT] = 1.0;
-            acc[ICP_MOM_SP + 0] = px; acc[ICP_MOM_SP + 1] = py; acc[ICP_MOM_SP + 2] = pz;
-            acc[ICP_MOM_SQ + 0] = qx; acc[ICP_MOM_SQ + 1] = qy; acc[ICP_MOM_SQ + 2] = qz;
-            acc[ICP_MOM_SQP + 0] = qx * px; acc[ICP_MOM_SQP + 1] = qx * py; acc[ICP_MOM_SQP + 2] = qx * pz;
-            acc[ICP_MOM_SQP + 3] = qy * px; acc[ICP_MOM_SQP + 4] = qy * py; acc[ICP_MOM_SQP + 5] = qy * pz;
-            acc[ICP_MOM_SQP + 6] = qz * px; acc[ICP_MOM_SQP + 7] = qz * py; acc[ICP_MOM_SQP + 8] = qz * pz;
-            acc[ICP_MOM_SPP] = px * px + py * py + pz * pz;
-            acc[ICP_MOM_SQQ] = qx * qx + qy * qy + qz * qz;
+            if constexpr (METRIC == ICP_POINT_TO_POINT) {
+                acc[ICP_MOM_SP + 0] = px; acc[ICP_MOM_SP + 1] = py; acc[ICP_MOM_SP + 2] = pz;
+                acc[ICP_MOM_SQ + 0] = qx; acc[ICP_MOM_SQ + 1] = qy; acc[ICP_MOM_SQ + 2] = qz;
+                acc[ICP_MOM_SQP + 0] = qx * px; acc[ICP_MOM_SQP + 1] = qx * py; acc[ICP_MOM_SQP + 2] = qx * pz;
+                acc[ICP_MOM_SQP + 3] = qy * px; acc[ICP_MOM_SQP + 4] = qy * py; acc[ICP_MOM_SQP + 5] = qy * pz;
+                acc[ICP_MOM_SQP + 6] = qz * px; acc[ICP_MOM_SQP + 7] = qz * py; acc[ICP_MOM_SQP + 8] = qz * pz;
+                acc[ICP_MOM_SPP] = px * px + py * py + pz * pz;
+                acc[ICP_MOM_SQQ] = qx * qx + qy * qy + qz * qz;
+            } else {
+                const F* Nx = Nrm + pr.q_off;
+                const double nx = (double)Nx[j], ny = (double)Nx[q_plane + j], nz = (double)Nx[2 * q_plane + j];
+                double cn[6];
+                cn[0] = py * nz - pz * ny;
+                cn[1] = pz * nx - px * nz;
+                cn[2] = px * ny - py * nx;
+                cn[3] = nx; cn[4] = ny; cn[5] = nz;
+                const double bi = (px - qx) * nx + (py - qy) * ny + (pz - qz) * nz;
+                int o = ICP_MOM_C;
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int c = a; c < 6; ++c) acc[o++] += cn[a] * cn[c];
+#pragma unroll
+                for (int a = 0; a < 6; ++a) acc[ICP_MOM_B + a] -= cn[a] * bi;
+            }
         }
     }
     // (waves 1-3 add zeros: the row is wave 0's 64 lanes, summed in lane order)
@@ -988,16 +1012,17 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_match_batch(const BatchItem* __re
 }
 
 // one block per pair: mom[pair] = the pair's item rows added up in a fixed order (thread (k, part) adds items part, part + 8, ...
-// of slot k; the eight part sums are then added in part order -- finalize_kernel's scheme, over the pair's own items only)
+// of slot k; the eight part sums are then added in part order -- finalize_kernel's scheme, over the pair's own items only).
+// last = the metric's last slot: ICP_MOM_SQQ, or ICP_MOM_B + 5 for a plane loop; the slots behind it are written as zeros.
 __global__ __launch_bounds__(256) void batch_finalize_kernel(const BatchPair* __restrict__ pairs, const int* __restrict__ mode,
-                                                             const double* __restrict__ partials, double* __restrict__ mom)
+                                                             const double* __restrict__ partials, int last, double* __restrict__ mom)
 {
     __shared__ double red[8][ICP_NMOM];
     if (mode[blockIdx.x] == 0) return;
     const int k = threadIdx.x & 31, part = threadIdx.x >> 5;
     const int i0 = pairs[blockIdx.x].item0, i1 = pairs[blockIdx.x].item1;
     double s = 0.0;
-    if (k <= ICP_MOM_SQQ)
+    if (k <= last)
         for (int i = i0 + part; i < i1; i += 8) s += partials[(size_t)i * ICP_NMOM + k];
     red[part][k] = s;
     __syncthreads();
@@ -1009,19 +1034,25 @@ __global__ __launch_bounds__(256) void batch_finalize_kernel(const BatchPair* __
     }
 }
 
-hipError_t launch_batch_pass(int precision, const BatchItem* items, int n_items, const BatchPair* pairs, int n_pairs, const int* mode,
-                             const void* rt, void* P, long long p_plane, const void* Q, long long q_plane, const int32_t* idx_prev,
-                             int32_t* idx_cur, double* partials, double* mom, hipStream_t st)
+hipError_t launch_batch_pass(int precision, int metric, const BatchItem* items, int n_items, const BatchPair* pairs, int n_pairs,
+                             const int* mode, const void* rt, void* P, long long p_plane, const void* Q, const void* Nrm,
+                             long long q_plane, const int32_t* idx_prev, int32_t* idx_cur, double* partials, double* mom, hipStream_t st)
 {
     if (n_items <= 0 || n_pairs <= 0) return hipSuccess;
-    if (precision == ICP_F64)
-        hipLaunchKernelGGL((nn_match_batch<double>), dim3(n_items), dim3(NN_BLOCK), 0, st, items, pairs, mode, (const RT<double>*)rt,
-                           (double*)P, p_plane, (const double*)Q, q_plane, idx_prev, idx_cur, partials);
-    else
-        hipLaunchKernelGGL((nn_match_batch<float>), dim3(n_items), dim3(NN_BLOCK), 0, st, items, pairs, mode, (const RT<float>*)rt,
-                           (float*)P, p_plane, (const float*)Q, q_plane, idx_prev, idx_cur, partials);
+    const bool plane = metric == ICP_POINT_TO_PLANE;
+    if (plane && !Nrm) return hipErrorInvalidValue;
+#define ICP_LAUNCH_BATCH(F, MET)                                                                                                  \
+    hipLaunchKernelGGL((nn_match_batch<F, MET>), dim3(n_items), dim3(NN_BLOCK), 0, st, items, pairs, mode, (const RT<F>*)rt, (F*)P, \
+                       p_plane, (const F*)Q, (const F*)Nrm, q_plane, idx_prev, idx_cur, partials)
+    if (precision == ICP_F64) {
+        if (plane) ICP_LAUNCH_BATCH(double, ICP_POINT_TO_PLANE); else ICP_LAUNCH_BATCH(double, ICP_POINT_TO_POINT);
+    } else {
+        if (plane) ICP_LAUNCH_BATCH(float, ICP_POINT_TO_PLANE); else ICP_LAUNCH_BATCH(float, ICP_POINT_TO_POINT);
+    }
+#undef ICP_LAUNCH_BATCH
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(batch_finalize_kernel, dim3(n_pairs), dim3(256), 0, st, pairs, mode, (const double*)partials, mom);
+    hipLaunchKernelGGL(batch_finalize_kernel, dim3(n_pairs), dim3(256), 0, st, pairs, mode, (const double*)partials,
+                       plane ? ICP_MOM_B + 5 : ICP_MOM_SQQ, mom);
     return hipGetLastError();
 }
 

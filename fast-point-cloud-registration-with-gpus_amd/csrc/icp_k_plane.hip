@@ -246,21 +246,20 @@ __global__ void knn4_merge_kernel(const float* __restrict__ part_d, const int32_
 // k), then a cyclic-Jacobi eigen-solve in fp64 registers (stands in for the reference's HOST loop of
 // LAPACKE_ssyev, src/ICP_point_to_plane.cu:429-438) and the eigenvector of the eigenvalue of smallest magnitude
 // (cblas_isamin over the ascending eigenvalues, first on ties).  Writes the padded SoA normal cloud directly.
+// The per-point body, shared by normals_kernel and normals_batch_kernel: the same statements on the same four neighbours give
+// the same bits (contraction is off for this translation unit).  Qx, Qy, Qz: the coordinate planes the indices nb4[0..3] refer to.
 template <typename F>
-__global__ void normals_kernel(const F* __restrict__ Q, int m, int m_pad, const int32_t* __restrict__ nbr,
-                               F* __restrict__ Nrm)
+__device__ __forceinline__ void pca_normal(const F* __restrict__ Qx, const F* __restrict__ Qy, const F* __restrict__ Qz,
+                                           const int32_t* __restrict__ nb4, double& nx, double& ny, double& nz)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m_pad) return;
-    const int src = i < m ? i : m - 1;  // padding replicates the last point's normal (never referenced)
     float x[4], y[4], z[4];
     float bx = 0.f, by = 0.f, bz = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const int s = nbr[(size_t)src * 4 + j];
-        x[j] = (float)Q[s];
-        y[j] = (float)Q[(size_t)m_pad + s];
-        z[j] = (float)Q[2 * (size_t)m_pad + s];
+        const int s = nb4[j];
+        x[j] = (float)Qx[s];
+        y[j] = (float)Qy[s];
+        z[j] = (float)Qz[s];
         bx += x[j]; by += y[j]; bz += z[j];
     }
     const float qa = 1.0f / 4.0f;
@@ -328,13 +327,185 @@ __global__ void normals_kernel(const F* __restrict__ Q, int m, int m_pad, const 
     ICP_SWAP_EIG(w0, e0x, e0y, e0z, w2, e2x, e2y, e2z)
     ICP_SWAP_EIG(w1, e1x, e1y, e1z, w2, e2x, e2y, e2z)
 #undef ICP_SWAP_EIG
-    double nx = e0x, ny = e0y, nz = e0z;
+    nx = e0x; ny = e0y; nz = e0z;
     float wm = fabsf((float)w0);
     if (fabsf((float)w1) < wm) { wm = fabsf((float)w1); nx = e1x; ny = e1y; nz = e1z; }
     if (fabsf((float)w2) < wm) { nx = e2x; ny = e2y; nz = e2z; }
+}
+
+template <typename F>
+__global__ void normals_kernel(const F* __restrict__ Q, int m, int m_pad, const int32_t* __restrict__ nbr,
+                               F* __restrict__ Nrm)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m_pad) return;
+    const int src = i < m ? i : m - 1;  // padding replicates the last point's normal (never referenced)
+    double nx, ny, nz;
+    pca_normal<F>(Q, Q + (size_t)m_pad, Q + 2 * (size_t)m_pad, nbr + (size_t)src * 4, nx, ny, nz);
     Nrm[i] = (F)nx;
     Nrm[(size_t)m_pad + i] = (F)ny;
     Nrm[2 * (size_t)m_pad + i] = (F)nz;
+}
+
+// ------------------------------------------------------------------------------------------------
+// batched point-to-plane front end (icp_batch_estimate_normals, icp_batch.cpp): the neighbours and normals of every pair's
+// model in one launch each.  The clouds lie in the batch's SoA planes (BatchPair::q_off, plane stride q_plane); the
+// neighbours of model point i of a pair are nbr[(q_off + i) * 4 ..], indices WITHIN that pair's model.
+//
+// knn4_batch: grid = one block per work item of BATCH_ITEM model points of one pair, cut from that pair's first model point.
+// All four waves hold the item's points as queries (one per lane); wave w streams the w-th contiguous quarter of the pair's
+// model through its own LDS sub-tile (every lane reads the same address) and keeps a sorted (d, j) top-5 in registers --
+// knn4_kernel's insertion, entered under a wave-uniform test of the chunk's minimum against every lane's fifth best.  The
+// four lists are merged in quarter order, ties to the lower quarter = the lower index; rank 0 is dropped.  What comes out is
+// the first five of the (d, j)-ascending order of the pair's model, as knn4_kernel's single ascending scan leaves them.
+// ------------------------------------------------------------------------------------------------
+template <typename F> struct KnnBatchCfg;
+template <> struct KnnBatchCfg<float> { static constexpr int TW = 512; };    // model points per wave and tile
+template <> struct KnnBatchCfg<double> { static constexpr int TW = 256; };
+constexpr int KNNB_C = 8;   // model points per early-out chunk
+
+template <typename F>
+__global__ __launch_bounds__(NN_BLOCK) void knn4_batch(const BatchItem* __restrict__ items, const BatchPair* __restrict__ pairs,
+                                                       const F* __restrict__ Q, long long q_plane, int32_t* __restrict__ nbr)
+{
+    using V = typename Vec16<F>::type;
+    constexpr int VN = Vec16<F>::N;
+    constexpr int TW = KnnBatchCfg<F>::TW, C = KNNB_C;
+    static_assert(BATCH_ITEM == 64 && NN_BLOCK == 4 * BATCH_ITEM && TW % C == 0 && C % VN == 0, "one query per lane, four waves per item");
+    __shared__ __attribute__((aligned(16))) F sq[4][3][TW];
+    __shared__ F ld[4][5][BATCH_ITEM];
+    __shared__ int lj[4][5][BATCH_ITEM];
+
+    const BatchItem it = items[blockIdx.x];
+    const BatchPair pr = pairs[it.pair];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool live = lane < it.count;
+    const int i = it.first + (live ? lane : 0);   // (lanes past the item's end repeat its first point: nothing of theirs is kept)
+    const F* Qx = Q + pr.q_off;
+    const F* Qy = Qx + q_plane;
+    const F* Qz = Qx + 2 * q_plane;
+    const F px = Qx[i], py = Qy[i], pz = Qz[i];
+    F bd[5];
+    int bj[5];
+#pragma unroll
+    for (int r = 0; r < 5; ++r) { bd[r] = inf_<F>(); bj[r] = 0; }
+
+    const int m = pr.m;
+    const int wseg = ((m + 3) / 4 + C - 1) / C * C;   // model points per wave, whole chunks
+    const int my0 = w * wseg, my1 = min(my0 + wseg, m);  // may be empty (my1 <= my0)
+    const int ntile = (wseg + TW - 1) / TW;           // the same for every wave: the barriers pair up
+    for (int k = 0; k < ntile; ++k) {
+        const int t0 = my0 + k * TW;
+        // (sq[w] is written and read by wave w alone; the two barriers are the block-level ordering between its lanes' LDS stores
+        // and the broadcast loads that follow -- ntile is uniform, so they pair up.  A tile is 512 / 256 model points per wave,
+        // ~1.5 k distance instructions between two barriers)
+        __syncthreads();
+        // this wave's sub-tile; places past the quarter's end hold +inf: such a distance is +inf or NaN and enters no list
+        for (int e = lane; e < TW; e += 64) {
+            const int j = t0 + e;
+            F qx = inf_<F>(), qy = inf_<F>(), qz = inf_<F>();
+            if (j < my1) { qx = Qx[j]; qy = Qy[j]; qz = Qz[j]; }
+            sq[w][0][e] = qx;
+            sq[w][1][e] = qy;
+            sq[w][2][e] = qz;
+        }
+        __syncthreads();
+        const int len = min(TW, my1 - t0);   // <= 0: this wave's quarter is exhausted
+        for (int c = 0; c < len; c += C) {
+            F dd[C];
+            F cmin = inf_<F>();
+#pragma unroll
+            for (int kk = 0; kk < C; kk += VN) {
+                const V qx = *reinterpret_cast<const V*>(&sq[w][0][c + kk]);
+                const V qy = *reinterpret_cast<const V*>(&sq[w][1][c + kk]);
+                const V qz = *reinterpret_cast<const V*>(&sq[w][2][c + kk]);
+#pragma unroll
+                for (int v = 0; v < VN; ++v) {
+                    dd[kk + v] = dist2<F>(px, py, pz, vget(qx, v), vget(qy, v), vget(qz, v));
+                    cmin = fmin_(cmin, dd[kk + v]);
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(cmin < bd[4]) == 0ull) continue;
+#pragma unroll
+            for (int kk = 0; kk < C; ++kk) {
+                const F d = dd[kk];
+                if (d < bd[4]) {
+                    // insert keeping (d, j) ascending; equal d keeps the earlier (lower) j first
+                    F cd = d;
+                    int cj = t0 + c + kk;
+                    bool shifting = false;
+#pragma unroll
+                    for (int r = 0; r < 5; ++r) {
+                        const bool sw = shifting || (cd < bd[r]);
+                        shifting = sw;
+                        const F td = bd[r];
+                        const int tj = bj[r];
+                        bd[r] = sw ? cd : td;
+                        bj[r] = sw ? cj : tj;
+                        cd = sw ? td : cd;
+                        cj = sw ? tj : cj;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+        ld[w][r][lane] = bd[r];
+        lj[w][r][lane] = bj[r];
+    }
+    __syncthreads();
+    if (w == 0 && live) {
+        // 4-way merge of sorted lists; on equal d the lower quarter (lower indices) goes first
+        int h[4] = {0, 0, 0, 0};
+        int out[5];
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            F best = inf_<F>();
+            int bw = 0;
+#pragma unroll
+            for (int ww = 3; ww >= 0; --ww) {
+                F d = inf_<F>();
+#pragma unroll
+                for (int s = 0; s < 5; ++s) d = (h[ww] == s) ? ld[ww][s][lane] : d;
+                if (d <= best) { best = d; bw = ww; }   // descending ww with <= : the lowest quarter wins ties
+            }
+            int hj = 0;
+#pragma unroll
+            for (int ww = 0; ww < 4; ++ww)
+#pragma unroll
+                for (int s = 0; s < 5; ++s) hj = (bw == ww && h[ww] == s) ? lj[ww][s][lane] : hj;
+            out[r] = (best < inf_<F>() && (unsigned)hj < (unsigned)m) ? hj : 0;   // (an empty slot, as knn4_kernel leaves it: in range)
+#pragma unroll
+            for (int ww = 0; ww < 4; ++ww) h[ww] += (ww == bw) ? 1 : 0;
+        }
+        int32_t* o = nbr + (size_t)(pr.q_off + i) * 4;
+#pragma unroll
+        for (int r = 1; r < 5; ++r) o[r - 1] = out[r];
+    }
+}
+
+// one lane per model point over all pairs: block = four work items of the model item list, one wave each
+template <typename F>
+__global__ __launch_bounds__(NN_BLOCK) void normals_batch_kernel(const BatchItem* __restrict__ items, int n_items,
+                                                                 const BatchPair* __restrict__ pairs, const F* __restrict__ Q,
+                                                                 long long q_plane, const int32_t* __restrict__ nbr,
+                                                                 F* __restrict__ Nrm)
+{
+    const int item = blockIdx.x * (NN_BLOCK / BATCH_ITEM) + (threadIdx.x >> 6);
+    if (item >= n_items) return;
+    const BatchItem it = items[item];
+    const int lane = threadIdx.x & 63;
+    if (lane >= it.count) return;
+    const BatchPair pr = pairs[it.pair];
+    const long long g = pr.q_off + it.first + lane;
+    const F* Qx = Q + pr.q_off;
+    double nx, ny, nz;
+    pca_normal<F>(Qx, Qx + q_plane, Qx + 2 * q_plane, nbr + (size_t)g * 4, nx, ny, nz);
+    Nrm[g] = (F)nx;
+    Nrm[q_plane + g] = (F)ny;
+    Nrm[2 * q_plane + g] = (F)nz;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -440,6 +611,25 @@ hipError_t launch_normals(int precision, const void* Q, int m, int m_pad, const 
     else
         hipLaunchKernelGGL((normals_kernel<float>), dim3(blocks), dim3(128), 0, st, (const float*)Q, m, m_pad, nbr,
                            (float*)Nrm_soa);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_normals(int precision, const BatchItem* q_items, int n_q_items, const BatchPair* pairs, const void* Q,
+                                long long q_plane, int32_t* nbr, void* Nrm_soa, hipStream_t st)
+{
+    if (n_q_items <= 0) return hipSuccess;
+    const int nb = (n_q_items + NN_BLOCK / BATCH_ITEM - 1) / (NN_BLOCK / BATCH_ITEM);
+    if (precision == ICP_F64)
+        hipLaunchKernelGGL((knn4_batch<double>), dim3(n_q_items), dim3(NN_BLOCK), 0, st, q_items, pairs, (const double*)Q, q_plane, nbr);
+    else
+        hipLaunchKernelGGL((knn4_batch<float>), dim3(n_q_items), dim3(NN_BLOCK), 0, st, q_items, pairs, (const float*)Q, q_plane, nbr);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    if (precision == ICP_F64)
+        hipLaunchKernelGGL((normals_batch_kernel<double>), dim3(nb), dim3(NN_BLOCK), 0, st, q_items, n_q_items, pairs, (const double*)Q,
+                           q_plane, (const int32_t*)nbr, (double*)Nrm_soa);
+    else
+        hipLaunchKernelGGL((normals_batch_kernel<float>), dim3(nb), dim3(NN_BLOCK), 0, st, q_items, n_q_items, pairs, (const float*)Q,
+                           q_plane, (const int32_t*)nbr, (float*)Nrm_soa);
     return hipGetLastError();
 }
 

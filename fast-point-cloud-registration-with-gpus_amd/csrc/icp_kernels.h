@@ -365,8 +365,9 @@ hipError_t launch_transform_error(int precision, void* P_soa, int n, int n_pad, 
 hipError_t launch_finalize(double* mom_out, const double* mom_partials, int mom_blocks, const double* err_partials,
                            int err_blocks, int rows_have_err /* slot 0 of the rows carries error shares */, hipStream_t st, double* scratch = nullptr /* >= 256 x ICP_NMOM doubles: many rows are added in two stages */);
 
-// batched point-to-point (icp_batch_*, icp_batch.cpp).  Every cloud of a batch starts at a multiple of BATCH_ALIGN elements in
-// its SoA plane (x at [off], y at [plane + off], z at [2 * plane + off]); the moving clouds' matches use the same offsets.
+// batched ICP (icp_batch_*, icp_batch.cpp).  Every cloud of a batch starts at a multiple of BATCH_ALIGN elements in
+// its SoA plane (x at [off], y at [plane + off], z at [2 * plane + off]); the moving clouds' matches use the same offsets, the
+// model normals (point-to-plane) the model's.
 // One work item = BATCH_ITEM moving points of one pair, cut from that pair's first point: one block of NN_BLOCK threads,
 // the four waves scanning four contiguous quarters of the pair's model for the same points.
 constexpr int BATCH_ITEM = 64;
@@ -375,10 +376,18 @@ constexpr int BATCH_APPLY = 1, BATCH_MATCH = 2;   // per-pair mode bits of one p
 struct BatchItem { int pair, first, count, pad_; };
 struct BatchPair { long long p_off, q_off; int n, m, item0, item1; };   // items [item0, item1) belong to the pair, in point order
 // pass over every item whose pair's mode is non-zero: [apply rt[pair] + error against idx_prev] -> [match -> idx_cur, moments]
-// -> partials[item][0..ICP_MOM_SQQ]; then mom[pair][ICP_NMOM] = that pair's items added in item order (pairs of mode 0 untouched)
-hipError_t launch_batch_pass(int precision, const BatchItem* items, int n_items, const BatchPair* pairs, int n_pairs, const int* mode,
-                             const void* rt /* RT<F>[n_pairs] */, void* P_soa, long long p_plane, const void* Q_soa, long long q_plane,
-                             const int32_t* idx_prev, int32_t* idx_cur, double* partials, double* mom, hipStream_t st);
+// -> partials[item][0..last slot of the metric]; then mom[pair][ICP_NMOM] = that pair's items added in item order (pairs of
+// mode 0 untouched).  metric ICP_POINT_TO_PLANE: N_soa = the model normals, laid out as Q_soa; the sums are moments_kernel's
+// plane terms (ICP_MOM_CNT, ICP_MOM_C .. ICP_MOM_B + 5).
+hipError_t launch_batch_pass(int precision, int metric, const BatchItem* items, int n_items, const BatchPair* pairs, int n_pairs,
+                             const int* mode, const void* rt /* RT<F>[n_pairs] */, void* P_soa, long long p_plane, const void* Q_soa,
+                             const void* N_soa, long long q_plane, const int32_t* idx_prev, int32_t* idx_cur, double* partials,
+                             double* mom, hipStream_t st);
+// the neighbours and normals of every pair's model: q_items = work items of BATCH_ITEM MODEL points (BatchItem::first / count
+// within the pair's model); one knn4_batch launch (nbr[(q_off + i) * 4 ..]: indices within the pair's model) + one
+// normals_batch_kernel launch (Nrm_soa laid out as Q_soa)
+hipError_t launch_batch_normals(int precision, const BatchItem* q_items, int n_q_items, const BatchPair* pairs, const void* Q_soa,
+                                long long q_plane, int32_t* nbr, void* Nrm_soa, hipStream_t st);
 
 // soa2 (optional): a second copy of the result (the pristine moving cloud); enc (optional, fp32): the cloud's bounding cube as six
 // ordered-integer words {~ord(min xyz), ord(max xyz)}, zero before the launch

@@ -252,7 +252,7 @@ class Context:
     def point_to_plane(self, D, M, normals=None, max_iter=50, tol=1e-6, fixed_iterations=False):
         return self._run(capi.ICP_POINT_TO_PLANE, D, M, normals, max_iter, tol, fixed_iterations)
 
-    # ---- batched point-to-point (icp_batch_*): many independent pairs, one launch per step ------------
+    # ---- batched ICP (icp_batch_*): many independent pairs, one launch per step -----------------------
     def batch(self, pairs):
         """a Batch of (D, M) pairs of one dtype, uploaded once (see Batch)"""
         return Batch(self, pairs)
@@ -260,9 +260,17 @@ class Context:
     def point_to_point_batch(self, pairs, max_iter=40, tol=1e-6, fixed_iterations=False):
         """point_to_point for every (D, M) of `pairs` (one dtype) in one batched registration; a list of Result in pair order,
         each exactly what point_to_point gives for that pair alone (extra["status"]: ICP_OK or the code that ended its loop)"""
+        return self._run_batch(capi.ICP_POINT_TO_POINT, pairs, None, max_iter, tol, fixed_iterations)
+
+    def point_to_plane_batch(self, pairs, normals=None, max_iter=50, tol=1e-6, fixed_iterations=False):
+        """point_to_plane for every (D, M) of `pairs` in one batched registration, as point_to_point_batch; normals: one (m, 3)
+        array per pair, or None (then estimated on the device: one neighbour launch + one normals launch for all pairs)"""
+        return self._run_batch(capi.ICP_POINT_TO_PLANE, pairs, normals, max_iter, tol, fixed_iterations)
+
+    def _run_batch(self, metric, pairs, normals, max_iter, tol, fixed_iterations):
         Ds, Ms, moff, qoff, dtype = _batch_arrays(pairs)
         count, cap = len(Ds), int(max_iter) + 1
-        prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(dtype), capi.ICP_POINT_TO_POINT)
+        prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(dtype), metric)
         T = np.zeros((count, 16))
         it, ps, st = (np.zeros(count, dtype=np.int32) for _ in range(3))
         err = np.zeros((count, cap))
@@ -270,11 +278,17 @@ class Context:
         moved = np.zeros((int(moff[-1]), 3), dtype=dtype)
         D, M = np.concatenate(Ds), np.concatenate(Ms)
         pi, pd, p64 = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int64)
-        rc = self._lib.icp_point_to_point_batch(self._h, count, D.ctypes.data, moff.ctypes.data_as(p64), M.ctypes.data, qoff.ctypes.data_as(p64),
-                                                C.byref(prm), T.ctypes.data_as(pd), it.ctypes.data_as(pi), ps.ctypes.data_as(pi),
-                                                err.ctypes.data_as(pd), idx.ctypes.data_as(C.POINTER(C.c_int32)), moved.ctypes.data,
-                                                st.ctypes.data_as(pi))
-        capi.check(rc, "icp_point_to_point_batch")
+        outs = (T.ctypes.data_as(pd), it.ctypes.data_as(pi), ps.ctypes.data_as(pi), err.ctypes.data_as(pd),
+                idx.ctypes.data_as(C.POINTER(C.c_int32)), moved.ctypes.data, st.ctypes.data_as(pi))
+        if metric == capi.ICP_POINT_TO_PLANE:
+            N = _batch_normals(normals, Ms, dtype) if normals is not None else None
+            rc = self._lib.icp_point_to_plane_batch(self._h, count, D.ctypes.data, moff.ctypes.data_as(p64), M.ctypes.data, qoff.ctypes.data_as(p64),
+                                                    N.ctypes.data if N is not None else None, C.byref(prm), *outs)
+            capi.check(rc, "icp_point_to_plane_batch")
+        else:
+            rc = self._lib.icp_point_to_point_batch(self._h, count, D.ctypes.data, moff.ctypes.data_as(p64), M.ctypes.data, qoff.ctypes.data_as(p64),
+                                                    C.byref(prm), *outs)
+            capi.check(rc, "icp_point_to_point_batch")
         return [Result(T=T[b].reshape(4, 4).copy(), iterations=int(it[b]), passes=int(ps[b]), err=err[b, : ps[b] + 1].copy(),
                        idx=idx[moff[b]:moff[b + 1]].copy(), moved=moved[moff[b]:moff[b + 1]].copy(), extra={"status": int(st[b])})
                 for b in range(count)]
@@ -379,14 +393,29 @@ def _batch_arrays(pairs):
     return Ds, Ms, moff, qoff, dtype
 
 
+def _batch_normals(normals, Ms, dtype):
+    """one (m, 3) array of normals per pair -> their concatenation in the models' layout"""
+    normals = list(normals)
+    if len(normals) != len(Ms):
+        raise ValueError("one array of normals per pair")
+    Ns = [_as_cloud(N, dtype) for N in normals]
+    for N, M in zip(Ns, Ms):
+        if N.shape != M.shape:
+            raise ValueError("a pair's normals must have the shape of its model")
+    return np.concatenate(Ns)
+
+
 class Batch:
     """icp_batch: (D, M) pairs of one dtype resident on the context's device; every step runs the pass of every pair still
-    running in one launch.  Each pair's loop is the one Context.point_to_point runs for it alone.  Outputs are split per pair."""
+    running in one launch.  Each pair's loop is the one Context.point_to_point (point_to_plane, with the batch's normals) runs
+    for it alone.  Outputs are split per pair."""
 
     def __init__(self, ctx, pairs):
         self._ctx = ctx   # (keeps the context alive: a batch must go before it)
         self._lib = ctx._lib
         Ds, Ms, self._moff, qoff, self._dtype = _batch_arrays(pairs)
+        self._qoff = qoff
+        self._model_shapes = [M.shape for M in Ms]
         self.count = len(Ds)
         D, M = np.concatenate(Ds), np.concatenate(Ms)
         h = C.c_void_p()
@@ -416,9 +445,32 @@ class Batch:
     def _split(self, flat):
         return [flat[self._moff[b]:self._moff[b + 1]].copy() for b in range(self.count)]
 
-    def begin(self, max_iter=40, tol=1e-6, fixed_iterations=False):
-        """start every pair's registration from the uploaded clouds"""
-        prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(self._dtype), capi.ICP_POINT_TO_POINT)
+    def set_model_normals(self, normals):
+        """the unit normals of every pair's model points (one (m, 3) array per pair): what a point-to-plane begin needs"""
+        normals = list(normals)
+        if len(normals) != self.count:
+            raise ValueError("one array of normals per pair")
+        Ns = [_as_cloud(N, self._dtype) for N in normals]
+        for N, shape in zip(Ns, self._model_shapes):
+            if N.shape != shape:
+                raise ValueError("a pair's normals must have the shape of its model")
+        N = np.concatenate(Ns)
+        capi.check(self._lib.icp_batch_set_model_normals(self._h, N.ctypes.data), "icp_batch_set_model_normals")
+
+    def estimate_normals(self, want_neighbours=False):
+        """kNN(4) + PCA normals of every pair's model on the device (one neighbour launch + one normals launch for all pairs);
+        a per-pair list of normals, and a per-pair list of (m, 4) neighbours (indices within that pair's model) when asked"""
+        total = int(self._qoff[-1])
+        nrm = np.empty((total, 3), dtype=self._dtype)
+        nbr = np.empty((total, 4), dtype=np.int32) if want_neighbours else None
+        capi.check(self._lib.icp_batch_estimate_normals(self._h, nrm.ctypes.data, nbr.ctypes.data_as(C.POINTER(C.c_int32)) if want_neighbours else None),
+                   "icp_batch_estimate_normals")
+        cut = lambda a: [a[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
+        return (cut(nrm), cut(nbr)) if want_neighbours else cut(nrm)
+
+    def begin(self, max_iter=40, tol=1e-6, fixed_iterations=False, metric=capi.ICP_POINT_TO_POINT):
+        """start every pair's registration from the uploaded clouds (ICP_POINT_TO_PLANE: the batch must hold normals)"""
+        prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(self._dtype), int(metric))
         capi.check(self._lib.icp_batch_begin(self._h, C.byref(prm)), "icp_batch_begin")
         self._max_iter = int(max_iter)
 

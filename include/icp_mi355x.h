@@ -203,29 +203,50 @@ int icp_loop_phase_seconds(icp_ctx* ctx, double* seconds_nn, double* seconds_hos
 /* correspondences of the last pass that contributed to T (ping-pong buffer), n int32 */
 int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
 
-/* ---- batched point-to-point: many independent small pairs, one launch of every pair's pass per step ----------------
- * The reference registers one pair per program run (src/ICP_point_to_point.cu:295-423); a loop of icp_point_to_point over
- * many small pairs pays a whole iteration's launch and round trip per pair.  A batch keeps all its pairs on the device and
+/* ---- batched ICP: many independent small pairs, one launch of every pair's pass per step -----------------------------
+ * The reference registers one pair per program run (src/ICP_point_to_point.cu:295-423, src/ICP_point_to_plane.cu:517-631); a
+ * loop of icp_point_to_point / icp_point_to_plane over many small pairs pays a whole iteration's launch and round trip (and,
+ * for point-to-plane, a neighbour search of its own) per pair.  A batch keeps all its pairs on the device and
  * runs ONE matching launch + ONE reduction launch + ONE 32-double-per-pair download per step for every pair still running.
  *   - pair b = moving points [moving_off[b], moving_off[b+1]) and model points [model_off[b], model_off[b+1]) of the
  *     concatenated AoS arrays, element type = precision (as icp_set_model).  Offsets: count+1 int64, starting at 0, strictly
  *     increasing (every cloud >= 1 point, <= ICP_BATCH_MAX_POINTS).  Anything else, a NaN or an infinite coordinate
- *     anywhere, count < 1 or a metric other than ICP_POINT_TO_POINT is refused with ICP_ERR_INVALID, and no batch is made.
- *   - each pair's loop is exactly what icp_point_to_point computes for that pair alone (same stop rule, iterations, passes,
+ *     anywhere or count < 1 is refused with ICP_ERR_INVALID, and no batch is made.
+ *   - each pair's loop is exactly what icp_point_to_point (icp_point_to_plane with the same normals) computes for that pair
+ *     alone (same stop rule, iterations, passes,
  *     err series, composed T, idx of the last contributing pass, final cloud), and a pair's bits do not depend on the other
  *     pairs of the batch or their order: work is cut relative to each pair's first point, partial sums are added per pair
  *     in a fixed order, there are no floating-point atomics.  Pairs finish independently; a numeric failure of one pair's
- *     minimisation ends that pair only (its status), the others go on.
+ *     minimisation ends that pair only (its status: ICP_ERR_SINGULAR where a pair's 6x6 point-to-plane system is not
+ *     positive definite), the others go on.
  *   - a batch uses the context's device and stream and nothing else of it (resident clouds, loop, counters stay as they
  *     were).  It must be destroyed before its context.  While the context has an enqueued pass that is not completed
  *     (icp_loop_enqueue without icp_loop_complete) the batch calls return ICP_ERR_STATE.
- *   - icp_batch_begin starts every pair's registration from the clouds icp_batch_create uploaded. */
+ *   - icp_batch_begin starts every pair's registration from the clouds icp_batch_create uploaded.
+ *   - point-to-plane needs the unit normals of every pair's model points.  The batch holds one set: the caller's
+ *     (icp_batch_set_model_normals) or the one icp_batch_estimate_normals makes on the device -- kNN(4) + PCA exactly as
+ *     icp_estimate_normals does for one model (src/CUDA/GPU_point_to_plane_real.cu:54-188,391-423), with ONE neighbour launch
+ *     and ONE normals launch for all pairs; every pair's neighbours and normals are those of icp_estimate_normals on that
+ *     model alone, bit for bit.  Either call may come at any time after icp_batch_create and replaces the set; a loop under
+ *     way is discarded (icp_batch_run returns ICP_ERR_STATE until the next icp_batch_begin).  A refused call leaves the batch's
+ *     normals as they were (none, or the previous set).  icp_batch_begin accepts ICP_POINT_TO_PLANE only on a batch that holds
+ *     normals (else ICP_ERR_INVALID); a batch that holds normals still begins ICP_POINT_TO_POINT, with the bits of one that
+ *     holds none. */
 typedef struct icp_batch icp_batch;
 #define ICP_BATCH_MAX_POINTS 65536 /* per cloud of one pair */
 int icp_batch_create(icp_ctx* ctx, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
                      const int64_t* model_off, int precision, icp_batch** out);
 void icp_batch_destroy(icp_batch* b);
-int icp_batch_begin(icp_batch* b, const icp_params* prm); /* prm->metric must be ICP_POINT_TO_POINT, prm->precision the batch's */
+/* unit normals of every pair's model points, concatenated exactly as model_aos was (model_off layout), element type = the
+ * batch's precision.  NULL, a NaN or an infinite component anywhere: ICP_ERR_INVALID */
+int icp_batch_set_model_normals(icp_batch* b, const void* nxyz_aos);
+/* kNN(4) + PCA normals of every pair's model on the device: one neighbour launch + one normals launch for the whole batch.
+ * nxyz_aos_out (3 per model point) and neighbours_out (4 per model point, indices WITHIN that pair's model) may be NULL.
+ * A pair's model of fewer than 5 points (k = 4 neighbours + self, as icp_estimate_normals): ICP_ERR_INVALID, the message
+ * names the pair */
+int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighbours_out);
+/* prm->precision must be the batch's; prm->metric ICP_POINT_TO_POINT, or ICP_POINT_TO_PLANE on a batch that holds normals */
+int icp_batch_begin(icp_batch* b, const icp_params* prm);
 /* up to max_steps passes for every pair still running; *active (optional) = pairs not yet done */
 int icp_batch_run(icp_batch* b, int max_steps, int* steps_done, int* active);
 /* per pair: status = ICP_OK or the rc that ended this pair's loop; the rest as icp_loop_state */
@@ -238,10 +259,14 @@ int icp_batch_loop_indices(icp_batch* b, int32_t* idx_out); /* each pair's last 
 /* one call: create + begin + run to the end + results, then destroy.  Every output pointer may be NULL; per pair:
  * T16_out 16, iterations_out / passes_out / status_out 1, err_out max_iter+1 doubles; idx_out and moved_out (3 values per
  * point, precision of the run) concatenated as the moving clouds.  A failed pair is reported in status_out, not in the
- * return code. */
+ * return code.  prm->metric must be ICP_POINT_TO_POINT. */
 int icp_point_to_point_batch(icp_ctx* ctx, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
                              const int64_t* model_off, const icp_params* prm, double* T16_out, int* iterations_out,
                              int* passes_out, double* err_out, int32_t* idx_out, void* moved_out, int* status_out);
+/* as icp_point_to_point_batch; normals_aos may be NULL (then estimated on the device); prm->metric must be ICP_POINT_TO_PLANE */
+int icp_point_to_plane_batch(icp_ctx* ctx, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
+                             const int64_t* model_off, const void* normals_aos, const icp_params* prm, double* T16_out,
+                             int* iterations_out, int* passes_out, double* err_out, int32_t* idx_out, void* moved_out, int* status_out);
 
 /* ---- multi-GPU: the loop's single collective issued by the library (RCCL over xGMI, bound at run time) ----
  * One process per GPU.  Rank 0 obtains an id (icp_comm_unique_id), the host application distributes those

@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
-"""Pair-iterations per second of the batched point-to-point loop (Context.point_to_point_batch, one launch per step for all
-pairs) against a loop of Context.point_to_point over the same pairs (GPU box).
+"""Pair-iterations per second of the batched loops (Context.point_to_point_batch / point_to_plane_batch, one launch per step
+for all pairs) against a loop of Context.point_to_point / point_to_plane over the same pairs (GPU box).
 
-  python3 tools/batch_time.py [--reps 5] [--out FILE]
+  python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE]
 
-Cases: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids (make_model_gpu, tol 1e-6);
-16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  Both sides are timed end to end (upload included) with a host clock
+Cases, --metric point: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids
+(make_model_gpu, tol 1e-6); 16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  --metric plane: the fp32 case sets and the
+64 grids in fp64 (max_iter 50, tol 1e-6), each once with the caller's normals (the oracle's, computed outside the timed region)
+and once with normals estimated on the device (the batch: one neighbour launch + one normals launch for all pairs; the
+sequential loop: icp_estimate_normals per pair).  Both sides are timed end to end (upload included) with a host clock
 around calls that end in a device synchronisation; a pair-iteration is one matching pass of one pair (Result.passes).  The
-sequential side also reports its loops alone (Result.seconds_total, the registration without the upload).  Median of --reps
-after one warm-up of every case.
+sequential side also reports its loops alone (Result.seconds_total, the registration without the upload and the normals).
+Median of --reps after one warm-up of every case.  Every pair must run the same passes on both sides: the rows carry the number of
+pairs that did not (pairs_stopping_apart), and the tool exits non-zero if there is one.
 """
 import argparse
 import json
@@ -21,6 +25,26 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def plane_cases(pkg, orc):
+    """(name, pairs, normals or None, max_iter, tol)"""
+    ds = pkg.datasets
+    G = ds.synthetic_grid(32, np.float32)
+    Gm = ds.make_model_gpu(G, *ds.P2P_GPU)
+    B = np.fromfile(os.path.join(ROOT, "tests", "golden", "bunny_res_xyz_f32.bin"), dtype=np.float32).reshape(-1, 3)
+    rng = np.random.default_rng(5)
+    bunny = [(B, ds.make_model_gpu(B, tuple(np.asarray(ds.BUNNY[0]) + rng.uniform(-0.05, 0.05, 3)), ds.BUNNY[1])) for _ in range(16)]
+    nrm = lambda M: orc.normals(M, orc.knn4(M))[0]
+    Gn = nrm(Gm)
+    sets = [("grid1024_fp32_x64", [(G, Gm)] * 64, [Gn] * 64),
+            ("grid1024_fp64_x64", [(G.astype(np.float64), Gm.astype(np.float64))] * 64, [Gn.astype(np.float64)] * 64),
+            ("bunny_res_fp32_x16", bunny, [nrm(M) for _, M in bunny])]
+    out = []
+    for name, pairs, normals in sets:
+        out.append((name + "_plane_given", pairs, normals, 50, 1e-6))
+        out.append((name + "_plane_estimated", pairs, None, 50, 1e-6))
+    return out
 
 
 def cases(pkg, orc):
@@ -42,6 +66,7 @@ def cases(pkg, orc):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--metric", choices=("point", "plane"), default="point")
     ap.add_argument("--out", default="")
     ap.add_argument("--profile-case", default="", help="run only this case's batched registration, once after a warm-up (for a kernel trace)")
     a = ap.parse_args()
@@ -52,24 +77,37 @@ def main():
     orc = oracle_lib.Oracle()
     rows = []
     with pkg.Context(0) as ctx:
-        for name, pairs, it, tol in cases(pkg, orc):
+        plane = a.metric == "plane"
+        todo = plane_cases(pkg, orc) if plane else [(name, pairs, None, it, tol) for name, pairs, it, tol in cases(pkg, orc)]
+        for name, pairs, normals, it, tol in todo:
+            def run_batched():
+                if plane:
+                    return ctx.point_to_plane_batch(pairs, normals=normals, max_iter=it, tol=tol)
+                return ctx.point_to_point_batch(pairs, max_iter=it, tol=tol)
+
+            def run_sequential():
+                if plane:
+                    return [ctx.point_to_plane(D, M, normals=None if normals is None else normals[k], max_iter=it, tol=tol)
+                            for k, (D, M) in enumerate(pairs)]
+                return [ctx.point_to_point(D, M, max_iter=it, tol=tol) for D, M in pairs]
+
             if a.profile_case:
                 if name == a.profile_case:
                     for _ in range(2):
-                        res = ctx.point_to_point_batch(pairs, max_iter=it, tol=tol)
+                        res = run_batched()
                     print(json.dumps(dict(case=name, pairs=len(pairs), pair_iterations=sum(r.passes for r in res),
                                           steps=max(r.passes for r in res) + 1)), flush=True)
                 continue
 
             def batched():
                 t0 = time.perf_counter()
-                res = ctx.point_to_point_batch(pairs, max_iter=it, tol=tol)
-                return time.perf_counter() - t0, sum(r.passes for r in res), None
+                res = run_batched()
+                return time.perf_counter() - t0, [r.passes for r in res], None
 
             def sequential():
                 t0 = time.perf_counter()
-                res = [ctx.point_to_point(D, M, max_iter=it, tol=tol) for D, M in pairs]
-                return time.perf_counter() - t0, sum(r.passes for r in res), sum(r.seconds_total for r in res)
+                res = run_sequential()
+                return time.perf_counter() - t0, [r.passes for r in res], sum(r.seconds_total for r in res)
 
             batched()
             sequential()
@@ -80,19 +118,24 @@ def main():
                 s, ps, loops = sequential()
                 ts.append(s)
                 tl.append(loops)
-            assert pb == ps, (name, pb, ps)   # the same registrations
+            # the same registrations: every pair must run the same passes on both sides (checked when all rows are out)
+            apart = sum(1 for x, y in zip(pb, ps) if x != y)
+            pb, ps = sum(pb), sum(ps)
             mb, ms, ml = float(np.median(tb)), float(np.median(ts)), float(np.median(tl))
-            row = dict(case=name, pairs=len(pairs), points=int(pairs[0][0].shape[0]), pair_iterations=pb,
+            row = dict(case=name, pairs=len(pairs), points=int(pairs[0][0].shape[0]), pair_iterations=pb, sequential_pair_iterations=ps, pairs_stopping_apart=apart,
                        batched_s=mb, sequential_s=ms, sequential_loops_s=ml,
-                       batched_pair_it_per_s=pb / mb, sequential_pair_it_per_s=pb / ms,
-                       batched_us_per_pair_it=1e6 * mb / pb, sequential_us_per_pair_it=1e6 * ms / pb,
-                       sequential_loops_us_per_pair_it=1e6 * ml / pb, speedup=ms / mb, speedup_vs_loops=ml / mb)
+                       batched_pair_it_per_s=pb / mb, sequential_pair_it_per_s=ps / ms,
+                       batched_us_per_pair_it=1e6 * mb / pb, sequential_us_per_pair_it=1e6 * ms / ps,
+                       sequential_loops_us_per_pair_it=1e6 * ml / ps, speedup=ms / mb, speedup_vs_loops=ml / mb)
             rows.append(row)
             print(json.dumps(row), flush=True)
     if a.out:
         with open(a.out, "w") as f:
             for r in rows:
                 f.write(json.dumps(r) + "\n")
+    bad = [r["case"] for r in rows if r["pairs_stopping_apart"]]
+    if bad:
+        sys.exit(f"batched and sequential registrations ran different passes in: {bad}")
 
 
 if __name__ == "__main__":
