@@ -49,7 +49,7 @@ const char* icp_strerror(int code)
         case ICP_ERR_INVALID: return "invalid argument";
         case ICP_ERR_NO_DEVICE: return "no usable gfx950 HIP device (there is no CPU fallback)";
         case ICP_ERR_HIP: return "HIP runtime error";
-        case ICP_ERR_EMPTY: return "empty model cloud";
+        case ICP_ERR_EMPTY: return "no model point, or no correspondence within the maximum distance";
         case ICP_ERR_SINGULAR: return "point-to-plane system is not positive definite";
         case ICP_ERR_IO: return "dataset file missing or malformed";
         case ICP_ERR_STATE: return "call sequence error";

@@ -5,6 +5,11 @@
 //            ->  batch_finalize_kernel (per pair, fixed order)  ->  D2H count x ICP_NMOM  ->  sync
 //            ->  HostLoop::advance per pair that took part (error, stop rule, 3x3 solve or 6x6 solve)
 //
+// A batch may hold a maximum correspondence distance per pair (icp_batch_set_max_distance).  Its passes then run the gated
+// instantiations of nn_match_batch: a match farther than that enters no sum, the point's idx entry carries the rejection in
+// its top bit for the next pass's error (and for the mask downloads), and a pass that keeps nothing ends its pair with
+// ICP_ERR_EMPTY.  Launches and downloads per step stay as above; a batch without thresholds runs the ungated kernels.
+//
 // Point-to-plane needs the model normals of every pair, in planes laid out as the models: given by the caller
 // (icp_batch_set_model_normals) or made on the device by ONE neighbour launch + ONE normals launch for the whole batch
 // (icp_batch_estimate_normals: knn4_batch + normals_batch_kernel, icp_k_plane.hip).  The reference estimates them once per
@@ -39,6 +44,8 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     DevBuf N, q_items, nbr;                  // point-to-plane: the model normals (planes as Q), the model's work items, 4 neighbours per model point
     int n_q_items = 0;
     bool have_normals = false;
+    DevBuf thr;                              // the gate: every pair's squared maximum correspondence distance, in the batch's precision
+    bool gated = false;                      // the batch holds thresholds (icp_batch_set_max_distance): the passes run the gated kernels
     int metric = ICP_POINT_TO_POINT;         // of the loop under way
     void* h_ctl = nullptr;                   // pinned: R, t of every pair (12 values of the precision), then its mode (int)
     double* h_mom = nullptr;                 // pinned: count x ICP_NMOM
@@ -74,7 +81,7 @@ int ready(icp_batch* b)
 
 void release(icp_batch* b)
 {
-    for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr})
+    for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr})
         d->release();
     if (b->h_ctl) (void)hipHostFree(b->h_ctl);
     if (b->h_mom) (void)hipHostFree(b->h_mom);
@@ -208,7 +215,8 @@ int step(icp_batch* b)
     HIP_TRY(icp::launch_batch_pass(b->prec, b->metric, (const icp::BatchItem*)b->items.p, b->n_items, (const icp::BatchPair*)b->pairs_d.p,
                                    b->count, (const int*)(static_cast<char*>(b->ctl.p) + b->rt_bytes), b->ctl.p, b->P.p, b->p_plane, b->Q.p,
                                    b->metric == ICP_POINT_TO_PLANE ? b->N.p : nullptr, b->q_plane, (const int32_t*)b->idx[cur ^ 1].p,
-                                   (int32_t*)b->idx[cur].p, (double*)b->partials.p, (double*)b->mom.p, c->stream));
+                                   (int32_t*)b->idx[cur].p, (double*)b->partials.p, (double*)b->mom.p, b->gated ? b->thr.p : nullptr,
+                                   c->stream));
     HIP_TRY(hipMemcpyAsync(b->h_mom, b->mom.p, (size_t)b->count * ICP_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     b->steps += 1;
@@ -225,10 +233,11 @@ int step(icp_batch* b)
 }
 
 // the buffer each pair's indices are read from: its most recent matching pass, or the pass whose motion it applied last
-int download_indices(icp_batch* b, bool contributing, int32_t* out)
+// (out: the indices; mask: 1 where that pass kept the point's match -- one of the two)
+int download_indices(icp_batch* b, bool contributing, int32_t* out, uint8_t* mask = nullptr)
 {
     if (int rc = ready(b)) return rc;
-    if (!out) return fail(ICP_ERR_INVALID, "idx_out == NULL");
+    if (!out && !mask) return fail(ICP_ERR_INVALID, "output pointer == NULL");
     if (!b->begun || b->steps == 0) return fail(ICP_ERR_STATE, "no matching pass since icp_batch_begin");
     std::vector<int32_t> h[2];
     for (int k = 0; k < 2; ++k) {
@@ -238,7 +247,11 @@ int download_indices(icp_batch* b, bool contributing, int32_t* out)
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
     for (int p = 0; p < b->count; ++p) {
         const int which = contributing && b->H[p].applied > 0 ? b->applied_buf[p] : b->last_match[p];
-        std::memcpy(out + b->moff[p], h[which].data() + b->pairs[p].p_off, (size_t)b->pairs[p].n * sizeof(int32_t));
+        const int32_t* src = h[which].data() + b->pairs[p].p_off;
+        for (int i = 0; i < b->pairs[p].n; ++i) {   // (a gated pass marks its rejected matches above the index: see BATCH_IDX_REJECTED)
+            if (out) out[b->moff[p] + i] = src[i] & icp::BATCH_IDX_MASK;
+            if (mask) mask[b->moff[p] + i] = src[i] >= 0 ? 1 : 0;
+        }
     }
     return ICP_OK;
 }
@@ -327,6 +340,7 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
     b->metric = prm->metric;
     for (int p = 0; p < b->count; ++p)
         if (int rc = b->H[p].begin(*prm)) return fail(rc, "bad loop parameters");
+    for (int p = 0; p < b->count; ++p) b->H[p].gated = b->gated;
     b->status.assign((size_t)b->count, ICP_OK);
     b->last_match.assign((size_t)b->count, 0);
     b->applied_buf.assign((size_t)b->count, 0);
@@ -408,6 +422,43 @@ int icp_batch_get_moving(icp_batch* b, void* aos_out)
 int icp_batch_get_indices(icp_batch* b, int32_t* idx_out) { return download_indices(b, false, idx_out); }
 
 int icp_batch_loop_indices(icp_batch* b, int32_t* idx_out) { return download_indices(b, true, idx_out); }
+
+int icp_batch_get_inliers(icp_batch* b, uint8_t* mask_out)
+{
+    return download_indices(b, false, nullptr, mask_out);
+}
+
+int icp_batch_loop_inliers(icp_batch* b, uint8_t* mask_out)
+{
+    return download_indices(b, true, nullptr, mask_out);
+}
+
+int icp_batch_set_max_distance(icp_batch* b, const double* max_dist)
+{
+    if (int rc = ready(b)) return rc;
+    if (max_dist) {
+        for (int p = 0; p < b->count; ++p)   // (NaN fails the comparison too; -inf is <= 0)
+            if (!(max_dist[p] > 0))
+                return fail(ICP_ERR_INVALID, "the maximum correspondence distance must be > 0 or +INFINITY: pair " + std::to_string(p));
+        // thr = (F)(max_dist^2): the product in double, rounded once to the batch's precision
+        std::vector<char> h((size_t)b->count * b->esize);
+        for (int p = 0; p < b->count; ++p) {
+            const double sq = max_dist[p] * max_dist[p];
+            if (b->prec == ICP_F64) reinterpret_cast<double*>(h.data())[p] = sq;
+            else reinterpret_cast<float*>(h.data())[p] = (float)sq;
+        }
+        HIP_TRY(b->thr.ensure(h.size()));
+        b->begun = false;   // a loop under way is discarded: its passes so far used other thresholds (or none)
+        b->gated = false;
+        HIP_TRY(hipMemcpyAsync(b->thr.p, h.data(), h.size(), hipMemcpyHostToDevice, b->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
+        b->gated = true;
+    } else {
+        b->begun = false;
+        b->gated = false;
+    }
+    return ICP_OK;
+}
 
 int icp_batch_set_model_normals(icp_batch* b, const void* nxyz_aos)
 {

@@ -45,12 +45,16 @@ void HostLoop::note_applied()
 int HostLoop::advance(const double* mom)
 {
     if (done) return ICP_ERR_STATE;
+    // the error of this vector measures the matches the PREVIOUS vector delivered: its divisor is their count.  (A gated
+    // batch keeps another number of points in every pass; where the count never changes, or no earlier vector carried
+    // one, this is the current count.)
+    const double n_err = n_total > 0 ? n_total : mom[ICP_MOM_CNT];
     if (mom[ICP_MOM_CNT] > 0) n_total = mom[ICP_MOM_CNT];
     const int k = applied;
     if (k >= 1) {
-        if (!(n_total > 0)) return ICP_ERR_INVALID;
+        if (!(n_err > 0)) return ICP_ERR_INVALID;
         // E[k] = || q[idx_{k-1}] - p_k ||_2 / sqrt(N)   (src/ICP_CPU.c:266)
-        err[k] = std::sqrt(mom[ICP_MOM_ERR]) / std::sqrt(n_total);
+        err[k] = std::sqrt(mom[ICP_MOM_ERR]) / std::sqrt(n_err);
         const bool stop = !prm.fixed_iterations && ((err[k] < prm.tol) || (std::fabs(err[k] - err[k - 1]) < prm.tol));
         if (stop) {
             iterations = k - 1;  // break before the counter is incremented (src/ICP_CPU.c:267)
@@ -59,6 +63,10 @@ int HostLoop::advance(const double* mom)
             iterations = k;
             if (k > prm.max_iter - 1) done = true;  // src/ICP_CPU.c:268-269
         }
+    }
+    if (!done && gated && !(mom[ICP_MOM_CNT] > 0)) {   // the loop goes on, so this pass matched -- and kept no point
+        done = true;
+        return ICP_ERR_EMPTY;
     }
     if (!done) {
         const int rc = prm.metric == ICP_POINT_TO_PLANE ? solve_point_to_plane(mom, R, t, nullptr)

@@ -14,7 +14,8 @@ struct HostLoop {
     int iterations = 0;   // the reference's loop counter at exit
     bool done = false;
     bool have_rt = false; // R, t of the last advance() wait to be applied
-    double n_total = 0.0; // moving points that contributed (summed over ranks)
+    double n_total = 0.0; // moving points that contributed to the latest matching pass (summed over ranks)
+    bool gated = false;   // set after begin(): a matching pass may keep no point, which ends the loop with ICP_ERR_EMPTY
     double R[9], t[3], T[16];
     std::vector<double> err;
 
@@ -24,8 +25,9 @@ struct HostLoop {
     void note_applied();
     // true when the pass that is about to be enqueued is the last one whatever its error turns out to be
     bool next_is_final() const { return applied + (have_rt ? 1 : 0) >= prm.max_iter; }
-    // feed the (rank-reduced) moment vector of the enqueue that followed note_applied(): E[k], the stop
-    // rule of src/ICP_CPU.c:267-269, and -- unless the loop ended -- the next R, t.
+    // feed the (rank-reduced) moment vector of the enqueue that followed note_applied(): E[k] (ICP_MOM_ERR over
+    // the count of the vector before it, whose matches it measures), the stop rule of src/ICP_CPU.c:267-269,
+    // and -- unless the loop ended -- the next R, t.
     int advance(const double* mom);
 };
 

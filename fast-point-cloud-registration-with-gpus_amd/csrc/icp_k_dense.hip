@@ -863,6 +863,11 @@ hipError_t launch_dense_v2(const NNPlan& pl, const void* P, const void* Qscan, v
 //     n[idx] too, from the normal planes laid out as the model's, and forms moments_kernel's plane terms statement for
 //     statement -- cn = (p x n, n), bi = (p - q) . n, C += cn cn^T, b -= cn bi -- into slots ICP_MOM_CNT, ICP_MOM_C ..
 //     ICP_MOM_B + 5.  The front end and the error-only last pass are the same code.
+//   GATE (its own instantiations: the ungated ones have no branch on it and never read thr): wave 0 keeps the match only if
+//     the merged minimum b -- the dist2<F> the scan already holds, nothing recomputed -- is <= thr[pair], the pair's squared
+//     maximum correspondence distance in F (+inf: not gated).  A rejected point leaves every accumulator 0, ICP_MOM_CNT
+//     included, and its idx entry carries BATCH_IDX_REJECTED above the nearest neighbour's index; the next pass's front end
+//     reads that entry anyway (idx_prev) and adds the point's error only if the bit is clear.  Downloads strip the bit.
 // A pair's blocks, their geometry and every sum depend on that pair alone (no atomics): its bits do not depend on the batch.
 // ------------------------------------------------------------------------------------------------
 template <typename F> struct BatchCfg;
@@ -870,13 +875,13 @@ template <> struct BatchCfg<float> { static constexpr int TW = 512; };    // mod
 template <> struct BatchCfg<double> { static constexpr int TW = 256; };
 static_assert(sizeof(RT<float>) == 12 * sizeof(float) && sizeof(RT<double>) == 12 * sizeof(double), "the host writes R, t as 12 values per pair");
 
-template <typename F, int METRIC>
+template <typename F, int METRIC, bool GATE>
 __global__ __launch_bounds__(NN_BLOCK) void nn_match_batch(const BatchItem* __restrict__ items, const BatchPair* __restrict__ pairs,
                                                            const int* __restrict__ mode, const RT<F>* __restrict__ rts,
                                                            F* __restrict__ P, long long p_plane, const F* __restrict__ Q,
                                                            const F* __restrict__ Nrm, long long q_plane,
                                                            const int32_t* __restrict__ idx_prev, int32_t* __restrict__ idx_cur,
-                                                           double* __restrict__ partials)
+                                                           double* __restrict__ partials, const F* __restrict__ thr)
 {
     using V = typename Vec16<F>::type;
     constexpr int VN = Vec16<F>::N;
@@ -912,11 +917,12 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_match_batch(const BatchItem* __re
             P[gi] = x;
             P[p_plane + gi] = y;
             P[2 * p_plane + gi] = z;
-            const int j = idx_prev[gi];
+            const int jr = idx_prev[gi];
+            const int j = GATE ? (jr & BATCH_IDX_MASK) : jr;
             const double dx = (double)Qx[j] - (double)x;
             const double dy = (double)Qy[j] - (double)y;
             const double dz = (double)Qz[j] - (double)z;
-            acc[ICP_MOM_ERR] = dx * dx + dy * dy + dz * dz;
+            if (!GATE || jr >= 0) acc[ICP_MOM_ERR] = dx * dx + dy * dy + dz * dz;   // (only a point kept by that matching pass)
         }
     }
 
@@ -976,11 +982,14 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_match_batch(const BatchItem* __re
             for (int ww = 1; ww < 4; ++ww)
                 if (md[ww][lane] < b) { b = md[ww][lane]; j = mi[ww][lane]; }
             j = ((unsigned)j < (unsigned)m) ? j : 0;   // (nothing found only if every distance overflowed: idx stays in range)
-            idx_cur[gi] = j;
+            const bool kept = !GATE || b <= thr[it.pair];
+            idx_cur[gi] = kept ? j : (j | BATCH_IDX_REJECTED);
             const double px = (double)x, py = (double)y, pz = (double)z;
             const double qx = (double)Qx[j], qy = (double)Qy[j], qz = (double)Qz[j];
-            acc[ICP_MOM_CNT] = 1.0;
-            if constexpr (METRIC == ICP_POINT_TO_POINT) {
+            if (!kept) {
+                // (a rejected point adds nothing: every accumulator stays 0, the count included)
+            } else if constexpr (METRIC == ICP_POINT_TO_POINT) {
+                acc[ICP_MOM_CNT] = 1.0;
                 acc[ICP_MOM_SP + 0] = px; acc[ICP_MOM_SP + 1] = py; acc[ICP_MOM_SP + 2] = pz;
                 acc[ICP_MOM_SQ + 0] = qx; acc[ICP_MOM_SQ + 1] = qy; acc[ICP_MOM_SQ + 2] = qz;
                 acc[ICP_MOM_SQP + 0] = qx * px; acc[ICP_MOM_SQP + 1] = qx * py; acc[ICP_MOM_SQP + 2] = qx * pz;
@@ -989,6 +998,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_match_batch(const BatchItem* __re
                 acc[ICP_MOM_SPP] = px * px + py * py + pz * pz;
                 acc[ICP_MOM_SQQ] = qx * qx + qy * qy + qz * qz;
             } else {
+                acc[ICP_MOM_CNT] = 1.0;
                 const F* Nx = Nrm + pr.q_off;
                 const double nx = (double)Nx[j], ny = (double)Nx[q_plane + j], nz = (double)Nx[2 * q_plane + j];
                 double cn[6];
@@ -1036,19 +1046,25 @@ __global__ __launch_bounds__(256) void batch_finalize_kernel(const BatchPair* __
 
 hipError_t launch_batch_pass(int precision, int metric, const BatchItem* items, int n_items, const BatchPair* pairs, int n_pairs,
                              const int* mode, const void* rt, void* P, long long p_plane, const void* Q, const void* Nrm,
-                             long long q_plane, const int32_t* idx_prev, int32_t* idx_cur, double* partials, double* mom, hipStream_t st)
+                             long long q_plane, const int32_t* idx_prev, int32_t* idx_cur, double* partials, double* mom,
+                             const void* thr, hipStream_t st)
 {
     if (n_items <= 0 || n_pairs <= 0) return hipSuccess;
     const bool plane = metric == ICP_POINT_TO_PLANE;
     if (plane && !Nrm) return hipErrorInvalidValue;
-#define ICP_LAUNCH_BATCH(F, MET)                                                                                                  \
-    hipLaunchKernelGGL((nn_match_batch<F, MET>), dim3(n_items), dim3(NN_BLOCK), 0, st, items, pairs, mode, (const RT<F>*)rt, (F*)P, \
-                       p_plane, (const F*)Q, (const F*)Nrm, q_plane, idx_prev, idx_cur, partials)
-    if (precision == ICP_F64) {
-        if (plane) ICP_LAUNCH_BATCH(double, ICP_POINT_TO_PLANE); else ICP_LAUNCH_BATCH(double, ICP_POINT_TO_POINT);
-    } else {
-        if (plane) ICP_LAUNCH_BATCH(float, ICP_POINT_TO_PLANE); else ICP_LAUNCH_BATCH(float, ICP_POINT_TO_POINT);
-    }
+#define ICP_LAUNCH_BATCH(F, MET, GATE)                                                                                             \
+    hipLaunchKernelGGL((nn_match_batch<F, MET, GATE>), dim3(n_items), dim3(NN_BLOCK), 0, st, items, pairs, mode, (const RT<F>*)rt, \
+                       (F*)P, p_plane, (const F*)Q, (const F*)Nrm, q_plane, idx_prev, idx_cur, partials, (const F*)thr)
+#define ICP_LAUNCH_BATCH_F(F)                                                                                                  \
+    do {                                                                                                                       \
+        if (thr) {                                                                                                             \
+            if (plane) ICP_LAUNCH_BATCH(F, ICP_POINT_TO_PLANE, true); else ICP_LAUNCH_BATCH(F, ICP_POINT_TO_POINT, true);      \
+        } else {                                                                                                               \
+            if (plane) ICP_LAUNCH_BATCH(F, ICP_POINT_TO_PLANE, false); else ICP_LAUNCH_BATCH(F, ICP_POINT_TO_POINT, false);    \
+        }                                                                                                                      \
+    } while (0)
+    if (precision == ICP_F64) ICP_LAUNCH_BATCH_F(double); else ICP_LAUNCH_BATCH_F(float);
+#undef ICP_LAUNCH_BATCH_F
 #undef ICP_LAUNCH_BATCH
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     hipLaunchKernelGGL(batch_finalize_kernel, dim3(n_pairs), dim3(256), 0, st, pairs, mode, (const double*)partials,

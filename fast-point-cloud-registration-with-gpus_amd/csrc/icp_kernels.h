@@ -375,14 +375,19 @@ constexpr int BATCH_ALIGN = 64;
 constexpr int BATCH_APPLY = 1, BATCH_MATCH = 2;   // per-pair mode bits of one pass (0: the pair is not part of it)
 struct BatchItem { int pair, first, count, pad_; };
 struct BatchPair { long long p_off, q_off; int n, m, item0, item1; };   // items [item0, item1) belong to the pair, in point order
+// a gated pass marks a match it rejected in the top bit of the point's device-side idx entry (indices stay below
+// ICP_BATCH_MAX_POINTS); an ungated pass never sets it, so a clear bit reads "kept" whichever pass wrote the entry
+constexpr int32_t BATCH_IDX_REJECTED = INT32_MIN, BATCH_IDX_MASK = INT32_MAX;
 // pass over every item whose pair's mode is non-zero: [apply rt[pair] + error against idx_prev] -> [match -> idx_cur, moments]
 // -> partials[item][0..last slot of the metric]; then mom[pair][ICP_NMOM] = that pair's items added in item order (pairs of
 // mode 0 untouched).  metric ICP_POINT_TO_PLANE: N_soa = the model normals, laid out as Q_soa; the sums are moments_kernel's
-// plane terms (ICP_MOM_CNT, ICP_MOM_C .. ICP_MOM_B + 5).
+// plane terms (ICP_MOM_CNT, ICP_MOM_C .. ICP_MOM_B + 5).  thr: NULL (the ungated instantiations), or F[n_pairs], every pair's
+// squared maximum correspondence distance (+inf: that pair is not gated): only matches with d <= thr[pair] enter the sums, and
+// the error counts only the points idx_prev marks as kept.
 hipError_t launch_batch_pass(int precision, int metric, const BatchItem* items, int n_items, const BatchPair* pairs, int n_pairs,
                              const int* mode, const void* rt /* RT<F>[n_pairs] */, void* P_soa, long long p_plane, const void* Q_soa,
                              const void* N_soa, long long q_plane, const int32_t* idx_prev, int32_t* idx_cur, double* partials,
-                             double* mom, hipStream_t st);
+                             double* mom, const void* thr, hipStream_t st);
 // the neighbours and normals of every pair's model: q_items = work items of BATCH_ITEM MODEL points (BatchItem::first / count
 // within the pair's model); one knn4_batch launch (nbr[(q_off + i) * 4 ..]: indices within the pair's model) + one
 // normals_batch_kernel launch (Nrm_soa laid out as Q_soa)

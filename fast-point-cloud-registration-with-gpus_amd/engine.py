@@ -257,15 +257,46 @@ class Context:
         """a Batch of (D, M) pairs of one dtype, uploaded once (see Batch)"""
         return Batch(self, pairs)
 
-    def point_to_point_batch(self, pairs, max_iter=40, tol=1e-6, fixed_iterations=False):
+    def point_to_point_batch(self, pairs, max_iter=40, tol=1e-6, fixed_iterations=False, max_distance=None):
         """point_to_point for every (D, M) of `pairs` (one dtype) in one batched registration; a list of Result in pair order,
-        each exactly what point_to_point gives for that pair alone (extra["status"]: ICP_OK or the code that ended its loop)"""
+        each exactly what point_to_point gives for that pair alone (extra["status"]: ICP_OK or the code that ended its loop).
+        max_distance (a scalar or one value per pair, inf = that pair is not gated): a match farther away than that pulls on
+        nothing (Batch.set_max_distance); extra["inliers"] is then the mask of the last contributing pass and extra["fitness"]
+        the share of the points it kept"""
+        if max_distance is not None:
+            return self._run_batch_gated(capi.ICP_POINT_TO_POINT, pairs, None, max_iter, tol, fixed_iterations, max_distance)
         return self._run_batch(capi.ICP_POINT_TO_POINT, pairs, None, max_iter, tol, fixed_iterations)
 
     def point_to_plane_batch(self, pairs, normals=None, max_iter=50, tol=1e-6, fixed_iterations=False):
         """point_to_plane for every (D, M) of `pairs` in one batched registration, as point_to_point_batch; normals: one (m, 3)
         array per pair, or None (then estimated on the device: one neighbour launch + one normals launch for all pairs)"""
         return self._run_batch(capi.ICP_POINT_TO_PLANE, pairs, normals, max_iter, tol, fixed_iterations)
+
+    def point_to_plane_batch_gated(self, pairs, max_distance, normals=None, max_iter=50, tol=1e-6, fixed_iterations=False):
+        """point_to_plane_batch with a maximum correspondence distance (a scalar or one value per pair; the gate is on the Euclidean
+        distance to the matched point), as point_to_point_batch(max_distance=...): extra["inliers"], extra["fitness"].
+        (point_to_plane_batch itself keeps its parameter list, which tests/test_batch_plane_abi.py holds fixed.)"""
+        return self._run_batch_gated(capi.ICP_POINT_TO_PLANE, pairs, normals, max_iter, tol, fixed_iterations, max_distance)
+
+    def _run_batch_gated(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance):
+        """the one-call functions have no gate: create, [normals], set_max_distance, begin, run to the end, results"""
+        with Batch(self, pairs) as bt:
+            if metric == capi.ICP_POINT_TO_PLANE:
+                if normals is not None:
+                    bt.set_model_normals(normals)
+                else:
+                    bt.estimate_normals()
+            bt.set_max_distance(max_distance)
+            bt.begin(max_iter=max_iter, tol=tol, fixed_iterations=fixed_iterations, metric=metric)
+            while bt.run(1 << 20)[1] > 0:
+                pass
+            idx, inl, moved = bt.loop_indices(), bt.loop_inliers(), bt.get_moving()
+            out = []
+            for b in range(bt.count):
+                st = bt.state(b)
+                out.append(Result(T=st["T"].copy(), iterations=st["iterations"], passes=st["passes"], err=st["err"], idx=idx[b], moved=moved[b],
+                                  extra={"status": st["status"], "inliers": inl[b], "fitness": float(inl[b].sum()) / inl[b].size}))
+            return out
 
     def _run_batch(self, metric, pairs, normals, max_iter, tol, fixed_iterations):
         Ds, Ms, moff, qoff, dtype = _batch_arrays(pairs)
@@ -468,6 +499,20 @@ class Batch:
         cut = lambda a: [a[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
         return (cut(nrm), cut(nbr)) if want_neighbours else cut(nrm)
 
+    def set_max_distance(self, v):
+        """the maximum correspondence distance: a scalar for every pair, one value per pair (inf: that pair is not gated), or
+        None (no gate).  A match farther away than that enters no sum of its pass.  Discards a loop under way."""
+        if v is None:
+            capi.check(self._lib.icp_batch_set_max_distance(self._h, None), "icp_batch_set_max_distance")
+            return
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(self.count, float(a))
+        a = np.ascontiguousarray(a)
+        if a.shape != (self.count,):
+            raise ValueError("one maximum distance per pair (or a scalar)")
+        capi.check(self._lib.icp_batch_set_max_distance(self._h, a.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_max_distance")
+
     def begin(self, max_iter=40, tol=1e-6, fixed_iterations=False, metric=capi.ICP_POINT_TO_POINT):
         """start every pair's registration from the uploaded clouds (ICP_POINT_TO_PLANE: the batch must hold normals)"""
         prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(self._dtype), int(metric))
@@ -518,6 +563,19 @@ class Batch:
     def loop_indices(self):
         """each pair's matches of the last pass that contributed to its T"""
         return self._indices(self._lib.icp_batch_loop_indices, "icp_batch_loop_indices")
+
+    def _inliers(self, fn, where):
+        out = np.empty(int(self._moff[-1]), dtype=np.uint8)
+        capi.check(fn(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))), where)
+        return self._split(out.astype(bool))
+
+    def get_inliers(self):
+        """per pair, a bool per moving point: its match of the most recent matching pass was kept (all True without a gate)"""
+        return self._inliers(self._lib.icp_batch_get_inliers, "icp_batch_get_inliers")
+
+    def loop_inliers(self):
+        """per pair, a bool per moving point: its match of the last pass that contributed to T was kept"""
+        return self._inliers(self._lib.icp_batch_loop_inliers, "icp_batch_loop_inliers")
 
 
 # ---- host-only helpers (no device) -------------------------------------------------------------

@@ -44,7 +44,8 @@ extern "C" {
 #define ICP_ERR_INVALID (-1)   /* bad argument (NULL pointer, negative size, unknown enum) */
 #define ICP_ERR_NO_DEVICE (-2) /* no usable HIP device / device index out of range */
 #define ICP_ERR_HIP (-3)       /* a HIP runtime call or kernel launch failed (see icp_last_error) */
-#define ICP_ERR_EMPTY (-4)     /* empty model cloud (m == 0) where a match is required */
+#define ICP_ERR_EMPTY (-4)     /* no model point (m == 0) where a match is required, or no correspondence within the maximum
+                                * distance (a gated pair of a batch whose matching pass kept no point) */
 #define ICP_ERR_SINGULAR (-5)  /* 6x6 point-to-plane system not positive definite */
 #define ICP_ERR_IO (-6)        /* dataset file missing / malformed */
 #define ICP_ERR_STATE (-7)     /* call sequence error (e.g. step before begin, clouds not set) */
@@ -231,7 +232,33 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *     way is discarded (icp_batch_run returns ICP_ERR_STATE until the next icp_batch_begin).  A refused call leaves the batch's
  *     normals as they were (none, or the previous set).  icp_batch_begin accepts ICP_POINT_TO_PLANE only on a batch that holds
  *     normals (else ICP_ERR_INVALID); a batch that holds normals still begins ICP_POINT_TO_POINT, with the bits of one that
- *     holds none. */
+ *     holds none.
+ *   - maximum correspondence distance (icp_batch_set_max_distance): one double per pair, each > 0 or +INFINITY (that pair is
+ *     not gated); NULL removes the gate.  Without it every moving point pulls on its nearest model point however far away,
+ *     which is the reference's behaviour.
+ *       threshold: thr_p = (F)(max_dist[p] * max_dist[p]) -- the product formed in double and rounded once to the batch's
+ *         precision F; +INFINITY gives thr = +inf.  A NaN, a value <= 0 or -INFINITY anywhere: ICP_ERR_INVALID, the message
+ *         names the pair, and the batch keeps the thresholds it had (or none).
+ *       the call may come at any time after icp_batch_create; like the normals calls it discards a loop under way
+ *         (icp_batch_run returns ICP_ERR_STATE until the next icp_batch_begin).
+ *       gate: a match is kept iff d <= thr_p, where d is the winning squared distance the matching already holds --
+ *         (dx*dx + dy*dy) + dz*dz, every operation rounded separately in F; nothing is recomputed in double, and a point
+ *         exactly on the threshold is kept.  For point-to-plane the gate is on the same Euclidean d.
+ *       idx is unchanged: every index is the bit-exact nearest neighbour in [0, m), kept or not.
+ *       sums: only kept points contribute to ICP_MOM_CNT and to every sum of the pass, for both metrics.  ICP_MOM_ERR of a
+ *         pass is the sum of |p_new - q[idx_prev]|^2 over the points kept by the matching pass those indices came from, and
+ *         err[k] = sqrt(ERR_k) / sqrt(CNT_{k-1}), CNT_{k-1} being the kept count of that same matching pass.
+ *       a matching pass that keeps no point ends that pair with status ICP_ERR_EMPTY (unless the stop rule ended its loop on
+ *         that very pass): err[k] of the pass is recorded; T, iterations, passes and the cloud are those of the passes
+ *         completed; the other pairs go on.  One or two kept points in point-to-point behave as a one- or two-point cloud
+ *         does; a 6x6 system that is not positive definite ends the pair with ICP_ERR_SINGULAR.
+ *       a batch with no gate, or with every value +INFINITY, produces the bits of a batch that never heard of the gate, and a
+ *         gated pair's bits depend on that pair and its threshold alone (no atomics, fixed order).
+ *       icp_batch_get_inliers / icp_batch_loop_inliers: one byte per moving point, 1 = that point's match was kept, for the
+ *         pass icp_batch_get_indices / icp_batch_loop_indices report, with their errors and ordering (ICP_ERR_STATE before
+ *         the first pass and during the context's pending pass).  An ungated batch answers all ones.
+ *     Not gated: the single-pair loops (icp_point_to_*, icp_loop_*) and the multi-GPU sums -- a single pair that needs a
+ *     gate is a batch of one.  There are no initial transforms and no trimmed or percentile rejection. */
 typedef struct icp_batch icp_batch;
 #define ICP_BATCH_MAX_POINTS 65536 /* per cloud of one pair */
 int icp_batch_create(icp_ctx* ctx, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
@@ -256,6 +283,11 @@ int icp_batch_done(icp_batch* b, int32_t* done_out);
 int icp_batch_get_moving(icp_batch* b, void* aos_out);      /* all pairs, concatenated as uploaded, as icp_get_moving */
 int icp_batch_get_indices(icp_batch* b, int32_t* idx_out);  /* each pair's most recent matching pass, as icp_get_indices */
 int icp_batch_loop_indices(icp_batch* b, int32_t* idx_out); /* each pair's last contributing pass, as icp_loop_indices */
+/* per-pair gate: count doubles, or NULL = no gate.  Each value > 0, or +INFINITY (that pair is not gated). */
+int icp_batch_set_max_distance(icp_batch* b, const double* max_dist);
+/* 1 byte per moving point, concatenated as the moving clouds: 1 = that point's match was kept */
+int icp_batch_get_inliers(icp_batch* b, uint8_t* mask_out);   /* each pair's most recent matching pass (as icp_batch_get_indices) */
+int icp_batch_loop_inliers(icp_batch* b, uint8_t* mask_out);  /* each pair's last contributing pass (as icp_batch_loop_indices) */
 /* one call: create + begin + run to the end + results, then destroy.  Every output pointer may be NULL; per pair:
  * T16_out 16, iterations_out / passes_out / status_out 1, err_out max_iter+1 doubles; idx_out and moved_out (3 values per
  * point, precision of the run) concatenated as the moving clouds.  A failed pair is reported in status_out, not in the

@@ -2,7 +2,7 @@
 """Pair-iterations per second of the batched loops (Context.point_to_point_batch / point_to_plane_batch, one launch per step
 for all pairs) against a loop of Context.point_to_point / point_to_plane over the same pairs (GPU box).
 
-  python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE]
+  python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE] [--only CASE,CASE] [--max-distance V] [--label TEXT]
 
 Cases, --metric point: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids
 (make_model_gpu, tol 1e-6); 16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  --metric plane: the fp32 case sets and the
@@ -13,6 +13,13 @@ around calls that end in a device synchronisation; a pair-iteration is one match
 sequential side also reports its loops alone (Result.seconds_total, the registration without the upload and the normals).
 Median of --reps after one warm-up of every case.  Every pair must run the same passes on both sides: the rows carry the number of
 pairs that did not (pairs_stopping_apart), and the tool exits non-zero if there is one.
+
+--max-distance V (a distance, or inf) runs the batched side with that maximum correspondence distance on every pair
+(Context.point_to_point_batch(max_distance=V) / point_to_plane_batch_gated: the gated kernels, through the Batch object); the
+sequential side has no gate, so the passes agree only for inf and only then are they compared.  The cost of the gate is
+--max-distance inf against a run without the option.  Every row carries the fastest and the slowest of its --reps runs beside the
+median (batched_s_min / batched_s_max), and --label TEXT as "label" (which build, which round).  ICP_LIB_PATH selects another
+build of the library for an A/B run on one box.
 """
 import argparse
 import json
@@ -68,6 +75,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--metric", choices=("point", "plane"), default="point")
     ap.add_argument("--out", default="")
+    ap.add_argument("--only", default="", help="comma-separated case names: run only these")
+    ap.add_argument("--max-distance", type=float, default=None, help="gate the batched side at this distance (inf: the gated kernels, nothing rejected)")
+    ap.add_argument("--label", default="", help="copied into every row")
     ap.add_argument("--profile-case", default="", help="run only this case's batched registration, once after a warm-up (for a kernel trace)")
     a = ap.parse_args()
     import torch  # noqa: F401  (torch first: it bundles the HIP runtime)
@@ -79,11 +89,21 @@ def main():
     with pkg.Context(0) as ctx:
         plane = a.metric == "plane"
         todo = plane_cases(pkg, orc) if plane else [(name, pairs, None, it, tol) for name, pairs, it, tol in cases(pkg, orc)]
+        only = [c for c in a.only.split(",") if c]
+        unknown = [c for c in only if c not in [t[0] for t in todo]]
+        if unknown:
+            sys.exit(f"unknown case(s) {unknown}: {[t[0] for t in todo]}")
+        gate = a.max_distance
         for name, pairs, normals, it, tol in todo:
+            if only and name not in only:
+                continue
+
             def run_batched():
+                if plane and gate is not None:
+                    return ctx.point_to_plane_batch_gated(pairs, gate, normals=normals, max_iter=it, tol=tol)
                 if plane:
                     return ctx.point_to_plane_batch(pairs, normals=normals, max_iter=it, tol=tol)
-                return ctx.point_to_point_batch(pairs, max_iter=it, tol=tol)
+                return ctx.point_to_point_batch(pairs, max_iter=it, tol=tol, max_distance=gate)
 
             def run_sequential():
                 if plane:
@@ -119,14 +139,16 @@ def main():
                 ts.append(s)
                 tl.append(loops)
             # the same registrations: every pair must run the same passes on both sides (checked when all rows are out)
-            apart = sum(1 for x, y in zip(pb, ps) if x != y)
+            apart = sum(1 for x, y in zip(pb, ps) if x != y) if gate is None or np.isinf(gate) else 0
             pb, ps = sum(pb), sum(ps)
             mb, ms, ml = float(np.median(tb)), float(np.median(ts)), float(np.median(tl))
             row = dict(case=name, pairs=len(pairs), points=int(pairs[0][0].shape[0]), pair_iterations=pb, sequential_pair_iterations=ps, pairs_stopping_apart=apart,
                        batched_s=mb, sequential_s=ms, sequential_loops_s=ml,
                        batched_pair_it_per_s=pb / mb, sequential_pair_it_per_s=ps / ms,
                        batched_us_per_pair_it=1e6 * mb / pb, sequential_us_per_pair_it=1e6 * ms / ps,
-                       sequential_loops_us_per_pair_it=1e6 * ml / ps, speedup=ms / mb, speedup_vs_loops=ml / mb)
+                       sequential_loops_us_per_pair_it=1e6 * ml / ps, speedup=ms / mb, speedup_vs_loops=ml / mb,
+                       batched_s_min=float(min(tb)), batched_s_max=float(max(tb)), reps=a.reps,
+                       max_distance=None if gate is None else str(gate), label=a.label)
             rows.append(row)
             print(json.dumps(row), flush=True)
     if a.out:
