@@ -241,33 +241,37 @@ __global__ void knn4_merge_kernel(const float* __restrict__ part_d, const int32_
     for (int r = 1; r < 5; ++r) nbr[(size_t)i * 4 + (r - 1)] = L.j[r];
 }
 
-// PCA normal of every model point from its 4 neighbours, entirely on the device: float covariance in the
-// order of src/CUDA/CPU_ICP_point_to-plane.cpp:217-246 (bar = sum * 0.25f, A += (x-bar)(y-bar), not divided by
-// k), then a cyclic-Jacobi eigen-solve in fp64 registers (stands in for the reference's HOST loop of
-// LAPACKE_ssyev, src/ICP_point_to_plane.cu:429-438) and the eigenvector of the eigenvalue of smallest magnitude
-// (cblas_isamin over the ascending eigenvalues, first on ties).  Writes the padded SoA normal cloud directly.
+__device__ __forceinline__ float mag_(float v) { return fabsf(v); }
+__device__ __forceinline__ double mag_(double v) { return fabs(v); }
+
+// PCA normal of every model point from its 4 neighbours, entirely on the device: the covariance in the cloud's own precision F
+// (float clouds: the order of src/CUDA/CPU_ICP_point_to-plane.cpp:217-246; double clouds: the same statements in double -- a
+// float covariance of a cloud far from the origin keeps nothing of a small neighbourhood) -- bar = sum * 0.25,
+// A += (x-bar)(y-bar), not divided by k --, then a cyclic-Jacobi eigen-solve in fp64 registers (stands in for the reference's
+// HOST loop of LAPACKE_ssyev, src/ICP_point_to_plane.cu:429-438) and the eigenvector of the eigenvalue of smallest magnitude
+// (cblas_isamin over the ascending eigenvalues rounded to F, first on ties).  Writes the padded SoA normal cloud directly.
 // The per-point body, shared by normals_kernel and normals_batch_kernel: the same statements on the same four neighbours give
 // the same bits (contraction is off for this translation unit).  Qx, Qy, Qz: the coordinate planes the indices nb4[0..3] refer to.
 template <typename F>
 __device__ __forceinline__ void pca_normal(const F* __restrict__ Qx, const F* __restrict__ Qy, const F* __restrict__ Qz,
                                            const int32_t* __restrict__ nb4, double& nx, double& ny, double& nz)
 {
-    float x[4], y[4], z[4];
-    float bx = 0.f, by = 0.f, bz = 0.f;
+    F x[4], y[4], z[4];
+    F bx = 0, by = 0, bz = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int s = nb4[j];
-        x[j] = (float)Qx[s];
-        y[j] = (float)Qy[s];
-        z[j] = (float)Qz[s];
+        x[j] = Qx[s];
+        y[j] = Qy[s];
+        z[j] = Qz[s];
         bx += x[j]; by += y[j]; bz += z[j];
     }
-    const float qa = 1.0f / 4.0f;
+    const F qa = (F)1 / (F)4;
     bx *= qa; by *= qa; bz *= qa;
-    float A[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    F A[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float dx = x[j] - bx, dy = y[j] - by, dz = z[j] - bz;
+        const F dx = x[j] - bx, dy = y[j] - by, dz = z[j] - bz;
         A[0] += dx * dx; A[1] += dx * dy; A[2] += dx * dz;
         A[3] += dy * dy; A[4] += dy * dz; A[5] += dz * dz;
     }
@@ -318,7 +322,7 @@ __device__ __forceinline__ void pca_normal(const F* __restrict__ Qx, const F* __
             p = v21; q = v22; v21 = c * p - s * q; v22 = s * p + c * q;
         }
     }
-    // ascending eigenvalues (stable w.r.t. the original slot), then the first of smallest |w| as floats
+    // ascending eigenvalues (stable w.r.t. the original slot), then the first of smallest |w| in the cloud's precision
     double w0 = a00, w1 = a11, w2 = a22;
     double e0x = v00, e0y = v10, e0z = v20, e1x = v01, e1y = v11, e1z = v21, e2x = v02, e2y = v12, e2z = v22;
 #define ICP_SWAP_EIG(wa, ax, ay, az, wb, bx_, by_, bz_) \
@@ -328,9 +332,9 @@ __device__ __forceinline__ void pca_normal(const F* __restrict__ Qx, const F* __
     ICP_SWAP_EIG(w1, e1x, e1y, e1z, w2, e2x, e2y, e2z)
 #undef ICP_SWAP_EIG
     nx = e0x; ny = e0y; nz = e0z;
-    float wm = fabsf((float)w0);
-    if (fabsf((float)w1) < wm) { wm = fabsf((float)w1); nx = e1x; ny = e1y; nz = e1z; }
-    if (fabsf((float)w2) < wm) { nx = e2x; ny = e2y; nz = e2z; }
+    F wm = mag_((F)w0);
+    if (mag_((F)w1) < wm) { wm = mag_((F)w1); nx = e1x; ny = e1y; nz = e1z; }
+    if (mag_((F)w2) < wm) { nx = e2x; ny = e2y; nz = e2z; }
 }
 
 template <typename F>

@@ -149,7 +149,9 @@ int icp_set_exclusive(icp_ctx* ctx, int on);
 
 /* ---- model normals: replaces knn + Normals + host ssyev loop
  *      src/CUDA/GPU_point_to_plane_real.cu:54-188,391-423 (k = 4 neighbours, self excluded).
- *      Works on the resident model; results stay resident and are optionally returned. ------- */
+ *      Works on the resident model; results stay resident and are optionally returned.
+ *      Neighbours, mean and covariance are formed in the model's own precision: an ICP_F64 model (survey coordinates,
+ *      a small patch far from the origin) gets its normals from double arithmetic throughout. ------- */
 int icp_estimate_normals(icp_ctx* ctx, void* nxyz_aos_out /*3m or NULL*/, int32_t* neighbours_out /*4m or NULL*/);
 
 /* ---- the ICP loops: replace main()'s while-loops

@@ -649,6 +649,159 @@ int orc_icp_p2plane_f32x(const float* D, const float* M, int n, int m, const flo
 }
 
 /* ------------------------------------------------------------------------------------------
+ * Point-to-plane, fp64.  The reference has no such program (its fp64 program, src/ICP_CPU.c, is
+ * point-to-point only); the product offers ICP_F64 + ICP_POINT_TO_PLANE, and this is its checker:
+ * the statements of the fp32 plane path above with `double` throughout, the matching of
+ * src/ICP_CPU.c (orc_nn_f64).
+ * ---------------------------------------------------------------------------------------- */
+
+/* k=4 neighbours: distance (dx*dx + dy*dy) + dz*dz with every operation rounded in double; the
+ * first five of the (d, j)-ascending order of the model, rank 0 (self or an equal-distance lower
+ * index) dropped.  The order is stated directly -- a sorted top-5 kept over one ascending scan,
+ * a candidate going behind every entry with d_e <= d -- instead of the fp32 twin's k+1 passes of
+ * first-argmin with overwrite-by-10000, which stop being that order once distances exceed 10000. */
+void orc_knn4_f64(const double* q, int m, int* neighborIds /* m*4 */)
+{
+    const size_t ms = (size_t)m;
+    for (int i = 0; i < m; i++) {
+        const double px = q[i], py = q[i + ms], pz = q[i + 2 * ms];
+        double bd[5];
+        int bj[5], have = 0;
+        for (int c = 0; c < m; c++) {
+            double dx = q[c] - px, dy = q[c + ms] - py, dz = q[c + 2 * ms] - pz;
+            dx = dx * dx; dy = dy * dy; dz = dz * dz;
+            double d = dx + dy;
+            d = d + dz;
+            if (have == 5 && !(d < bd[4])) continue;
+            int r = have < 5 ? have : 4;              /* the slot that opens at the end */
+            while (r > 0 && d < bd[r - 1]) { bd[r] = bd[r - 1]; bj[r] = bj[r - 1]; r--; }
+            bd[r] = d; bj[r] = c;
+            if (have < 5) have++;
+        }
+        for (int r = 1; r < 5; r++) neighborIds[(r - 1) + i * 4] = r < have ? bj[r] : 0;
+    }
+}
+
+/* orc_normals_f32's statements in double: bar = (sum of 4 neighbours) * 0.25, upper-triangular
+ * covariance (not divided by k), orc_eigh3, the eigenvector of the eigenvalue of smallest magnitude
+ * among the ascending ones (first on ties).  A_out (optional, m*9): the covariance handed to the
+ * eigen-solver. */
+void orc_normals_f64(const double* q, int m, const int* neighborIds, double* normals /*SoA*/, double* A_out)
+{
+    const size_t ms = (size_t)m;
+    const int k = 4;
+    for (int i = 0; i < m; i++) {
+        double bar[3] = {0.0, 0.0, 0.0};
+        for (int j = 0; j < k; j++) {
+            const int s = neighborIds[j + i * k];
+            bar[0] += q[s];
+            bar[1] += q[s + ms];
+            bar[2] += q[s + 2 * ms];
+        }
+        const double a = 1 / (double)k;
+        bar[0] *= a; bar[1] *= a; bar[2] *= a;
+        double A[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int j = 0; j < k; j++) {
+            const int s = neighborIds[j + i * k];
+            const double xi = q[s], yi = q[s + ms], zi = q[s + 2 * ms];
+            A[0] += (xi - bar[0]) * (xi - bar[0]);
+            A[1] += (xi - bar[0]) * (yi - bar[1]);
+            A[2] += (xi - bar[0]) * (zi - bar[2]);
+            A[4] += (yi - bar[1]) * (yi - bar[1]);
+            A[5] += (yi - bar[1]) * (zi - bar[2]);
+            A[8] += (zi - bar[2]) * (zi - bar[2]);
+        }
+        if (A_out) memcpy(A_out + 9 * (size_t)i, A, sizeof A);
+        double w[3], Z[9];
+        orc_eigh3(A, w, Z);
+        int idx_min = 0;
+        for (int e = 1; e < 3; e++) if (fabs(w[e]) < fabs(w[idx_min])) idx_min = e;
+        for (int j = 0; j < 3; j++) normals[i + ms * j] = Z[j * 3 + idx_min];
+    }
+}
+
+/* the statements of orc_p2plane_minimize_f32x on double inputs */
+int orc_p2plane_minimize_f64(const double* p, int n, const double* q, int m, const int* q_idx,
+                             const double* normals, double* R /*9, row-major*/, double* t /*3*/,
+                             double* C_out /*36 or NULL*/, double* b_out /*6 or NULL*/)
+{
+    const size_t ns = (size_t)n, ms = (size_t)m;
+    double Cd[36], bd[6];
+    for (int e = 0; e < 36; e++) Cd[e] = 0;
+    for (int e = 0; e < 6; e++) bd[e] = 0;
+    for (int i = 0; i < n; i++) {
+        const int s = q_idx[i];
+        const double px = p[i], py = p[i + ns], pz = p[i + 2 * ns];
+        const double nx = normals[s], ny = normals[s + ms], nz = normals[s + 2 * ms];
+        double cn[6];
+        cn[0] = py * nz - pz * ny;
+        cn[1] = pz * nx - px * nz;
+        cn[2] = px * ny - py * nx;
+        cn[3] = nx; cn[4] = ny; cn[5] = nz;
+        const double bi = (px - q[s]) * nx + (py - q[s + ms]) * ny + (pz - q[s + 2 * ms]) * nz;
+        for (int a = 0; a < 6; a++) {
+            for (int c = 0; c < 6; c++) Cd[a * 6 + c] += cn[a] * cn[c];
+            bd[a] -= cn[a] * bi;
+        }
+    }
+    if (C_out) memcpy(C_out, Cd, sizeof Cd);
+    if (b_out) memcpy(b_out, bd, sizeof bd);
+    double x[6];
+    const int info = orc_solve6(Cd, bd, x);
+    if (info) return info;
+    const double cx = cos(x[0]), cy = cos(x[1]), cz = cos(x[2]);
+    const double sx = sin(x[0]), sy = sin(x[1]), sz = sin(x[2]);
+    R[0] = cy * cz; R[1] = cz * sx * sy - cx * sz; R[2] = cx * cz * sy + sx * sz;
+    R[3] = cy * sz; R[4] = cx * cz + sx * sy * sz; R[5] = cx * sy * sz - cz * sx;
+    R[6] = -sy; R[7] = cy * sx; R[8] = cx * cy;
+    t[0] = x[3]; t[1] = x[4]; t[2] = x[5];
+    return 0;
+}
+
+/* orc_icp_p2plane_f32x's loop with the cloud, R = Rz Ry Rx and t kept in double: orc_nn_f64,
+ * orc_transform_f64, orc_rms_error_f64; the same stop rule and the same `fixed` flag. */
+int orc_icp_p2plane_f64(const double* D, const double* M, int n, int m, const double* normals, int max_iter,
+                        double tol, int fixed, double* E, double* T_total, int* idx_last, double* pt_out, int* passes)
+{
+    const size_t ns = (size_t)n;
+    double* p = (double*)malloc(3 * ns * sizeof(double));
+    int* q_idx = (int*)malloc(ns * sizeof(int));
+    if (!p || !q_idx) { free(p); free(q_idx); return -1; }
+    memcpy(p, D, 3 * ns * sizeof(double));
+    for (int k = 0; k <= max_iter; k++) E[k] = 0;
+    double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    int it = 0, npass = 0, rc = 0;
+    while (it < max_iter) {
+        orc_nn_f64(p, n, M, m, q_idx);
+        npass++;
+        double R[9], t[3];
+        rc = orc_p2plane_minimize_f64(p, n, M, m, q_idx, normals, R, t, NULL, NULL);
+        if (rc) break;
+        orc_transform_f64(p, n, R, t);
+        {
+            double Tk[16] = {R[0], R[1], R[2], t[0], R[3], R[4], R[5], t[1], R[6], R[7], R[8], t[2], 0, 0, 0, 1};
+            double Tn[16];
+            for (int a = 0; a < 4; a++)
+                for (int b = 0; b < 4; b++) {
+                    double s = 0;
+                    for (int k = 0; k < 4; k++) s += Tk[a * 4 + k] * T[k * 4 + b];
+                    Tn[a * 4 + b] = s;
+                }
+            memcpy(T, Tn, sizeof T);
+        }
+        E[it + 1] = orc_rms_error_f64(p, n, M, m, q_idx);
+        if (!fixed && ((E[it + 1] < tol) || (fabs(E[it + 1] - E[it]) < tol))) break;
+        it++;
+    }
+    if (T_total) memcpy(T_total, T, sizeof T);
+    if (idx_last) memcpy(idx_last, q_idx, ns * sizeof(int));
+    if (pt_out) memcpy(pt_out, p, 3 * ns * sizeof(double));
+    if (passes) *passes = npass;
+    free(p); free(q_idx);
+    return rc ? -rc : it;
+}
+
+/* ------------------------------------------------------------------------------------------
  * Hall ingest: GPU_point_to_point_real.cu:432-623.
  * ---------------------------------------------------------------------------------------- */
 

@@ -154,21 +154,30 @@ class Oracle:
         return D, M
 
     # ---- point-to-plane -------------------------------------------------------------------------
+    @staticmethod
+    def _plane_dtype(Q):
+        """float64 clouds go to the fp64 functions, everything else is taken as float32 (as before there were fp64 ones)"""
+        return np.float64 if np.asarray(Q).dtype == np.float64 else np.float32
+
     def knn4(self, Q):
-        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        """the first five of the (d, j)-ascending order without rank 0, in Q's precision (orc_knn4_f32 / orc_knn4_f64)"""
+        dt = self._plane_dtype(Q)
+        Q = np.ascontiguousarray(Q, dtype=dt)
         qs = soa(Q)
         nbr = np.zeros((Q.shape[0], 4), dtype=np.int32)
-        self.lib.orc_knn4_f32(qs.ctypes.data_as(C.c_void_p), Q.shape[0], nbr.ctypes.data_as(C.c_void_p))
+        getattr(self.lib, "orc_knn4_" + self._s(dt))(qs.ctypes.data_as(C.c_void_p), Q.shape[0], nbr.ctypes.data_as(C.c_void_p))
         return nbr
 
     def normals(self, Q, nbr):
-        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        """(normals (m,3), covariance (m,9): upper triangle filled) in Q's precision (orc_normals_f32 / orc_normals_f64)"""
+        dt = self._plane_dtype(Q)
+        Q = np.ascontiguousarray(Q, dtype=dt)
         qs = soa(Q)
         nbr = np.ascontiguousarray(nbr, dtype=np.int32)
-        nr = np.zeros(3 * Q.shape[0], dtype=np.float32)
-        A = np.zeros((Q.shape[0], 9), dtype=np.float32)
-        self.lib.orc_normals_f32(qs.ctypes.data_as(C.c_void_p), Q.shape[0], nbr.ctypes.data_as(C.c_void_p),
-                                 nr.ctypes.data_as(C.c_void_p), A.ctypes.data_as(C.c_void_p))
+        nr = np.zeros(3 * Q.shape[0], dtype=dt)
+        A = np.zeros((Q.shape[0], 9), dtype=dt)
+        getattr(self.lib, "orc_normals_" + self._s(dt))(qs.ctypes.data_as(C.c_void_p), Q.shape[0], nbr.ctypes.data_as(C.c_void_p),
+                                                        nr.ctypes.data_as(C.c_void_p), A.ctypes.data_as(C.c_void_p))
         return aos(nr, Q.shape[0]), A
 
     def p2plane_minimize(self, P, Q, idx, normals, accumulate_f64=False):
@@ -234,6 +243,37 @@ class Oracle:
                                                 idx.ctypes.data_as(C.c_void_p), ns.ctypes.data_as(C.c_void_p),
                                                 R.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
                                                 Cm.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p))
+        return rc, R.reshape(3, 3), t, Cm.reshape(6, 6), b
+
+    def icp_p2plane_f64(self, D, M, normals, max_iter, tol, fixed=False):
+        """fp64 matching, minimisation, move and error (see oracle/icp_oracle.c, orc_icp_p2plane_f64); < 0 iterations: singular"""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        n, m = D.shape[0], M.shape[0]
+        ds, ms, ns = soa(D), soa(M), soa(np.asarray(normals, dtype=np.float64))
+        E = np.zeros(max_iter + 1, dtype=np.float64)
+        T = np.zeros(16)
+        idx = np.zeros(n, dtype=np.int32)
+        pt = np.zeros(3 * n, dtype=np.float64)
+        passes = C.c_int(0)
+        self.lib.orc_icp_p2plane_f64.restype = C.c_int
+        it = self.lib.orc_icp_p2plane_f64(ds.ctypes.data_as(C.c_void_p), ms.ctypes.data_as(C.c_void_p), n, m,
+                                          ns.ctypes.data_as(C.c_void_p), int(max_iter), C.c_double(tol), 1 if fixed else 0,
+                                          E.ctypes.data_as(C.c_void_p), T.ctypes.data_as(C.c_void_p),
+                                          idx.ctypes.data_as(C.c_void_p), pt.ctypes.data_as(C.c_void_p), C.byref(passes))
+        return dict(iterations=it, passes=passes.value, err=E[: passes.value + 1].copy(), T=T.reshape(4, 4), idx=idx, moved=aos(pt, n))
+
+    def p2plane_minimize_f64(self, P, Q, idx, normals):
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        ps, qs, ns = soa(P), soa(Q), soa(np.asarray(normals, dtype=np.float64))
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        R, t, Cm, b = np.zeros(9), np.zeros(3), np.zeros(36), np.zeros(6)
+        self.lib.orc_p2plane_minimize_f64.restype = C.c_int
+        rc = self.lib.orc_p2plane_minimize_f64(ps.ctypes.data_as(C.c_void_p), P.shape[0], qs.ctypes.data_as(C.c_void_p), Q.shape[0],
+                                               idx.ctypes.data_as(C.c_void_p), ns.ctypes.data_as(C.c_void_p),
+                                               R.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                               Cm.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p))
         return rc, R.reshape(3, 3), t, Cm.reshape(6, 6), b
 
     # ---- hall ingest ----------------------------------------------------------------------------

@@ -73,7 +73,8 @@ def bits_equal(a, b):
 
 
 def normals_for(orc, M):
-    return orc.normals(M, orc.knn4(M))[0].astype(M.dtype)
+    M32 = np.asarray(M, dtype=np.float32)   # (the fp32 model's normals, cast: the oracle's kNN and normals follow the dtype they are given)
+    return orc.normals(M32, orc.knn4(M32))[0].astype(M.dtype)
 
 
 def run_to_end(bt, metric, max_iter=40, tol=1e-6, fixed=False):

@@ -77,8 +77,8 @@ def handle_results(bt, pkg, **begin):
 KNN_M = (5, 6, 32, 33, 63, 64, 65, 130, 257, 1000, 1024, 1025, 2048, 2049, 4097)
 
 
-def knn_models(dtype):
-    models = [cl.ragged_pair(s, 1, m)[1] for s, m in enumerate(KNN_M)]
+def knn_models(dtype, sizes=KNN_M):
+    models = [cl.ragged_pair(s, 1, m)[1] for s, m in enumerate(sizes)]
     Z = np.random.default_rng(5).standard_normal((300, 3)).astype(np.float32)
     Z[100:140] = 0.0   # 40 coincident points: the order among equal distances
     models.append(Z)
@@ -113,8 +113,7 @@ def test_batch_neighbours_and_normals_ragged(ctx, pkg, orc, dtype):
         nrm, nbr = bt.estimate_normals(want_neighbours=True)
         only = bt.estimate_normals()
     assert all(a.tobytes() == b.tobytes() for a, b in zip(nrm, only))
-    # (the oracle's kNN is fp32: the float64 batch is held to the single-pair path alone)
-    check_normals_against_single(ctx, models, nrm, nbr, orc if dtype == np.float32 else None)
+    check_normals_against_single(ctx, models, nrm, nbr, orc)   # (the oracle's kNN follows the dtype: orc_knn4_f32 / orc_knn4_f64)
 
 
 def test_batch_neighbours_and_normals_largest_model(ctx, pkg):
@@ -346,7 +345,7 @@ def test_batch_plane_against_single_pair_path(ctx, pkg, five):
 
 
 def test_batch_plane_fp64_against_single_pair_path(ctx, pkg, five):
-    """there is no fp64 plane oracle: the float64 batch is held to Context.point_to_plane of each pair alone"""
+    """the float64 batch is held to Context.point_to_plane of each pair alone (both against the fp64 oracle: test_gpu_plane_f64.py)"""
     pairs, normals, _, _ = five
     pairs = [(D.astype(np.float64), M.astype(np.float64)) for D, M in pairs]
     normals = [N.astype(np.float64) for N in normals]

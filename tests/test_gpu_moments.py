@@ -330,6 +330,36 @@ def test_full_rows_fp64(pkg, monkeypatch, sparse):
     report(label, f"{label}/loop_run")
 
 
+@pytest.mark.parametrize("sparse", ["1", "0"])
+def test_full_rows_fp64_point_to_plane(pkg, orc, monkeypatch, sparse):
+    """the 28 sums of the single-pair fp64 routes: ICP_F64_SPARSE=1, the TAIL == 2 branch of nn_match_row64_f64; =0, the dense kernel
+    + moments_kernel<double, POINT_TO_PLANE>.  Normals: the fp32 model's oracle normals cast to double, as the batch test takes them.
+    A cloud of one or two points has six unknowns: its loop may end ICP_ERR_SINGULAR after the first vector (stepwise() keeps that
+    vector)."""
+    B = bits(pkg)
+    kernel = B.ROUTE_FUSED_TAIL if sparse == "1" else B.ROUTE_MOMENTS_KERNEL
+    must = B.ROUTE_HOST_ROWS | B.ROUTE_AVX | kernel
+    never = B.ROUTE_COMPACT | B.ROUTE_FIN_LAUNCH | B.ROUTE_FIN_KERNEL | ((B.ROUTE_FUSED_TAIL | B.ROUTE_MOMENTS_KERNEL) & ~kernel)
+    label = f"full/fp64_plane_sparse{sparse}"
+    with fresh_context(pkg, monkeypatch, {"ICP_F64_SPARSE": sparse}) as c:
+        for m in cl.MODEL_M:
+            for n in cl.ROW64_N:
+                D, M = cl.case_pair(n, m, np.float64)
+                Nrm = normals_of(orc, cl.case_pair(n, m)[1]).astype(np.float64)
+                base = stepwise(c, pkg, D, M, pkg.ICP_POINT_TO_PLANE, Nrm)
+                assert base[0]["P"].dtype == np.float64
+                check_trajectory(pkg, label, base, M, must, never, plane=True, Nrm=Nrm)   # (P_{k+1} = apply_rt of the solve of pass k's vector, bit for bit)
+                assert n < 63 or not base[-1]["failed"], (n, m)   # (one or two points: six unknowns; the batch test draws the same line)
+                if base[-1]["failed"]:
+                    continue
+                for schedule in SCHEDULES:   # icp_loop_run, whichever form it takes for this plan: the same trajectory
+                    for k, rec in in_runs(c, pkg, D, M, pkg.ICP_POINT_TO_PLANE, Nrm, schedule).items():
+                        assert rec["P"].tobytes() == base[k]["P"].tobytes() and rec["idx"].tobytes() == base[k]["idx"].tobytes()
+                        expect_pass_route(pkg, rec, k == PASSES, must, never, f"{label} runs {schedule} pass {k}", rec["route"] & (B.ROUTE_ARMED | B.ROUTE_RESIDENT))
+                        check_pass(pkg, f"{label}/loop_run", rec, base[k - 1] if k else None, M, plane=True, Nrm=Nrm, final=(k == PASSES))
+    report(label, f"{label}/loop_run")
+
+
 # ---- 4. rows left on the device and added by finalize_kernel (an external moments buffer) ------------------------------------------
 def with_external_buffer(c, pkg, fn):
     """fn(read) with the loop's vector in a torch tensor; read() = the tensor's content once everything enqueued has run"""

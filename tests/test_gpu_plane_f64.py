@@ -1,0 +1,253 @@
+"""GPU: the fp64 point-to-plane path (ICP_F64 + ICP_POINT_TO_PLANE) against a reference computed off the device, at every seam:
+neighbours (orc_knn4_f64, bit for bit), fp64 matching where one ulp decides (the fused-tie lattice), normals (orc_normals_f64's
+covariance; a second reference in np.longdouble + LAPACK sets the gate), and the loop (orc_icp_p2plane_f64; the numpy / LAPACK
+loop of ref_numpy.py sets the gate).  The conditions on the clouds -- that a fused multiply-add or a float covariance would be
+seen -- are asserted on the references alone in tests/test_oracle.py; the 28 plane sums of the single-pair fp64 routes are in
+tests/test_gpu_moments.py (test_full_rows_fp64_point_to_plane).
+"""
+import numpy as np
+import pytest
+
+import clouds as cl
+import ref_numpy
+from test_gpu_batch_plane import KNN_M, degenerate_pair, five_pairs, knn_models
+from test_gpu_moments import fresh_context
+
+pytestmark = pytest.mark.gpu
+
+_ORC = {}      # oracle neighbours / normals, once per cloud
+
+
+def reference(orc, M):
+    """(neighbours, normals, covariance (m,3,3)) of a float64 model by the oracle"""
+    assert M.dtype == np.float64
+    key = (M.shape[0], M.tobytes())
+    if key not in _ORC:
+        nbr = orc.knn4(M)
+        nrm, A = orc.normals(M, nbr)
+        _ORC[key] = (nbr, nrm, ref_numpy.symmetric(A))
+    return _ORC[key]
+
+
+def far_patch():
+    return cl.far_surface(cl.FAR_OFF, cl.FAR_H)
+
+
+def near_patch():
+    return cl.far_surface(cl.NEAR_OFF, cl.NEAR_H)
+
+
+def batch_of_models(ctx, models):
+    """neighbours and normals of every model by one float64 batch"""
+    D = np.zeros((1, 3), dtype=np.float64)
+    with ctx.batch([(D, M) for M in models]) as bt:
+        return bt.estimate_normals(want_neighbours=True)
+
+
+# ---- a. neighbours ---------------------------------------------------------------------------------------------------------------
+# model sizes around the granules of knn4_kernel<double, 1024>: 256 queries per block (255 .. 257, 1023 .. 1025), an LDS tile of
+# 1024 model points (1023 .. 1025, 2049: a third tile of one point; 4097: a fifth), the model padded to 16 (1039 .. 1041)
+SINGLE_M = (5, 6, 17, 255, 256, 257, 1023, 1024, 1025, 1039, 1040, 1041, 2049, 4097)
+
+
+def special_models():
+    return [cl.fused_tie_lattice(np.float64, 1), cl.fused_tie_lattice(np.float64, 3), far_patch()]
+
+
+def test_neighbours_single_pair_against_oracle(ctx, orc):
+    models = knn_models(np.float64, SINGLE_M) + special_models()
+    assert [M.shape[0] for M in models[:len(SINGLE_M)]] == list(SINGLE_M) and models[len(SINGLE_M)].shape[0] == 300
+    assert not np.array_equal(models[3], models[3].astype(np.float32))   # mantissas that fp32 cannot hold
+    for M in models:
+        ctx.set_model(M)
+        _, nbr = ctx.estimate_normals(want_neighbours=True)
+        assert nbr.dtype == np.int32 and np.array_equal(nbr, reference(orc, M)[0]), f"m={M.shape[0]}: neighbours differ from orc_knn4_f64"
+
+
+def test_neighbours_batch_against_oracle(ctx, orc):
+    models = knn_models(np.float64) + special_models()
+    assert [M.shape[0] for M in models[:len(KNN_M)]] == list(KNN_M)
+    _, nbr = batch_of_models(ctx, models)
+    for M, got in zip(models, nbr):
+        assert np.array_equal(got, reference(orc, M)[0]), f"m={M.shape[0]}: neighbours differ from orc_knn4_f64"
+
+
+def test_far_patch_neighbours_need_double(orc):
+    """(no device) on the far patch the float cast has other neighbours: a device that computed in float could not pass the two above"""
+    S = far_patch()
+    assert (orc.knn4(S.astype(np.float32)) != reference(orc, S)[0]).any(axis=1).mean() > 0.9
+
+
+# ---- b. fp64 matching where one ulp decides ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sparse", ["1", "0"])
+def test_matching_on_the_fused_tie_lattice(pkg, orc, monkeypatch, sparse):
+    """Q: the tiled lattice; P: the cell centres at which the separately rounded distance ties at the minimum
+    (clouds.fused_tie_centres -- a fused multiply-add changes 28 % / 15 % of their answers, test_oracle.py), and the plain centres
+    (0.05, 0.05, 0.05) behind them.  ICP_F64_SPARSE=1: nn_match_row64_f64, =0: the dense fp64 kernel; and one pass of a batch."""
+    Q = cl.fused_tie_lattice(np.float64, 3)
+    P = np.concatenate([cl.fused_tie_centres(Q), Q + 0.05])
+    want = orc.nn(P, Q)
+    with fresh_context(pkg, monkeypatch, {"ICP_F64_SPARSE": sparse}) as c:
+        got = c.Matching(P, Q)
+        assert np.array_equal(got, want), f"{(got != want).sum()} of {len(P)} matches differ from orc_nn_f64"
+        with c.batch([(P, Q), (P[::-1].copy(), Q)]) as bt:
+            bt.begin(max_iter=1, tol=0.0, fixed_iterations=True)
+            assert bt.run(1)[0] == 1
+            idx = bt.get_indices()
+        assert np.array_equal(idx[0], want) and np.array_equal(idx[1], want[::-1])
+
+
+# ---- c. normals ------------------------------------------------------------------------------------------------------------------
+U = 2.0 ** -53
+DEFINED_MIN = {"knn": 0.85, "grid": 0.95, "far": 0.99, "near": 0.99}   # measured from the oracle's covariances: 0.8567 (the 40 coincident
+# points and their neighbours), 1.0 on the other random models, 0.9625, 0.9981, 0.9981; the gates sit just below
+
+
+def normal_clouds(pkg):
+    out = [("knn", M) for M in knn_models(np.float64)]
+    out += [("grid", pkg.datasets.synthetic_grid(40, np.float64)), ("far", far_patch()), ("near", near_patch())]
+    return out
+
+
+def normal_measures(n, want, A, w, ok):
+    """(unit length, Rayleigh quotient, residual, angle [deg] where the direction is defined): the four figures a set of normals is
+    judged by, against the oracle's covariance A and normals `want`; Rayleigh and residual relative to the largest |eigenvalue|"""
+    n = np.asarray(n, dtype=np.float64)
+    scale = np.maximum(np.abs(w).max(axis=1), 1e-300)
+    w_min = w[np.arange(len(w)), np.abs(w).argmin(axis=1)]
+    ray = np.einsum("ni,nij,nj->n", n, A, n)
+    resid = np.linalg.norm(np.einsum("nij,nj->ni", A, n) - ray[:, None] * n, axis=1)
+    return np.array([np.abs(np.linalg.norm(n, axis=1) - 1.0).max(), (np.abs(ray - w_min) / scale).max(), (resid / scale).max(),
+                     ref_numpy.angle_deg(n[ok], want[ok]).max() if ok.any() else 0.0])
+
+
+def check_normals(kind, M, nrm, orc):
+    """the device's normals against orc_normals_f64 in the form of test_normals_match_oracle_up_to_sign; the gate is 16 x N, N = the
+    same four figures of the second reference (np.longdouble mean and covariance, LAPACK's eigh), not below the unit roundoff.
+    Returns (N, device figures, gate)."""
+    nbr, want, A = reference(orc, M)
+    w = np.linalg.eigvalsh(A)
+    ok = (w[:, 1] - w[:, 0]) > 1e-3 * np.maximum(w[:, 2], 1e-300)
+    assert ok.mean() >= DEFINED_MIN[kind], (kind, M.shape[0], ok.mean())
+    N = normal_measures(ref_numpy.normals_longdouble(M, nbr)[0], want, A, w, ok)
+    gate = 16.0 * np.maximum(N, [U, U, U, np.degrees(U)])
+    got = normal_measures(nrm, want, A, w, ok)
+    what = f"{kind} m={M.shape[0]}: (unit, Rayleigh, residual, angle deg) device {got} second reference {N} gate {gate}"
+    print("[normals f64] " + what)
+    assert (got <= gate).all(), what
+    zero = np.abs(A).max(axis=(1, 2)) == 0   # coincident neighbourhood: both sides fall back to the same axis
+    if zero.any():
+        assert np.abs(np.abs((nrm[zero] * want[zero]).sum(axis=1)) - 1.0).max() < 1e-6
+    return N, got, gate
+
+
+def test_normals_against_the_double_reference(ctx, pkg, orc):
+    """The four figures: unit length, Rayleigh quotient and residual (both relative to the largest eigenvalue), and the angle to
+    orc_normals_f64 in degrees where the direction is defined.  Measured:
+        N, the second reference, largest over the 19 clouds:   1.1e-15   8.3e-16   6.4e-16   3.8e-12 deg
+        N on the far patch:                                     1.0e-15   4.4e-16   5.6e-16   3.1e-12 deg
+        device (MI355X), largest over the clouds:               6.7e-16   6.9e-16   7.6e-16   9.9e-13 deg
+        device, worst ratio to its cloud's gate of 16 N:        0.094     0.081     0.099     0.137
+    The angle gate on the far patch is 16 x 3.1e-12 = 4.9e-11 deg (asserted below 0.1 deg; the device is at 3.2e-13 deg there).
+    With mean and covariance formed in float, as pca_normal<double> did before, the device is a median of 35 deg and up to 89 deg
+    off on that patch (and 6.5e-6 deg off already on the 5-point model at the origin)."""
+    clouds = normal_clouds(pkg)
+    models = [M for _, M in clouds]
+    b_nrm, b_nbr = batch_of_models(ctx, models)
+    worst = np.zeros(4)
+    for (kind, M), bn, bb in zip(clouds, b_nrm, b_nbr):
+        ctx.set_model(M)
+        nrm, nbr = ctx.estimate_normals(want_neighbours=True)
+        assert nrm.dtype == np.float64 and np.array_equal(nbr, reference(orc, M)[0])
+        N, got, gate = check_normals(kind, M, nrm, orc)
+        worst = np.maximum(worst, got / gate)
+        if kind == "far":
+            assert gate[3] < 0.1, gate
+        assert np.array_equal(bb, nbr) and bn.tobytes() == nrm.tobytes(), f"{kind} m={M.shape[0]}: the batch's normals differ in their bits"
+    print(f"[normals f64] worst device / gate (unit, Rayleigh, residual, angle): {worst}")
+
+
+# ---- d. the loop -----------------------------------------------------------------------------------------------------------------
+GATE_L = 100 * ref_numpy.PLANE_F64_L     # 2.7e-13: T, the error series and the moved cloud, absolute
+MAX_ITER, TOL = 50, 1e-5
+
+
+@pytest.fixture(scope="module")
+def plane64(pkg, orc, golden):
+    """the five pairs in float64, orc_normals_f64's normals and orc_icp_p2plane_f64's runs -- shared, never modified"""
+    pairs = cl.widen_pairs(five_pairs(pkg, golden))
+    normals = [reference(orc, M)[1] for _, M in pairs]
+    wants = [orc.icp_p2plane_f64(D, M, N, MAX_ITER, TOL) for (D, M), N in zip(pairs, normals)]
+    print("[plane f64] oracle iterations:", [w["iterations"] for w in wants], "passes:", [w["passes"] for w in wants])
+    for w in wants:   # the oracle's own stop decisions sit far from the tolerance: the iteration counts must be equal
+        E = w["err"]
+        assert w["iterations"] >= 1 and (np.abs(E[1:] - TOL) > 1e-6).all() and (np.abs(np.abs(np.diff(E)) - TOL) > 1e-6).all(), E
+    return pairs, normals, wants
+
+
+def assert_same_run(res, want, what):
+    assert res["iterations"] == want["iterations"] and res["passes"] == want["passes"], (what, res["iterations"], res["passes"])
+    assert np.array_equal(res["idx"], want["idx"]), what
+    worst = max(float(np.abs(res["T"] - want["T"]).max()), float(np.abs(res["err"] - want["err"]).max()),
+                float(np.abs(res["moved"] - want["moved"]).max()))
+    print(f"[plane f64] {what}: max |device - oracle| over T, err, moved = {worst:.3e} ({worst / GATE_L:.3f} of the gate)")
+    assert worst <= GATE_L, (what, worst)
+    return worst
+
+
+def as_dict(r):
+    return dict(iterations=r.iterations, passes=r.passes, idx=r.idx, T=r.T, err=r.err, moved=r.moved)
+
+
+@pytest.mark.parametrize("sparse", ["1", "0"])
+def test_loop_single_pair_against_oracle(pkg, monkeypatch, plane64, sparse):
+    pairs, normals, wants = plane64
+    with fresh_context(pkg, monkeypatch, {"ICP_F64_SPARSE": sparse}) as c:
+        for k, ((D, M), N, want) in enumerate(zip(pairs, normals, wants)):
+            res = c.point_to_plane(D, M, normals=N, max_iter=MAX_ITER, tol=TOL)
+            assert res.moved.dtype == np.float64
+            assert_same_run(as_dict(res), want, f"single pair {k}, ICP_F64_SPARSE={sparse}")
+
+
+def test_loop_batch_against_oracle(ctx, pkg, plane64):
+    pairs, normals, wants = plane64
+    res = ctx.point_to_plane_batch(pairs, normals=normals, max_iter=MAX_ITER, tol=TOL)
+    for k, (r, want) in enumerate(zip(res, wants)):
+        assert r.extra["status"] == pkg.capi.ICP_OK and r.moved.dtype == np.float64
+        assert_same_run(as_dict(r), want, f"batch pair {k}")
+
+
+def test_loop_stepwise_matches_of_every_pass(ctx, pkg, orc, plane64):
+    """one icp_loop_enqueue + icp_loop_complete per pass: the correspondences of every matching pass are orc_nn_f64's on the cloud
+    the device matched on, and the loop ends where the oracle's does"""
+    pairs, normals, wants = plane64
+    B = pkg.capi
+    for k, ((D, M), N, want) in enumerate(zip(pairs, normals, wants)):
+        ctx.set_model(M)
+        ctx.set_model_normals(N)
+        ctx.set_moving(D)
+        ctx.loop_begin(pkg.ICP_POINT_TO_PLANE, max_iter=MAX_ITER, tol=TOL)
+        matched = 0
+        for _ in range(MAX_ITER + 2):
+            ctx.loop_enqueue()
+            done = ctx.loop_complete()
+            if not ctx.diag_loop_moments()[1] & B.ROUTE_ERROR_ONLY:
+                assert np.array_equal(ctx.get_indices(), orc.nn(ctx.get_moving(), M)), f"pair {k}, pass {matched}"
+                matched += 1
+            if done:
+                break
+        assert done and matched >= want["passes"]
+        st = ctx.loop_state()
+        assert_same_run(dict(st, idx=ctx.loop_indices(), moved=ctx.get_moving()), want, f"step-wise pair {k}")
+
+
+def test_loop_degenerate_pair_is_singular(ctx, pkg, plane64):
+    pairs, normals, _ = plane64
+    (P, Q), N = degenerate_pair()
+    P, Q, N = P.astype(np.float64), Q.astype(np.float64), N.astype(np.float64)
+    with pytest.raises(pkg.IcpError) as e:
+        ctx.point_to_plane(P, Q, normals=N, max_iter=3)
+    assert e.value.code == pkg.capi.ICP_ERR_SINGULAR
+    got = ctx.point_to_plane_batch([pairs[0], (P, Q), pairs[3]], normals=[normals[0], N, normals[3]], max_iter=MAX_ITER, tol=TOL)
+    assert got[1].extra["status"] == pkg.capi.ICP_ERR_SINGULAR and got[1].passes == 0
+    assert got[0].extra["status"] == got[2].extra["status"] == pkg.capi.ICP_OK

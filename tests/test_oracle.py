@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import clouds as cl
 import ref_numpy
 
 
@@ -219,3 +220,130 @@ def test_mkl_minimisation_on_the_hall_pair(orc, mkl, pkg):
     assert np.abs(R2.reshape(9) - mkl["hallmin_R"]).max() < 1e-9 and np.abs(t2 - mkl["hallmin_t"]).max() < 1e-9
     E = orc.rms_error(orc.transform(D64, mkl["hallmin_R"].reshape(3, 3), mkl["hallmin_t"]), Q64, idx)
     assert abs(E - float(mkl["hallmin_E"])) < 1e-12 * max(1.0, E)
+
+
+# ---------------------------------------------------------------------------------------------------
+# (5) the fp64 point-to-plane reference (orc_knn4_f64, orc_normals_f64, orc_p2plane_minimize_f64, orc_icp_p2plane_f64): the
+#     reference has no such program, so nothing but a second opinion can pin it -- numpy for the neighbours and the covariance
+#     (bit for bit, both precisions), numpy + LAPACK for the loop (measurement L) -- and the conditions on the clouds
+#     tests/test_gpu_plane_f64.py leans on, checked on the references alone.
+# ---------------------------------------------------------------------------------------------------
+def _knn_pin_clouds(dtype):
+    out = [cl.ragged_pair(31, 1, 1000)[1], cl.ragged_pair(32, 1, 4097)[1]]
+    g = np.stack(np.meshgrid(np.arange(7.0), np.arange(6.0), np.arange(3.0), indexing="ij"), -1).reshape(-1, 3)
+    g = np.concatenate([g, g[::5], np.zeros((40, 3))])   # a lattice (every distance exact, ties everywhere), duplicates, 40 coincident points
+    out.append(g[np.random.default_rng(9).permutation(len(g))].astype(np.float32))
+    if np.dtype(dtype) == np.float64:   # mantissas that fp32 cannot hold on the random models
+        out = [M.astype(np.float64) + (1e-9 * np.random.default_rng(k).standard_normal(M.shape) if k < 2 else 0.0) for k, M in enumerate(out)]
+    return out
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_knn4_and_covariance_against_numpy(orc, dtype):
+    for M in _knn_pin_clouds(dtype):
+        assert M.dtype == dtype
+        nbr = orc.knn4(M)
+        assert np.array_equal(nbr, ref_numpy.knn4(M)), len(M)
+        nrm, A = orc.normals(M, nbr)
+        assert nrm.dtype == A.dtype == dtype
+        assert A.tobytes() == ref_numpy.covariance4(M, nbr).tobytes(), len(M)
+    if dtype == np.float64:
+        R = _knn_pin_clouds(np.float64)[0]
+        assert not np.array_equal(R, R.astype(np.float32))
+
+
+def test_knn4_f64_beyond_the_fp32_twins_sentinel(orc):
+    # distances above 10000: the fp32 twin's overwrite-by-10000 would hand the same point out again; the fp64 order is stated directly
+    M = 1000.0 * cl.ragged_pair(33, 1, 300)[1].astype(np.float64)
+    nbr = orc.knn4(M)
+    assert np.array_equal(nbr, ref_numpy.knn4(M))
+    assert (np.sort(nbr, axis=1)[:, 1:] != np.sort(nbr, axis=1)[:, :-1]).all() and (nbr != np.arange(300)[:, None]).all()
+
+
+def plane_pairs_f64(pkg, golden):
+    from test_gpu_batch_plane import five_pairs
+    return cl.widen_pairs(five_pairs(pkg, golden))
+
+
+def test_plane_loop_f64_against_numpy(orc, pkg, golden):
+    """measurement L: the largest differences between orc_icp_p2plane_f64 and the numpy / LAPACK loop over the five pairs"""
+    L_T = L_E = L_P = 0.0
+    for D, M in plane_pairs_f64(pkg, golden):
+        N = orc.normals(M, orc.knn4(M))[0]
+        a = orc.icp_p2plane_f64(D, M, N, 50, 1e-5)
+        b = ref_numpy.icp_p2plane(D, M, N, 50, 1e-5)
+        assert a["iterations"] == b["iterations"] >= 1 and a["passes"] == b["passes"]
+        P = D
+        for k in range(a["passes"]):   # the oracle's loop one pass at a time (its only state is the moved cloud): pass k's correspondences
+            step = orc.icp_p2plane_f64(P, M, N, 1, 0.0, fixed=True)
+            assert np.array_equal(step["idx"], b["idx_passes"][k]), k
+            P = step["moved"]
+        assert P.tobytes() == a["moved"].tobytes()
+        assert np.array_equal(a["idx"], b["idx"])
+        L_T = max(L_T, float(np.abs(a["T"] - b["T"]).max()))
+        L_E = max(L_E, float(np.abs(a["err"] - b["err"]).max()))
+        L_P = max(L_P, float(np.abs(a["moved"] - b["moved"]).max()))
+        rc, R, t, Cm, bb = orc.p2plane_minimize_f64(D, M, orc.nn(D, M), N)
+        R2, t2 = ref_numpy.p2plane_minimize(D, M, orc.nn(D, M), N)
+        assert rc == 0 and np.abs(R - R2).max() < 1e-12 and np.abs(t - t2).max() < 1e-12
+    print(f"[plane f64] measurement L: max |T - T'| = {L_T:.3e}, max |E - E'| = {L_E:.3e}, max |moved - moved'| = {L_P:.3e}")
+    # the device is given 100 x the recorded L (tests/test_gpu_plane_f64.py); that must stay within the project's fp64 gate, 1e-9
+    assert max(L_T, L_E, L_P) <= ref_numpy.PLANE_F64_L and 100 * ref_numpy.PLANE_F64_L <= 1e-9
+
+
+def _changed_share(ref_rows, fused_rows):
+    return float((np.asarray(ref_rows).reshape(len(ref_rows), -1) != np.asarray(fused_rows).reshape(len(ref_rows), -1)).any(axis=1).mean())
+
+
+@pytest.mark.parametrize("tiles", [1, 3])
+def test_fused_tie_lattice_separates_fused_distances(orc, tiles):
+    """the condition on the cloud: a fused multiply-add in the fp64 distance changes the ordered neighbour list of at least 5 % of
+    the points -- exact rationals rounded once, against the separately rounded reference (measured: 9 % and 10 % of the 86 points,
+    7 % and 9 % of the 774)"""
+    Q = cl.fused_tie_lattice(np.float64, tiles)
+    assert Q.shape == (86 * tiles * tiles, 3)
+    ref = orc.knn4(Q)
+    assert np.array_equal(ref, ref_numpy.knn4(Q))
+    for form, name in enumerate(ref_numpy.FUSED_FORMS):
+        share = _changed_share(ref, ref_numpy.order_fused(Q, Q, form, 5)[:, 1:])
+        print(f"[fused ties] {len(Q)} points, kNN(4), {name}: {share:.3f} of the rows change")
+        assert share >= 0.05, (name, share)
+
+
+def test_fused_tie_centres_separate_fused_distances(orc):
+    """the same condition for the matching use: the fused forms change the reference's nearest model point on at least 5 % of the
+    moving points (measured: 28 % and 15 % of 359)"""
+    Q = cl.fused_tie_lattice(np.float64, 3)
+    P = cl.fused_tie_centres(Q)
+    assert P.shape[0] >= 300
+    ref = orc.nn(P, Q)
+    assert np.array_equal(ref, ref_numpy.nn(P, Q)) and np.array_equal(ref, ref_numpy.nn_chunked(P, Q))
+    for form, name in enumerate(ref_numpy.FUSED_FORMS):
+        share = _changed_share(ref, ref_numpy.order_fused(P, Q, form, 1))
+        print(f"[fused ties] {len(P)} moving points, matching, {name}: {share:.3f} of the rows change")
+        assert share >= 0.05, (name, share)
+
+
+def far_surface_references(orc, off, h):
+    """(cloud, neighbours, normals, covariance (m,3,3), eigenvalues ascending, defined mask) of clouds.far_surface by the oracle"""
+    S = cl.far_surface(off, h)
+    nbr = orc.knn4(S)
+    nrm, A = orc.normals(S, nbr)
+    A = ref_numpy.symmetric(A)
+    w = np.linalg.eigvalsh(A)
+    return S, nbr, nrm, A, w, (w[:, 1] - w[:, 0]) > 1e-3 * np.maximum(w[:, 2], 1e-300)
+
+
+def test_far_surface_conditions(orc):
+    """the far patch cannot be passed by accident: nearly every normal is defined, a kernel that forms mean and covariance in float
+    is tens of degrees off (measured: median 35 deg, share defined 0.998), and the neighbours of the float cast are other points"""
+    S, nbr, nrm, A, w, ok = far_surface_references(orc, cl.FAR_OFF, cl.FAR_H)
+    assert ok.mean() >= 0.99, ok.mean()
+    ang = ref_numpy.angle_deg(ref_numpy.normals_float_cast(S, nbr), nrm)
+    print(f"[far patch] defined {ok.mean():.4f}; float-cast covariance: median angle {np.median(ang):.2f} deg, max {ang.max():.2f} deg")
+    assert np.median(ang) > 5.0
+    assert not np.array_equal(orc.knn4(S.astype(np.float32)), nbr)
+    # the same patch at the origin, edge 1: float would do -- the far patch is what tells the two apart
+    S0, nbr0, nrm0, _, _, ok0 = far_surface_references(orc, cl.NEAR_OFF, cl.NEAR_H)
+    assert ok0.mean() >= 0.99
+    assert np.median(ref_numpy.angle_deg(ref_numpy.normals_float_cast(S0, nbr0), nrm0)) < 1e-3

@@ -97,9 +97,11 @@ def test_tolerance_sees_one_point_p2p(orc, n, m):
 
 @pytest.mark.parametrize("n,m", PLANE_CLOUDS)
 def test_tolerance_sees_one_point_plane(orc, n, m):
-    D, M = cl.case_pair(n, m)
-    Nrm = _normals(orc, M)
-    idx = orc.nn(D, M)
-    _, maj = rm.plane(D, M, Nrm, idx, P_new=D, idx_prev=idx)
-    terms = rm.plane_point_terms(D, M, Nrm, idx, idx_prev=idx)
-    assert _seen_fraction(terms, rm.tolerance(maj, n), list((rm.ERR, rm.CNT) + rm.PLANE_SLOTS)) >= 0.99
+    # float64: the clouds of test_full_rows_fp64_point_to_plane and the float64 batch (rows of 64), with the fp32 model's normals cast
+    for dtype in (np.float32, np.float64) if n in cl.ROW64_N + cl.BATCH_N else (np.float32,):
+        D, M = cl.case_pair(n, m, dtype)
+        Nrm = _normals(orc, cl.case_pair(n, m)[1]).astype(dtype)
+        idx = orc.nn(D, M)
+        _, maj = rm.plane(D, M, Nrm, idx, P_new=D, idx_prev=idx)
+        terms = rm.plane_point_terms(D, M, Nrm, idx, idx_prev=idx)
+        assert _seen_fraction(terms, rm.tolerance(maj, n), list((rm.ERR, rm.CNT) + rm.PLANE_SLOTS)) >= 0.99
