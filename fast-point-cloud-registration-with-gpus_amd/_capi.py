@@ -100,6 +100,7 @@ SIGNATURES = {
     "icp_batch_get_indices": (_i, [_vp, _pi32]),
     "icp_batch_loop_indices": (_i, [_vp, _pi32]),
     "icp_batch_set_max_distance": (_i, [_vp, _pd]),
+    "icp_batch_set_initial_transforms": (_i, [_vp, _pd]),
     "icp_batch_get_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_batch_loop_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_point_to_point_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),

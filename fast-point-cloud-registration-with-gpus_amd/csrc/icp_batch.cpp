@@ -10,6 +10,12 @@
 // its top bit for the next pass's error (and for the mask downloads), and a pass that keeps nothing ends its pair with
 // ICP_ERR_EMPTY.  Launches and downloads per step stay as above; a batch without thresholds runs the ungated kernels.
 //
+// A batch may hold an initial transform per pair (icp_batch_set_initial_transforms).  icp_batch_begin then makes every pair's
+// start cloud with ONE launch (batch_init_kernel: apply_rt of the transform rounded to the batch's precision, T0F, on the
+// clouds as uploaded) in place of the P0 -> P copy, and reads one flag per pair back: a pair whose start cloud left the
+// precision's range begins ended (ICP_ERR_INVALID).  The loops know nothing of it -- from the start cloud on a pair runs as
+// in a batch created from that cloud -- and icp_batch_state composes T_loop . T0F when it is read.  The steps are unchanged.
+//
 // Point-to-plane needs the model normals of every pair, in planes laid out as the models: given by the caller
 // (icp_batch_set_model_normals) or made on the device by ONE neighbour launch + ONE normals launch for the whole batch
 // (icp_batch_estimate_normals: knn4_batch + normals_batch_kernel, icp_k_plane.hip).  The reference estimates them once per
@@ -46,6 +52,10 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     bool have_normals = false;
     DevBuf thr;                              // the gate: every pair's squared maximum correspondence distance, in the batch's precision
     bool gated = false;                      // the batch holds thresholds (icp_batch_set_max_distance): the passes run the gated kernels
+    DevBuf rt0, init_kind, init_flag;        // initial transforms: R, t of every pair in the batch's precision, BATCH_INIT_APPLY / _COPY, the start cloud is not finite
+    bool have_init = false;                  // the batch holds initial transforms (icp_batch_set_initial_transforms)
+    std::vector<double> T0F;                 // count x 16: every pair's transform as rounded to the batch's precision, read back in double
+    std::vector<char> init_copy;             // the pair's 16 doubles were exactly the identity: its cloud is copied, its T is the loop's
     int metric = ICP_POINT_TO_POINT;         // of the loop under way
     void* h_ctl = nullptr;                   // pinned: R, t of every pair (12 values of the precision), then its mode (int)
     double* h_mom = nullptr;                 // pinned: count x ICP_NMOM
@@ -81,7 +91,7 @@ int ready(icp_batch* b)
 
 void release(icp_batch* b)
 {
-    for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr})
+    for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag})
         d->release();
     if (b->h_ctl) (void)hipHostFree(b->h_ctl);
     if (b->h_mom) (void)hipHostFree(b->h_mom);
@@ -345,7 +355,24 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
     b->last_match.assign((size_t)b->count, 0);
     b->applied_buf.assign((size_t)b->count, 0);
     b->mom_seen.assign((size_t)b->count, 0);
-    HIP_TRY(hipMemcpyAsync(b->P.p, b->P0.p, 3 * (size_t)b->p_plane * b->esize, hipMemcpyDeviceToDevice, b->ctx->stream));
+    if (b->have_init) {
+        // the start cloud of every pair in one launch, and one flag per pair back: a finite transform can carry a finite cloud
+        // out of the precision's range, and the library refuses non-finite clouds at the door -- that pair begins ended
+        hipStream_t st = b->ctx->stream;
+        std::vector<int> flag((size_t)b->count, 0);
+        HIP_TRY(hipMemsetAsync(b->init_flag.p, 0, flag.size() * sizeof(int), st));
+        HIP_TRY(icp::launch_batch_init(b->prec, (const icp::BatchItem*)b->items.p, b->n_items, (const icp::BatchPair*)b->pairs_d.p,
+                                       (const int*)b->init_kind.p, b->rt0.p, b->P0.p, b->P.p, b->p_plane, (int*)b->init_flag.p, st));
+        HIP_TRY(hipMemcpyAsync(flag.data(), b->init_flag.p, flag.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int p = 0; p < b->count; ++p)
+            if (flag[p]) {
+                b->status[p] = ICP_ERR_INVALID;
+                b->H[p].done = true;
+            }
+    } else {
+        HIP_TRY(hipMemcpyAsync(b->P.p, b->P0.p, 3 * (size_t)b->p_plane * b->esize, hipMemcpyDeviceToDevice, b->ctx->stream));
+    }
     b->steps = 0;
     b->begun = true;
     return ICP_OK;
@@ -386,7 +413,19 @@ int icp_batch_state(icp_batch* b, int pair, int* status, int* iterations, int* p
         const int cnt = (int)H.err.size() < err_cap ? (int)H.err.size() : err_cap;
         for (int i = 0; i < cnt; ++i) err[i] = H.err[i];
     }
-    if (T16) std::memcpy(T16, H.T, sizeof H.T);
+    if (T16) {
+        if (b->have_init && !b->init_copy[pair]) {   // T = T_loop . T0F, the product in HostLoop::note_applied's order
+            const double* T0 = b->T0F.data() + (size_t)pair * 16;
+            for (int a = 0; a < 4; ++a)
+                for (int c = 0; c < 4; ++c) {
+                    double s = 0;
+                    for (int k = 0; k < 4; ++k) s += H.T[a * 4 + k] * T0[k * 4 + c];
+                    T16[a * 4 + c] = s;
+                }
+        } else {
+            std::memcpy(T16, H.T, sizeof H.T);
+        }
+    }
     return ICP_OK;
 }
 
@@ -457,6 +496,63 @@ int icp_batch_set_max_distance(icp_batch* b, const double* max_dist)
         b->begun = false;
         b->gated = false;
     }
+    return ICP_OK;
+}
+
+int icp_batch_set_initial_transforms(icp_batch* b, const double* T16)
+{
+    if (int rc = ready(b)) return rc;
+    if (!T16) {
+        b->begun = false;
+        b->have_init = false;
+        return ICP_OK;
+    }
+    static const double ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    for (int p = 0; p < b->count; ++p) {
+        const double* T = T16 + (size_t)p * 16;
+        for (int k = 0; k < 16; ++k)
+            if (!std::isfinite(T[k]) || (b->prec == ICP_F32 && !std::isfinite((float)T[k])))   // (finite in the batch's precision too)
+                return fail(ICP_ERR_INVALID, "an initial transform has a NaN or an infinite value: pair " + std::to_string(p));
+        if (!(T[12] == 0.0 && T[13] == 0.0 && T[14] == 0.0 && T[15] == 1.0))
+            return fail(ICP_ERR_INVALID, "the bottom row of an initial transform must be exactly 0 0 0 1: pair " + std::to_string(p));
+    }
+    // the 12 values of a pair, rounded once to the batch's precision (T0F: that matrix read back in double); a pair whose 16
+    // doubles are the identity bit for bit is copied, not multiplied
+    std::vector<char> rt((size_t)b->count * 12 * b->esize);
+    std::vector<int> kind((size_t)b->count);
+    std::vector<double> T0F((size_t)b->count * 16);
+    std::vector<char> copy((size_t)b->count);
+    for (int p = 0; p < b->count; ++p) {
+        const double* T = T16 + (size_t)p * 16;
+        double* o = T0F.data() + (size_t)p * 16;
+        copy[p] = std::memcmp(T, ident, sizeof ident) == 0 ? 1 : 0;
+        kind[p] = copy[p] ? icp::BATCH_INIT_COPY : icp::BATCH_INIT_APPLY;
+        double R[9], t[3];
+        for (int a = 0; a < 3; ++a) {
+            for (int c = 0; c < 3; ++c) R[a * 3 + c] = T[a * 4 + c];
+            t[a] = T[a * 4 + 3];
+        }
+        void* dst = rt.data() + (size_t)p * 12 * b->esize;
+        if (b->prec == ICP_F64) put_rt<double>(dst, R, t);
+        else put_rt<float>(dst, R, t);
+        for (int a = 0; a < 3; ++a) {
+            for (int c = 0; c < 3; ++c) o[a * 4 + c] = b->prec == ICP_F64 ? R[a * 3 + c] : (double)(float)R[a * 3 + c];
+            o[a * 4 + 3] = b->prec == ICP_F64 ? t[a] : (double)(float)t[a];
+        }
+        o[12] = o[13] = o[14] = 0.0;
+        o[15] = 1.0;
+    }
+    HIP_TRY(b->rt0.ensure(rt.size()));
+    HIP_TRY(b->init_kind.ensure(kind.size() * sizeof(int)));
+    HIP_TRY(b->init_flag.ensure(kind.size() * sizeof(int)));
+    b->begun = false;   // a loop under way is discarded: it started from another cloud
+    b->have_init = false;
+    HIP_TRY(hipMemcpyAsync(b->rt0.p, rt.data(), rt.size(), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(b->init_kind.p, kind.data(), kind.size() * sizeof(int), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
+    b->T0F.swap(T0F);
+    b->init_copy.swap(copy);
+    b->have_init = true;
     return ICP_OK;
 }
 

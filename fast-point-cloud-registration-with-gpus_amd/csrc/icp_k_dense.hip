@@ -1072,4 +1072,48 @@ hipError_t launch_batch_pass(int precision, int metric, const BatchItem* items, 
     return hipGetLastError();
 }
 
+// the start cloud of every pair of a batch that holds initial transforms (icp_batch_begin): P = apply_rt(rt0[pair], P0) -- the
+// front end's own arithmetic, so a loop from here is the loop of a batch created from this cloud -- or P0's bytes for a pair
+// whose kind is BATCH_INIT_COPY (the exact identity: a -0.0 stays a -0.0).  Reads P0 and writes P, as the copy it replaces.
+// One wave per work item (four items per block), one point per lane; the padding between the clouds is not touched.  A
+// transformed point with a NaN or an infinite coordinate raises its pair's flag (zero before the launch): a plain vector store
+// of 1 from every such lane, whoever comes last.
+template <typename F>
+__global__ __launch_bounds__(NN_BLOCK) void batch_init_kernel(const BatchItem* __restrict__ items, int n_items,
+                                                              const BatchPair* __restrict__ pairs, const int* __restrict__ kind,
+                                                              const RT<F>* __restrict__ rt0, const F* __restrict__ P0,
+                                                              F* __restrict__ P, long long p_plane, int* __restrict__ nonfinite)
+{
+    const int item = blockIdx.x * (NN_BLOCK / BATCH_ITEM) + (threadIdx.x >> 6);
+    if (item >= n_items) return;
+    const BatchItem it = items[item];
+    const int lane = threadIdx.x & 63;
+    if (lane >= it.count) return;
+    const long long gi = pairs[it.pair].p_off + it.first + lane;
+    F x = P0[gi], y = P0[p_plane + gi], z = P0[2 * p_plane + gi];
+    if (kind[it.pair] != BATCH_INIT_COPY) {
+        apply_rt<F>(rt0[it.pair], x, y, z, x, y, z);
+        // (x - x is 0 for every finite x, NaN for NaN and for +-inf)
+        const bool finite = (x - x) == F(0) && (y - y) == F(0) && (z - z) == F(0);
+        if (!finite) nonfinite[it.pair] = 1;
+    }
+    P[gi] = x;
+    P[p_plane + gi] = y;
+    P[2 * p_plane + gi] = z;
+}
+
+hipError_t launch_batch_init(int precision, const BatchItem* items, int n_items, const BatchPair* pairs, const int* kind, const void* rt0,
+                             const void* P0, void* P, long long p_plane, int* nonfinite, hipStream_t st)
+{
+    if (n_items <= 0) return hipSuccess;
+    const int nb = (n_items + NN_BLOCK / BATCH_ITEM - 1) / (NN_BLOCK / BATCH_ITEM);
+    if (precision == ICP_F64)
+        hipLaunchKernelGGL((batch_init_kernel<double>), dim3(nb), dim3(NN_BLOCK), 0, st, items, n_items, pairs, kind, (const RT<double>*)rt0,
+                           (const double*)P0, (double*)P, p_plane, nonfinite);
+    else
+        hipLaunchKernelGGL((batch_init_kernel<float>), dim3(nb), dim3(NN_BLOCK), 0, st, items, n_items, pairs, kind, (const RT<float>*)rt0,
+                           (const float*)P0, (float*)P, p_plane, nonfinite);
+    return hipGetLastError();
+}
+
 }  // namespace icp

@@ -388,6 +388,13 @@ hipError_t launch_batch_pass(int precision, int metric, const BatchItem* items, 
                              const int* mode, const void* rt /* RT<F>[n_pairs] */, void* P_soa, long long p_plane, const void* Q_soa,
                              const void* N_soa, long long q_plane, const int32_t* idx_prev, int32_t* idx_cur, double* partials,
                              double* mom, const void* thr, hipStream_t st);
+// the start cloud of a batch that holds initial transforms, in one launch over the same items: P[pair] = apply_rt(rt0[pair],
+// P0[pair]), or P0[pair]'s bytes where kind[pair] == BATCH_INIT_COPY; nonfinite[pair] (int[n_pairs], zero before the launch)
+// becomes 1 where a transformed point of the pair has a NaN or an infinite coordinate.  The padding of P is not written.
+constexpr int BATCH_INIT_APPLY = 0, BATCH_INIT_COPY = 1;
+hipError_t launch_batch_init(int precision, const BatchItem* items, int n_items, const BatchPair* pairs, const int* kind,
+                             const void* rt0 /* RT<F>[n_pairs] */, const void* P0_soa, void* P_soa, long long p_plane, int* nonfinite,
+                             hipStream_t st);
 // the neighbours and normals of every pair's model: q_items = work items of BATCH_ITEM MODEL points (BatchItem::first / count
 // within the pair's model); one knn4_batch launch (nbr[(q_off + i) * 4 ..]: indices within the pair's model) + one
 // normals_batch_kernel launch (Nrm_soa laid out as Q_soa)

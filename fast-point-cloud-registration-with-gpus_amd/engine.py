@@ -257,14 +257,16 @@ class Context:
         """a Batch of (D, M) pairs of one dtype, uploaded once (see Batch)"""
         return Batch(self, pairs)
 
-    def point_to_point_batch(self, pairs, max_iter=40, tol=1e-6, fixed_iterations=False, max_distance=None):
+    def point_to_point_batch(self, pairs, max_iter=40, tol=1e-6, fixed_iterations=False, max_distance=None, init=None):
         """point_to_point for every (D, M) of `pairs` (one dtype) in one batched registration; a list of Result in pair order,
         each exactly what point_to_point gives for that pair alone (extra["status"]: ICP_OK or the code that ended its loop).
         max_distance (a scalar or one value per pair, inf = that pair is not gated): a match farther away than that pulls on
         nothing (Batch.set_max_distance); extra["inliers"] is then the mask of the last contributing pass and extra["fitness"]
-        the share of the points it kept"""
-        if max_distance is not None:
-            return self._run_batch_gated(capi.ICP_POINT_TO_POINT, pairs, None, max_iter, tol, fixed_iterations, max_distance)
+        the share of the points it kept.
+        init (one (4, 4) for every pair, or (count, 4, 4)): the pose every pair starts from (Batch.set_initial_transforms); the
+        gate then acts on distances measured after it, and Result.T includes it.  Runs through a Batch as max_distance does."""
+        if max_distance is not None or init is not None:
+            return self._run_batch_gated(capi.ICP_POINT_TO_POINT, pairs, None, max_iter, tol, fixed_iterations, max_distance, init)
         return self._run_batch(capi.ICP_POINT_TO_POINT, pairs, None, max_iter, tol, fixed_iterations)
 
     def point_to_plane_batch(self, pairs, normals=None, max_iter=50, tol=1e-6, fixed_iterations=False):
@@ -272,14 +274,15 @@ class Context:
         array per pair, or None (then estimated on the device: one neighbour launch + one normals launch for all pairs)"""
         return self._run_batch(capi.ICP_POINT_TO_PLANE, pairs, normals, max_iter, tol, fixed_iterations)
 
-    def point_to_plane_batch_gated(self, pairs, max_distance, normals=None, max_iter=50, tol=1e-6, fixed_iterations=False):
+    def point_to_plane_batch_gated(self, pairs, max_distance, normals=None, max_iter=50, tol=1e-6, fixed_iterations=False, init=None):
         """point_to_plane_batch with a maximum correspondence distance (a scalar or one value per pair; the gate is on the Euclidean
-        distance to the matched point), as point_to_point_batch(max_distance=...): extra["inliers"], extra["fitness"].
+        distance to the matched point), as point_to_point_batch(max_distance=...): extra["inliers"], extra["fitness"]; init as there.
         (point_to_plane_batch itself keeps its parameter list, which tests/test_batch_plane_abi.py holds fixed.)"""
-        return self._run_batch_gated(capi.ICP_POINT_TO_PLANE, pairs, normals, max_iter, tol, fixed_iterations, max_distance)
+        return self._run_batch_gated(capi.ICP_POINT_TO_PLANE, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init)
 
-    def _run_batch_gated(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance):
-        """the one-call functions have no gate: create, [normals], set_max_distance, begin, run to the end, results"""
+    def _run_batch_gated(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init=None):
+        """the one-call functions have neither a gate nor initial transforms: create, [normals], set_max_distance,
+        set_initial_transforms, begin, run to the end, results"""
         with Batch(self, pairs) as bt:
             if metric == capi.ICP_POINT_TO_PLANE:
                 if normals is not None:
@@ -287,6 +290,7 @@ class Context:
                 else:
                     bt.estimate_normals()
             bt.set_max_distance(max_distance)
+            bt.set_initial_transforms(init)
             bt.begin(max_iter=max_iter, tol=tol, fixed_iterations=fixed_iterations, metric=metric)
             while bt.run(1 << 20)[1] > 0:
                 pass
@@ -513,8 +517,24 @@ class Batch:
             raise ValueError("one maximum distance per pair (or a scalar)")
         capi.check(self._lib.icp_batch_set_max_distance(self._h, a.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_max_distance")
 
+    def set_initial_transforms(self, T):
+        """the pose every pair's registration starts from: one (4, 4) for every pair, (count, 4, 4), or None (none).  Rounded once
+        to the batch's dtype and applied to the uploaded clouds by every begin (they do not compound); state()["T"] includes
+        it.  Every value finite, every bottom row 0 0 0 1.  Discards a loop under way."""
+        if T is None:
+            capi.check(self._lib.icp_batch_set_initial_transforms(self._h, None), "icp_batch_set_initial_transforms")
+            return
+        a = np.asarray(T, dtype=np.float64)
+        if a.shape == (4, 4):
+            a = np.broadcast_to(a, (self.count, 4, 4))
+        if a.shape != (self.count, 4, 4):
+            raise ValueError("one (4, 4) initial transform for every pair, or (count, 4, 4)")
+        a = np.ascontiguousarray(a)
+        capi.check(self._lib.icp_batch_set_initial_transforms(self._h, a.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_initial_transforms")
+
     def begin(self, max_iter=40, tol=1e-6, fixed_iterations=False, metric=capi.ICP_POINT_TO_POINT):
-        """start every pair's registration from the uploaded clouds (ICP_POINT_TO_PLANE: the batch must hold normals)"""
+        """start every pair's registration from the uploaded clouds, moved by the pair's initial transform where the batch holds
+        any (ICP_POINT_TO_PLANE: the batch must hold normals)"""
         prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(self._dtype), int(metric))
         capi.check(self._lib.icp_batch_begin(self._h, C.byref(prm)), "icp_batch_begin")
         self._max_iter = int(max_iter)

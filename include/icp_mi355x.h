@@ -225,7 +225,8 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *   - a batch uses the context's device and stream and nothing else of it (resident clouds, loop, counters stay as they
  *     were).  It must be destroyed before its context.  While the context has an enqueued pass that is not completed
  *     (icp_loop_enqueue without icp_loop_complete) the batch calls return ICP_ERR_STATE.
- *   - icp_batch_begin starts every pair's registration from the clouds icp_batch_create uploaded.
+ *   - icp_batch_begin starts every pair's registration from the clouds icp_batch_create uploaded (moved by the pair's initial
+ *     transform, where the batch holds any: below).
  *   - point-to-plane needs the unit normals of every pair's model points.  The batch holds one set: the caller's
  *     (icp_batch_set_model_normals) or the one icp_batch_estimate_normals makes on the device -- kNN(4) + PCA exactly as
  *     icp_estimate_normals does for one model (src/CUDA/GPU_point_to_plane_real.cu:54-188,391-423), with ONE neighbour launch
@@ -259,8 +260,34 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *       icp_batch_get_inliers / icp_batch_loop_inliers: one byte per moving point, 1 = that point's match was kept, for the
  *         pass icp_batch_get_indices / icp_batch_loop_indices report, with their errors and ordering (ICP_ERR_STATE before
  *         the first pass and during the context's pending pass).  An ungated batch answers all ones.
- *     Not gated: the single-pair loops (icp_point_to_*, icp_loop_*) and the multi-GPU sums -- a single pair that needs a
- *     gate is a batch of one.  There are no initial transforms and no trimmed or percentile rejection. */
+ *   - initial transforms (icp_batch_set_initial_transforms): one row-major 4x4 of doubles per pair (the layout of icp_result.T),
+ *     the pose each pair's registration starts from -- an odometry guess, a coarse registration's result, the T of an earlier
+ *     run of this very batch (coarse-to-fine gating without another upload); NULL removes them.
+ *       validation: every value finite (and finite once rounded to the batch's precision), every bottom row 0 0 0 1; anything
+ *         else is ICP_ERR_INVALID, the message names the first offending pair, and the batch keeps the transforms it had (or
+ *         none).  The upper 3x4 is applied as given: no orthogonality or determinant check (the library's own R carries no
+ *         reflection fix either).
+ *       rounding: the 12 values of a pair are rounded once to the batch's precision F; T0F is that matrix read back in double.
+ *       the call may come at any time after icp_batch_create; like the normals and gate calls it discards a loop under way
+ *         (icp_batch_run returns ICP_ERR_STATE until the next icp_batch_begin).
+ *       icp_batch_begin: pair p starts from apply(T0F_p, p0), p0 the point as uploaded, in the arithmetic every pass moves
+ *         points with: ((r0 x + r1 y) + r2 z) + t, every operation rounded separately in F.  The uploaded clouds are never
+ *         modified: every begin starts from them, transforms do not compound over repeated begins.  A pair whose 16 doubles are
+ *         the identity bit for bit is copied, not multiplied (its start cloud has the bytes of the upload, a -0.0 included).
+ *         All pairs' start clouds come from ONE launch in icp_batch_begin, in place of the device-to-device copy; a batch that
+ *         holds no transforms begins with that copy, as it always did, and the steps are the same either way.
+ *       results: from the start cloud on, a pair's loop is that of a batch without initial transforms created from that start
+ *         cloud -- status, iterations, passes, the err series (err[0] = 0: the initial transform is not a pass), idx, inlier
+ *         masks, moment vectors and the final cloud, bit for bit, whatever the other pairs and their order.  The gate therefore
+ *         acts on distances measured after the initial transform.  icp_batch_state reports T = T_loop . T0F, T_loop being what
+ *         that plain batch reports and the product formed in double, s = 0; s += T_loop[a][k] * T0F[k][b] for k = 0..3; a
+ *         copied (identity) pair reports T_loop untouched.
+ *       overflow: a finite transform can carry a finite cloud out of F's range.  A pair whose start cloud holds a NaN or an
+ *         infinite coordinate begins ended: status ICP_ERR_INVALID, passes 0, iterations 0, T = T0F.  icp_batch_begin still
+ *         returns ICP_OK and the other pairs run.  (One int per pair comes back from the launch: icp_batch_begin waits for it
+ *         when, and only when, the batch holds transforms.)
+ *     Not gated and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the multi-GPU sums --
+ *     a single pair that needs either is a batch of one.  There is no trimmed or percentile rejection. */
 typedef struct icp_batch icp_batch;
 #define ICP_BATCH_MAX_POINTS 65536 /* per cloud of one pair */
 int icp_batch_create(icp_ctx* ctx, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
@@ -287,6 +314,8 @@ int icp_batch_get_indices(icp_batch* b, int32_t* idx_out);  /* each pair's most 
 int icp_batch_loop_indices(icp_batch* b, int32_t* idx_out); /* each pair's last contributing pass, as icp_loop_indices */
 /* per-pair gate: count doubles, or NULL = no gate.  Each value > 0, or +INFINITY (that pair is not gated). */
 int icp_batch_set_max_distance(icp_batch* b, const double* max_dist);
+/* count x 16 doubles, one row-major 4x4 per pair (the layout of icp_result.T), or NULL = no initial transforms */
+int icp_batch_set_initial_transforms(icp_batch* b, const double* T16);
 /* 1 byte per moving point, concatenated as the moving clouds: 1 = that point's match was kept */
 int icp_batch_get_inliers(icp_batch* b, uint8_t* mask_out);   /* each pair's most recent matching pass (as icp_batch_get_indices) */
 int icp_batch_loop_inliers(icp_batch* b, uint8_t* mask_out);  /* each pair's last contributing pass (as icp_batch_loop_indices) */

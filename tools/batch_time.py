@@ -3,6 +3,7 @@
 for all pairs) against a loop of Context.point_to_point / point_to_plane over the same pairs (GPU box).
 
   python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE] [--only CASE,CASE] [--max-distance V] [--label TEXT]
+                              [--init | --premoved]
 
 Cases, --metric point: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids
 (make_model_gpu, tol 1e-6); 16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  --metric plane: the fp32 case sets and the
@@ -20,6 +21,13 @@ sequential side has no gate, so the passes agree only for inf and only then are 
 --max-distance inf against a run without the option.  Every row carries the fastest and the slowest of its --reps runs beside the
 median (batched_s_min / batched_s_max), and --label TEXT as "label" (which build, which round).  ICP_LIB_PATH selects another
 build of the library for an A/B run on one box.
+
+--init times the batched side from a far pose -- every moving cloud carried off by G (40 degrees about z, shifted by (3, -2, 1))
+outside the timed region -- with the inverse pose as every pair's initial transform (Context.point_to_*_batch(init=...)).
+--premoved is its baseline: the same far clouds moved back on the host with the same arithmetic (ref_moments.apply_rt, outside
+the timed region) and no initial transform, through the same Batch route (create, begin, run, per-pair state), so the two differ
+by the start-cloud launch of icp_batch_begin and its synchronisation alone and run the same bits.  Under either option the
+sequential side registers the pre-moved clouds, and every pair must run the same passes on both sides.
 """
 import argparse
 import json
@@ -78,14 +86,34 @@ def main():
     ap.add_argument("--only", default="", help="comma-separated case names: run only these")
     ap.add_argument("--max-distance", type=float, default=None, help="gate the batched side at this distance (inf: the gated kernels, nothing rejected)")
     ap.add_argument("--label", default="", help="copied into every row")
+    ap.add_argument("--init", action="store_true", help="the batched side starts from a far pose with the inverse pose as initial transform")
+    ap.add_argument("--premoved", action="store_true", help="the baseline of --init: the far clouds moved back on the host, no initial transform, same route")
     ap.add_argument("--profile-case", default="", help="run only this case's batched registration, once after a warm-up (for a kernel trace)")
     a = ap.parse_args()
     import torch  # noqa: F401  (torch first: it bundles the HIP runtime)
     from __graft_entry__ import load_package
     import oracle_lib
+    import ref_moments
     pkg = load_package()
     orc = oracle_lib.Oracle()
     rows = []
+    if a.init and a.premoved:
+        sys.exit("--init or --premoved, not both")
+    ang = np.deg2rad(40.0)
+    G = np.eye(4)
+    G[:3, :3], G[:3, 3] = [[np.cos(ang), -np.sin(ang), 0], [np.sin(ang), np.cos(ang), 0], [0, 0, 1]], (3.0, -2.0, 1.0)
+    G_inv = np.eye(4)
+    G_inv[:3, :3], G_inv[:3, 3] = G[:3, :3].T, -G[:3, :3].T @ G[:3, 3]
+
+    def carried(pairs, back):
+        """every moving cloud carried to the far pose (and back again, as icp_batch_begin would move it); one cloud object once"""
+        seen = {}
+        for D, _ in pairs:
+            if id(D) not in seen:
+                far = ref_moments.apply_rt(D, G[:3, :3], G[:3, 3])
+                seen[id(D)] = ref_moments.apply_rt(far, G_inv[:3, :3], G_inv[:3, 3]) if back else far
+        return [(seen[id(D)], M) for D, M in pairs]
+
     with pkg.Context(0) as ctx:
         plane = a.metric == "plane"
         todo = plane_cases(pkg, orc) if plane else [(name, pairs, None, it, tol) for name, pairs, it, tol in cases(pkg, orc)]
@@ -97,8 +125,13 @@ def main():
         for name, pairs, normals, it, tol in todo:
             if only and name not in only:
                 continue
+            seq_pairs = carried(pairs, True) if a.init or a.premoved else pairs
+            bat_pairs = carried(pairs, False) if a.init else seq_pairs
+            metric = pkg.ICP_POINT_TO_PLANE if plane else pkg.ICP_POINT_TO_POINT
 
             def run_batched():
+                if a.init or a.premoved:   # both through the Batch object: they differ by the initial transforms alone
+                    return ctx._run_batch_gated(metric, bat_pairs, normals, it, tol, False, gate, G_inv if a.init else None)
                 if plane and gate is not None:
                     return ctx.point_to_plane_batch_gated(pairs, gate, normals=normals, max_iter=it, tol=tol)
                 if plane:
@@ -108,8 +141,8 @@ def main():
             def run_sequential():
                 if plane:
                     return [ctx.point_to_plane(D, M, normals=None if normals is None else normals[k], max_iter=it, tol=tol)
-                            for k, (D, M) in enumerate(pairs)]
-                return [ctx.point_to_point(D, M, max_iter=it, tol=tol) for D, M in pairs]
+                            for k, (D, M) in enumerate(seq_pairs)]
+                return [ctx.point_to_point(D, M, max_iter=it, tol=tol) for D, M in seq_pairs]
 
             if a.profile_case:
                 if name == a.profile_case:
@@ -148,7 +181,8 @@ def main():
                        batched_us_per_pair_it=1e6 * mb / pb, sequential_us_per_pair_it=1e6 * ms / ps,
                        sequential_loops_us_per_pair_it=1e6 * ml / ps, speedup=ms / mb, speedup_vs_loops=ml / mb,
                        batched_s_min=float(min(tb)), batched_s_max=float(max(tb)), reps=a.reps,
-                       max_distance=None if gate is None else str(gate), label=a.label)
+                       max_distance=None if gate is None else str(gate), start="init" if a.init else "premoved" if a.premoved else "uploaded",
+                       label=a.label)
             rows.append(row)
             print(json.dumps(row), flush=True)
     if a.out:
