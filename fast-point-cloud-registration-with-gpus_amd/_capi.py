@@ -101,6 +101,7 @@ SIGNATURES = {
     "icp_batch_loop_indices": (_i, [_vp, _pi32]),
     "icp_batch_set_max_distance": (_i, [_vp, _pd]),
     "icp_batch_set_initial_transforms": (_i, [_vp, _pd]),
+    "icp_batch_set_trim": (_i, [_vp, _pd]),
     "icp_batch_get_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_batch_loop_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_point_to_point_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
@@ -125,6 +126,7 @@ SIGNATURES = {
     "icp_diag_row_roles": (_i, [_vp, _pu32, _i, _i, _i, _i, _pi32]),
     "icp_diag_loop_moments": (_i, [_vp, _pd, _pi]),
     "icp_diag_batch_moments": (_i, [_vp, _i, _pd]),
+    "icp_diag_batch_trim": (_i, [_vp, _i, _pd, _pi]),
     "icp_eigh3": (_i, [_pd, _pd, _pd]),
     "icp_synthetic_grid_f32": (_i, [_i, C.c_float, C.c_float, _vp]),
     "icp_synthetic_grid_f64": (_i, [_i, C.c_double, C.c_double, _vp]),

@@ -16,6 +16,12 @@
 // precision's range begins ended (ICP_ERR_INVALID).  The loops know nothing of it -- from the start cloud on a pair runs as
 // in a batch created from that cloud -- and icp_batch_state composes T_loop . T0F when it is read.  The steps are unchanged.
 //
+// A batch may hold a share to keep per pair (icp_batch_set_trim): a pair then keeps the K = ceil(rho n) closest of its n matches in
+// every matching pass, and every match tied with the K-th.  The K-th distance is known only when all of the pair's points are
+// matched, so the steps of such a batch run deferred: nn_match_batch<.., DEFER> (matching, no decision)  ->  batch_trim_select
+// (tau = the K-th smallest distance, per pair)  ->  batch_trim_moments (the decision, with the gate's where there is one, and the
+// sums)  ->  batch_finalize_kernel: four launches, still one download.  A batch whose shares are all 1.0 runs the steps above.
+//
 // Point-to-plane needs the model normals of every pair, in planes laid out as the models: given by the caller
 // (icp_batch_set_model_normals) or made on the device by ONE neighbour launch + ONE normals launch for the whole batch
 // (icp_batch_estimate_normals: knn4_batch + normals_batch_kernel, icp_k_plane.hip).  The reference estimates them once per
@@ -52,6 +58,11 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     bool have_normals = false;
     DevBuf thr;                              // the gate: every pair's squared maximum correspondence distance, in the batch's precision
     bool gated = false;                      // the batch holds thresholds (icp_batch_set_max_distance): the passes run the gated kernels
+    DevBuf trim_rank, tau, dist;             // trimming: every pair's rank K (0: not trimmed), its K-th smallest squared distance of the latest matching pass, every point's winning squared distance (laid out as idx)
+    bool trimmed = false;                    // a pair keeps a share < 1 (icp_batch_set_trim): the passes run the deferred route
+    std::vector<double> rho;                 // the shares as given (empty: none)
+    std::vector<int> rank;                   // K_p = ceil(rho_p n_p) in [1, n_p]
+    std::vector<char> tau_seen;              // the pair has completed a matching pass since icp_batch_begin
     DevBuf rt0, init_kind, init_flag;        // initial transforms: R, t of every pair in the batch's precision, BATCH_INIT_APPLY / _COPY, the start cloud is not finite
     bool have_init = false;                  // the batch holds initial transforms (icp_batch_set_initial_transforms)
     std::vector<double> T0F;                 // count x 16: every pair's transform as rounded to the batch's precision, read back in double
@@ -91,7 +102,8 @@ int ready(icp_batch* b)
 
 void release(icp_batch* b)
 {
-    for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag})
+    for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag,
+                      &b->trim_rank, &b->tau, &b->dist})
         d->release();
     if (b->h_ctl) (void)hipHostFree(b->h_ctl);
     if (b->h_mom) (void)hipHostFree(b->h_mom);
@@ -226,12 +238,13 @@ int step(icp_batch* b)
                                    b->count, (const int*)(static_cast<char*>(b->ctl.p) + b->rt_bytes), b->ctl.p, b->P.p, b->p_plane, b->Q.p,
                                    b->metric == ICP_POINT_TO_PLANE ? b->N.p : nullptr, b->q_plane, (const int32_t*)b->idx[cur ^ 1].p,
                                    (int32_t*)b->idx[cur].p, (double*)b->partials.p, (double*)b->mom.p, b->gated ? b->thr.p : nullptr,
-                                   c->stream));
+                                   b->trimmed ? (const int*)b->trim_rank.p : nullptr, b->dist.p, b->tau.p, c->stream));
     HIP_TRY(hipMemcpyAsync(b->h_mom, b->mom.p, (size_t)b->count * ICP_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     b->steps += 1;
     for (int p = 0; p < b->count; ++p) {
         if (mode[p] == 0) continue;
+        if (mode[p] & icp::BATCH_MATCH) b->tau_seen[p] = 1;
         b->mom_seen[p] = 1;   // (a pair that takes no part in a later step keeps this row: batch_finalize_kernel skips it)
         const int rc = b->H[p].advance(b->h_mom + (size_t)p * ICP_NMOM);
         if (rc != ICP_OK) {   // a numeric failure ends this pair only; what its completed passes produced stays readable
@@ -321,6 +334,7 @@ int icp_batch_create(icp_ctx* c, int count, const void* moving_aos, const int64_
     b->last_match.assign((size_t)count, 0);
     b->applied_buf.assign((size_t)count, 0);
     b->mom_seen.assign((size_t)count, 0);
+    b->tau_seen.assign((size_t)count, 0);
     if (int rc = upload(b, moving_aos, moving_off, model_aos, model_off)) {
         (void)hipStreamSynchronize(c->stream);
         release(b);
@@ -350,11 +364,12 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
     b->metric = prm->metric;
     for (int p = 0; p < b->count; ++p)
         if (int rc = b->H[p].begin(*prm)) return fail(rc, "bad loop parameters");
-    for (int p = 0; p < b->count; ++p) b->H[p].gated = b->gated;
+    for (int p = 0; p < b->count; ++p) b->H[p].gated = b->gated || b->trimmed;
     b->status.assign((size_t)b->count, ICP_OK);
     b->last_match.assign((size_t)b->count, 0);
     b->applied_buf.assign((size_t)b->count, 0);
     b->mom_seen.assign((size_t)b->count, 0);
+    b->tau_seen.assign((size_t)b->count, 0);
     if (b->have_init) {
         // the start cloud of every pair in one launch, and one flag per pair back: a finite transform can carry a finite cloud
         // out of the precision's range, and the library refuses non-finite clouds at the door -- that pair begins ended
@@ -438,6 +453,26 @@ int icp_diag_batch_moments(icp_batch* b, int pair, double* out32)
     return ICP_OK;
 }
 
+int icp_diag_batch_trim(icp_batch* b, int pair, double* tau_sq, int* rank)
+{
+    if (int rc = ready(b)) return rc;
+    if (pair < 0 || pair >= b->count) return fail(ICP_ERR_INVALID, "pair out of range");
+    if (!b->begun || !b->tau_seen[pair]) return fail(ICP_ERR_STATE, "no completed matching pass of this pair");
+    if (rank) *rank = b->rank.empty() ? b->pairs[pair].n : b->rank[pair];
+    if (tau_sq) {
+        *tau_sq = INFINITY;   // (a batch that runs the fused pass keeps no tau buffer up to date: none of its pairs is trimmed)
+        if (b->trimmed) {
+            double d = 0.0;
+            float f = 0.0f;
+            void* dst = b->prec == ICP_F64 ? (void*)&d : (void*)&f;
+            HIP_TRY(hipMemcpyAsync(dst, static_cast<const char*>(b->tau.p) + (size_t)pair * b->esize, b->esize, hipMemcpyDeviceToHost, b->ctx->stream));
+            HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+            *tau_sq = b->prec == ICP_F64 ? d : (double)f;
+        }
+    }
+    return ICP_OK;
+}
+
 int icp_batch_done(icp_batch* b, int32_t* done_out)
 {
     if (!b || !done_out) return fail(ICP_ERR_INVALID, "null argument");
@@ -496,6 +531,46 @@ int icp_batch_set_max_distance(icp_batch* b, const double* max_dist)
         b->begun = false;
         b->gated = false;
     }
+    return ICP_OK;
+}
+
+int icp_batch_set_trim(icp_batch* b, const double* keep_ratio)
+{
+    if (int rc = ready(b)) return rc;
+    if (!keep_ratio) {
+        b->begun = false;
+        b->trimmed = false;
+        b->rho.clear();
+        b->rank.clear();
+        return ICP_OK;
+    }
+    for (int p = 0; p < b->count; ++p)   // (NaN fails both comparisons)
+        if (!(keep_ratio[p] > 0.0 && keep_ratio[p] <= 1.0))
+            return fail(ICP_ERR_INVALID, "the share to keep must satisfy 0 < ratio <= 1: pair " + std::to_string(p));
+    // K = ceil(rho * (double)n), the product in double, clamped to [1, n]; exactly 1.0: not trimmed (device rank 0, tau = +inf)
+    std::vector<int> rank((size_t)b->count), dev_rank((size_t)b->count);
+    std::vector<char> inf((size_t)b->count * b->esize);
+    bool any = false;
+    for (int p = 0; p < b->count; ++p) {
+        const int n = b->pairs[p].n;
+        const double k = std::ceil(keep_ratio[p] * (double)n);
+        rank[p] = k < 1.0 ? 1 : k > (double)n ? n : (int)k;
+        dev_rank[p] = keep_ratio[p] == 1.0 ? 0 : rank[p];
+        any = any || dev_rank[p] != 0;
+        if (b->prec == ICP_F64) reinterpret_cast<double*>(inf.data())[p] = INFINITY;
+        else reinterpret_cast<float*>(inf.data())[p] = INFINITY;
+    }
+    HIP_TRY(b->trim_rank.ensure(dev_rank.size() * sizeof(int)));
+    HIP_TRY(b->tau.ensure(inf.size()));
+    HIP_TRY(b->dist.ensure((size_t)b->p_plane * b->esize));
+    b->begun = false;   // a loop under way is discarded: its passes so far kept other shares (or everything)
+    b->trimmed = false;
+    HIP_TRY(hipMemcpyAsync(b->trim_rank.p, dev_rank.data(), dev_rank.size() * sizeof(int), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(b->tau.p, inf.data(), inf.size(), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
+    b->rho.assign(keep_ratio, keep_ratio + b->count);
+    b->rank.swap(rank);
+    b->trimmed = any;
     return ICP_OK;
 }
 

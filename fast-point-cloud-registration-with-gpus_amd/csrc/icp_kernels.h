@@ -384,10 +384,15 @@ constexpr int32_t BATCH_IDX_REJECTED = INT32_MIN, BATCH_IDX_MASK = INT32_MAX;
 // plane terms (ICP_MOM_CNT, ICP_MOM_C .. ICP_MOM_B + 5).  thr: NULL (the ungated instantiations), or F[n_pairs], every pair's
 // squared maximum correspondence distance (+inf: that pair is not gated): only matches with d <= thr[pair] enter the sums, and
 // the error counts only the points idx_prev marks as kept.
+// trim_rank: NULL (the fused pass, two launches), or int[n_pairs], every pair's rank K in [1, n] (0: that pair is not trimmed):
+// the pass then runs deferred, in four launches -- nn_match_batch<.., DEFER> leaves every point's winning squared distance in
+// dist (F[p_plane], laid out as idx), batch_trim_select writes tau[pair] = the K-th smallest of the pair's distances for the
+// pairs that match and are trimmed (tau: F[n_pairs], +inf from the host for the others), and batch_trim_moments keeps the
+// matches with d <= tau[pair] (and d <= thr[pair] where thr is given), marks the others in idx_cur and forms the sums.
 hipError_t launch_batch_pass(int precision, int metric, const BatchItem* items, int n_items, const BatchPair* pairs, int n_pairs,
                              const int* mode, const void* rt /* RT<F>[n_pairs] */, void* P_soa, long long p_plane, const void* Q_soa,
                              const void* N_soa, long long q_plane, const int32_t* idx_prev, int32_t* idx_cur, double* partials,
-                             double* mom, const void* thr, hipStream_t st);
+                             double* mom, const void* thr, const int* trim_rank, void* dist, void* tau, hipStream_t st);
 // the start cloud of a batch that holds initial transforms, in one launch over the same items: P[pair] = apply_rt(rt0[pair],
 // P0[pair]), or P0[pair]'s bytes where kind[pair] == BATCH_INIT_COPY; nonfinite[pair] (int[n_pairs], zero before the launch)
 // becomes 1 where a transformed point of the pair has a NaN or an infinite coordinate.  The padding of P is not written.

@@ -257,16 +257,19 @@ class Context:
         """a Batch of (D, M) pairs of one dtype, uploaded once (see Batch)"""
         return Batch(self, pairs)
 
-    def point_to_point_batch(self, pairs, max_iter=40, tol=1e-6, fixed_iterations=False, max_distance=None, init=None):
+    def point_to_point_batch(self, pairs, max_iter=40, tol=1e-6, fixed_iterations=False, max_distance=None, init=None, trim=None):
         """point_to_point for every (D, M) of `pairs` (one dtype) in one batched registration; a list of Result in pair order,
         each exactly what point_to_point gives for that pair alone (extra["status"]: ICP_OK or the code that ended its loop).
         max_distance (a scalar or one value per pair, inf = that pair is not gated): a match farther away than that pulls on
         nothing (Batch.set_max_distance); extra["inliers"] is then the mask of the last contributing pass and extra["fitness"]
         the share of the points it kept.
         init (one (4, 4) for every pair, or (count, 4, 4)): the pose every pair starts from (Batch.set_initial_transforms); the
-        gate then acts on distances measured after it, and Result.T includes it.  Runs through a Batch as max_distance does."""
-        if max_distance is not None or init is not None:
-            return self._run_batch_gated(capi.ICP_POINT_TO_POINT, pairs, None, max_iter, tol, fixed_iterations, max_distance, init)
+        gate then acts on distances measured after it, and Result.T includes it.  Runs through a Batch as max_distance does.
+        trim (a scalar or one value per pair, each in (0, 1]; 1.0 = that pair is not trimmed): the share of every moving cloud to
+        keep -- the closest matches of every pass, ties with the last one included (Batch.set_trim); extra["inliers"] and
+        extra["fitness"] as for max_distance.  Runs through a Batch too."""
+        if max_distance is not None or init is not None or trim is not None:
+            return self._run_batch_gated(capi.ICP_POINT_TO_POINT, pairs, None, max_iter, tol, fixed_iterations, max_distance, init, trim)
         return self._run_batch(capi.ICP_POINT_TO_POINT, pairs, None, max_iter, tol, fixed_iterations)
 
     def point_to_plane_batch(self, pairs, normals=None, max_iter=50, tol=1e-6, fixed_iterations=False):
@@ -274,15 +277,16 @@ class Context:
         array per pair, or None (then estimated on the device: one neighbour launch + one normals launch for all pairs)"""
         return self._run_batch(capi.ICP_POINT_TO_PLANE, pairs, normals, max_iter, tol, fixed_iterations)
 
-    def point_to_plane_batch_gated(self, pairs, max_distance, normals=None, max_iter=50, tol=1e-6, fixed_iterations=False, init=None):
-        """point_to_plane_batch with a maximum correspondence distance (a scalar or one value per pair; the gate is on the Euclidean
-        distance to the matched point), as point_to_point_batch(max_distance=...): extra["inliers"], extra["fitness"]; init as there.
+    def point_to_plane_batch_gated(self, pairs, max_distance, normals=None, max_iter=50, tol=1e-6, fixed_iterations=False, init=None, trim=None):
+        """point_to_plane_batch with a maximum correspondence distance (a scalar or one value per pair, or None; the gate is on the
+        Euclidean distance to the matched point), as point_to_point_batch(max_distance=...): extra["inliers"], extra["fitness"];
+        init and trim as there.
         (point_to_plane_batch itself keeps its parameter list, which tests/test_batch_plane_abi.py holds fixed.)"""
-        return self._run_batch_gated(capi.ICP_POINT_TO_PLANE, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init)
+        return self._run_batch_gated(capi.ICP_POINT_TO_PLANE, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init, trim)
 
-    def _run_batch_gated(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init=None):
-        """the one-call functions have neither a gate nor initial transforms: create, [normals], set_max_distance,
-        set_initial_transforms, begin, run to the end, results"""
+    def _run_batch_gated(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init=None, trim=None):
+        """the one-call functions have neither a gate nor initial transforms nor trimming: create, [normals], set_max_distance,
+        set_initial_transforms, set_trim, begin, run to the end, results"""
         with Batch(self, pairs) as bt:
             if metric == capi.ICP_POINT_TO_PLANE:
                 if normals is not None:
@@ -291,6 +295,8 @@ class Context:
                     bt.estimate_normals()
             bt.set_max_distance(max_distance)
             bt.set_initial_transforms(init)
+            if trim is not None:
+                bt.set_trim(trim)
             bt.begin(max_iter=max_iter, tol=tol, fixed_iterations=fixed_iterations, metric=metric)
             while bt.run(1 << 20)[1] > 0:
                 pass
@@ -516,6 +522,28 @@ class Batch:
         if a.shape != (self.count,):
             raise ValueError("one maximum distance per pair (or a scalar)")
         capi.check(self._lib.icp_batch_set_max_distance(self._h, a.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_max_distance")
+
+    def set_trim(self, v):
+        """the share of every moving cloud to keep: a scalar for every pair, one value per pair (1.0: that pair is not trimmed), or
+        None (no trimming).  Each in (0, 1].  A pair keeps the K = ceil(share * n) closest matches of every pass and every match
+        tied with the K-th; the others enter no sum.  Discards a loop under way."""
+        if v is None:
+            capi.check(self._lib.icp_batch_set_trim(self._h, None), "icp_batch_set_trim")
+            return
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(self.count, float(a))
+        a = np.ascontiguousarray(a)
+        if a.shape != (self.count,):
+            raise ValueError("one share to keep per pair (or a scalar)")
+        capi.check(self._lib.icp_batch_set_trim(self._h, a.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_trim")
+
+    def diag_trim(self, b):
+        """(tau_sq, K) of pair b (icp_diag_batch_trim): the squared-distance threshold of its most recent matching pass (inf for a
+        pair that is not trimmed) and its rank"""
+        tau, k = C.c_double(0.0), C.c_int(0)
+        capi.check(self._lib.icp_diag_batch_trim(self._h, int(b), C.byref(tau), C.byref(k)), "icp_diag_batch_trim")
+        return tau.value, k.value
 
     def set_initial_transforms(self, T):
         """the pose every pair's registration starts from: one (4, 4) for every pair, (count, 4, 4), or None (none).  Rounded once

@@ -286,8 +286,39 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *         infinite coordinate begins ended: status ICP_ERR_INVALID, passes 0, iterations 0, T = T0F.  icp_batch_begin still
  *         returns ICP_OK and the other pairs run.  (One int per pair comes back from the launch: icp_batch_begin waits for it
  *         when, and only when, the batch holds transforms.)
- *     Not gated and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the multi-GPU sums --
- *     a single pair that needs either is a batch of one.  There is no trimmed or percentile rejection. */
+ *   - trimmed rejection (icp_batch_set_trim): one double per pair, the share rho of the moving cloud to keep -- the share that
+ *     overlaps the model, which a user usually knows where a fitting distance is not known (Chetverikov's TrICP); NULL removes
+ *     trimming.
+ *       validation: each value must satisfy 0 < rho <= 1.  A NaN, a value <= 0 or a value > 1 anywhere: ICP_ERR_INVALID, the
+ *         message names the first offending pair, and the batch keeps the shares it had (or none).
+ *       the call may come at any time after icp_batch_create; like the normals, gate and initial-transform calls it discards
+ *         a loop under way (icp_batch_run returns ICP_ERR_STATE until the next icp_batch_begin), and it returns ICP_ERR_STATE
+ *         while the context has a pending pass.
+ *       rank: K_p = ceil(rho_p * (double)n_p), the product formed in double, clamped to [1, n_p]; fixed at the call, because
+ *         n_p never changes.  rho_p == 1.0 exactly means the pair is not trimmed.
+ *       threshold: in every matching pass of a trimmed pair tau_p is the K_p-th smallest of the pair's n_p winning squared
+ *         distances d_i, where d_i is the value the matching already holds -- (dx*dx + dy*dy) + dz*dz, every operation
+ *         rounded separately in the batch's precision F; nothing is recomputed.  tau_p is therefore one of the d_i, bit for
+ *         bit.  A pair that is not trimmed has tau = +inf.
+ *       a match is kept iff d_i <= tau_p -- and also d_i <= thr_p where the batch holds a gate.  Every point tied with the K-th
+ *         is kept: the kept count is then >= K_p, and the answer depends on no ordering of equal values.  The selection
+ *         ignores the gate: the rank counts all n_p points.  For point-to-plane the test is on the same Euclidean d.
+ *       everything else follows the gate's rules.  idx is unchanged: every index is the bit-exact nearest neighbour in [0, m),
+ *         kept or not.  Only kept points contribute to ICP_MOM_CNT and to every sum of the pass, for both metrics.
+ *         ICP_MOM_ERR of a pass is the sum of |p_new - q[idx_prev]|^2 over the points kept by the matching pass those indices
+ *         came from, and err[k] = sqrt(ERR_k) / sqrt(CNT_{k-1}).  icp_batch_get_inliers / icp_batch_loop_inliers report the
+ *         kept mask.  Trimming alone always keeps at least one point, so ICP_ERR_EMPTY can arise only together with a gate.
+ *       bits: a batch with no trim, or with every value 1.0, produces the bits of a batch that never heard of trimming and
+ *         runs the same two launches per step.  In a batch that trims some pairs, a pair with rho = 1.0 still has the bits
+ *         of that pair in a plain batch: every mask, idx, cloud, err, T and moment vector.  A trimmed pair's bits depend on
+ *         that pair, its rho and its gate alone, not on the other pairs or their order (no floating-point atomics, fixed
+ *         summation order).  Trimming works with initial transforms as the gate does: distances are measured after the
+ *         transform.
+ *       cost: a pair's tau is known only when every one of its points has been matched, so a step of a batch that trims at
+ *         least one pair runs four launches in place of two (matching, selection, sums, reduction) and still one download.
+ *     Not gated, not trimmed and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the
+ *     multi-GPU sums -- a single pair that needs any of them is a batch of one.  Trimming is the only rejection by rank: there
+ *     is no other percentile rejection (none by a multiple of the median or of the standard deviation of the distances). */
 typedef struct icp_batch icp_batch;
 #define ICP_BATCH_MAX_POINTS 65536 /* per cloud of one pair */
 int icp_batch_create(icp_ctx* ctx, int count, const void* moving_aos, const int64_t* moving_off, const void* model_aos,
@@ -314,6 +345,9 @@ int icp_batch_get_indices(icp_batch* b, int32_t* idx_out);  /* each pair's most 
 int icp_batch_loop_indices(icp_batch* b, int32_t* idx_out); /* each pair's last contributing pass, as icp_loop_indices */
 /* per-pair gate: count doubles, or NULL = no gate.  Each value > 0, or +INFINITY (that pair is not gated). */
 int icp_batch_set_max_distance(icp_batch* b, const double* max_dist);
+/* per-pair share of the moving cloud to keep: count doubles, or NULL = no trimming.  Each value in (0, 1]; exactly 1.0: that
+ * pair is not trimmed. */
+int icp_batch_set_trim(icp_batch* b, const double* keep_ratio);
 /* count x 16 doubles, one row-major 4x4 per pair (the layout of icp_result.T), or NULL = no initial transforms */
 int icp_batch_set_initial_transforms(icp_batch* b, const double* T16);
 /* 1 byte per moving point, concatenated as the moving clouds: 1 = that point's match was kept */

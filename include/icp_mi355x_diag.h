@@ -74,9 +74,15 @@ int icp_diag_row_roles(icp_ctx* ctx, uint32_t* hits_io, int rows, int min_part, 
 #define ICP_ROUTE_ARMED 0x400          /* the pass was an armed launch released through its mailbox */
 #define ICP_ROUTE_RESIDENT 0x800       /* the pass was a message to the resident kernel */
 int icp_diag_loop_moments(icp_ctx* ctx, double* out32, int* route);
-/* the same for pair `pair` of a batch: the row of the step's download that pair's loop last advanced on (the batch has one route:
- * nn_match_batch's item rows added by batch_finalize_kernel).  ICP_ERR_STATE before the pair's first completed pass. */
+/* the same for pair `pair` of a batch: the row of the step's download that pair's loop last advanced on (the rows are always
+ * added by batch_finalize_kernel; they come from nn_match_batch's fused tail, or from batch_trim_moments in a batch that trims).
+ * ICP_ERR_STATE before the pair's first completed pass. */
 int icp_diag_batch_moments(icp_batch* b, int pair, double* out32);
+/* trimmed rejection of pair `pair` (icp_batch_set_trim): *tau_sq = the threshold of the pair's most recent matching pass -- the
+ * K-th smallest winning squared distance, in the batch's precision, read back in double; +inf for a pair that is not trimmed --
+ * and *rank = K (n for a pair that is not trimmed).  Either pointer may be NULL.  The per-pair threshold buffer is copied down
+ * on demand: nothing is added to a step's download.  ICP_ERR_STATE before the pair's first completed matching pass. */
+int icp_diag_batch_trim(icp_batch* b, int pair, double* tau_sq, int* rank);
 
 #ifdef __cplusplus
 }

@@ -2,8 +2,8 @@
 """Pair-iterations per second of the batched loops (Context.point_to_point_batch / point_to_plane_batch, one launch per step
 for all pairs) against a loop of Context.point_to_point / point_to_plane over the same pairs (GPU box).
 
-  python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE] [--only CASE,CASE] [--max-distance V] [--label TEXT]
-                              [--init | --premoved]
+  python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE] [--only CASE,CASE] [--max-distance V] [--trim R]
+                              [--label TEXT] [--init | --premoved]
 
 Cases, --metric point: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids
 (make_model_gpu, tol 1e-6); 16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  --metric plane: the fp32 case sets and the
@@ -21,6 +21,11 @@ sequential side has no gate, so the passes agree only for inf and only then are 
 --max-distance inf against a run without the option.  Every row carries the fastest and the slowest of its --reps runs beside the
 median (batched_s_min / batched_s_max), and --label TEXT as "label" (which build, which round).  ICP_LIB_PATH selects another
 build of the library for an A/B run on one box.
+
+--trim R (a share in (0, 1]) runs the batched side with that share of every moving cloud kept (Context.point_to_*_batch(trim=R):
+the deferred route, four launches per step; R = 1.0 goes through the Batch object and runs the fused pass).  The sequential side
+does not trim, so the passes are compared only for R = 1.0.  The cost of trimming is --trim R against --max-distance inf of the
+same build (both through the Batch object).
 
 --init times the batched side from a far pose -- every moving cloud carried off by G (40 degrees about z, shifted by (3, -2, 1))
 outside the timed region -- with the inverse pose as every pair's initial transform (Context.point_to_*_batch(init=...)).
@@ -85,6 +90,7 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--only", default="", help="comma-separated case names: run only these")
     ap.add_argument("--max-distance", type=float, default=None, help="gate the batched side at this distance (inf: the gated kernels, nothing rejected)")
+    ap.add_argument("--trim", type=float, default=None, help="keep this share of every moving cloud on the batched side (the deferred route)")
     ap.add_argument("--label", default="", help="copied into every row")
     ap.add_argument("--init", action="store_true", help="the batched side starts from a far pose with the inverse pose as initial transform")
     ap.add_argument("--premoved", action="store_true", help="the baseline of --init: the far clouds moved back on the host, no initial transform, same route")
@@ -122,6 +128,7 @@ def main():
         if unknown:
             sys.exit(f"unknown case(s) {unknown}: {[t[0] for t in todo]}")
         gate = a.max_distance
+        trim = a.trim
         for name, pairs, normals, it, tol in todo:
             if only and name not in only:
                 continue
@@ -131,12 +138,12 @@ def main():
 
             def run_batched():
                 if a.init or a.premoved:   # both through the Batch object: they differ by the initial transforms alone
-                    return ctx._run_batch_gated(metric, bat_pairs, normals, it, tol, False, gate, G_inv if a.init else None)
-                if plane and gate is not None:
-                    return ctx.point_to_plane_batch_gated(pairs, gate, normals=normals, max_iter=it, tol=tol)
+                    return ctx._run_batch_gated(metric, bat_pairs, normals, it, tol, False, gate, G_inv if a.init else None, trim)
+                if plane and (gate is not None or trim is not None):
+                    return ctx.point_to_plane_batch_gated(pairs, gate, normals=normals, max_iter=it, tol=tol, trim=trim)
                 if plane:
                     return ctx.point_to_plane_batch(pairs, normals=normals, max_iter=it, tol=tol)
-                return ctx.point_to_point_batch(pairs, max_iter=it, tol=tol, max_distance=gate)
+                return ctx.point_to_point_batch(pairs, max_iter=it, tol=tol, max_distance=gate, trim=trim)
 
             def run_sequential():
                 if plane:
@@ -172,7 +179,7 @@ def main():
                 ts.append(s)
                 tl.append(loops)
             # the same registrations: every pair must run the same passes on both sides (checked when all rows are out)
-            apart = sum(1 for x, y in zip(pb, ps) if x != y) if gate is None or np.isinf(gate) else 0
+            apart = sum(1 for x, y in zip(pb, ps) if x != y) if (gate is None or np.isinf(gate)) and (trim is None or trim == 1.0) else 0
             pb, ps = sum(pb), sum(ps)
             mb, ms, ml = float(np.median(tb)), float(np.median(ts)), float(np.median(tl))
             row = dict(case=name, pairs=len(pairs), points=int(pairs[0][0].shape[0]), pair_iterations=pb, sequential_pair_iterations=ps, pairs_stopping_apart=apart,
@@ -181,7 +188,7 @@ def main():
                        batched_us_per_pair_it=1e6 * mb / pb, sequential_us_per_pair_it=1e6 * ms / ps,
                        sequential_loops_us_per_pair_it=1e6 * ml / ps, speedup=ms / mb, speedup_vs_loops=ml / mb,
                        batched_s_min=float(min(tb)), batched_s_max=float(max(tb)), reps=a.reps,
-                       max_distance=None if gate is None else str(gate), start="init" if a.init else "premoved" if a.premoved else "uploaded",
+                       max_distance=None if gate is None else str(gate), trim=trim, start="init" if a.init else "premoved" if a.premoved else "uploaded",
                        label=a.label)
             rows.append(row)
             print(json.dumps(row), flush=True)
