@@ -1,7 +1,7 @@
 // icp_batch.cpp -- batched ICP (icp_batch_*, icp_point_to_point_batch, icp_point_to_plane_batch): many independent pairs, and per
 // step ONE matching launch + ONE reduction launch + ONE download of ICP_NMOM doubles per pair for every pair still running.
 //
-//   step k:  [R, t + mode of every pair: H2D]  ->  nn_match_batch (transform + error, match, moments per work item)
+//   step k:  [R, t + mode of every pair: H2D]  ->  nn_match_batch (icp_k_batch.hip: transform + error, match, moments per work item)
 //            ->  batch_finalize_kernel (per pair, fixed order)  ->  D2H count x ICP_NMOM  ->  sync
 //            ->  HostLoop::advance per pair that took part (error, stop rule, 3x3 solve or 6x6 solve)
 //
@@ -92,12 +92,27 @@ int count_running(const icp_batch* b)
 }
 
 // a batch borrows the context's device and stream -- never in the middle of the context's own pass
+int ctx_ready(icp_ctx* c)
+{
+    if (int rc = use(c)) return rc;
+    if (c->loop.pending) return fail(ICP_ERR_STATE, "the context has an enqueued pass that is not completed (icp_loop_complete first)");
+    return ICP_OK;
+}
+
 int ready(icp_batch* b)
 {
     if (!b) return fail(ICP_ERR_INVALID, "null batch");
-    if (int rc = use(b->ctx)) return rc;
-    if (b->ctx->loop.pending) return fail(ICP_ERR_STATE, "the context has an enqueued pass that is not completed (icp_loop_complete first)");
-    return ICP_OK;
+    return ctx_ready(b->ctx);
+}
+
+// what icp_batch_begin forgets of the loop before (icp_batch_create: the same, of none)
+void reset_loop_state(icp_batch* b)
+{
+    b->status.assign((size_t)b->count, ICP_OK);
+    b->last_match.assign((size_t)b->count, 0);
+    b->applied_buf.assign((size_t)b->count, 0);
+    b->mom_seen.assign((size_t)b->count, 0);
+    b->tau_seen.assign((size_t)b->count, 0);
 }
 
 void release(icp_batch* b)
@@ -130,26 +145,85 @@ bool all_finite(const void* aos, int64_t points)
     return true;
 }
 
-// the pairs' AoS clouds -> padded SoA planes, every cloud at its offset (the padding is never read)
+// one side of the batch -- the moving clouds or the models: the caller's offsets, where each cloud starts in its plane, the plane
+struct Side {
+    const int64_t* off;
+    std::vector<long long> dst;
+    long long plane;
+};
+
+Side side(const icp_batch* b, bool model)
+{
+    Side s{model ? b->qoff.data() : b->moff.data(), std::vector<long long>((size_t)b->count), model ? b->q_plane : b->p_plane};
+    for (int p = 0; p < b->count; ++p) s.dst[p] = model ? b->pairs[p].q_off : b->pairs[p].p_off;
+    return s;
+}
+
+// the pairs' AoS clouds -> padded SoA planes, every cloud at its offset (the padding is never read), and back
 template <typename F>
-std::vector<F> to_planes(const void* aos, const int64_t* off, int count, const std::vector<long long>& dst, long long plane)
+void to_planes(const void* aos, const Side& s, std::vector<char>& raw)
 {
     const F* a = static_cast<const F*>(aos);
-    std::vector<F> out((size_t)(3 * plane), F(0));
-    for (int p = 0; p < count; ++p)
-        for (int64_t i = 0; i < off[p + 1] - off[p]; ++i)
-            for (int k = 0; k < 3; ++k) out[(size_t)(k * plane + dst[p] + i)] = a[3 * (off[p] + i) + k];
-    return out;
+    F* out = reinterpret_cast<F*>(raw.data());
+    for (size_t p = 0; p < s.dst.size(); ++p)
+        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
+            for (int k = 0; k < 3; ++k) out[(size_t)(k * s.plane + s.dst[p] + i)] = a[3 * (s.off[p] + i) + k];
 }
 
 template <typename F>
-void from_planes(const std::vector<char>& raw, const icp_batch* b, void* aos)
+void from_planes(const std::vector<char>& raw, const Side& s, void* aos)
 {
-    const F* s = reinterpret_cast<const F*>(raw.data());
+    const F* in = reinterpret_cast<const F*>(raw.data());
     F* o = static_cast<F*>(aos);
-    for (int p = 0; p < b->count; ++p)
-        for (int i = 0; i < b->pairs[p].n; ++i)
-            for (int k = 0; k < 3; ++k) o[3 * (b->moff[p] + i) + k] = s[k * b->p_plane + b->pairs[p].p_off + i];
+    for (size_t p = 0; p < s.dst.size(); ++p)
+        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
+            for (int k = 0; k < 3; ++k) o[3 * (s.off[p] + i) + k] = in[(size_t)(k * s.plane + s.dst[p] + i)];
+}
+
+// the moving clouds' (the models') layout, in the batch's precision: AoS as the caller holds it -> the planes of `dev`.  Enqueues
+// the copy from `host`, which must outlive it: the caller synchronises.
+int enqueue_planes(icp_batch* b, const void* aos, bool model, void* dev, std::vector<char>& host)
+{
+    const Side s = side(b, model);
+    host.assign(3 * (size_t)s.plane * b->esize, 0);   // (all-zero bytes: 0.0 in both precisions)
+    if (b->prec == ICP_F64) to_planes<double>(aos, s, host);
+    else to_planes<float>(aos, s, host);
+    HIP_TRY(hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, b->ctx->stream));
+    return ICP_OK;
+}
+
+// ... and back: planes downloaded into `raw` -> AoS in the caller's layout
+void planes_to_aos(const icp_batch* b, const std::vector<char>& raw, bool model, void* aos)
+{
+    if (b->prec == ICP_F64) from_planes<double>(raw, side(b, model), aos);
+    else from_planes<float>(raw, side(b, model), aos);
+}
+
+// element i of an array in the batch's precision: written from a double (rounded once), read back as a double
+void put_scalar(const icp_batch* b, void* dst, size_t i, double v)
+{
+    const float f = (float)v;
+    std::memcpy(static_cast<char*>(dst) + i * b->esize, b->prec == ICP_F64 ? (const void*)&v : (const void*)&f, b->esize);
+}
+
+double get_scalar(const icp_batch* b, const void* src, size_t i)
+{
+    double d = 0.0;
+    float f = 0.0f;
+    std::memcpy(b->prec == ICP_F64 ? (void*)&d : (void*)&f, static_cast<const char*>(src) + i * b->esize, b->esize);
+    return b->prec == ICP_F64 ? d : (double)f;
+}
+
+// the work items of the moving clouds (of the models): BATCH_ITEM points of one pair, cut from that pair's first point
+std::vector<icp::BatchItem> work_items(const icp_batch* b, bool model)
+{
+    std::vector<icp::BatchItem> items;
+    for (int p = 0; p < b->count; ++p) {
+        const int len = model ? b->pairs[p].m : b->pairs[p].n;
+        for (int first = 0; first < len; first += icp::BATCH_ITEM)
+            items.push_back(icp::BatchItem{p, first, std::min(icp::BATCH_ITEM, len - first), 0});
+    }
+    return items;
 }
 
 template <typename F>
@@ -160,34 +234,19 @@ void put_rt(void* dst, const double* R, const double* t)
     for (int k = 0; k < 3; ++k) o[9 + k] = (F)t[k];
 }
 
-int upload(icp_batch* b, const void* moving, const int64_t* moving_off, const void* model, const int64_t* model_off)
+int upload(icp_batch* b, const void* moving, const void* model)
 {
     icp_ctx* c = b->ctx;
-    std::vector<long long> pdst(b->count), qdst(b->count);
-    for (int p = 0; p < b->count; ++p) { pdst[p] = b->pairs[p].p_off; qdst[p] = b->pairs[p].q_off; }
     const size_t pb = 3 * (size_t)b->p_plane * b->esize, qb = 3 * (size_t)b->q_plane * b->esize;
     HIP_TRY(b->P.ensure(pb));
     HIP_TRY(b->P0.ensure(pb));
     HIP_TRY(b->Q.ensure(qb));
-    if (b->prec == ICP_F64) {
-        const std::vector<double> ps = to_planes<double>(moving, moving_off, b->count, pdst, b->p_plane);
-        const std::vector<double> qs = to_planes<double>(model, model_off, b->count, qdst, b->q_plane);
-        HIP_TRY(hipMemcpyAsync(b->P0.p, ps.data(), pb, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(b->Q.p, qs.data(), qb, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));   // (before the host vectors go)
-    } else {
-        const std::vector<float> ps = to_planes<float>(moving, moving_off, b->count, pdst, b->p_plane);
-        const std::vector<float> qs = to_planes<float>(model, model_off, b->count, qdst, b->q_plane);
-        HIP_TRY(hipMemcpyAsync(b->P0.p, ps.data(), pb, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(b->Q.p, qs.data(), qb, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+    std::vector<char> ps, qs;
+    if (int rc = enqueue_planes(b, moving, false, b->P0.p, ps)) return rc;
+    if (int rc = enqueue_planes(b, model, true, b->Q.p, qs)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));   // (before the host vectors go)
     HIP_TRY(hipMemcpyAsync(b->P.p, b->P0.p, pb, hipMemcpyDeviceToDevice, c->stream));
-    std::vector<icp::BatchItem> items;
-    items.reserve((size_t)b->n_items);
-    for (int p = 0; p < b->count; ++p)
-        for (int first = 0; first < b->pairs[p].n; first += icp::BATCH_ITEM)
-            items.push_back(icp::BatchItem{p, first, std::min(icp::BATCH_ITEM, b->pairs[p].n - first), 0});
+    const std::vector<icp::BatchItem> items = work_items(b, false);
     HIP_TRY(b->items.ensure(items.size() * sizeof(icp::BatchItem)));
     HIP_TRY(b->pairs_d.ensure(b->pairs.size() * sizeof(icp::BatchPair)));
     HIP_TRY(hipMemcpyAsync(b->items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, c->stream));
@@ -234,11 +293,29 @@ int step(icp_batch* b)
         }
     }
     HIP_TRY(hipMemcpyAsync(b->ctl.p, b->h_ctl, b->ctl_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(icp::launch_batch_pass(b->prec, b->metric, (const icp::BatchItem*)b->items.p, b->n_items, (const icp::BatchPair*)b->pairs_d.p,
-                                   b->count, (const int*)(static_cast<char*>(b->ctl.p) + b->rt_bytes), b->ctl.p, b->P.p, b->p_plane, b->Q.p,
-                                   b->metric == ICP_POINT_TO_PLANE ? b->N.p : nullptr, b->q_plane, (const int32_t*)b->idx[cur ^ 1].p,
-                                   (int32_t*)b->idx[cur].p, (double*)b->partials.p, (double*)b->mom.p, b->gated ? b->thr.p : nullptr,
-                                   b->trimmed ? (const int*)b->trim_rank.p : nullptr, b->dist.p, b->tau.p, c->stream));
+    icp::BatchPassArgs a{};
+    a.precision = b->prec;
+    a.metric = b->metric;
+    a.items = (const icp::BatchItem*)b->items.p;
+    a.n_items = b->n_items;
+    a.pairs = (const icp::BatchPair*)b->pairs_d.p;
+    a.n_pairs = b->count;
+    a.mode = (const int*)(static_cast<char*>(b->ctl.p) + b->rt_bytes);
+    a.rt = b->ctl.p;
+    a.P_soa = b->P.p;
+    a.p_plane = b->p_plane;
+    a.Q_soa = b->Q.p;
+    a.N_soa = b->metric == ICP_POINT_TO_PLANE ? b->N.p : nullptr;
+    a.q_plane = b->q_plane;
+    a.idx_prev = (const int32_t*)b->idx[cur ^ 1].p;
+    a.idx_cur = (int32_t*)b->idx[cur].p;
+    a.partials = (double*)b->partials.p;
+    a.mom = (double*)b->mom.p;
+    a.thr = b->gated ? b->thr.p : nullptr;
+    a.trim_rank = b->trimmed ? (const int*)b->trim_rank.p : nullptr;
+    a.dist = b->dist.p;
+    a.tau = b->tau.p;
+    HIP_TRY(icp::launch_batch_pass(a, c->stream));
     HIP_TRY(hipMemcpyAsync(b->h_mom, b->mom.p, (size_t)b->count * ICP_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     b->steps += 1;
@@ -299,8 +376,7 @@ int icp_batch_create(icp_ctx* c, int count, const void* moving_aos, const int64_
     const bool finite = precision == ICP_F64 ? all_finite<double>(moving_aos, moving_off[count]) && all_finite<double>(model_aos, model_off[count])
                                              : all_finite<float>(moving_aos, moving_off[count]) && all_finite<float>(model_aos, model_off[count]);
     if (!finite) return fail(ICP_ERR_INVALID, "a cloud of the batch has a NaN or an infinite coordinate");
-    if (int rc = use(c)) return rc;
-    if (c->loop.pending) return fail(ICP_ERR_STATE, "the context has an enqueued pass that is not completed (icp_loop_complete first)");
+    if (int rc = ctx_ready(c)) return rc;
     ScopedPin pin(c);
     icp_batch* b = new (std::nothrow) icp_batch();
     if (!b) return fail(ICP_ERR_NOMEM, "batch");
@@ -330,12 +406,8 @@ int icp_batch_create(icp_ctx* c, int count, const void* moving_aos, const int64_
     }
     b->n_items = (int)items;
     b->H.resize((size_t)count);
-    b->status.assign((size_t)count, ICP_OK);
-    b->last_match.assign((size_t)count, 0);
-    b->applied_buf.assign((size_t)count, 0);
-    b->mom_seen.assign((size_t)count, 0);
-    b->tau_seen.assign((size_t)count, 0);
-    if (int rc = upload(b, moving_aos, moving_off, model_aos, model_off)) {
+    reset_loop_state(b);
+    if (int rc = upload(b, moving_aos, model_aos)) {
         (void)hipStreamSynchronize(c->stream);
         release(b);
         return rc;
@@ -365,11 +437,7 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
     for (int p = 0; p < b->count; ++p)
         if (int rc = b->H[p].begin(*prm)) return fail(rc, "bad loop parameters");
     for (int p = 0; p < b->count; ++p) b->H[p].gated = b->gated || b->trimmed;
-    b->status.assign((size_t)b->count, ICP_OK);
-    b->last_match.assign((size_t)b->count, 0);
-    b->applied_buf.assign((size_t)b->count, 0);
-    b->mom_seen.assign((size_t)b->count, 0);
-    b->tau_seen.assign((size_t)b->count, 0);
+    reset_loop_state(b);
     if (b->have_init) {
         // the start cloud of every pair in one launch, and one flag per pair back: a finite transform can carry a finite cloud
         // out of the precision's range, and the library refuses non-finite clouds at the door -- that pair begins ended
@@ -462,12 +530,10 @@ int icp_diag_batch_trim(icp_batch* b, int pair, double* tau_sq, int* rank)
     if (tau_sq) {
         *tau_sq = INFINITY;   // (a batch that runs the fused pass keeps no tau buffer up to date: none of its pairs is trimmed)
         if (b->trimmed) {
-            double d = 0.0;
-            float f = 0.0f;
-            void* dst = b->prec == ICP_F64 ? (void*)&d : (void*)&f;
-            HIP_TRY(hipMemcpyAsync(dst, static_cast<const char*>(b->tau.p) + (size_t)pair * b->esize, b->esize, hipMemcpyDeviceToHost, b->ctx->stream));
+            double raw = 0.0;   // (room for either precision)
+            HIP_TRY(hipMemcpyAsync(&raw, static_cast<const char*>(b->tau.p) + (size_t)pair * b->esize, b->esize, hipMemcpyDeviceToHost, b->ctx->stream));
             HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-            *tau_sq = b->prec == ICP_F64 ? d : (double)f;
+            *tau_sq = get_scalar(b, &raw, 0);
         }
     }
     return ICP_OK;
@@ -488,8 +554,7 @@ int icp_batch_get_moving(icp_batch* b, void* aos_out)
     std::vector<char> raw(3 * (size_t)b->p_plane * b->esize);
     HIP_TRY(hipMemcpyAsync(raw.data(), b->P.p, raw.size(), hipMemcpyDeviceToHost, b->ctx->stream));
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    if (b->prec == ICP_F64) from_planes<double>(raw, b, aos_out);
-    else from_planes<float>(raw, b, aos_out);
+    planes_to_aos(b, raw, false, aos_out);
     return ICP_OK;
 }
 
@@ -516,11 +581,7 @@ int icp_batch_set_max_distance(icp_batch* b, const double* max_dist)
                 return fail(ICP_ERR_INVALID, "the maximum correspondence distance must be > 0 or +INFINITY: pair " + std::to_string(p));
         // thr = (F)(max_dist^2): the product in double, rounded once to the batch's precision
         std::vector<char> h((size_t)b->count * b->esize);
-        for (int p = 0; p < b->count; ++p) {
-            const double sq = max_dist[p] * max_dist[p];
-            if (b->prec == ICP_F64) reinterpret_cast<double*>(h.data())[p] = sq;
-            else reinterpret_cast<float*>(h.data())[p] = (float)sq;
-        }
+        for (int p = 0; p < b->count; ++p) put_scalar(b, h.data(), (size_t)p, max_dist[p] * max_dist[p]);
         HIP_TRY(b->thr.ensure(h.size()));
         b->begun = false;   // a loop under way is discarded: its passes so far used other thresholds (or none)
         b->gated = false;
@@ -557,8 +618,7 @@ int icp_batch_set_trim(icp_batch* b, const double* keep_ratio)
         rank[p] = k < 1.0 ? 1 : k > (double)n ? n : (int)k;
         dev_rank[p] = keep_ratio[p] == 1.0 ? 0 : rank[p];
         any = any || dev_rank[p] != 0;
-        if (b->prec == ICP_F64) reinterpret_cast<double*>(inf.data())[p] = INFINITY;
-        else reinterpret_cast<float*>(inf.data())[p] = INFINITY;
+        put_scalar(b, inf.data(), (size_t)p, INFINITY);
     }
     HIP_TRY(b->trim_rank.ensure(dev_rank.size() * sizeof(int)));
     HIP_TRY(b->tau.ensure(inf.size()));
@@ -611,8 +671,8 @@ int icp_batch_set_initial_transforms(icp_batch* b, const double* T16)
         if (b->prec == ICP_F64) put_rt<double>(dst, R, t);
         else put_rt<float>(dst, R, t);
         for (int a = 0; a < 3; ++a) {
-            for (int c = 0; c < 3; ++c) o[a * 4 + c] = b->prec == ICP_F64 ? R[a * 3 + c] : (double)(float)R[a * 3 + c];
-            o[a * 4 + 3] = b->prec == ICP_F64 ? t[a] : (double)(float)t[a];
+            for (int c = 0; c < 3; ++c) o[a * 4 + c] = get_scalar(b, dst, (size_t)(a * 3 + c));
+            o[a * 4 + 3] = get_scalar(b, dst, (size_t)(9 + a));
         }
         o[12] = o[13] = o[14] = 0.0;
         o[15] = 1.0;
@@ -638,21 +698,12 @@ int icp_batch_set_model_normals(icp_batch* b, const void* nxyz_aos)
     const int64_t points = b->qoff[b->count];
     if (!(b->prec == ICP_F64 ? all_finite<double>(nxyz_aos, points) : all_finite<float>(nxyz_aos, points)))
         return fail(ICP_ERR_INVALID, "a normal of the batch has a NaN or an infinite component");
-    std::vector<long long> qdst(b->count);
-    for (int p = 0; p < b->count; ++p) qdst[p] = b->pairs[p].q_off;
-    const size_t qb = 3 * (size_t)b->q_plane * b->esize;
-    HIP_TRY(b->N.ensure(qb));
+    HIP_TRY(b->N.ensure(3 * (size_t)b->q_plane * b->esize));
     b->begun = false;   // a loop under way is discarded: its passes so far used other normals (or none)
     b->have_normals = false;
-    if (b->prec == ICP_F64) {
-        const std::vector<double> ns = to_planes<double>(nxyz_aos, b->qoff.data(), b->count, qdst, b->q_plane);
-        HIP_TRY(hipMemcpyAsync(b->N.p, ns.data(), qb, hipMemcpyHostToDevice, b->ctx->stream));
-        HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
-    } else {
-        const std::vector<float> ns = to_planes<float>(nxyz_aos, b->qoff.data(), b->count, qdst, b->q_plane);
-        HIP_TRY(hipMemcpyAsync(b->N.p, ns.data(), qb, hipMemcpyHostToDevice, b->ctx->stream));
-        HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    }
+    std::vector<char> ns;
+    if (int rc = enqueue_planes(b, nxyz_aos, true, b->N.p, ns)) return rc;
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
     b->have_normals = true;
     return ICP_OK;
 }
@@ -667,10 +718,7 @@ int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighb
     icp_ctx* c = b->ctx;
     const size_t qb = 3 * (size_t)b->q_plane * b->esize, nb = 4 * (size_t)b->q_plane * sizeof(int32_t);
     if (b->n_q_items == 0) {   // the model's work items: BATCH_ITEM model points of one pair, cut from that pair's first model point
-        std::vector<icp::BatchItem> items;
-        for (int p = 0; p < b->count; ++p)
-            for (int first = 0; first < b->pairs[p].m; first += icp::BATCH_ITEM)
-                items.push_back(icp::BatchItem{p, first, std::min(icp::BATCH_ITEM, b->pairs[p].m - first), 0});
+        const std::vector<icp::BatchItem> items = work_items(b, true);
         if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
         HIP_TRY(b->q_items.ensure(items.size() * sizeof(icp::BatchItem)));
         HIP_TRY(hipMemcpyAsync(b->q_items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, c->stream));
@@ -696,18 +744,10 @@ int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighb
         HIP_TRY(hipMemcpyAsync(hn.data(), b->nbr.p, nb, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int p = 0; p < b->count; ++p) {
-        const icp::BatchPair& pr = b->pairs[p];
-        if (nxyz_aos_out)
-            for (int i = 0; i < pr.m; ++i)
-                for (int k = 0; k < 3; ++k) {
-                    const size_t src = (size_t)(k * b->q_plane + pr.q_off + i), dst = 3 * (size_t)(b->qoff[p] + i) + k;
-                    if (b->prec == ICP_F64) static_cast<double*>(nxyz_aos_out)[dst] = reinterpret_cast<const double*>(raw.data())[src];
-                    else static_cast<float*>(nxyz_aos_out)[dst] = reinterpret_cast<const float*>(raw.data())[src];
-                }
-        if (neighbours_out)
-            std::memcpy(neighbours_out + 4 * b->qoff[p], hn.data() + 4 * (size_t)pr.q_off, 4 * (size_t)pr.m * sizeof(int32_t));
-    }
+    if (nxyz_aos_out) planes_to_aos(b, raw, true, nxyz_aos_out);
+    if (neighbours_out)
+        for (int p = 0; p < b->count; ++p)
+            std::memcpy(neighbours_out + 4 * b->qoff[p], hn.data() + 4 * (size_t)b->pairs[p].q_off, 4 * (size_t)b->pairs[p].m * sizeof(int32_t));
     b->have_normals = true;
     return ICP_OK;
 }

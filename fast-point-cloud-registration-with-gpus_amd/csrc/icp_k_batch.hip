@@ -1,0 +1,446 @@
+// icp_k_batch.hip -- gfx950 kernels of batched ICP (icp_batch.cpp): the pass of every running pair in one launch (nn_match_batch:
+// front end, matching, moments), trimmed rejection (batch_trim_select, batch_trim_moments), the per-pair reduction
+// (batch_finalize_kernel) and the start clouds of a batch with initial transforms (batch_init_kernel).  The batched neighbours and
+// normals (knn4_batch, normals_batch_kernel) live with the single-pair ones in icp_k_plane.hip.  Reference statements: the loop a
+// pair runs is src/ICP_point_to_point.cu:295-423 / src/ICP_point_to_plane.cu:517-631; the kernels restate nn_match_kernel,
+// moments_kernel and transform_error_kernel (icp_k_dense.hip) per work item.
+#include "icp_device.h"
+#include <math.h>
+#include <stdlib.h>
+#include <cstring>
+
+namespace icp {
+
+// ------------------------------------------------------------------------------------------------
+// batched ICP (icp_batch.cpp): the pass of every running pair of a batch in one launch.
+//
+// grid = one block per work item: BATCH_ITEM moving points of one pair, cut from that pair's first point.  All four waves
+// hold the item's points (one per lane); wave w scans the w-th contiguous quarter of the pair's model through its own LDS
+// sub-tile (every lane reads the same address), keeping the running minimum and the first chunk that lowered it, as
+// nn_match_kernel does; the index is recovered inside that chunk, and the quarters are merged in ascending order with a
+// strict <: the lowest index wins ties, as in the reference's ascending scan.
+//   front end (pass >= 1): the pair's previous R, t by apply_rt -- every wave moves its copy of the points with the same
+//     instructions; wave 0 stores them and adds |p_new - q[idx_prev]|^2 in double (transform_error_kernel's arithmetic);
+//   tail: wave 0 stores idx, gathers q[idx] and forms moments_kernel's point-to-point terms in double; block_sum_store
+//     writes the item's row partials[item][0 .. ICP_MOM_SQQ] (error in slot ICP_MOM_ERR).
+//   METRIC == ICP_POINT_TO_PLANE (its own instantiation: the point-to-point one has no branch on the metric): wave 0 gathers
+//     n[idx] too, from the normal planes laid out as the model's, and forms moments_kernel's plane terms statement for
+//     statement -- cn = (p x n, n), bi = (p - q) . n, C += cn cn^T, b -= cn bi -- into slots ICP_MOM_CNT, ICP_MOM_C ..
+//     ICP_MOM_B + 5.  The front end and the error-only last pass are the same code.
+//   GATE (its own instantiations: the ungated ones have no branch on it and never read thr): wave 0 keeps the match only if
+//     the merged minimum b -- the dist2<F> the scan already holds, nothing recomputed -- is <= thr[pair], the pair's squared
+//     maximum correspondence distance in F (+inf: not gated).  A rejected point leaves every accumulator 0, ICP_MOM_CNT
+//     included, and its idx entry carries BATCH_IDX_REJECTED above the nearest neighbour's index; the next pass's front end
+//     reads that entry anyway (idx_prev) and adds the point's error only if the bit is clear.  Downloads strip the bit.
+// A pair's blocks, their geometry and every sum depend on that pair alone (no atomics): its bits do not depend on the batch.
+// ------------------------------------------------------------------------------------------------
+template <typename F> struct BatchCfg;
+template <> struct BatchCfg<float> { static constexpr int TW = 512; };    // model points per wave and tile: 6 KiB per wave
+template <> struct BatchCfg<double> { static constexpr int TW = 256; };
+static_assert(sizeof(RT<float>) == 12 * sizeof(float) && sizeof(RT<double>) == 12 * sizeof(double), "the host writes R, t as 12 values per pair");
+
+// slots of the moment vector a batch pass fills: error, count, sum p, sum q, sum q p^T, |p|^2, |q|^2 -- or error, count, C (21), b (6)
+template <int METRIC> struct BatchAcc { static constexpr int N = (METRIC == ICP_POINT_TO_POINT) ? ICP_MOM_SQQ + 1 : ICP_MOM_B + 6; };
+
+// What one moving point (x, y, z), matched to model point j of its pair, adds to the accumulators acc[] of its lane (all zero
+// before): nothing if the match was not kept.  ONE definition for the fused tail of nn_match_batch and for batch_trim_moments,
+// so that the two cannot drift and a pair that is not trimmed has the same bits on either route.  A macro, not a function: a
+// __device__ function, force-inlined, is simplified on its own before it is inlined, and the eight fused instantiations then
+// come out with other register numbers and commuted operands than the kernels whose timings DESIGN.md records (tried: by value,
+// by reference, into a local array).  As statements they compile to the listings they always had.  To be used inside a template
+// with METRIC in scope; Qx_, Qy_, Qz_: the pair's model planes, Nrm_ + q_off_: its normal planes (read for the plane metric only).
+#define ICP_BATCH_POINT_TERMS(acc, kept_, x_, y_, z_, j_, Qx_, Qy_, Qz_, Nrm_, q_off_, q_plane_)                              \
+    {                                                                                                                        \
+        const double px = (double)(x_), py = (double)(y_), pz = (double)(z_);                                                \
+        const double qx = (double)(Qx_)[j_], qy = (double)(Qy_)[j_], qz = (double)(Qz_)[j_];                                 \
+        if (!(kept_)) {                                                                                                      \
+            /* (a rejected point adds nothing: every accumulator stays 0, the count included) */                             \
+        } else if constexpr (METRIC == ICP_POINT_TO_POINT) {                                                                 \
+            acc[ICP_MOM_CNT] = 1.0;                                                                                          \
+            acc[ICP_MOM_SP + 0] = px; acc[ICP_MOM_SP + 1] = py; acc[ICP_MOM_SP + 2] = pz;                                    \
+            acc[ICP_MOM_SQ + 0] = qx; acc[ICP_MOM_SQ + 1] = qy; acc[ICP_MOM_SQ + 2] = qz;                                    \
+            acc[ICP_MOM_SQP + 0] = qx * px; acc[ICP_MOM_SQP + 1] = qx * py; acc[ICP_MOM_SQP + 2] = qx * pz;                  \
+            acc[ICP_MOM_SQP + 3] = qy * px; acc[ICP_MOM_SQP + 4] = qy * py; acc[ICP_MOM_SQP + 5] = qy * pz;                  \
+            acc[ICP_MOM_SQP + 6] = qz * px; acc[ICP_MOM_SQP + 7] = qz * py; acc[ICP_MOM_SQP + 8] = qz * pz;                  \
+            acc[ICP_MOM_SPP] = px * px + py * py + pz * pz;                                                                  \
+            acc[ICP_MOM_SQQ] = qx * qx + qy * qy + qz * qz;                                                                  \
+        } else {                                                                                                             \
+            acc[ICP_MOM_CNT] = 1.0;                                                                                          \
+            const F* Nx = (Nrm_) + (q_off_);                                                                                 \
+            const double nx = (double)Nx[j_], ny = (double)Nx[(q_plane_) + j_], nz = (double)Nx[2 * (q_plane_) + j_];        \
+            double cn[6];                                                                                                    \
+            cn[0] = py * nz - pz * ny;                                                                                       \
+            cn[1] = pz * nx - px * nz;                                                                                       \
+            cn[2] = px * ny - py * nx;                                                                                       \
+            cn[3] = nx; cn[4] = ny; cn[5] = nz;                                                                              \
+            const double bi = (px - qx) * nx + (py - qy) * ny + (pz - qz) * nz;                                              \
+            int o = ICP_MOM_C;                                                                                               \
+            _Pragma("unroll") for (int a = 0; a < 6; ++a)                                                                    \
+                _Pragma("unroll") for (int c = a; c < 6; ++c) acc[o++] += cn[a] * cn[c];                                     \
+            _Pragma("unroll") for (int a = 0; a < 6; ++a) acc[ICP_MOM_B + a] -= cn[a] * bi;                                  \
+        }                                                                                                                    \
+    }
+
+// DEFER (its own instantiations, <F, METRIC, true, true>, for a batch that trims: see batch_trim_select below): the gated front
+// end and the same search, and a tail in which wave 0 only stores idx_cur[gi] = j and dist[gi] = the merged minimum b -- no
+// decision, no terms; the row carries ICP_MOM_ERR and zeros.  The fused instantiations never touch dist.
+template <typename F, int METRIC, bool GATE, bool DEFER = false>
+__global__ __launch_bounds__(NN_BLOCK) void nn_match_batch(const BatchItem* __restrict__ items, const BatchPair* __restrict__ pairs,
+                                                           const int* __restrict__ mode, const RT<F>* __restrict__ rts,
+                                                           F* __restrict__ P, long long p_plane, const F* __restrict__ Q,
+                                                           const F* __restrict__ Nrm, long long q_plane,
+                                                           const int32_t* __restrict__ idx_prev, int32_t* __restrict__ idx_cur,
+                                                           double* __restrict__ partials, const F* __restrict__ thr,
+                                                           F* __restrict__ dist)
+{
+    using V = typename Vec16<F>::type;
+    constexpr int VN = Vec16<F>::N;
+    constexpr int TW = BatchCfg<F>::TW, C = NN_CHUNK;
+    constexpr int NACC = BatchAcc<METRIC>::N;
+    static_assert(BATCH_ITEM == 64 && NN_BLOCK == 4 * BATCH_ITEM, "one point per lane, four waves per item");
+    __shared__ __attribute__((aligned(16))) F sq[4][3][TW];
+    __shared__ F md[4][BATCH_ITEM];
+    __shared__ int mi[4][BATCH_ITEM];
+
+    const BatchItem it = items[blockIdx.x];
+    const int pm = mode[it.pair];
+    if (pm == 0) return;   // the pair has ended (or takes no part in this pass): the whole block leaves
+    const BatchPair pr = pairs[it.pair];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool live = lane < it.count;
+    const long long gi = pr.p_off + it.first + (live ? lane : 0);   // (lanes past the item's end work on its first point: nothing of theirs is kept)
+    const F* Qx = Q + pr.q_off;
+    const F* Qy = Qx + q_plane;
+    const F* Qz = Qx + 2 * q_plane;
+
+    F x = P[gi], y = P[p_plane + gi], z = P[2 * p_plane + gi];
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    __syncthreads();   // every wave holds its points before wave 0 overwrites them
+
+    if (pm & BATCH_APPLY) {
+        apply_rt<F>(rts[it.pair], x, y, z, x, y, z);
+        if (w == 0 && live) {
+            P[gi] = x;
+            P[p_plane + gi] = y;
+            P[2 * p_plane + gi] = z;
+            const int jr = idx_prev[gi];
+            const int j = GATE ? (jr & BATCH_IDX_MASK) : jr;
+            const double dx = (double)Qx[j] - (double)x;
+            const double dy = (double)Qy[j] - (double)y;
+            const double dz = (double)Qz[j] - (double)z;
+            if (!GATE || jr >= 0) acc[ICP_MOM_ERR] = dx * dx + dy * dy + dz * dz;   // (only a point kept by that matching pass)
+        }
+    }
+
+    if (pm & BATCH_MATCH) {
+        const int m = pr.m;
+        const int wseg = ((m + 3) / 4 + C - 1) / C * C;   // model points per wave, whole chunks
+        const int my0 = w * wseg, my1 = min(my0 + wseg, m);  // may be empty (my1 <= my0)
+        const int ntile = (wseg + TW - 1) / TW;           // the same for every wave: the barriers pair up
+        F best = inf_<F>();
+        int cst = -1;   // first model index of the chunk that last lowered `best`
+        for (int k = 0; k < ntile; ++k) {
+            const int t0 = my0 + k * TW;
+            __syncthreads();
+            // this wave's sub-tile; places past the quarter's end hold +inf, which never lowers a minimum
+            for (int e = lane; e < TW; e += 64) {
+                const int j = t0 + e;
+                F qx = inf_<F>(), qy = inf_<F>(), qz = inf_<F>();
+                if (j < my1) { qx = Qx[j]; qy = Qy[j]; qz = Qz[j]; }
+                sq[w][0][e] = qx;
+                sq[w][1][e] = qy;
+                sq[w][2][e] = qz;
+            }
+            __syncthreads();
+            const int len = min(TW, my1 - t0);   // <= 0: this wave's quarter is exhausted
+            for (int c = 0; c < len; c += C) {
+                const F bo = best;
+#pragma unroll
+                for (int kk = 0; kk < C; kk += VN) {
+                    const V qx = *reinterpret_cast<const V*>(&sq[w][0][c + kk]);
+                    const V qy = *reinterpret_cast<const V*>(&sq[w][1][c + kk]);
+                    const V qz = *reinterpret_cast<const V*>(&sq[w][2][c + kk]);
+#pragma unroll
+                    for (int v = 0; v < VN; ++v) best = fmin_(best, dist2<F>(x, y, z, vget(qx, v), vget(qy, v), vget(qz, v)));
+                }
+                cst = (best < bo) ? t0 + c : cst;
+            }
+        }
+        // the lowest j of the winning chunk with d_j == min (global memory, L2-resident)
+        int bi = 0x7fffffff;
+        if (cst >= 0) {
+            bi = cst;
+            for (int kk = C - 1; kk >= 0; --kk) {
+                const int j = cst + kk;
+                if (j < my1) {
+                    const F d = dist2<F>(x, y, z, Qx[j], Qy[j], Qz[j]);
+                    bi = (d == best) ? j : bi;
+                }
+            }
+        }
+        md[w][lane] = cst >= 0 ? best : inf_<F>();
+        mi[w][lane] = bi;
+        __syncthreads();
+        if (w == 0 && live) {
+            F b = md[0][lane];
+            int j = mi[0][lane];
+#pragma unroll
+            for (int ww = 1; ww < 4; ++ww)
+                if (md[ww][lane] < b) { b = md[ww][lane]; j = mi[ww][lane]; }
+            j = ((unsigned)j < (unsigned)m) ? j : 0;   // (nothing found only if every distance overflowed: idx stays in range)
+            if constexpr (DEFER) {
+                // (the deferred route: batch_trim_select ranks the pair's distances, batch_trim_moments decides and forms the terms)
+                idx_cur[gi] = j;
+                dist[gi] = b;
+            } else {
+                const bool kept = !GATE || b <= thr[it.pair];
+                idx_cur[gi] = kept ? j : (j | BATCH_IDX_REJECTED);
+                ICP_BATCH_POINT_TERMS(acc, kept, x, y, z, j, Qx, Qy, Qz, Nrm, pr.q_off, q_plane)
+            }
+        }
+    }
+    // (waves 1-3 add zeros: the row is wave 0's 64 lanes, summed in lane order)
+    block_sum_store<NACC, NN_BLOCK>(acc, partials + (size_t)blockIdx.x * ICP_NMOM);
+}
+
+// ------------------------------------------------------------------------------------------------
+// trimmed rejection (icp_batch_set_trim): a pair keeps the K closest of its n matches (and every match tied with the K-th).  The
+// K-th smallest distance of a pair is known only when every one of its points has been matched -- by other blocks, for a
+// pair of more than one work item -- so the fused pass cannot decide; a step of a batch that trims runs four launches:
+//   nn_match_batch<.., DEFER>   front end + search as the gated pass; wave 0 stores idx and the winning distance, no terms
+//   batch_trim_select         one block per pair: tau[pair] = the K-th smallest of the pair's n distances
+//   batch_trim_moments        one block per work item: kept = d <= tau[pair] (and d <= thr[pair]); marks idx, forms the terms
+//   batch_finalize_kernel     as ever
+// A pair's tau, its masks and its sums depend on that pair alone: integer counts, fixed summation order, no floating-point
+// atomics.  A pair that is not trimmed (rank 0, tau = +inf, written once by the host) keeps everything, and its rows are the
+// fused pass's bit for bit: the same terms (ICP_BATCH_POINT_TERMS) in the same lanes through the same block_sum_store.
+// ------------------------------------------------------------------------------------------------
+// the values are >= +0 and never NaN (a sum of squares of finite differences, +inf on overflow): their bit patterns, read as
+// unsigned integers, sort as the values do
+template <typename F> struct TrimKey;
+template <> struct TrimKey<float> {
+    using U = unsigned int;
+    static __device__ __forceinline__ U key(float v) { return __float_as_uint(v); }
+    static __device__ __forceinline__ float value(U k) { return __uint_as_float(k); }
+};
+template <> struct TrimKey<double> {
+    using U = unsigned long long;
+    static __device__ __forceinline__ U key(double v) { return (U)__double_as_longlong(v); }
+    static __device__ __forceinline__ double value(U k) { return __longlong_as_double((long long)k); }
+};
+
+// one block per pair: tau[pair] = the rank[pair]-th smallest of dist[p_off .. p_off + n), one of those values bit for bit.
+// Most-significant-digit radix select, 8 bits per round (4 rounds for fp32, 8 for fp64): every thread adds the values that
+// still carry the prefix found so far to a 256-bin LDS histogram of their next digit (integer LDS atomics: the counts do not
+// depend on the order of the adds), wave 0 scans the bins for the one that holds the remaining rank, and that digit joins the
+// prefix.  Each round re-reads the pair's at most ICP_BATCH_MAX_POINTS values (L2-resident).  rank 0: the pair is not trimmed.
+constexpr int TRIM_BLOCK = 256;
+template <typename F>
+__global__ __launch_bounds__(TRIM_BLOCK) void batch_trim_select(const BatchPair* __restrict__ pairs, const int* __restrict__ mode,
+                                                                const int* __restrict__ rank, const F* __restrict__ dist,
+                                                                F* __restrict__ tau)
+{
+    using K = TrimKey<F>;
+    using U = typename K::U;
+    constexpr int BITS = 8 * (int)sizeof(U);
+    __shared__ unsigned int hist[256];
+    __shared__ U s_prefix;
+    __shared__ unsigned int s_rest;
+    const int pair = blockIdx.x;
+    if (!(mode[pair] & BATCH_MATCH)) return;
+    const int kth = rank[pair];
+    const int n = pairs[pair].n;
+    if (kth < 1 || kth > n) return;   // not trimmed (a trimmed pair's rank lies in [1, n])
+    const F* d = dist + pairs[pair].p_off;
+    const int lane = threadIdx.x & 63;
+    U prefix = 0;
+    unsigned int rest = (unsigned int)(kth - 1);   // values below the wanted one among those that carry the prefix
+    for (int shift = BITS - 8; shift >= 0; shift -= 8) {
+        hist[threadIdx.x] = 0u;
+        __syncthreads();
+        // (a shift by the type's width is undefined: the first round, where every value carries the empty prefix, has no mask)
+        const U high = (shift + 8 < BITS) ? (~U(0) << ((shift + 8) & (BITS - 1))) : U(0);
+        for (int i = threadIdx.x; i < n; i += TRIM_BLOCK) {
+            const U k = K::key(d[i]);
+            if ((k & high) == prefix) atomicAdd(&hist[(unsigned int)(k >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            // lane l holds bins 4l .. 4l + 3; an inclusive scan over the lanes finds the lane, then the bin, that holds `rest`
+            const unsigned int c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
+            const unsigned int mine = c0 + c1 + c2 + c3;
+            unsigned int incl = mine;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned int up = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += up;
+            }
+            const unsigned int excl = incl - mine;
+            if (excl <= rest && rest < incl) {   // exactly one lane: the bins hold more than `rest` values between them
+                unsigned int r = rest - excl, bin = 4u * lane;
+                if (r >= c0) { r -= c0; ++bin; if (r >= c1) { r -= c1; ++bin; if (r >= c2) { r -= c2; ++bin; } } }
+                s_prefix = prefix | ((U)bin << shift);
+                s_rest = r;
+            }
+        }
+        __syncthreads();
+        prefix = s_prefix;
+        rest = s_rest;
+    }
+    if (threadIdx.x == 0) tau[pair] = K::value(prefix);
+}
+
+// one block per work item, over nn_match_batch's items and in its block shape (wave 0 alone carries data, waves 1-3 add zeros, so
+// that block_sum_store adds a row in the fused pass's order): kept = d <= tau[pair] && (no gate || d <= thr[pair]); a rejected
+// point's idx entry gets BATCH_IDX_REJECTED; the kept points' terms go to slots 1 .. of the item's row.  Slot ICP_MOM_ERR, which
+// nn_match_batch<.., DEFER> wrote, is not touched.
+template <typename F, int METRIC>
+__global__ __launch_bounds__(NN_BLOCK) void batch_trim_moments(const BatchItem* __restrict__ items, const BatchPair* __restrict__ pairs,
+                                                               const int* __restrict__ mode, const F* __restrict__ P, long long p_plane,
+                                                               const F* __restrict__ Q, const F* __restrict__ Nrm, long long q_plane,
+                                                               int32_t* __restrict__ idx_cur, const F* __restrict__ dist,
+                                                               const F* __restrict__ tau, const F* __restrict__ thr,
+                                                               double* __restrict__ partials)
+{
+    constexpr int NACC = BatchAcc<METRIC>::N;
+    static_assert(ICP_MOM_ERR == 0, "the row's slots behind the error are written as one run");
+    const BatchItem it = items[blockIdx.x];
+    if (!(mode[it.pair] & BATCH_MATCH)) return;   // nothing was matched for this pair: the row stays the error and zeros
+    const BatchPair pr = pairs[it.pair];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    if (w == 0 && lane < it.count) {
+        const long long gi = pr.p_off + it.first + lane;
+        const F* Qx = Q + pr.q_off;
+        const F b = dist[gi];
+        const int j = idx_cur[gi];
+        const bool kept = b <= tau[it.pair] && (thr == nullptr || b <= thr[it.pair]);
+        if (!kept) idx_cur[gi] = j | BATCH_IDX_REJECTED;
+        const F* Qy = Qx + q_plane;
+        const F* Qz = Qx + 2 * q_plane;
+        const F x = P[gi], y = P[p_plane + gi], z = P[2 * p_plane + gi];
+        ICP_BATCH_POINT_TERMS(acc, kept, x, y, z, j, Qx, Qy, Qz, Nrm, pr.q_off, q_plane)
+    }
+    double tail[NACC - 1];
+#pragma unroll
+    for (int k = 1; k < NACC; ++k) tail[k - 1] = acc[k];
+    block_sum_store<NACC - 1, NN_BLOCK>(tail, partials + (size_t)blockIdx.x * ICP_NMOM + 1);
+}
+#undef ICP_BATCH_POINT_TERMS
+
+// one block per pair: mom[pair] = the pair's item rows added up in a fixed order (thread (k, part) adds items part, part + 8, ...
+// of slot k; the eight part sums are then added in part order -- finalize_kernel's scheme, over the pair's own items only).
+// last = the metric's last slot: ICP_MOM_SQQ, or ICP_MOM_B + 5 for a plane loop; the slots behind it are written as zeros.
+__global__ __launch_bounds__(256) void batch_finalize_kernel(const BatchPair* __restrict__ pairs, const int* __restrict__ mode,
+                                                             const double* __restrict__ partials, int last, double* __restrict__ mom)
+{
+    __shared__ double red[8][ICP_NMOM];
+    if (mode[blockIdx.x] == 0) return;
+    const int k = threadIdx.x & 31, part = threadIdx.x >> 5;
+    const int i0 = pairs[blockIdx.x].item0, i1 = pairs[blockIdx.x].item1;
+    double s = 0.0;
+    if (k <= last)
+        for (int i = i0 + part; i < i1; i += 8) s += partials[(size_t)i * ICP_NMOM + k];
+    red[part][k] = s;
+    __syncthreads();
+    if (threadIdx.x < ICP_NMOM) {
+        double tot = red[0][k];
+#pragma unroll
+        for (int p = 1; p < 8; ++p) tot += red[p][k];
+        mom[(size_t)blockIdx.x * ICP_NMOM + k] = tot;
+    }
+}
+
+hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st)
+{
+    if (a.n_items <= 0 || a.n_pairs <= 0) return hipSuccess;
+    const bool plane = a.metric == ICP_POINT_TO_PLANE;
+    if (plane && !a.N_soa) return hipErrorInvalidValue;
+    if (a.trim_rank && (!a.dist || !a.tau)) return hipErrorInvalidValue;
+#define ICP_LAUNCH_BATCH(F, MET, GATE)                                                                                           \
+    hipLaunchKernelGGL((nn_match_batch<F, MET, GATE>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs, a.mode,          \
+                       (const RT<F>*)a.rt, (F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)a.N_soa, a.q_plane, a.idx_prev,   \
+                       a.idx_cur, a.partials, (const F*)a.thr, (F*)nullptr)
+    // a batch that trims: matching without a decision, the K-th distance of every pair, then the decision and the terms
+#define ICP_LAUNCH_BATCH_TRIM(F, MET)                                                                                            \
+    do {                                                                                                                         \
+        hipLaunchKernelGGL((nn_match_batch<F, MET, true, true>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs,        \
+                           a.mode, (const RT<F>*)a.rt, (F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)nullptr, a.q_plane,   \
+                           a.idx_prev, a.idx_cur, a.partials, (const F*)nullptr, (F*)a.dist);                                     \
+        hipLaunchKernelGGL((batch_trim_select<F>), dim3(a.n_pairs), dim3(TRIM_BLOCK), 0, st, a.pairs, a.mode, a.trim_rank,        \
+                           (const F*)a.dist, (F*)a.tau);                                                                          \
+        hipLaunchKernelGGL((batch_trim_moments<F, MET>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs, a.mode,        \
+                           (const F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)a.N_soa, a.q_plane, a.idx_cur,              \
+                           (const F*)a.dist, (const F*)a.tau, (const F*)a.thr, a.partials);                                       \
+    } while (0)
+#define ICP_LAUNCH_BATCH_F(F)                                                                                                  \
+    do {                                                                                                                       \
+        if (a.trim_rank) {                                                                                                     \
+            if (plane) ICP_LAUNCH_BATCH_TRIM(F, ICP_POINT_TO_PLANE); else ICP_LAUNCH_BATCH_TRIM(F, ICP_POINT_TO_POINT);        \
+        } else if (a.thr) {                                                                                                    \
+            if (plane) ICP_LAUNCH_BATCH(F, ICP_POINT_TO_PLANE, true); else ICP_LAUNCH_BATCH(F, ICP_POINT_TO_POINT, true);      \
+        } else {                                                                                                               \
+            if (plane) ICP_LAUNCH_BATCH(F, ICP_POINT_TO_PLANE, false); else ICP_LAUNCH_BATCH(F, ICP_POINT_TO_POINT, false);    \
+        }                                                                                                                      \
+    } while (0)
+    if (a.precision == ICP_F64) ICP_LAUNCH_BATCH_F(double); else ICP_LAUNCH_BATCH_F(float);
+#undef ICP_LAUNCH_BATCH_F
+#undef ICP_LAUNCH_BATCH_TRIM
+#undef ICP_LAUNCH_BATCH
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(batch_finalize_kernel, dim3(a.n_pairs), dim3(256), 0, st, a.pairs, a.mode, (const double*)a.partials,
+                       plane ? ICP_MOM_B + 5 : ICP_MOM_SQQ, a.mom);
+    return hipGetLastError();
+}
+
+// the start cloud of every pair of a batch that holds initial transforms (icp_batch_begin): P = apply_rt(rt0[pair], P0) -- the
+// front end's own arithmetic, so a loop from here is the loop of a batch created from this cloud -- or P0's bytes for a pair
+// whose kind is BATCH_INIT_COPY (the exact identity: a -0.0 stays a -0.0).  Reads P0 and writes P, as the copy it replaces.
+// One wave per work item (four items per block), one point per lane; the padding between the clouds is not touched.  A
+// transformed point with a NaN or an infinite coordinate raises its pair's flag (zero before the launch): a plain vector store
+// of 1 from every such lane, whoever comes last.
+template <typename F>
+__global__ __launch_bounds__(NN_BLOCK) void batch_init_kernel(const BatchItem* __restrict__ items, int n_items,
+                                                              const BatchPair* __restrict__ pairs, const int* __restrict__ kind,
+                                                              const RT<F>* __restrict__ rt0, const F* __restrict__ P0,
+                                                              F* __restrict__ P, long long p_plane, int* __restrict__ nonfinite)
+{
+    const int item = blockIdx.x * (NN_BLOCK / BATCH_ITEM) + (threadIdx.x >> 6);
+    if (item >= n_items) return;
+    const BatchItem it = items[item];
+    const int lane = threadIdx.x & 63;
+    if (lane >= it.count) return;
+    const long long gi = pairs[it.pair].p_off + it.first + lane;
+    F x = P0[gi], y = P0[p_plane + gi], z = P0[2 * p_plane + gi];
+    if (kind[it.pair] != BATCH_INIT_COPY) {
+        apply_rt<F>(rt0[it.pair], x, y, z, x, y, z);
+        // (x - x is 0 for every finite x, NaN for NaN and for +-inf)
+        const bool finite = (x - x) == F(0) && (y - y) == F(0) && (z - z) == F(0);
+        if (!finite) nonfinite[it.pair] = 1;
+    }
+    P[gi] = x;
+    P[p_plane + gi] = y;
+    P[2 * p_plane + gi] = z;
+}
+
+hipError_t launch_batch_init(int precision, const BatchItem* items, int n_items, const BatchPair* pairs, const int* kind, const void* rt0,
+                             const void* P0, void* P, long long p_plane, int* nonfinite, hipStream_t st)
+{
+    if (n_items <= 0) return hipSuccess;
+    const int nb = (n_items + NN_BLOCK / BATCH_ITEM - 1) / (NN_BLOCK / BATCH_ITEM);
+    if (precision == ICP_F64)
+        hipLaunchKernelGGL((batch_init_kernel<double>), dim3(nb), dim3(NN_BLOCK), 0, st, items, n_items, pairs, kind, (const RT<double>*)rt0,
+                           (const double*)P0, (double*)P, p_plane, nonfinite);
+    else
+        hipLaunchKernelGGL((batch_init_kernel<float>), dim3(nb), dim3(NN_BLOCK), 0, st, items, n_items, pairs, kind, (const RT<float>*)rt0,
+                           (const float*)P0, (float*)P, p_plane, nonfinite);
+    return hipGetLastError();
+}
+
+}  // namespace icp

@@ -4,6 +4,7 @@
 //   icp_k_row64.hip   nn_match_row64       rows of 64 points: the hall scan and everything up to 32 768 points
 //   icp_k_f64.hip     nn_match_row64_f64   the CPU path's precision on the same structure
 //   icp_k_dense.hip   nn_match_kernel / nn_match_f32_v2 (every pair), merge, moments, transform + error, finalize, layout
+//   icp_k_batch.hip   nn_match_batch (many pairs per launch), trimmed rejection, per-pair finalize, initial transforms
 //   icp_k_plane.hip   kNN(4) + normals, OS1 decode + conversion
 //   icp_k_setup.hip   duplicates, spatial order, boxes / samples / records, row order + roles, the control block of a pass
 //   icp_launch.hip    the plan (nn_plan) and the dispatch (launch_nn): host code only
@@ -380,19 +381,38 @@ struct BatchPair { long long p_off, q_off; int n, m, item0, item1; };   // items
 constexpr int32_t BATCH_IDX_REJECTED = INT32_MIN, BATCH_IDX_MASK = INT32_MAX;
 // pass over every item whose pair's mode is non-zero: [apply rt[pair] + error against idx_prev] -> [match -> idx_cur, moments]
 // -> partials[item][0..last slot of the metric]; then mom[pair][ICP_NMOM] = that pair's items added in item order (pairs of
-// mode 0 untouched).  metric ICP_POINT_TO_PLANE: N_soa = the model normals, laid out as Q_soa; the sums are moments_kernel's
-// plane terms (ICP_MOM_CNT, ICP_MOM_C .. ICP_MOM_B + 5).  thr: NULL (the ungated instantiations), or F[n_pairs], every pair's
-// squared maximum correspondence distance (+inf: that pair is not gated): only matches with d <= thr[pair] enter the sums, and
-// the error counts only the points idx_prev marks as kept.
-// trim_rank: NULL (the fused pass, two launches), or int[n_pairs], every pair's rank K in [1, n] (0: that pair is not trimmed):
-// the pass then runs deferred, in four launches -- nn_match_batch<.., DEFER> leaves every point's winning squared distance in
-// dist (F[p_plane], laid out as idx), batch_trim_select writes tau[pair] = the K-th smallest of the pair's distances for the
-// pairs that match and are trimmed (tau: F[n_pairs], +inf from the host for the others), and batch_trim_moments keeps the
-// matches with d <= tau[pair] (and d <= thr[pair] where thr is given), marks the others in idx_cur and forms the sums.
-hipError_t launch_batch_pass(int precision, int metric, const BatchItem* items, int n_items, const BatchPair* pairs, int n_pairs,
-                             const int* mode, const void* rt /* RT<F>[n_pairs] */, void* P_soa, long long p_plane, const void* Q_soa,
-                             const void* N_soa, long long q_plane, const int32_t* idx_prev, int32_t* idx_cur, double* partials,
-                             double* mom, const void* thr, const int* trim_rank, void* dist, void* tau, hipStream_t st);
+// mode 0 untouched).  F = the batch's precision.
+struct BatchPassArgs {
+    int precision;             // ICP_F32 / ICP_F64
+    int metric;                // ICP_POINT_TO_PLANE: the sums are moments_kernel's plane terms (ICP_MOM_CNT, ICP_MOM_C .. ICP_MOM_B + 5)
+    const BatchItem* items;
+    int n_items;
+    const BatchPair* pairs;
+    int n_pairs;
+    const int* mode;           // int[n_pairs]: BATCH_APPLY | BATCH_MATCH
+    const void* rt;            // RT<F>[n_pairs]: R, t of the pairs that apply
+    void* P_soa;               // the moving clouds
+    long long p_plane;
+    const void* Q_soa;         // the models
+    const void* N_soa;         // point-to-plane: the model normals, laid out as Q_soa (else NULL)
+    long long q_plane;
+    const int32_t* idx_prev;   // the matches the error of this pass is taken against
+    int32_t* idx_cur;          // the matches of this pass
+    double* partials;          // [n_items][ICP_NMOM]
+    double* mom;               // [n_pairs][ICP_NMOM]
+    // NULL (the ungated instantiations), or F[n_pairs], every pair's squared maximum correspondence distance (+inf: that pair is
+    // not gated): only matches with d <= thr[pair] enter the sums, and the error counts only the points idx_prev marks as kept
+    const void* thr;
+    // NULL (the fused pass, two launches), or int[n_pairs], every pair's rank K in [1, n] (0: that pair is not trimmed): the pass
+    // then runs deferred, in four launches -- nn_match_batch<.., DEFER> leaves every point's winning squared distance in dist,
+    // batch_trim_select writes tau[pair] = the K-th smallest of the pair's distances for the pairs that match and are trimmed, and
+    // batch_trim_moments keeps the matches with d <= tau[pair] (and d <= thr[pair] where thr is given), marks the others in
+    // idx_cur and forms the sums
+    const int* trim_rank;
+    void* dist;                // F[p_plane], laid out as idx (read and written only with trim_rank)
+    void* tau;                 // F[n_pairs], +inf from the host for the pairs that are not trimmed (only with trim_rank)
+};
+hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st);
 // the start cloud of a batch that holds initial transforms, in one launch over the same items: P[pair] = apply_rt(rt0[pair],
 // P0[pair]), or P0[pair]'s bytes where kind[pair] == BATCH_INIT_COPY; nonfinite[pair] (int[n_pairs], zero before the launch)
 // becomes 1 where a transformed point of the pair has a NaN or an infinite coordinate.  The padding of P is not written.

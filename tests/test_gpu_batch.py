@@ -9,53 +9,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from batch_ref import TOL_E, TOL_T, assert_same_run, fp32_pairs, fp64_pairs, rel, same_result_bits
 from clouds import ragged_pair   # (one home for the construction: the moment tests use the same clouds)
 
 pytestmark = pytest.mark.gpu
-
-TOL_T = 1e-5
-TOL_E = 1e-5
-
-
-def rel(a, b):
-    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(1e-300, np.abs(np.asarray(b)).max()))
-
-
-def assert_same_run(res_iterations, res_err, res_T, want, tol, fp32):
-    """(test_gpu_parity.assert_same_run) fp64 stops at the oracle's iteration; fp32 may stop one pass apart, but only where
-    the deciding |dE| sits on the threshold"""
-    n = min(len(res_err), len(want["err"]))
-    assert np.abs(np.asarray(res_err)[:n] - want["err"][:n]).max() < TOL_E
-    if res_iterations != want["iterations"]:
-        assert fp32 and abs(res_iterations - want["iterations"]) == 1, (res_iterations, want["iterations"])
-        k = min(res_iterations, want["iterations"]) + 1
-        dE = abs(want["err"][k] - want["err"][k - 1])
-        assert abs(dE - tol) < 5e-7 or abs(want["err"][k] - tol) < 5e-7, f"stop rule disagreed away from the threshold: dE={dE}"
-    assert rel(res_T, want["T"]) < TOL_T
-
-
-def fp64_pairs(pkg, orc):
-    """configs[0]-style pairs that stop at different iterations (25, 10, 56, 7, 1, 10 passes)"""
-    pairs = [orc.synth_icp_cpu(W) for W in (16, 24, 32)]
-    D = orc.synth_icp_cpu(20)[0]
-    for ang, t in [((0.3, -0.2, 0.1), (0.2, 0.1, -0.1)), ((0.05, 0.02, -0.04), (0.05, -0.02, 0.01)), ((0.6, 0.1, -0.3), (0.5, -0.2, 0.3))]:
-        pairs.append((D, pkg.datasets.make_model_cpu(D, ang, t)))
-    return pairs
-
-
-def fp32_pairs(pkg, golden):
-    import os
-    D = pkg.datasets.synthetic_grid(32, np.float32)
-    B = np.fromfile(os.path.join(golden, "bunny_res_xyz_f32.bin"), dtype=np.float32).reshape(-1, 3)
-    return [(D, pkg.datasets.make_model_gpu(D, *pkg.datasets.P2P_GPU)), (D, pkg.datasets.make_model_standard(D)),
-            (B, pkg.datasets.make_model_gpu(B, *pkg.datasets.BUNNY))]
-
-
-def same_bits(a, b):
-    assert a.iterations == b.iterations and a.passes == b.passes and a.extra["status"] == b.extra["status"]
-    for f in ("T", "err", "idx", "moved"):
-        x, y = getattr(a, f), getattr(b, f)
-        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), f
 
 
 # 1 ------------------------------------------------------------------------------------------------------------------------
@@ -150,8 +107,8 @@ def test_batch_pair_bits_do_not_depend_on_neighbours(ctx, pkg, orc, dtype):
     first = ctx.point_to_point_batch([X] + others, max_iter=60, tol=1e-7)[0]
     sixth = ctx.point_to_point_batch(others[:5] + [X] + others[5:], max_iter=60, tol=1e-7)[5]
     assert alone.passes > 3
-    same_bits(alone, first)
-    same_bits(alone, sixth)
+    same_result_bits(alone, first)
+    same_result_bits(alone, sixth)
 
 
 # 6 ------------------------------------------------------------------------------------------------------------------------
@@ -160,7 +117,7 @@ def test_batch_is_deterministic(ctx, pkg, orc, golden):
         a = ctx.point_to_point_batch(pairs, max_iter=it, tol=tol)
         b = ctx.point_to_point_batch(pairs, max_iter=it, tol=tol)
         for x, y in zip(a, b):
-            same_bits(x, y)
+            same_result_bits(x, y)
         with ctx.batch(pairs) as bt:   # begin starts again from the uploaded clouds
             for _ in range(2):
                 bt.begin(max_iter=it, tol=tol)
@@ -283,4 +240,4 @@ def test_batch_scale_256_pairs(ctx, pkg, orc):
         assert r.iterations == w["iterations"] and rel(r.T, w["T"]) < TOL_T and np.abs(r.err - w["err"]).max() < TOL_E
         assert np.array_equal(r.idx, w["idx"]) and rel(r.moved, w["moved"]) < TOL_T
     for b in (3, 100, 201, 255):
-        same_bits(ctx.point_to_point_batch([pairs[b]], max_iter=200, tol=1e-5)[0], res[b])
+        same_result_bits(ctx.point_to_point_batch([pairs[b]], max_iter=200, tol=1e-5)[0], res[b])

@@ -22,76 +22,15 @@ import numpy as np
 import pytest
 
 import ref_moments as rm
-import ref_numpy
-from clouds import ragged_pair
+from batch_ref import (CASES, TOL_E, TOL_T, bits_equal, check_front_end, check_sums, gate_case, gate_mask, keep_within, normals_for,
+                       reference_loop, rel, run_to_end, same_pair_bytes, sq_dist)
 
 pytestmark = pytest.mark.gpu
 
-TOL_T = 1e-5
-TOL_E = 1e-5
 MD = 0.05          # keeps the true picks once the clouds are roughly aligned
 MD_EMPTY = 0.03    # keeps nothing at pass 0
-CASES = [(200, 300, 70), (130, 1000, 64), (1025, 513, 130), (63, 17, 5)]
 KEPT = {(200, 300, 70): [29, 200, 200], (130, 1000, 64): [16, 120, 130, 130], (1025, 513, 130): [121, 1025, 1025]}
 PASSES = 4         # matching passes of the fixed-length loops of test 1; pass PASSES is the error-only one
-
-
-def gate_case(n, m, n_out, dtype=np.float32):
-    """(A, M, is_out): ragged_pair(n, m) with n_out far points as one run starting at point 64 (or behind a shorter cloud)"""
-    D, M = ragged_pair(n * 1000 + m, n, m)
-    O = (np.random.default_rng(n * 1000 + m + 7).standard_normal((n_out, 3)) * 0.5 + np.array([6.0, -5.0, 4.0])).astype(np.float32)
-    A = np.concatenate([D[:64], O, D[64:]])
-    is_out = np.zeros(n + n_out, dtype=bool)
-    is_out[min(64, n):min(64, n) + n_out] = True
-    return A.astype(dtype), M.astype(dtype), is_out
-
-
-def sq_dist(P, M, idx):
-    """the winning squared distance as the matching holds it: (dx*dx + dy*dy) + dz*dz, every operation rounded in P's dtype"""
-    G = M[idx]
-    dx, dy, dz = P[:, 0] - G[:, 0], P[:, 1] - G[:, 1], P[:, 2] - G[:, 2]
-    d = (dx * dx + dy * dy) + dz * dz
-    assert d.dtype == P.dtype
-    return d
-
-
-def threshold(md, dtype):
-    """(F)(md * md): the product in double, rounded once"""
-    return np.dtype(dtype).type(float(md) * float(md))
-
-
-def gate_mask(P, M, idx, md):
-    return sq_dist(P, M, idx) <= threshold(md, P.dtype)
-
-
-def rel(a, b):
-    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(1e-300, np.abs(np.asarray(b)).max()))
-
-
-def bits_equal(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def normals_for(orc, M):
-    M32 = np.asarray(M, dtype=np.float32)   # (the fp32 model's normals, cast: the oracle's kNN and normals follow the dtype they are given)
-    return orc.normals(M32, orc.knn4(M32))[0].astype(M.dtype)
-
-
-def run_to_end(bt, metric, max_iter=40, tol=1e-6, fixed=False):
-    bt.begin(max_iter=max_iter, tol=tol, fixed_iterations=fixed, metric=metric)
-    while bt.run(1 << 20)[1]:
-        pass
-    idx, moved, inl, linl = bt.loop_indices(), bt.get_moving(), bt.get_inliers(), bt.loop_inliers()
-    return [dict(st=bt.state(b), idx=idx[b], moved=moved[b], inl=inl[b], linl=linl[b]) for b in range(bt.count)]
-
-
-def same_pair_bytes(a, b, what=""):
-    for f in ("status", "iterations", "passes"):
-        assert a["st"][f] == b["st"][f], (what, f, a["st"][f], b["st"][f])
-    for f in ("T", "err"):
-        assert bits_equal(a["st"][f], b["st"][f]), (what, f)
-    for f in ("idx", "moved", "inl", "linl"):
-        assert bits_equal(a[f], b[f]), (what, f)
 
 
 # 1 ------------------------------------------------------------------------------------------------------------------------
@@ -102,7 +41,6 @@ def test_gate_every_pass_exactly(ctx, pkg, orc, dtype, plane):
     pairs = [(A, M) for A, M, _ in cases]
     nrm = [normals_for(orc, M) for _, M in pairs] if plane else None
     metric = pkg.ICP_POINT_TO_PLANE if plane else pkg.ICP_POINT_TO_POINT
-    ulp = np.finfo(np.float64).eps
     checked, worst = [0] * len(pairs), 0.0
     with ctx.batch(pairs) as bt:
         if plane:
@@ -123,18 +61,7 @@ def test_gate_every_pass_exactly(ctx, pkg, orc, dtype, plane):
                 what = f"pair {b} {CASES[b]} pass {k}"
                 mom = bt.diag_moments(b)
                 st = bt.state(b)
-                pv = prev[b]
-                if pv is not None:   # the transform front end: P_k from P_{k-1} and the host solve of pass k-1's vector
-                    R, t = (pkg.solve_point_to_plane(pv["mom"])[:2] if plane else pkg.solve_point_to_point(pv["mom"]))
-                    assert bits_equal(P, rm.apply_rt(pv["P"], R, t)), what
-                    want_err = rm.sq_error(P[pv["mask"]], M, pv["idx"][pv["mask"]])
-                    tol_err = rm.tolerance(np.full(rm.NMOM, want_err), n)[rm.ERR]
-                    assert abs(mom[rm.ERR] - want_err) <= tol_err, f"{what}: ERR {mom[rm.ERR]!r} exact {want_err!r} tol {tol_err:.3e}"
-                    e = np.sqrt(mom[rm.ERR]) / np.sqrt(float(pv["mask"].sum()))
-                    print(f"{what}: err[{k}] {st['err'][k]!r} from the vector {e!r}")
-                    assert abs(st["err"][k] - e) <= 4 * ulp * e, what
-                else:
-                    assert mom[rm.ERR] == 0.0, what
+                check_front_end(pkg, plane, P, M, mom, st["err"][k], prev[b], what)
                 if k == PASSES:   # the error-only pass matches nothing
                     checked[b] += 1
                     continue
@@ -143,16 +70,7 @@ def test_gate_every_pass_exactly(ctx, pkg, orc, dtype, plane):
                 assert inl[b].dtype == bool and np.array_equal(inl[b], mask), f"{what}: mask differs at {np.flatnonzero(inl[b] != mask)[:8]}"
                 print(f"{what}: kept {int(mask.sum())} of {n}")
                 assert mom[rm.CNT] == float(mask.sum()), f"{what}: CNT {mom[rm.CNT]!r}"
-                if mask.any():
-                    want, maj = (rm.plane(P[mask], M, nrm[b], idx[b][mask]) if plane else rm.p2p(P[mask], M, idx[b][mask]))
-                else:
-                    want, maj = np.zeros(rm.NMOM), np.zeros(rm.NMOM)
-                tol = rm.tolerance(maj, n)
-                for s in (rm.PLANE_SLOTS if plane else rm.P2P_SLOTS):
-                    dev = abs(mom[s] - want[s])
-                    assert dev <= tol[s], f"{what}: slot {s} device {mom[s]!r} exact {want[s]!r} |diff| {dev:.3e} tol {tol[s]:.3e}"
-                    if tol[s] > 0:
-                        worst = max(worst, dev / tol[s])
+                worst = max(worst, check_sums(plane, P, M, nrm[b] if plane else None, idx[b], mask, mom, what))
                 if not mask.any():
                     assert st["status"] == pkg.capi.ICP_ERR_EMPTY, what
                 prev[b] = dict(P=P, idx=idx[b], mask=mask, mom=mom)
@@ -165,39 +83,11 @@ def test_gate_every_pass_exactly(ctx, pkg, orc, dtype, plane):
 
 
 # 2 ------------------------------------------------------------------------------------------------------------------------
-def reference_loop(orc, A, M, md, max_iter, tol):
-    """orc.nn + the mask + ref_numpy.minimize on the kept points; the error over the kept points, divided by their count"""
-    P = A.copy()
-    E, T, i, kept, margin, mask = [0.0], np.eye(4), 0, [], np.inf, None
-    thr = float(threshold(md, A.dtype))
-    while True:
-        idx = orc.nn(P, M)
-        d = sq_dist(P, M, idx)
-        mask = d <= threshold(md, A.dtype)
-        margin = min(margin, float(np.abs(d.astype(np.float64) - thr).min() / thr))
-        kept.append(int(mask.sum()))
-        if not mask.any():
-            break
-        R, t = ref_numpy.minimize(P[mask], M, idx[mask])
-        P = (P.astype(np.float64) @ R.T + t).astype(A.dtype)
-        Tk = np.eye(4)
-        Tk[:3, :3], Tk[:3, 3] = R, t
-        T = Tk @ T
-        diff = M[idx][mask].astype(np.float64) - P[mask].astype(np.float64)
-        E.append(float(np.sqrt((diff ** 2).sum() / mask.sum())))
-        if E[-1] < tol or abs(E[-1] - E[-2]) < tol:
-            break
-        i += 1
-        if i > max_iter - 1:
-            break
-    return dict(iterations=i, err=np.array(E), T=T, kept=kept, mask=mask, margin=margin)
-
-
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 def test_gate_end_to_end(ctx, pkg, orc, dtype):
     tol = 1e-6
     cases = [gate_case(*c, dtype=dtype) for c in CASES[:3]]
-    wants = [reference_loop(orc, A, M, MD, 40, tol) for A, M, _ in cases]
+    wants = [reference_loop(orc, A, M, keep_within(MD), 40, tol) for A, M, _ in cases]
     for c, w, (A, M, is_out) in zip(CASES, wants, cases):   # the reference alone: the figures the module's docstring quotes
         print(f"{c}: reference keeps {w['kept']}, margin {w['margin']:.3e}, iterations {w['iterations']}")
         assert w["margin"] >= 1e-4
@@ -205,7 +95,7 @@ def test_gate_end_to_end(ctx, pkg, orc, dtype):
         assert k >= 3 and w["kept"][:k] == KEPT[c][:k] and set(w["kept"][k:]) <= {KEPT[c][-1]}
         assert w["kept"][0] < w["kept"][-1]     # the kept set changes between passes
         assert np.array_equal(w["mask"], ~is_out)
-        assert reference_loop(orc, A, M, MD_EMPTY, 40, tol)["kept"] == [0]
+        assert reference_loop(orc, A, M, keep_within(MD_EMPTY), 40, tol)["kept"] == [0]
     pairs = [(A, M) for A, M, _ in cases]
     with ctx.batch(pairs) as bt:   # the kept count of every pass
         bt.set_max_distance(MD)

@@ -19,36 +19,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import ref_moments as rm
-import ref_numpy
-from clouds import BATCH_N, case_pair, ragged_pair
+from batch_ref import (CASES, TOL_E, TOL_T, apply, bits_equal, compose, final, gate_case, hom, inv_rigid, keep_within, normals_for,
+                       reference_loop, rel, rot, run_to_end, same_pair_bytes, step_together, t0f)
+from clouds import BATCH_N, case_pair
 
 pytestmark = pytest.mark.gpu
 
-TOL_T = 1e-5
-TOL_E = 1e-5
 MD = 0.05          # the gate of the equivalence tests
 MD_FINE = 0.03     # keeps nothing at pass 0 from the far pose, exactly the non-outliers from T_good
-CASES = [(200, 300, 70), (130, 1000, 64), (1025, 513, 130), (63, 17, 5)]
 
 
 # ---- constructions -------------------------------------------------------------------------------------------------------------
-def rot(axis, a):
-    c, s = np.cos(a), np.sin(a)
-    return {"x": np.array([[1, 0, 0], [0, c, -s], [0, s, c]]), "y": np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]]),
-            "z": np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])}[axis]
-
-
-def hom(R, t):
-    T = np.eye(4)
-    T[:3, :3], T[:3, 3] = R, t
-    return T
-
-
-def inv_rigid(T):
-    return hom(T[:3, :3].T, -T[:3, :3].T @ T[:3, 3])
-
-
 G = hom(rot("z", np.deg2rad(40.0)), (3.0, -2.0, 1.0))
 RAGGED = hom(rot("z", 0.04) @ rot("y", -0.03) @ rot("x", 0.05), (0.02, -0.01, 0.03))   # m = R d + c (clouds.ragged_pair)
 PERTURB = hom(rot("z", 0.004) @ rot("y", -0.003) @ rot("x", 0.002), (0.003, -0.002, 0.0025))
@@ -56,113 +37,10 @@ T_BACK = inv_rigid(G)
 T_GOOD = PERTURB @ RAGGED @ inv_rigid(G)
 
 
-def gate_case(n, m, n_out, dtype=np.float32):
-    """(A, M, is_out): ragged_pair(n, m) with n_out far points as one run starting at point 64 (or behind a shorter cloud)"""
-    D, M = ragged_pair(n * 1000 + m, n, m)
-    O = (np.random.default_rng(n * 1000 + m + 7).standard_normal((n_out, 3)) * 0.5 + np.array([6.0, -5.0, 4.0])).astype(np.float32)
-    A = np.concatenate([D[:64], O, D[64:]])
-    is_out = np.zeros(n + n_out, dtype=bool)
-    is_out[min(64, n):min(64, n) + n_out] = True
-    return A.astype(dtype), M.astype(dtype), is_out
-
-
-def apply(P, T):
-    """the start cloud: ref_moments.apply_rt with the upper 3x4 of T (rounded there to P's precision, once)"""
-    T = np.asarray(T, dtype=np.float64)
-    return rm.apply_rt(P, T[:3, :3], T[:3, 3])
-
-
 def far_case(c, dtype):
     """(A_far, M, is_out): the gate case carried to the far pose"""
     A, M, is_out = gate_case(*c, dtype=dtype)
     return apply(A, G), M, is_out
-
-
-def t0f(T, dtype):
-    """T as the batch holds it: the 12 values rounded once to dtype, read back in double"""
-    out = np.eye(4)
-    out[:3, :] = np.asarray(T, dtype=np.float64)[:3, :].astype(dtype).astype(np.float64)
-    return out
-
-
-def compose(Tl, T0):
-    """T_loop . T0F in HostLoop::note_applied's order: s = 0; for k = 0..3: s += T_loop[a][k] * T0F[k][b], in Python floats"""
-    out = np.zeros((4, 4))
-    for a in range(4):
-        for b in range(4):
-            s = 0.0
-            for k in range(4):
-                s += float(Tl[a][k]) * float(T0[k][b])
-            out[a][b] = s
-    return out
-
-
-def sq_dist(P, M, idx):
-    """the winning squared distance as the matching holds it: (dx*dx + dy*dy) + dz*dz, every operation rounded in P's dtype"""
-    Gq = M[idx]
-    dx, dy, dz = P[:, 0] - Gq[:, 0], P[:, 1] - Gq[:, 1], P[:, 2] - Gq[:, 2]
-    d = (dx * dx + dy * dy) + dz * dz
-    assert d.dtype == P.dtype
-    return d
-
-
-def threshold(md, dtype):
-    return np.dtype(dtype).type(float(md) * float(md))
-
-
-def rel(a, b):
-    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(1e-300, np.abs(np.asarray(b)).max()))
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def normals_for(orc, M):
-    M32 = np.asarray(M, dtype=np.float32)
-    return orc.normals(M32, orc.knn4(M32))[0].astype(M.dtype)
-
-
-def run_to_end(bt, metric, max_iter=12, tol=1e-6):
-    bt.begin(max_iter=max_iter, tol=tol, metric=metric)
-    while bt.run(1 << 20)[1]:
-        pass
-    return final(bt)
-
-
-def final(bt):
-    idx, moved, inl, linl = bt.loop_indices(), bt.get_moving(), bt.get_inliers(), bt.loop_inliers()
-    return [dict(st=bt.state(b), idx=idx[b], moved=moved[b], inl=inl[b], linl=linl[b]) for b in range(bt.count)]
-
-
-def same_pair_bytes(a, b, what="", T0=None):
-    """every output of pair a is that of pair b, bit for bit; with T0, a's T is compose(b's T, T0)"""
-    for f in ("status", "iterations", "passes"):
-        assert a["st"][f] == b["st"][f], (what, f, a["st"][f], b["st"][f])
-    assert bits_equal(a["st"]["err"], b["st"]["err"]), (what, "err")
-    assert bits_equal(a["st"]["T"], b["st"]["T"] if T0 is None else compose(b["st"]["T"], T0)), (what, "T")
-    for f in ("idx", "moved", "inl", "linl"):
-        assert bits_equal(a[f], b[f]), (what, f)
-
-
-def step_together(X, Y, what):
-    """run(1) on both batches to the end; after every step the moment vectors, indices and masks of every pair that took part are
-    byte-equal.  Returns the kept count of every pass of every pair of Y."""
-    counts = [[] for _ in range(Y.count)]
-    while True:
-        running = ~Y.done()
-        assert np.array_equal(running, ~X.done()), what
-        kx, ky = X.run(1), Y.run(1)
-        assert kx == ky, (what, kx, ky)
-        if not ky[0]:
-            break
-        ix, iy, mx, my = X.get_indices(), Y.get_indices(), X.get_inliers(), Y.get_inliers()
-        for b in np.flatnonzero(running):
-            assert bits_equal(X.diag_moments(b), Y.diag_moments(b)), (what, b, "moments")
-            assert bits_equal(ix[b], iy[b]) and bits_equal(mx[b], my[b]), (what, b)
-            counts[b].append(int(my[b].sum()))
-    return counts
 
 
 # 1 ------------------------------------------------------------------------------------------------------------------------
@@ -233,7 +111,7 @@ def test_init_is_a_plain_batch_on_the_moved_clouds(ctx, pkg, orc, dtype, plane, 
         counts = step_together(X, Y, what)
         fx, fy = final(X), final(Y)
         for b in range(len(far)):
-            same_pair_bytes(fx[b], fy[b], f"{what} pair {b}", T0=t0f(T_BACK, dtype))
+            same_pair_bytes(fx[b], fy[b], f"{what} pair {b}", T=compose(fy[b]["st"]["T"], t0f(T_BACK, dtype)))
             assert not bits_equal(fx[b]["st"]["T"], fy[b]["st"]["T"])
         print(f"[init equivalence] {what}: passes {[f['st']['passes'] for f in fy]}, kept per pass {counts}")
         if gated and not plane:   # on the plain batch alone: the gate is at work, the kept set changes from pass to pass
@@ -243,44 +121,17 @@ def test_init_is_a_plain_batch_on_the_moved_clouds(ctx, pkg, orc, dtype, plane, 
 
 
 # 3 ------------------------------------------------------------------------------------------------------------------------
-def reference_loop(orc, A, M, md, max_iter, tol):
-    """orc.nn + the mask + ref_numpy.minimize on the kept points; the error over the kept points, divided by their count"""
-    P = A.copy()
-    E, T, i, kept, masks, margin = [0.0], np.eye(4), 0, [], [], np.inf
-    thr = float(threshold(md, A.dtype))
-    while True:
-        idx = orc.nn(P, M)
-        d = sq_dist(P, M, idx)
-        mask = d <= threshold(md, A.dtype)
-        margin = min(margin, float(np.abs(d.astype(np.float64) - thr).min() / thr))
-        kept.append(int(mask.sum()))
-        masks.append(mask)
-        if not mask.any():
-            break
-        R, t = ref_numpy.minimize(P[mask], M, idx[mask])
-        P = (P.astype(np.float64) @ R.T + t).astype(A.dtype)
-        T = hom(R, t) @ T
-        diff = M[idx][mask].astype(np.float64) - P[mask].astype(np.float64)
-        E.append(float(np.sqrt((diff ** 2).sum() / mask.sum())))
-        if E[-1] < tol or abs(E[-1] - E[-2]) < tol:
-            break
-        i += 1
-        if i > max_iter - 1:
-            break
-    return dict(iterations=i, err=np.array(E), T=T, kept=kept, masks=masks, margin=margin)
-
-
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 def test_init_end_to_end_from_the_far_pose(ctx, pkg, orc, dtype):
     tol = 1e-6
     cases = [far_case(c, dtype) for c in CASES]
     wants = []
     for c, (A, M, is_out) in zip(CASES, cases):   # the reference alone, before the device is looked at
-        w = reference_loop(orc, apply(A, T_GOOD), M, MD_FINE, 40, tol)
+        w = reference_loop(orc, apply(A, T_GOOD), M, keep_within(MD_FINE), 40, tol)
         print(f"{c}: reference keeps {w['kept']}, margin {w['margin']:.3e}, iterations {w['iterations']}, err {w['err']}")
         assert all(np.array_equal(m, ~is_out) for m in w["masks"]), c   # exactly the non-outliers, in every pass
         assert w["margin"] >= 1e-3, (c, w["margin"])
-        assert reference_loop(orc, A, M, MD_FINE, 40, tol)["kept"] == [0], c   # without the initial transform: nothing
+        assert reference_loop(orc, A, M, keep_within(MD_FINE), 40, tol)["kept"] == [0], c   # without the initial transform: nothing
         wants.append(w)
     pairs = [(A, M) for A, M, _ in cases]
     with ctx.batch(pairs) as bt:   # the kept count of every pass
@@ -326,7 +177,7 @@ def test_init_pairs_are_independent(ctx, pkg, dtype):
         with ctx.batch([pairs[i] for i in sel]) as bt:
             bt.set_max_distance(MD)
             bt.set_initial_transforms(Ts[sel])
-            return run_to_end(bt, pkg.ICP_POINT_TO_POINT)
+            return run_to_end(bt, pkg.ICP_POINT_TO_POINT, max_iter=12)
 
     fwd, rev = run([0, 1, 2]), run([2, 1, 0])[::-1]
     for i in range(3):
@@ -347,9 +198,9 @@ def test_init_state_and_refusals(ctx, pkg):
     T_b = np.array([T_GOOD, T_BACK, hom(rot("x", 0.3), (1.0, 2.0, 3.0))])
     P2P = pkg.ICP_POINT_TO_POINT
     with ctx.batch(pairs) as bt:
-        fresh = run_to_end(bt, P2P)
+        fresh = run_to_end(bt, P2P, max_iter=12)
         bt.set_initial_transforms(T_a)
-        want = run_to_end(bt, P2P)
+        want = run_to_end(bt, P2P, max_iter=12)
         assert not bits_equal(want[0]["moved"], fresh[0]["moved"])
         bads = []
         # a NaN, an inf, bottom rows 0 0 0 2 and 1e-30 0 0 1 (and 0 0 -1 1, 0 0 0 NaN), a double that is infinite as a float
@@ -368,7 +219,7 @@ def test_init_state_and_refusals(ctx, pkg):
         assert lib.icp_batch_set_initial_transforms(bt._h, first.ctypes.data_as(pd)) == pkg.capi.ICP_ERR_INVALID
         assert "pair 1" in lib.icp_last_error().decode()
         assert bt.run(1) == (0, 0)   # a refused call leaves the batch alone: its loop is still the finished one
-        got = run_to_end(bt, P2P)    # ... and the transforms are those set before
+        got = run_to_end(bt, P2P, max_iter=12)    # ... and the transforms are those set before
         for b in range(3):
             same_pair_bytes(want[b], got[b], f"after the refusals, pair {b}")
         # a set during a loop discards it
@@ -381,7 +232,7 @@ def test_init_state_and_refusals(ctx, pkg):
                     bt.run(1)
                 assert e.value.code == pkg.capi.ICP_ERR_STATE
         # transforms do not compound: T_a, begin, run; T_b, begin -- the start cloud is apply(A, T_b)
-        run_to_end(bt, P2P)
+        run_to_end(bt, P2P, max_iter=12)
         bt.set_initial_transforms(T_b)
         for _ in range(2):   # (nor over repeated begins)
             bt.begin(max_iter=12)
@@ -391,13 +242,13 @@ def test_init_state_and_refusals(ctx, pkg):
             bt.run(2)
         # NULL restores the bytes of a fresh batch
         bt.set_initial_transforms(None)
-        again = run_to_end(bt, P2P)
+        again = run_to_end(bt, P2P, max_iter=12)
         for b in range(3):
             same_pair_bytes(fresh[b], again[b], f"None, pair {b}")
     with ctx.batch(pairs[:1]) as bt:   # a batch that never held transforms keeps none after a refused call
         with pytest.raises(pkg.IcpError):
             bt.set_initial_transforms(np.full((4, 4), np.nan))
-        same_pair_bytes(fresh[0], run_to_end(bt, P2P)[0], "refused on a fresh batch")
+        same_pair_bytes(fresh[0], run_to_end(bt, P2P, max_iter=12)[0], "refused on a fresh batch")
 
 
 # 6 ------------------------------------------------------------------------------------------------------------------------
@@ -428,7 +279,7 @@ def test_init_overflow_ends_that_pair_only(ctx, pkg, dtype):
     with ctx.batch([pairs[0], pairs[2]]) as bt:
         bt.set_max_distance(MD)
         bt.set_initial_transforms(Ts[[0, 2]])
-        want = run_to_end(bt, pkg.ICP_POINT_TO_POINT)
+        want = run_to_end(bt, pkg.ICP_POINT_TO_POINT, max_iter=12)
     same_pair_bytes(got[0], want[0], "pair 0 beside the overflowing pair")
     same_pair_bytes(got[2], want[1], "pair 2 beside the overflowing pair")
     assert want[0]["st"]["status"] == pkg.capi.ICP_OK and want[0]["st"]["passes"] >= 1
@@ -455,7 +306,7 @@ def test_init_coarse_to_fine_on_one_batch(ctx, pkg, dtype):
         bt.set_max_distance(MD_FINE)
         plain = run_to_end(bt, pkg.ICP_POINT_TO_POINT, max_iter=40)
     for b, (_, _, is_out) in enumerate(cases):
-        same_pair_bytes(fine[b], plain[b], f"pair {b}", T0=t0f(T1[b], dtype))
+        same_pair_bytes(fine[b], plain[b], f"pair {b}", T=compose(plain[b]["st"]["T"], t0f(T1[b], dtype)))
         assert fine[b]["st"]["status"] == pkg.capi.ICP_OK
         if b < 3:
             assert np.array_equal(fine[b]["linl"], ~is_out) and np.array_equal(fine[b]["inl"], ~is_out), b

@@ -8,51 +8,15 @@ counts where the oracle's own stop decisions sit far from the threshold), every 
 (ref_moments.py) at the derived bound, and with bits that do not depend on the other pairs of the batch.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import clouds as cl
 import ref_moments as rm
-from test_gpu_batch import fp32_pairs, same_bits   # (the point-to-point batch's pairs and its byte comparison)
+from batch_ref import TOL_E, TOL_T, degenerate_pair, five_pairs, fp32_pairs, knn_models, oracle_normals, rel, same_result_bits
 
 pytestmark = pytest.mark.gpu
-
-TOL_T = 1e-5
-TOL_E = 1e-5
-_NORMALS = {}     # oracle normals are computed once per model
-
-
-def rel(a, b):
-    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(1e-300, np.abs(np.asarray(b)).max()))
-
-
-def oracle_normals(orc, M):
-    M = np.ascontiguousarray(M, dtype=np.float32)
-    key = (M.shape[0], M.tobytes())
-    if key not in _NORMALS:
-        _NORMALS[key] = orc.normals(M, orc.knn4(M))[0]
-    return _NORMALS[key]
-
-
-def five_pairs(pkg, golden):
-    """test 3's batch: four synthetic grids and Bunny_res; the oracle stops them after 2, 3, 3, 1 and 5 iterations"""
-    ds = pkg.datasets
-    grid = lambda W: ds.synthetic_grid(W, np.float32)
-    B = np.fromfile(os.path.join(golden, "bunny_res_xyz_f32.bin"), dtype=np.float32).reshape(-1, 3)
-    G20 = grid(20)
-    return [(grid(12), ds.make_model_gpu(grid(12), *ds.P2P_GPU)), (grid(24), ds.make_model_gpu(grid(24), *ds.P2P_GPU)),
-            (grid(40), ds.make_model_gpu(grid(40), *ds.P2P_GPU)), (G20, ds.make_model_gpu(G20, (0.05, 0.02, -0.04), (0.05, -0.02, 0.01))),
-            (B, ds.make_model_gpu(B, *ds.BUNNY))]
-
-
-def degenerate_pair():
-    """an 8 x 8 planar grid registered on itself with parallel normals (test_point_to_plane_degenerate_is_reported): the third
-    pivot of the 6 x 6 system is an exact zero"""
-    g = np.stack(np.meshgrid(np.arange(8.0), np.arange(8.0), indexing="ij"), -1).reshape(-1, 2)
-    P = np.concatenate([g, np.zeros((64, 1))], 1).astype(np.float32)
-    return (P, P.copy()), np.tile(np.array([[0, 0, 1]], dtype=np.float32), (64, 1))
 
 
 def handle_results(bt, pkg, **begin):
@@ -69,30 +33,7 @@ def handle_results(bt, pkg, **begin):
     return out
 
 
-# 1 ------------------------------------------------------------------------------------------------------------------------
-# model sizes around the kernel's granules: a work item of 64 query points; four quarters of wseg = ceil(ceil(m / 4) / 8) * 8 model
-# points, cut in whole chunks of 8 (m = 5, 6: all points in the first quarter, three quarters empty; 32: four quarters of 8; 33:
-# quarters of 16, 16, 1 and 0; 63 .. 65: the last quarter short or one point over an item); a sub-tile of 512 (fp32) or 256
-# (fp64) model points per wave (2048 / 2049 and 1024 / 1025: one tile per quarter / a second one)
-KNN_M = (5, 6, 32, 33, 63, 64, 65, 130, 257, 1000, 1024, 1025, 2048, 2049, 4097)
-
-
-def knn_models(dtype, sizes=KNN_M):
-    models = [cl.ragged_pair(s, 1, m)[1] for s, m in enumerate(sizes)]
-    Z = np.random.default_rng(5).standard_normal((300, 3)).astype(np.float32)
-    Z[100:140] = 0.0   # 40 coincident points: the order among equal distances
-    models.append(Z)
-    if np.dtype(dtype) == np.float64:   # mantissas that fp32 cannot hold (clouds.case_pair); the coincident points stay coincident
-        out = []
-        for k, M in enumerate(models):
-            M64 = M.astype(np.float64) + 1e-9 * np.random.default_rng(1000 + k).standard_normal(M.shape)
-            if k == len(models) - 1:
-                M64[100:140] = 0.0
-            out.append(M64)
-        models = out
-    return models
-
-
+# 1 (model sizes around the kernels' granules: batch_ref.KNN_M) -------------------------------------------------------------
 def check_normals_against_single(ctx, models, got_nrm, got_nbr, orc=None):
     for k, M in enumerate(models):
         ctx.set_model(M)
@@ -152,7 +93,7 @@ def test_batch_plane_refusals(ctx, pkg, orc):
         want = ctx.point_to_plane_batch(pairs, normals=good, max_iter=6, tol=0.0, fixed_iterations=True)
         got = handle_results(bt, pkg, max_iter=6, tol=0.0, fixed_iterations=True, metric=PLANE)   # the earlier set is still in force
         for a, b in zip(got, want):
-            same_bits(a, b)
+            same_result_bits(a, b)
         # new normals in the middle of a loop discard it
         bt.begin(max_iter=6, tol=0.0, fixed_iterations=True, metric=PLANE)
         assert bt.run(2) == (2, 2)
@@ -211,7 +152,7 @@ def test_batch_plane_device_estimated_normals(ctx, pkg, five):
     a = ctx.point_to_plane_batch(pairs, normals=None, max_iter=50, tol=1e-5)
     b = ctx.point_to_plane_batch(pairs, normals=est, max_iter=50, tol=1e-5)
     for x, y, r in zip(a, b, res):
-        same_bits(x, y)
+        same_result_bits(x, y)
         assert x.extra["status"] == pkg.capi.ICP_OK
         assert rel(x.T, r.T) < 5e-3   # (test_point_to_plane_loop's gate: the sign of a normal does not matter)
 
@@ -308,21 +249,21 @@ def test_batch_plane_pair_bits_do_not_depend_on_neighbours(ctx, pkg, orc):
     first = ctx.point_to_plane_batch([X] + others, normals=[nX] + nO, **kw)[0]
     sixth = ctx.point_to_plane_batch(others[:5] + [X] + others[5:], normals=nO[:5] + [nX] + nO[5:], **kw)[5]
     assert alone.extra["status"] == pkg.capi.ICP_OK and alone.passes >= 3
-    same_bits(alone, first)
-    same_bits(alone, sixth)
+    same_result_bits(alone, first)
+    same_result_bits(alone, sixth)
 
 
 def test_batch_plane_is_deterministic(ctx, pkg, five):
     pairs, normals, _, res = five
     again = ctx.point_to_plane_batch(pairs, normals=normals, max_iter=50, tol=1e-5)
     for x, y in zip(res, again):
-        same_bits(x, y)
+        same_result_bits(x, y)
     with ctx.batch(pairs) as bt:   # begin starts again from the uploaded clouds
         bt.set_model_normals(normals)
         for _ in range(2):
             got = handle_results(bt, pkg, max_iter=50, tol=1e-5, metric=pkg.capi.ICP_POINT_TO_PLANE)
             for x, y in zip(res, got):
-                same_bits(x, y)
+                same_result_bits(x, y)
 
 
 # 8 ------------------------------------------------------------------------------------------------------------------------
@@ -332,7 +273,7 @@ def test_batch_plane_degenerate_pair_ends_alone(ctx, pkg, five):
     got = ctx.point_to_plane_batch(pairs[:2] + [bad] + pairs[2:], normals=normals[:2] + [bad_n] + normals[2:], max_iter=50, tol=1e-5)
     assert got[2].extra["status"] == pkg.capi.ICP_ERR_SINGULAR and got[2].passes == 0
     for x, y in zip(res, got[:2] + got[3:]):
-        same_bits(x, y)
+        same_result_bits(x, y)
 
 
 # 9 ------------------------------------------------------------------------------------------------------------------------
@@ -371,5 +312,5 @@ def test_batch_point_to_point_is_untouched_by_normals(ctx, pkg, orc, golden):
         estimated = handle_results(bt, pkg, max_iter=40, tol=1e-6)
     for a, b, c in zip(plain, held, estimated):
         assert a.passes > 1
-        same_bits(a, b)
-        same_bits(a, c)
+        same_result_bits(a, b)
+        same_result_bits(a, c)

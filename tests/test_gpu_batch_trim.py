@@ -12,7 +12,7 @@ pair's n distances, K = ceil(rho n): the deferred route -- matching without a de
     5  bits: untrimmed means untrimmed, an untrimmed pair in a batch that trims, independence of the other pairs, refusals, state,
        initial transforms
 
-The clouds of 3 - 5 are those of test_gpu_batch_gate.py (gate_case and sq_dist are copied from there).  Keeping the closest half a
+The clouds of 3 - 5 are those of test_gpu_batch_gate.py (batch_ref.gate_case).  Keeping the closest half a
 numpy restatement of the loop keeps 135, 97, 578 and 34 points in every pass, ends with no outlier kept and an RMS of about
 1.2e-3 in 5, 4, 5, 4 iterations; the relative gap between the K-th and the (K+1)-th smallest d never falls below 1e-4, so a
 flipped mask is never rounding -- every such condition is asserted on the reference alone before the device is consulted.
@@ -20,113 +20,24 @@ flipped mask is never rounding -- every such condition is asserted on the refere
 Bounds: tau, every mask, index and moved cloud bit for bit; the sums at ref_moments.tolerance (derived there); T and err of the
 end-to-end run at the project's 1e-5 (test_gpu_batch.py)."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
 import ref_moments as rm
-import ref_numpy
-from clouds import ragged_pair
+from batch_ref import (CASES, TOL_E, TOL_T, bits_equal, check_front_end, check_sums, compose, final, gate_case, gate_margin, hom,
+                       keep_closest, kth_gap, normals_for, rank, reference_loop, rel, rho_for, rot, run_to_end, same_pair_bytes, sq_dist,
+                       tau_bits_equal, tau_ref, threshold)
 
 pytestmark = pytest.mark.gpu
 
-TOL_T = 1e-5
-TOL_E = 1e-5
 MD = 0.05
 RHO = 0.5
-CASES = [(200, 300, 70), (130, 1000, 64), (1025, 513, 130), (63, 17, 5)]
 KEPT_TRIM = [135, 97, 578, 34]          # ceil(0.5 n), no ties at the K-th
 KEPT_GATE_PASS0 = [29, 16, 121, 7]      # the gate decides at pass 0 ...
 KEPT_GATE_LATER = [135, 97, 578, 7]     # ... the trim from pass 1 on (point-to-point, a numpy loop)
 PASSES = 4
 SELECT_N = [1, 63, 64, 65, 255, 256, 257, 1025, 4097, 65536]
-
-
-# ---- helpers (gate_case, sq_dist: copies of test_gpu_batch_gate.py's) ------------------------------------------------------
-def gate_case(n, m, n_out, dtype=np.float32):
-    """(A, M, is_out): ragged_pair(n, m) with n_out far points as one run starting at point 64 (or behind a shorter cloud)"""
-    D, M = ragged_pair(n * 1000 + m, n, m)
-    O = (np.random.default_rng(n * 1000 + m + 7).standard_normal((n_out, 3)) * 0.5 + np.array([6.0, -5.0, 4.0])).astype(np.float32)
-    A = np.concatenate([D[:64], O, D[64:]])
-    is_out = np.zeros(n + n_out, dtype=bool)
-    is_out[min(64, n):min(64, n) + n_out] = True
-    return A.astype(dtype), M.astype(dtype), is_out
-
-
-def sq_dist(P, M, idx):
-    """the winning squared distance as the matching holds it: (dx*dx + dy*dy) + dz*dz, every operation rounded in P's dtype"""
-    G = M[idx]
-    dx, dy, dz = P[:, 0] - G[:, 0], P[:, 1] - G[:, 1], P[:, 2] - G[:, 2]
-    d = (dx * dx + dy * dy) + dz * dz
-    assert d.dtype == P.dtype
-    return d
-
-
-def threshold(md, dtype):
-    return np.dtype(dtype).type(float(md) * float(md))
-
-
-def rank(rho, n):
-    """K = ceil(rho * (double)n), clamped to [1, n]"""
-    return min(max(int(math.ceil(float(rho) * float(n))), 1), n)
-
-
-def rho_for(K, n):
-    """a share that gives rank K: (K - 0.5) / n, or 1 - 1e-9 for K = n (1.0 itself would mean: not trimmed)"""
-    r = 1.0 - 1e-9 if K == n else (K - 0.5) / n
-    assert rank(r, n) == K and r < 1.0
-    return r
-
-
-def tau_ref(d, K):
-    return np.partition(d, K - 1)[K - 1]
-
-
-def kth_gap(d, K):
-    """relative gap between the K-th and the (K+1)-th smallest d (inf where K = n)"""
-    s = np.sort(d.astype(np.float64))
-    return np.inf if K >= s.size else float((s[K] - s[K - 1]) / s[K])
-
-
-def same_bits(dev_tau, want):
-    """the device's tau, read back in double, is the value `want` of the batch's dtype bit for bit"""
-    return np.float64(dev_tau).tobytes() == np.float64(want).tobytes()
-
-
-def rel(a, b):
-    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(1e-300, np.abs(np.asarray(b)).max()))
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def normals_for(orc, M):
-    M32 = np.asarray(M, dtype=np.float32)
-    return orc.normals(M32, orc.knn4(M32))[0].astype(M.dtype)
-
-
-def final(bt):
-    idx, moved, inl, linl = bt.loop_indices(), bt.get_moving(), bt.get_inliers(), bt.loop_inliers()
-    return [dict(st=bt.state(b), idx=idx[b], moved=moved[b], inl=inl[b], linl=linl[b]) for b in range(bt.count)]
-
-
-def run_to_end(bt, metric, max_iter=12, tol=1e-6):
-    bt.begin(max_iter=max_iter, tol=tol, metric=metric)
-    while bt.run(1 << 20)[1]:
-        pass
-    return final(bt)
-
-
-def same_pair_bytes(a, b, what="", T=None):
-    for f in ("status", "iterations", "passes"):
-        assert a["st"][f] == b["st"][f], (what, f, a["st"][f], b["st"][f])
-    assert bits_equal(a["st"]["err"], b["st"]["err"]), (what, "err")
-    assert bits_equal(a["st"]["T"], b["st"]["T"] if T is None else T), (what, "T")
-    for f in ("idx", "moved", "inl", "linl"):
-        assert bits_equal(a[f], b[f]), (what, f)
 
 
 # 1 ------------------------------------------------------------------------------------------------------------------------
@@ -183,7 +94,7 @@ def test_trim_selection_every_digit_and_granule(ctx, pkg, orc, dtype):
                 tau, k = bt.diag_trim(b)
                 want = tau_ref(d[b], K)
                 assert k == K, (what, k)
-                assert same_bits(tau, want), f"{what}: tau {tau!r}, reference {float(want)!r}"
+                assert tau_bits_equal(tau, want), f"{what}: tau {tau!r}, reference {float(want)!r}"
                 mask = d[b] <= want
                 assert mask.sum() >= K
                 assert np.array_equal(inl[b], mask), f"{what}: mask differs at {np.flatnonzero(inl[b] != mask)[:8]}"
@@ -208,7 +119,7 @@ def test_trim_keeps_every_point_tied_with_the_kth(ctx, pkg, orc, dtype):
         bt.begin(max_iter=2, tol=0.0, fixed_iterations=True)
         assert bt.run(1)[0] == 1
         tau, k = bt.diag_trim(0)
-        assert k == 60 and same_bits(tau, dtype(1.0))
+        assert k == 60 and tau_bits_equal(tau, dtype(1.0))
         assert np.array_equal(bt.get_indices()[0], idx)
         assert np.array_equal(bt.get_inliers()[0], d <= 1.0)
         assert bt.diag_moments(0)[rm.CNT] == 102.0
@@ -226,7 +137,6 @@ def test_trim_every_pass_exactly(ctx, pkg, orc, dtype, plane, gated):
     Ks = [rank(RHO, A.shape[0]) for A, _ in pairs]
     assert Ks == KEPT_TRIM
     thr = threshold(MD, dtype)
-    ulp = np.finfo(np.float64).eps
     checked, worst, kept_log = [0] * len(pairs), 0.0, [[] for _ in pairs]
     with ctx.batch(pairs) as bt:
         if plane:
@@ -249,17 +159,7 @@ def test_trim_every_pass_exactly(ctx, pkg, orc, dtype, plane, gated):
                 what = f"pair {b} {CASES[b]} pass {k}"
                 mom = bt.diag_moments(b)
                 st = bt.state(b)
-                pv = prev[b]
-                if pv is not None:   # the transform front end: P_k from P_{k-1} and the host solve of pass k-1's vector
-                    R, t = (pkg.solve_point_to_plane(pv["mom"])[:2] if plane else pkg.solve_point_to_point(pv["mom"]))
-                    assert bits_equal(P, rm.apply_rt(pv["P"], R, t)), what
-                    want_err = rm.sq_error(P[pv["mask"]], M, pv["idx"][pv["mask"]])
-                    tol_err = rm.tolerance(np.full(rm.NMOM, want_err), n)[rm.ERR]
-                    assert abs(mom[rm.ERR] - want_err) <= tol_err, f"{what}: ERR {mom[rm.ERR]!r} exact {want_err!r} tol {tol_err:.3e}"
-                    e = np.sqrt(mom[rm.ERR]) / np.sqrt(float(pv["mask"].sum()))
-                    assert abs(st["err"][k] - e) <= 4 * ulp * e, what
-                else:
-                    assert mom[rm.ERR] == 0.0, what
+                check_front_end(pkg, plane, P, M, mom, st["err"][k], prev[b], what)
                 if k == PASSES:   # the error-only pass matches nothing
                     checked[b] += 1
                     continue
@@ -269,7 +169,7 @@ def test_trim_every_pass_exactly(ctx, pkg, orc, dtype, plane, gated):
                 gap = kth_gap(d, Ks[b])
                 assert gap >= 1e-4, f"{what}: relative gap at the K-th distance {gap:.3e}"
                 if gated:
-                    margin = float(np.abs(d.astype(np.float64) - float(thr)).min() / float(thr))
+                    margin = gate_margin(d, MD)
                     assert margin >= 1e-4, f"{what}: a distance within {margin:.3e} of the gate"
                 tau_want = tau_ref(d, Ks[b])
                 mask = (d <= tau_want) & ((d <= thr) if gated else True)
@@ -285,16 +185,10 @@ def test_trim_every_pass_exactly(ctx, pkg, orc, dtype, plane, gated):
                 # the device
                 assert np.array_equal(idx[b], want_idx), what
                 tau, kk = bt.diag_trim(b)
-                assert kk == Ks[b] and same_bits(tau, tau_want), f"{what}: tau {tau!r}, reference {float(tau_want)!r}"
+                assert kk == Ks[b] and tau_bits_equal(tau, tau_want), f"{what}: tau {tau!r}, reference {float(tau_want)!r}"
                 assert inl[b].dtype == bool and np.array_equal(inl[b], mask), f"{what}: mask differs at {np.flatnonzero(inl[b] != mask)[:8]}"
                 assert mom[rm.CNT] == float(mask.sum()), f"{what}: CNT {mom[rm.CNT]!r}"
-                want, maj = (rm.plane(P[mask], M, nrm[b], want_idx[mask]) if plane else rm.p2p(P[mask], M, want_idx[mask]))
-                tol = rm.tolerance(maj, n)
-                for s in (rm.PLANE_SLOTS if plane else rm.P2P_SLOTS):
-                    dev = abs(mom[s] - want[s])
-                    assert dev <= tol[s], f"{what}: slot {s} device {mom[s]!r} exact {want[s]!r} |diff| {dev:.3e} tol {tol[s]:.3e}"
-                    if tol[s] > 0:
-                        worst = max(worst, dev / tol[s])
+                worst = max(worst, check_sums(plane, P, M, nrm[b] if plane else None, want_idx, mask, mom, what))
                 prev[b] = dict(P=P, idx=want_idx, mask=mask, mom=mom)
                 checked[b] += 1
         assert bt.done().all()
@@ -306,40 +200,14 @@ def test_trim_every_pass_exactly(ctx, pkg, orc, dtype, plane, gated):
 
 
 # 4 ------------------------------------------------------------------------------------------------------------------------
-def reference_loop(orc, A, M, rho, max_iter, tol):
-    """orc.nn + the trim mask + ref_numpy.minimize on the kept points; the error over the kept points, divided by their count"""
-    P = A.copy()
-    K = rank(rho, A.shape[0])
-    E, T, i, kept, gap, mask = [0.0], np.eye(4), 0, [], np.inf, None
-    while True:
-        idx = orc.nn(P, M)
-        d = sq_dist(P, M, idx)
-        mask = d <= tau_ref(d, K)
-        gap = min(gap, kth_gap(d, K))
-        kept.append(int(mask.sum()))
-        R, t = ref_numpy.minimize(P[mask], M, idx[mask])
-        P = (P.astype(np.float64) @ R.T + t).astype(A.dtype)
-        Tk = np.eye(4)
-        Tk[:3, :3], Tk[:3, 3] = R, t
-        T = Tk @ T
-        diff = M[idx][mask].astype(np.float64) - P[mask].astype(np.float64)
-        E.append(float(np.sqrt((diff ** 2).sum() / mask.sum())))
-        if E[-1] < tol or abs(E[-1] - E[-2]) < tol:
-            break
-        i += 1
-        if i > max_iter - 1:
-            break
-    return dict(iterations=i, err=np.array(E), T=T, kept=kept, mask=mask, gap=gap)
-
-
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 def test_trim_end_to_end(ctx, pkg, orc, dtype):
     tol = 1e-6
     cases = [gate_case(*c, dtype=dtype) for c in CASES]
-    wants = [reference_loop(orc, A, M, RHO, 40, tol) for A, M, _ in cases]
+    wants = [reference_loop(orc, A, M, keep_closest(RHO), 40, tol) for A, M, _ in cases]
     for c, w, (A, M, is_out), K in zip(CASES, wants, cases, KEPT_TRIM):   # the reference alone
-        print(f"{c}: reference keeps {w['kept']}, smallest K-th gap {w['gap']:.3e}, iterations {w['iterations']}, final RMS {w['err'][-1]:.3e}")
-        assert w["gap"] >= 1e-4
+        print(f"{c}: reference keeps {w['kept']}, smallest K-th gap {w['margin']:.3e}, iterations {w['iterations']}, final RMS {w['err'][-1]:.3e}")
+        assert w["margin"] >= 1e-4
         assert set(w["kept"]) == {K}
         assert not (w["mask"] & is_out).any()
         assert w["err"][-1] < 2e-3
@@ -371,14 +239,14 @@ def test_trim_off_means_off(ctx, pkg, orc, dtype, plane):
     with ctx.batch(pairs) as bt:
         if plane:
             bt.set_model_normals(nrm)
-        plain = run_to_end(bt, metric)
+        plain = run_to_end(bt, metric, max_iter=12)
         bt.set_trim(1.0)
-        ones = run_to_end(bt, metric)
+        ones = run_to_end(bt, metric, max_iter=12)
         taus = [bt.diag_trim(b) for b in range(bt.count)]
         bt.set_trim(RHO)
-        half = run_to_end(bt, metric)
+        half = run_to_end(bt, metric, max_iter=12)
         bt.set_trim(None)
-        again = run_to_end(bt, metric)
+        again = run_to_end(bt, metric, max_iter=12)
     for b in range(len(pairs)):
         same_pair_bytes(plain[b], ones[b], f"1.0, pair {b}")
         same_pair_bytes(plain[b], again[b], f"None after a trimmed run, pair {b}")
@@ -442,7 +310,7 @@ def test_trim_pairs_are_independent(ctx, pkg, orc, dtype, plane):
                 bt.set_model_normals([nrm[i] for i in sel])
             bt.set_max_distance(md[sel])
             bt.set_trim(rho[sel])
-            return run_to_end(bt, metric)
+            return run_to_end(bt, metric, max_iter=12)
 
     everything = list(range(len(pairs)))
     fwd, rev = run(everything), run(everything[::-1])[::-1]
@@ -475,7 +343,7 @@ def test_trim_refusals_and_state(ctx, pkg, orc):
         bt.begin(max_iter=12)
         assert lib.icp_diag_batch_trim(bt._h, 0, C.byref(tau), C.byref(k)) == pkg.capi.ICP_ERR_STATE   # no matching pass yet
         assert lib.icp_diag_batch_trim(bt._h, 3, C.byref(tau), C.byref(k)) == pkg.capi.ICP_ERR_INVALID
-        want = run_to_end(bt, P2P)
+        want = run_to_end(bt, P2P, max_iter=12)
         assert [bt.diag_trim(b)[1] for b in range(3)] == [135, 194, rank(0.7, 1155)]
         for bad in (np.nan, 0.0, -0.5, 1.0 + 1e-12, np.inf, -np.inf):
             v = np.array([0.9, 0.9, bad])
@@ -488,7 +356,7 @@ def test_trim_refusals_and_state(ctx, pkg, orc):
         assert lib.icp_batch_set_trim(bt._h, first.ctypes.data_as(pd)) == pkg.capi.ICP_ERR_INVALID
         assert "pair 1" in lib.icp_last_error().decode()
         assert bt.run(1) == (0, 0)   # a refused call leaves the batch alone: its loop is still the finished one
-        got = run_to_end(bt, P2P)    # ... and the shares are those set before
+        got = run_to_end(bt, P2P, max_iter=12)    # ... and the shares are those set before
         for b in range(3):
             same_pair_bytes(want[b], got[b], f"pair {b}")
         assert not got[0]["linl"].all() and got[1]["linl"].all() and not got[2]["linl"].all()
@@ -508,35 +376,11 @@ def test_trim_refusals_and_state(ctx, pkg, orc):
         with pytest.raises(ValueError):
             bt.set_trim([RHO, RHO])
     with ctx.batch(pairs[:1]) as bt:   # a batch that never held shares keeps none after a refused call
-        plain = run_to_end(bt, P2P)
+        plain = run_to_end(bt, P2P, max_iter=12)
         with pytest.raises(pkg.IcpError) as e:
             bt.set_trim(1.5)
         assert e.value.code == pkg.capi.ICP_ERR_INVALID
-        same_pair_bytes(plain[0], run_to_end(bt, P2P)[0])
-
-
-def rot(axis, a):
-    c, s = np.cos(a), np.sin(a)
-    return {"x": np.array([[1, 0, 0], [0, c, -s], [0, s, c]]), "y": np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]]),
-            "z": np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])}[axis]
-
-
-def hom(R, t):
-    T = np.eye(4)
-    T[:3, :3], T[:3, 3] = R, t
-    return T
-
-
-def compose(Tl, T0):
-    """T_loop . T0F in HostLoop::note_applied's order: s = 0; for k = 0..3: s += T_loop[a][k] * T0F[k][b], in Python floats"""
-    out = np.zeros((4, 4))
-    for a in range(4):
-        for b in range(4):
-            s = 0.0
-            for k in range(4):
-                s += float(Tl[a][k]) * float(T0[k][b])
-            out[a][b] = s
-    return out
+        same_pair_bytes(plain[0], run_to_end(bt, P2P, max_iter=12)[0])
 
 
 @pytest.mark.parametrize("gated", [False, True], ids=["no gate", "gate"])
@@ -557,7 +401,7 @@ def test_trim_with_initial_transforms(ctx, pkg, orc, dtype, gated):
             if gated:
                 bt.set_max_distance(MD)
             bt.set_trim(RHO)
-        fx, fy = run_to_end(X, pkg.ICP_POINT_TO_POINT), run_to_end(Y, pkg.ICP_POINT_TO_POINT)
+        fx, fy = run_to_end(X, pkg.ICP_POINT_TO_POINT, max_iter=12), run_to_end(Y, pkg.ICP_POINT_TO_POINT, max_iter=12)
         for b in range(len(far)):
             same_pair_bytes(fx[b], fy[b], f"pair {b}", T=compose(fy[b]["st"]["T"], T0F))
             assert X.diag_trim(b) == Y.diag_trim(b)

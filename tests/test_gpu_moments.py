@@ -17,33 +17,18 @@ a launch argument, a mailbox message or the batch's control block must all round
 
 Each test prints, per route, the largest |device - exact| / tol_s it saw.
 """
-import contextlib
-
 import numpy as np
 import pytest
 
 import clouds as cl
 import ref_moments as rm
+from switches import fresh_context
 
 pytestmark = pytest.mark.gpu
 
 PASSES = 4        # matching passes of a fixed_iterations loop; pass PASSES is the error-only one
-SWITCHES = ("ICP_TRACE", "ICP_MAILBOX", "ICP_RESIDENT", "ICP_ARMED", "ICP_NN_ROW", "ICP_NN_WAVES128", "ICP_NN_HIER", "ICP_SORT", "ICP_F64_SPARSE",
-            "ICP_HOST_ROWS_MAX", "ICP_FUSED_TAIL", "ICP_NN_SPARSE", "ICP_NN_SHARE", "ICP_NN_ORDER", "ICP_SHARE_RESIDENT_AFTER", "ICP_SHARE_AUTO")
-
 RATIO = {}        # route label -> largest |device - exact| / tol seen
 _REF = {}         # exact sums are shared by the forms that must reproduce one trajectory
-
-
-@contextlib.contextmanager
-def fresh_context(pkg, monkeypatch, env):
-    """the ICP_* switches are read by icp_create"""
-    for k in SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    with pkg.Context(0) as c:
-        yield c
 
 
 def bits(pkg):

@@ -10,8 +10,8 @@ import pytest
 
 import clouds as cl
 import ref_numpy
-from test_gpu_batch_plane import KNN_M, degenerate_pair, five_pairs, knn_models
-from test_gpu_moments import fresh_context
+from batch_ref import KNN_M, degenerate_pair, five_pairs, knn_models
+from switches import fresh_context
 
 pytestmark = pytest.mark.gpu
 

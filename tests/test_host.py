@@ -37,7 +37,7 @@ def test_matching_isa_has_no_fused_multiply_add():
     kernel must not contain fp fma/mad/fmac (integer mad for addressing is fine)."""
     import glob
     files = sorted(glob.glob(os.path.join(ROOT, "fast-point-cloud-registration-with-gpus_amd", "csrc", "build", "icp_k_*.s")))
-    assert len(files) == 6, "run `python __graft_entry__.py build` first"   # one translation unit per kernel family (csrc/Makefile)
+    assert len(files) == 7, "run `python __graft_entry__.py build` first"   # one translation unit per kernel family (csrc/Makefile)
     text = "".join(open(f).read() for f in files)
     kernels = re.findall(r"^(_ZN3icp\w*(?:nn_match|knn4)\w*):[^\n]*\n(.*?)\.Lfunc_end", text, flags=re.S | re.M)
     assert len(kernels) >= 6

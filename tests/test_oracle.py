@@ -261,7 +261,7 @@ def test_knn4_f64_beyond_the_fp32_twins_sentinel(orc):
 
 
 def plane_pairs_f64(pkg, golden):
-    from test_gpu_batch_plane import five_pairs
+    from batch_ref import five_pairs
     return cl.widen_pairs(five_pairs(pkg, golden))
 
 
