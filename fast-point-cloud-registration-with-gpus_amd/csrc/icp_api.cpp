@@ -156,7 +156,7 @@ int icp_create(int device, icp_ctx** out)
             (void)hipGetLastError();
             e = hipHostMalloc((void**)&c->h_mail, kMailSlots * kMailSlotBytes, hipHostMallocMapped | hipHostMallocCoherent);
         }
-        if (e == hipSuccess) { std::memset(c->h_mail, 0, kMailSlots * kMailSlotBytes); bar_fence(); }
+        if (e == hipSuccess) { std::memset(c->h_mail, 0, kMailSlots * kMailSlotBytes); icp::bar_fence(); }
     }
     if (e == hipSuccess) {
         if (hipExtMallocWithFlags((void**)&c->relay, kMailSlotBytes, hipDeviceMallocFinegrained) == hipSuccess) {

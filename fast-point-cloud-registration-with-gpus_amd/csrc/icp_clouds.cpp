@@ -286,8 +286,7 @@ int ensure_work_buffers(icp_ctx* c)
         }
         HIP_TRY(c->seed_pub.ensure((size_t)pl.blocks_x * 384 * sizeof(float)));
     }
-    if (pl.sparse && pl.version == 2 && pl.row != 64 && pl.blocks_x > c->host_rows_max && icp::nn_can_fuse_tail(pl)) {
-        // rows added up inside the launch
+    if (c->sums_in_launch(pl)) {   // (whether or not the tail is fused now: ICP_FUSED_TAIL is looked at per launch)
         if (c->fin_tickets.cap == 0) {
             HIP_TRY(c->fin_tickets.ensure((icp::NN_FIN_GROUPS + 1) * sizeof(unsigned int)));
             HIP_TRY(hipMemsetAsync(c->fin_tickets.p, 0, c->fin_tickets.cap, c->stream));

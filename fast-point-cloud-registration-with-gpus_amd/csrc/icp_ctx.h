@@ -2,10 +2,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#if defined(__x86_64__) || defined(__i386__)
-#include <immintrin.h>
-#endif
-
 #include <chrono>
 #include <cstdint>
 #include <sched.h>
@@ -15,6 +11,7 @@
 #include "icp_host_loop.h"
 #include "icp_kernels.h"
 #include "icp_lcomm.h"
+#include "icp_wire.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -32,17 +29,6 @@ inline int fail(int code, const std::string& msg)
         if (e_ != hipSuccess)                                                                                 \
             return fail(ICP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                      \
     } while (0)
-
-// orders the stores of a mailbox message before its sequence number (and pushes them out, should the mailbox ever
-// live in write-combining memory: the `lock or` compilers emit for a seq_cst fence does not do that)
-inline void bar_fence()
-{
-#if defined(__x86_64__) || defined(__i386__)
-    _mm_sfence();
-#else
-    __sync_synchronize();
-#endif
-}
 
 constexpr int kMailSlots = 4;  // armed launches: ring of mailboxes (one is live at a time)
 constexpr size_t kMailSlotBytes = sizeof(icp::NNMailbox64);   // a slot holds a float message (one line) or a double one (two)
@@ -247,6 +233,8 @@ struct __attribute__((visibility("hidden"))) icp_ctx {   // (the public header o
     static constexpr int kHostRowsMax = 1024;
     bool host_reduce() const { return !comm && mom_dev == (double*)mom_own.p && h_mom_partials != nullptr && (plan.blocks_x <= host_rows_max || plan.n == 0); }
     int host_rows_max = kHostRowsMax;   // (ICP_HOST_ROWS_MAX: A/B runs)
+    // the plan half of "this plan's rows are added up inside the launch" (the buffers: ensure_work_buffers; the rest: fin_in_launch)
+    bool sums_in_launch(const icp::NNPlan& pl) const { return pl.sparse && pl.version == 2 && pl.row != 64 && pl.blocks_x > host_rows_max && icp::nn_can_fuse_tail(pl); }
     icp::NNPlan plan{};
     LoopState loop;
 };

@@ -12,6 +12,9 @@
 // is issued speculatively before the stop rule for E[k] is known; when the rule fires that one
 // pass is discarded (it never touched P).  Correspondences ping-pong between two buffers so the
 // indices of the last CONTRIBUTING pass survive the speculative one.
+//
+// This file holds the loop's decisions: which form runs, what is pending, when to arm, withdraw or redo.  The bytes that travel
+// between the host and a running kernel -- mailbox lines, row formats, the row sweep, the adders, the tags -- are icp_wire.h's.
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -24,122 +27,11 @@
 
 namespace {
 
-#if defined(__x86_64__)
-// The compact rows of a pass added up, rows in block order: four 4-double accumulators take a row's sixteen slots at once.
-// Every slot is still the sum of its 256 values in block order, starting from zero -- the bits of the scalar loop -- but the
-// sixteen chains advance together instead of one after the other (hall: 256 rows, once per pass, on the path between the last
-// row's arrival and the next message).  The first slot of every 32-byte sector (0, 4, 8, 12) carries the row's tag in its low
-// mantissa bits (round 4: one store per row, no drain -- tail_reduce_store): masked off as it is loaded.
-__attribute__((target("avx"))) void add_compact_rows_avx(const double* rows, int count, unsigned long long tag_mask, double (&out)[16])
-{
-    const __m256d keep = _mm256_castsi256_pd(_mm256_set_epi64x(-1ll, -1ll, -1ll, (long long)~tag_mask));
-    __m256d a0 = _mm256_setzero_pd(), a1 = a0, a2 = a0, a3 = a0;
-    for (int b = 0; b < count; ++b) {
-        const double* r = rows + (size_t)b * 16;
-        a0 = _mm256_add_pd(a0, _mm256_and_pd(_mm256_loadu_pd(r), keep));
-        a1 = _mm256_add_pd(a1, _mm256_and_pd(_mm256_loadu_pd(r + 4), keep));
-        a2 = _mm256_add_pd(a2, _mm256_and_pd(_mm256_loadu_pd(r + 8), keep));
-        a3 = _mm256_add_pd(a3, _mm256_and_pd(_mm256_loadu_pd(r + 12), keep));
-    }
-    _mm256_storeu_pd(out, a0); _mm256_storeu_pd(out + 4, a1); _mm256_storeu_pd(out + 8, a2); _mm256_storeu_pd(out + 12, a3);
-}
-
-// the same for rows in the full format (ICP_NMOM = 32 doubles, the last one the row's tag: not a moment -- left out)
-__attribute__((target("avx"))) void add_full_rows_avx(const double* rows, int count, double (&out)[32])
-{
-    const __m256d keep = _mm256_castsi256_pd(_mm256_set_epi64x(0ll, -1ll, -1ll, -1ll));
-    __m256d a[8];
-    for (int v = 0; v < 8; ++v) a[v] = _mm256_setzero_pd();
-    for (int b = 0; b < count; ++b) {
-        const double* r = rows + (size_t)b * 32;
-        for (int v = 0; v < 7; ++v) a[v] = _mm256_add_pd(a[v], _mm256_loadu_pd(r + 4 * v));
-        a[7] = _mm256_add_pd(a[7], _mm256_and_pd(_mm256_loadu_pd(r + 28), keep));
-    }
-    for (int v = 0; v < 8; ++v) _mm256_storeu_pd(out + 4 * v, a[v]);
-}
-
-__attribute__((target("avx"))) void store_line_avx(uint32_t* dst, const uint32_t* line)
-{
-    _mm256_store_si256(reinterpret_cast<__m256i*>(dst), _mm256_load_si256(reinterpret_cast<const __m256i*>(line)));
-    _mm256_store_si256(reinterpret_cast<__m256i*>(dst + 8), _mm256_load_si256(reinterpret_cast<const __m256i*>(line + 8)));
-}
-#endif
-
-// One message = one 64-byte line (layout: icp_kernels.h, NNMailbox): each 32-byte half is written by ONE vector store
-// and carries the tag in its last word, then one fence pushes the line out.  rt may be NULL (commands that carry no
-// transform); seq = 0 clears the mailbox (no tag ever equals 0).
-inline void post_message(icp::NNMailbox* mb, const double* R9, const double* t3, int cmd, double seq, bool wide_stores)
-{
-    alignas(32) uint32_t line[16];
-    std::memset(line, 0, sizeof line);
-    const uint32_t tag = seq == 0.0 ? 0u : icp::mailbox_tag(seq);
-    if (R9 && t3) {
-        for (int k = 0; k < 12; ++k) {
-            const float f = (float)(k < 9 ? R9[k] : t3[k - 9]);
-            std::memcpy(&line[icp::mailbox_rt_word(k)], &f, sizeof f);
-        }
-    }
-    line[icp::ICP_MB_CMD] = (uint32_t)cmd;
-    line[icp::ICP_MB_TAG0] = tag;
-    line[icp::ICP_MB_TAG1] = tag;
-#if defined(__x86_64__)
-    static const bool have_avx = __builtin_cpu_supports("avx");
-    if (have_avx && wide_stores) {
-        store_line_avx(mb->w, line);
-        bar_fence();
-        return;
-    }
-#endif
-    // no 32-byte stores: the payload first, then (fenced) the two tags -- the reader still accepts only a line whose
-    // tags both match, so the order of the words within a half does not matter
-    volatile uint32_t* dst = mb->w;
-    for (int k = 0; k < 16; ++k)
-        if (k != icp::ICP_MB_TAG0 && k != icp::ICP_MB_TAG1) dst[k] = line[k];
-    bar_fence();
-    dst[icp::ICP_MB_TAG0] = tag;
-    dst[icp::ICP_MB_TAG1] = tag;
-    bar_fence();
-}
-
-// the message of a registration in double (NNMailbox64): four 32-byte parts {3 doubles, cmd, tag}, one vector store each
-inline void post_message64(icp::NNMailbox* mb32, const double* R9, const double* t3, int cmd, double seq, bool wide_stores)
-{
-    alignas(32) uint32_t line[32];
-    std::memset(line, 0, sizeof line);
-    const uint32_t tag = seq == 0.0 ? 0u : icp::mailbox_tag(seq);
-    for (int h = 0; h < 4; ++h) {
-        if (R9 && t3)
-            for (int k = 0; k < 3; ++k) {
-                const int i = 3 * h + k;
-                const double v = i < 9 ? R9[i] : t3[i - 9];
-                std::memcpy(&line[h * 8 + 2 * k], &v, sizeof v);
-            }
-        line[h * 8 + icp::ICP_MB64_CMD] = (uint32_t)cmd;
-        line[h * 8 + 7] = tag;
-    }
-    uint32_t* dstw = reinterpret_cast<uint32_t*>(mb32);
-#if defined(__x86_64__)
-    static const bool have_avx = __builtin_cpu_supports("avx");
-    if (have_avx && wide_stores) {
-        store_line_avx(dstw, line);
-        store_line_avx(dstw + 16, line + 16);
-        bar_fence();
-        return;
-    }
-#endif
-    volatile uint32_t* dst = dstw;
-    for (int k = 0; k < 32; ++k)
-        if ((k & 7) != 7) dst[k] = line[k];
-    bar_fence();
-    for (int h = 0; h < 4; ++h) dst[h * 8 + 7] = tag;
-    bar_fence();
-}
-
 // one message to the kernel listening at mb, in the registration's precision (ICP_MAILBOX=plain: written word by word)
 inline void post(const icp_ctx* c, icp::NNMailbox* mb, const double* R9, const double* t3, int cmd, double seq)
 {
-    if (c->prec == ICP_F64) post_message64(mb, R9, t3, cmd, seq, c->mail_wide);
-    else post_message(mb, R9, t3, cmd, seq, c->mail_wide);
+    if (c->prec == ICP_F64) icp::post_message64(mb, R9, t3, cmd, seq, c->mail_wide);
+    else icp::post_message(mb, R9, t3, cmd, seq, c->mail_wide);
 }
 
 // Time budgets of a kernel that waits for the host, ordered so that a late host and a waiting kernel can never disagree:
@@ -159,29 +51,15 @@ static_assert(kMailLeaseS * 2.0 < (double)ICP_MAILBOX_BUDGET_S && kRowPollS < (d
 // polls it) -- else in the device vector a collective, or the caller, goes on from.
 bool fin_in_launch(const icp_ctx* c, const icp::NNPlan& pl)
 {
-    return c->fused_tail && pl.sparse && pl.version == 2 && pl.row != 64 && icp::nn_can_fuse_tail(pl) && pl.blocks_x > c->host_rows_max &&
-           c->fin_tickets.p != nullptr && c->fin_scratch.p != nullptr && c->h_final != nullptr;
+    return c->fused_tail && c->sums_in_launch(pl) && c->fin_tickets.p != nullptr && c->fin_scratch.p != nullptr && c->h_final != nullptr;
 }
 bool fin_to_host(const icp_ctx* c) { return !c->comm && c->mom_dev == (double*)c->mom_own.p; }
 // rows the host itself adds up (single GPU, or ranks meeting in host memory) leave the sparse point-to-point kernels in
 // the compact two-cache-line form (icp_kernels.h, NNTailArgs)
 bool use_compact_rows(const icp_ctx* c, const icp::NNPlan& pl, int metric, const double* rows)
 {
-    // (fp32 only: the compact row spends the last 16 mantissa bits of the error share on its tag -- 2^-36 of a sum of squares
-    // of floats is nothing, but the fp64 path is held to 1e-12 against src/ICP_CPU.c's arithmetic)
+    // (fp32 only: the compact row spends mantissa bits on its tag, and the fp64 path is held to 1e-12 against src/ICP_CPU.c's arithmetic)
     return c->prec == ICP_F32 && pl.sparse && metric == ICP_POINT_TO_POINT && rows == c->h_mom_partials;
-}
-
-// Completion tags are consecutive integers.  A compact row shows only the low NN_CROW_TAG_BITS bits of its tag, and a
-// wiped row shows zero: no tag that is ever waited for may have those bits all zero.  Returns the first of `count`
-// consecutive tags that are safe in that sense and reserves them.
-uint64_t take_tags(icp_ctx* c, uint64_t count)
-{
-    constexpr uint64_t kMod = 1ull << icp::NN_CROW_TAG_BITS;
-    uint64_t first = c->tag_seq + 1;
-    if (first % kMod == 0 || first / kMod != (first + count - 1) / kMod) first = (first / kMod + 1) * kMod + 1;   // (count << kMod)
-    c->tag_seq = first + count - 1;
-    return first;
 }
 
 // The two row formats keep their completion tags in different places of the same pinned buffer: when the format changes
@@ -192,7 +70,7 @@ void prepare_rows_format(icp_ctx* c, bool compact)
     const int want = compact ? 1 : 0;
     if (c->rows_format == want || !c->h_mom_partials) { c->rows_format = want; return; }
     std::memset(c->h_mom_partials, 0, c->rows_cap * ICP_NMOM * sizeof(double));
-    bar_fence();
+    icp::bar_fence();
     c->rows_format = want;
 }
 
@@ -317,77 +195,29 @@ void debug_stall(icp_ctx* c)
 }
 
 // ---- the three waits of a complete -------------------------------------------------------------------------------
-constexpr unsigned long long kTagMask = (1ull << icp::NN_CROW_TAG_BITS) - 1ull;
-
-// the tag row b carries now: a double of its own (full rows), or the low mantissa bits of slot 0 (compact rows)
-// (compact rows: a tag in every 32-byte sector -- slots 0, 4, 8, 12; the row's tag is what all four agree on, else "none")
-double row_tag(const icp_ctx* c, int b, bool compact)
-{
-    const size_t stride = compact ? (size_t)icp::NN_CROW : (size_t)ICP_NMOM, tag_slot = compact ? 0 : ICP_NMOM - 1;
-    const volatile double* p = c->h_mom_partials + (size_t)b * stride + tag_slot;
-    if (!compact) return *p;
-    const volatile unsigned long long* q = reinterpret_cast<const volatile unsigned long long*>(p);
-    const unsigned long long t0 = q[0] & kTagMask, t1 = q[4] & kTagMask, t2 = q[8] & kTagMask, t3 = q[12] & kTagMask;
-    return (t0 == t1 && t0 == t2 && t0 == t3) ? (double)t0 : -1.0;
-}
+const icp::RowFormat& pending_format(const LoopState& L) { return L.rows_compact ? icp::kCompactRows : icp::kFullRows; }
 
 // The kernels wrote their partial rows into mapped pinned memory.  Instead of a stream synchronisation the host polls the
-// per-row completion tags (each row is released to system scope before its tag); the matching kernel's error rows were
-// complete before the moments kernel started.
-// The poll is a SWEEP over the rows whose tag is still missing -- the cache misses of different rows overlap, where polling
-// row b to completion before looking at row b + 1 takes them one after the other -- and fetches a row's other lines as soon
-// as its tag is seen (tools/rows_probe.hip: 256 rows 6.6 -> 5.8 us).  sum_host_rows adds the rows up in block order once all
-// are there.
-// (round 3 tried a LIST of the rows still missing instead of the flags -- a sweep then costs what is missing, not the row count:
-// no difference on the hall loop, 8.99-9.07 against 8.92-9.04 us per iteration on one box; the tags are compared as the
-// integers they are.)  Rows in the full format (point-to-plane, fp64) are swept the same way; their tag is a double of its own
-// in the row's last slot, compared by its bits.
+// per-row completion tags (icp_wire.h, sweep_rows); the matching kernel's error rows were complete before the moments
+// kernel started.  sum_host_rows adds the rows up in block order once all are there.
 int wait_host_rows(icp_ctx* c, bool tracing)
 {
     LoopState& L = c->loop;
-    const bool compact = L.rows_compact;
+    const icp::RowFormat& fmt = pending_format(L);
     const int rows = L.mom_blocks;
-    const double want = compact ? (double)((unsigned long long)L.wait_tag & kTagMask) : L.wait_tag;
     if (rows > 0 && !L.timed_nn && L.err_blocks == 0) {
         // (the poll's start: what the 2 s time-out counts from; the host got here right after posting the message, whose
         // time the resident loop has just read -- an armed or plain pass reads the clock itself)
         const auto t0 = L.live_mailbox != nullptr && !tracing ? c->posted_at : std::chrono::steady_clock::now();
-        const size_t stride = compact ? (size_t)icp::NN_CROW : (size_t)ICP_NMOM, tag_slot = compact ? 0 : ICP_NMOM - 1;
-        unsigned long long want_bits = (unsigned long long)want, tag_bits_mask = kTagMask;
-        if (!compact) { std::memcpy(&want_bits, &want, sizeof want_bits); tag_bits_mask = ~0ull; }
-        const double* base = c->h_mom_partials;   // (a local: a store to the flags, unsigned char, may alias any field of *c)
-        const volatile unsigned long long* tags = reinterpret_cast<const volatile unsigned long long*>(base) + tag_slot;
-        unsigned char* seen = c->rows_seen;
-        std::memset(seen, 0, (size_t)rows);
-        int left = rows;
-        unsigned spins = 0;
-        while (left > 0) {
-            for (int r = 0; r < rows; ++r) {
-                const volatile unsigned long long* t = tags + (size_t)r * stride;
-                if (seen[r] || (t[0] & tag_bits_mask) != want_bits) continue;
-                // (compact rows: every 32-byte sector carries the tag; the row is there when all four do)
-                if (compact && ((t[4] & tag_bits_mask) != want_bits || (t[8] & tag_bits_mask) != want_bits || (t[12] & tag_bits_mask) != want_bits)) continue;
-                seen[r] = 1;
-                --left;
-                const char* row = reinterpret_cast<const char*>(base + (size_t)r * stride);
-                if (compact) __builtin_prefetch(row + 64);
-                else for (int l = 0; l < 3; ++l) __builtin_prefetch(row + 64 * l);   // (the tag sits in the row's fourth line)
-                if (left == rows - 1 && c->trace_passes) c->tr_first_row = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            }
-            if (left > 0 && (++spins & 0x3f) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > kRowPollS)
-                break;  // something is wrong (fault, hang): let the runtime report it
-        }
+        const int left = icp::sweep_rows(c->h_mom_partials, rows, fmt, L.wait_tag, c->rows_seen, t0, kRowPollS, c->trace_passes ? &c->tr_first_row : nullptr);
         c->rows_done_at = std::chrono::steady_clock::now();
         if (c->trace_passes) { c->tr_last_row = std::chrono::duration<double>(c->rows_done_at - t0).count(); c->tr_rows_done = c->rows_done_at; }
-        if (left == 0) {
-            std::atomic_thread_fence(std::memory_order_acquire);
-            return ICP_OK;
-        }
+        if (left == 0) return ICP_OK;
         if (c->trace) {
             std::fprintf(stderr, "[icp trace]   poll gave up with %d of %d rows in; rows still missing:", rows - left, rows);
             int shown = 0;
             for (int r = 0; r < rows && shown < 40; ++r)
-                if (!seen[r]) { std::fprintf(stderr, " %d", r); ++shown; }
+                if (!c->rows_seen[r]) { std::fprintf(stderr, " %d", r); ++shown; }
             std::fprintf(stderr, "\n");
         }
     }
@@ -395,14 +225,15 @@ int wait_host_rows(icp_ctx* c, bool tracing)
     // next message -- withdraw it (under the tag it will wait for) -- and let the stream say what happened
     if (L.live_mailbox) post(c, L.live_mailbox, nullptr, nullptr, icp::ICP_CMD_EXIT, L.wait_tag + 1.0);
     HIP_TRY(hipStreamSynchronize(c->stream));
+    const double want = fmt.shows(L.wait_tag);
     for (int b = 0; b < rows; ++b)
-        if (row_tag(c, b, compact) != want) {
+        if (icp::row_tag(c->h_mom_partials, b, fmt) != want) {
             L.pending = false;
             char msg[240];
             int have = 0;
-            for (int r = 0; r < rows; ++r) have += row_tag(c, r, compact) == want ? 1 : 0;
+            for (int r = 0; r < rows; ++r) have += icp::row_tag(c->h_mom_partials, r, fmt) == want ? 1 : 0;
             std::snprintf(msg, sizeof msg, "a matching pass ended without producing its rows: row %d of %d carries tag %.0f, expected %.0f; %d rows arrived (armed / resident launch timed out?)",
-                          b, rows, row_tag(c, b, compact), want, have);
+                          b, rows, icp::row_tag(c->h_mom_partials, b, fmt), want, have);
             c->rows_timed_out = true;
             return fail(ICP_ERR_HIP, msg);
         }
@@ -415,49 +246,13 @@ int wait_host_rows(icp_ctx* c, bool tracing)
 int sum_host_rows(icp_ctx* c)
 {
     const LoopState& L = c->loop;
-    const bool compact = L.rows_compact;
     double* mom = c->h_mom;
     for (int k = 0; k < ICP_NMOM; ++k) mom[k] = 0.0;
     for (int b = 0; b < L.err_blocks; ++b) mom[ICP_MOM_ERR] += c->h_err_partials[b];
     // (a compact row does not carry its point count: a row of the sparse kernels holds the real points of its slots)
-    if (compact) mom[ICP_MOM_CNT] = (double)c->n;
+    if (L.rows_compact) mom[ICP_MOM_CNT] = (double)c->n;
     if (L.mom_blocks == 0) return 0;
-#if defined(__x86_64__)
-    static const bool have_avx = __builtin_cpu_supports("avx");
-    static_assert(icp::NN_CROW == 16 && ICP_NMOM == 32, "the AVX adders take rows of sixteen and of 32 doubles");
-    if (have_avx && c->mail_wide && compact) {
-        double sum[16];
-        add_compact_rows_avx(c->h_mom_partials, L.mom_blocks, kTagMask, sum);
-        mom[ICP_MOM_ERR] += sum[0];
-        for (int k = 1; k < icp::NN_CROW; ++k) mom[ICP_MOM_SP - 1 + k] += sum[k];
-        return ICP_ROUTE_AVX;
-    }
-    if (have_avx && c->mail_wide) {
-        double sum[32];
-        add_full_rows_avx(c->h_mom_partials, L.mom_blocks, sum);
-        for (int k = 0; k < ICP_NMOM - 1; ++k) mom[k] += sum[k];
-        return ICP_ROUTE_AVX;
-    }
-#endif
-    for (int b = 0; b < L.mom_blocks; ++b) {
-        if (compact) {   // {error share + tag, sum p, sum q, sum q p^T} -> slots ICP_MOM_SP .. ICP_MOM_SQP + 8, ICP_MOM_ERR
-            const double* row = c->h_mom_partials + (size_t)b * icp::NN_CROW;
-            auto untagged = [&](int k) {
-                unsigned long long bits;
-                std::memcpy(&bits, &row[k], sizeof bits);
-                if ((k & 3) == 0) bits &= ~kTagMask;   // (the first slot of every 32-byte sector carries the tag)
-                double v;
-                std::memcpy(&v, &bits, sizeof v);
-                return v;
-            };
-            for (int k = 1; k < icp::NN_CROW; ++k) mom[ICP_MOM_SP - 1 + k] += untagged(k);
-            mom[ICP_MOM_ERR] += untagged(0);
-        } else {
-            const double* row = c->h_mom_partials + (size_t)b * ICP_NMOM;
-            for (int k = 0; k < ICP_NMOM - 1; ++k) mom[k] += row[k];  // the last slot is the completion tag
-        }
-    }
-    return 0;
+    return icp::sum_rows(c->h_mom_partials, L.mom_blocks, pending_format(L), c->mail_wide, mom) ? ICP_ROUTE_AVX : 0;
 }
 
 // the launch itself added its rows up and leaves the vector in pinned memory, the pass's tag in its last slot
@@ -537,7 +332,7 @@ int loop_enqueue_body(icp_ctx* c)
         c->idx_valid = true;
         const bool time_this = c->profile_stride > 0 && (c->nn_launch_count++ % (uint64_t)c->profile_stride) == 0;
         if (time_this) { HIP_TRY(hipEventRecord(c->ev0, c->stream)); }
-        if (tail) ta = tail_args(c, pl, (int32_t*)c->idx[c->cur].p, (double)take_tags(c, 1), host_reduce);
+        if (tail) ta = tail_args(c, pl, (int32_t*)c->idx[c->cur].p, (double)icp::take_tags(c->tag_seq, 1), host_reduce);
         if (host_reduce) prepare_rows_format(c, ta.compact != 0);   // (also the two-kernel form: launch_moments writes full rows)
         icp::NNFusedTransform ft{L.H.R, L.H.t, (const int32_t*)c->idx[L.applied_idx].p, c->P2.p, err_rows};
         // every fused pass of the sparse kernels leaves its points and matches in slot order; the next one starts from them
@@ -560,7 +355,7 @@ int loop_enqueue_body(icp_ctx* c)
         } else {
             HIP_TRY(icp::launch_moments(pl, L.H.prm.metric, c->P.p, c->Q.p, c->Nrm.p, c->part_d.p,
                                         (const int32_t*)c->part_idx.p, (int32_t*)c->idx[c->cur].p, host_reduce ? c->h_mom_partials : (double*)c->mom_partials.p,
-                                        &mom_blocks, (double)take_tags(c, 1), err_rows, err_blocks, c->stream));
+                                        &mom_blocks, (double)icp::take_tags(c->tag_seq, 1), err_rows, err_blocks, c->stream));
             if (host_reduce) err_blocks = 0;  // already inside the moment rows
         }
     }
@@ -697,7 +492,7 @@ int loop_arm(icp_ctx* c)
     const int prev_cur = c->cur;
     const int slot = (int)(c->mail_seq++ % kMailSlots);
     icp::NNMailbox* mb = mail_slot(c->h_mail, slot);
-    const double tag = (double)take_tags(c, 1);
+    const double tag = (double)icp::take_tags(c->tag_seq, 1);
     post(c, mb, nullptr, nullptr, icp::ICP_CMD_EXIT, 0.0);   // cleared: nothing to act on yet
     // (can_arm: the host adds the rows up, or the launch does and the vector comes back in pinned memory)
     const bool host_rows = c->host_reduce();
@@ -775,7 +570,7 @@ int loop_run_resident(icp_ctx* c, int max_steps, int* k_io, int* d_io, bool* fel
     rp.seg_len = icp::round_up(rp.m_pad, 8);
     icp::NNMailbox* mb = mail_slot(c->h_mail, (int)(c->mail_seq++ % kMailSlots));
     const int pass_cap = L.H.prm.max_iter + 2;
-    const double base = (double)take_tags(c, (uint64_t)pass_cap + 1);
+    const double base = (double)icp::take_tags(c->tag_seq, (uint64_t)pass_cap + 1);
     post(c, mb, nullptr, nullptr, icp::ICP_CMD_EXIT, 0.0);   // cleared
     const int c0 = c->cur;
     const icp::NNCullInputs cull = make_cull(c, L.matched ? (const int32_t*)c->idx[c0].p : nullptr);
