@@ -28,6 +28,8 @@ ICP_BATCH_MAX_POINTS = 65536   # per cloud of one pair of a batch
 ROUTE_HOST_ROWS, ROUTE_COMPACT, ROUTE_AVX, ROUTE_FIN_LAUNCH, ROUTE_FIN_PINNED, ROUTE_FIN_KERNEL = 0x001, 0x002, 0x004, 0x008, 0x010, 0x020
 ROUTE_FIN_TWO_STAGE, ROUTE_FUSED_TAIL, ROUTE_MOMENTS_KERNEL, ROUTE_ERROR_ONLY, ROUTE_ARMED, ROUTE_RESIDENT = 0x040, 0x080, 0x100, 0x200, 0x400, 0x800
 MOM_ERR, MOM_CNT, MOM_SP, MOM_SQ, MOM_SQP, MOM_SPP, MOM_SQQ, MOM_C, MOM_B = 0, 1, 2, 5, 8, 17, 18, 2, 23
+# icp_batch_evaluate: slots of a pair's evaluation vector (include/icp_mi355x_diag.h); the plane metric fills MOM_C .. MOM_C + 20
+EVAL_SD, EVAL_CNT, EVAL_SQ, EVAL_SQQ = 0, 1, 2, 5
 
 
 class icp_params(C.Structure):
@@ -104,6 +106,7 @@ SIGNATURES = {
     "icp_batch_set_trim": (_i, [_vp, _pd]),
     "icp_batch_get_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_batch_loop_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
+    "icp_batch_evaluate": (_i, [_vp, _i, _pd, _pi, _pi32, _pd, _pd, _pd, _pi32, C.POINTER(C.c_uint8)]),
     "icp_point_to_point_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_point_to_plane_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, _vp, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_comm_unique_id": (_i, [_vp]),
@@ -127,6 +130,7 @@ SIGNATURES = {
     "icp_diag_loop_moments": (_i, [_vp, _pd, _pi]),
     "icp_diag_batch_moments": (_i, [_vp, _i, _pd]),
     "icp_diag_batch_trim": (_i, [_vp, _i, _pd, _pi]),
+    "icp_diag_batch_eval_moments": (_i, [_vp, _i, _pd]),
     "icp_eigh3": (_i, [_pd, _pd, _pd]),
     "icp_synthetic_grid_f32": (_i, [_i, C.c_float, C.c_float, _vp]),
     "icp_synthetic_grid_f64": (_i, [_i, C.c_double, C.c_double, _vp]),

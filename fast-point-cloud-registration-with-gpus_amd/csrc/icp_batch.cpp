@@ -22,6 +22,12 @@
 // (tau = the K-th smallest distance, per pair)  ->  batch_trim_moments (the decision, with the gate's where there is one, and the
 // sums)  ->  batch_finalize_kernel: four launches, still one download.  A batch whose shares are all 1.0 runs the steps above.
 //
+// A batch answers how well every pair is registered where it stands (icp_batch_evaluate): the loop's own matching -- the deferred
+// instantiation with mode BATCH_MATCH alone, which only reads P -- into buffers of the evaluation's own, batch_eval_moments (the
+// decision at the caller's distance and the ICP_EVAL_* terms), batch_finalize_kernel, and one download of ICP_NMOM doubles per
+// pair: three launches, none of which writes idx, mom, tau, thr or ctl of the loop.  Fitness, inlier RMSE and the 6 x 6 information
+// matrix are assembled on the host from that vector alone.  The loop does not notice the call.
+//
 // Point-to-plane needs the model normals of every pair, in planes laid out as the models: given by the caller
 // (icp_batch_set_model_normals) or made on the device by ONE neighbour launch + ONE normals launch for the whole batch
 // (icp_batch_estimate_normals: knn4_batch + normals_batch_kernel, icp_k_plane.hip).  The reference estimates them once per
@@ -78,6 +84,11 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     std::vector<int> last_match;             // idx buffer of the pair's most recent matching pass
     std::vector<int> applied_buf;            // idx buffer of the pass whose motion the pair applied last
     std::vector<char> mom_seen;              // the pair's HostLoop has advanced on its row of h_mom since icp_batch_begin
+    std::vector<char> refused;               // icp_batch_begin refused the pair's start cloud (not finite): it is not evaluated
+    // icp_batch_evaluate: buffers of its own, allocated by the first call (the loop's are never written)
+    DevBuf e_mode, e_thr, e_idx, e_dist, e_partials, e_mom;
+    double* h_eval = nullptr;                // pinned: count x ICP_NMOM, the vectors of the latest evaluation
+    bool eval_seen = false;                  // h_eval holds an evaluation
 };
 
 namespace {
@@ -113,13 +124,15 @@ void reset_loop_state(icp_batch* b)
     b->applied_buf.assign((size_t)b->count, 0);
     b->mom_seen.assign((size_t)b->count, 0);
     b->tau_seen.assign((size_t)b->count, 0);
+    b->refused.assign((size_t)b->count, 0);
 }
 
 void release(icp_batch* b)
 {
     for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag,
-                      &b->trim_rank, &b->tau, &b->dist})
+                      &b->trim_rank, &b->tau, &b->dist, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom})
         d->release();
+    if (b->h_eval) (void)hipHostFree(b->h_eval);
     if (b->h_ctl) (void)hipHostFree(b->h_ctl);
     if (b->h_mom) (void)hipHostFree(b->h_mom);
     delete b;
@@ -452,6 +465,7 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
             if (flag[p]) {
                 b->status[p] = ICP_ERR_INVALID;
                 b->H[p].done = true;
+                b->refused[p] = 1;
             }
     } else {
         HIP_TRY(hipMemcpyAsync(b->P.p, b->P0.p, 3 * (size_t)b->p_plane * b->esize, hipMemcpyDeviceToDevice, b->ctx->stream));
@@ -536,6 +550,121 @@ int icp_diag_batch_trim(icp_batch* b, int pair, double* tau_sq, int* rank)
             *tau_sq = get_scalar(b, &raw, 0);
         }
     }
+    return ICP_OK;
+}
+
+int icp_batch_evaluate(icp_batch* b, int metric, const double* max_dist, int* status_out, int32_t* inliers_out, double* fitness_out,
+                       double* rmse_out, double* info_out, int32_t* idx_out, uint8_t* mask_out)
+{
+    if (int rc = ready(b)) return rc;
+    if (metric != ICP_POINT_TO_POINT && metric != ICP_POINT_TO_PLANE) return fail(ICP_ERR_INVALID, "unknown metric");
+    if (!b->begun) return fail(ICP_ERR_STATE, "icp_batch_begin first: an evaluation needs the clouds of a loop");
+    const bool plane = metric == ICP_POINT_TO_PLANE;
+    if (plane && !b->have_normals)
+        return fail(ICP_ERR_INVALID, "a point-to-plane evaluation needs the model normals: icp_batch_set_model_normals or icp_batch_estimate_normals first");
+    if (max_dist)
+        for (int p = 0; p < b->count; ++p)   // (icp_batch_set_max_distance's rule: NaN fails the comparison too; -inf is <= 0)
+            if (!(max_dist[p] > 0))
+                return fail(ICP_ERR_INVALID, "the evaluation distance must be > 0 or +INFINITY: pair " + std::to_string(p));
+    icp_ctx* c = b->ctx;
+    ScopedPin pin(c);
+    const size_t vec_bytes = (size_t)b->count * ICP_NMOM * sizeof(double);
+    HIP_TRY(b->e_mode.ensure((size_t)b->count * sizeof(int)));
+    HIP_TRY(b->e_thr.ensure((size_t)b->count * b->esize));
+    HIP_TRY(b->e_idx.ensure((size_t)b->p_plane * sizeof(int32_t)));
+    HIP_TRY(b->e_dist.ensure((size_t)b->p_plane * b->esize));
+    HIP_TRY(b->e_partials.ensure((size_t)b->n_items * ICP_NMOM * sizeof(double)));
+    HIP_TRY(b->e_mom.ensure(vec_bytes));
+    if (!b->h_eval) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_eval), vec_bytes, hipHostMallocDefault));
+    // every pair is evaluated where its cloud stands -- running, ended or failed -- but one whose start cloud was refused
+    std::vector<int> mode((size_t)b->count);
+    for (int p = 0; p < b->count; ++p) mode[p] = b->refused[p] ? 0 : icp::BATCH_MATCH;
+    std::vector<char> thr;
+    HIP_TRY(hipMemcpyAsync(b->e_mode.p, mode.data(), mode.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (max_dist) {   // thr = (F)(max_dist^2): the product in double, rounded once to the batch's precision
+        thr.resize((size_t)b->count * b->esize);
+        for (int p = 0; p < b->count; ++p) put_scalar(b, thr.data(), (size_t)p, max_dist[p] * max_dist[p]);
+        HIP_TRY(hipMemcpyAsync(b->e_thr.p, thr.data(), thr.size(), hipMemcpyHostToDevice, c->stream));
+    }
+    icp::BatchEvalArgs a{};
+    a.precision = b->prec;
+    a.metric = metric;
+    a.items = (const icp::BatchItem*)b->items.p;
+    a.n_items = b->n_items;
+    a.pairs = (const icp::BatchPair*)b->pairs_d.p;
+    a.n_pairs = b->count;
+    a.mode = (const int*)b->e_mode.p;
+    a.P_soa = b->P.p;
+    a.p_plane = b->p_plane;
+    a.Q_soa = b->Q.p;
+    a.N_soa = plane ? b->N.p : nullptr;
+    a.q_plane = b->q_plane;
+    a.thr = max_dist ? b->e_thr.p : nullptr;
+    a.idx = (int32_t*)b->e_idx.p;
+    a.dist = b->e_dist.p;
+    a.partials = (double*)b->e_partials.p;
+    a.mom = (double*)b->e_mom.p;
+    std::vector<int32_t> hidx;
+    hipError_t e = icp::launch_batch_evaluate(a, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b->h_eval, b->e_mom.p, vec_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && (idx_out || mask_out)) {
+        hidx.resize((size_t)b->p_plane);
+        e = hipMemcpyAsync(hidx.data(), b->e_idx.p, hidx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);   // (always: the host vectors above must outlive their copies)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        b->eval_seen = false;   // (the pinned vectors are in an unknown state; the loop's buffers were not written)
+        return fail(ICP_ERR_HIP, std::string("icp_batch_evaluate: ") + hipGetErrorString(e));
+    }
+    b->eval_seen = true;
+    for (int p = 0; p < b->count; ++p) {
+        double* v = b->h_eval + (size_t)p * ICP_NMOM;
+        const int n = b->pairs[p].n;
+        if (b->refused[p]) std::memset(v, 0, ICP_NMOM * sizeof(double));   // (its row of the device vector was never written)
+        const double cnt = v[ICP_EVAL_CNT];
+        if (status_out) status_out[p] = b->refused[p] ? ICP_ERR_INVALID : ICP_OK;
+        if (inliers_out) inliers_out[p] = (int32_t)cnt;
+        if (fitness_out) fitness_out[p] = cnt / (double)n;
+        if (rmse_out) rmse_out[p] = cnt > 0.0 ? std::sqrt(v[ICP_EVAL_SD] / cnt) : 0.0;
+        if (info_out) {
+            double* I = info_out + (size_t)p * 36;
+            for (int k = 0; k < 36; ++k) I[k] = 0.0;
+            if (b->refused[p]) {
+                // (zeros)
+            } else if (plane) {   // C, mirrored
+                int o = ICP_MOM_C;
+                for (int r = 0; r < 6; ++r)
+                    for (int s = r; s < 6; ++s) I[r * 6 + s] = I[s * 6 + r] = v[o++];
+            } else {   // sum over the kept q = (x, y, z) of g1 g1^T + g2 g2^T + g3 g3^T: g1 = (0, z, -y, 1, 0, 0), g2 = (-z, 0, x, 0, 1, 0), g3 = (y, -x, 0, 0, 0, 1)
+                const double sx = v[ICP_EVAL_SQ], sy = v[ICP_EVAL_SQ + 1], sz = v[ICP_EVAL_SQ + 2];
+                const double xx = v[ICP_EVAL_SQQ], xy = v[ICP_EVAL_SQQ + 1], xz = v[ICP_EVAL_SQQ + 2];
+                const double yy = v[ICP_EVAL_SQQ + 3], yz = v[ICP_EVAL_SQQ + 4], zz = v[ICP_EVAL_SQQ + 5];
+                auto sym = [I](int r, int s, double val) { I[r * 6 + s] = I[s * 6 + r] = val; };
+                sym(0, 0, yy + zz); sym(1, 1, xx + zz); sym(2, 2, xx + yy);
+                sym(0, 1, -xy); sym(0, 2, -xz); sym(1, 2, -yz);
+                sym(0, 4, -sz); sym(0, 5, sy);
+                sym(1, 3, sz); sym(1, 5, -sx);
+                sym(2, 3, -sy); sym(2, 4, sx);
+                sym(3, 3, cnt); sym(4, 4, cnt); sym(5, 5, cnt);
+            }
+        }
+        for (int i = 0; i < n && (idx_out || mask_out); ++i) {
+            const int32_t raw = b->refused[p] ? 0 : hidx[(size_t)b->pairs[p].p_off + i];
+            if (idx_out) idx_out[b->moff[p] + i] = raw & icp::BATCH_IDX_MASK;
+            if (mask_out) mask_out[b->moff[p] + i] = (!b->refused[p] && raw >= 0) ? 1 : 0;
+        }
+    }
+    return ICP_OK;
+}
+
+int icp_diag_batch_eval_moments(icp_batch* b, int pair, double* out32)
+{
+    if (!b || !out32) return fail(ICP_ERR_INVALID, "null argument");
+    if (pair < 0 || pair >= b->count) return fail(ICP_ERR_INVALID, "pair out of range");
+    if (!b->eval_seen || !b->h_eval) return fail(ICP_ERR_STATE, "no evaluation of this batch");
+    std::memcpy(out32, b->h_eval + (size_t)pair * ICP_NMOM, ICP_NMOM * sizeof(double));
     return ICP_OK;
 }
 

@@ -1,10 +1,12 @@
 // icp_k_batch.hip -- gfx950 kernels of batched ICP (icp_batch.cpp): the pass of every running pair in one launch (nn_match_batch:
 // front end, matching, moments), trimmed rejection (batch_trim_select, batch_trim_moments), the per-pair reduction
-// (batch_finalize_kernel) and the start clouds of a batch with initial transforms (batch_init_kernel).  The batched neighbours and
+// (batch_finalize_kernel), the evaluation of every pair at its present pose (batch_eval_moments) and the start clouds of a batch
+// with initial transforms (batch_init_kernel).  The batched neighbours and
 // normals (knn4_batch, normals_batch_kernel) live with the single-pair ones in icp_k_plane.hip.  Reference statements: the loop a
 // pair runs is src/ICP_point_to_point.cu:295-423 / src/ICP_point_to_plane.cu:517-631; the kernels restate nn_match_kernel,
 // moments_kernel and transform_error_kernel (icp_k_dense.hip) per work item.
 #include "icp_device.h"
+#include "../../include/icp_mi355x_diag.h"
 #include <math.h>
 #include <stdlib.h>
 #include <cstring>
@@ -396,6 +398,109 @@ hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st)
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     hipLaunchKernelGGL(batch_finalize_kernel, dim3(a.n_pairs), dim3(256), 0, st, a.pairs, a.mode, (const double*)a.partials,
                        plane ? ICP_MOM_B + 5 : ICP_MOM_SQQ, a.mom);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// evaluation (icp_batch_evaluate): how well every pair is registered where its moving cloud stands -- kept count, squared
+// distances, and the sums a 6 x 6 information matrix is assembled from.  Three launches, none of which writes anything the loop
+// reads again:
+//   nn_match_batch<F, POINT, true, true>   the deferred matching instantiation, mode BATCH_MATCH alone: P is only read; the loop's
+//                                          own idx and winning distance, into evaluation-only buffers
+//   batch_eval_moments                     one block per work item: kept = d <= thr[pair] (thr == NULL: everything), marks idx, forms
+//                                          the terms of the ICP_EVAL_* slots
+//   batch_finalize_kernel                  as ever, into an evaluation-only vector per pair
+// batch_trim_moments' block shape: wave 0 alone carries data, waves 1-3 add zeros, block_sum_store writes the whole row (slot 0
+// included).  Every term is formed in double from the widened coordinates; a pair's bits depend on that pair and its threshold alone.
+//   both metrics: ICP_EVAL_SD = |q - p|^2 with the differences in double (the front end's error arithmetic), ICP_EVAL_CNT = 1
+//   point-to-point: ICP_EVAL_SQ = q, ICP_EVAL_SQQ = the upper triangle of q q^T
+//   point-to-plane: ICP_MOM_C .. + 20 = cn cn^T, cn = (p x n, n) -- the statements of a plane pass's C, restated here so that the
+//     loop's kernels keep their listings
+// ------------------------------------------------------------------------------------------------
+template <int METRIC> struct BatchEvalAcc { static constexpr int N = (METRIC == ICP_POINT_TO_POINT) ? ICP_EVAL_SQQ + 6 : ICP_MOM_C + 21; };
+
+template <typename F, int METRIC>
+__global__ __launch_bounds__(NN_BLOCK) void batch_eval_moments(const BatchItem* __restrict__ items, const BatchPair* __restrict__ pairs,
+                                                               const int* __restrict__ mode, const F* __restrict__ P, long long p_plane,
+                                                               const F* __restrict__ Q, const F* __restrict__ Nrm, long long q_plane,
+                                                               int32_t* __restrict__ idx, const F* __restrict__ dist,
+                                                               const F* __restrict__ thr, double* __restrict__ partials)
+{
+    constexpr int NACC = BatchEvalAcc<METRIC>::N;
+    static_assert(ICP_EVAL_SD == 0 && ICP_EVAL_CNT == 1 && NACC <= ICP_NMOM, "the row is written from its first slot on");
+    const BatchItem it = items[blockIdx.x];
+    if (!(mode[it.pair] & BATCH_MATCH)) return;   // the pair is not evaluated: nothing was matched for it
+    const BatchPair pr = pairs[it.pair];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    if (w == 0 && lane < it.count) {
+        const long long gi = pr.p_off + it.first + lane;
+        const F b = dist[gi];
+        const int j = idx[gi];   // in [0, m): the matching launch wrote it
+        const bool kept = thr == nullptr || b <= thr[it.pair];
+        if (!kept) {
+            idx[gi] = j | BATCH_IDX_REJECTED;   // (a rejected point adds nothing: every accumulator stays 0, the count included)
+        } else {
+            const F* Qx = Q + pr.q_off;
+            const F* Qy = Qx + q_plane;
+            const F* Qz = Qx + 2 * q_plane;
+            const double px = (double)P[gi], py = (double)P[p_plane + gi], pz = (double)P[2 * p_plane + gi];
+            const double qx = (double)Qx[j], qy = (double)Qy[j], qz = (double)Qz[j];
+            const double dx = qx - px, dy = qy - py, dz = qz - pz;
+            acc[ICP_EVAL_SD] = dx * dx + dy * dy + dz * dz;
+            acc[ICP_EVAL_CNT] = 1.0;
+            if constexpr (METRIC == ICP_POINT_TO_POINT) {
+                acc[ICP_EVAL_SQ + 0] = qx; acc[ICP_EVAL_SQ + 1] = qy; acc[ICP_EVAL_SQ + 2] = qz;
+                acc[ICP_EVAL_SQQ + 0] = qx * qx; acc[ICP_EVAL_SQQ + 1] = qx * qy; acc[ICP_EVAL_SQQ + 2] = qx * qz;
+                acc[ICP_EVAL_SQQ + 3] = qy * qy; acc[ICP_EVAL_SQQ + 4] = qy * qz; acc[ICP_EVAL_SQQ + 5] = qz * qz;
+            } else {
+                const F* Nx = Nrm + pr.q_off;
+                const double nx = (double)Nx[j], ny = (double)Nx[q_plane + j], nz = (double)Nx[2 * q_plane + j];
+                double cn[6];
+                cn[0] = py * nz - pz * ny;
+                cn[1] = pz * nx - px * nz;
+                cn[2] = px * ny - py * nx;
+                cn[3] = nx; cn[4] = ny; cn[5] = nz;
+                int o = ICP_MOM_C;
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int c = a; c < 6; ++c) acc[o++] += cn[a] * cn[c];
+            }
+        }
+    }
+    block_sum_store<NACC, NN_BLOCK>(acc, partials + (size_t)blockIdx.x * ICP_NMOM);
+}
+
+hipError_t launch_batch_evaluate(const BatchEvalArgs& a, hipStream_t st)
+{
+    if (a.n_items <= 0 || a.n_pairs <= 0) return hipSuccess;
+    const bool plane = a.metric == ICP_POINT_TO_PLANE;
+    if (plane && !a.N_soa) return hipErrorInvalidValue;
+    if (!a.idx || !a.dist || !a.partials || !a.mom) return hipErrorInvalidValue;
+    // (the matching launch reads neither rt nor idx_prev without BATCH_APPLY, and neither the normals nor thr when deferred)
+#define ICP_LAUNCH_BATCH_EVAL(F, MET)                                                                                            \
+    do {                                                                                                                         \
+        hipLaunchKernelGGL((nn_match_batch<F, ICP_POINT_TO_POINT, true, true>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, \
+                           a.pairs, a.mode, (const RT<F>*)nullptr, (F*)const_cast<void*>(a.P_soa), a.p_plane, (const F*)a.Q_soa,  \
+                           (const F*)nullptr, a.q_plane, (const int32_t*)nullptr, a.idx, a.partials, (const F*)nullptr,           \
+                           (F*)a.dist);                                                                                           \
+        hipLaunchKernelGGL((batch_eval_moments<F, MET>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs, a.mode,        \
+                           (const F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)a.N_soa, a.q_plane, a.idx,                  \
+                           (const F*)a.dist, (const F*)a.thr, a.partials);                                                        \
+    } while (0)
+    if (a.precision == ICP_F64) {
+        if (plane) ICP_LAUNCH_BATCH_EVAL(double, ICP_POINT_TO_PLANE); else ICP_LAUNCH_BATCH_EVAL(double, ICP_POINT_TO_POINT);
+    } else {
+        if (plane) ICP_LAUNCH_BATCH_EVAL(float, ICP_POINT_TO_PLANE); else ICP_LAUNCH_BATCH_EVAL(float, ICP_POINT_TO_POINT);
+    }
+#undef ICP_LAUNCH_BATCH_EVAL
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(batch_finalize_kernel, dim3(a.n_pairs), dim3(256), 0, st, a.pairs, a.mode, (const double*)a.partials,
+                       plane ? ICP_MOM_C + 20 : ICP_EVAL_SQQ + 5, a.mom);
     return hipGetLastError();
 }
 

@@ -413,6 +413,30 @@ struct BatchPassArgs {
     void* tau;                 // F[n_pairs], +inf from the host for the pairs that are not trimmed (only with trim_rank)
 };
 hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st);
+// evaluation of every pair whose mode is BATCH_MATCH at its present pose (icp_batch_evaluate): the deferred matching launch
+// (point-to-point instantiation whatever the metric, P only read) -> idx, dist; batch_eval_moments: kept = d <= thr[pair], rejected
+// matches marked in idx, the ICP_EVAL_* terms of the kept ones -> partials; batch_finalize_kernel -> mom[pair][ICP_NMOM] (pairs of
+// mode 0 untouched).  Three launches.  Every buffer written here is the evaluation's own: never one of BatchPassArgs.
+struct BatchEvalArgs {
+    int precision;             // ICP_F32 / ICP_F64
+    int metric;                // ICP_POINT_TO_POINT: sum q, sum q q^T; ICP_POINT_TO_PLANE: C (ICP_MOM_C .. + 20)
+    const BatchItem* items;
+    int n_items;
+    const BatchPair* pairs;
+    int n_pairs;
+    const int* mode;           // int[n_pairs]: BATCH_MATCH for a pair to evaluate, else 0
+    const void* P_soa;         // the moving clouds as they stand (read only)
+    long long p_plane;
+    const void* Q_soa;         // the models
+    const void* N_soa;         // point-to-plane: the model normals, laid out as Q_soa (else NULL)
+    long long q_plane;
+    const void* thr;           // NULL (every match is kept), or F[n_pairs]: the squared distance of the evaluation (+inf: everything)
+    int32_t* idx;              // [p_plane]: the matches, BATCH_IDX_REJECTED above the index of a match that was not kept
+    void* dist;                // F[p_plane]: every point's winning squared distance
+    double* partials;          // [n_items][ICP_NMOM]
+    double* mom;               // [n_pairs][ICP_NMOM]
+};
+hipError_t launch_batch_evaluate(const BatchEvalArgs& a, hipStream_t st);
 // the start cloud of a batch that holds initial transforms, in one launch over the same items: P[pair] = apply_rt(rt0[pair],
 // P0[pair]), or P0[pair]'s bytes where kind[pair] == BATCH_INIT_COPY; nonfinite[pair] (int[n_pairs], zero before the launch)
 // becomes 1 where a transformed point of the pair has a NaN or an infinite coordinate.  The padding of P is not written.

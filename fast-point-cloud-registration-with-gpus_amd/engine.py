@@ -625,6 +625,44 @@ class Batch:
         """per pair, a bool per moving point: its match of the last pass that contributed to T was kept"""
         return self._inliers(self._lib.icp_batch_loop_inliers, "icp_batch_loop_inliers")
 
+    def evaluate(self, max_distance=None, metric=capi.ICP_POINT_TO_POINT, want_matches=False):
+        """how well every pair is registered where its moving cloud stands (icp_batch_evaluate: after begin the start cloud, after
+        run the moved one; the loop does not notice).  max_distance: a scalar for every pair, one value per pair (inf: every match of
+        that pair counts), or None (every match counts) -- the evaluation's own distance, not the batch's gate.  One dict per pair:
+        status, inliers, fitness (inliers / n), rmse (over the inliers), information (6 x 6 float64, order rx ry rz tx ty tz: the
+        metric's Gauss-Newton matrix over the inliers); with want_matches also idx and inliers_mask (bool)."""
+        md = None
+        if max_distance is not None:
+            a = np.asarray(max_distance, dtype=np.float64)
+            if a.ndim == 0:
+                a = np.full(self.count, float(a))
+            md = np.ascontiguousarray(a)
+            if md.shape != (self.count,):
+                raise ValueError("one evaluation distance per pair (or a scalar)")
+        total = int(self._moff[-1])
+        status, inl = np.zeros(self.count, dtype=np.intc), np.zeros(self.count, dtype=np.int32)
+        fit, rmse, info = np.zeros(self.count), np.zeros(self.count), np.zeros((self.count, 6, 6))
+        idx = np.zeros(total, dtype=np.int32) if want_matches else None
+        mask = np.zeros(total, dtype=np.uint8) if want_matches else None
+        pd, pi32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        capi.check(self._lib.icp_batch_evaluate(self._h, int(metric), md.ctypes.data_as(pd) if md is not None else None,
+                                                status.ctypes.data_as(C.POINTER(C.c_int)), inl.ctypes.data_as(pi32), fit.ctypes.data_as(pd),
+                                                rmse.ctypes.data_as(pd), info.ctypes.data_as(pd),
+                                                idx.ctypes.data_as(pi32) if want_matches else None,
+                                                mask.ctypes.data_as(C.POINTER(C.c_uint8)) if want_matches else None), "icp_batch_evaluate")
+        out = [dict(status=int(status[b]), inliers=int(inl[b]), fitness=float(fit[b]), rmse=float(rmse[b]), information=info[b].copy())
+               for b in range(self.count)]
+        if want_matches:
+            for b, (i, m) in enumerate(zip(self._split(idx), self._split(mask.astype(bool)))):
+                out[b]["idx"], out[b]["inliers_mask"] = i, m
+        return out
+
+    def diag_eval_moments(self, b):
+        """the ICP_NMOM evaluation vector of pair b from the latest evaluate() (icp_diag_batch_eval_moments; slots capi.EVAL_*)"""
+        mom = np.zeros(capi.ICP_NMOM, dtype=np.float64)
+        capi.check(self._lib.icp_diag_batch_eval_moments(self._h, int(b), mom.ctypes.data_as(C.POINTER(C.c_double))), "icp_diag_batch_eval_moments")
+        return mom
+
 
 # ---- host-only helpers (no device) -------------------------------------------------------------
 def solve_point_to_point(mom):

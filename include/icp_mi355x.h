@@ -37,7 +37,7 @@ extern "C" {
 #endif
 
 #define ICP_ABI_VERSION 2 /* 2: icp_result gained seconds_host / seconds_setup, icp_loop_phase_seconds; later the icp_batch_* entry
-                           * points were added (new symbols only: nothing that existed changed) */
+                           * points were added, icp_batch_evaluate among them (new symbols only: nothing that existed changed) */
 
 /* return codes */
 #define ICP_OK 0
@@ -210,7 +210,9 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  * The reference registers one pair per program run (src/ICP_point_to_point.cu:295-423, src/ICP_point_to_plane.cu:517-631); a
  * loop of icp_point_to_point / icp_point_to_plane over many small pairs pays a whole iteration's launch and round trip (and,
  * for point-to-plane, a neighbour search of its own) per pair.  A batch keeps all its pairs on the device and
- * runs ONE matching launch + ONE reduction launch + ONE 32-double-per-pair download per step for every pair still running.
+ * runs ONE matching launch + ONE reduction launch + ONE 32-double-per-pair download per step for every pair still running.  It
+ * offers both metrics, and per pair a maximum correspondence distance, an initial transform, trimmed rejection and an evaluation
+ * of the pose it stands at (fitness, inlier RMSE, information matrix).
  *   - pair b = moving points [moving_off[b], moving_off[b+1]) and model points [model_off[b], model_off[b+1]) of the
  *     concatenated AoS arrays, element type = precision (as icp_set_model).  Offsets: count+1 int64, starting at 0, strictly
  *     increasing (every cloud >= 1 point, <= ICP_BATCH_MAX_POINTS).  Anything else, a NaN or an infinite coordinate
@@ -316,7 +318,44 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *         transform.
  *       cost: a pair's tau is known only when every one of its points has been matched, so a step of a batch that trims at
  *         least one pair runs four launches in place of two (matching, selection, sums, reduction) and still one download.
- *     Not gated, not trimmed and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the
+ *   - evaluation (icp_batch_evaluate): did pair p register, and how well is it constrained?  Per pair the fitness (the share of
+     its moving points with a model point within a distance of the caller's choosing), the inlier RMSE and the 6 x 6
+     information matrix a pose-graph optimiser takes beside T -- measured where the pair's moving cloud stands on the device,
+     exactly the cloud icp_batch_get_moving returns: after icp_batch_begin the start cloud (initial transform included: K
+     candidate poses of one pair, uploaded K times, are scored with no ICP iteration), after icp_batch_run the cloud moved by
+     the `passes` motions icp_batch_state's T describes, for an ended pair the final cloud.
+       matching: the batch's own search.  idx is the bit-exact nearest neighbour in [0, m), the lowest index on ties; d is the
+         winning squared distance the matching holds -- (dx*dx + dy*dy) + dz*dz, every operation rounded separately in the
+         batch's precision F; nothing is recomputed.
+       gate: max_dist follows icp_batch_set_max_distance's rules -- count doubles, each > 0 or +INFINITY, thr = (F)(max_dist *
+         max_dist) with the product formed in double and rounded once, a match kept iff d <= thr (a point on the threshold is
+         kept); a NaN, a value <= 0 or -INFINITY is ICP_ERR_INVALID, the message names the pair, and nothing is launched.  NULL:
+         every match is kept.  The batch's own gate, its trim shares and tau are neither read nor changed.
+       evaluation vector: ICP_NMOM doubles per pair (slots ICP_EVAL_*, icp_mi355x_diag.h), every term formed in double from
+         the widened coordinates of the kept matches, added per work item and then per pair in a fixed order, no
+         floating-point atomics: a pair's bits depend on that pair and its threshold alone.  Both metrics: SD = sum |q[idx] -
+         p|^2 (differences in double) and CNT.  ICP_POINT_TO_POINT: sum q and the upper triangle of sum q q^T, q the matched
+         model point.  ICP_POINT_TO_PLANE: sum cn cn^T, cn = (p x n[idx], n[idx]), the statements and slots of a plane pass's
+         C; it needs the batch's normals (ICP_ERR_INVALID without them).
+       outputs, formed on the host in double from that vector and nothing else (every pointer may be NULL; per pair):
+         status_out 1, inliers_out = (int)CNT, fitness_out = CNT / (double)n, rmse_out = sqrt(SD / CNT) or 0.0 where CNT = 0,
+         info_out 36 doubles: the symmetric row-major 6 x 6 in the order (rx, ry, rz, tx, ty, tz) of icp_solve_point_to_plane's
+         x, written in full.  Point-to-plane: C, mirrored.  Point-to-point: sum over the kept q = (x, y, z) of g1 g1^T + g2 g2^T
+         + g3 g3^T with g1 = (0, z, -y, 1, 0, 0), g2 = (-z, 0, x, 0, 1, 0), g3 = (y, -x, 0, 0, 0, 1) -- I00 = Syy + Szz, I11 =
+         Sxx + Szz, I22 = Sxx + Syy, I01 = -Sxy, I02 = -Sxz, I12 = -Syz, I04 = -Sz, I05 = Sy, I13 = Sz, I15 = -Sx, I23 = -Sy,
+         I24 = Sx, I03 = I14 = I25 = 0, I33 = I44 = I55 = CNT, the rest of the lower-right block 0: each entry at most one
+         addition of two slots.  idx_out (always in [0, m)) and mask_out (1 = the match was kept) are concatenated as the
+         moving clouds.
+       pair status: a pair whose start cloud icp_batch_begin refused (not finite after its initial transform) is not evaluated:
+         status ICP_ERR_INVALID and zeros throughout.  Every other pair is evaluated and gets ICP_OK, ended pairs and pairs that
+         failed with ICP_ERR_SINGULAR or ICP_ERR_EMPTY included.
+       errors: ICP_ERR_STATE before icp_batch_begin, after any call that discards the loop and while the context has a pending
+         pass; ICP_ERR_INVALID for a null batch or an unknown metric.
+       the loop does not notice: the call neither discards nor advances it, and every later icp_batch_run, _state, _get_*,
+         _loop_*, icp_diag_batch_moments and icp_diag_batch_trim answers with the bytes it would have given without the call.
+       cost: three launches (the loop's deferred matching with nothing applied, the decision and the terms, the reduction) and
+         one download of 32 doubles per pair, plus the indices when idx_out or mask_out is given.
+     Not gated, not trimmed and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the
  *     multi-GPU sums -- a single pair that needs any of them is a batch of one.  Trimming is the only rejection by rank: there
  *     is no other percentile rejection (none by a multiple of the median or of the standard deviation of the distances). */
 typedef struct icp_batch icp_batch;
@@ -350,6 +389,10 @@ int icp_batch_set_max_distance(icp_batch* b, const double* max_dist);
 int icp_batch_set_trim(icp_batch* b, const double* keep_ratio);
 /* count x 16 doubles, one row-major 4x4 per pair (the layout of icp_result.T), or NULL = no initial transforms */
 int icp_batch_set_initial_transforms(icp_batch* b, const double* T16);
+/* per-pair fitness, inlier RMSE and information matrix where the moving clouds stand (above); max_dist: count doubles or NULL;
+ * every output pointer may be NULL: status / inliers / fitness / rmse 1 per pair, info 36 per pair, idx / mask 1 per moving point */
+int icp_batch_evaluate(icp_batch* b, int metric, const double* max_dist, int* status_out, int32_t* inliers_out, double* fitness_out,
+                       double* rmse_out, double* info_out, int32_t* idx_out, uint8_t* mask_out);
 /* 1 byte per moving point, concatenated as the moving clouds: 1 = that point's match was kept */
 int icp_batch_get_inliers(icp_batch* b, uint8_t* mask_out);   /* each pair's most recent matching pass (as icp_batch_get_indices) */
 int icp_batch_loop_inliers(icp_batch* b, uint8_t* mask_out);  /* each pair's last contributing pass (as icp_batch_loop_indices) */

@@ -83,6 +83,20 @@ int icp_diag_batch_moments(icp_batch* b, int pair, double* out32);
  * and *rank = K (n for a pair that is not trimmed).  Either pointer may be NULL.  The per-pair threshold buffer is copied down
  * on demand: nothing is added to a step's download.  ICP_ERR_STATE before the pair's first completed matching pass. */
 int icp_diag_batch_trim(icp_batch* b, int pair, double* tau_sq, int* rank);
+/* The evaluation vector of pair `pair` from the latest icp_batch_evaluate (icp_mi355x.h): ICP_NMOM doubles, the only data the
+ * call's per-pair outputs (inliers, fitness, rmse, information) are formed from.  Every term is formed in double from the widened
+ * coordinates of the kept matches, added per work item and then per pair in a fixed order.  Slots, q = the matched model point,
+ * p = the moving point, n = the model normal at the match:
+ *   ICP_EVAL_SD   sum |q - p|^2, the differences formed in double        ICP_EVAL_CNT  the kept count
+ *   ICP_POINT_TO_POINT:  ICP_EVAL_SQ (3) sum q;  ICP_EVAL_SQQ (6) sum q_x q_x, q_x q_y, q_x q_z, q_y q_y, q_y q_z, q_z q_z
+ *   ICP_POINT_TO_PLANE:  ICP_MOM_C .. ICP_MOM_C + 20  sum cn cn^T, upper triangle row-major, cn = (p x n, n): a plane pass's C
+ * Every other slot is 0; a pair that was not evaluated (status ICP_ERR_INVALID) has an all-zero vector.  ICP_ERR_STATE before the
+ * batch's first evaluation; a refused icp_batch_evaluate leaves the vectors of the evaluation before it. */
+#define ICP_EVAL_SD 0
+#define ICP_EVAL_CNT 1
+#define ICP_EVAL_SQ 2
+#define ICP_EVAL_SQQ 5
+int icp_diag_batch_eval_moments(icp_batch* b, int pair, double* out32);
 
 #ifdef __cplusplus
 }

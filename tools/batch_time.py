@@ -3,7 +3,7 @@
 for all pairs) against a loop of Context.point_to_point / point_to_plane over the same pairs (GPU box).
 
   python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE] [--only CASE,CASE] [--max-distance V] [--trim R]
-                              [--label TEXT] [--init | --premoved]
+                              [--label TEXT] [--init | --premoved] [--evaluate]
 
 Cases, --metric point: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids
 (make_model_gpu, tol 1e-6); 16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  --metric plane: the fp32 case sets and the
@@ -33,6 +33,11 @@ outside the timed region -- with the inverse pose as every pair's initial transf
 the timed region) and no initial transform, through the same Batch route (create, begin, run, per-pair state), so the two differ
 by the start-cloud launch of icp_batch_begin and its synchronisation alone and run the same bits.  Under either option the
 sequential side registers the pre-moved clouds, and every pair must run the same passes on both sides.
+
+--evaluate times one evaluation of every case's batch (Batch.evaluate: three launches and one download, without and with the
+matches) beside one step of the same batch (Batch.run(1): the first step after begin, which matches only, and the second, which
+applies and matches) and the whole batched registration (batched_s, as in the rows without the option); nothing sequential is
+run.  A build without icp_batch_evaluate (ICP_LIB_PATH) reports the steps and the registration alone (evaluate_s null).
 """
 import argparse
 import json
@@ -94,6 +99,7 @@ def main():
     ap.add_argument("--label", default="", help="copied into every row")
     ap.add_argument("--init", action="store_true", help="the batched side starts from a far pose with the inverse pose as initial transform")
     ap.add_argument("--premoved", action="store_true", help="the baseline of --init: the far clouds moved back on the host, no initial transform, same route")
+    ap.add_argument("--evaluate", action="store_true", help="time one evaluation of every case's batch beside one step of the same batch")
     ap.add_argument("--profile-case", default="", help="run only this case's batched registration, once after a warm-up (for a kernel trace)")
     a = ap.parse_args()
     import torch  # noqa: F401  (torch first: it bundles the HIP runtime)
@@ -157,6 +163,41 @@ def main():
                         res = run_batched()
                     print(json.dumps(dict(case=name, pairs=len(pairs), pair_iterations=sum(r.passes for r in res),
                                           steps=max(r.passes for r in res) + 1)), flush=True)
+                continue
+
+            if a.evaluate:
+                med = lambda v: float(np.median(v))
+                have = hasattr(ctx._lib, "icp_batch_evaluate")
+                with ctx.batch(pairs) as bt:
+                    if plane:
+                        bt.set_model_normals(normals) if normals is not None else bt.estimate_normals()
+
+                    def timed(fn):
+                        t0 = time.perf_counter()
+                        fn()
+                        return time.perf_counter() - t0
+
+                    def steps():   # (first step, second step) of a fresh loop
+                        bt.begin(max_iter=it, tol=tol, metric=metric)
+                        return timed(lambda: bt.run(1)), timed(lambda: bt.run(1))
+
+                    steps()
+                    st = [steps() for _ in range(a.reps)]
+                    ev, evm = [], []
+                    if have:   # where the second step left the clouds
+                        bt.evaluate(metric=metric, want_matches=True)   # (allocates the evaluation's buffers)
+                        ev = [timed(lambda: bt.evaluate(metric=metric)) for _ in range(a.reps)]
+                        evm = [timed(lambda: bt.evaluate(metric=metric, want_matches=True)) for _ in range(a.reps)]
+                run_batched()
+                tb = [timed(run_batched) for _ in range(a.reps)]
+                row = dict(case=name, pairs=len(pairs), points=int(pairs[0][0].shape[0]), batched_s=med(tb), batched_s_min=float(min(tb)),
+                           batched_s_max=float(max(tb)), first_step_s=med([x for x, _ in st]), step_s=med([y for _, y in st]),
+                           step_s_min=float(min(y for _, y in st)), step_s_max=float(max(y for _, y in st)),
+                           evaluate_s=med(ev) if have else None, evaluate_s_min=float(min(ev)) if have else None,
+                           evaluate_s_max=float(max(ev)) if have else None, evaluate_matches_s=med(evm) if have else None,
+                           reps=a.reps, pairs_stopping_apart=0, label=a.label)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
                 continue
 
             def batched():
