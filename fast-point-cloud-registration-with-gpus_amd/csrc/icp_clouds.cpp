@@ -235,8 +235,8 @@ int ensure_work_buffers(icp_ctx* c)
     const icp::NNPlan& pl = c->plan;
     // the moving cloud's order was judged when it was uploaded, possibly before the model was known: now that the plan is
     // fixed, judge it again if the kernel works on groups of another size than the one assumed then
-    if (c->prec == ICP_F32 && c->have_moving && c->n > 128 && pl.sparse && c->moving_group != 0 && c->moving_group != (pl.row == 64 ? 64 : 128) && c->P0.p)
-        if (int rc = decide_moving_order(c, c->P0.p, pl.row == 64 ? 64 : 128)) return rc;
+    if (c->prec == ICP_F32 && c->have_moving && c->n > 128 && icp::nn_is_sparse(pl) && c->moving_group != 0 && c->moving_group != icp::nn_moving_group(pl) && c->P0.p)
+        if (int rc = decide_moving_order(c, c->P0.p, icp::nn_moving_group(pl))) return rc;
     if (before.n_pad != pl.n_pad || before.m_pad != pl.m_pad) c->resident_refused = false;  // another geometry: ask again
     if (before.n_pad != pl.n_pad || before.blocks_x != pl.blocks_x) c->rows_format = -1;     // (rows that were not in use keep old tags: wiped before the next launch)
     const size_t es = icp::elem_size(c->prec);
@@ -373,8 +373,7 @@ int icp_set_model(icp_ctx* c, const void* xyz, int m, int precision)
     // hierarchy by a cloud of more rows than shared 8-wave blocks serve, flat by a smaller one, and the model is set before the cloud is
     // known: it gets the upper levels and the records whenever SOME cloud would ask for them.  Round 3 built them by the plan of a
     // one-row cloud; a 65 536-point grid against itself then failed with "invalid argument" at its first pass.)
-    const int group2 = (precision == ICP_F32 && m > 0 && (icp::nn_plan(128, m, precision, c->num_cus, c->tune).hier ||
-                                                          icp::nn_plan(1 << 22, m, precision, c->num_cus, c->tune).hier)) ? 512 : 0;
+    const int group2 = icp::nn_model_may_be_hier(m, precision, c->tune) ? 512 : 0;
     const bool short_setup = precision == ICP_F32 && m > 0 && m <= icp_ctx::kPrepSmallMax && group2 == 0;
     const int m_pad = icp::pad_model(m);
     icp::PrepBuffers pb{};
@@ -490,7 +489,7 @@ int icp_set_moving(icp_ctx* c, const void* xyz, int n, int precision)
         // judged on the groups the matching kernel will work on (rows of 64 or of 128 points: nn_plan's rule, overrides
         // included); with no model resident yet the plan assumes one of the moving cloud's size -- ensure_work_buffers looks again
         const icp::NNPlan guess = icp::nn_plan(n, c->have_model && c->m > 0 ? c->m : n, precision, c->num_cus, c->tune);
-        if (int rc = decide_moving_order(c, c->P.p, (guess.sparse && guess.row == 64) ? 64 : 128, short_setup)) return rc;
+        if (int rc = decide_moving_order(c, c->P.p, icp::nn_moving_group(guess), short_setup)) return rc;
     }
     c->have_moving = true;
     c->moving_is_pristine = false;

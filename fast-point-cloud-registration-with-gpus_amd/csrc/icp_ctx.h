@@ -234,7 +234,7 @@ struct __attribute__((visibility("hidden"))) icp_ctx {   // (the public header o
     bool host_reduce() const { return !comm && mom_dev == (double*)mom_own.p && h_mom_partials != nullptr && (plan.blocks_x <= host_rows_max || plan.n == 0); }
     int host_rows_max = kHostRowsMax;   // (ICP_HOST_ROWS_MAX: A/B runs)
     // the plan half of "this plan's rows are added up inside the launch" (the buffers: ensure_work_buffers; the rest: fin_in_launch)
-    bool sums_in_launch(const icp::NNPlan& pl) const { return pl.sparse && pl.version == 2 && pl.row != 64 && pl.blocks_x > host_rows_max && icp::nn_can_fuse_tail(pl); }
+    bool sums_in_launch(const icp::NNPlan& pl) const { return icp::nn_can_sum_rows_in_launch(pl) && pl.blocks_x > host_rows_max && icp::nn_can_fuse_tail(pl); }
     icp::NNPlan plan{};
     LoopState loop;
 };

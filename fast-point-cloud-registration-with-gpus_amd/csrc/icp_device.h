@@ -396,13 +396,4 @@ struct NNFuse {
         if (slot_ < fuse.tlog_cap) fuse.tlog[slot_] = (long long)wall_clock64();                                   \
     }
 
-// geometry of the sparse kernels' blocks and hit lists (the launchers in icp_launch.hip size their rounds by these)
-constexpr int SP_NW = 16;                       // waves per block (the default; NWS = 8 is the other instantiation)
-constexpr int SP_HCAP = 4096;                   // hit-list entries of the hierarchical search = chunks per round (SP_NW * 64 * passes <= this)
-constexpr int SP_MAX_PASSES = SP_HCAP / (SP_NW * 64);
-// flat search (models below 2^19 points = 65 536 chunks): the list holds 16-bit chunk numbers, twice as many in the same
-// 16 KB -- a model of up to 65 536 points is one round of the find (Bunny.csv: 5040 chunks, two rounds with 4096 entries)
-constexpr int SP_HCAP_FLAT = 2 * SP_HCAP;
-constexpr int R64_NW = 8;                       // rows of 64 points: waves per block (16 with the device to itself)
-
 }  // namespace icp

@@ -7,7 +7,8 @@
 //   icp_k_batch.hip   nn_match_batch (many pairs per launch), trimmed rejection, per-pair finalize, initial transforms
 //   icp_k_plane.hip   kNN(4) + normals, OS1 decode + conversion
 //   icp_k_setup.hip   duplicates, spatial order, boxes / samples / records, row order + roles, the control block of a pass
-//   icp_launch.hip    the plan (nn_plan) and the dispatch (launch_nn): host code only
+//   icp_launch.hip    the dispatch (launch_nn): host code only
+//   icp_plan.cpp      the plan a launch follows (icp_plan.h: nn_plan, nn_launch_shape): kernel family, geometry, waves -- no HIP
 // Internal to libicp_mi355x.so; the public surface is include/icp_mi355x.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,74 +16,9 @@
 #include <stdint.h>
 
 #include "../../include/icp_mi355x.h"
+#include "icp_plan.h"
 
 namespace icp {
-
-// Internal HBM layout of a cloud: SoA, x[pad] | y[pad] | z[pad], `pad` >= count.
-//   moving cloud: pad = multiple of NN_POINT_ALIGN (whole NN blocks, no bounds checks in the hot loop)
-//   model  cloud: pad = multiple of NN_CHUNK; entries [m, m_pad) replicate point m-1, which can
-//                 never win a first-minimum search against its lower-index original.
-constexpr int NN_BLOCK = 256;        // threads per matching block (4 wave64)
-constexpr int NN_POINT_ALIGN = 1024; // moving-point padding granule
-constexpr int NN_CHUNK = 16;         // model points per index-tracking chunk
-
-struct NNPlan {
-    int precision;  // ICP_F32 / ICP_F64
-    int n, m;       // real counts
-    int n_pad, m_pad;
-    int pts_per_thread; // T
-    int blocks_x;       // n_pad / (NN_BLOCK * T)
-    int splits;         // S: model segments scanned by different blocks (grid.y)
-    int seg_len;        // model points per segment (multiple of NN_CHUNK)
-    int version;        // 1: generic kernel (dense fp64, A/B), 2: packed fp32 kernels, 3: fp64 on the sparse structure (rows of 64)
-    int chunk;          // index-tracking chunk of the launched kernel
-    int cull;           // the packed kernel may use the seeded-bound / xy early-out variant
-    int sparse;         // the geometry is the sparse kernel's (16-wave blocks of 128 moving points; needs chunk boxes)
-    int hier;           // sparse kernel: two-level search (boxes of 64 chunks first) -- large models
-    int row;            // sparse geometry: moving points per block row -- 128 (nn_match_sparse, 16 waves) or 64 (nn_match_row64, 8 waves)
-    int nw;             // rows of 128: waves per block -- 16, or 8 (two blocks per CU: clouds whose rows outnumber the CUs; launches with a fused tail),
-                        // or 4 (four per CU: the hierarchical search of clouds with rows for several rounds of blocks)
-    int share_blocks;   // rows of 128, 8 waves, one launch per pass: blocks of a launch (> blocks_x: the spare ones go to the heavy rows), or 0
-    int order;          // rows of 128, many more rows than the machine holds at once: the blocks of a launch take the rows heaviest first
-                        // (by the hits of the launch before) -- see launch_row_order
-};
-int nn_block_threads(const NNPlan& pl);
-
-// Every switch the plan and the launchers look at, read ONCE per context (icp_create -> nn_tuning_from_env): nothing on the
-// launch path scans the environment (the advisor's finding on round 3), and a test that wants another form creates another
-// context.  Defaults = production.  All of these select among forms that give the same bits (INTEGRATION.md lists them).
-struct NNTuning {
-    int sparse = 1;          // ICP_NN_SPARSE=0: the dense packed kernel (every pair executed; no boxes, no hierarchy)
-    int cull = 1;            // ICP_NN_CULL=0: ... without its seeded early-out
-    int row = 0;             // ICP_NN_ROW=64 / 128: force the row size of the sparse kernels
-    int waves64 = 0;         // ICP_NN_WAVES=16: rows of 64 points as 16-wave blocks (what icp_set_exclusive selects)
-    int waves128 = 0;        // ICP_NN_WAVES128=4 / 8 / 16: waves per block of the rows of 128
-    int cold8 = 1;           // ICP_NN_COLD8=0: a plan of 4-wave blocks runs its cold launches on 4 waves too
-    int hier = -1;           // ICP_NN_HIER=0 / 1: box hierarchy never / always (-1: by the model's size)
-    int order = 1;           // ICP_NN_ORDER=0 / 2: rows in index order / heaviest first also where the rows are few
-    int share = 1;           // ICP_NN_SHARE=0: no shared rows
-    int share_resident = 1;  // ICP_NN_SHARE_RESIDENT=0: a resident launch keeps one block per row
-    int speculate = 1;       // ICP_NN_SPECULATE=0: resident launches without their speculative hit list
-    int f64_sparse = 1;      // ICP_F64_SPARSE=0: ICP_F64 clouds on the dense thread-per-point kernel
-    int sort = -1;           // ICP_SORT=0 / 1: spatially sorted views never / always (-1: by the extent test)
-    // ICP_NN_PHASES=file[:pass[:slots[:wipe]]] -- per-wave phase stamps of the matching kernels (tools/phase_report.py); the
-    // context owns the log
-    long long* phase_log = nullptr;
-    long long phase_cap = 0;
-    int phase_pass = -1;
-    int phase_wipe = 0;
-};
-NNTuning nn_tuning_from_env();
-
-inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
-inline int pad_moving(int n) { return n <= 0 ? 0 : round_up(n, NN_POINT_ALIGN); }
-inline int pad_model(int m) { return m <= 0 ? 0 : round_up(m, NN_CHUNK); }
-
-// Choose the launch geometry.  `num_cus` comes from hipDeviceProp_t::multiProcessorCount.
-// force_dense != 0: the geometry of the dense packed kernel (every pair executed) even where the sparse kernel would run
-NNPlan nn_plan(int n, int m, int precision, int num_cus, const NNTuning& tune, int force_dense = 0);
-
-size_t elem_size(int precision);
 
 // the transform of the previous pass, fused into the front of the matching kernel (fp32 kernel only):
 // P_out <- R * P_in + t, err_rows[block_x] <- sum |p_new - q[idx_prev]|^2
@@ -137,7 +73,6 @@ struct NNFusedTransform {
     bool slot_valid = false;             // ... the previous pass wrote them
     bool slot_flip = false;              // ... which of the two planes of points this launch reads (it writes the other): 9 x n_pad floats in all
 };
-bool nn_can_fuse_transform(const NNPlan& pl);
 
 // inputs of the early-out ("cull") variant of the packed kernel.  Q_scan is a copy of the model whose
 // exact duplicates (same x,y,z as a LOWER index) are voided to +inf: such a point can never be the
@@ -246,7 +181,6 @@ constexpr int NN_ORDER_EXTRA = 4096;   // blocks of an ordered launch beyond its
 constexpr int NN_ORDER_CLASS_BITS = 1;
 constexpr int NN_ORDER_XCD_SHIFT = 4;
 constexpr int NN_ORDER_HEAD = 1024;    // rows (the heaviest) that may be split
-constexpr int NN_ROLE_ROW_BITS = 21, NN_ROLE_PART_BITS = 6;   // role = row | part << 21 | log2(parts) << 27
 // the hierarchical search fetches a hit from one 160-byte record per chunk (icp_kernels.hip, model_records_kernel)
 constexpr int NN_REC_WORDS = 40;
 size_t model_records_bytes(int m_pad);
@@ -339,7 +273,6 @@ struct NNTailArgs {
 constexpr int NN_FIN_GROUPS = 256;     // ranges of rows of an in-launch finalize, at most
 constexpr int NN_CROW = 16;            // doubles per compact row
 constexpr int NN_CROW_TAG_BITS = 16;   // low mantissa bits of slot 0 that carry the row's tag (mod 2^16)
-bool nn_can_fuse_tail(const NNPlan& pl);
 
 // matching: per (segment, point) partial minimum + index.  `ft` (optional) = fused transform,
 // `opt` (optional) = early-out inputs, `ta` (optional) = fused tail (then no partials are written).

@@ -59,7 +59,7 @@ bool fin_to_host(const icp_ctx* c) { return !c->comm && c->mom_dev == (double*)c
 bool use_compact_rows(const icp_ctx* c, const icp::NNPlan& pl, int metric, const double* rows)
 {
     // (fp32 only: the compact row spends mantissa bits on its tag, and the fp64 path is held to 1e-12 against src/ICP_CPU.c's arithmetic)
-    return c->prec == ICP_F32 && pl.sparse && metric == ICP_POINT_TO_POINT && rows == c->h_mom_partials;
+    return c->prec == ICP_F32 && icp::nn_is_sparse(pl) && metric == ICP_POINT_TO_POINT && rows == c->h_mom_partials;
 }
 
 // The two row formats keep their completion tags in different places of the same pinned buffer: when the format changes
@@ -337,7 +337,7 @@ int loop_enqueue_body(icp_ctx* c)
         icp::NNFusedTransform ft{L.H.R, L.H.t, (const int32_t*)c->idx[L.applied_idx].p, c->P2.p, err_rows};
         // every fused pass of the sparse kernels leaves its points and matches in slot order; the next one starts from them
         // (one level of coalesced loads instead of slot -> point -> seed -> model point), as the armed launches do
-        if (fused && tail && pl.sparse && pl.row != 64 && pl.splits == 1 && c->slot_state.ensure(9 * (size_t)pl.n_pad * sizeof(float)) == hipSuccess) {
+        if (fused && tail && icp::nn_keeps_slot_order(pl) && c->slot_state.ensure(9 * (size_t)pl.n_pad * sizeof(float)) == hipSuccess) {
             ft.slot_state = c->slot_state.p;
             ft.slot_valid = L.slot_written;
             ft.slot_flip = L.slot_flip;
@@ -429,7 +429,7 @@ int loop_complete_body(icp_ctx* c, int* done)
 bool mailbox_launch_possible(const icp_ctx* c)
 {
     const icp::NNPlan& pl = c->plan;
-    return c->h_mail && (c->relay || c->mail_in_bar) && c->fused_tail && pl.sparse && icp::nn_can_fuse_tail(pl) && c->have_scan_copy && c->use_boxes &&
+    return c->h_mail && (c->relay || c->mail_in_bar) && c->fused_tail && icp::nn_is_sparse(pl) && icp::nn_can_fuse_tail(pl) && c->have_scan_copy && c->use_boxes &&
            c->loop.active && !c->loop.H.done;
 }
 
@@ -558,7 +558,7 @@ bool can_reside(icp_ctx* c)
     // not -- one rank's waiting blocks would hold the CUs the other's rows are waited for on, the circular wait of can_arm)
     // ICP_DEBUG=shared_resident (tests: two hall-sized ranks, 2 x 256 half-CU blocks, known to fit together) lifts it.
     return c->resident && (!c->shares_device || c->debug_shared_resident) && (c->resident > 1 || pl.share_blocks == 0 || share_wants_resident(c)) &&
-           (c->prec == ICP_F32 || pl.version == 3) && !c->resident_refused && mailbox_launch_possible(c) && c->host_reduce() && !c->loop.pending;
+           (c->prec == ICP_F32 || pl.family == icp::NNFamily::Row64F64) && !c->resident_refused && mailbox_launch_possible(c) && c->host_reduce() && !c->loop.pending;
 }
 
 // returns ICP_OK with *fell_back = true when the resident kernel could not be launched (nothing has been done)

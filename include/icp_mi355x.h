@@ -138,7 +138,9 @@ int icp_get_indices(icp_ctx* ctx, int32_t* idx_out);        /* n int32: the most
  * receives the hipEvent time of the matching kernel(s) alone. */
 int icp_nn_match_resident(icp_ctx* ctx, float* kernel_ms);
 /* geometry of the last matching launch (the programs print it as the reference prints its Grid Size / Block Size,
- * src/CUDA/GPU_point_to_point_real.cu:237) */
+ * src/CUDA/GPU_point_to_point_real.cu:237).  threads: the block of a steady pass of the loop, not exclusive.  For ICP_F64 clouds
+ * on rows of 64 points it reports 512 although the launch takes 1024 wherever the rows do not outnumber the CUs (a value kept
+ * as callers have seen it). */
 int icp_nn_launch_info(icp_ctx* ctx, int* splits, int* blocks, int* threads, int* n_pad, int* m_pad);
 /* The caller owns the device (no other context of this or any other process keeps kernels resident on it): clouds of up to
  * 16 384 moving points (one row of 64 per CU) then run their rows as 16-wave blocks, one to a CU, instead of 8-wave blocks that
