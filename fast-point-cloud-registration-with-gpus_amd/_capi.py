@@ -104,6 +104,7 @@ SIGNATURES = {
     "icp_batch_set_max_distance": (_i, [_vp, _pd]),
     "icp_batch_set_initial_transforms": (_i, [_vp, _pd]),
     "icp_batch_set_trim": (_i, [_vp, _pd]),
+    "icp_batch_set_reciprocal": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_batch_get_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_batch_loop_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_batch_evaluate": (_i, [_vp, _i, _pd, _pi, _pi32, _pd, _pd, _pd, _pi32, C.POINTER(C.c_uint8)]),
@@ -130,6 +131,7 @@ SIGNATURES = {
     "icp_diag_loop_moments": (_i, [_vp, _pd, _pi]),
     "icp_diag_batch_moments": (_i, [_vp, _i, _pd]),
     "icp_diag_batch_trim": (_i, [_vp, _i, _pd, _pi]),
+    "icp_diag_batch_reverse": (_i, [_vp, _pi32]),
     "icp_diag_batch_eval_moments": (_i, [_vp, _i, _pd]),
     "icp_eigh3": (_i, [_pd, _pd, _pd]),
     "icp_synthetic_grid_f32": (_i, [_i, C.c_float, C.c_float, _vp]),

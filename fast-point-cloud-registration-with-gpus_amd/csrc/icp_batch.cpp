@@ -2,6 +2,8 @@
 // step ONE matching launch + ONE reduction launch + ONE download of ICP_NMOM doubles per pair for every pair still running.
 //
 //   step k:  [R, t + mode of every pair: H2D]  ->  nn_match_batch (icp_k_batch.hip: transform + error, match, moments per work item)
+//            [a batch that trims or holds a reciprocal pair: nn_match_batch<DEFER>  ->  nn_match_batch_rev (reciprocal)  ->
+//             batch_trim_select (trims)  ->  batch_trim_moments -- see the table below]
 //            ->  batch_finalize_kernel (per pair, fixed order)  ->  D2H count x ICP_NMOM  ->  sync
 //            ->  HostLoop::advance per pair that took part (error, stop rule, 3x3 solve or 6x6 solve)
 //
@@ -21,6 +23,19 @@
 // matched, so the steps of such a batch run deferred: nn_match_batch<.., DEFER> (matching, no decision)  ->  batch_trim_select
 // (tau = the K-th smallest distance, per pair)  ->  batch_trim_moments (the decision, with the gate's where there is one, and the
 // sums)  ->  batch_finalize_kernel: four launches, still one download.  A batch whose shares are all 1.0 runs the steps above.
+//
+// A batch may hold a reciprocity flag per pair (icp_batch_set_reciprocal): a reciprocal pair keeps a match only if the model
+// point's own nearest moving point, on the cloud the pass matched on, is that very point (rev[idx[i]] == i).  That decision needs
+// the reverse search of the whole pair, so the steps of such a batch run deferred as well: nn_match_batch<.., DEFER>  ->
+// nn_match_batch_rev (one block per model work item: rev)  ->  batch_trim_select (only if the batch also trims)  ->
+// batch_trim_moments<.., MUTUAL> (mutual && trim && gate, and the sums)  ->  batch_finalize_kernel: four launches, five with
+// trimming, still one download.  rev is consumed inside the step that wrote it (no ping-pong), and a pair's rows of it are
+// rewritten only when that pair matches.  A batch whose flags are all 0 runs the steps it ran without them.
+//
+//   batch kind             launches of a step
+//   any reciprocal pair    nn_match_batch<DEFER>, nn_match_batch_rev, [batch_trim_select,] batch_trim_moments<MUTUAL>, batch_finalize_kernel
+//   trims only             nn_match_batch<DEFER>, batch_trim_select, batch_trim_moments, batch_finalize_kernel
+//   gates only / plain     nn_match_batch, batch_finalize_kernel
 //
 // A batch answers how well every pair is registered where it stands (icp_batch_evaluate): the loop's own matching -- the deferred
 // instantiation with mode BATCH_MATCH alone, which only reads P -- into buffers of the evaluation's own, batch_eval_moments (the
@@ -69,6 +84,9 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     std::vector<double> rho;                 // the shares as given (empty: none)
     std::vector<int> rank;                   // K_p = ceil(rho_p n_p) in [1, n_p]
     std::vector<char> tau_seen;              // the pair has completed a matching pass since icp_batch_begin
+    DevBuf recip_d, rev;                     // reciprocity: every pair's flag (uint8), every model point's nearest moving point of its pair's most recent matching pass (q_plane int32, laid out as the models; with trimming's dist)
+    bool reciprocal = false;                 // a pair's flag is set (icp_batch_set_reciprocal): the passes run the deferred route with the reverse search
+    std::vector<uint8_t> recip;              // the flags as given (empty: none)
     DevBuf rt0, init_kind, init_flag;        // initial transforms: R, t of every pair in the batch's precision, BATCH_INIT_APPLY / _COPY, the start cloud is not finite
     bool have_init = false;                  // the batch holds initial transforms (icp_batch_set_initial_transforms)
     std::vector<double> T0F;                 // count x 16: every pair's transform as rounded to the batch's precision, read back in double
@@ -130,7 +148,7 @@ void reset_loop_state(icp_batch* b)
 void release(icp_batch* b)
 {
     for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag,
-                      &b->trim_rank, &b->tau, &b->dist, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom})
+                      &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom})
         d->release();
     if (b->h_eval) (void)hipHostFree(b->h_eval);
     if (b->h_ctl) (void)hipHostFree(b->h_ctl);
@@ -239,6 +257,19 @@ std::vector<icp::BatchItem> work_items(const icp_batch* b, bool model)
     return items;
 }
 
+// ... of the models, on the device (q_items, n_q_items): made once, by whichever of the normals and the reverse search asks first
+int ensure_model_items(icp_batch* b)
+{
+    if (b->n_q_items != 0) return ICP_OK;
+    const std::vector<icp::BatchItem> items = work_items(b, true);
+    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    HIP_TRY(b->q_items.ensure(items.size() * sizeof(icp::BatchItem)));
+    HIP_TRY(hipMemcpyAsync(b->q_items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (items: a host vector)
+    b->n_q_items = (int)items.size();
+    return ICP_OK;
+}
+
 template <typename F>
 void put_rt(void* dst, const double* R, const double* t)
 {
@@ -328,6 +359,10 @@ int step(icp_batch* b)
     a.trim_rank = b->trimmed ? (const int*)b->trim_rank.p : nullptr;
     a.dist = b->dist.p;
     a.tau = b->tau.p;
+    a.recip = b->reciprocal ? (const uint8_t*)b->recip_d.p : nullptr;
+    a.rev = (int32_t*)b->rev.p;
+    a.q_items = (const icp::BatchItem*)b->q_items.p;
+    a.n_q_items = b->n_q_items;
     HIP_TRY(icp::launch_batch_pass(a, c->stream));
     HIP_TRY(hipMemcpyAsync(b->h_mom, b->mom.p, (size_t)b->count * ICP_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -449,7 +484,7 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
     b->metric = prm->metric;
     for (int p = 0; p < b->count; ++p)
         if (int rc = b->H[p].begin(*prm)) return fail(rc, "bad loop parameters");
-    for (int p = 0; p < b->count; ++p) b->H[p].gated = b->gated || b->trimmed;
+    for (int p = 0; p < b->count; ++p) b->H[p].gated = b->gated || b->trimmed || b->reciprocal;
     reset_loop_state(b);
     if (b->have_init) {
         // the start cloud of every pair in one launch, and one flag per pair back: a finite transform can carry a finite cloud
@@ -763,6 +798,53 @@ int icp_batch_set_trim(icp_batch* b, const double* keep_ratio)
     return ICP_OK;
 }
 
+int icp_batch_set_reciprocal(icp_batch* b, const uint8_t* on)
+{
+    if (int rc = ready(b)) return rc;
+    bool any = false;
+    for (int p = 0; on && p < b->count; ++p) any = any || on[p] != 0;
+    if (!any) {   // NULL, or every flag 0: the batch runs the steps it ran without flags
+        b->begun = false;
+        b->reciprocal = false;
+        if (on) b->recip.assign((size_t)b->count, 0);
+        else b->recip.clear();
+        return ICP_OK;
+    }
+    std::vector<uint8_t> flags((size_t)b->count);
+    for (int p = 0; p < b->count; ++p) flags[p] = on[p] ? 1 : 0;
+    // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
+    if (int rc = ensure_model_items(b)) return rc;
+    HIP_TRY(b->recip_d.ensure(flags.size()));
+    HIP_TRY(b->rev.ensure((size_t)b->q_plane * sizeof(int32_t)));
+    HIP_TRY(b->dist.ensure((size_t)b->p_plane * b->esize));
+    b->begun = false;   // a loop under way is discarded: its passes so far kept other matches
+    b->reciprocal = false;
+    HIP_TRY(hipMemcpyAsync(b->recip_d.p, flags.data(), flags.size(), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(hipMemsetAsync(b->rev.p, 0xff, (size_t)b->q_plane * sizeof(int32_t), b->ctx->stream));   // (-1: never random, the padding included)
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
+    b->recip.swap(flags);
+    b->reciprocal = true;
+    return ICP_OK;
+}
+
+int icp_diag_batch_reverse(icp_batch* b, int32_t* rev_out)
+{
+    if (int rc = ready(b)) return rc;
+    if (!rev_out) return fail(ICP_ERR_INVALID, "rev_out == NULL");
+    if (!b->begun || b->steps == 0) return fail(ICP_ERR_STATE, "no step since icp_batch_begin");
+    std::vector<int32_t> h;
+    if (b->reciprocal) {
+        h.resize((size_t)b->q_plane);
+        HIP_TRY(hipMemcpyAsync(h.data(), b->rev.p, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, b->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    }
+    for (int p = 0; p < b->count; ++p) {
+        const bool have = b->reciprocal && b->recip[p] && b->tau_seen[p];   // (tau_seen: the pair has completed a matching pass)
+        for (int j = 0; j < b->pairs[p].m; ++j) rev_out[b->qoff[p] + j] = have ? h[(size_t)b->pairs[p].q_off + j] : -1;
+    }
+    return ICP_OK;
+}
+
 int icp_batch_set_initial_transforms(icp_batch* b, const double* T16)
 {
     if (int rc = ready(b)) return rc;
@@ -846,14 +928,7 @@ int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighb
                                              std::to_string(b->pairs[p].m));
     icp_ctx* c = b->ctx;
     const size_t qb = 3 * (size_t)b->q_plane * b->esize, nb = 4 * (size_t)b->q_plane * sizeof(int32_t);
-    if (b->n_q_items == 0) {   // the model's work items: BATCH_ITEM model points of one pair, cut from that pair's first model point
-        const std::vector<icp::BatchItem> items = work_items(b, true);
-        if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
-        HIP_TRY(b->q_items.ensure(items.size() * sizeof(icp::BatchItem)));
-        HIP_TRY(hipMemcpyAsync(b->q_items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));   // (items: a host vector)
-        b->n_q_items = (int)items.size();
-    }
+    if (int rc = ensure_model_items(b)) return rc;   // BATCH_ITEM model points of one pair, cut from that pair's first model point
     HIP_TRY(b->nbr.ensure(nb));
     HIP_TRY(b->N.ensure(qb));
     b->begun = false;   // a loop under way is discarded

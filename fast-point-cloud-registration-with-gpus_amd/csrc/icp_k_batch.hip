@@ -1,5 +1,6 @@
 // icp_k_batch.hip -- gfx950 kernels of batched ICP (icp_batch.cpp): the pass of every running pair in one launch (nn_match_batch:
-// front end, matching, moments), trimmed rejection (batch_trim_select, batch_trim_moments), the per-pair reduction
+// front end, matching, moments), the reverse search of reciprocal pairs (nn_match_batch_rev), trimmed rejection and the deferred
+// decision (batch_trim_select, batch_trim_moments), the per-pair reduction
 // (batch_finalize_kernel), the evaluation of every pair at its present pose (batch_eval_moments) and the start clouds of a batch
 // with initial transforms (batch_init_kernel).  The batched neighbours and
 // normals (knn4_batch, normals_batch_kernel) live with the single-pair ones in icp_k_plane.hip.  Reference statements: the loop a
@@ -209,6 +210,107 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_match_batch(const BatchItem* __re
 }
 
 // ------------------------------------------------------------------------------------------------
+// reciprocal matches (icp_batch_set_reciprocal): the reverse search of a step -- rev[j] = the lowest i that minimises
+// dist2<F>(p_i, q_j) over the pair's n moving points, for every model point j of every reciprocal pair that matches in this
+// step.  nn_match_batch with the two clouds exchanged, and only its search:
+//   grid = one block per MODEL work item (q_items: BATCH_ITEM model points of one pair, the items of knn4_batch); all four
+//   waves hold the item's model points (one per lane); wave w scans the w-th contiguous quarter of the pair's MOVING cloud,
+//   wseg = ceil(ceil(n / 4) / NN_CHUNK) * NN_CHUNK points, through its own LDS sub-tile of BatchCfg<F>::TW points (every lane
+//   reads the same address: a broadcast, no bank conflict), keeping the running minimum and the first chunk that lowered it;
+//   the lowest index inside that chunk is recovered from global memory, and the quarters are merged in ascending order with a
+//   strict <: the lowest i wins ties.
+// No front end, no accumulators, no block_sum_store: wave 0 writes rev[q_off + first + lane] for its live lanes and nothing
+// else.  P is read as the forward launch of the same step left it (stream order): the cloud this pass matched on.  dist2
+// squares its differences, so the distance of (j, i) here is the forward distance of (i, j) bit for bit.  A block leaves at
+// once when its pair does not match in this step or is not reciprocal: rev keeps that pair's rows of its last matching pass.
+// The scan is restated, not shared with nn_match_batch, whose listings stay as they are (see ICP_BATCH_POINT_TERMS).
+// LDS: 4 x 3 x TW x sizeof(F) = 24 KiB of tiles + 2 KiB of merge slots, the forward kernel's footprint (six blocks per CU).
+// ------------------------------------------------------------------------------------------------
+template <typename F>
+__global__ __launch_bounds__(NN_BLOCK) void nn_match_batch_rev(const BatchItem* __restrict__ q_items, const BatchPair* __restrict__ pairs,
+                                                               const int* __restrict__ mode, const uint8_t* __restrict__ recip,
+                                                               const F* __restrict__ P, long long p_plane, const F* __restrict__ Q,
+                                                               long long q_plane, int32_t* __restrict__ rev)
+{
+    using V = typename Vec16<F>::type;
+    constexpr int VN = Vec16<F>::N;
+    constexpr int TW = BatchCfg<F>::TW, C = NN_CHUNK;
+    static_assert(BATCH_ITEM == 64 && NN_BLOCK == 4 * BATCH_ITEM && TW % C == 0, "one model point per lane, four waves per item, whole chunks per tile");
+    __shared__ __attribute__((aligned(16))) F sp[4][3][TW];
+    __shared__ F md[4][BATCH_ITEM];
+    __shared__ int mi[4][BATCH_ITEM];
+
+    const BatchItem it = q_items[blockIdx.x];
+    if (!(mode[it.pair] & BATCH_MATCH) || recip[it.pair] == 0) return;   // (block-uniform: no barrier is left waiting)
+    const BatchPair pr = pairs[it.pair];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool live = lane < it.count;
+    const long long gj = pr.q_off + it.first + (live ? lane : 0);   // (lanes past the item's end work on its first point: nothing of theirs is kept)
+    const F* Px = P + pr.p_off;
+    const F* Py = Px + p_plane;
+    const F* Pz = Px + 2 * p_plane;
+    const F x = Q[gj], y = Q[q_plane + gj], z = Q[2 * q_plane + gj];
+
+    const int n = pr.n;
+    const int wseg = ((n + 3) / 4 + C - 1) / C * C;   // moving points per wave, whole chunks
+    const int my0 = w * wseg, my1 = min(my0 + wseg, n);  // may be empty (my1 <= my0)
+    const int ntile = (wseg + TW - 1) / TW;           // the same for every wave: the barriers pair up
+    F best = inf_<F>();
+    int cst = -1;   // first moving index of the chunk that last lowered `best`
+    for (int k = 0; k < ntile; ++k) {
+        const int t0 = my0 + k * TW;
+        __syncthreads();
+        // this wave's sub-tile; places past the quarter's end hold +inf, which never lowers a minimum
+        for (int e = lane; e < TW; e += 64) {
+            const int i = t0 + e;
+            F px = inf_<F>(), py = inf_<F>(), pz = inf_<F>();
+            if (i < my1) { px = Px[i]; py = Py[i]; pz = Pz[i]; }
+            sp[w][0][e] = px;
+            sp[w][1][e] = py;
+            sp[w][2][e] = pz;
+        }
+        __syncthreads();
+        const int len = min(TW, my1 - t0);   // <= 0: this wave's quarter is exhausted
+        for (int c = 0; c < len; c += C) {
+            const F bo = best;
+#pragma unroll
+            for (int kk = 0; kk < C; kk += VN) {
+                const V px = *reinterpret_cast<const V*>(&sp[w][0][c + kk]);
+                const V py = *reinterpret_cast<const V*>(&sp[w][1][c + kk]);
+                const V pz = *reinterpret_cast<const V*>(&sp[w][2][c + kk]);
+#pragma unroll
+                for (int v = 0; v < VN; ++v) best = fmin_(best, dist2<F>(vget(px, v), vget(py, v), vget(pz, v), x, y, z));
+            }
+            cst = (best < bo) ? t0 + c : cst;
+        }
+    }
+    // the lowest i of the winning chunk with d_i == min (global memory, L2-resident)
+    int bi = 0x7fffffff;
+    if (cst >= 0) {
+        bi = cst;
+        for (int kk = C - 1; kk >= 0; --kk) {
+            const int i = cst + kk;
+            if (i < my1) {
+                const F d = dist2<F>(Px[i], Py[i], Pz[i], x, y, z);
+                bi = (d == best) ? i : bi;
+            }
+        }
+    }
+    md[w][lane] = cst >= 0 ? best : inf_<F>();
+    mi[w][lane] = bi;
+    __syncthreads();
+    if (w == 0 && live) {
+        F b = md[0][lane];
+        int i = mi[0][lane];
+#pragma unroll
+        for (int ww = 1; ww < 4; ++ww)
+            if (md[ww][lane] < b) { b = md[ww][lane]; i = mi[ww][lane]; }
+        rev[gj] = ((unsigned)i < (unsigned)n) ? i : 0;   // (nothing found only if every distance overflowed: rev stays in range)
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // trimmed rejection (icp_batch_set_trim): a pair keeps the K closest of its n matches (and every match tied with the K-th).  The
 // K-th smallest distance of a pair is known only when every one of its points has been matched -- by other blocks, for a
 // pair of more than one work item -- so the fused pass cannot decide; a step of a batch that trims runs four launches:
@@ -299,13 +401,19 @@ __global__ __launch_bounds__(TRIM_BLOCK) void batch_trim_select(const BatchPair*
 // that block_sum_store adds a row in the fused pass's order): kept = d <= tau[pair] && (no gate || d <= thr[pair]); a rejected
 // point's idx entry gets BATCH_IDX_REJECTED; the kept points' terms go to slots 1 .. of the item's row.  Slot ICP_MOM_ERR, which
 // nn_match_batch<.., DEFER> wrote, is not touched.
-template <typename F, int METRIC>
+// MUTUAL (its own instantiations, for a batch with a reciprocal pair; the others keep their code and never read rev or recip):
+// kept = mutual && d <= tau[pair] && d <= thr[pair], three independent tests, with mutual = rev[idx[i]] == i for a pair whose flag
+// recip[pair] is set (rev: nn_match_batch_rev's, of this step) and true for a pair whose flag is 0.  These instantiations take a
+// NULL tau -- a reciprocal batch that holds no trim allocates no tau and launches no batch_trim_select -- and read it as +inf.  A
+// pair with flag 0 and no trim keeps what the gate keeps: the fused pass's rows bit for bit, as any untrimmed pair on this route.
+template <typename F, int METRIC, bool MUTUAL = false>
 __global__ __launch_bounds__(NN_BLOCK) void batch_trim_moments(const BatchItem* __restrict__ items, const BatchPair* __restrict__ pairs,
                                                                const int* __restrict__ mode, const F* __restrict__ P, long long p_plane,
                                                                const F* __restrict__ Q, const F* __restrict__ Nrm, long long q_plane,
                                                                int32_t* __restrict__ idx_cur, const F* __restrict__ dist,
                                                                const F* __restrict__ tau, const F* __restrict__ thr,
-                                                               double* __restrict__ partials)
+                                                               double* __restrict__ partials, const int32_t* __restrict__ rev = nullptr,
+                                                               const uint8_t* __restrict__ recip = nullptr)
 {
     constexpr int NACC = BatchAcc<METRIC>::N;
     static_assert(ICP_MOM_ERR == 0, "the row's slots behind the error are written as one run");
@@ -322,7 +430,13 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_trim_moments(const BatchItem* 
         const F* Qx = Q + pr.q_off;
         const F b = dist[gi];
         const int j = idx_cur[gi];
-        const bool kept = b <= tau[it.pair] && (thr == nullptr || b <= thr[it.pair]);
+        bool kept;
+        if constexpr (MUTUAL) {
+            const bool mutual = recip[it.pair] == 0 || rev[pr.q_off + j] == it.first + lane;
+            kept = mutual && (tau == nullptr || b <= tau[it.pair]) && (thr == nullptr || b <= thr[it.pair]);
+        } else {
+            kept = b <= tau[it.pair] && (thr == nullptr || b <= thr[it.pair]);
+        }
         if (!kept) idx_cur[gi] = j | BATCH_IDX_REJECTED;
         const F* Qy = Qx + q_plane;
         const F* Qz = Qx + 2 * q_plane;
@@ -365,6 +479,7 @@ hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st)
     const bool plane = a.metric == ICP_POINT_TO_PLANE;
     if (plane && !a.N_soa) return hipErrorInvalidValue;
     if (a.trim_rank && (!a.dist || !a.tau)) return hipErrorInvalidValue;
+    if (a.recip && (!a.dist || !a.rev || !a.q_items || a.n_q_items <= 0)) return hipErrorInvalidValue;
 #define ICP_LAUNCH_BATCH(F, MET, GATE)                                                                                           \
     hipLaunchKernelGGL((nn_match_batch<F, MET, GATE>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs, a.mode,          \
                        (const RT<F>*)a.rt, (F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)a.N_soa, a.q_plane, a.idx_prev,   \
@@ -381,9 +496,28 @@ hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st)
                            (const F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)a.N_soa, a.q_plane, a.idx_cur,              \
                            (const F*)a.dist, (const F*)a.tau, (const F*)a.thr, a.partials);                                       \
     } while (0)
+    // a batch with a reciprocal pair: matching without a decision, the reverse search, [the K-th distance of every pair where the
+    // batch also trims,] then the decision -- mutual, trim, gate -- and the terms
+#define ICP_LAUNCH_BATCH_RECIP(F, MET)                                                                                           \
+    do {                                                                                                                         \
+        hipLaunchKernelGGL((nn_match_batch<F, MET, true, true>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs,        \
+                           a.mode, (const RT<F>*)a.rt, (F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)nullptr, a.q_plane,   \
+                           a.idx_prev, a.idx_cur, a.partials, (const F*)nullptr, (F*)a.dist);                                     \
+        hipLaunchKernelGGL((nn_match_batch_rev<F>), dim3(a.n_q_items), dim3(NN_BLOCK), 0, st, a.q_items, a.pairs, a.mode,         \
+                           a.recip, (const F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, a.q_plane, a.rev);                           \
+        if (a.trim_rank)                                                                                                         \
+            hipLaunchKernelGGL((batch_trim_select<F>), dim3(a.n_pairs), dim3(TRIM_BLOCK), 0, st, a.pairs, a.mode, a.trim_rank,    \
+                               (const F*)a.dist, (F*)a.tau);                                                                      \
+        hipLaunchKernelGGL((batch_trim_moments<F, MET, true>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs, a.mode,  \
+                           (const F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)a.N_soa, a.q_plane, a.idx_cur,              \
+                           (const F*)a.dist, a.trim_rank ? (const F*)a.tau : (const F*)nullptr, (const F*)a.thr, a.partials,      \
+                           (const int32_t*)a.rev, a.recip);                                                                       \
+    } while (0)
 #define ICP_LAUNCH_BATCH_F(F)                                                                                                  \
     do {                                                                                                                       \
-        if (a.trim_rank) {                                                                                                     \
+        if (a.recip) {                                                                                                         \
+            if (plane) ICP_LAUNCH_BATCH_RECIP(F, ICP_POINT_TO_PLANE); else ICP_LAUNCH_BATCH_RECIP(F, ICP_POINT_TO_POINT);      \
+        } else if (a.trim_rank) {                                                                                                   \
             if (plane) ICP_LAUNCH_BATCH_TRIM(F, ICP_POINT_TO_PLANE); else ICP_LAUNCH_BATCH_TRIM(F, ICP_POINT_TO_POINT);        \
         } else if (a.thr) {                                                                                                    \
             if (plane) ICP_LAUNCH_BATCH(F, ICP_POINT_TO_PLANE, true); else ICP_LAUNCH_BATCH(F, ICP_POINT_TO_POINT, true);      \
@@ -393,6 +527,7 @@ hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st)
     } while (0)
     if (a.precision == ICP_F64) ICP_LAUNCH_BATCH_F(double); else ICP_LAUNCH_BATCH_F(float);
 #undef ICP_LAUNCH_BATCH_F
+#undef ICP_LAUNCH_BATCH_RECIP
 #undef ICP_LAUNCH_BATCH_TRIM
 #undef ICP_LAUNCH_BATCH
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;

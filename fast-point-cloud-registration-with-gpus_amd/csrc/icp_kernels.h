@@ -4,7 +4,7 @@
 //   icp_k_row64.hip   nn_match_row64       rows of 64 points: the hall scan and everything up to 32 768 points
 //   icp_k_f64.hip     nn_match_row64_f64   the CPU path's precision on the same structure
 //   icp_k_dense.hip   nn_match_kernel / nn_match_f32_v2 (every pair), merge, moments, transform + error, finalize, layout
-//   icp_k_batch.hip   nn_match_batch (many pairs per launch), trimmed rejection, per-pair finalize, initial transforms
+//   icp_k_batch.hip   nn_match_batch (many pairs per launch), nn_match_batch_rev (reciprocal pairs), trimmed rejection, per-pair finalize, initial transforms
 //   icp_k_plane.hip   kNN(4) + normals, OS1 decode + conversion
 //   icp_k_setup.hip   duplicates, spatial order, boxes / samples / records, row order + roles, the control block of a pass
 //   icp_launch.hip    the dispatch (launch_nn): host code only
@@ -344,6 +344,15 @@ struct BatchPassArgs {
     const int* trim_rank;
     void* dist;                // F[p_plane], laid out as idx (read and written only with trim_rank)
     void* tau;                 // F[n_pairs], +inf from the host for the pairs that are not trimmed (only with trim_rank)
+    // NULL, or uint8[n_pairs], every pair's reciprocity flag, at least one of them set: the pass then runs deferred too --
+    // nn_match_batch<.., DEFER>, nn_match_batch_rev (one block per model work item of q_items: rev[q_off + j] = the lowest i that
+    // minimises dist2(p_i, q_j) over the pair's moving cloud as the matching launch left it, for the pairs that match and whose flag
+    // is set), batch_trim_select only where trim_rank is given, and batch_trim_moments<.., MUTUAL>: kept = (flag == 0 || rev[idx[i]]
+    // == i) && d <= tau[pair] (with trim_rank) && d <= thr[pair] (with thr).  Four launches + the reduction, five with trim_rank.
+    const uint8_t* recip;
+    int32_t* rev;              // [q_plane], laid out as the models (written only with recip; dist is needed too)
+    const BatchItem* q_items;  // the model's work items (launch_batch_normals' q_items; read only with recip)
+    int n_q_items;
 };
 hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st);
 // evaluation of every pair whose mode is BATCH_MATCH at its present pose (icp_batch_evaluate): the deferred matching launch

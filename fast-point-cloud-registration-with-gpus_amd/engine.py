@@ -284,9 +284,21 @@ class Context:
         (point_to_plane_batch itself keeps its parameter list, which tests/test_batch_plane_abi.py holds fixed.)"""
         return self._run_batch_gated(capi.ICP_POINT_TO_PLANE, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init, trim)
 
-    def _run_batch_gated(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init=None, trim=None):
-        """the one-call functions have neither a gate nor initial transforms nor trimming: create, [normals], set_max_distance,
-        set_initial_transforms, set_trim, begin, run to the end, results"""
+    def register_batch(self, pairs, metric=capi.ICP_POINT_TO_POINT, normals=None, max_iter=None, tol=1e-6, fixed_iterations=False,
+                       max_distance=None, init=None, trim=None, reciprocal=None):
+        """the one-call entry that takes every option of a batch: metric (ICP_POINT_TO_POINT, or ICP_POINT_TO_PLANE with normals --
+        one (m, 3) array per pair, or None: estimated on the device), max_iter (None: 40 for point-to-point, 50 for
+        point-to-plane, the defaults of point_to_point_batch / point_to_plane_batch), max_distance, init and trim as
+        point_to_point_batch takes them, and reciprocal (None: off; a bool for every pair; or one flag per pair): a reciprocal
+        pair keeps only mutual nearest neighbours (Batch.set_reciprocal).  Always runs through a Batch; a list of Result in pair
+        order with extra["status"], extra["inliers"] (the mask of the last contributing pass) and extra["fitness"]."""
+        if max_iter is None:
+            max_iter = 50 if metric == capi.ICP_POINT_TO_PLANE else 40
+        return self._run_batch_gated(metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init, trim, reciprocal)
+
+    def _run_batch_gated(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init=None, trim=None, reciprocal=None):
+        """the one-call functions have neither a gate nor initial transforms nor trimming nor reciprocity: create, [normals],
+        set_max_distance, set_initial_transforms, set_trim, set_reciprocal, begin, run to the end, results"""
         with Batch(self, pairs) as bt:
             if metric == capi.ICP_POINT_TO_PLANE:
                 if normals is not None:
@@ -297,6 +309,8 @@ class Context:
             bt.set_initial_transforms(init)
             if trim is not None:
                 bt.set_trim(trim)
+            if reciprocal is not None:
+                bt.set_reciprocal(reciprocal)
             bt.begin(max_iter=max_iter, tol=tol, fixed_iterations=fixed_iterations, metric=metric)
             while bt.run(1 << 20)[1] > 0:
                 pass
@@ -544,6 +558,29 @@ class Batch:
         tau, k = C.c_double(0.0), C.c_int(0)
         capi.check(self._lib.icp_diag_batch_trim(self._h, int(b), C.byref(tau), C.byref(k)), "icp_diag_batch_trim")
         return tau.value, k.value
+
+    def set_reciprocal(self, v):
+        """reciprocal (mutual nearest neighbour) matches: None (off), a bool for every pair, or one flag per pair.  A reciprocal
+        pair keeps, in every matching pass, only the matches i -> idx[i] whose model point's own nearest moving point is i; with
+        a gate or a trim all tests must pass.  Discards a loop under way."""
+        if v is None:
+            capi.check(self._lib.icp_batch_set_reciprocal(self._h, None), "icp_batch_set_reciprocal")
+            return
+        if isinstance(v, (bool, np.bool_)):
+            a = np.full(self.count, 1 if v else 0, dtype=np.uint8)
+        else:
+            a = np.ascontiguousarray(np.asarray(v).astype(bool).astype(np.uint8))
+            if a.shape != (self.count,):
+                raise ValueError("one reciprocity flag per pair (or a bool, or None)")
+        capi.check(self._lib.icp_batch_set_reciprocal(self._h, a.ctypes.data_as(C.POINTER(C.c_uint8))), "icp_batch_set_reciprocal")
+
+    def diag_reverse(self):
+        """per pair, (m,) int32: for a reciprocal pair each model point's nearest moving point (the lowest index on ties) of the
+        pair's most recent matching pass (icp_diag_batch_reverse); -1 throughout for a pair whose flag is off or that has not
+        matched since begin"""
+        out = np.empty(int(self._qoff[-1]), dtype=np.int32)
+        capi.check(self._lib.icp_diag_batch_reverse(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))), "icp_diag_batch_reverse")
+        return [out[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
 
     def set_initial_transforms(self, T):
         """the pose every pair's registration starts from: one (4, 4) for every pair, (count, 4, 4), or None (none).  Rounded once

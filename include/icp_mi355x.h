@@ -320,6 +320,34 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *         transform.
  *       cost: a pair's tau is known only when every one of its points has been matched, so a step of a batch that trims at
  *         least one pair runs four launches in place of two (matching, selection, sums, reduction) and still one download.
+ *   - reciprocal matches (icp_batch_set_reciprocal): one byte per pair, non-zero = that pair keeps only mutual nearest neighbours
+ *     (PCL's reciprocal correspondences): the remedy where many moving points collapse onto one model point at the border of a
+ *     partial overlap or next to clutter.  NULL switches reciprocity off for the whole batch.
+ *       the call may come at any time after icp_batch_create; like the other icp_batch_set_* calls it discards a loop under way
+ *         (icp_batch_run returns ICP_ERR_STATE until the next icp_batch_begin).  A null batch is ICP_ERR_INVALID, a context with
+ *         a pending pass ICP_ERR_STATE; a refused call leaves the batch as it was.
+ *       rule, in every matching pass of a reciprocal pair: idx[i] is the forward match as ever, the lowest j that minimises
+ *         dist2(p_i, q_j) = (dx*dx + dy*dy) + dz*dz, every operation rounded separately in the batch's precision F.  rev[j] is
+ *         the lowest i that minimises the same dist2 over the pair's n moving points, on the cloud this pass matched on (the
+ *         cloud after the pass's front end has applied the previous motion).  The match of i is mutual iff rev[idx[i]] == i.
+ *         dist2 squares its differences, so the reverse distance of (j, i) is the forward distance of (i, j) bit for bit:
+ *         both searches compare the same numbers, and only the order among equal ones (lowest index first, both ways) differs.
+ *       combination: kept = mutual && d <= tau_p && d <= thr_p -- three independent tests.  tau_p stays the K_p-th smallest of
+ *         ALL n_p winning distances of the pair, exactly as without reciprocity (the selection ignores the mutual rule as it
+ *         ignores the gate): a reciprocal, trimmed pair may therefore keep fewer than ceil(rho n) points.  (Ranking only the
+ *         mutual matches is not offered.)
+ *       everything else follows the gate's rules.  idx is unchanged, kept or not; only kept points contribute to ICP_MOM_CNT
+ *         and to every sum of the pass, for both metrics; the next pass's ICP_MOM_ERR covers kept points only and err[k] =
+ *         sqrt(ERR_k) / sqrt(CNT_{k-1}); icp_batch_get_inliers / icp_batch_loop_inliers report the kept mask.  The mutual rule
+ *         alone always keeps at least one point -- the lowest i that attains the pair's smallest distance is mutual -- so
+ *         ICP_ERR_EMPTY can still arise only together with a gate.
+ *       bits: a batch with no flags, or with every flag 0, runs exactly the steps it runs without them, with the same bits.  In
+ *         a batch with a reciprocal pair, a pair whose flag is 0 still has the bits of that pair in a batch without flags, and a
+ *         reciprocal pair's bits depend on that pair, its flag, its rho and its gate alone.  Initial transforms: reciprocity
+ *         acts on the start cloud.
+ *       cost: the reverse search is a second scan of m x n distances in a launch of its own (one block per 64 model points),
+ *         so a step of a batch with a reciprocal pair runs four launches (matching, reverse search, decision and sums,
+ *         reduction), five when it also trims, and still one download.
  *   - evaluation (icp_batch_evaluate): did pair p register, and how well is it constrained?  Per pair the fitness (the share of
      its moving points with a model point within a distance of the caller's choosing), the inlier RMSE and the 6 x 6
      information matrix a pose-graph optimiser takes beside T -- measured where the pair's moving cloud stands on the device,
@@ -332,7 +360,8 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
        gate: max_dist follows icp_batch_set_max_distance's rules -- count doubles, each > 0 or +INFINITY, thr = (F)(max_dist *
          max_dist) with the product formed in double and rounded once, a match kept iff d <= thr (a point on the threshold is
          kept); a NaN, a value <= 0 or -INFINITY is ICP_ERR_INVALID, the message names the pair, and nothing is launched.  NULL:
-         every match is kept.  The batch's own gate, its trim shares and tau are neither read nor changed.
+         every match is kept.  The batch's own gate, its trim shares and tau are neither read nor changed, and neither are its reciprocity
+         flags: an evaluation scores forward matches at a distance, whatever icp_batch_set_reciprocal was told.
        evaluation vector: ICP_NMOM doubles per pair (slots ICP_EVAL_*, icp_mi355x_diag.h), every term formed in double from
          the widened coordinates of the kept matches, added per work item and then per pair in a fixed order, no
          floating-point atomics: a pair's bits depend on that pair and its threshold alone.  Both metrics: SD = sum |q[idx] -
@@ -389,6 +418,8 @@ int icp_batch_set_max_distance(icp_batch* b, const double* max_dist);
 /* per-pair share of the moving cloud to keep: count doubles, or NULL = no trimming.  Each value in (0, 1]; exactly 1.0: that
  * pair is not trimmed. */
 int icp_batch_set_trim(icp_batch* b, const double* keep_ratio);
+/* per-pair reciprocity: count bytes, non-zero = that pair keeps only mutual nearest neighbours; NULL = off for the whole batch */
+int icp_batch_set_reciprocal(icp_batch* b, const uint8_t* on);
 /* count x 16 doubles, one row-major 4x4 per pair (the layout of icp_result.T), or NULL = no initial transforms */
 int icp_batch_set_initial_transforms(icp_batch* b, const double* T16);
 /* per-pair fitness, inlier RMSE and information matrix where the moving clouds stand (above); max_dist: count doubles or NULL;

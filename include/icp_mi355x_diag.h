@@ -75,7 +75,8 @@ int icp_diag_row_roles(icp_ctx* ctx, uint32_t* hits_io, int rows, int min_part, 
 #define ICP_ROUTE_RESIDENT 0x800       /* the pass was a message to the resident kernel */
 int icp_diag_loop_moments(icp_ctx* ctx, double* out32, int* route);
 /* the same for pair `pair` of a batch: the row of the step's download that pair's loop last advanced on (the rows are always
- * added by batch_finalize_kernel; they come from nn_match_batch's fused tail, or from batch_trim_moments in a batch that trims).
+ * added by batch_finalize_kernel; they come from nn_match_batch's fused tail, or from batch_trim_moments in a batch that trims
+ * or holds a reciprocal pair).
  * ICP_ERR_STATE before the pair's first completed pass. */
 int icp_diag_batch_moments(icp_batch* b, int pair, double* out32);
 /* trimmed rejection of pair `pair` (icp_batch_set_trim): *tau_sq = the threshold of the pair's most recent matching pass -- the
@@ -83,6 +84,11 @@ int icp_diag_batch_moments(icp_batch* b, int pair, double* out32);
  * and *rank = K (n for a pair that is not trimmed).  Either pointer may be NULL.  The per-pair threshold buffer is copied down
  * on demand: nothing is added to a step's download.  ICP_ERR_STATE before the pair's first completed matching pass. */
 int icp_diag_batch_trim(icp_batch* b, int pair, double* tau_sq, int* rank);
+/* reciprocal matches (icp_batch_set_reciprocal): the reverse search, one int32 per model point, concatenated as the models were
+ * (model_off[count] entries).  For every reciprocal pair: rev[j] of that pair's most recent matching pass, the lowest i in [0, n)
+ * that minimises dist2(p_i, q_j).  -1 throughout for a pair whose flag is 0, or that has completed no matching pass since
+ * icp_batch_begin.  Downloaded on demand: nothing is added to a step.  ICP_ERR_STATE before the first step of a loop. */
+int icp_diag_batch_reverse(icp_batch* b, int32_t* rev_out);
 /* The evaluation vector of pair `pair` from the latest icp_batch_evaluate (icp_mi355x.h): ICP_NMOM doubles, the only data the
  * call's per-pair outputs (inliers, fitness, rmse, information) are formed from.  Every term is formed in double from the widened
  * coordinates of the kept matches, added per work item and then per pair in a fixed order.  Slots, q = the matched model point,

@@ -3,7 +3,7 @@
 for all pairs) against a loop of Context.point_to_point / point_to_plane over the same pairs (GPU box).
 
   python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE] [--only CASE,CASE] [--max-distance V] [--trim R]
-                              [--label TEXT] [--init | --premoved] [--evaluate]
+                              [--reciprocal] [--label TEXT] [--init | --premoved] [--evaluate]
 
 Cases, --metric point: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids
 (make_model_gpu, tol 1e-6); 16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  --metric plane: the fp32 case sets and the
@@ -26,6 +26,12 @@ build of the library for an A/B run on one box.
 the deferred route, four launches per step; R = 1.0 goes through the Batch object and runs the fused pass).  The sequential side
 does not trim, so the passes are compared only for R = 1.0.  The cost of trimming is --trim R against --max-distance inf of the
 same build (both through the Batch object).
+
+--reciprocal runs the batched side with every pair reciprocal (Context.register_batch(reciprocal=True): the deferred route with the
+reverse search, four launches per step, five with --trim), combinable with --max-distance and --trim.  The sequential side has no
+such rule, so the passes are not compared.  The cost of reciprocity is --reciprocal against --trim R of the same build (the
+deferred route without the reverse search), and --reciprocal --trim R against both.  With --evaluate the timed steps (first_step_s,
+step_s) and the registration run with the gate, the trim and the flags given; the evaluation itself never looks at them.
 
 --init times the batched side from a far pose -- every moving cloud carried off by G (40 degrees about z, shifted by (3, -2, 1))
 outside the timed region -- with the inverse pose as every pair's initial transform (Context.point_to_*_batch(init=...)).
@@ -96,6 +102,7 @@ def main():
     ap.add_argument("--only", default="", help="comma-separated case names: run only these")
     ap.add_argument("--max-distance", type=float, default=None, help="gate the batched side at this distance (inf: the gated kernels, nothing rejected)")
     ap.add_argument("--trim", type=float, default=None, help="keep this share of every moving cloud on the batched side (the deferred route)")
+    ap.add_argument("--reciprocal", action="store_true", help="every pair keeps only mutual nearest neighbours on the batched side (the deferred route with the reverse search)")
     ap.add_argument("--label", default="", help="copied into every row")
     ap.add_argument("--init", action="store_true", help="the batched side starts from a far pose with the inverse pose as initial transform")
     ap.add_argument("--premoved", action="store_true", help="the baseline of --init: the far clouds moved back on the host, no initial transform, same route")
@@ -135,6 +142,7 @@ def main():
             sys.exit(f"unknown case(s) {unknown}: {[t[0] for t in todo]}")
         gate = a.max_distance
         trim = a.trim
+        recip = True if a.reciprocal else None
         for name, pairs, normals, it, tol in todo:
             if only and name not in only:
                 continue
@@ -143,8 +151,8 @@ def main():
             metric = pkg.ICP_POINT_TO_PLANE if plane else pkg.ICP_POINT_TO_POINT
 
             def run_batched():
-                if a.init or a.premoved:   # both through the Batch object: they differ by the initial transforms alone
-                    return ctx._run_batch_gated(metric, bat_pairs, normals, it, tol, False, gate, G_inv if a.init else None, trim)
+                if a.init or a.premoved or recip:   # through the Batch object (--init / --premoved differ by the initial transforms alone)
+                    return ctx._run_batch_gated(metric, bat_pairs, normals, it, tol, False, gate, G_inv if a.init else None, trim, recip)
                 if plane and (gate is not None or trim is not None):
                     return ctx.point_to_plane_batch_gated(pairs, gate, normals=normals, max_iter=it, tol=tol, trim=trim)
                 if plane:
@@ -171,6 +179,12 @@ def main():
                 with ctx.batch(pairs) as bt:
                     if plane:
                         bt.set_model_normals(normals) if normals is not None else bt.estimate_normals()
+                    if gate is not None:
+                        bt.set_max_distance(gate)
+                    if trim is not None:
+                        bt.set_trim(trim)
+                    if recip:
+                        bt.set_reciprocal(True)
 
                     def timed(fn):
                         t0 = time.perf_counter()
@@ -195,7 +209,8 @@ def main():
                            step_s_min=float(min(y for _, y in st)), step_s_max=float(max(y for _, y in st)),
                            evaluate_s=med(ev) if have else None, evaluate_s_min=float(min(ev)) if have else None,
                            evaluate_s_max=float(max(ev)) if have else None, evaluate_matches_s=med(evm) if have else None,
-                           reps=a.reps, pairs_stopping_apart=0, label=a.label)
+                           reps=a.reps, pairs_stopping_apart=0, max_distance=None if gate is None else str(gate), trim=trim,
+                           reciprocal=bool(recip), label=a.label)
                 rows.append(row)
                 print(json.dumps(row), flush=True)
                 continue
@@ -220,7 +235,7 @@ def main():
                 ts.append(s)
                 tl.append(loops)
             # the same registrations: every pair must run the same passes on both sides (checked when all rows are out)
-            apart = sum(1 for x, y in zip(pb, ps) if x != y) if (gate is None or np.isinf(gate)) and (trim is None or trim == 1.0) else 0
+            apart = sum(1 for x, y in zip(pb, ps) if x != y) if (gate is None or np.isinf(gate)) and (trim is None or trim == 1.0) and not recip else 0
             pb, ps = sum(pb), sum(ps)
             mb, ms, ml = float(np.median(tb)), float(np.median(ts)), float(np.median(tl))
             row = dict(case=name, pairs=len(pairs), points=int(pairs[0][0].shape[0]), pair_iterations=pb, sequential_pair_iterations=ps, pairs_stopping_apart=apart,
@@ -229,7 +244,7 @@ def main():
                        batched_us_per_pair_it=1e6 * mb / pb, sequential_us_per_pair_it=1e6 * ms / ps,
                        sequential_loops_us_per_pair_it=1e6 * ml / ps, speedup=ms / mb, speedup_vs_loops=ml / mb,
                        batched_s_min=float(min(tb)), batched_s_max=float(max(tb)), reps=a.reps,
-                       max_distance=None if gate is None else str(gate), trim=trim, start="init" if a.init else "premoved" if a.premoved else "uploaded",
+                       max_distance=None if gate is None else str(gate), trim=trim, reciprocal=bool(recip), start="init" if a.init else "premoved" if a.premoved else "uploaded",
                        label=a.label)
             rows.append(row)
             print(json.dumps(row), flush=True)
