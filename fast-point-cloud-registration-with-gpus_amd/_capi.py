@@ -23,6 +23,8 @@ ICP_ERR_NOMEM = -8
 ICP_F32, ICP_F64 = 0, 1
 ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1
 ICP_NMOM = 32
+ICP_MOM_W = 29   # slot of a robust pass's weight sum
+ICP_ROBUST_NONE, ICP_ROBUST_HUBER, ICP_ROBUST_CAUCHY, ICP_ROBUST_TUKEY = 0, 1, 2, 3
 ICP_BATCH_MAX_POINTS = 65536   # per cloud of one pair of a batch
 # icp_diag_loop_moments: how the vector came about (include/icp_mi355x_diag.h)
 ROUTE_HOST_ROWS, ROUTE_COMPACT, ROUTE_AVX, ROUTE_FIN_LAUNCH, ROUTE_FIN_PINNED, ROUTE_FIN_KERNEL = 0x001, 0x002, 0x004, 0x008, 0x010, 0x020
@@ -105,6 +107,8 @@ SIGNATURES = {
     "icp_batch_set_initial_transforms": (_i, [_vp, _pd]),
     "icp_batch_set_trim": (_i, [_vp, _pd]),
     "icp_batch_set_reciprocal": (_i, [_vp, C.POINTER(C.c_uint8)]),
+    "icp_batch_set_robust": (_i, [_vp, _pi, _pd]),
+    "icp_batch_get_weights": (_i, [_vp, _pd]),
     "icp_batch_get_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_batch_loop_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_batch_evaluate": (_i, [_vp, _i, _pd, _pi, _pi32, _pd, _pd, _pd, _pi32, C.POINTER(C.c_uint8)]),
@@ -124,6 +128,7 @@ SIGNATURES = {
     "icp_host_loop_destroy": (None, [_vp]),
     "icp_host_loop_advance": (_i, [_vp, _pd, _pi, _pd, _pd]),
     "icp_host_loop_note_applied": (_i, [_vp]),
+    "icp_host_loop_set_weighted": (_i, [_vp, _i]),
     "icp_host_loop_state": (_i, [_vp, _pi, _pi, _pd, _i, _pd]),
     "icp_shard_range": (_i, [C.c_int64, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "icp_share_rows_plan": (_i, [_pu32, _i, _i, _i, _i, _pi32, _pu32]),

@@ -2,8 +2,8 @@
 // step ONE matching launch + ONE reduction launch + ONE download of ICP_NMOM doubles per pair for every pair still running.
 //
 //   step k:  [R, t + mode of every pair: H2D]  ->  nn_match_batch (icp_k_batch.hip: transform + error, match, moments per work item)
-//            [a batch that trims or holds a reciprocal pair: nn_match_batch<DEFER>  ->  nn_match_batch_rev (reciprocal)  ->
-//             batch_trim_select (trims)  ->  batch_trim_moments -- see the table below]
+//            [a batch that trims or holds a reciprocal or a robust pair: nn_match_batch<DEFER>  ->  nn_match_batch_rev (reciprocal)
+//             ->  batch_trim_select (trims)  ->  batch_trim_moments / batch_robust_moments -- see the table below]
 //            ->  batch_finalize_kernel (per pair, fixed order)  ->  D2H count x ICP_NMOM  ->  sync
 //            ->  HostLoop::advance per pair that took part (error, stop rule, 3x3 solve or 6x6 solve)
 //
@@ -32,7 +32,16 @@
 // trimming, still one download.  rev is consumed inside the step that wrote it (no ping-pong), and a pair's rows of it are
 // rewritten only when that pair matches.  A batch whose flags are all 0 runs the steps it ran without them.
 //
+// A batch may hold a robust kernel per pair (icp_batch_set_robust: Huber, Cauchy or Tukey weights at a scale k): every kept match
+// of such a pair enters the sums with a weight in [0, 1] that falls with its residual, and the pair's HostLoop solves on the
+// weighted vector (HostLoop::weighted: CNT <- W).  The weight needs nothing the deferred decision does not have, so the steps of a
+// batch with a robust pair always run deferred, with batch_robust_moments in batch_trim_moments' place: the same decision, then
+// residual, weight and weighted terms, the weight of every point into a buffer of its own (icp_batch_get_weights), and the
+// reduction up to slot ICP_MOM_W.  Three launches with nothing else, up to five, still one download.  A batch whose kinds are all
+// NONE runs the steps it ran without them.
+//
 //   batch kind             launches of a step
+//   any robust pair        nn_match_batch<DEFER>, [nn_match_batch_rev,] [batch_trim_select,] batch_robust_moments<MUTUAL?>, batch_finalize_kernel
 //   any reciprocal pair    nn_match_batch<DEFER>, nn_match_batch_rev, [batch_trim_select,] batch_trim_moments<MUTUAL>, batch_finalize_kernel
 //   trims only             nn_match_batch<DEFER>, batch_trim_select, batch_trim_moments, batch_finalize_kernel
 //   gates only / plain     nn_match_batch, batch_finalize_kernel
@@ -87,6 +96,10 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     DevBuf recip_d, rev;                     // reciprocity: every pair's flag (uint8), every model point's nearest moving point of its pair's most recent matching pass (q_plane int32, laid out as the models; with trimming's dist)
     bool reciprocal = false;                 // a pair's flag is set (icp_batch_set_reciprocal): the passes run the deferred route with the reverse search
     std::vector<uint8_t> recip;              // the flags as given (empty: none)
+    DevBuf rob_kind, rob_k, rob_k2, weights; // robust kernels: every pair's kind (int), k and k * k (double); every moving point's weight of its pair's most recent matching pass (p_plane doubles, laid out as idx; allocated with the first kernel)
+    bool robust = false;                     // a pair's kind is not NONE (icp_batch_set_robust): the passes run the deferred route with batch_robust_moments
+    std::vector<int> rkind;                  // the kinds as given (empty: none)
+    std::vector<double> rscale;              // the scales (0 for a NONE pair)
     DevBuf rt0, init_kind, init_flag;        // initial transforms: R, t of every pair in the batch's precision, BATCH_INIT_APPLY / _COPY, the start cloud is not finite
     bool have_init = false;                  // the batch holds initial transforms (icp_batch_set_initial_transforms)
     std::vector<double> T0F;                 // count x 16: every pair's transform as rounded to the batch's precision, read back in double
@@ -148,7 +161,7 @@ void reset_loop_state(icp_batch* b)
 void release(icp_batch* b)
 {
     for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag,
-                      &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom})
+                      &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->rob_kind, &b->rob_k, &b->rob_k2, &b->weights, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom})
         d->release();
     if (b->h_eval) (void)hipHostFree(b->h_eval);
     if (b->h_ctl) (void)hipHostFree(b->h_ctl);
@@ -363,6 +376,10 @@ int step(icp_batch* b)
     a.rev = (int32_t*)b->rev.p;
     a.q_items = (const icp::BatchItem*)b->q_items.p;
     a.n_q_items = b->n_q_items;
+    a.robust_kind = b->robust ? (const int*)b->rob_kind.p : nullptr;
+    a.robust_k = (const double*)b->rob_k.p;
+    a.robust_k2 = (const double*)b->rob_k2.p;
+    a.weights = (double*)b->weights.p;
     HIP_TRY(icp::launch_batch_pass(a, c->stream));
     HIP_TRY(hipMemcpyAsync(b->h_mom, b->mom.p, (size_t)b->count * ICP_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -485,6 +502,7 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
     for (int p = 0; p < b->count; ++p)
         if (int rc = b->H[p].begin(*prm)) return fail(rc, "bad loop parameters");
     for (int p = 0; p < b->count; ++p) b->H[p].gated = b->gated || b->trimmed || b->reciprocal;
+    for (int p = 0; p < b->count; ++p) b->H[p].weighted = b->robust;   // (a NONE pair of a robust batch: W == CNT exactly)
     reset_loop_state(b);
     if (b->have_init) {
         // the start cloud of every pair in one launch, and one flag per pair back: a finite transform can carry a finite cloud
@@ -824,6 +842,75 @@ int icp_batch_set_reciprocal(icp_batch* b, const uint8_t* on)
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
     b->recip.swap(flags);
     b->reciprocal = true;
+    return ICP_OK;
+}
+
+int icp_batch_set_robust(icp_batch* b, const int* kind, const double* scale)
+{
+    if (int rc = ready(b)) return rc;
+    bool any = false;
+    for (int p = 0; kind && p < b->count; ++p) {
+        if (kind[p] != ICP_ROBUST_NONE && kind[p] != ICP_ROBUST_HUBER && kind[p] != ICP_ROBUST_CAUCHY && kind[p] != ICP_ROBUST_TUKEY)
+            return fail(ICP_ERR_INVALID, "unknown robust kernel: pair " + std::to_string(p));
+        if (kind[p] == ICP_ROBUST_NONE) continue;
+        if (!scale) return fail(ICP_ERR_INVALID, "a robust kernel needs a scale (scale == NULL): pair " + std::to_string(p));
+        const double k = scale[p], k2 = k * k;   // (NaN fails every comparison; k * k may overflow or underflow)
+        if (!(std::isfinite(k) && k > 0 && std::isfinite(k2) && k2 > 0))
+            return fail(ICP_ERR_INVALID, "the scale of a robust kernel must be finite and > 0, and so must its square: pair " + std::to_string(p));
+        any = true;
+    }
+    if (!any) {   // NULL, or every kind NONE: the batch runs the steps it ran without kernels
+        b->begun = false;
+        b->robust = false;
+        if (kind) b->rkind.assign((size_t)b->count, ICP_ROBUST_NONE);
+        else b->rkind.clear();
+        b->rscale.assign(b->rkind.size(), 0.0);
+        return ICP_OK;
+    }
+    std::vector<int> kinds(kind, kind + b->count);
+    std::vector<double> k((size_t)b->count, 0.0), k2((size_t)b->count, 0.0);
+    for (int p = 0; p < b->count; ++p)
+        if (kinds[p] != ICP_ROBUST_NONE) {
+            k[p] = scale[p];
+            k2[p] = scale[p] * scale[p];
+        }
+    // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
+    const size_t wb = (size_t)b->p_plane * sizeof(double);
+    HIP_TRY(b->rob_kind.ensure(kinds.size() * sizeof(int)));
+    HIP_TRY(b->rob_k.ensure(k.size() * sizeof(double)));
+    HIP_TRY(b->rob_k2.ensure(k2.size() * sizeof(double)));
+    HIP_TRY(b->weights.ensure(wb));
+    HIP_TRY(b->dist.ensure((size_t)b->p_plane * b->esize));
+    b->begun = false;   // a loop under way is discarded: its passes so far weighed the matches otherwise (or not at all)
+    b->robust = false;
+    hipStream_t st = b->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(b->rob_kind.p, kinds.data(), kinds.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->rob_k.p, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->rob_k2.p, k2.data(), k2.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(b->weights.p, 0, wb, st));   // (never random, the padding included)
+    HIP_TRY(hipStreamSynchronize(st));   // (before the host vectors go)
+    b->rkind.swap(kinds);
+    b->rscale.swap(k);
+    b->robust = true;
+    return ICP_OK;
+}
+
+int icp_batch_get_weights(icp_batch* b, double* w_out)
+{
+    if (int rc = ready(b)) return rc;
+    if (!w_out) return fail(ICP_ERR_INVALID, "output pointer == NULL");
+    if (!b->begun || b->steps == 0) return fail(ICP_ERR_STATE, "no matching pass since icp_batch_begin");
+    if (!b->robust) {   // no kernels: the kept mask as 1.0 / 0.0, from the index marks
+        std::vector<uint8_t> mask((size_t)b->moff[b->count]);
+        if (int rc = download_indices(b, false, nullptr, mask.data())) return rc;
+        for (size_t i = 0; i < mask.size(); ++i) w_out[i] = mask[i] ? 1.0 : 0.0;
+        return ICP_OK;
+    }
+    std::vector<double> h((size_t)b->p_plane);
+    HIP_TRY(hipMemcpyAsync(h.data(), b->weights.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    for (int p = 0; p < b->count; ++p)
+        std::memcpy(w_out + b->moff[p], h.data() + b->pairs[p].p_off, (size_t)b->pairs[p].n * sizeof(double));
     return ICP_OK;
 }
 

@@ -68,7 +68,19 @@ int HostLoop::advance(const double* mom)
         done = true;
         return ICP_ERR_EMPTY;
     }
+    if (!done && weighted && !(mom[ICP_MOM_W] > 0)) {   // ... or kept only points of weight 0
+        done = true;
+        return ICP_ERR_EMPTY;
+    }
     if (!done) {
+        // a robust pass: the sums are weighted, and the solve's divisor is the sum of the weights (the weighted Kabsch solve; the
+        // plane solve never reads the slot).  Everything else is as delivered.
+        double wmom[ICP_NMOM];
+        if (weighted) {
+            std::memcpy(wmom, mom, sizeof wmom);
+            wmom[ICP_MOM_CNT] = mom[ICP_MOM_W];
+            mom = wmom;
+        }
         const int rc = prm.metric == ICP_POINT_TO_PLANE ? solve_point_to_plane(mom, R, t, nullptr)
                                                         : solve_point_to_point(mom, R, t);
         if (rc != ICP_OK) {
@@ -122,6 +134,13 @@ int icp_host_loop_note_applied(icp_host_loop* h)
 {
     if (!h || !h->H.have_rt) return ICP_ERR_STATE;
     h->H.note_applied();
+    return ICP_OK;
+}
+
+int icp_host_loop_set_weighted(icp_host_loop* h, int on)
+{
+    if (!h) return ICP_ERR_INVALID;
+    h->H.weighted = on != 0;
     return ICP_OK;
 }
 

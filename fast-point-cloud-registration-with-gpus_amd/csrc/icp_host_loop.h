@@ -16,6 +16,7 @@ struct HostLoop {
     bool have_rt = false; // R, t of the last advance() wait to be applied
     double n_total = 0.0; // moving points that contributed to the latest matching pass (summed over ranks)
     bool gated = false;   // set after begin(): a matching pass may keep no point, which ends the loop with ICP_ERR_EMPTY
+    bool weighted = false; // set after begin(): the vectors are a robust pass's -- the solve reads ICP_MOM_W where it read ICP_MOM_CNT, and a matching pass of weight sum 0 ends the loop with ICP_ERR_EMPTY
     double R[9], t[3], T[16];
     std::vector<double> err;
 
@@ -27,7 +28,7 @@ struct HostLoop {
     bool next_is_final() const { return applied + (have_rt ? 1 : 0) >= prm.max_iter; }
     // feed the (rank-reduced) moment vector of the enqueue that followed note_applied(): E[k] (ICP_MOM_ERR over
     // the count of the vector before it, whose matches it measures), the stop rule of src/ICP_CPU.c:267-269,
-    // and -- unless the loop ended -- the next R, t.
+    // and -- unless the loop ended -- the next R, t (weighted: solved on a copy of the vector with CNT <- W).
     int advance(const double* mom);
 };
 

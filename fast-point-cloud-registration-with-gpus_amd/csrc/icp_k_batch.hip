@@ -1,6 +1,6 @@
 // icp_k_batch.hip -- gfx950 kernels of batched ICP (icp_batch.cpp): the pass of every running pair in one launch (nn_match_batch:
 // front end, matching, moments), the reverse search of reciprocal pairs (nn_match_batch_rev), trimmed rejection and the deferred
-// decision (batch_trim_select, batch_trim_moments), the per-pair reduction
+// decision (batch_trim_select, batch_trim_moments), robust kernels (batch_robust_moments), the per-pair reduction
 // (batch_finalize_kernel), the evaluation of every pair at its present pose (batch_eval_moments) and the start clouds of a batch
 // with initial transforms (batch_init_kernel).  The batched neighbours and
 // normals (knn4_batch, normals_batch_kernel) live with the single-pair ones in icp_k_plane.hip.  Reference statements: the loop a
@@ -450,6 +450,116 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_trim_moments(const BatchItem* 
 }
 #undef ICP_BATCH_POINT_TERMS
 
+// ------------------------------------------------------------------------------------------------
+// robust kernels (icp_batch_set_robust): the decision, the residual, the weight and the weighted terms of a step of a batch that
+// holds a robust pair -- batch_trim_moments' place on the deferred route, over the same items and in its block shape (wave 0 alone
+// carries data, waves 1-3 add zeros, block_sum_store adds a row in the fused pass's order).
+//   kept: batch_trim_moments' tests, restated -- (tau == NULL || d <= tau[pair]) && (thr == NULL || d <= thr[pair]), and with
+//     MUTUAL (its own instantiations: the others never read rev or recip) && (recip[pair] == 0 || rev[idx[i]] == i).  A rejected
+//     point's idx entry gets BATCH_IDX_REJECTED and its weight entry 0.0.
+//   residual, in double from the widened coordinates: point-to-point r2 = dx*dx + dy*dy + dz*dz, d = q - p (the front end's error
+//     arithmetic); point-to-plane r2 = bi * bi, the bi of the plane terms.
+//   weight w, in double, from kind[pair], k[pair], k2[pair] = k * k (the host's product): Huber r2 <= k2 ? 1 : k / sqrt(r2), Cauchy
+//     1 / (1 + r2 / k2), Tukey r2 <= k2 ? (1 - r2/k2)^2 : 0, none 1.0 exactly.  r2 = +inf: 0 for all three.  weights[gi] = w.
+//   terms: ICP_MOM_CNT = 1, ICP_MOM_W = w, every other slot the fused pass's term times w.  w = 1.0 multiplies exactly, so a
+//     pair without a kernel has the rows of batch_trim_moments bit for bit.
+// The block writes slots 1 .. ICP_MOM_W of its row -- zeros in the slots between the metric's last one and ICP_MOM_W, which no
+// other launch writes -- and leaves ICP_MOM_ERR, the matching launch's.  A pair that takes part in the step without matching (the
+// loop's error-only last pass) gets zeros throughout: nothing of an earlier pass's weight sum stays in the row.
+// The point's terms are restated, not routed through ICP_BATCH_POINT_TERMS: the existing kernels keep their listings (see that
+// macro's comment).  No LDS beyond block_sum_store's 4 x 29 doubles.
+// ------------------------------------------------------------------------------------------------
+template <typename F, int METRIC, bool MUTUAL>
+__global__ __launch_bounds__(NN_BLOCK) void batch_robust_moments(const BatchItem* __restrict__ items, const BatchPair* __restrict__ pairs,
+                                                                 const int* __restrict__ mode, const F* __restrict__ P, long long p_plane,
+                                                                 const F* __restrict__ Q, const F* __restrict__ Nrm, long long q_plane,
+                                                                 int32_t* __restrict__ idx_cur, const F* __restrict__ dist,
+                                                                 const F* __restrict__ tau, const F* __restrict__ thr,
+                                                                 const int* __restrict__ kind, const double* __restrict__ ks,
+                                                                 const double* __restrict__ k2s, double* __restrict__ weights,
+                                                                 double* __restrict__ partials, const int32_t* __restrict__ rev,
+                                                                 const uint8_t* __restrict__ recip)
+{
+    constexpr int NACC = ICP_MOM_W + 1;
+    static_assert(ICP_MOM_ERR == 0 && BatchAcc<METRIC>::N <= ICP_MOM_W && ICP_MOM_W < ICP_NMOM, "the weight sum sits behind every slot of either metric");
+    const BatchItem it = items[blockIdx.x];
+    const int pm = mode[it.pair];
+    if (pm == 0) return;   // the pair takes no part in this step: its row is not read
+    const BatchPair pr = pairs[it.pair];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    if ((pm & BATCH_MATCH) && w == 0 && lane < it.count) {
+        const long long gi = pr.p_off + it.first + lane;
+        const F* Qx = Q + pr.q_off;
+        const F* Qy = Qx + q_plane;
+        const F* Qz = Qx + 2 * q_plane;
+        const F b = dist[gi];
+        const int j = idx_cur[gi];   // in [0, m): the matching launch wrote it
+        bool kept = (tau == nullptr || b <= tau[it.pair]) && (thr == nullptr || b <= thr[it.pair]);
+        if constexpr (MUTUAL) kept = kept && (recip[it.pair] == 0 || rev[pr.q_off + j] == it.first + lane);
+        double wgt = 0.0;
+        if (!kept) {
+            idx_cur[gi] = j | BATCH_IDX_REJECTED;   // (a rejected point adds nothing: every accumulator stays 0, the count included)
+        } else {
+            const double px = (double)P[gi], py = (double)P[p_plane + gi], pz = (double)P[2 * p_plane + gi];
+            const double qx = (double)Qx[j], qy = (double)Qy[j], qz = (double)Qz[j];
+            const int kd = kind[it.pair];
+            const double kk = ks[it.pair], kk2 = k2s[it.pair];
+            double r2, nx = 0.0, ny = 0.0, nz = 0.0, bi = 0.0;
+            if constexpr (METRIC == ICP_POINT_TO_POINT) {
+                const double dx = qx - px, dy = qy - py, dz = qz - pz;
+                r2 = dx * dx + dy * dy + dz * dz;
+            } else {
+                const F* Nx = Nrm + pr.q_off;
+                nx = (double)Nx[j]; ny = (double)Nx[q_plane + j]; nz = (double)Nx[2 * q_plane + j];
+                bi = (px - qx) * nx + (py - qy) * ny + (pz - qz) * nz;
+                r2 = bi * bi;
+            }
+            wgt = 1.0;
+            if (kd == ICP_ROBUST_HUBER) {
+                wgt = r2 <= kk2 ? 1.0 : kk / sqrt(r2);
+            } else if (kd == ICP_ROBUST_CAUCHY) {
+                wgt = 1.0 / (1.0 + r2 / kk2);
+            } else if (kd == ICP_ROBUST_TUKEY) {
+                const double u = 1.0 - r2 / kk2;
+                wgt = r2 <= kk2 ? u * u : 0.0;
+            }
+            acc[ICP_MOM_CNT] = 1.0;
+            acc[ICP_MOM_W] = wgt;
+            if constexpr (METRIC == ICP_POINT_TO_POINT) {
+                acc[ICP_MOM_SP + 0] = px * wgt; acc[ICP_MOM_SP + 1] = py * wgt; acc[ICP_MOM_SP + 2] = pz * wgt;
+                acc[ICP_MOM_SQ + 0] = qx * wgt; acc[ICP_MOM_SQ + 1] = qy * wgt; acc[ICP_MOM_SQ + 2] = qz * wgt;
+                acc[ICP_MOM_SQP + 0] = (qx * px) * wgt; acc[ICP_MOM_SQP + 1] = (qx * py) * wgt; acc[ICP_MOM_SQP + 2] = (qx * pz) * wgt;
+                acc[ICP_MOM_SQP + 3] = (qy * px) * wgt; acc[ICP_MOM_SQP + 4] = (qy * py) * wgt; acc[ICP_MOM_SQP + 5] = (qy * pz) * wgt;
+                acc[ICP_MOM_SQP + 6] = (qz * px) * wgt; acc[ICP_MOM_SQP + 7] = (qz * py) * wgt; acc[ICP_MOM_SQP + 8] = (qz * pz) * wgt;
+                acc[ICP_MOM_SPP] = (px * px + py * py + pz * pz) * wgt;
+                acc[ICP_MOM_SQQ] = (qx * qx + qy * qy + qz * qz) * wgt;
+            } else {
+                double cn[6];
+                cn[0] = py * nz - pz * ny;
+                cn[1] = pz * nx - px * nz;
+                cn[2] = px * ny - py * nx;
+                cn[3] = nx; cn[4] = ny; cn[5] = nz;
+                int o = ICP_MOM_C;
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int c = a; c < 6; ++c) acc[o++] += (cn[a] * cn[c]) * wgt;
+#pragma unroll
+                for (int a = 0; a < 6; ++a) acc[ICP_MOM_B + a] -= (cn[a] * bi) * wgt;
+            }
+        }
+        weights[gi] = wgt;
+    }
+    double tail[NACC - 1];
+#pragma unroll
+    for (int k = 1; k < NACC; ++k) tail[k - 1] = acc[k];
+    block_sum_store<NACC - 1, NN_BLOCK>(tail, partials + (size_t)blockIdx.x * ICP_NMOM + 1);
+}
+
 // one block per pair: mom[pair] = the pair's item rows added up in a fixed order (thread (k, part) adds items part, part + 8, ...
 // of slot k; the eight part sums are then added in part order -- finalize_kernel's scheme, over the pair's own items only).
 // last = the metric's last slot: ICP_MOM_SQQ, or ICP_MOM_B + 5 for a plane loop; the slots behind it are written as zeros.
@@ -480,6 +590,7 @@ hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st)
     if (plane && !a.N_soa) return hipErrorInvalidValue;
     if (a.trim_rank && (!a.dist || !a.tau)) return hipErrorInvalidValue;
     if (a.recip && (!a.dist || !a.rev || !a.q_items || a.n_q_items <= 0)) return hipErrorInvalidValue;
+    if (a.robust_kind && (!a.robust_k || !a.robust_k2 || !a.weights || !a.dist)) return hipErrorInvalidValue;
 #define ICP_LAUNCH_BATCH(F, MET, GATE)                                                                                           \
     hipLaunchKernelGGL((nn_match_batch<F, MET, GATE>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs, a.mode,          \
                        (const RT<F>*)a.rt, (F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)a.N_soa, a.q_plane, a.idx_prev,   \
@@ -513,9 +624,31 @@ hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st)
                            (const F*)a.dist, a.trim_rank ? (const F*)a.tau : (const F*)nullptr, (const F*)a.thr, a.partials,      \
                            (const int32_t*)a.rev, a.recip);                                                                       \
     } while (0)
+    // a batch with a robust pair: matching without a decision, [the reverse search,] [the K-th distance of every pair,] then the
+    // decision, the weights and the weighted terms
+#define ICP_LAUNCH_BATCH_ROBUST(F, MET, MUT)                                                                                     \
+    do {                                                                                                                         \
+        hipLaunchKernelGGL((nn_match_batch<F, MET, true, true>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs,        \
+                           a.mode, (const RT<F>*)a.rt, (F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)nullptr, a.q_plane,   \
+                           a.idx_prev, a.idx_cur, a.partials, (const F*)nullptr, (F*)a.dist);                                     \
+        if (MUT)                                                                                                                 \
+            hipLaunchKernelGGL((nn_match_batch_rev<F>), dim3(a.n_q_items), dim3(NN_BLOCK), 0, st, a.q_items, a.pairs, a.mode,     \
+                               a.recip, (const F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, a.q_plane, a.rev);                       \
+        if (a.trim_rank)                                                                                                         \
+            hipLaunchKernelGGL((batch_trim_select<F>), dim3(a.n_pairs), dim3(TRIM_BLOCK), 0, st, a.pairs, a.mode, a.trim_rank,    \
+                               (const F*)a.dist, (F*)a.tau);                                                                      \
+        hipLaunchKernelGGL((batch_robust_moments<F, MET, MUT>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs,         \
+                           a.mode, (const F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)a.N_soa, a.q_plane, a.idx_cur,      \
+                           (const F*)a.dist, a.trim_rank ? (const F*)a.tau : (const F*)nullptr, (const F*)a.thr, a.robust_kind,   \
+                           a.robust_k, a.robust_k2, a.weights, a.partials, (const int32_t*)a.rev, a.recip);                       \
+    } while (0)
 #define ICP_LAUNCH_BATCH_F(F)                                                                                                  \
     do {                                                                                                                       \
-        if (a.recip) {                                                                                                         \
+        if (a.robust_kind && a.recip) {                                                                                        \
+            if (plane) ICP_LAUNCH_BATCH_ROBUST(F, ICP_POINT_TO_PLANE, true); else ICP_LAUNCH_BATCH_ROBUST(F, ICP_POINT_TO_POINT, true); \
+        } else if (a.robust_kind) {                                                                                            \
+            if (plane) ICP_LAUNCH_BATCH_ROBUST(F, ICP_POINT_TO_PLANE, false); else ICP_LAUNCH_BATCH_ROBUST(F, ICP_POINT_TO_POINT, false); \
+        } else if (a.recip) {                                                                                                         \
             if (plane) ICP_LAUNCH_BATCH_RECIP(F, ICP_POINT_TO_PLANE); else ICP_LAUNCH_BATCH_RECIP(F, ICP_POINT_TO_POINT);      \
         } else if (a.trim_rank) {                                                                                                   \
             if (plane) ICP_LAUNCH_BATCH_TRIM(F, ICP_POINT_TO_PLANE); else ICP_LAUNCH_BATCH_TRIM(F, ICP_POINT_TO_POINT);        \
@@ -527,12 +660,13 @@ hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st)
     } while (0)
     if (a.precision == ICP_F64) ICP_LAUNCH_BATCH_F(double); else ICP_LAUNCH_BATCH_F(float);
 #undef ICP_LAUNCH_BATCH_F
+#undef ICP_LAUNCH_BATCH_ROBUST
 #undef ICP_LAUNCH_BATCH_RECIP
 #undef ICP_LAUNCH_BATCH_TRIM
 #undef ICP_LAUNCH_BATCH
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     hipLaunchKernelGGL(batch_finalize_kernel, dim3(a.n_pairs), dim3(256), 0, st, a.pairs, a.mode, (const double*)a.partials,
-                       plane ? ICP_MOM_B + 5 : ICP_MOM_SQQ, a.mom);
+                       a.robust_kind ? ICP_MOM_W : plane ? ICP_MOM_B + 5 : ICP_MOM_SQQ, a.mom);
     return hipGetLastError();
 }
 

@@ -4,7 +4,7 @@
 //   icp_k_row64.hip   nn_match_row64       rows of 64 points: the hall scan and everything up to 32 768 points
 //   icp_k_f64.hip     nn_match_row64_f64   the CPU path's precision on the same structure
 //   icp_k_dense.hip   nn_match_kernel / nn_match_f32_v2 (every pair), merge, moments, transform + error, finalize, layout
-//   icp_k_batch.hip   nn_match_batch (many pairs per launch), nn_match_batch_rev (reciprocal pairs), trimmed rejection, per-pair finalize, initial transforms
+//   icp_k_batch.hip   nn_match_batch (many pairs per launch), nn_match_batch_rev (reciprocal pairs), trimmed rejection, robust kernels, per-pair finalize, initial transforms
 //   icp_k_plane.hip   kNN(4) + normals, OS1 decode + conversion
 //   icp_k_setup.hip   duplicates, spatial order, boxes / samples / records, row order + roles, the control block of a pass
 //   icp_launch.hip    the dispatch (launch_nn): host code only
@@ -353,6 +353,15 @@ struct BatchPassArgs {
     int32_t* rev;              // [q_plane], laid out as the models (written only with recip; dist is needed too)
     const BatchItem* q_items;  // the model's work items (launch_batch_normals' q_items; read only with recip)
     int n_q_items;
+    // NULL, or int[n_pairs], every pair's robust kernel (ICP_ROBUST_*), at least one of them not NONE: the pass then always runs
+    // deferred -- nn_match_batch<.., DEFER>, nn_match_batch_rev (with recip), batch_trim_select (with trim_rank) and
+    // batch_robust_moments<.., MUTUAL = recip given>: kept as batch_trim_moments decides it, w = the kernel's weight of the match's
+    // residual (double), weights[i] = w (0.0 where rejected), ICP_MOM_CNT = the kept count, ICP_MOM_W = sum w, every other slot
+    // the term times w; the reduction then runs to ICP_MOM_W.  Three launches with nothing else, up to five.
+    const int* robust_kind;
+    const double* robust_k;    // double[n_pairs]: every pair's scale k (read only where the kind is not NONE; with robust_kind)
+    const double* robust_k2;   // double[n_pairs]: k * k, the host's product
+    double* weights;           // double[p_plane], laid out as idx (written only with robust_kind; dist is needed too)
 };
 hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st);
 // evaluation of every pair whose mode is BATCH_MATCH at its present pose (icp_batch_evaluate): the deferred matching launch

@@ -296,9 +296,30 @@ class Context:
             max_iter = 50 if metric == capi.ICP_POINT_TO_PLANE else 40
         return self._run_batch_gated(metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init, trim, reciprocal)
 
+    def register_batch_robust(self, pairs, kernel, scale, **options):
+        """register_batch with a robust kernel: kernel ("huber", "cauchy", "tukey", None or an ICP_ROBUST_* integer) and scale (the
+        kernel's k, in the clouds' unit) for every pair, or one of each per pair (Batch.set_robust).  Every kept match pulls with a
+        weight in [0, 1] that falls smoothly with its residual; the loop is iteratively re-weighted least squares.  options:
+        register_batch's, by keyword.  The same list of Result, with extra["weights"] added: the (n,) float64 weights of each
+        pair's most recent matching pass (0.0 where the match was rejected)."""
+        unknown = set(options) - {"metric", "normals", "max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal"}
+        if unknown:
+            raise TypeError(f"register_batch_robust: unknown option(s) {sorted(unknown)}")
+        metric = options.get("metric", capi.ICP_POINT_TO_POINT)
+        max_iter = options.get("max_iter")
+        if max_iter is None:
+            max_iter = 50 if metric == capi.ICP_POINT_TO_PLANE else 40
+        return self._run_batch_options(metric, pairs, options.get("normals"), max_iter, options.get("tol", 1e-6),
+                                       options.get("fixed_iterations", False), options.get("max_distance"), options.get("init"),
+                                       options.get("trim"), options.get("reciprocal"), (kernel, scale))
+
     def _run_batch_gated(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init=None, trim=None, reciprocal=None):
         """the one-call functions have neither a gate nor initial transforms nor trimming nor reciprocity: create, [normals],
         set_max_distance, set_initial_transforms, set_trim, set_reciprocal, begin, run to the end, results"""
+        return self._run_batch_options(metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init, trim, reciprocal, None)
+
+    def _run_batch_options(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init, trim, reciprocal, robust):
+        """... and robust: None, or (kernel, scale) for set_robust -- the results then carry extra["weights"]"""
         with Batch(self, pairs) as bt:
             if metric == capi.ICP_POINT_TO_PLANE:
                 if normals is not None:
@@ -311,15 +332,20 @@ class Context:
                 bt.set_trim(trim)
             if reciprocal is not None:
                 bt.set_reciprocal(reciprocal)
+            if robust is not None:
+                bt.set_robust(*robust)
             bt.begin(max_iter=max_iter, tol=tol, fixed_iterations=fixed_iterations, metric=metric)
             while bt.run(1 << 20)[1] > 0:
                 pass
             idx, inl, moved = bt.loop_indices(), bt.loop_inliers(), bt.get_moving()
+            wts = bt.get_weights() if robust is not None else None
             out = []
             for b in range(bt.count):
                 st = bt.state(b)
                 out.append(Result(T=st["T"].copy(), iterations=st["iterations"], passes=st["passes"], err=st["err"], idx=idx[b], moved=moved[b],
                                   extra={"status": st["status"], "inliers": inl[b], "fitness": float(inl[b].sum()) / inl[b].size}))
+                if wts is not None:
+                    out[-1].extra["weights"] = wts[b]
             return out
 
     def _run_batch(self, metric, pairs, normals, max_iter, tol, fixed_iterations):
@@ -460,6 +486,10 @@ def _batch_normals(normals, Ms, dtype):
     return np.concatenate(Ns)
 
 
+_ROBUST_KINDS = {None: capi.ICP_ROBUST_NONE, "none": capi.ICP_ROBUST_NONE, "huber": capi.ICP_ROBUST_HUBER,
+                 "cauchy": capi.ICP_ROBUST_CAUCHY, "tukey": capi.ICP_ROBUST_TUKEY}
+
+
 class Batch:
     """icp_batch: (D, M) pairs of one dtype resident on the context's device; every step runs the pass of every pair still
     running in one launch.  Each pair's loop is the one Context.point_to_point (point_to_plane, with the batch's normals) runs
@@ -581,6 +611,37 @@ class Batch:
         out = np.empty(int(self._qoff[-1]), dtype=np.int32)
         capi.check(self._lib.icp_diag_batch_reverse(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))), "icp_diag_batch_reverse")
         return [out[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
+
+    def set_robust(self, kind, scale=None):
+        """robust kernels: kind None (none), one kernel for every pair, or one per pair -- "huber", "cauchy", "tukey", None or the
+        ICP_ROBUST_* integers; scale: the kernel's k, one value for every pair or one per pair (not read where the kind is None).
+        Every kept match of a robust pair enters the sums of a pass with the kernel's weight of its residual (point-to-point: the
+        distance to the match; point-to-plane: the distance along the match's normal); gate, trim and reciprocity decide as ever.
+        Discards a loop under way."""
+        if kind is None:
+            capi.check(self._lib.icp_batch_set_robust(self._h, None, None), "icp_batch_set_robust")
+            return
+        kinds = [kind] * self.count if isinstance(kind, (str, int, np.integer)) else list(kind)
+        if len(kinds) != self.count:
+            raise ValueError("one robust kernel per pair (or one for every pair, or None)")
+        k = np.ascontiguousarray([_ROBUST_KINDS[x] if (x is None or isinstance(x, str)) else int(x) for x in kinds], dtype=np.intc)
+        sp = None
+        if scale is not None:
+            a = np.asarray(scale, dtype=np.float64)
+            if a.ndim == 0:
+                a = np.full(self.count, float(a))
+            a = np.ascontiguousarray(a)
+            if a.shape != (self.count,):
+                raise ValueError("one scale per pair (or a scalar)")
+            sp = a.ctypes.data_as(C.POINTER(C.c_double))
+        capi.check(self._lib.icp_batch_set_robust(self._h, k.ctypes.data_as(C.POINTER(C.c_int)), sp), "icp_batch_set_robust")
+
+    def get_weights(self):
+        """per pair, (n,) float64: the weight of every moving point's match in the pair's most recent matching pass
+        (icp_batch_get_weights): 0.0 where the match was rejected, 1.0 for a kept match of a pair without a kernel"""
+        out = np.empty(int(self._moff[-1]), dtype=np.float64)
+        capi.check(self._lib.icp_batch_get_weights(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_get_weights")
+        return self._split(out)
 
     def set_initial_transforms(self, T):
         """the pose every pair's registration starts from: one (4, 4) for every pair, (count, 4, 4), or None (none).  Rounded once

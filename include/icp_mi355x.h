@@ -68,6 +68,7 @@ typedef struct icp_ctx icp_ctx; /* opaque: owns device buffers, stream, pinned s
 #define ICP_MOM_SQQ 18 /* sum |q[idx]|^2  fast path, whose rows the host adds itself, leaves them 0)                         */
 #define ICP_MOM_C 2    /* point-to-plane: upper triangle of C, row-major (21) */
 #define ICP_MOM_B 23   /* point-to-plane: b (6) */
+#define ICP_MOM_W 29   /* sum of the weights of the kept matches (robust batches; both metrics) */
 
 typedef struct icp_params {
     int max_iter;         /* MAX_ITER: 200 src/ICP_CPU.c:17, 40 src/ICP_point_to_point.cu:24, 50 ICP_point_to_plane.cu:23 */
@@ -348,6 +349,42 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *       cost: the reverse search is a second scan of m x n distances in a launch of its own (one block per 64 model points),
  *         so a step of a batch with a reciprocal pair runs four launches (matching, reverse search, decision and sums,
  *         reduction), five when it also trims, and still one download.
+ *   - robust kernels (icp_batch_set_robust): one kind (ICP_ROBUST_*) and one scale k per pair.  Every kept match of a robust pair
+ *     pulls with a weight w(r) in [0, 1] that falls smoothly with its residual r -- M-estimator weighting, solved as iteratively
+ *     re-weighted least squares (Open3D's RobustKernel): the remedy that needs no keep-or-drop decision.  kind == NULL, or every
+ *     kind ICP_ROBUST_NONE: the batch is not robust; it runs the steps and produces the bits of a batch that never heard of this.
+ *       validation: every kind is one of the four constants; for a kind other than NONE, scale[p] = k must be finite and > 0 and
+ *         k * k (formed in double) finite and > 0; the scale of a NONE pair is not read, and scale == NULL is allowed only if
+ *         every kind is NONE.  Anything else is ICP_ERR_INVALID, the message names the first offending pair, and the batch keeps
+ *         what it had.  A null batch is ICP_ERR_INVALID, a context with a pending pass ICP_ERR_STATE.  Like the other
+ *         icp_batch_set_* calls it may come at any time after icp_batch_create and discards a loop under way.
+ *       residual, every term formed in double from the widened coordinates of the match (p, q = Q[idx], n = N[idx]):
+ *         point-to-point r2 = dx*dx + dy*dy + dz*dz with d = q - p (the front end's error arithmetic); point-to-plane r2 = bi *
+ *         bi with bi = (px-qx)*nx + (py-qy)*ny + (pz-qz)*nz, the bi the plane terms form.
+ *       weight, in double, k2 = k * k formed once on the host:  ICP_ROBUST_HUBER  r2 <= k2 ? 1 : k / sqrt(r2);
+ *         ICP_ROBUST_CAUCHY  1 / (1 + r2 / k2);  ICP_ROBUST_TUKEY  r2 <= k2 ? (1 - r2/k2)^2 : 0;  ICP_ROBUST_NONE  exactly 1.0.
+ *         All three are continuous in r: no decision hangs on a rounding.  An overflowed r2 = +inf gives 0, never a NaN.
+ *       combination: kept is decided exactly as without kernels -- gate, trim (tau still ranks all n distances) and the mutual
+ *         rule.  Weights change no mask and no idx, and nothing icp_batch_get_inliers reports; a kept point whose weight is 0 is
+ *         still kept.
+ *       sums: ICP_MOM_CNT stays the kept count; ICP_MOM_W = sum w over the kept points; every other slot of the pass is the term
+ *         it always was times the point's w (point-to-point SP, SQ, SQP, SPP, SQQ; point-to-plane C, B).  ICP_MOM_ERR is
+ *         unchanged: unweighted, over the points the previous matching pass kept; err[k] = sqrt(ERR_k) / sqrt(CNT_{k-1}), the stop
+ *         rule and the iteration counting are untouched.
+ *       solve: on a copy of the vector whose ICP_MOM_CNT slot holds ICP_MOM_W (icp_host_loop_set_weighted): the point-to-point
+ *         solve divides by that slot -- the weighted Kabsch solve -- and the plane solve never reads it.  A matching pass whose
+ *         ICP_MOM_W is not > 0 ends the pair with ICP_ERR_EMPTY (unless the stop rule ended the loop on that very pass).
+ *       bits: in a robust batch a pair of kind NONE has the bits of that pair in the same batch without kernels (w = 1.0
+ *         multiplies exactly; the rows are added in the same block shape and order), and a robust pair's bits depend on that
+ *         pair, its kernel, its scale and its other options alone: no floating-point atomics, fixed summation order.  Initial
+ *         transforms: weights act on residuals measured after the transform.  icp_batch_evaluate neither reads nor changes
+ *         kernels or weights.
+ *       icp_batch_get_weights: one double per moving point, each pair's most recent matching pass, with the errors and ordering
+ *         of icp_batch_get_indices: 0.0 for a rejected point, 1.0 for a kept point of a NONE pair; a batch without kernels
+ *         answers the kept mask as 1.0 / 0.0.  The device buffer behind it exists only once a batch is given kernels.
+ *       cost: a step of a robust batch always runs deferred -- matching, [reverse search,] [selection,] batch_robust_moments
+ *         (decision, residual, weight, weighted terms), reduction: three launches with nothing else, up to five with reciprocity
+ *         and trimming, still one download.
  *   - evaluation (icp_batch_evaluate): did pair p register, and how well is it constrained?  Per pair the fitness (the share of
      its moving points with a model point within a distance of the caller's choosing), the inlier RMSE and the 6 x 6
      information matrix a pose-graph optimiser takes beside T -- measured where the pair's moving cloud stands on the device,
@@ -387,7 +424,7 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
        cost: three launches (the loop's deferred matching with nothing applied, the decision and the terms, the reduction) and
          one download of 32 doubles per pair, plus the indices when idx_out or mask_out is given.
      Not gated, not trimmed and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the
- *     multi-GPU sums -- a single pair that needs any of them is a batch of one.  Trimming is the only rejection by rank: there
+ *     multi-GPU sums -- a single pair that needs any of them is a batch of one; nor do they weigh matches by a robust kernel.  Trimming is the only rejection by rank: there
  *     is no other percentile rejection (none by a multiple of the median or of the standard deviation of the distances). */
 typedef struct icp_batch icp_batch;
 #define ICP_BATCH_MAX_POINTS 65536 /* per cloud of one pair */
@@ -420,6 +457,16 @@ int icp_batch_set_max_distance(icp_batch* b, const double* max_dist);
 int icp_batch_set_trim(icp_batch* b, const double* keep_ratio);
 /* per-pair reciprocity: count bytes, non-zero = that pair keeps only mutual nearest neighbours; NULL = off for the whole batch */
 int icp_batch_set_reciprocal(icp_batch* b, const uint8_t* on);
+/* per-pair robust kernel: count ints (ICP_ROBUST_*) + count doubles (the scale k of every pair whose kind is not NONE), or
+ * kind == NULL: no robust kernels */
+#define ICP_ROBUST_NONE 0
+#define ICP_ROBUST_HUBER 1
+#define ICP_ROBUST_CAUCHY 2
+#define ICP_ROBUST_TUKEY 3
+int icp_batch_set_robust(icp_batch* b, const int* kind, const double* scale);
+/* 1 double per moving point, concatenated as the moving clouds: the weight of each pair's most recent matching pass (0.0 = the
+ * match was rejected; as icp_batch_get_indices) */
+int icp_batch_get_weights(icp_batch* b, double* w_out);
 /* count x 16 doubles, one row-major 4x4 per pair (the layout of icp_result.T), or NULL = no initial transforms */
 int icp_batch_set_initial_transforms(icp_batch* b, const double* T16);
 /* per-pair fitness, inlier RMSE and information matrix where the moving clouds stand (above); max_dist: count doubles or NULL;
@@ -483,6 +530,11 @@ int icp_host_loop_create(const icp_params* prm, icp_host_loop** out);
 void icp_host_loop_destroy(icp_host_loop* h);
 int icp_host_loop_advance(icp_host_loop* h, const double* mom /*ICP_NMOM*/, int* done, double* R9, double* t3);
 int icp_host_loop_note_applied(icp_host_loop* h);
+/* on != 0: the vectors are those of a robust pass -- every advance from now on solves on a copy of the vector whose ICP_MOM_CNT slot
+ * holds mom[ICP_MOM_W] (the weighted Kabsch solve; the plane solve never reads the slot), and a matching pass whose ICP_MOM_W is
+ * not > 0 ends the loop with ICP_ERR_EMPTY.  The error, its divisor (the kept count), the stop rule and the iteration counting
+ * do not change.  Off (the default): the loop is the one it always was. */
+int icp_host_loop_set_weighted(icp_host_loop* h, int on);
 int icp_host_loop_state(icp_host_loop* h, int* iterations, int* passes, double* err, int err_cap, double* T16);
 /* contiguous shard [begin, begin+count) of n moving points for `rank` of `world`.  Any partition of the moving points is the same
  * registration, and a registration is as slow as its slowest rank: where the work per point varies over a LARGE cloud (BASELINE

@@ -76,7 +76,9 @@ int icp_diag_row_roles(icp_ctx* ctx, uint32_t* hits_io, int rows, int min_part, 
 int icp_diag_loop_moments(icp_ctx* ctx, double* out32, int* route);
 /* the same for pair `pair` of a batch: the row of the step's download that pair's loop last advanced on (the rows are always
  * added by batch_finalize_kernel; they come from nn_match_batch's fused tail, or from batch_trim_moments in a batch that trims
- * or holds a reciprocal pair).
+ * or holds a reciprocal pair, or from batch_robust_moments in a batch with a robust kernel: there slot ICP_MOM_W = 29 holds the sum
+ * of the kept matches' weights, ICP_MOM_CNT stays the kept count and every other slot behind ICP_MOM_ERR is weighted; in every
+ * other batch slot 29 is 0).
  * ICP_ERR_STATE before the pair's first completed pass. */
 int icp_diag_batch_moments(icp_batch* b, int pair, double* out32);
 /* trimmed rejection of pair `pair` (icp_batch_set_trim): *tau_sq = the threshold of the pair's most recent matching pass -- the

@@ -3,7 +3,7 @@
 for all pairs) against a loop of Context.point_to_point / point_to_plane over the same pairs (GPU box).
 
   python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE] [--only CASE,CASE] [--max-distance V] [--trim R]
-                              [--reciprocal] [--label TEXT] [--init | --premoved] [--evaluate]
+                              [--reciprocal] [--robust KIND:SCALE] [--label TEXT] [--init | --premoved] [--evaluate]
 
 Cases, --metric point: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids
 (make_model_gpu, tol 1e-6); 16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  --metric plane: the fp32 case sets and the
@@ -32,6 +32,12 @@ reverse search, four launches per step, five with --trim), combinable with --max
 such rule, so the passes are not compared.  The cost of reciprocity is --reciprocal against --trim R of the same build (the
 deferred route without the reverse search), and --reciprocal --trim R against both.  With --evaluate the timed steps (first_step_s,
 step_s) and the registration run with the gate, the trim and the flags given; the evaluation itself never looks at them.
+
+--robust KIND:SCALE (huber, cauchy or tukey, and the kernel's k in the clouds' unit) runs the batched side with that robust kernel on
+every pair (Context.register_batch_robust: the deferred route with batch_robust_moments, three launches per step, up to five with
+--reciprocal and --trim), combinable with the options above.  The sequential side has no kernels, so the passes are not compared.
+The cost of a robust step is --robust against a run without it of the same build (--evaluate: step_s), and against --trim R (the
+deferred route without the weights).
 
 --init times the batched side from a far pose -- every moving cloud carried off by G (40 degrees about z, shifted by (3, -2, 1))
 outside the timed region -- with the inverse pose as every pair's initial transform (Context.point_to_*_batch(init=...)).
@@ -103,6 +109,7 @@ def main():
     ap.add_argument("--max-distance", type=float, default=None, help="gate the batched side at this distance (inf: the gated kernels, nothing rejected)")
     ap.add_argument("--trim", type=float, default=None, help="keep this share of every moving cloud on the batched side (the deferred route)")
     ap.add_argument("--reciprocal", action="store_true", help="every pair keeps only mutual nearest neighbours on the batched side (the deferred route with the reverse search)")
+    ap.add_argument("--robust", default="", metavar="KIND:SCALE", help="every pair weighs its matches with this robust kernel on the batched side, e.g. cauchy:0.05")
     ap.add_argument("--label", default="", help="copied into every row")
     ap.add_argument("--init", action="store_true", help="the batched side starts from a far pose with the inverse pose as initial transform")
     ap.add_argument("--premoved", action="store_true", help="the baseline of --init: the far clouds moved back on the host, no initial transform, same route")
@@ -143,6 +150,12 @@ def main():
         gate = a.max_distance
         trim = a.trim
         recip = True if a.reciprocal else None
+        robust = None
+        if a.robust:
+            kind, _, scale = a.robust.partition(":")
+            if kind not in ("huber", "cauchy", "tukey") or not scale:
+                sys.exit("--robust KIND:SCALE with KIND huber, cauchy or tukey")
+            robust = (kind, float(scale))
         for name, pairs, normals, it, tol in todo:
             if only and name not in only:
                 continue
@@ -151,6 +164,9 @@ def main():
             metric = pkg.ICP_POINT_TO_PLANE if plane else pkg.ICP_POINT_TO_POINT
 
             def run_batched():
+                if robust:
+                    return ctx.register_batch_robust(bat_pairs, robust[0], robust[1], metric=metric, normals=normals, max_iter=it, tol=tol,
+                                                     max_distance=gate, init=G_inv if a.init else None, trim=trim, reciprocal=recip)
                 if a.init or a.premoved or recip:   # through the Batch object (--init / --premoved differ by the initial transforms alone)
                     return ctx._run_batch_gated(metric, bat_pairs, normals, it, tol, False, gate, G_inv if a.init else None, trim, recip)
                 if plane and (gate is not None or trim is not None):
@@ -185,6 +201,8 @@ def main():
                         bt.set_trim(trim)
                     if recip:
                         bt.set_reciprocal(True)
+                    if robust:
+                        bt.set_robust(*robust)
 
                     def timed(fn):
                         t0 = time.perf_counter()
@@ -210,7 +228,7 @@ def main():
                            evaluate_s=med(ev) if have else None, evaluate_s_min=float(min(ev)) if have else None,
                            evaluate_s_max=float(max(ev)) if have else None, evaluate_matches_s=med(evm) if have else None,
                            reps=a.reps, pairs_stopping_apart=0, max_distance=None if gate is None else str(gate), trim=trim,
-                           reciprocal=bool(recip), label=a.label)
+                           reciprocal=bool(recip), robust=a.robust or None, label=a.label)
                 rows.append(row)
                 print(json.dumps(row), flush=True)
                 continue
@@ -235,7 +253,7 @@ def main():
                 ts.append(s)
                 tl.append(loops)
             # the same registrations: every pair must run the same passes on both sides (checked when all rows are out)
-            apart = sum(1 for x, y in zip(pb, ps) if x != y) if (gate is None or np.isinf(gate)) and (trim is None or trim == 1.0) and not recip else 0
+            apart = sum(1 for x, y in zip(pb, ps) if x != y) if (gate is None or np.isinf(gate)) and (trim is None or trim == 1.0) and not recip and not robust else 0
             pb, ps = sum(pb), sum(ps)
             mb, ms, ml = float(np.median(tb)), float(np.median(ts)), float(np.median(tl))
             row = dict(case=name, pairs=len(pairs), points=int(pairs[0][0].shape[0]), pair_iterations=pb, sequential_pair_iterations=ps, pairs_stopping_apart=apart,
@@ -244,7 +262,7 @@ def main():
                        batched_us_per_pair_it=1e6 * mb / pb, sequential_us_per_pair_it=1e6 * ms / ps,
                        sequential_loops_us_per_pair_it=1e6 * ml / ps, speedup=ms / mb, speedup_vs_loops=ml / mb,
                        batched_s_min=float(min(tb)), batched_s_max=float(max(tb)), reps=a.reps,
-                       max_distance=None if gate is None else str(gate), trim=trim, reciprocal=bool(recip), start="init" if a.init else "premoved" if a.premoved else "uploaded",
+                       max_distance=None if gate is None else str(gate), trim=trim, reciprocal=bool(recip), robust=a.robust or None, start="init" if a.init else "premoved" if a.premoved else "uploaded",
                        label=a.label)
             rows.append(row)
             print(json.dumps(row), flush=True)
