@@ -112,6 +112,9 @@ SIGNATURES = {
     "icp_batch_get_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_batch_loop_inliers": (_i, [_vp, C.POINTER(C.c_uint8)]),
     "icp_batch_evaluate": (_i, [_vp, _i, _pd, _pi, _pi32, _pd, _pd, _pd, _pi32, C.POINTER(C.c_uint8)]),
+    "icp_batch_downsample": (_i, [_vp, _pd, _pd, _pi32, _pi32, C.POINTER(_vp)]),
+    "icp_batch_get_offsets": (_i, [_vp, _pi64, _pi64]),
+    "icp_batch_get_clouds": (_i, [_vp, _vp, _vp]),
     "icp_point_to_point_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_point_to_plane_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, _vp, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_comm_unique_id": (_i, [_vp]),

@@ -52,6 +52,14 @@
 // pair: three launches, none of which writes idx, mom, tau, thr or ctl of the loop.  Fitness, inlier RMSE and the 6 x 6 information
 // matrix are assembled on the host from that vector alone.  The loop does not notice the call.
 //
+// A batch is thinned on the device (icp_batch_downsample): a new batch on the same context whose clouds are P0 and Q of the source,
+// reduced to one point per occupied cell of a voxel grid per cloud -- the rule, which numpy reproduces bit for bit, is stated in
+// include/icp_mi355x.h.  batch_voxel_keys (bounds, range check, keys)  ->  batch_voxel_group (first point of every cell, the
+// sequential sums)  ->  batch_voxel_rank (output ranks, counts, maps)  ->  [D2H: 2 x count counts and range flags, the first wait;
+// the new batch is laid out and allocated as icp_batch_create does it: lay_out + allocate]  ->  batch_voxel_compact (the centroids
+// into the new planes)  ->  the second wait.  Four launches, two waits; the source is only read, its loop does not notice, and the
+// temporaries live for the call.
+//
 // Point-to-plane needs the model normals of every pair, in planes laid out as the models: given by the caller
 // (icp_batch_set_model_normals) or made on the device by ONE neighbour launch + ONE normals launch for the whole batch
 // (icp_batch_estimate_normals: knn4_batch + normals_batch_kernel, icp_k_plane.hip).  The reference estimates them once per
@@ -291,19 +299,53 @@ void put_rt(void* dst, const double* R, const double* t)
     for (int k = 0; k < 3; ++k) o[9 + k] = (F)t[k];
 }
 
-int upload(icp_batch* b, const void* moving, const void* model)
+// a new, empty batch on c: the layout two offset arrays give it -- where every pair's clouds start in the planes, its work items
+// (host only; icp_batch_create and icp_batch_downsample both start here)
+int lay_out(icp_ctx* c, int count, int precision, const int64_t* moving_off, const int64_t* model_off, icp_batch** out)
+{
+    icp_batch* b = new (std::nothrow) icp_batch();
+    if (!b) return fail(ICP_ERR_NOMEM, "batch");
+    b->ctx = c;
+    b->count = count;
+    b->prec = precision;
+    b->esize = precision == ICP_F64 ? sizeof(double) : sizeof(float);
+    b->moff.assign(moving_off, moving_off + count + 1);
+    b->qoff.assign(model_off, model_off + count + 1);
+    b->pairs.resize((size_t)count);
+    long long items = 0;
+    for (int p = 0; p < count; ++p) {
+        icp::BatchPair& pr = b->pairs[p];
+        pr.n = (int)(moving_off[p + 1] - moving_off[p]);
+        pr.m = (int)(model_off[p + 1] - model_off[p]);
+        pr.p_off = b->p_plane;
+        pr.q_off = b->q_plane;
+        b->p_plane += icp::round_up(pr.n, icp::BATCH_ALIGN);
+        b->q_plane += icp::round_up(pr.m, icp::BATCH_ALIGN);
+        pr.item0 = (int)std::min<long long>(items, INT_MAX);
+        items += (pr.n + icp::BATCH_ITEM - 1) / icp::BATCH_ITEM;
+        pr.item1 = (int)std::min<long long>(items, INT_MAX);
+    }
+    if (items > INT_MAX) {
+        delete b;
+        return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    }
+    b->n_items = (int)items;
+    b->H.resize((size_t)count);
+    reset_loop_state(b);
+    *out = b;
+    return ICP_OK;
+}
+
+// everything of a laid-out batch but its clouds: the planes (not filled), the work items and the pairs on the device, the loop's
+// buffers.  Enqueues the copy of `items`, which must outlive it: the caller synchronises.
+int allocate(icp_batch* b, std::vector<icp::BatchItem>& items)
 {
     icp_ctx* c = b->ctx;
     const size_t pb = 3 * (size_t)b->p_plane * b->esize, qb = 3 * (size_t)b->q_plane * b->esize;
     HIP_TRY(b->P.ensure(pb));
     HIP_TRY(b->P0.ensure(pb));
     HIP_TRY(b->Q.ensure(qb));
-    std::vector<char> ps, qs;
-    if (int rc = enqueue_planes(b, moving, false, b->P0.p, ps)) return rc;
-    if (int rc = enqueue_planes(b, model, true, b->Q.p, qs)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));   // (before the host vectors go)
-    HIP_TRY(hipMemcpyAsync(b->P.p, b->P0.p, pb, hipMemcpyDeviceToDevice, c->stream));
-    const std::vector<icp::BatchItem> items = work_items(b, false);
+    items = work_items(b, false);
     HIP_TRY(b->items.ensure(items.size() * sizeof(icp::BatchItem)));
     HIP_TRY(b->pairs_d.ensure(b->pairs.size() * sizeof(icp::BatchPair)));
     HIP_TRY(hipMemcpyAsync(b->items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, c->stream));
@@ -320,7 +362,138 @@ int upload(icp_batch* b, const void* moving, const void* model)
     HIP_TRY(hipHostMalloc(&b->h_ctl, b->ctl_bytes, hipHostMallocDefault));
     std::memset(b->h_ctl, 0, b->ctl_bytes);
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_mom), (size_t)b->count * ICP_NMOM * sizeof(double), hipHostMallocDefault));
-    HIP_TRY(hipStreamSynchronize(c->stream));   // (items: a host vector)
+    return ICP_OK;
+}
+
+// the caller's clouds into the planes of an allocated batch
+int upload(icp_batch* b, const void* moving, const void* model)
+{
+    icp_ctx* c = b->ctx;
+    std::vector<icp::BatchItem> items;
+    std::vector<char> ps, qs;
+    int rc = allocate(b, items);
+    if (rc == ICP_OK) rc = enqueue_planes(b, moving, false, b->P0.p, ps);
+    if (rc == ICP_OK) rc = enqueue_planes(b, model, true, b->Q.p, qs);
+    const hipError_t es = hipStreamSynchronize(c->stream);   // (always, a refusal included: before the host vectors go)
+    if (rc != ICP_OK) return rc;
+    HIP_TRY(es);
+    HIP_TRY(hipMemcpyAsync(b->P.p, b->P0.p, 3 * (size_t)b->p_plane * b->esize, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ICP_OK;
+}
+
+// the per-point temporaries of one icp_batch_downsample: released when the call returns, whichever way -- after what the call
+// enqueued has ended (the host vectors of its copies are declared before this and so outlive it)
+struct VoxelTmp {
+    hipStream_t st;
+    DevBuf clouds, items, voxel, keys, too_fine, first, cent, rank, map, count;
+    explicit VoxelTmp(hipStream_t s) : st(s) {}
+    ~VoxelTmp()
+    {
+        (void)hipStreamSynchronize(st);
+        for (DevBuf* d : {&clouds, &items, &voxel, &keys, &too_fine, &first, &cent, &rank, &map, &count}) d->release();
+    }
+};
+
+// icp_batch_downsample after its argument checks; *made: the new batch as far as it got (the caller releases it on failure)
+int downsample(icp_batch* src, const std::vector<double>& voxel, int32_t* moving_map_out, int32_t* model_map_out, icp_batch** made)
+{
+    icp_ctx* c = src->ctx;
+    hipStream_t st = c->stream;
+    const int count = src->count, n_clouds = 2 * count;
+    // the 2 * count clouds, moving clouds first, and their work items; every cloud owns a stretch of the temporaries
+    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
+    std::vector<icp::BatchItem> items, new_items;
+    std::vector<int> too_fine((size_t)n_clouds);
+    std::vector<int32_t> cells((size_t)n_clouds), hmap;
+    long long tmp_plane = 0;
+    for (int k = 0; k < n_clouds; ++k) {
+        const int side = k < count ? 0 : 1;
+        const icp::BatchPair& pr = src->pairs[k - side * count];
+        icp::VoxelCloud& cl = clouds[k];
+        cl.side = side;
+        cl.n = side ? pr.m : pr.n;
+        cl.src_off = side ? pr.q_off : pr.p_off;
+        cl.tmp_off = tmp_plane;
+        cl.dst_off = 0;
+        tmp_plane += icp::round_up(cl.n, icp::BATCH_ALIGN);
+        for (int first = 0; first < cl.n; first += icp::BATCH_ITEM)
+            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, cl.n - first), 0});
+    }
+    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    VoxelTmp t(st);
+    HIP_TRY(t.clouds.ensure(clouds.size() * sizeof(icp::VoxelCloud)));
+    HIP_TRY(t.items.ensure(items.size() * sizeof(icp::BatchItem)));
+    HIP_TRY(t.voxel.ensure(voxel.size() * sizeof(double)));
+    HIP_TRY(t.keys.ensure((size_t)tmp_plane * sizeof(unsigned long long)));
+    HIP_TRY(t.too_fine.ensure((size_t)n_clouds * sizeof(int)));
+    HIP_TRY(t.first.ensure((size_t)tmp_plane * sizeof(int32_t)));
+    HIP_TRY(t.cent.ensure(3 * (size_t)tmp_plane * src->esize));
+    HIP_TRY(t.rank.ensure((size_t)tmp_plane * sizeof(int32_t)));
+    HIP_TRY(t.map.ensure((size_t)tmp_plane * sizeof(int32_t)));
+    HIP_TRY(t.count.ensure((size_t)n_clouds * sizeof(int32_t)));
+    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t.items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t.voxel.p, voxel.data(), voxel.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    icp::BatchVoxelArgs a{};
+    a.precision = src->prec;
+    a.clouds = (const icp::VoxelCloud*)t.clouds.p;
+    a.n_clouds = n_clouds;
+    a.items = (const icp::BatchItem*)t.items.p;
+    a.n_items = (int)items.size();
+    a.voxel = (const double*)t.voxel.p;
+    a.src[0] = src->P0.p;
+    a.src[1] = src->Q.p;
+    a.src_plane[0] = src->p_plane;
+    a.src_plane[1] = src->q_plane;
+    a.tmp_plane = tmp_plane;
+    a.keys = (unsigned long long*)t.keys.p;
+    a.too_fine = (int*)t.too_fine.p;
+    a.first = (int32_t*)t.first.p;
+    a.cent = t.cent.p;
+    a.rank = (int32_t*)t.rank.p;
+    a.map = (int32_t*)t.map.p;
+    a.count = (int32_t*)t.count.p;
+    HIP_TRY(icp::launch_batch_voxel_group(a, st));
+    HIP_TRY(hipMemcpyAsync(too_fine.data(), t.too_fine.p, too_fine.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(cells.data(), t.count.p, cells.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the first wait: the new batch's layout needs every cloud's count
+    for (int p = 0; p < count; ++p)
+        for (int side = 0; side < 2; ++side)
+            if (too_fine[(size_t)side * count + p])
+                return fail(ICP_ERR_INVALID, "the voxel grid is too fine for the cloud's extent (a cell index above 2097151): pair " + std::to_string(p) +
+                                                 (side ? ", model" : ", moving cloud"));
+    std::vector<int64_t> moff((size_t)count + 1, 0), qoff((size_t)count + 1, 0);
+    for (int p = 0; p < count; ++p) {
+        if (cells[p] < 1 || cells[p] > src->pairs[p].n || cells[(size_t)count + p] < 1 || cells[(size_t)count + p] > src->pairs[p].m)
+            return fail(ICP_ERR_HIP, "icp_batch_downsample: a cloud's cell count is out of range");   // (cannot happen: every cloud has a point)
+        moff[p + 1] = moff[p] + cells[p];
+        qoff[p + 1] = qoff[p] + cells[(size_t)count + p];
+    }
+    if (int rc = lay_out(c, count, src->prec, moff.data(), qoff.data(), made)) return rc;
+    icp_batch* nb = *made;
+    if (int rc = allocate(nb, new_items)) return rc;
+    for (int k = 0; k < n_clouds; ++k) clouds[k].dst_off = k < count ? nb->pairs[k].p_off : nb->pairs[k - count].q_off;
+    const size_t pb = 3 * (size_t)nb->p_plane * nb->esize, qb = 3 * (size_t)nb->q_plane * nb->esize;
+    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(nb->P0.p, 0, pb, st));   // (the padding between the clouds: all-zero bytes, as an upload leaves it)
+    HIP_TRY(hipMemsetAsync(nb->Q.p, 0, qb, st));
+    a.dst[0] = nb->P0.p;
+    a.dst[1] = nb->Q.p;
+    a.dst_plane[0] = nb->p_plane;
+    a.dst_plane[1] = nb->q_plane;
+    HIP_TRY(icp::launch_batch_voxel_compact(a, st));
+    HIP_TRY(hipMemcpyAsync(nb->P.p, nb->P0.p, pb, hipMemcpyDeviceToDevice, st));
+    if (moving_map_out || model_map_out) {
+        hmap.resize((size_t)tmp_plane);
+        HIP_TRY(hipMemcpyAsync(hmap.data(), t.map.p, hmap.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // the second wait: the host vectors go, the temporaries are freed
+    for (int p = 0; p < count; ++p) {
+        if (moving_map_out) std::memcpy(moving_map_out + src->moff[p], hmap.data() + clouds[p].tmp_off, (size_t)src->pairs[p].n * sizeof(int32_t));
+        if (model_map_out)
+            std::memcpy(model_map_out + src->qoff[p], hmap.data() + clouds[(size_t)count + p].tmp_off, (size_t)src->pairs[p].m * sizeof(int32_t));
+    }
     return ICP_OK;
 }
 
@@ -443,41 +616,69 @@ int icp_batch_create(icp_ctx* c, int count, const void* moving_aos, const int64_
     if (!finite) return fail(ICP_ERR_INVALID, "a cloud of the batch has a NaN or an infinite coordinate");
     if (int rc = ctx_ready(c)) return rc;
     ScopedPin pin(c);
-    icp_batch* b = new (std::nothrow) icp_batch();
-    if (!b) return fail(ICP_ERR_NOMEM, "batch");
-    b->ctx = c;
-    b->count = count;
-    b->prec = precision;
-    b->esize = precision == ICP_F64 ? sizeof(double) : sizeof(float);
-    b->moff.assign(moving_off, moving_off + count + 1);
-    b->qoff.assign(model_off, model_off + count + 1);
-    b->pairs.resize((size_t)count);
-    long long items = 0;
-    for (int p = 0; p < count; ++p) {
-        icp::BatchPair& pr = b->pairs[p];
-        pr.n = (int)(moving_off[p + 1] - moving_off[p]);
-        pr.m = (int)(model_off[p + 1] - model_off[p]);
-        pr.p_off = b->p_plane;
-        pr.q_off = b->q_plane;
-        b->p_plane += icp::round_up(pr.n, icp::BATCH_ALIGN);
-        b->q_plane += icp::round_up(pr.m, icp::BATCH_ALIGN);
-        pr.item0 = (int)std::min<long long>(items, INT_MAX);
-        items += (pr.n + icp::BATCH_ITEM - 1) / icp::BATCH_ITEM;
-        pr.item1 = (int)std::min<long long>(items, INT_MAX);
-    }
-    if (items > INT_MAX) {
-        delete b;
-        return fail(ICP_ERR_INVALID, "too many work items for one batch");
-    }
-    b->n_items = (int)items;
-    b->H.resize((size_t)count);
-    reset_loop_state(b);
+    icp_batch* b = nullptr;
+    if (int rc = lay_out(c, count, precision, moving_off, model_off, &b)) return rc;
     if (int rc = upload(b, moving_aos, model_aos)) {
         (void)hipStreamSynchronize(c->stream);
         release(b);
         return rc;
     }
     *out = b;
+    return ICP_OK;
+}
+
+int icp_batch_downsample(icp_batch* src, const double* voxel_moving, const double* voxel_model, int32_t* moving_map_out,
+                         int32_t* model_map_out, icp_batch** out)
+{
+    if (!out) return fail(ICP_ERR_INVALID, "out == NULL");
+    *out = nullptr;
+    if (int rc = ready(src)) return rc;
+    std::vector<double> voxel(2 * (size_t)src->count, 0.0);   // the moving clouds' edges, then the models'
+    for (int p = 0; p < src->count; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const double* given = side ? voxel_model : voxel_moving;
+            const double v = given ? given[p] : 0.0;
+            if (!(std::isfinite(v) && v >= 0.0))   // (NaN fails both)
+                return fail(ICP_ERR_INVALID, std::string("a voxel edge must be finite and > 0, or exactly 0 (copy): pair ") + std::to_string(p) +
+                                                 (side ? ", model" : ", moving cloud"));
+            voxel[(size_t)side * src->count + p] = v;
+        }
+    ScopedPin pin(src->ctx);
+    icp_batch* made = nullptr;
+    const int rc = downsample(src, voxel, moving_map_out, model_map_out, &made);
+    if (rc != ICP_OK) {   // src was only read; what the call enqueued ends before its host vectors and the new batch go
+        (void)hipStreamSynchronize(src->ctx->stream);
+        (void)hipGetLastError();
+        if (made) release(made);
+        return rc;
+    }
+    *out = made;
+    return ICP_OK;
+}
+
+int icp_batch_get_offsets(icp_batch* b, int64_t* moving_off_out, int64_t* model_off_out)
+{
+    if (!b) return fail(ICP_ERR_INVALID, "null batch");
+    if (moving_off_out) std::memcpy(moving_off_out, b->moff.data(), b->moff.size() * sizeof(int64_t));
+    if (model_off_out) std::memcpy(model_off_out, b->qoff.data(), b->qoff.size() * sizeof(int64_t));
+    return ICP_OK;
+}
+
+int icp_batch_get_clouds(icp_batch* b, void* moving_aos_out, void* model_aos_out)
+{
+    if (int rc = ready(b)) return rc;
+    std::vector<char> ps, qs;
+    if (moving_aos_out) {
+        ps.resize(3 * (size_t)b->p_plane * b->esize);
+        HIP_TRY(hipMemcpyAsync(ps.data(), b->P0.p, ps.size(), hipMemcpyDeviceToHost, b->ctx->stream));
+    }
+    if (model_aos_out) {
+        qs.resize(3 * (size_t)b->q_plane * b->esize);
+        HIP_TRY(hipMemcpyAsync(qs.data(), b->Q.p, qs.size(), hipMemcpyDeviceToHost, b->ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    if (moving_aos_out) planes_to_aos(b, ps, false, moving_aos_out);
+    if (model_aos_out) planes_to_aos(b, qs, true, model_aos_out);
     return ICP_OK;
 }
 

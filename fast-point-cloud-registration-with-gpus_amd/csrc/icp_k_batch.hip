@@ -1,8 +1,9 @@
 // icp_k_batch.hip -- gfx950 kernels of batched ICP (icp_batch.cpp): the pass of every running pair in one launch (nn_match_batch:
 // front end, matching, moments), the reverse search of reciprocal pairs (nn_match_batch_rev), trimmed rejection and the deferred
 // decision (batch_trim_select, batch_trim_moments), robust kernels (batch_robust_moments), the per-pair reduction
-// (batch_finalize_kernel), the evaluation of every pair at its present pose (batch_eval_moments) and the start clouds of a batch
-// with initial transforms (batch_init_kernel).  The batched neighbours and
+// (batch_finalize_kernel), the evaluation of every pair at its present pose (batch_eval_moments), the start clouds of a batch
+// with initial transforms (batch_init_kernel) and voxel-grid downsampling (batch_voxel_keys, batch_voxel_group, batch_voxel_rank,
+// batch_voxel_compact).  The batched neighbours and
 // normals (knn4_batch, normals_batch_kernel) live with the single-pair ones in icp_k_plane.hip.  Reference statements: the loop a
 // pair runs is src/ICP_point_to_point.cu:295-423 / src/ICP_point_to_plane.cu:517-631; the kernels restate nn_match_kernel,
 // moments_kernel and transform_error_kernel (icp_k_dense.hip) per work item.
@@ -814,6 +815,230 @@ hipError_t launch_batch_init(int precision, const BatchItem* items, int n_items,
     else
         hipLaunchKernelGGL((batch_init_kernel<float>), dim3(nb), dim3(NN_BLOCK), 0, st, items, n_items, pairs, kind, (const RT<float>*)rt0,
                            (const float*)P0, (float*)P, p_plane, nonfinite);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// voxel-grid downsampling of every cloud of a batch (icp_batch_downsample, icp_batch.cpp; the rule is stated in
+// include/icp_mi355x.h and every step here is one statement of it).  Brute force, as the matching kernels: a cloud has at most
+// ICP_BATCH_MAX_POINTS points, so nothing is sorted.
+//   batch_voxel_keys    one block per cloud: lo, hi = the component-wise minimum and maximum (comparisons only: exact), the range
+//                       check floor(((double)hi - (double)lo) / v) <= VOXEL_MAX_CELL per axis -> too_fine[cloud], and every point's
+//                       key = cx | cy << 21 | cz << 42 with c = floor(((double)x - (double)lo) / v): one subtraction, one IEEE
+//                       division (never a reciprocal), one floor, all in double
+//   batch_voxel_group   one wave per work item, one point per lane: the lane scans its cloud's keys in ascending j through LDS
+//                       tiles of VOXEL_TILE keys and points.  The first j with its key is its cell's first point (first[i]); a lane
+//                       that is that point itself goes on and adds the later members as they come, s += (double)x_j from s = 0.0 in
+//                       ascending j -- the sequential sum of the rule -- and leaves (F)(s / (double)c), or its own bytes where it
+//                       is alone, in cent.  The wave stops when every lane knows its cell and none leads one.
+//   batch_voxel_rank    one block per cloud: an exclusive scan of the flags first[i] == i in chunks of VOXEL_SCAN_BLOCK (a wave scan
+//                       by shuffles, the four waves' totals through LDS, a running carry) -> rank, count[cloud]; then
+//                       map[i] = rank[first[i]]
+//   batch_voxel_compact one wave per work item: a leading point's cent goes to the new batch's planes at dst_off + rank
+// No atomics of any kind: every output element has one writer and every sum one order.  v == 0.0: the cloud is copied -- every
+// point leads its own cell: no keys, no search, and rank and map are the point's own index (no scan).  A cloud of too_fine is skipped by the later kernels (the host refuses the call).
+// ------------------------------------------------------------------------------------------------
+template <typename F>
+__global__ __launch_bounds__(VOXEL_SCAN_BLOCK) void batch_voxel_keys(const BatchVoxelArgs a)
+{
+    __shared__ F s_lo[VOXEL_SCAN_BLOCK / 64][3], s_hi[VOXEL_SCAN_BLOCK / 64][3];
+    const int cloud = blockIdx.x;
+    const double v = a.voxel[cloud];
+    if (v == 0.0) {
+        if (threadIdx.x == 0) a.too_fine[cloud] = 0;
+        return;
+    }
+    const VoxelCloud c = a.clouds[cloud];
+    const long long sp = a.src_plane[c.side];
+    const F* S = static_cast<const F*>(a.src[c.side]) + c.src_off;
+    F lo[3], hi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) lo[k] = hi[k] = S[k * sp];
+    for (int i = threadIdx.x; i < c.n; i += VOXEL_SCAN_BLOCK)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const F x = S[k * sp + i];
+            lo[k] = x < lo[k] ? x : lo[k];
+            hi[k] = x > hi[k] ? x : hi[k];
+        }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const F ol = __shfl_xor(lo[k], off, 64), oh = __shfl_xor(hi[k], off, 64);
+            lo[k] = ol < lo[k] ? ol : lo[k];
+            hi[k] = oh > hi[k] ? oh : hi[k];
+        }
+        if ((threadIdx.x & 63) == 0) {
+            s_lo[threadIdx.x >> 6][k] = lo[k];
+            s_hi[threadIdx.x >> 6][k] = hi[k];
+        }
+    }
+    __syncthreads();
+    bool bad = false;
+    double dlo[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = s_lo[0][k];
+        hi[k] = s_hi[0][k];
+#pragma unroll
+        for (int w = 1; w < VOXEL_SCAN_BLOCK / 64; ++w) {
+            lo[k] = s_lo[w][k] < lo[k] ? s_lo[w][k] : lo[k];
+            hi[k] = s_hi[w][k] > hi[k] ? s_hi[w][k] : hi[k];
+        }
+        dlo[k] = (double)lo[k];
+        const double top = floor(((double)hi[k] - dlo[k]) / v);   // (the largest index of the axis: every step is monotonic)
+        bad = bad || !(top <= (double)VOXEL_MAX_CELL);
+    }
+    if (threadIdx.x == 0) a.too_fine[cloud] = bad ? 1 : 0;
+    if (bad) return;
+    unsigned long long* keys = a.keys + c.tmp_off;
+    for (int i = threadIdx.x; i < c.n; i += VOXEL_SCAN_BLOCK) {
+        unsigned long long key = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double cell = floor(((double)S[k * sp + i] - dlo[k]) / v);
+            key |= (unsigned long long)cell << (21 * k);
+        }
+        keys[i] = key;
+    }
+}
+
+template <typename F>
+__global__ __launch_bounds__(BATCH_ITEM) void batch_voxel_group(const BatchVoxelArgs a)
+{
+    __shared__ unsigned long long s_key[VOXEL_TILE];
+    __shared__ F s_x[3][VOXEL_TILE];
+    const BatchItem it = a.items[blockIdx.x];
+    const VoxelCloud c = a.clouds[it.pair];
+    const int lane = threadIdx.x;
+    const bool active = lane < it.count;
+    const int i = it.first + lane;
+    const long long sp = a.src_plane[c.side];
+    const F* S = static_cast<const F*>(a.src[c.side]) + c.src_off;
+    F* cent = static_cast<F*>(a.cent) + c.tmp_off;
+    int32_t* first_out = a.first + c.tmp_off;
+    if (a.voxel[it.pair] == 0.0) {   // copied: the point's bytes, every point its own cell
+        if (active) {
+            first_out[i] = i;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) cent[k * a.tmp_plane + i] = S[k * sp + i];
+        }
+        return;
+    }
+    if (a.too_fine[it.pair]) return;
+    const unsigned long long* keys = a.keys + c.tmp_off;
+    const unsigned long long mine = active ? keys[i] : ~0ull;   // (a key has 63 bits: no point's cell is all ones)
+    int first = -1, members = 0;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int base = 0; base < c.n; base += VOXEL_TILE) {
+        const int len = min(VOXEL_TILE, c.n - base);
+        __syncthreads();
+        for (int j = lane; j < len; j += BATCH_ITEM) {
+            s_key[j] = keys[base + j];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s_x[k][j] = S[k * sp + base + j];
+        }
+        __syncthreads();
+        for (int j = 0; j < len; ++j) {
+            if (s_key[j] == mine) {
+                if (first < 0) first = base + j;
+                if (first == i) {   // this lane leads the cell: its own point first, then the later members as they come
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) s[k] += (double)s_x[k][j];
+                    ++members;
+                }
+            }
+        }
+        if (__all(!active || (first >= 0 && first != i))) break;   // (the whole wave: no barrier is skipped by a part of it)
+    }
+    if (!active) return;
+    first_out[i] = first;
+    if (first != i) return;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        cent[k * a.tmp_plane + i] = members == 1 ? S[k * sp + i] : (F)(s[k] / (double)members);
+}
+
+__global__ __launch_bounds__(VOXEL_SCAN_BLOCK) void batch_voxel_rank(const BatchVoxelArgs a)
+{
+    __shared__ int s_wave[VOXEL_SCAN_BLOCK / 64];
+    const int cloud = blockIdx.x;
+    if (a.too_fine[cloud]) {
+        if (threadIdx.x == 0) a.count[cloud] = 0;
+        return;
+    }
+    const VoxelCloud c = a.clouds[cloud];
+    const int32_t* first = a.first + c.tmp_off;
+    int32_t* rank = a.rank + c.tmp_off;
+    int32_t* map = a.map + c.tmp_off;
+    if (a.voxel[cloud] == 0.0) {   // copied: every point leads its own cell, in its place -- nothing to scan
+        for (int i = threadIdx.x; i < c.n; i += VOXEL_SCAN_BLOCK) rank[i] = map[i] = i;
+        if (threadIdx.x == 0) a.count[cloud] = c.n;
+        return;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0;
+    for (int base = 0; base < c.n; base += VOXEL_SCAN_BLOCK) {
+        const int i = base + threadIdx.x;
+        const int flag = (i < c.n && first[i] == i) ? 1 : 0;
+        int incl = flag;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int up = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += up;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < VOXEL_SCAN_BLOCK / 64; ++w) {
+            before += w < wave ? s_wave[w] : 0;
+            total += s_wave[w];
+        }
+        if (i < c.n) rank[i] = carry + before + incl - flag;
+        carry += total;
+        __syncthreads();   // (s_wave is rewritten by the next chunk; after the last one: the block's ranks are written)
+    }
+    if (threadIdx.x == 0) a.count[cloud] = carry;
+    for (int i = threadIdx.x; i < c.n; i += VOXEL_SCAN_BLOCK) map[i] = rank[first[i]];
+}
+
+template <typename F>
+__global__ __launch_bounds__(BATCH_ITEM) void batch_voxel_compact(const BatchVoxelArgs a)
+{
+    const BatchItem it = a.items[blockIdx.x];
+    const int lane = threadIdx.x;
+    if (lane >= it.count) return;
+    const VoxelCloud c = a.clouds[it.pair];
+    const int i = it.first + lane;
+    if (a.first[c.tmp_off + i] != i) return;
+    const F* cent = static_cast<const F*>(a.cent) + c.tmp_off;
+    F* D = static_cast<F*>(a.dst[c.side]) + c.dst_off + a.rank[c.tmp_off + i];
+    const long long dp = a.dst_plane[c.side];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) D[k * dp] = cent[k * a.tmp_plane + i];
+}
+
+hipError_t launch_batch_voxel_group(const BatchVoxelArgs& a, hipStream_t st)
+{
+    if (a.n_clouds <= 0 || a.n_items <= 0) return hipSuccess;
+    if (a.precision == ICP_F64) {
+        hipLaunchKernelGGL((batch_voxel_keys<double>), dim3(a.n_clouds), dim3(VOXEL_SCAN_BLOCK), 0, st, a);
+        hipLaunchKernelGGL((batch_voxel_group<double>), dim3(a.n_items), dim3(BATCH_ITEM), 0, st, a);
+    } else {
+        hipLaunchKernelGGL((batch_voxel_keys<float>), dim3(a.n_clouds), dim3(VOXEL_SCAN_BLOCK), 0, st, a);
+        hipLaunchKernelGGL((batch_voxel_group<float>), dim3(a.n_items), dim3(BATCH_ITEM), 0, st, a);
+    }
+    hipLaunchKernelGGL(batch_voxel_rank, dim3(a.n_clouds), dim3(VOXEL_SCAN_BLOCK), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_voxel_compact(const BatchVoxelArgs& a, hipStream_t st)
+{
+    if (a.n_items <= 0) return hipSuccess;
+    if (a.precision == ICP_F64) hipLaunchKernelGGL((batch_voxel_compact<double>), dim3(a.n_items), dim3(BATCH_ITEM), 0, st, a);
+    else hipLaunchKernelGGL((batch_voxel_compact<float>), dim3(a.n_items), dim3(BATCH_ITEM), 0, st, a);
     return hipGetLastError();
 }
 

@@ -400,6 +400,39 @@ hipError_t launch_batch_init(int precision, const BatchItem* items, int n_items,
 // normals_batch_kernel launch (Nrm_soa laid out as Q_soa)
 hipError_t launch_batch_normals(int precision, const BatchItem* q_items, int n_q_items, const BatchPair* pairs, const void* Q_soa,
                                 long long q_plane, int32_t* nbr, void* Nrm_soa, hipStream_t st);
+// voxel-grid downsampling of every cloud of a batch (icp_batch_downsample; the rule: include/icp_mi355x.h).  The 2 * n_pairs clouds
+// are numbered moving clouds first, then the models; cloud c reads the planes of its side (src[side], src_plane[side]) and owns
+// the elements [tmp_off, tmp_off + n) of every per-point temporary.  Work items: BATCH_ITEM points of one cloud (BatchItem::pair =
+// the cloud's number), over both sides.
+constexpr int VOXEL_TILE = 512;          // keys (and their points) per LDS tile of batch_voxel_group
+constexpr int VOXEL_SCAN_BLOCK = 256;    // threads of batch_voxel_keys / batch_voxel_rank: one block per cloud
+constexpr long long VOXEL_MAX_CELL = 2097151;   // 21 bits per axis
+struct VoxelCloud { long long src_off, tmp_off, dst_off; int n, side; };   // dst_off: where the thinned cloud starts in dst[side] (read by the compaction only)
+struct BatchVoxelArgs {
+    int precision;             // ICP_F32 / ICP_F64
+    const VoxelCloud* clouds;  // [2 * n_pairs]
+    int n_clouds;
+    const BatchItem* items;    // the work items of all clouds, in cloud order
+    int n_items;
+    const double* voxel;       // double[n_clouds]: the grid's edge, 0.0 = copy
+    const void* src[2];        // P0 and Q of the source batch (read only)
+    long long src_plane[2];
+    long long tmp_plane;       // elements of every per-point temporary: all clouds of both sides, each at a multiple of BATCH_ALIGN
+    unsigned long long* keys;  // [tmp]: the cell of every point, 21 bits per axis
+    int* too_fine;             // int[n_clouds]: 1 where an axis has a cell index above VOXEL_MAX_CELL (written for every cloud)
+    int32_t* first;            // [tmp]: the lowest index of the point's cell within its cloud (== its own index: it leads the cell)
+    void* cent;                // F[3][tmp]: the output point of every leading point
+    int32_t* rank;             // [tmp]: leading points before this one in its cloud (the output index of a leading point)
+    int32_t* map;              // [tmp]: the output index of the point's cell
+    int32_t* count;            // int32[n_clouds]: occupied cells
+    void* dst[2];              // P0 and Q of the new batch (the compaction)
+    long long dst_plane[2];
+};
+// batch_voxel_keys (bounds, range check, keys; one block per cloud) -> batch_voxel_group (one wave per work item: first, cent) ->
+// batch_voxel_rank (one block per cloud: rank, map, count).  Three launches; dst is not read.
+hipError_t launch_batch_voxel_group(const BatchVoxelArgs& a, hipStream_t st);
+// batch_voxel_compact: dst[side][k * dst_plane + dst_off + rank[i]] = cent[k][i] for every leading point i.  One launch.
+hipError_t launch_batch_voxel_compact(const BatchVoxelArgs& a, hipStream_t st);
 
 // soa2 (optional): a second copy of the result (the pristine moving cloud); enc (optional, fp32): the cloud's bounding cube as six
 // ordered-integer words {~ord(min xyz), ord(max xyz)}, zero before the launch

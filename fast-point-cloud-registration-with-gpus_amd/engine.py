@@ -313,6 +313,75 @@ class Context:
                                        options.get("fixed_iterations", False), options.get("max_distance"), options.get("init"),
                                        options.get("trim"), options.get("reciprocal"), (kernel, scale))
 
+    def register_batch_multiscale(self, pairs, voxels, **options):
+        """coarse-to-fine register_batch on a voxel pyramid made on the device: the pairs are uploaded once, and level l runs on
+        that batch thinned at voxels[l] (Batch.downsample; 0 or None: full resolution, the uploaded batch itself).  voxels:
+        coarsest first.  Level 0 starts from init, level l + 1 from the T every pair's state reported at level l, whatever its
+        status.  options: register_batch's, by keyword, plus kernel and scale as register_batch_robust takes them.
+        max_distance: one value or one per pair (every level), or a list or tuple of len(voxels) such values, one per level (a
+        list of that length always reads per level: give per-pair values as an array).
+        Point-to-plane levels estimate their own normals on the device; normals given together with a level that downsamples is
+        a ValueError.  Returns the last level's list of Result; each carries extra["levels"]: per level a dict of voxel, n, m,
+        status, iterations and T."""
+        known = {"metric", "normals", "max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal", "kernel", "scale"}
+        unknown = set(options) - known
+        if unknown:
+            raise TypeError(f"register_batch_multiscale: unknown option(s) {sorted(unknown)}")
+        voxels = [0.0 if v is None else float(v) for v in voxels]
+        if not voxels:
+            raise ValueError("register_batch_multiscale needs at least one level")
+        metric = options.get("metric", capi.ICP_POINT_TO_POINT)
+        normals = options.get("normals")
+        if normals is not None and any(v != 0.0 for v in voxels):
+            raise ValueError("caller-given normals cannot follow a downsampled model: every level estimates its own")
+        max_iter = options.get("max_iter")
+        if max_iter is None:
+            max_iter = 50 if metric == capi.ICP_POINT_TO_PLANE else 40
+        gate = options.get("max_distance")
+        per_level = isinstance(gate, (list, tuple)) and len(gate) == len(voxels)
+        with Batch(self, pairs) as full:
+            T = options.get("init")
+            levels = [[] for _ in range(full.count)]
+            out = None
+            for l, v in enumerate(voxels):
+                bt = full if v == 0.0 else full.downsample(v)
+                try:
+                    if metric == capi.ICP_POINT_TO_PLANE:
+                        if normals is not None:
+                            bt.set_model_normals(normals)
+                        else:
+                            bt.estimate_normals()
+                    bt.set_max_distance(gate[l] if per_level else gate)
+                    bt.set_initial_transforms(T)
+                    if options.get("trim") is not None:
+                        bt.set_trim(options["trim"])
+                    if options.get("reciprocal") is not None:
+                        bt.set_reciprocal(options["reciprocal"])
+                    if options.get("kernel") is not None:
+                        bt.set_robust(options["kernel"], options.get("scale"))
+                    bt.begin(max_iter=max_iter, tol=options.get("tol", 1e-6), fixed_iterations=options.get("fixed_iterations", False), metric=metric)
+                    while bt.run(1 << 20)[1] > 0:
+                        pass
+                    states = [bt.state(b) for b in range(bt.count)]
+                    T = np.stack([st["T"] for st in states])
+                    for b, st in enumerate(states):
+                        levels[b].append({"voxel": v, "n": int(bt._moff[b + 1] - bt._moff[b]), "m": int(bt._qoff[b + 1] - bt._qoff[b]),
+                                          "status": st["status"], "iterations": st["iterations"], "T": st["T"].copy()})
+                    if l == len(voxels) - 1:
+                        idx, inl, moved = bt.loop_indices(), bt.loop_inliers(), bt.get_moving()
+                        wts = bt.get_weights() if options.get("kernel") is not None else None
+                        out = []
+                        for b, st in enumerate(states):
+                            out.append(Result(T=st["T"].copy(), iterations=st["iterations"], passes=st["passes"], err=st["err"], idx=idx[b], moved=moved[b],
+                                              extra={"status": st["status"], "inliers": inl[b], "fitness": float(inl[b].sum()) / inl[b].size,
+                                                     "levels": levels[b]}))
+                            if wts is not None:
+                                out[-1].extra["weights"] = wts[b]
+                finally:
+                    if bt is not full:
+                        bt.close()
+            return out
+
     def _run_batch_gated(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init=None, trim=None, reciprocal=None):
         """the one-call functions have neither a gate nor initial transforms nor trimming nor reciprocity: create, [normals],
         set_max_distance, set_initial_transforms, set_trim, set_reciprocal, begin, run to the end, results"""
@@ -509,6 +578,59 @@ class Batch:
                                               qoff.ctypes.data_as(p64), _prec(self._dtype), C.byref(h)), "icp_batch_create")
         self._h = h
         self._max_iter = 0
+
+    @classmethod
+    def _from_handle(cls, ctx, h, count, dtype):
+        """a Batch around a ready icp_batch handle (Batch.downsample): its layout is read back with icp_batch_get_offsets"""
+        self = cls.__new__(cls)
+        self._ctx = ctx
+        self._lib = ctx._lib
+        self._h = h
+        self._max_iter = 0
+        self._dtype = dtype
+        self.count = int(count)
+        self._moff = np.zeros(self.count + 1, dtype=np.int64)
+        self._qoff = np.zeros(self.count + 1, dtype=np.int64)
+        p64 = C.POINTER(C.c_int64)
+        capi.check(self._lib.icp_batch_get_offsets(h, self._moff.ctypes.data_as(p64), self._qoff.ctypes.data_as(p64)), "icp_batch_get_offsets")
+        self._model_shapes = [(int(self._qoff[b + 1] - self._qoff[b]), 3) for b in range(self.count)]
+        return self
+
+    def _per_pair(self, v, what):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(self.count, float(a))
+        a = np.ascontiguousarray(a)
+        if a.shape != (self.count,):
+            raise ValueError(f"one {what} per pair (or a scalar)")
+        return a
+
+    def downsample(self, voxel, voxel_model=None, want_maps=False):
+        """a new Batch on the same context whose clouds are this batch's clouds as uploaded, thinned on a voxel grid on the
+        device (icp_batch_downsample): one point per occupied cell, cells in first-occurrence order, a cell's point the mean of
+        its members added in source order in double (a lone point: its own bytes).  voxel: the grid's edge, a scalar or one
+        value per pair, 0 = copy that cloud; voxel_model: the same for the models (None: as voxel).  This batch is only read,
+        and its loop does not notice.  want_maps: also return, per pair, the (n,) and (m,) int32 maps from every source point
+        to its output point: (Batch, moving_maps, model_maps)."""
+        vm = self._per_pair(voxel, "voxel edge")
+        vq = vm if voxel_model is None else self._per_pair(voxel_model, "model voxel edge")
+        pd, p32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        mm = np.empty(int(self._moff[-1]), dtype=np.int32) if want_maps else None
+        qm = np.empty(int(self._qoff[-1]), dtype=np.int32) if want_maps else None
+        h = C.c_void_p()
+        capi.check(self._lib.icp_batch_downsample(self._h, vm.ctypes.data_as(pd), vq.ctypes.data_as(pd), mm.ctypes.data_as(p32) if want_maps else None,
+                                                  qm.ctypes.data_as(p32) if want_maps else None, C.byref(h)), "icp_batch_downsample")
+        out = Batch._from_handle(self._ctx, h, self.count, self._dtype)
+        if not want_maps:
+            return out
+        return out, self._split(mm), [qm[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
+
+    def get_clouds(self):
+        """the clouds the batch holds as uploaded (or as Batch.downsample made them; never the moved cloud): a list of (D, M)"""
+        D = np.empty((int(self._moff[-1]), 3), dtype=self._dtype)
+        M = np.empty((int(self._qoff[-1]), 3), dtype=self._dtype)
+        capi.check(self._lib.icp_batch_get_clouds(self._h, D.ctypes.data, M.ctypes.data), "icp_batch_get_clouds")
+        return [(D[self._moff[b]:self._moff[b + 1]].copy(), M[self._qoff[b]:self._qoff[b + 1]].copy()) for b in range(self.count)]
 
     def close(self):
         if getattr(self, "_h", None):

@@ -37,7 +37,7 @@ extern "C" {
 #endif
 
 #define ICP_ABI_VERSION 2 /* 2: icp_result gained seconds_host / seconds_setup, icp_loop_phase_seconds; later the icp_batch_* entry
-                           * points were added, icp_batch_evaluate among them (new symbols only: nothing that existed changed) */
+                           * points were added, icp_batch_evaluate and icp_batch_downsample among them (new symbols only: nothing that existed changed) */
 
 /* return codes */
 #define ICP_OK 0
@@ -423,6 +423,47 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
          _loop_*, icp_diag_batch_moments and icp_diag_batch_trim answers with the bytes it would have given without the call.
        cost: three launches (the loop's deferred matching with nothing applied, the decision and the terms, the reduction) and
          one download of 32 doubles per pair, plus the indices when idx_out or mask_out is given.
+ *   - voxel-grid downsampling (icp_batch_downsample): a new, thinner batch made on the device from the clouds a batch already
+ *     holds -- same context, same count, same precision, every cloud reduced to one point per occupied cell of a voxel grid of
+ *     its own.  The rule is deterministic and can be reproduced bit for bit in numpy (tests/batch_voxel_ref.py does).
+ *       inputs: voxel_moving and voxel_model hold count doubles each.  A value that is finite and > 0 is the edge v of that
+ *         cloud's grid; exactly 0.0 copies that cloud unchanged, its bytes and its order; a NULL array means every value is 0.0.
+ *         A NaN, a negative or an infinite value: ICP_ERR_INVALID, the message names the first offending pair.  A null src or a
+ *         null out: ICP_ERR_INVALID.  A context with a pending pass: ICP_ERR_STATE.  On any refusal *out is NULL and nothing of
+ *         src changes.
+ *       source: the clouds src holds as uploaded (or as made by an earlier icp_batch_downsample), P0 and Q -- never the moved
+ *         cloud.  The options, the normals and the loop of src are not read.  The loop does not notice: the call neither
+ *         discards nor advances it, and every later icp_batch_run, _state, _get_*, _loop_*, icp_diag_batch_moments and
+ *         icp_diag_batch_trim of src answers with the bytes it would have given without the call.
+ *       cell of a point: lo = the component-wise minimum of the cloud's points (comparisons only: exact in the batch's
+ *         precision F).  For each axis c = floor(((double)x - (double)lo) / v): the subtraction, the division and the floor are
+ *         each one IEEE operation in double, v is the caller's double as given, and nothing is multiplied by a reciprocal.
+ *       range: every cell index must be <= 2097151 (21 bits per axis).  The largest index of an axis is
+ *         floor(((double)hi - (double)lo) / v), hi the component-wise maximum (every step of the expression is monotonic); the
+ *         call checks that value per cloud and axis.  A grid too fine for the cloud's extent: ICP_ERR_INVALID, the message names
+ *         the pair and the side.  How the three indices are packed into a key is internal: only equality of cells is observable.
+ *       output cloud: one point per occupied cell, the cells ordered by the lowest source index they contain (first occurrence).
+ *         Output points therefore keep the order of the input, and a grid so fine that every point is alone returns the input
+ *         cloud byte for byte, in its order.
+ *       output point: a cell with one point outputs that point's bytes -- copied, not computed: a -0.0 survives.  A cell with
+ *         c >= 2 points, per axis: s = 0.0; s += (double)x_i over the members in ascending source index; the output is
+ *         (F)(s / (double)c), one division and one rounding to F.  Nothing is fused, nothing is reordered, and there are no
+ *         floating-point atomics.
+ *       maps: moving_map_out and model_map_out are optional (NULL: not wanted).  Each holds one int32 per source point,
+ *         concatenated in src's layout: the index, within its pair's new cloud, of the output point that source point went into
+ *         (for a copied cloud 0 .. n-1).  What a caller needs to carry colours or labels along.
+ *       independence: a pair's output clouds and maps depend on that pair's cloud and its v alone -- not on the other pairs,
+ *         their order or the batch size.
+ *       new batch: *out is a complete batch, as if icp_batch_create had been called with the output clouds: its own offsets
+ *         (icp_batch_get_offsets), the library's usual alignment and work items, no options, no normals
+ *         (icp_batch_estimate_normals on it estimates from the thinned model and refuses a model left with fewer than 5 points,
+ *         as it always does), no loop under way.  Every cloud keeps at least one point.  It is destroyed on its own, before the
+ *         context; src may be destroyed first.  icp_batch_get_clouds downloads its clouds (or any batch's: P0 and Q).
+ *       cost: four launches (bounds + range check + keys, one block per cloud; grouping and centroids, one wave per 64 points;
+ *         ranks and maps, one block per cloud; compaction into the new batch's planes) and two host waits: one for the cell
+ *         count of every cloud (2 x count int32, with the range flags), which the new batch's layout needs, one at the end (with
+ *         the maps where they are asked for).  The grouping is brute force -- every point compares its key with its cloud's keys,
+ *         n^2 / 64 tile steps per cloud -- and the longest chain is the sequential sum of the most populated cell.
      Not gated, not trimmed and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the
  *     multi-GPU sums -- a single pair that needs any of them is a batch of one; nor do they weigh matches by a robust kernel.  Trimming is the only rejection by rank: there
  *     is no other percentile rejection (none by a multiple of the median or of the standard deviation of the distances). */
@@ -476,6 +517,16 @@ int icp_batch_evaluate(icp_batch* b, int metric, const double* max_dist, int* st
 /* 1 byte per moving point, concatenated as the moving clouds: 1 = that point's match was kept */
 int icp_batch_get_inliers(icp_batch* b, uint8_t* mask_out);   /* each pair's most recent matching pass (as icp_batch_get_indices) */
 int icp_batch_loop_inliers(icp_batch* b, uint8_t* mask_out);  /* each pair's last contributing pass (as icp_batch_loop_indices) */
+/* a new batch on src's context: same count and precision, every pair's clouds thinned on a voxel grid (the rule: above).
+ * voxel_moving / voxel_model: count doubles each (0.0 = copy that cloud), or NULL = copy that side; the maps (1 int32 per source
+ * point, src's layout) may be NULL */
+int icp_batch_downsample(icp_batch* src, const double* voxel_moving, const double* voxel_model, int32_t* moving_map_out,
+                         int32_t* model_map_out, icp_batch** out);
+/* the layout of a batch: count+1 int64 each, as icp_batch_create takes them; either pointer may be NULL */
+int icp_batch_get_offsets(icp_batch* b, int64_t* moving_off_out, int64_t* model_off_out);
+/* the clouds as uploaded / as made by icp_batch_downsample (P0 and Q, never the moved cloud), AoS, concatenated by the offsets
+ * above; either pointer may be NULL */
+int icp_batch_get_clouds(icp_batch* b, void* moving_aos_out, void* model_aos_out);
 /* one call: create + begin + run to the end + results, then destroy.  Every output pointer may be NULL; per pair:
  * T16_out 16, iterations_out / passes_out / status_out 1, err_out max_iter+1 doubles; idx_out and moved_out (3 values per
  * point, precision of the run) concatenated as the moving clouds.  A failed pair is reported in status_out, not in the

@@ -3,7 +3,7 @@
 for all pairs) against a loop of Context.point_to_point / point_to_plane over the same pairs (GPU box).
 
   python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE] [--only CASE,CASE] [--max-distance V] [--trim R]
-                              [--reciprocal] [--robust KIND:SCALE] [--label TEXT] [--init | --premoved] [--evaluate]
+                              [--reciprocal] [--robust KIND:SCALE] [--label TEXT] [--init | --premoved] [--evaluate] [--voxel V]
 
 Cases, --metric point: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids
 (make_model_gpu, tol 1e-6); 16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  --metric plane: the fp32 case sets and the
@@ -50,6 +50,14 @@ sequential side registers the pre-moved clouds, and every pair must run the same
 matches) beside one step of the same batch (Batch.run(1): the first step after begin, which matches only, and the second, which
 applies and matches) and the whole batched registration (batched_s, as in the rows without the option); nothing sequential is
 run.  A build without icp_batch_evaluate (ICP_LIB_PATH) reports the steps and the registration alone (evaluate_s null).
+
+--voxel V times one voxel-grid downsampling of every case's batch on the device (Batch.downsample: four launches, two host waits)
+beside a host path that does the same job -- Batch.get_clouds, the numpy rule (tests/batch_voxel_ref.downsample) and a new Batch
+from the result -- and beside the first and the second step of the same batch; nothing sequential is run.  The cases' clouds differ
+in scale by orders of magnitude, so V is a share of the largest extent of the case's first moving cloud (0.05: about 20 cells along
+it); the row carries the edge itself (voxel_edge) and the points before and after.  Two more rows time one pair of 65 536
+normal points at its extremes: every point alone (the widest scan) and every point in one cell (one lane adds them all).  The two paths must make the same bytes (same_bytes in
+the row): the tool exits non-zero if they do not.  With --profile-case the case's batch is downsampled twice and nothing else is run.
 """
 import argparse
 import json
@@ -114,6 +122,7 @@ def main():
     ap.add_argument("--init", action="store_true", help="the batched side starts from a far pose with the inverse pose as initial transform")
     ap.add_argument("--premoved", action="store_true", help="the baseline of --init: the far clouds moved back on the host, no initial transform, same route")
     ap.add_argument("--evaluate", action="store_true", help="time one evaluation of every case's batch beside one step of the same batch")
+    ap.add_argument("--voxel", type=float, default=None, metavar="V", help="time one device downsampling of every case's batch at V x the cloud's extent beside the host path")
     ap.add_argument("--profile-case", default="", help="run only this case's batched registration, once after a warm-up (for a kernel trace)")
     a = ap.parse_args()
     import torch  # noqa: F401  (torch first: it bundles the HIP runtime)
@@ -143,6 +152,12 @@ def main():
     with pkg.Context(0) as ctx:
         plane = a.metric == "plane"
         todo = plane_cases(pkg, orc) if plane else [(name, pairs, None, it, tol) for name, pairs, it, tol in cases(pkg, orc)]
+        edge_of = {}
+        if a.voxel is not None and not plane:   # the two extremes of one cloud at ICP_BATCH_MAX_POINTS: the widest scan, the longest sum
+            import batch_voxel_ref as vr
+            B = vr.normal(vr.MAX_POINTS, 12, np.float32)
+            todo += [("normal65536_fp32_x1_alone", [(B, B)], None, 2, 1e-6), ("normal65536_fp32_x1_one_cell", [(B, B)], None, 2, 1e-6)]
+            edge_of = {"normal65536_fp32_x1_alone": vr.identity_voxel(B), "normal65536_fp32_x1_one_cell": 1e6}
         only = [c for c in a.only.split(",") if c]
         unknown = [c for c in only if c not in [t[0] for t in todo]]
         if unknown:
@@ -180,6 +195,60 @@ def main():
                     return [ctx.point_to_plane(D, M, normals=None if normals is None else normals[k], max_iter=it, tol=tol)
                             for k, (D, M) in enumerate(seq_pairs)]
                 return [ctx.point_to_point(D, M, max_iter=it, tol=tol) for D, M in seq_pairs]
+
+            if a.voxel is not None:
+                import batch_voxel_ref as vr
+                if a.profile_case and name != a.profile_case:
+                    continue
+                D0 = pairs[0][0]
+                edge = edge_of.get(name, float(a.voxel) * float((D0.max(axis=0).astype(np.float64) - D0.min(axis=0).astype(np.float64)).max()))
+                med = lambda v: float(np.median(v))
+
+                def timed(fn):
+                    t0 = time.perf_counter()
+                    out = fn()
+                    return time.perf_counter() - t0, out
+
+                with ctx.batch(pairs) as bt:
+                    def device():
+                        return bt.downsample(edge)
+
+                    def host():
+                        thin = [(vr.downsample(D, edge)[0], vr.downsample(M, edge)[0]) for D, M in bt.get_clouds()]
+                        return ctx.batch(thin)
+
+                    if a.profile_case:
+                        for _ in range(2):
+                            device().close()
+                        print(json.dumps(dict(case=name, pairs=len(pairs), voxel_edge=edge)), flush=True)
+                        continue
+
+                    def steps():   # (first step, second step) of a fresh loop
+                        bt.begin(max_iter=it, tol=tol, metric=pkg.ICP_POINT_TO_POINT)
+                        return timed(lambda: bt.run(1))[0], timed(lambda: bt.run(1))[0]
+
+                    steps()
+                    st = [steps() for _ in range(a.reps)]
+                    with device() as X, host() as Y:   # (warm-up, and the check: the same bytes)
+                        same = all(x[0].tobytes() == y[0].tobytes() and x[1].tobytes() == y[1].tobytes() for x, y in zip(X.get_clouds(), Y.get_clouds()))
+                        after = (int(X._moff[-1]), int(X._qoff[-1]))
+                    td, th = [], []
+                    for _ in range(a.reps):   # alternated, so that both see the same box
+                        s, nb = timed(device)
+                        nb.close()
+                        td.append(s)
+                        s, nb = timed(host)
+                        nb.close()
+                        th.append(s)
+                row = dict(case=name, pairs=len(pairs), points=int(pairs[0][0].shape[0]), voxel=a.voxel, voxel_edge=edge,
+                           points_before=[int(bt._moff[-1]), int(bt._qoff[-1])], points_after=list(after),
+                           downsample_s=med(td), downsample_s_min=float(min(td)), downsample_s_max=float(max(td)),
+                           host_path_s=med(th), host_path_s_min=float(min(th)), host_path_s_max=float(max(th)),
+                           first_step_s=med([x for x, _ in st]), step_s=med([y for _, y in st]), reps=a.reps,
+                           pairs_stopping_apart=0, same_bytes=bool(same), label=a.label)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                continue
 
             if a.profile_case:
                 if name == a.profile_case:
@@ -270,6 +339,9 @@ def main():
         with open(a.out, "w") as f:
             for r in rows:
                 f.write(json.dumps(r) + "\n")
+    differ = [r["case"] for r in rows if not r.get("same_bytes", True)]
+    if differ:
+        sys.exit(f"the device's downsampled clouds are not the host path's bytes in: {differ}")
     bad = [r["case"] for r in rows if r["pairs_stopping_apart"]]
     if bad:
         sys.exit(f"batched and sequential registrations ran different passes in: {bad}")
