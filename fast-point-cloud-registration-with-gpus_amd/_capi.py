@@ -26,6 +26,8 @@ ICP_NMOM = 32
 ICP_MOM_W = 29   # slot of a robust pass's weight sum
 ICP_ROBUST_NONE, ICP_ROBUST_HUBER, ICP_ROBUST_CAUCHY, ICP_ROBUST_TUKEY = 0, 1, 2, 3
 ICP_BATCH_MAX_POINTS = 65536   # per cloud of one pair of a batch
+ICP_OUTLIER_NONE, ICP_OUTLIER_STATISTICAL, ICP_OUTLIER_RADIUS = 0, 1, 2   # icp_outlier_rule.kind
+ICP_OUTLIER_MAX_NEIGHBOURS = 32
 # icp_diag_loop_moments: how the vector came about (include/icp_mi355x_diag.h)
 ROUTE_HOST_ROWS, ROUTE_COMPACT, ROUTE_AVX, ROUTE_FIN_LAUNCH, ROUTE_FIN_PINNED, ROUTE_FIN_KERNEL = 0x001, 0x002, 0x004, 0x008, 0x010, 0x020
 ROUTE_FIN_TWO_STAGE, ROUTE_FUSED_TAIL, ROUTE_MOMENTS_KERNEL, ROUTE_ERROR_ONLY, ROUTE_ARMED, ROUTE_RESIDENT = 0x040, 0x080, 0x100, 0x200, 0x400, 0x800
@@ -44,6 +46,10 @@ class icp_result(C.Structure):
                 ("err", C.POINTER(C.c_double)), ("idx", C.POINTER(C.c_int32)), ("moved", C.c_void_p),
                 ("seconds_total", C.c_double), ("seconds_nn", C.c_double),
                 ("seconds_host", C.c_double), ("seconds_setup", C.c_double)]
+
+
+class icp_outlier_rule(C.Structure):
+    _fields_ = [("kind", C.c_int), ("neighbours", C.c_int), ("value", C.c_double)]
 
 
 _vp, _i, _pi = C.c_void_p, C.c_int, C.POINTER(C.c_int)
@@ -114,6 +120,7 @@ SIGNATURES = {
     "icp_batch_evaluate": (_i, [_vp, _i, _pd, _pi, _pi32, _pd, _pd, _pd, _pi32, C.POINTER(C.c_uint8)]),
     "icp_batch_downsample": (_i, [_vp, _pd, _pd, _pi32, _pi32, C.POINTER(_vp)]),
     "icp_batch_get_offsets": (_i, [_vp, _pi64, _pi64]),
+    "icp_batch_remove_outliers": (_i, [_vp, C.POINTER(icp_outlier_rule), C.POINTER(icp_outlier_rule), _pi32, _pi32, _pd, _pd, _pd, C.POINTER(_vp)]),
     "icp_batch_get_clouds": (_i, [_vp, _vp, _vp]),
     "icp_point_to_point_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_point_to_plane_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, _vp, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),

@@ -60,6 +60,13 @@
 // into the new planes)  ->  the second wait.  Four launches, two waits; the source is only read, its loop does not notice, and the
 // temporaries live for the call.
 //
+// Isolated points are removed on the device (icp_batch_remove_outliers): a new batch on the same context whose clouds are P0 and Q
+// of the source without the points a statistical or a radius rule per cloud rejects -- the rules, which numpy reproduces bit for
+// bit, are stated in include/icp_mi355x.h.  batch_outlier_scan (every point's mean neighbour distance or neighbour count)  ->
+// batch_outlier_decide (the ordered sums, the threshold, maps and counts)  ->  [D2H: 2 x count counts and flags, the first wait;
+// lay_out + allocate]  ->  batch_outlier_compact (the kept points' bytes into the new planes)  ->  the second wait, with the
+// optional outputs.  Three launches, two waits; the source is only read, its loop does not notice.
+//
 // Point-to-plane needs the model normals of every pair, in planes laid out as the models: given by the caller
 // (icp_batch_set_model_normals) or made on the device by ONE neighbour launch + ONE normals launch for the whole batch
 // (icp_batch_estimate_normals: knn4_batch + normals_batch_kernel, icp_k_plane.hip).  The reference estimates them once per
@@ -497,6 +504,136 @@ int downsample(icp_batch* src, const std::vector<double>& voxel, int32_t* moving
     return ICP_OK;
 }
 
+// the temporaries of one icp_batch_remove_outliers, released as VoxelTmp's are
+struct OutlierTmp {
+    hipStream_t st;
+    DevBuf clouds, items, rules, score, map, stats, count, bad;
+    explicit OutlierTmp(hipStream_t s) : st(s) {}
+    ~OutlierTmp()
+    {
+        (void)hipStreamSynchronize(st);
+        for (DevBuf* d : {&clouds, &items, &rules, &score, &map, &stats, &count, &bad}) d->release();
+    }
+};
+
+// icp_batch_remove_outliers after its argument checks; *made: the new batch as far as it got (the caller releases it on failure).
+// batch_outlier_scan (every point's score)  ->  batch_outlier_decide (the ordered sums, the threshold, maps and counts)  ->  [D2H:
+// 2 x count counts and flags, the first wait; lay_out + allocate]  ->  batch_outlier_compact  ->  the second wait, which brings the
+// optional outputs.  Three launches, two waits; no output array is written before the call can no longer be refused for its data.
+int remove_outliers(icp_batch* src, const std::vector<icp::OutlierRule>& rules, int32_t* moving_map_out, int32_t* model_map_out,
+                    double* moving_score_out, double* model_score_out, double* stats_out, icp_batch** made)
+{
+    icp_ctx* c = src->ctx;
+    hipStream_t st = c->stream;
+    const int count = src->count, n_clouds = 2 * count;
+    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
+    std::vector<icp::BatchItem> items, new_items;
+    std::vector<int> bad((size_t)n_clouds);
+    std::vector<int32_t> kept((size_t)n_clouds), hmap;
+    std::vector<double> hscore, hstats;
+    long long tmp_plane = 0;
+    int cap = 8;
+    for (int k = 0; k < n_clouds; ++k) {
+        const int side = k < count ? 0 : 1;
+        const icp::BatchPair& pr = src->pairs[k - side * count];
+        icp::VoxelCloud& cl = clouds[k];
+        cl.side = side;
+        cl.n = side ? pr.m : pr.n;
+        cl.src_off = side ? pr.q_off : pr.p_off;
+        cl.tmp_off = tmp_plane;
+        cl.dst_off = 0;
+        tmp_plane += icp::round_up(cl.n, icp::BATCH_ALIGN);
+        for (int first = 0; first < cl.n; first += icp::BATCH_ITEM)
+            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, cl.n - first), 0});
+        if (rules[k].kind == ICP_OUTLIER_STATISTICAL) cap = std::max(cap, rules[k].neighbours <= 8 ? 8 : rules[k].neighbours <= 16 ? 16 : 32);
+    }
+    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    OutlierTmp t(st);
+    HIP_TRY(t.clouds.ensure(clouds.size() * sizeof(icp::VoxelCloud)));
+    HIP_TRY(t.items.ensure(items.size() * sizeof(icp::BatchItem)));
+    HIP_TRY(t.rules.ensure(rules.size() * sizeof(icp::OutlierRule)));
+    HIP_TRY(t.score.ensure((size_t)tmp_plane * sizeof(double)));
+    HIP_TRY(t.map.ensure((size_t)tmp_plane * sizeof(int32_t)));
+    HIP_TRY(t.stats.ensure(4 * (size_t)n_clouds * sizeof(double)));
+    HIP_TRY(t.count.ensure((size_t)n_clouds * sizeof(int32_t)));
+    HIP_TRY(t.bad.ensure((size_t)n_clouds * sizeof(int)));
+    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t.items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t.rules.p, rules.data(), rules.size() * sizeof(icp::OutlierRule), hipMemcpyHostToDevice, st));
+    icp::BatchOutlierArgs a{};
+    a.precision = src->prec;
+    a.cap = cap;
+    a.clouds = (const icp::VoxelCloud*)t.clouds.p;
+    a.n_clouds = n_clouds;
+    a.items = (const icp::BatchItem*)t.items.p;
+    a.n_items = (int)items.size();
+    a.rules = (const icp::OutlierRule*)t.rules.p;
+    a.src[0] = src->P0.p;
+    a.src[1] = src->Q.p;
+    a.src_plane[0] = src->p_plane;
+    a.src_plane[1] = src->q_plane;
+    a.tmp_plane = tmp_plane;
+    a.score = (double*)t.score.p;
+    a.map = (int32_t*)t.map.p;
+    a.stats = (double*)t.stats.p;
+    a.count = (int32_t*)t.count.p;
+    a.bad = (int*)t.bad.p;
+    HIP_TRY(icp::launch_batch_outlier_scan(a, st));
+    HIP_TRY(hipMemcpyAsync(bad.data(), t.bad.p, bad.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(kept.data(), t.count.p, kept.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the first wait: the new batch's layout needs every cloud's count
+    for (int p = 0; p < count; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const size_t k = (size_t)side * count + p;
+            const std::string where = std::string(": pair ") + std::to_string(p) + (side ? ", model" : ", moving cloud");
+            if (bad[k]) return fail(ICP_ERR_INVALID, "the mean or the deviation of a cloud's neighbour distances is not finite" + where);
+            if (kept[k] < 1) return fail(ICP_ERR_EMPTY, "the rule keeps no point of the cloud" + where);
+            if (kept[k] > clouds[k].n) return fail(ICP_ERR_HIP, "icp_batch_remove_outliers: a cloud's kept count is out of range");   // (cannot happen)
+        }
+    std::vector<int64_t> moff((size_t)count + 1, 0), qoff((size_t)count + 1, 0);
+    for (int p = 0; p < count; ++p) {
+        moff[p + 1] = moff[p] + kept[p];
+        qoff[p + 1] = qoff[p] + kept[(size_t)count + p];
+    }
+    if (int rc = lay_out(c, count, src->prec, moff.data(), qoff.data(), made)) return rc;
+    icp_batch* nb = *made;
+    if (int rc = allocate(nb, new_items)) return rc;
+    for (int k = 0; k < n_clouds; ++k) clouds[k].dst_off = k < count ? nb->pairs[k].p_off : nb->pairs[k - count].q_off;
+    const size_t pb = 3 * (size_t)nb->p_plane * nb->esize, qb = 3 * (size_t)nb->q_plane * nb->esize;
+    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(nb->P0.p, 0, pb, st));   // (the padding between the clouds: all-zero bytes, as an upload leaves it)
+    HIP_TRY(hipMemsetAsync(nb->Q.p, 0, qb, st));
+    a.dst[0] = nb->P0.p;
+    a.dst[1] = nb->Q.p;
+    a.dst_plane[0] = nb->p_plane;
+    a.dst_plane[1] = nb->q_plane;
+    HIP_TRY(icp::launch_batch_outlier_compact(a, st));
+    HIP_TRY(hipMemcpyAsync(nb->P.p, nb->P0.p, pb, hipMemcpyDeviceToDevice, st));
+    if (moving_map_out || model_map_out) {
+        hmap.resize((size_t)tmp_plane);
+        HIP_TRY(hipMemcpyAsync(hmap.data(), t.map.p, hmap.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    if (moving_score_out || model_score_out) {
+        hscore.resize((size_t)tmp_plane);
+        HIP_TRY(hipMemcpyAsync(hscore.data(), t.score.p, hscore.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (stats_out) {
+        hstats.resize(4 * (size_t)n_clouds);
+        HIP_TRY(hipMemcpyAsync(hstats.data(), t.stats.p, hstats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // the second wait: the host vectors go, the temporaries are freed
+    for (int p = 0; p < count; ++p) {
+        const size_t np = (size_t)src->pairs[p].n, mp = (size_t)src->pairs[p].m;
+        const long long to = clouds[p].tmp_off, tq = clouds[(size_t)count + p].tmp_off;
+        if (moving_map_out) std::memcpy(moving_map_out + src->moff[p], hmap.data() + to, np * sizeof(int32_t));
+        if (model_map_out) std::memcpy(model_map_out + src->qoff[p], hmap.data() + tq, mp * sizeof(int32_t));
+        if (moving_score_out) std::memcpy(moving_score_out + src->moff[p], hscore.data() + to, np * sizeof(double));
+        if (model_score_out) std::memcpy(model_score_out + src->qoff[p], hscore.data() + tq, mp * sizeof(double));
+    }
+    if (stats_out) std::memcpy(stats_out, hstats.data(), hstats.size() * sizeof(double));
+    return ICP_OK;
+}
+
 // one step: enqueue the pass of every running pair, then complete it (loop_enqueue_body + loop_complete_body, per pair)
 int step(icp_batch* b)
 {
@@ -646,6 +783,51 @@ int icp_batch_downsample(icp_batch* src, const double* voxel_moving, const doubl
     ScopedPin pin(src->ctx);
     icp_batch* made = nullptr;
     const int rc = downsample(src, voxel, moving_map_out, model_map_out, &made);
+    if (rc != ICP_OK) {   // src was only read; what the call enqueued ends before its host vectors and the new batch go
+        (void)hipStreamSynchronize(src->ctx->stream);
+        (void)hipGetLastError();
+        if (made) release(made);
+        return rc;
+    }
+    *out = made;
+    return ICP_OK;
+}
+
+int icp_batch_remove_outliers(icp_batch* src, const icp_outlier_rule* moving, const icp_outlier_rule* model, int32_t* moving_map_out,
+                              int32_t* model_map_out, double* moving_score_out, double* model_score_out, double* stats_out,
+                              icp_batch** out)
+{
+    if (!out) return fail(ICP_ERR_INVALID, "out == NULL");
+    *out = nullptr;
+    if (int rc = ready(src)) return rc;
+    static_assert(sizeof(icp::OutlierRule) == sizeof(icp_outlier_rule) && icp::OUTLIER_MAX_K == ICP_OUTLIER_MAX_NEIGHBOURS, "the kernels read the caller's rules");
+    std::vector<icp::OutlierRule> rules(2 * (size_t)src->count, icp::OutlierRule{ICP_OUTLIER_NONE, 0, 0.0});   // the moving clouds', then the models'
+    for (int p = 0; p < src->count; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const icp_outlier_rule* given = side ? model : moving;
+            if (!given) continue;
+            const icp_outlier_rule& r = given[p];
+            const int n = side ? src->pairs[p].m : src->pairs[p].n;
+            const std::string where = std::string(": pair ") + std::to_string(p) + (side ? ", model" : ", moving cloud");
+            if (r.kind == ICP_OUTLIER_NONE) continue;
+            if (r.kind == ICP_OUTLIER_STATISTICAL) {
+                if (r.neighbours < 1 || r.neighbours > ICP_OUTLIER_MAX_NEIGHBOURS)
+                    return fail(ICP_ERR_INVALID, "a statistical rule's neighbours (k) must lie in [1, ICP_OUTLIER_MAX_NEIGHBOURS]" + where);
+                if (n < r.neighbours + 1) return fail(ICP_ERR_INVALID, "a statistical rule needs a cloud of at least k + 1 points" + where);
+                if (!(std::isfinite(r.value) && r.value >= 0.0))   // (NaN fails both)
+                    return fail(ICP_ERR_INVALID, "a statistical rule's ratio must be finite and >= 0" + where);
+            } else if (r.kind == ICP_OUTLIER_RADIUS) {
+                if (!(std::isfinite(r.value) && r.value > 0.0)) return fail(ICP_ERR_INVALID, "a radius must be finite and > 0" + where);
+                if (r.neighbours < 1 || r.neighbours > 65535)
+                    return fail(ICP_ERR_INVALID, "a radius rule's least number of neighbours must lie in [1, 65535]" + where);
+            } else {
+                return fail(ICP_ERR_INVALID, "unknown outlier rule kind" + where);
+            }
+            rules[(size_t)side * src->count + p] = icp::OutlierRule{r.kind, r.neighbours, r.value};
+        }
+    ScopedPin pin(src->ctx);
+    icp_batch* made = nullptr;
+    const int rc = remove_outliers(src, rules, moving_map_out, model_map_out, moving_score_out, model_score_out, stats_out, &made);
     if (rc != ICP_OK) {   // src was only read; what the call enqueued ends before its host vectors and the new batch go
         (void)hipStreamSynchronize(src->ctx->stream);
         (void)hipGetLastError();

@@ -3,7 +3,8 @@
 // decision (batch_trim_select, batch_trim_moments), robust kernels (batch_robust_moments), the per-pair reduction
 // (batch_finalize_kernel), the evaluation of every pair at its present pose (batch_eval_moments), the start clouds of a batch
 // with initial transforms (batch_init_kernel) and voxel-grid downsampling (batch_voxel_keys, batch_voxel_group, batch_voxel_rank,
-// batch_voxel_compact).  The batched neighbours and
+// batch_voxel_compact) and statistical / radius outlier removal (batch_outlier_scan, batch_outlier_decide, batch_outlier_compact).
+// The batched neighbours and
 // normals (knn4_batch, normals_batch_kernel) live with the single-pair ones in icp_k_plane.hip.  Reference statements: the loop a
 // pair runs is src/ICP_point_to_point.cu:295-423 / src/ICP_point_to_plane.cu:517-631; the kernels restate nn_match_kernel,
 // moments_kernel and transform_error_kernel (icp_k_dense.hip) per work item.
@@ -1039,6 +1040,325 @@ hipError_t launch_batch_voxel_compact(const BatchVoxelArgs& a, hipStream_t st)
     if (a.n_items <= 0) return hipSuccess;
     if (a.precision == ICP_F64) hipLaunchKernelGGL((batch_voxel_compact<double>), dim3(a.n_items), dim3(BATCH_ITEM), 0, st, a);
     else hipLaunchKernelGGL((batch_voxel_compact<float>), dim3(a.n_items), dim3(BATCH_ITEM), 0, st, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// statistical and radius outlier removal of every cloud of a batch (icp_batch_remove_outliers, icp_batch.cpp; the rule is stated
+// in include/icp_mi355x.h and every step here is one statement of it).  The clouds and work items are the voxel call's.
+//   batch_outlier_scan    one block of NN_BLOCK threads per work item, one query per lane: the four waves stream the four
+//                         contiguous quarters of the query's own cloud through their LDS sub-tiles, as knn4_batch does.  Places
+//                         past a quarter's end hold +inf (a list) or NaN (a count): such a distance enters nothing.  The rule is
+//                         uniform per block.  A statistical cloud keeps the k smallest dist2<F> -- distances only -- ascending in the TOP k
+//                         of CAP registers (the slots below hold -inf, which nothing displaces: bd[CAP - 1] is the k-th smallest
+//                         at a compile-time index and the insertion is CAP medians of three, fully unrolled: outlier_insert); it is
+//                         entered under a wave-uniform test of the chunk's minimum.  The query itself (j == i, by index: a
+//                         coincident point counts) is masked to +inf in the chunks that overlap the item, a wave-uniform test.
+//                         Waves 1-3 leave their lists in LDS (over the sub-tiles, after a barrier) and wave 0 inserts them into
+//                         its own: a multiset has one order.  Then dbar = (sum of sqrt((double)d), ascending, from 0.0) / (double)k.
+//                         A radius cloud counts dist2 <= thr2 per wave, the query included (its distance is exactly 0), and
+//                         wave 0 adds the four counts and takes the query out.  score[i] = dbar or (double)c; 0.0 where copied.
+//   batch_outlier_decide  one block per cloud: granule sums (64 consecutive points from 0.0 in ascending index, one thread per
+//                         granule), thread 0 adds them from 0.0 in ascending order: S, then Qsum the same way; mean, std, thr;
+//                         the keep flags, their exclusive scan (batch_voxel_rank's), map, count, stats.
+//   batch_outlier_compact one wave per work item: a kept point's bytes go to the new batch's planes at dst_off + map
+// No atomics of any kind; nothing is fused (contraction is off for this file), nothing multiplied by a reciprocal.
+// ------------------------------------------------------------------------------------------------
+constexpr int OUTLIER_CHUNK = 8;   // points per early-out chunk
+
+template <typename F> __device__ __forceinline__ F nan_();
+template <> __device__ __forceinline__ float nan_<float>() { return __builtin_nanf(""); }
+template <> __device__ __forceinline__ double nan_<double>() { return __builtin_nan(""); }
+
+// d into the ascending list bd[0 .. CAP-1], the largest entry falling off: bd[r] = median(bd[r-1], d, bd[r]) -- bd[r-1] where d
+// lies below it, d where it lies between the two, bd[r] where it lies above -- from the top slot down, so that every step reads
+// its lower neighbour as it was.  One v_med3_f32, or one max and one min in double, per slot: selections only, no branch, no
+// predicate; equal values change nothing of the multiset.  d is never NaN here (+inf: the list is left as it is).
+__device__ __forceinline__ float outlier_med3(float lo, float d, float hi) { return __builtin_amdgcn_fmed3f(lo, d, hi); }
+__device__ __forceinline__ double outlier_med3(double lo, double d, double hi) { return __builtin_fmin(hi, __builtin_fmax(lo, d)); }
+template <typename F, int CAP>
+__device__ __forceinline__ void outlier_insert(F (&bd)[CAP], F d)
+{
+#pragma unroll
+    for (int r = CAP - 1; r >= 1; --r) bd[r] = outlier_med3(bd[r - 1], d, bd[r]);
+    bd[0] = fmin_(bd[0], d);
+}
+
+template <typename F, int CAP>
+__global__ __launch_bounds__(NN_BLOCK) void batch_outlier_scan(const BatchOutlierArgs a)
+{
+    using V = typename Vec16<F>::type;
+    constexpr int VN = Vec16<F>::N;
+    constexpr int TW = BatchCfg<F>::TW, C = OUTLIER_CHUNK;
+    constexpr size_t TILE_BYTES = sizeof(F) * 4 * 3 * TW, LIST_BYTES = sizeof(F) * 3 * CAP * BATCH_ITEM;
+    static_assert(BATCH_ITEM == 64 && NN_BLOCK == 4 * BATCH_ITEM && TW % C == 0 && C % VN == 0, "one query per lane, four waves per item");
+    static_assert(CAP >= 1 && CAP <= OUTLIER_MAX_K, "the list's capacity");
+    // the sub-tiles during the scan, the lists of waves 1-3 after it
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[TILE_BYTES > LIST_BYTES ? TILE_BYTES : LIST_BYTES];
+    __shared__ int s_cnt[4][BATCH_ITEM];
+    F(*sq)[3][TW] = reinterpret_cast<F(*)[3][TW]>(s_raw);
+    F(*ld)[CAP][BATCH_ITEM] = reinterpret_cast<F(*)[CAP][BATCH_ITEM]>(s_raw);
+
+    const BatchItem it = a.items[blockIdx.x];
+    const OutlierRule rule = a.rules[it.pair];
+    const VoxelCloud c = a.clouds[it.pair];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool live = lane < it.count;
+    const int i = it.first + (live ? lane : 0);   // (lanes past the item's end repeat its first point: nothing of theirs is kept)
+    double* score = a.score + c.tmp_off;
+    if (rule.kind == ICP_OUTLIER_NONE) {
+        if (w == 0 && live) score[i] = 0.0;
+        return;
+    }
+    const long long sp = a.src_plane[c.side];
+    const F* Sx = static_cast<const F*>(a.src[c.side]) + c.src_off;
+    const F* Sy = Sx + sp;
+    const F* Sz = Sx + 2 * sp;
+    const F px = Sx[i], py = Sy[i], pz = Sz[i];
+    const int n = c.n;
+    const int wseg = ((n + 3) / 4 + C - 1) / C * C;   // points per wave, whole chunks
+    const int my0 = w * wseg, my1 = min(my0 + wseg, n);  // may be empty (my1 <= my0)
+    const int ntile = (wseg + TW - 1) / TW;           // the same for every wave: the barriers pair up
+    const bool radius = rule.kind == ICP_OUTLIER_RADIUS;
+    const F thr2 = (F)(rule.value * rule.value);      // (the radius rule's; the product in double, rounded once)
+    const int k = rule.neighbours;
+    // places past a quarter's end: NaN for a count (such a distance is NaN and compares false, whatever thr2), +inf for a list
+    // (such a distance is +inf, never NaN, and enters no list)
+    const F pad = radius ? nan_<F>() : inf_<F>();
+    int cnt = 0;
+    F bd[CAP];
+#pragma unroll
+    for (int r = 0; r < CAP; ++r) bd[r] = (r >= CAP - k) ? inf_<F>() : -inf_<F>();
+
+    for (int t = 0; t < ntile; ++t) {
+        const int t0 = my0 + t * TW;
+        __syncthreads();
+        for (int e = lane; e < TW; e += 64) {
+            const int j = t0 + e;
+            F qx = pad, qy = pad, qz = pad;
+            if (j < my1) { qx = Sx[j]; qy = Sy[j]; qz = Sz[j]; }
+            sq[w][0][e] = qx;
+            sq[w][1][e] = qy;
+            sq[w][2][e] = qz;
+        }
+        __syncthreads();
+        const int len = min(TW, my1 - t0);   // <= 0: this wave's quarter is exhausted
+        for (int cc = 0; cc < len; cc += C) {
+            F dd[C];
+#pragma unroll
+            for (int kk = 0; kk < C; kk += VN) {
+                const V qx = *reinterpret_cast<const V*>(&sq[w][0][cc + kk]);
+                const V qy = *reinterpret_cast<const V*>(&sq[w][1][cc + kk]);
+                const V qz = *reinterpret_cast<const V*>(&sq[w][2][cc + kk]);
+#pragma unroll
+                for (int v = 0; v < VN; ++v) dd[kk + v] = dist2<F>(px, py, pz, vget(qx, v), vget(qy, v), vget(qz, v));
+            }
+            if (radius) {
+#pragma unroll
+                for (int kk = 0; kk < C; ++kk) cnt += (dd[kk] <= thr2) ? 1 : 0;
+                continue;
+            }
+            const int j0 = t0 + cc;
+            if (j0 + C > it.first && j0 < it.first + BATCH_ITEM) {   // (wave-uniform) the chunk holds queries of this item: j != i
+#pragma unroll
+                for (int kk = 0; kk < C; ++kk) dd[kk] = (j0 + kk == i) ? inf_<F>() : dd[kk];
+            }
+            F cmin = inf_<F>();
+#pragma unroll
+            for (int kk = 0; kk < C; ++kk) cmin = fmin_(cmin, dd[kk]);
+            if (__builtin_amdgcn_ballot_w64(cmin < bd[CAP - 1]) == 0ull) continue;
+#pragma unroll
+            for (int kk = 0; kk < C; ++kk) {
+                const F d = dd[kk];
+                outlier_insert<F, CAP>(bd, d);
+            }
+        }
+    }
+    if (radius) {
+        s_cnt[w][lane] = cnt;
+        __syncthreads();
+        if (w == 0 && live) score[i] = (double)(s_cnt[0][lane] + s_cnt[1][lane] + s_cnt[2][lane] + s_cnt[3][lane] - 1);
+        return;
+    }
+    __syncthreads();   // every wave has read its last sub-tile: the lists go over them
+    if (w > 0) {
+#pragma unroll
+        for (int r = 0; r < CAP; ++r) ld[w - 1][r][lane] = bd[r];
+    }
+    __syncthreads();
+    if (w != 0) return;
+    for (int ww = 0; ww < 3; ++ww) {
+#pragma unroll 1
+        for (int s = CAP - k; s < CAP; ++s) {
+            const F d = ld[ww][s][lane];
+            if (__builtin_amdgcn_ballot_w64(d < bd[CAP - 1]) == 0ull) break;   // (ascending lists: no later entry of this wave's enters any lane's)
+            outlier_insert<F, CAP>(bd, d);
+        }
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int r = 0; r < CAP; ++r) {
+        const double t = s + sqrt((double)bd[r]);
+        s = (r >= CAP - k) ? t : s;
+    }
+    if (live) score[i] = s / (double)k;
+}
+
+__global__ __launch_bounds__(VOXEL_SCAN_BLOCK) void batch_outlier_decide(const BatchOutlierArgs a)
+{
+    __shared__ double s_g[OUTLIER_MAX_GRANULES];
+    __shared__ double s_val[2];
+    __shared__ int s_wave[VOXEL_SCAN_BLOCK / 64];
+    const int cloud = blockIdx.x;
+    const OutlierRule rule = a.rules[cloud];
+    const VoxelCloud c = a.clouds[cloud];
+    const double* score = a.score + c.tmp_off;
+    int32_t* map = a.map + c.tmp_off;
+    double* stats = a.stats + 4 * (size_t)cloud;
+    const int n = c.n;
+    if (rule.kind == ICP_OUTLIER_NONE) {   // copied: every point kept, in its place -- nothing to scan
+        for (int i = threadIdx.x; i < n; i += VOXEL_SCAN_BLOCK) map[i] = i;
+        if (threadIdx.x == 0) {
+            a.count[cloud] = n;
+            a.bad[cloud] = 0;
+            stats[0] = stats[1] = stats[2] = 0.0;
+            stats[3] = (double)n;
+        }
+        return;
+    }
+    double mean = 0.0, sd = 0.0, thr;
+    if (rule.kind == ICP_OUTLIER_RADIUS) {
+        const double r2 = rule.value * rule.value;
+        thr = a.precision == ICP_F64 ? r2 : (double)(float)r2;
+    } else {
+        const int ng = (n + BATCH_ITEM - 1) / BATCH_ITEM;   // <= OUTLIER_MAX_GRANULES
+        for (int g = threadIdx.x; g < ng; g += VOXEL_SCAN_BLOCK) {
+            const int i1 = min(n, (g + 1) * BATCH_ITEM);
+            double s = 0.0;
+            for (int i = g * BATCH_ITEM; i < i1; ++i) s += score[i];
+            s_g[g] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double S = 0.0;
+            for (int g = 0; g < ng; ++g) S += s_g[g];
+            s_val[0] = S / (double)n;
+        }
+        __syncthreads();
+        mean = s_val[0];
+        for (int g = threadIdx.x; g < ng; g += VOXEL_SCAN_BLOCK) {
+            const int i1 = min(n, (g + 1) * BATCH_ITEM);
+            double q = 0.0;
+            for (int i = g * BATCH_ITEM; i < i1; ++i) {
+                const double dev = score[i] - mean;
+                const double qi = dev * dev;
+                q += qi;
+            }
+            s_g[g] = q;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double Qs = 0.0;
+            for (int g = 0; g < ng; ++g) Qs += s_g[g];
+            s_val[1] = sqrt(Qs / (double)(n - 1));
+        }
+        __syncthreads();
+        sd = s_val[1];
+        const double scaled = rule.value * sd;
+        thr = mean + scaled;
+        if (!(isfinite(mean) && isfinite(sd))) {   // (the whole block: the host refuses the call)
+            if (threadIdx.x == 0) {
+                a.count[cloud] = 0;
+                a.bad[cloud] = 1;
+                stats[0] = mean;
+                stats[1] = sd;
+                stats[2] = thr;
+                stats[3] = 0.0;
+            }
+            return;
+        }
+    }
+    const bool radius = rule.kind == ICP_OUTLIER_RADIUS;
+    const double least = (double)rule.neighbours;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0;
+    for (int base = 0; base < n; base += VOXEL_SCAN_BLOCK) {
+        const int i = base + threadIdx.x;
+        int flag = 0;
+        if (i < n) {
+            const double sc = score[i];
+            flag = (radius ? sc >= least : sc <= thr) ? 1 : 0;
+        }
+        int incl = flag;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int up = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += up;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < VOXEL_SCAN_BLOCK / 64; ++w) {
+            before += w < wave ? s_wave[w] : 0;
+            total += s_wave[w];
+        }
+        if (i < n) map[i] = flag ? carry + before + incl - flag : -1;
+        carry += total;
+        __syncthreads();   // (s_wave is rewritten by the next chunk)
+    }
+    if (threadIdx.x == 0) {
+        a.count[cloud] = carry;
+        a.bad[cloud] = 0;
+        stats[0] = mean;
+        stats[1] = sd;
+        stats[2] = thr;
+        stats[3] = (double)carry;
+    }
+}
+
+template <typename F>
+__global__ __launch_bounds__(BATCH_ITEM) void batch_outlier_compact(const BatchOutlierArgs a)
+{
+    const BatchItem it = a.items[blockIdx.x];
+    const int lane = threadIdx.x;
+    if (lane >= it.count) return;
+    const VoxelCloud c = a.clouds[it.pair];
+    const int i = it.first + lane;
+    const int32_t to = a.map[c.tmp_off + i];
+    if (to < 0) return;
+    const F* S = static_cast<const F*>(a.src[c.side]) + c.src_off + i;
+    F* D = static_cast<F*>(a.dst[c.side]) + c.dst_off + to;
+    const long long sp = a.src_plane[c.side], dp = a.dst_plane[c.side];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) D[k * dp] = S[k * sp];
+}
+
+hipError_t launch_batch_outlier_scan(const BatchOutlierArgs& a, hipStream_t st)
+{
+    if (a.n_clouds <= 0 || a.n_items <= 0) return hipSuccess;
+    if (a.cap != 8 && a.cap != 16 && a.cap != 32) return hipErrorInvalidValue;
+#define ICP_OUTLIER_SCAN(F, CAP) hipLaunchKernelGGL((batch_outlier_scan<F, CAP>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a)
+    if (a.precision == ICP_F64) {
+        if (a.cap == 8) ICP_OUTLIER_SCAN(double, 8);
+        else if (a.cap == 16) ICP_OUTLIER_SCAN(double, 16);
+        else ICP_OUTLIER_SCAN(double, 32);
+    } else {
+        if (a.cap == 8) ICP_OUTLIER_SCAN(float, 8);
+        else if (a.cap == 16) ICP_OUTLIER_SCAN(float, 16);
+        else ICP_OUTLIER_SCAN(float, 32);
+    }
+#undef ICP_OUTLIER_SCAN
+    hipLaunchKernelGGL(batch_outlier_decide, dim3(a.n_clouds), dim3(VOXEL_SCAN_BLOCK), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_outlier_compact(const BatchOutlierArgs& a, hipStream_t st)
+{
+    if (a.n_items <= 0) return hipSuccess;
+    if (a.precision == ICP_F64) hipLaunchKernelGGL((batch_outlier_compact<double>), dim3(a.n_items), dim3(BATCH_ITEM), 0, st, a);
+    else hipLaunchKernelGGL((batch_outlier_compact<float>), dim3(a.n_items), dim3(BATCH_ITEM), 0, st, a);
     return hipGetLastError();
 }
 

@@ -433,6 +433,36 @@ struct BatchVoxelArgs {
 hipError_t launch_batch_voxel_group(const BatchVoxelArgs& a, hipStream_t st);
 // batch_voxel_compact: dst[side][k * dst_plane + dst_off + rank[i]] = cent[k][i] for every leading point i.  One launch.
 hipError_t launch_batch_voxel_compact(const BatchVoxelArgs& a, hipStream_t st);
+// statistical and radius outlier removal of every cloud of a batch (icp_batch_remove_outliers; the rule: include/icp_mi355x.h).
+// The clouds, their numbering, their stretches of the per-point temporaries and the work items are the voxel call's (VoxelCloud,
+// BatchItem::pair = the cloud's number).  rules[c] is the caller's icp_outlier_rule of cloud c (kind, neighbours, value).
+constexpr int OUTLIER_MAX_K = 32;           // == ICP_OUTLIER_MAX_NEIGHBOURS
+constexpr int OUTLIER_MAX_GRANULES = 1024;  // ICP_BATCH_MAX_POINTS / BATCH_ITEM: the granule sums of one cloud fit one LDS array
+struct OutlierRule { int kind, neighbours; double value; };   // (the layout of icp_outlier_rule)
+struct BatchOutlierArgs {
+    int precision;             // ICP_F32 / ICP_F64
+    int cap;                   // 8, 16 or 32: the register capacity of the scan's list, >= the largest statistical k of the launch
+    const VoxelCloud* clouds;  // [2 * n_pairs]
+    int n_clouds;
+    const BatchItem* items;    // the work items of all clouds, in cloud order
+    int n_items;
+    const OutlierRule* rules;  // [n_clouds]
+    const void* src[2];        // P0 and Q of the source batch (read only)
+    long long src_plane[2];
+    long long tmp_plane;       // elements of every per-point temporary
+    double* score;             // [tmp]: dbar_i (statistical), (double)c_i (radius), 0.0 (copied)
+    int32_t* map;              // [tmp]: the index of a kept point in its new cloud, -1 for a removed one
+    double* stats;             // double[n_clouds][4]: mean, std, thr, kept
+    int32_t* count;            // int32[n_clouds]: kept points (0 where bad)
+    int* bad;                  // int[n_clouds]: 1 where mean or std is not finite (written for every cloud)
+    void* dst[2];              // P0 and Q of the new batch (the compaction)
+    long long dst_plane[2];
+};
+// batch_outlier_scan (one block of NN_BLOCK threads per work item: score) -> batch_outlier_decide (one block per cloud: the
+// ordered sums, stats, bad, map, count).  Two launches; dst is not read.
+hipError_t launch_batch_outlier_scan(const BatchOutlierArgs& a, hipStream_t st);
+// batch_outlier_compact: dst[side][k * dst_plane + dst_off + map[i]] = src[side][k * src_plane + src_off + i] for every kept i.
+hipError_t launch_batch_outlier_compact(const BatchOutlierArgs& a, hipStream_t st);
 
 // soa2 (optional): a second copy of the result (the pristine moving cloud); enc (optional, fp32): the cloud's bounding cube as six
 // ordered-integer words {~ord(min xyz), ord(max xyz)}, zero before the launch

@@ -625,6 +625,58 @@ class Batch:
             return out
         return out, self._split(mm), [qm[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
 
+    def _outlier_rules(self, rules, what):
+        """one rule or one per pair -> a ctypes array of count icp_outlier_rule (None: NULL, copy that side)"""
+        if rules is None:
+            return None
+        one = isinstance(rules, tuple) and len(rules) == 3 and isinstance(rules[0], str)
+        rules = [rules] * self.count if one else list(rules)
+        if len(rules) != self.count:
+            raise ValueError(f"one {what} rule per pair (or a single rule)")
+        arr = (capi.icp_outlier_rule * self.count)()
+        for b, r in enumerate(rules):
+            if r is None:
+                arr[b] = capi.icp_outlier_rule(capi.ICP_OUTLIER_NONE, 0, 0.0)
+            elif r[0] == "statistical":   # ("statistical", k, ratio)
+                arr[b] = capi.icp_outlier_rule(capi.ICP_OUTLIER_STATISTICAL, int(r[1]), float(r[2]))
+            elif r[0] == "radius":        # ("radius", r, min_neighbours)
+                arr[b] = capi.icp_outlier_rule(capi.ICP_OUTLIER_RADIUS, int(r[2]), float(r[1]))
+            else:
+                raise ValueError(f"unknown outlier rule {r[0]!r}: 'statistical', 'radius' or None")
+        return arr
+
+    def remove_outliers(self, moving=None, model=None, want_maps=False, want_scores=False):
+        """a new Batch on the same context whose clouds are this batch's clouds as uploaded without their isolated points, made
+        on the device (icp_batch_remove_outliers; the rules are stated in include/icp_mi355x.h).  moving, model: one rule or one
+        per pair -- ("statistical", k, ratio): keep a point iff the mean distance to its k nearest neighbours is at most the
+        cloud's mean + ratio * its sample deviation; ("radius", r, min_neighbours): keep a point iff at least min_neighbours
+        other points lie within r; None: copy.  Kept points are copied, in the source order.  This batch is only read, and its
+        loop does not notice.  Returns (Batch, info): info["stats"] is a (2 * count, 4) array of [mean, std, thr, kept], the
+        moving clouds first; want_maps adds "moving_map" and "model_map" (per pair, int32: the new index of a kept point, -1 for
+        a removed one), want_scores "moving_score" and "model_score" (per pair, float64: the mean neighbour distance, or the
+        neighbour count of a radius rule)."""
+        rm, rq = self._outlier_rules(moving, "moving"), self._outlier_rules(model, "model")
+        pd, p32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        n, m = int(self._moff[-1]), int(self._qoff[-1])
+        mm = np.empty(n, dtype=np.int32) if want_maps else None
+        qm = np.empty(m, dtype=np.int32) if want_maps else None
+        ms = np.empty(n, dtype=np.float64) if want_scores else None
+        qs = np.empty(m, dtype=np.float64) if want_scores else None
+        stats = np.empty((2 * self.count, 4), dtype=np.float64)
+        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        h = C.c_void_p()
+        capi.check(self._lib.icp_batch_remove_outliers(self._h, rm, rq, ptr(mm, p32), ptr(qm, p32), ptr(ms, pd), ptr(qs, pd), ptr(stats, pd),
+                                                       C.byref(h)), "icp_batch_remove_outliers")
+        out = Batch._from_handle(self._ctx, h, self.count, self._dtype)
+        info = {"stats": stats}
+        per_model = lambda a: [a[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
+        per_moving = lambda a: [a[self._moff[b]:self._moff[b + 1]].copy() for b in range(self.count)]
+        if want_maps:
+            info["moving_map"], info["model_map"] = per_moving(mm), per_model(qm)
+        if want_scores:
+            info["moving_score"], info["model_score"] = per_moving(ms), per_model(qs)
+        return out, info
+
     def get_clouds(self):
         """the clouds the batch holds as uploaded (or as Batch.downsample made them; never the moved cloud): a list of (D, M)"""
         D = np.empty((int(self._moff[-1]), 3), dtype=self._dtype)

@@ -37,7 +37,7 @@ extern "C" {
 #endif
 
 #define ICP_ABI_VERSION 2 /* 2: icp_result gained seconds_host / seconds_setup, icp_loop_phase_seconds; later the icp_batch_* entry
-                           * points were added, icp_batch_evaluate and icp_batch_downsample among them (new symbols only: nothing that existed changed) */
+                           * points were added, icp_batch_evaluate, icp_batch_downsample and icp_batch_remove_outliers among them (new symbols only: nothing that existed changed) */
 
 /* return codes */
 #define ICP_OK 0
@@ -464,6 +464,51 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *         count of every cloud (2 x count int32, with the range flags), which the new batch's layout needs, one at the end (with
  *         the maps where they are asked for).  The grouping is brute force -- every point compares its key with its cloud's keys,
  *         n^2 / 64 tile steps per cloud -- and the longest chain is the sequential sum of the most populated cell.
+ *   - statistical and radius outlier removal (icp_batch_remove_outliers): a new batch made on the device from the clouds a
+ *     batch already holds -- same context, same count, same precision, every cloud without its isolated points.  Each cloud
+ *     has a rule of its own (icp_outlier_rule).  The rules are deterministic and can be reproduced bit for bit in numpy
+ *     (tests/batch_outlier_ref.py does).  Where the two overlap the call behaves as icp_batch_downsample.
+ *       inputs: moving and model hold count rules each; a NULL array copies that side.  kind ICP_OUTLIER_NONE copies the
+ *         cloud, its bytes and its order.  ICP_OUTLIER_STATISTICAL: neighbours = k, value = the ratio a.  ICP_OUTLIER_RADIUS:
+ *         value = the radius r, neighbours = min, the least number of other points within r.
+ *       source: the clouds src holds as uploaded (or as made by an earlier call), P0 and Q -- never the moved cloud.  The
+ *         options, the normals and the loop of src are not read.  The loop does not notice: every later icp_batch_run, _state,
+ *         _get_*, _loop_* and icp_diag_batch_* of src answers with the bytes it would have given without the call.
+ *       distance: d2(i, j) is the matching's squared distance (dx*dx + dy*dy) + dz*dz, every operation rounded separately in
+ *         the batch's precision F.  j runs over the other points of the same cloud, j != i by index: a coincident point
+ *         counts, at distance 0.
+ *       statistical rule: take the k smallest d2(i, .) as a multiset (ties cannot change a multiset); widen each to double and
+ *         take a correctly rounded double sqrt; add them from the smallest to the largest, starting at 0.0; divide once by
+ *         (double)k: this is dbar_i.  Per cloud every sum is formed in one order: a granule is 64 consecutive points from the
+ *         cloud's first point; each granule is added from 0.0 in ascending index; the granule sums are added from 0.0 in
+ *         ascending granule order.  S = the sum of dbar_i, mean = S / (double)n; dev_i = dbar_i - mean, q_i = dev_i * dev_i,
+ *         Qsum = the sum of q_i; std = sqrt(Qsum / (double)(n - 1)), the sample deviation; thr = mean + a * std, one
+ *         multiplication then one addition.  Keep iff dbar_i <= thr: a point on the threshold is kept, so a lattice with
+ *         std == 0 keeps everything.  Nothing is fused, nothing is multiplied by a reciprocal, and there are no floating-point
+ *         atomics.
+ *       radius rule: thr2 = (F)(r * r), the product formed in double and rounded once (the gate's rule);
+ *         c_i = #{ j != i : d2(i, j) <= thr2 }; keep iff c_i >= min.
+ *       output cloud: the kept points, copied, not computed, in the source order: a -0.0 survives.
+ *       outputs, all optional (NULL: not wanted): the maps hold one int32 per source point in src's layout -- the index of a
+ *         kept point within its new cloud, -1 for a removed point, 0 .. n-1 for a copied cloud.  The scores hold one double per
+ *         source point: dbar_i, or (double)c_i for the radius rule, for kept and removed points alike; 0.0 for a copied cloud.
+ *         stats_out holds four doubles per cloud, [mean, std, thr, kept], the moving clouds first (2 * count x 4): a radius
+ *         cloud has [0, 0, (double)thr2, kept], a copied cloud [0, 0, 0, n].
+ *       refusals: on any refusal *out is NULL, nothing of src changes and no output array is written; where a pair is at fault
+ *         the message names the first offending pair and the side.  ICP_ERR_INVALID: a null src or a null out; an unknown kind;
+ *         a statistical k outside [1, ICP_OUTLIER_MAX_NEIGHBOURS] or a cloud of n < k + 1 points; a ratio that is negative, NaN
+ *         or infinite; a radius that is not finite or not > 0; a radius min outside [1, 65535]; a cloud whose mean or std comes
+ *         out not finite.  ICP_ERR_STATE: a pass pending on the context.  ICP_ERR_EMPTY: a cloud would keep no point (known at
+ *         the first host wait, before the new batch exists).
+ *       independence: a pair's outputs depend on that pair's cloud and its rule alone -- not on the other pairs, their order
+ *         or the batch size.
+ *       new batch: *out is a complete batch, as if icp_batch_create had been called with the output clouds: no options, no
+ *         normals, no loop under way; it can go straight into icp_batch_downsample, icp_batch_estimate_normals or
+ *         icp_batch_begin, and it is destroyed on its own.
+ *       cost: three launches (the neighbour scan, one block per 64 points; the statistic, the decision and the maps, one
+ *         block per cloud; compaction into the new batch's planes) and two host waits: one for the kept count of every cloud,
+ *         which the new batch's layout needs, one at the end with the optional outputs.  The scan is brute force, n^2 distances
+ *         per cloud.
      Not gated, not trimmed and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the
  *     multi-GPU sums -- a single pair that needs any of them is a batch of one; nor do they weigh matches by a robust kernel.  Trimming is the only rejection by rank: there
  *     is no other percentile rejection (none by a multiple of the median or of the standard deviation of the distances). */
@@ -527,6 +572,18 @@ int icp_batch_get_offsets(icp_batch* b, int64_t* moving_off_out, int64_t* model_
 /* the clouds as uploaded / as made by icp_batch_downsample (P0 and Q, never the moved cloud), AoS, concatenated by the offsets
  * above; either pointer may be NULL */
 int icp_batch_get_clouds(icp_batch* b, void* moving_aos_out, void* model_aos_out);
+/* a new batch on src's context: same count and precision, every pair's clouds without their outliers (the rules: above) */
+#define ICP_OUTLIER_NONE 0         /* copy the cloud: its bytes, its order */
+#define ICP_OUTLIER_STATISTICAL 1  /* neighbours = k, value = std_ratio */
+#define ICP_OUTLIER_RADIUS 2       /* neighbours = the least number of other points within value = radius */
+#define ICP_OUTLIER_MAX_NEIGHBOURS 32
+typedef struct icp_outlier_rule { int kind; int neighbours; double value; } icp_outlier_rule;
+int icp_batch_remove_outliers(icp_batch* src,
+        const icp_outlier_rule* moving, const icp_outlier_rule* model,      /* count each; NULL = copy that side */
+        int32_t* moving_map_out, int32_t* model_map_out,                    /* 1 per source point, src's layout; may be NULL */
+        double* moving_score_out, double* model_score_out,                  /* 1 per source point; may be NULL */
+        double* stats_out,                                                  /* 2*count x 4, moving clouds first; may be NULL */
+        icp_batch** out);
 /* one call: create + begin + run to the end + results, then destroy.  Every output pointer may be NULL; per pair:
  * T16_out 16, iterations_out / passes_out / status_out 1, err_out max_iter+1 doubles; idx_out and moved_out (3 values per
  * point, precision of the run) concatenated as the moving clouds.  A failed pair is reported in status_out, not in the

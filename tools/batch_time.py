@@ -4,6 +4,7 @@ for all pairs) against a loop of Context.point_to_point / point_to_plane over th
 
   python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE] [--only CASE,CASE] [--max-distance V] [--trim R]
                               [--reciprocal] [--robust KIND:SCALE] [--label TEXT] [--init | --premoved] [--evaluate] [--voxel V]
+                              [--outliers KIND:N:VALUE]
 
 Cases, --metric point: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids
 (make_model_gpu, tol 1e-6); 16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  --metric plane: the fp32 case sets and the
@@ -58,6 +59,16 @@ in scale by orders of magnitude, so V is a share of the largest extent of the ca
 it); the row carries the edge itself (voxel_edge) and the points before and after.  Two more rows time one pair of 65 536
 normal points at its extremes: every point alone (the widest scan) and every point in one cell (one lane adds them all).  The two paths must make the same bytes (same_bytes in
 the row): the tool exits non-zero if they do not.  With --profile-case the case's batch is downsampled twice and nothing else is run.
+
+--outliers KIND:N:VALUE times one outlier removal of every case's batch on the device (Batch.remove_outliers with that rule on both
+sides: three launches, two host waits) beside a host path that does the same job -- Batch.get_clouds, the numpy brute force of the
+rule (tests/batch_outlier_ref.remove; a cloud the case repeats is filtered once, host_filtered_clouds in the row, so the host time is
+a lower bound) and a new Batch from the result -- and beside the first and the second step of the same batch;
+nothing sequential is run.  statistical:K:RATIO, or radius:MIN:R with R a share of the largest extent of the case's first moving
+cloud (the cases differ in scale by orders of magnitude; the row carries the radius itself).  One more row times one pair of
+65 536 normal points on the device alone (host_path_s null: the numpy brute force of 2 x 65 536^2 distances takes minutes).  The
+two paths must make the same bytes (same_bytes), or the tool exits non-zero.  With --profile-case the case's batch is filtered
+twice and nothing else is run.
 """
 import argparse
 import json
@@ -123,6 +134,7 @@ def main():
     ap.add_argument("--premoved", action="store_true", help="the baseline of --init: the far clouds moved back on the host, no initial transform, same route")
     ap.add_argument("--evaluate", action="store_true", help="time one evaluation of every case's batch beside one step of the same batch")
     ap.add_argument("--voxel", type=float, default=None, metavar="V", help="time one device downsampling of every case's batch at V x the cloud's extent beside the host path")
+    ap.add_argument("--outliers", default="", metavar="KIND:N:VALUE", help="time one device outlier removal of every case's batch beside the host path, e.g. statistical:16:1.0 or radius:4:0.05")
     ap.add_argument("--profile-case", default="", help="run only this case's batched registration, once after a warm-up (for a kernel trace)")
     a = ap.parse_args()
     import torch  # noqa: F401  (torch first: it bundles the HIP runtime)
@@ -158,6 +170,17 @@ def main():
             B = vr.normal(vr.MAX_POINTS, 12, np.float32)
             todo += [("normal65536_fp32_x1_alone", [(B, B)], None, 2, 1e-6), ("normal65536_fp32_x1_one_cell", [(B, B)], None, 2, 1e-6)]
             edge_of = {"normal65536_fp32_x1_alone": vr.identity_voxel(B), "normal65536_fp32_x1_one_cell": 1e6}
+        outlier = None
+        if a.outliers:
+            kind, _, rest = a.outliers.partition(":")
+            cnt, _, val = rest.partition(":")
+            if kind not in ("statistical", "radius") or not cnt or not val:
+                sys.exit("--outliers statistical:K:RATIO or radius:MIN:SHARE")
+            outlier = (kind, int(cnt), float(val))
+            if not plane:
+                import batch_voxel_ref as vr
+                B = vr.normal(vr.MAX_POINTS, 12, np.float32)
+                todo += [("normal65536_fp32_x1", [(B, B)], None, 2, 1e-6)]
         only = [c for c in a.only.split(",") if c]
         unknown = [c for c in only if c not in [t[0] for t in todo]]
         if unknown:
@@ -195,6 +218,72 @@ def main():
                     return [ctx.point_to_plane(D, M, normals=None if normals is None else normals[k], max_iter=it, tol=tol)
                             for k, (D, M) in enumerate(seq_pairs)]
                 return [ctx.point_to_point(D, M, max_iter=it, tol=tol) for D, M in seq_pairs]
+
+            if outlier is not None:
+                import batch_outlier_ref as ro
+                if a.profile_case and name != a.profile_case:
+                    continue
+                D0 = pairs[0][0]
+                extent = float((D0.max(axis=0).astype(np.float64) - D0.min(axis=0).astype(np.float64)).max())
+                rule = ("statistical", outlier[1], outlier[2]) if outlier[0] == "statistical" else ("radius", outlier[2] * extent, outlier[1])
+                med = lambda v: float(np.median(v))
+                with_host = pairs[0][0].shape[0] < 65536
+
+                def timed(fn):
+                    t0 = time.perf_counter()
+                    out = fn()
+                    return time.perf_counter() - t0, out
+
+                with ctx.batch(pairs) as bt:
+                    def device():
+                        return bt.remove_outliers(rule, rule)[0]
+
+                    def host():
+                        seen = {}   # (a cloud object the case repeats is filtered once: the row says so, and the host time is a lower bound)
+
+                        def one(src, X):
+                            if id(src) not in seen:
+                                seen[id(src)] = ro.remove(X, rule)[0]
+                            return seen[id(src)]
+                        return ctx.batch([(one(D, g[0]), one(M, g[1])) for (D, M), g in zip(pairs, bt.get_clouds())])
+
+                    if a.profile_case:
+                        for _ in range(2):
+                            device().close()
+                        print(json.dumps(dict(case=name, pairs=len(pairs), rule=list(rule))), flush=True)
+                        continue
+
+                    def steps():   # (first step, second step) of a fresh loop
+                        bt.begin(max_iter=it, tol=tol, metric=pkg.ICP_POINT_TO_POINT)
+                        return timed(lambda: bt.run(1))[0], timed(lambda: bt.run(1))[0]
+
+                    steps()
+                    st = [steps() for _ in range(a.reps)]
+                    same = None
+                    with device() as X:   # (warm-up, and the check: the same bytes)
+                        after = (int(X._moff[-1]), int(X._qoff[-1]))
+                        if with_host:
+                            with host() as Y:
+                                same = all(x[0].tobytes() == y[0].tobytes() and x[1].tobytes() == y[1].tobytes() for x, y in zip(X.get_clouds(), Y.get_clouds()))
+                    td, th = [], []
+                    for _ in range(a.reps):   # alternated, so that both see the same box
+                        s, nb = timed(device)
+                        nb.close()
+                        td.append(s)
+                        if with_host:
+                            s, nb = timed(host)
+                            nb.close()
+                            th.append(s)
+                row = dict(case=name, pairs=len(pairs), points=int(pairs[0][0].shape[0]), outliers=a.outliers, rule=list(rule),
+                           points_before=[int(bt._moff[-1]), int(bt._qoff[-1])], points_after=list(after),
+                           remove_outliers_s=med(td), remove_outliers_s_min=float(min(td)), remove_outliers_s_max=float(max(td)),
+                           host_path_s=med(th) if th else None, host_path_s_min=float(min(th)) if th else None, host_path_s_max=float(max(th)) if th else None,
+                           host_filtered_clouds=len({id(X) for pr in pairs for X in pr}),
+                           first_step_s=med([x for x, _ in st]), step_s=med([y for _, y in st]), reps=a.reps,
+                           pairs_stopping_apart=0, same_bytes=same, label=a.label)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                continue
 
             if a.voxel is not None:
                 import batch_voxel_ref as vr
@@ -339,9 +428,9 @@ def main():
         with open(a.out, "w") as f:
             for r in rows:
                 f.write(json.dumps(r) + "\n")
-    differ = [r["case"] for r in rows if not r.get("same_bytes", True)]
+    differ = [r["case"] for r in rows if r.get("same_bytes", True) is False]
     if differ:
-        sys.exit(f"the device's downsampled clouds are not the host path's bytes in: {differ}")
+        sys.exit(f"the device's new clouds are not the host path's bytes in: {differ}")
     bad = [r["case"] for r in rows if r["pairs_stopping_apart"]]
     if bad:
         sys.exit(f"batched and sequential registrations ran different passes in: {bad}")
