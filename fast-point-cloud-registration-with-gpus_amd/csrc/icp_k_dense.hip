@@ -534,7 +534,7 @@ __global__ void merge_kernel(const F* __restrict__ part_d, const int32_t* __rest
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     int j = merge_partials<F>(part_d, part_idx, S, n_pad, i);
-    idx[i] = j < m ? j : m - 1;  // unreachable clamp (padding never wins); keeps idx in range by construction
+    idx[i] = j < m ? j : 0;  // out of range: a sparse kernel's "no candidate" (every squared distance overflowed) -- point 0, as an ascending scan answers
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -560,7 +560,7 @@ __global__ __launch_bounds__(MOM_BLOCK) void moments_kernel(const F* __restrict_
 
     for (int i = blockIdx.x * MOM_BLOCK + threadIdx.x; i < n; i += gridDim.x * MOM_BLOCK) {
         int j = merge_partials<F>(part_d, part_idx, S, n_pad, i);
-        j = j < m ? j : m - 1;
+        j = j < m ? j : 0;   // (no candidate: point 0, see merge_kernel)
         idx_out[i] = j;
         const double px = (double)P[i], py = (double)P[(size_t)n_pad + i], pz = (double)P[2 * (size_t)n_pad + i];
         const double qx = (double)Q[j], qy = (double)Q[(size_t)m_pad + j], qz = (double)Q[2 * (size_t)m_pad + j];

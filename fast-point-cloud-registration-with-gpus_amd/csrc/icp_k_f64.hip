@@ -353,6 +353,18 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void nn_match_row64_f64(c
     cand_d[w][lane] = bj >= 0 ? best : kInf;
     cand_j[w][lane] = bj >= 0 ? bj : 0x7fffffff;
     cand_q[0][w][lane] = bq[0]; cand_q[1][w][lane] = bq[1]; cand_q[2][w][lane] = bq[2];
+    if constexpr (TAIL != 0) {
+        // A real point whose every squared distance overflowed to +inf (finite coordinates around 1e160 do that) has no candidate
+        // in any wave: its bound is +inf, no chunk passes `L < B`, and `inf < inf` takes nothing.  The ascending scan of
+        // src/ICP_CPU.c:220-234 keeps its first point then, and so does wave 0 here: model point 0 at distance +inf, which any
+        // candidate of another wave beats (the dense kernel gives the same answer, nn_match_batch states the rule).
+        if (w == 0) {
+            const bool none0 = real && bj < 0 && best == kInf;
+            if (__builtin_amdgcn_ballot_w64(none0) != 0ull) {
+                if (none0) { cand_j[0][lane] = 0; cand_q[0][0][lane] = Qg[0]; cand_q[1][0][lane] = Qg[(size_t)m_pad]; cand_q[2][0][lane] = Qg[2 * (size_t)m_pad]; }
+            }
+        }
+    }
     __syncthreads();
     if (w != 0) {
         if (!fuse.resident) return;
@@ -369,10 +381,10 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void nn_match_row64_f64(c
     }
     if constexpr (TAIL == 0) {
         part_d[pi] = fb;
-        part_idx[pi] = fj;
+        part_idx[pi] = fj;   // (no candidate -- every distance +inf, or a padding lane --: 0x7fffffff, which merge_kernel / moments_kernel resolve to point 0)
         return;
     } else {
-        fj = ((unsigned)fj < (unsigned)fuse.m) ? fj : fuse.m - 1;  // unreachable clamp (padding lanes)
+        fj = ((unsigned)fj < (unsigned)fuse.m) ? fj : 0;   // (out of range: a padding lane, whose index nobody reads)
         const double qx = cand_q[0][bw][lane], qy = cand_q[1][bw][lane], qz = cand_q[2][bw][lane];
         if (real) ((pass & 1) ? tail.idx_out_odd : tail.idx_out)[pi] = fj;
         double nx = 0.0, ny = 0.0, nz = 0.0;

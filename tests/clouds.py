@@ -103,3 +103,129 @@ def widen_pairs(pairs):
         rng = np.random.default_rng(7000 + k)
         out.append((D.astype(np.float64) + 1e-9 * rng.standard_normal(D.shape), M.astype(np.float64) + 1e-9 * rng.standard_normal(M.shape)))
     return out
+
+
+# ---- clouds of the matching fuzzes (tests/test_gpu_parity.py in float32, tests/test_gpu_f64_matching.py in float64; conditions on
+# ---- them: tests/test_f64_clouds.py) ----------------------------------------------------------------------------------------------
+FUZZ_KINDS = ("uniform", "clustered", "lattice", "line")
+FUZZ_SCALES = (1e-3, 1.0, 1e3)
+
+
+def fuzz_cloud(rng, n, kind, scale, dtype=np.float32, signed_zeros=False):
+    """n points of one kind -- uniform / clustered with exact duplicates / integer lattice / line -- times scale.  float32 rounds
+    the float64 construction once; float64 keeps it as it is, mantissas full.  signed_zeros (float64 only): about half of the
+    exact zeros (lattice coordinates, a line's y and z) become -0.0 -- the same point to every comparison, other bits to a sort
+    by bit pattern.  The draws of the float32 form do not depend on the two options."""
+    if kind == "uniform":
+        X = rng.uniform(-1, 1, (n, 3))
+    elif kind == "clustered":          # a few tight clusters with exact duplicates sprinkled in
+        c = rng.uniform(-1, 1, (6, 3))
+        X = c[rng.integers(0, 6, n)] + 0.01 * rng.standard_normal((n, 3))
+        d = rng.integers(0, n, max(1, n // 10))
+        X[d] = X[rng.integers(0, n, d.size)]
+    elif kind == "lattice":            # integer lattice: exact ties everywhere
+        X = rng.integers(-3, 4, (n, 3)).astype(np.float64)
+    else:                              # "line": degenerate extent in two axes
+        X = np.zeros((n, 3))
+        X[:, 0] = rng.uniform(-1, 1, n)
+    X = scale * X
+    if np.dtype(dtype) == np.float32:
+        assert not signed_zeros
+        return X.astype(np.float32)
+    if signed_zeros:
+        X[(X == 0.0) & (rng.random(X.shape) < 0.5)] = -0.0
+    return X
+
+
+F64_FUZZ_SEEDS = {"1": 6401, "0": 6400}     # ICP_F64_SPARSE -> the seed of its cases
+
+
+def f64_matching_cases(seed, cases):
+    """the cases of the float64 matching fuzz, in order: (n, m, kind of the cloud, kind of the model, scale, P, Q) -- n in [1, 700),
+    m in [1, 900), the kinds independent, one scale per case, signed zeros in every second case"""
+    rng = np.random.default_rng(seed)
+    for case in range(cases):
+        n, m = int(rng.integers(1, 700)), int(rng.integers(1, 900))
+        kp, km = (str(k) for k in rng.choice(FUZZ_KINDS, 2))
+        scale = float(rng.choice(FUZZ_SCALES))
+        sz = case % 2 == 1
+        yield n, m, kp, km, scale, fuzz_cloud(rng, n, kp, scale, np.float64, sz), fuzz_cloud(rng, m, km, scale, np.float64, sz)
+
+
+# ---- models of more than one round of nn_match_row64_f64 (a round is 4096 chunks of 8 = 32 768 model points) -------------------
+ROUND_POINTS = 32768
+SPARSE_M_PAD_BELOW = 1 << 17       # larger models (padded to a multiple of NN_CHUNK = 16 points) go to the dense kernel
+EIGHT_WAVE_N = 16448               # 257 rows of 64; padded to 17 408 points it is 272 blocks, more than the 256 CUs of an MI355X
+TIE_DIMS = (35, 35, 33)
+
+
+def straddling_tie_pair(n=700, replace=False, scale=1.0):
+    """model: the 35 x 35 x 33 integer lattice (40 425 distinct points) in a fixed random order; cloud: n cell centres (+0.5) drawn
+    by the same generator.  Every centre has 8 tied minima at d = 0.75, scattered over the model's indices: for four centres in
+    five on both sides of point 32 768, where the first round ends.  scale 1e-170 / 1e160: every squared distance underflows to 0 /
+    overflows to +inf, and the first minimum of an ascending scan is point 0 for every centre."""
+    rng = np.random.default_rng(6464)
+    a, b, c = TIE_DIMS
+    g = np.stack(np.meshgrid(np.arange(float(a)), np.arange(float(b)), np.arange(float(c)), indexing="ij"), -1).reshape(-1, 3)
+    M = g[rng.permutation(g.shape[0])]
+    cells = np.stack(np.meshgrid(np.arange(a - 1.0), np.arange(b - 1.0), np.arange(c - 1.0), indexing="ij"), -1).reshape(-1, 3) + 0.5
+    P = cells[rng.choice(cells.shape[0], n, replace=replace)]
+    return np.ascontiguousarray(P * scale), np.ascontiguousarray(M * scale)
+
+
+UNDERFLOW_SCALE, OVERFLOW_SCALE = 1e-170, 1e160
+
+
+def far_pair(n=700, m=40000):
+    """model: m uniform float64 points in [-1, 1]^3; cloud: n picks of it shifted by (5, 5, 5) -- the bound a cold start gets from
+    any model point is wider than the model, so nearly every chunk of both rounds is a hit"""
+    rng = np.random.default_rng(4000)
+    M = rng.uniform(-1, 1, (m, 3))
+    return M[rng.integers(0, m, n)] + 5.0, M
+
+
+def twin_model(m=40000):
+    """a model with exact twins, and a cloud that hits them: (P, M, want).  M is m uniform float64 points whose x or y is exactly 0
+    for every fifth point (a -0.0 must not look nearer or farther than them either); groups of three model indices a < b < c hold one point -- b and c in a's chunk of 8, in other chunks of
+    a's round, and (c, or b and c) in the other round --, the copies of a point with a zero coordinate with the zero's sign
+    flipped.  Every group is hit through its HIGHER members' coordinates (signed zeros included); want is the lowest member."""
+    rng = np.random.default_rng(2222)
+    M = rng.uniform(-1, 1, (m, 3))
+    M[::5, 0] = 0.0
+    M[2::10, 1] = 0.0
+    used = set()
+    groups = []
+
+    def free(lo, hi, chunk=None):
+        while True:
+            j = int(rng.integers(lo, hi)) if chunk is None else chunk * 8 + int(rng.integers(0, 8))
+            if j not in used and lo <= j < hi:
+                used.add(j)
+                return j
+
+    for rep in range(60):
+        form = rep % 4
+        a = free(0, ROUND_POINTS - 8) if form != 3 else free(ROUND_POINTS, m - 8)
+        if form == 0:      # the same chunk
+            b, c = free(0, m, a // 8), free(0, m, a // 8)
+        elif form == 1:    # other chunks of the first round
+            b, c = free(0, ROUND_POINTS), free(0, ROUND_POINTS)
+        elif form == 2:    # the other round
+            b, c = free(0, ROUND_POINTS), free(ROUND_POINTS, m)
+        else:              # all in the second round
+            b, c = free(ROUND_POINTS, m), free(ROUND_POINTS, m)
+        groups.append(sorted((a, b, c)))
+    P, want = [], []
+    for k, (a, b, c) in enumerate(groups):
+        src = M[(a, b, c)[k % 3]].copy()   # the group's point is the one any of the three held ...
+        if k % 2 == 0:
+            src[k % 3] = 0.0               # ... every second one with an exact zero
+        for j in (a, b, c):
+            M[j] = src
+        for j, flip in ((b, k % 2 == 0), (c, True)):
+            if flip:
+                M[j] = np.where(src == 0.0, -0.0, src)
+        for j in (b, c):
+            P.append(M[j].copy())
+            want.append(a)
+    return np.array(P), M, np.array(want, dtype=np.int32)

@@ -10,6 +10,8 @@ import os
 import numpy as np
 import pytest
 
+from clouds import fuzz_cloud as _fuzz_cloud
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -930,22 +932,6 @@ def test_resident_loop_small_and_ragged_clouds(ctx, pkg, orc, n, m):
     assert_same_run(res.iterations, res.err, res.T, want, 1e-9, fp32=True)
     if res.iterations == want["iterations"]:
         assert np.array_equal(res.idx, want["idx"])
-
-
-def _fuzz_cloud(rng, n, kind, scale):
-    if kind == "uniform":
-        X = rng.uniform(-1, 1, (n, 3))
-    elif kind == "clustered":          # a few tight clusters with exact duplicates sprinkled in
-        c = rng.uniform(-1, 1, (6, 3))
-        X = c[rng.integers(0, 6, n)] + 0.01 * rng.standard_normal((n, 3))
-        d = rng.integers(0, n, max(1, n // 10))
-        X[d] = X[rng.integers(0, n, d.size)]
-    elif kind == "lattice":            # integer lattice: exact ties everywhere
-        X = rng.integers(-3, 4, (n, 3)).astype(np.float64)
-    else:                              # "line": degenerate extent in two axes
-        X = np.zeros((n, 3))
-        X[:, 0] = rng.uniform(-1, 1, n)
-    return (scale * X).astype(np.float32)
 
 
 # (sort, hier, row): Morton views forbidden / forced; flat search with 64-point rows (nn_match_row64) and with 128-point rows
