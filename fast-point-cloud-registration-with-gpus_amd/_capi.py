@@ -22,6 +22,9 @@ ICP_ERR_NOMEM = -8
 
 ICP_F32, ICP_F64 = 0, 1
 ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1
+ICP_GENERALIZED = 2   # the generalized (plane-to-plane) metric of a batch that holds covariances
+ICP_COV_NONE, ICP_COV_FROBENIUS = 0, 1   # icp_batch_estimate_covariances: the regularisation
+ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS = 3, 32
 ICP_NMOM = 32
 ICP_MOM_W = 29   # slot of a robust pass's weight sum
 ICP_ROBUST_NONE, ICP_ROBUST_HUBER, ICP_ROBUST_CAUCHY, ICP_ROBUST_TUKEY = 0, 1, 2, 3
@@ -122,6 +125,9 @@ SIGNATURES = {
     "icp_batch_get_offsets": (_i, [_vp, _pi64, _pi64]),
     "icp_batch_remove_outliers": (_i, [_vp, C.POINTER(icp_outlier_rule), C.POINTER(icp_outlier_rule), _pi32, _pi32, _pd, _pd, _pd, C.POINTER(_vp)]),
     "icp_batch_get_clouds": (_i, [_vp, _vp, _vp]),
+    "icp_batch_set_covariances": (_i, [_vp, _pd, _pd]),
+    "icp_batch_estimate_covariances": (_i, [_vp, _pi, _pi, _i, C.c_double, _pd, _pd]),
+    "icp_batch_get_covariances": (_i, [_vp, _pd, _pd]),
     "icp_point_to_point_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_point_to_plane_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, _vp, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_comm_unique_id": (_i, [_vp]),
@@ -148,6 +154,7 @@ SIGNATURES = {
     "icp_diag_batch_trim": (_i, [_vp, _i, _pd, _pi]),
     "icp_diag_batch_reverse": (_i, [_vp, _pi32]),
     "icp_diag_batch_eval_moments": (_i, [_vp, _i, _pd]),
+    "icp_diag_batch_rotation": (_i, [_vp, _i, _pd]),
     "icp_eigh3": (_i, [_pd, _pd, _pd]),
     "icp_synthetic_grid_f32": (_i, [_i, C.c_float, C.c_float, _vp]),
     "icp_synthetic_grid_f64": (_i, [_i, C.c_double, C.c_double, _vp]),

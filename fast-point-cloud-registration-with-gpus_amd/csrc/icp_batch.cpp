@@ -40,7 +40,17 @@
 // reduction up to slot ICP_MOM_W.  Three launches with nothing else, up to five, still one download.  A batch whose kinds are all
 // NONE runs the steps it ran without them.
 //
+// A batch may hold a covariance per point on both sides (icp_batch_set_covariances; icp_batch_estimate_covariances: ONE launch of
+// batch_cov_kernel, icp_k_gicp.hip, for all clouds of the sides asked for -- the rule, which numpy reproduces bit for bit, is stated
+// in include/icp_mi355x.h).  icp_batch_begin then takes a third metric, ICP_GENERALIZED (plane-to-plane): the steps always run
+// deferred with the point-to-point matching launch and batch_gicp_moments in batch_trim_moments' place -- the same decision, a match
+// whose det(Cq + Rc Cp Rc^T) is not finite and > 0 rejected too, then the terms of the 6 x 6 system into a plane pass's slots --
+// and every pair's HostLoop solves as for point-to-plane.  Rc, the rotation of every motion applied to the cloud a pass matches
+// on, is composed on the host as icp_batch_state composes T and travels with the step's control words (9 doubles per pair).
+// Three launches, up to five, one download.  The other metrics of such a batch run the steps they ran without covariances.
+//
 //   batch kind             launches of a step
+//   generalized metric     nn_match_batch<DEFER>, [nn_match_batch_rev,] [batch_trim_select,] batch_gicp_moments<MUTUAL?>, batch_finalize_kernel
 //   any robust pair        nn_match_batch<DEFER>, [nn_match_batch_rev,] [batch_trim_select,] batch_robust_moments<MUTUAL?>, batch_finalize_kernel
 //   any reciprocal pair    nn_match_batch<DEFER>, nn_match_batch_rev, [batch_trim_select,] batch_trim_moments<MUTUAL>, batch_finalize_kernel
 //   trims only             nn_match_batch<DEFER>, batch_trim_select, batch_trim_moments, batch_finalize_kernel
@@ -119,6 +129,14 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     bool have_init = false;                  // the batch holds initial transforms (icp_batch_set_initial_transforms)
     std::vector<double> T0F;                 // count x 16: every pair's transform as rounded to the batch's precision, read back in double
     std::vector<char> init_copy;             // the pair's 16 doubles were exactly the identity: its cloud is copied, its T is the loop's
+    DevBuf cov[2];                           // the generalized metric: every point's covariance, moving clouds / models -- 6 planes of doubles (xx, xy, xz, yy, yz, zz), laid out as the clouds
+    bool have_cov[2] = {false, false};       // that side holds covariances (icp_batch_set_covariances, icp_batch_estimate_covariances)
+    DevBuf cov_args;                         // icp_batch_estimate_covariances: the clouds, their work items and their k of the latest call, as one buffer
+    void* h_cov_args = nullptr;              // pinned: what that buffer is copied from (a call waits for nothing unless it wants an output)
+    size_t h_cov_cap = 0;
+    hipEvent_t cov_ev = nullptr;             // recorded behind the latest call's launch: the next call waits for it before it rewrites h_cov_args
+    std::vector<double> rot;                 // count x 9: the rotation every pair's most recent matching pass of a generalized loop rotated its moving covariances by
+    size_t rot_off = 0;                      // where those rotations sit in ctl and h_ctl, behind the modes (copied by a generalized step only)
     int metric = ICP_POINT_TO_POINT;         // of the loop under way
     void* h_ctl = nullptr;                   // pinned: R, t of every pair (12 values of the precision), then its mode (int)
     double* h_mom = nullptr;                 // pinned: count x ICP_NMOM
@@ -176,8 +194,10 @@ void reset_loop_state(icp_batch* b)
 void release(icp_batch* b)
 {
     for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag,
-                      &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->rob_kind, &b->rob_k, &b->rob_k2, &b->weights, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom})
+                      &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->rob_kind, &b->rob_k, &b->rob_k2, &b->weights, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom, &b->cov[0], &b->cov[1], &b->cov_args})
         d->release();
+    if (b->cov_ev) (void)hipEventDestroy(b->cov_ev);
+    if (b->h_cov_args) (void)hipHostFree(b->h_cov_args);
     if (b->h_eval) (void)hipHostFree(b->h_eval);
     if (b->h_ctl) (void)hipHostFree(b->h_ctl);
     if (b->h_mom) (void)hipHostFree(b->h_mom);
@@ -365,9 +385,11 @@ int allocate(icp_batch* b, std::vector<icp::BatchItem>& items)
     HIP_TRY(b->mom.ensure((size_t)b->count * ICP_NMOM * sizeof(double)));
     b->rt_bytes = (size_t)b->count * 12 * b->esize;
     b->ctl_bytes = b->rt_bytes + (size_t)b->count * sizeof(int);
-    HIP_TRY(b->ctl.ensure(b->ctl_bytes));
-    HIP_TRY(hipHostMalloc(&b->h_ctl, b->ctl_bytes, hipHostMallocDefault));
-    std::memset(b->h_ctl, 0, b->ctl_bytes);
+    b->rot_off = (b->ctl_bytes + 7) / 8 * 8;   // (room for 9 doubles per pair behind the control words: a generalized step's rotations)
+    const size_t ctl_room = b->rot_off + (size_t)b->count * 9 * sizeof(double);
+    HIP_TRY(b->ctl.ensure(ctl_room));
+    HIP_TRY(hipHostMalloc(&b->h_ctl, ctl_room, hipHostMallocDefault));
+    std::memset(b->h_ctl, 0, ctl_room);
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_mom), (size_t)b->count * ICP_NMOM * sizeof(double), hipHostMallocDefault));
     return ICP_OK;
 }
@@ -634,11 +656,30 @@ int remove_outliers(icp_batch* src, const std::vector<icp::OutlierRule>& rules, 
     return ICP_OK;
 }
 
+// T of pair `pair` as icp_batch_state reports it: the loop's T, times the initial transform as rounded to the batch's precision
+// where the pair has one (T = T_loop . T0F, the product in HostLoop::note_applied's order)
+void composed_T(const icp_batch* b, int pair, double* T16)
+{
+    const icp::HostLoop& H = b->H[pair];
+    if (b->have_init && !b->init_copy[pair]) {
+        const double* T0 = b->T0F.data() + (size_t)pair * 16;
+        for (int a = 0; a < 4; ++a)
+            for (int c = 0; c < 4; ++c) {
+                double s = 0;
+                for (int k = 0; k < 4; ++k) s += H.T[a * 4 + k] * T0[k * 4 + c];
+                T16[a * 4 + c] = s;
+            }
+    } else {
+        std::memcpy(T16, H.T, sizeof H.T);
+    }
+}
+
 // one step: enqueue the pass of every running pair, then complete it (loop_enqueue_body + loop_complete_body, per pair)
 int step(icp_batch* b)
 {
     icp_ctx* c = b->ctx;
     const int cur = (int)(b->steps & 1);
+    const bool generalized = b->metric == ICP_GENERALIZED;
     int* mode = reinterpret_cast<int*>(static_cast<char*>(b->h_ctl) + b->rt_bytes);
     for (int p = 0; p < b->count; ++p) {
         mode[p] = 0;
@@ -657,9 +698,17 @@ int step(icp_batch* b)
         if (!final_only) {
             b->last_match[p] = cur;
             mode[p] |= icp::BATCH_MATCH;
+            if (generalized) {   // Rc: the rotation of every motion applied to the cloud this pass matches on
+                double T[16];
+                composed_T(b, p, T);
+                double* R = b->rot.data() + (size_t)p * 9;
+                for (int a = 0; a < 3; ++a)
+                    for (int k = 0; k < 3; ++k) R[a * 3 + k] = T[a * 4 + k];
+            }
         }
     }
-    HIP_TRY(hipMemcpyAsync(b->ctl.p, b->h_ctl, b->ctl_bytes, hipMemcpyHostToDevice, c->stream));
+    if (generalized) std::memcpy(static_cast<char*>(b->h_ctl) + b->rot_off, b->rot.data(), b->rot.size() * sizeof(double));
+    HIP_TRY(hipMemcpyAsync(b->ctl.p, b->h_ctl, generalized ? b->rot_off + b->rot.size() * sizeof(double) : b->ctl_bytes, hipMemcpyHostToDevice, c->stream));
     icp::BatchPassArgs a{};
     a.precision = b->prec;
     a.metric = b->metric;
@@ -690,6 +739,11 @@ int step(icp_batch* b)
     a.robust_k = (const double*)b->rob_k.p;
     a.robust_k2 = (const double*)b->rob_k2.p;
     a.weights = (double*)b->weights.p;
+    if (generalized) {
+        a.cov_p = (const double*)b->cov[0].p;
+        a.cov_q = (const double*)b->cov[1].p;
+        a.rot = reinterpret_cast<const double*>(static_cast<const char*>(b->ctl.p) + b->rot_off);
+    }
     HIP_TRY(icp::launch_batch_pass(a, c->stream));
     HIP_TRY(hipMemcpyAsync(b->h_mom, b->mom.p, (size_t)b->count * ICP_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -875,16 +929,25 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
 {
     if (int rc = ready(b)) return rc;
     if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
-    if (prm->metric != ICP_POINT_TO_POINT && prm->metric != ICP_POINT_TO_PLANE) return fail(ICP_ERR_INVALID, "unknown metric");
+    if (prm->metric != ICP_POINT_TO_POINT && prm->metric != ICP_POINT_TO_PLANE && prm->metric != ICP_GENERALIZED) return fail(ICP_ERR_INVALID, "unknown metric");
     if (prm->metric == ICP_POINT_TO_PLANE && !b->have_normals)
         return fail(ICP_ERR_INVALID, "a point-to-plane batch needs the model normals: icp_batch_set_model_normals or icp_batch_estimate_normals first");
+    if (prm->metric == ICP_GENERALIZED) {
+        if (!b->have_cov[0] || !b->have_cov[1])
+            return fail(ICP_ERR_INVALID, std::string("a generalized batch needs covariances on both sides (icp_batch_set_covariances or icp_batch_estimate_covariances first): the ") +
+                                             (!b->have_cov[0] ? "moving clouds" : "models") + " have none");
+        if (b->robust) return fail(ICP_ERR_INVALID, "the generalized metric takes no robust kernels (icp_batch_set_robust(NULL) first)");
+        HIP_TRY(b->dist.ensure((size_t)b->p_plane * b->esize));   // (the deferred route's winning distances)
+    }
     if (prm->precision != b->prec) return fail(ICP_ERR_INVALID, "params precision differs from the batch's clouds");
     if (prm->max_iter < 1) return fail(ICP_ERR_INVALID, "max_iter must be >= 1");
     b->begun = false;
     b->metric = prm->metric;
     for (int p = 0; p < b->count; ++p)
         if (int rc = b->H[p].begin(*prm)) return fail(rc, "bad loop parameters");
-    for (int p = 0; p < b->count; ++p) b->H[p].gated = b->gated || b->trimmed || b->reciprocal;
+    // (a generalized pass may keep nothing whatever the options: a match whose det(S) is not > 0 is rejected)
+    for (int p = 0; p < b->count; ++p) b->H[p].gated = b->gated || b->trimmed || b->reciprocal || prm->metric == ICP_GENERALIZED;
+    if (prm->metric == ICP_GENERALIZED) b->rot.assign((size_t)b->count * 9, 0.0);
     for (int p = 0; p < b->count; ++p) b->H[p].weighted = b->robust;   // (a NONE pair of a robust batch: W == CNT exactly)
     reset_loop_state(b);
     if (b->have_init) {
@@ -946,19 +1009,7 @@ int icp_batch_state(icp_batch* b, int pair, int* status, int* iterations, int* p
         const int cnt = (int)H.err.size() < err_cap ? (int)H.err.size() : err_cap;
         for (int i = 0; i < cnt; ++i) err[i] = H.err[i];
     }
-    if (T16) {
-        if (b->have_init && !b->init_copy[pair]) {   // T = T_loop . T0F, the product in HostLoop::note_applied's order
-            const double* T0 = b->T0F.data() + (size_t)pair * 16;
-            for (int a = 0; a < 4; ++a)
-                for (int c = 0; c < 4; ++c) {
-                    double s = 0;
-                    for (int k = 0; k < 4; ++k) s += H.T[a * 4 + k] * T0[k * 4 + c];
-                    T16[a * 4 + c] = s;
-                }
-        } else {
-            std::memcpy(T16, H.T, sizeof H.T);
-        }
-    }
+    if (T16) composed_T(b, pair, T16);
     return ICP_OK;
 }
 
@@ -1423,6 +1474,183 @@ int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighb
         for (int p = 0; p < b->count; ++p)
             std::memcpy(neighbours_out + 4 * b->qoff[p], hn.data() + 4 * (size_t)b->pairs[p].q_off, 4 * (size_t)b->pairs[p].m * sizeof(int32_t));
     b->have_normals = true;
+    return ICP_OK;
+}
+
+namespace {
+
+// one side's covariances: the caller's 6 doubles per point, concatenated as the clouds <-> six planes laid out as the cloud's
+void cov_to_planes(const double* aos, const Side& s, std::vector<double>& planes)
+{
+    planes.assign(6 * (size_t)s.plane, 0.0);
+    for (size_t p = 0; p < s.dst.size(); ++p)
+        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
+            for (int k = 0; k < 6; ++k) planes[(size_t)(k * s.plane + s.dst[p] + i)] = aos[6 * (s.off[p] + i) + k];
+}
+
+void cov_from_planes(const std::vector<double>& planes, const Side& s, double* aos)
+{
+    for (size_t p = 0; p < s.dst.size(); ++p)
+        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
+            for (int k = 0; k < 6; ++k) aos[6 * (s.off[p] + i) + k] = planes[(size_t)(k * s.plane + s.dst[p] + i)];
+}
+
+// downloads the covariance planes of the sides whose output pointer is given (one wait) and lays them out as the caller's
+int download_covariances(icp_batch* b, double* const out[2])
+{
+    std::vector<double> h[2];
+    for (int side = 0; side < 2; ++side)
+        if (out[side]) {
+            h[side].resize(6 * (size_t)(side ? b->q_plane : b->p_plane));
+            HIP_TRY(hipMemcpyAsync(h[side].data(), b->cov[side].p, h[side].size() * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
+        }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    for (int side = 0; side < 2; ++side)
+        if (out[side]) cov_from_planes(h[side], ::side(b, side != 0), out[side]);
+    return ICP_OK;
+}
+
+const char* side_name(int side) { return side ? ", model" : ", moving cloud"; }
+
+}  // namespace
+
+int icp_batch_set_covariances(icp_batch* b, const double* moving_cov, const double* model_cov)
+{
+    if (int rc = ready(b)) return rc;
+    const double* given[2] = {moving_cov, model_cov};
+    if (!given[0] && !given[1]) return fail(ICP_ERR_INVALID, "moving_cov == NULL and model_cov == NULL");
+    for (int side = 0; side < 2; ++side) {
+        if (!given[side]) continue;
+        const int64_t* off = side ? b->qoff.data() : b->moff.data();
+        for (int p = 0; p < b->count; ++p)
+            for (int64_t i = 6 * off[p]; i < 6 * off[p + 1]; ++i)
+                if (!std::isfinite(given[side][i]))
+                    return fail(ICP_ERR_INVALID, "a covariance has a NaN or an infinite value: pair " + std::to_string(p) + side_name(side));
+    }
+    // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
+    for (int side = 0; side < 2; ++side)
+        if (given[side]) HIP_TRY(b->cov[side].ensure(6 * (size_t)(side ? b->q_plane : b->p_plane) * sizeof(double)));
+    b->begun = false;   // a loop under way is discarded: its passes so far used other covariances (or none)
+    std::vector<double> h[2];
+    for (int side = 0; side < 2; ++side) {
+        if (!given[side]) continue;
+        b->have_cov[side] = false;
+        cov_to_planes(given[side], ::side(b, side != 0), h[side]);
+        HIP_TRY(hipMemcpyAsync(b->cov[side].p, h[side].data(), h[side].size() * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
+    for (int side = 0; side < 2; ++side)
+        if (given[side]) b->have_cov[side] = true;
+    return ICP_OK;
+}
+
+int icp_batch_estimate_covariances(icp_batch* b, const int* k_moving, const int* k_model, int regularisation, double lambda,
+                                   double* moving_cov_out, double* model_cov_out)
+{
+    if (int rc = ready(b)) return rc;
+    const int* given[2] = {k_moving, k_model};
+    if (!given[0] && !given[1]) return fail(ICP_ERR_INVALID, "k_moving == NULL and k_model == NULL");
+    if (regularisation != ICP_COV_NONE && regularisation != ICP_COV_FROBENIUS) return fail(ICP_ERR_INVALID, "unknown covariance regularisation");
+    if (regularisation == ICP_COV_FROBENIUS && !(std::isfinite(lambda) && lambda > 0.0))   // (NaN fails both)
+        return fail(ICP_ERR_INVALID, "the lambda of ICP_COV_FROBENIUS must be finite and > 0");
+    static_assert(icp::COV_MAX_K == ICP_COV_MAX_NEIGHBOURS, "the kernel's list holds the largest k");
+    const int count = b->count, n_clouds = 2 * count;
+    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
+    std::vector<icp::BatchItem> items;
+    std::vector<int> ks((size_t)n_clouds, 0);
+    int cap = 8;
+    for (int k = 0; k < n_clouds; ++k) {   // the 2 * count clouds, moving clouds first; work items for the sides asked for
+        const int side = k < count ? 0 : 1, p = k - side * count;
+        const icp::BatchPair& pr = b->pairs[p];
+        clouds[k] = icp::VoxelCloud{side ? pr.q_off : pr.p_off, 0, 0, side ? pr.m : pr.n, side};
+        if (!given[side]) continue;
+        const int kk = given[side][p];
+        if (kk < ICP_COV_MIN_NEIGHBOURS || kk > ICP_COV_MAX_NEIGHBOURS)
+            return fail(ICP_ERR_INVALID, "the neighbours (k) of a covariance must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]: pair " +
+                                             std::to_string(p) + side_name(side));
+        if (clouds[k].n < kk + 1)
+            return fail(ICP_ERR_INVALID, "covariances from k neighbours need a cloud of at least k + 1 points: pair " + std::to_string(p) + side_name(side));
+        ks[k] = kk;
+        cap = std::max(cap, kk <= 8 ? 8 : kk <= 16 ? 16 : 32);
+        for (int first = 0; first < clouds[k].n; first += icp::BATCH_ITEM)
+            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, clouds[k].n - first), 0});
+    }
+    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    icp_ctx* c = b->ctx;
+    hipStream_t st = c->stream;
+    ScopedPin pin(c);
+    // one device buffer and one pinned host buffer of the batch's hold the clouds, the items and the k of the call, so that nothing
+    // has to outlive it on the stack: the call returns without a host wait unless an output is wanted.  The allocations come
+    // before the batch changes: a call refused for want of memory leaves it as it was
+    auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
+    const size_t off_items = up16(clouds.size() * sizeof(icp::VoxelCloud));
+    const size_t off_k = off_items + up16(items.size() * sizeof(icp::BatchItem));
+    const size_t arg_bytes = off_k + ks.size() * sizeof(int);
+    if (b->cov_ev) HIP_TRY(hipEventSynchronize(b->cov_ev));   // (the call before has long read the host buffer: no wait in practice)
+    else HIP_TRY(hipEventCreateWithFlags(&b->cov_ev, hipEventDisableTiming));
+    if (arg_bytes > b->h_cov_cap) {
+        if (b->h_cov_args) (void)hipHostFree(b->h_cov_args);
+        b->h_cov_args = nullptr;
+        b->h_cov_cap = 0;
+        HIP_TRY(hipHostMalloc(&b->h_cov_args, arg_bytes, hipHostMallocDefault));
+        b->h_cov_cap = arg_bytes;
+    }
+    HIP_TRY(b->cov_args.ensure(arg_bytes));
+    for (int side = 0; side < 2; ++side)
+        if (given[side]) HIP_TRY(b->cov[side].ensure(6 * (size_t)(side ? b->q_plane : b->p_plane) * sizeof(double)));
+    b->begun = false;   // a loop under way is discarded
+    for (int side = 0; side < 2; ++side)
+        if (given[side]) b->have_cov[side] = false;
+    char* hs = static_cast<char*>(b->h_cov_args);
+    std::memcpy(hs, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud));
+    std::memcpy(hs + off_items, items.data(), items.size() * sizeof(icp::BatchItem));
+    std::memcpy(hs + off_k, ks.data(), ks.size() * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(b->cov_args.p, hs, arg_bytes, hipMemcpyHostToDevice, st));
+    for (int side = 0; side < 2; ++side)   // (the padding between the clouds: never read, never random)
+        if (given[side]) HIP_TRY(hipMemsetAsync(b->cov[side].p, 0, 6 * (size_t)(side ? b->q_plane : b->p_plane) * sizeof(double), st));
+    const char* ds = static_cast<const char*>(b->cov_args.p);
+    icp::BatchCovArgs a{};
+    a.precision = b->prec;
+    a.cap = cap;
+    a.regularisation = regularisation;
+    a.lambda = regularisation == ICP_COV_FROBENIUS ? lambda : 0.0;
+    a.clouds = reinterpret_cast<const icp::VoxelCloud*>(ds);
+    a.items = reinterpret_cast<const icp::BatchItem*>(ds + off_items);
+    a.n_items = (int)items.size();
+    a.k = reinterpret_cast<const int*>(ds + off_k);
+    a.src[0] = b->P0.p;
+    a.src[1] = b->Q.p;
+    a.src_plane[0] = b->p_plane;
+    a.src_plane[1] = b->q_plane;
+    a.cov[0] = (double*)b->cov[0].p;
+    a.cov[1] = (double*)b->cov[1].p;
+    HIP_TRY(icp::launch_batch_covariances(a, st));
+    HIP_TRY(hipEventRecord(b->cov_ev, st));
+    double* const out[2] = {given[0] ? moving_cov_out : nullptr, given[1] ? model_cov_out : nullptr};
+    if (out[0] || out[1]) {
+        if (int rc = download_covariances(b, out)) return rc;   // (the one wait of a call that wants an output)
+    }
+    for (int side = 0; side < 2; ++side)
+        if (given[side]) b->have_cov[side] = true;
+    return ICP_OK;
+}
+
+int icp_batch_get_covariances(icp_batch* b, double* moving_cov_out, double* model_cov_out)
+{
+    if (int rc = ready(b)) return rc;
+    double* const out[2] = {moving_cov_out, model_cov_out};
+    if (!out[0] && !out[1]) return fail(ICP_ERR_INVALID, "output pointer == NULL");
+    for (int side = 0; side < 2; ++side)
+        if (out[side] && !b->have_cov[side]) return fail(ICP_ERR_STATE, std::string("the batch holds no covariances of the ") + (side ? "models" : "moving clouds"));
+    return download_covariances(b, out);
+}
+
+int icp_diag_batch_rotation(icp_batch* b, int pair, double* R9)
+{
+    if (!b || !R9) return fail(ICP_ERR_INVALID, "null argument");
+    if (pair < 0 || pair >= b->count) return fail(ICP_ERR_INVALID, "pair out of range");
+    if (!b->begun || b->metric != ICP_GENERALIZED || !b->tau_seen[pair]) return fail(ICP_ERR_STATE, "no completed matching pass of this pair in a generalized loop");
+    std::memcpy(R9, b->rot.data() + (size_t)pair * 9, 9 * sizeof(double));
     return ICP_OK;
 }
 

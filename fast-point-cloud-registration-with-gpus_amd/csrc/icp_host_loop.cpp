@@ -13,7 +13,7 @@ namespace icp {
 int HostLoop::begin(const icp_params& p)
 {
     if (p.max_iter < 1) return ICP_ERR_INVALID;
-    if (p.metric != ICP_POINT_TO_POINT && p.metric != ICP_POINT_TO_PLANE) return ICP_ERR_INVALID;
+    if (p.metric != ICP_POINT_TO_POINT && p.metric != ICP_POINT_TO_PLANE && p.metric != ICP_GENERALIZED) return ICP_ERR_INVALID;
     if (p.precision != ICP_F32 && p.precision != ICP_F64) return ICP_ERR_INVALID;
     *this = HostLoop();
     prm = p;
@@ -81,7 +81,8 @@ int HostLoop::advance(const double* mom)
             wmom[ICP_MOM_CNT] = mom[ICP_MOM_W];
             mom = wmom;
         }
-        const int rc = prm.metric == ICP_POINT_TO_PLANE ? solve_point_to_plane(mom, R, t, nullptr)
+        // (the generalized metric fills a plane pass's slots with its own 6 x 6 system: the same solve)
+        const int rc = prm.metric != ICP_POINT_TO_POINT ? solve_point_to_plane(mom, R, t, nullptr)
                                                         : solve_point_to_point(mom, R, t);
         if (rc != ICP_OK) {
             done = true;

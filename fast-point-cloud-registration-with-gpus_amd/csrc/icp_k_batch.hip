@@ -593,7 +593,31 @@ hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st)
     if (a.trim_rank && (!a.dist || !a.tau)) return hipErrorInvalidValue;
     if (a.recip && (!a.dist || !a.rev || !a.q_items || a.n_q_items <= 0)) return hipErrorInvalidValue;
     if (a.robust_kind && (!a.robust_k || !a.robust_k2 || !a.weights || !a.dist)) return hipErrorInvalidValue;
-#define ICP_LAUNCH_BATCH(F, MET, GATE)                                                                                           \
+    if (a.metric == ICP_GENERALIZED) {
+        // the generalized metric: matching without a decision (the point-to-point instantiation), [the reverse search,] [the K-th
+        // distance of every pair,] then batch_gicp_moments (icp_k_gicp.hip): the decision and the terms of the 6 x 6 system
+        if (a.robust_kind || !a.dist) return hipErrorInvalidValue;
+#define ICP_LAUNCH_BATCH_GICP(F)                                                                                                 \
+    do {                                                                                                                         \
+        hipLaunchKernelGGL((nn_match_batch<F, ICP_POINT_TO_POINT, true, true>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items,  \
+                           a.pairs, a.mode, (const RT<F>*)a.rt, (F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)nullptr,     \
+                           a.q_plane, a.idx_prev, a.idx_cur, a.partials, (const F*)nullptr, (F*)a.dist);                          \
+        if (a.recip)                                                                                                             \
+            hipLaunchKernelGGL((nn_match_batch_rev<F>), dim3(a.n_q_items), dim3(NN_BLOCK), 0, st, a.q_items, a.pairs, a.mode,     \
+                               a.recip, (const F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, a.q_plane, a.rev);                       \
+        if (a.trim_rank)                                                                                                         \
+            hipLaunchKernelGGL((batch_trim_select<F>), dim3(a.n_pairs), dim3(TRIM_BLOCK), 0, st, a.pairs, a.mode, a.trim_rank,    \
+                               (const F*)a.dist, (F*)a.tau);                                                                      \
+    } while (0)
+        if (a.precision == ICP_F64) ICP_LAUNCH_BATCH_GICP(double); else ICP_LAUNCH_BATCH_GICP(float);
+#undef ICP_LAUNCH_BATCH_GICP
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        if (hipError_t e = launch_batch_gicp_moments(a, st); e != hipSuccess) return e;
+        hipLaunchKernelGGL(batch_finalize_kernel, dim3(a.n_pairs), dim3(256), 0, st, a.pairs, a.mode, (const double*)a.partials,
+                           ICP_MOM_B + 5, a.mom);
+        return hipGetLastError();
+    }
+#define ICP_LAUNCH_BATCH(F, MET, GATE)                                                                                          \
     hipLaunchKernelGGL((nn_match_batch<F, MET, GATE>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs, a.mode,          \
                        (const RT<F>*)a.rt, (F*)a.P_soa, a.p_plane, (const F*)a.Q_soa, (const F*)a.N_soa, a.q_plane, a.idx_prev,   \
                        a.idx_cur, a.partials, (const F*)a.thr, (F*)nullptr)

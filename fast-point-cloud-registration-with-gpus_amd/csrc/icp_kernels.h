@@ -362,8 +362,17 @@ struct BatchPassArgs {
     const double* robust_k;    // double[n_pairs]: every pair's scale k (read only where the kind is not NONE; with robust_kind)
     const double* robust_k2;   // double[n_pairs]: k * k, the host's product
     double* weights;           // double[p_plane], laid out as idx (written only with robust_kind; dist is needed too)
+    // metric == ICP_GENERALIZED (never with robust_kind): the pass always runs deferred too, with the point-to-point matching
+    // launch -- nn_match_batch<.., DEFER>, nn_match_batch_rev (with recip), batch_trim_select (with trim_rank) and
+    // batch_gicp_moments<.., MUTUAL = recip given> (icp_k_gicp.hip): kept as batch_trim_moments decides it and det(S) finite and
+    // > 0, the terms of the 6 x 6 system into a plane pass's slots; the reduction runs to ICP_MOM_B + 5.  Three launches, up to five.
+    const double* cov_p;       // double[6][p_plane]: xx, xy, xz, yy, yz, zz of every moving point, in the frame of the cloud as uploaded
+    const double* cov_q;       // double[6][q_plane]: ... of every model point
+    const double* rot;         // double[n_pairs][9]: row-major, the rotation that carries the uploaded cloud's frame into this pass's
 };
 hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st);
+// batch_gicp_moments alone, on the buffers the deferred launches of launch_batch_pass left (called by it; icp_k_gicp.hip)
+hipError_t launch_batch_gicp_moments(const BatchPassArgs& a, hipStream_t st);
 // evaluation of every pair whose mode is BATCH_MATCH at its present pose (icp_batch_evaluate): the deferred matching launch
 // (point-to-point instantiation whatever the metric, P only read) -> idx, dist; batch_eval_moments: kept = d <= thr[pair], rejected
 // matches marked in idx, the ICP_EVAL_* terms of the kept ones -> partials; batch_finalize_kernel -> mom[pair][ICP_NMOM] (pairs of
@@ -463,6 +472,24 @@ struct BatchOutlierArgs {
 hipError_t launch_batch_outlier_scan(const BatchOutlierArgs& a, hipStream_t st);
 // batch_outlier_compact: dst[side][k * dst_plane + dst_off + map[i]] = src[side][k * src_plane + src_off + i] for every kept i.
 hipError_t launch_batch_outlier_compact(const BatchOutlierArgs& a, hipStream_t st);
+// per-point covariances of the clouds of a batch (icp_batch_estimate_covariances; the rule: include/icp_mi355x.h).  The clouds and
+// their numbering are the voxel call's (moving clouds first; VoxelCloud::src_off is also where the cloud starts in its covariance
+// planes, tmp_off and dst_off are not read); the work items cover the clouds of the sides asked for.  One launch, icp_k_gicp.hip.
+constexpr int COV_MAX_K = 32;               // == ICP_COV_MAX_NEIGHBOURS
+struct BatchCovArgs {
+    int precision;             // ICP_F32 / ICP_F64
+    int cap;                   // 8, 16 or 32: the register capacity of the list, >= the largest k of the launch
+    int regularisation;        // ICP_COV_NONE / ICP_COV_FROBENIUS
+    double lambda;             // ICP_COV_FROBENIUS: added to the diagonal
+    const VoxelCloud* clouds;  // [2 * n_pairs]
+    const BatchItem* items;    // BatchItem::pair = the cloud's number
+    int n_items;
+    const int* k;              // int[2 * n_pairs]: the neighbours of every cloud that has items
+    const void* src[2];        // P0 and Q (read only)
+    long long src_plane[2];
+    double* cov[2];            // double[6][src_plane[side]]: xx, xy, xz, yy, yz, zz, laid out as the clouds
+};
+hipError_t launch_batch_covariances(const BatchCovArgs& a, hipStream_t st);
 
 // soa2 (optional): a second copy of the result (the pristine moving cloud); enc (optional, fp32): the cloud's bounding cube as six
 // ordered-integer words {~ord(min xyz), ord(max xyz)}, zero before the launch

@@ -313,6 +313,44 @@ class Context:
                                        options.get("fixed_iterations", False), options.get("max_distance"), options.get("init"),
                                        options.get("trim"), options.get("reciprocal"), (kernel, scale))
 
+    def register_batch_generalized(self, pairs, k=20, regularisation="frobenius", lam=1e-3, covariances=None, **options):
+        """register_batch with the generalized (plane-to-plane) metric: every kept match pulls with the inverse of the summed
+        local covariances of both clouds at the match (Batch.begin with ICP_GENERALIZED).  The covariances are estimated on the
+        device from the k nearest neighbours of every point (k: one value, or (k_moving, k_model), each a scalar or one per pair;
+        regularisation and lam as Batch.estimate_covariances takes them), or given: covariances = (moving, model), one (n, 6) and
+        one (m, 6) float64 array per pair (Batch.set_covariances; covariances_from_normals makes them from good normals).
+        options: register_batch's, by keyword, without metric and normals; robust kernels are not combined with this metric.  The
+        same list of Result as register_batch."""
+        unknown = set(options) - {"max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal"}
+        if unknown:
+            raise TypeError(f"register_batch_generalized: unknown option(s) {sorted(unknown)}")
+        max_iter = options.get("max_iter")
+        if max_iter is None:
+            max_iter = 50
+        with Batch(self, pairs) as bt:
+            if covariances is not None:
+                moving, model = covariances
+                bt.set_covariances(moving, model)
+            else:
+                km, kq = k if isinstance(k, tuple) else (k, None)
+                bt.estimate_covariances(km, kq, regularisation=regularisation, lam=lam)
+            bt.set_max_distance(options.get("max_distance"))
+            bt.set_initial_transforms(options.get("init"))
+            if options.get("trim") is not None:
+                bt.set_trim(options["trim"])
+            if options.get("reciprocal") is not None:
+                bt.set_reciprocal(options["reciprocal"])
+            bt.begin(max_iter=max_iter, tol=options.get("tol", 1e-6), fixed_iterations=options.get("fixed_iterations", False), metric=capi.ICP_GENERALIZED)
+            while bt.run(1 << 20)[1] > 0:
+                pass
+            idx, inl, moved = bt.loop_indices(), bt.loop_inliers(), bt.get_moving()
+            out = []
+            for b in range(bt.count):
+                st = bt.state(b)
+                out.append(Result(T=st["T"].copy(), iterations=st["iterations"], passes=st["passes"], err=st["err"], idx=idx[b], moved=moved[b],
+                                  extra={"status": st["status"], "inliers": inl[b], "fitness": float(inl[b].sum()) / inl[b].size}))
+            return out
+
     def register_batch_multiscale(self, pairs, voxels, **options):
         """coarse-to-fine register_batch on a voxel pyramid made on the device: the pairs are uploaded once, and level l runs on
         that batch thinned at voxels[l] (Batch.downsample; 0 or None: full resolution, the uploaded batch itself).  voxels:
@@ -322,8 +360,11 @@ class Context:
         list of that length always reads per level: give per-pair values as an array).
         Point-to-plane levels estimate their own normals on the device; normals given together with a level that downsamples is
         a ValueError.  Returns the last level's list of Result; each carries extra["levels"]: per level a dict of voxel, n, m,
-        status, iterations and T."""
-        known = {"metric", "normals", "max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal", "kernel", "scale"}
+        status, iterations and T.
+        metric ICP_GENERALIZED: every level estimates the covariances of its own clouds on the device; the options k,
+        regularisation and lam are then read as register_batch_generalized takes them."""
+        known = {"metric", "normals", "max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal", "kernel", "scale",
+                 "k", "regularisation", "lam"}
         unknown = set(options) - known
         if unknown:
             raise TypeError(f"register_batch_multiscale: unknown option(s) {sorted(unknown)}")
@@ -336,7 +377,7 @@ class Context:
             raise ValueError("caller-given normals cannot follow a downsampled model: every level estimates its own")
         max_iter = options.get("max_iter")
         if max_iter is None:
-            max_iter = 50 if metric == capi.ICP_POINT_TO_PLANE else 40
+            max_iter = 40 if metric == capi.ICP_POINT_TO_POINT else 50
         gate = options.get("max_distance")
         per_level = isinstance(gate, (list, tuple)) and len(gate) == len(voxels)
         with Batch(self, pairs) as full:
@@ -351,6 +392,10 @@ class Context:
                             bt.set_model_normals(normals)
                         else:
                             bt.estimate_normals()
+                    if metric == capi.ICP_GENERALIZED:
+                        k = options.get("k", 20)
+                        km, kq = k if isinstance(k, tuple) else (k, None)
+                        bt.estimate_covariances(km, kq, regularisation=options.get("regularisation", "frobenius"), lam=options.get("lam", 1e-3))
                     bt.set_max_distance(gate[l] if per_level else gate)
                     bt.set_initial_transforms(T)
                     if options.get("trim") is not None:
@@ -727,6 +772,78 @@ class Batch:
         cut = lambda a: [a[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
         return (cut(nrm), cut(nbr)) if want_neighbours else cut(nrm)
 
+    def _cov_side(self, covs, off, what):
+        """one (n, 6) float64 array per pair -> their concatenation in that side's layout (None: NULL)"""
+        if covs is None:
+            return None
+        covs = [np.ascontiguousarray(c, dtype=np.float64) for c in covs]
+        if len(covs) != self.count:
+            raise ValueError(f"one array of {what} covariances per pair")
+        for b, c in enumerate(covs):
+            if c.shape != (int(off[b + 1] - off[b]), 6):
+                raise ValueError(f"a pair's {what} covariances must be (points, 6): xx, xy, xz, yy, yz, zz")
+        return np.ascontiguousarray(np.concatenate(covs))
+
+    def _cut6(self, flat, off):
+        return [flat[off[b]:off[b + 1]].copy() for b in range(self.count)]
+
+    def set_covariances(self, moving=None, model=None):
+        """the covariance of every point, what a generalized begin needs on both sides: per side one (points, 6) float64 array per
+        pair -- xx, xy, xz, yy, yz, zz, symmetric positive semi-definite (the caller's duty; only finiteness is checked) -- or
+        None: that side is left as it is.  The moving covariances belong to the clouds as uploaded, in their own frame.  Discards
+        a loop under way."""
+        pd = C.POINTER(C.c_double)
+        a, q = self._cov_side(moving, self._moff, "moving"), self._cov_side(model, self._qoff, "model")
+        capi.check(self._lib.icp_batch_set_covariances(self._h, a.ctypes.data_as(pd) if a is not None else None,
+                                                       q.ctypes.data_as(pd) if q is not None else None), "icp_batch_set_covariances")
+
+    def _cov_k(self, k, what):
+        if k is None:
+            return None
+        a = np.asarray(k)
+        if a.ndim == 0:
+            a = np.full(self.count, int(a))
+        a = np.ascontiguousarray(a, dtype=np.intc)
+        if a.shape != (self.count,):
+            raise ValueError(f"one {what} per pair (or a scalar)")
+        return a
+
+    def estimate_covariances(self, k=20, k_model=None, regularisation="frobenius", lam=1e-3, want=False):
+        """the covariance of every point from its k nearest neighbours, on the device in one launch (icp_batch_estimate_covariances):
+        the neighbourhood of point i is every point of its cloud no farther than its k-th nearest other point (ties included, i
+        itself included), the covariance the neighbourhood's, in double.  k: a scalar or one value per pair, each in [3, 32], for
+        the moving clouds, or None (that side is left as it is); k_model: the same for the models, None: as k.
+        regularisation "frobenius": C / ||C||_F + lam I (lam > 0); "none" or None: the raw covariance.  want: also return
+        (moving, model), per pair the (points, 6) float64 arrays of the sides estimated (None for a side left as it is).
+        Discards a loop under way."""
+        reg = {"frobenius": capi.ICP_COV_FROBENIUS, "none": capi.ICP_COV_NONE, None: capi.ICP_COV_NONE}[regularisation] if (
+            regularisation is None or isinstance(regularisation, str)) else int(regularisation)
+        km = self._cov_k(k, "k")
+        kq = self._cov_k(k if k_model is None else k_model, "model k")
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        om = np.empty((int(self._moff[-1]), 6)) if want and km is not None else None
+        oq = np.empty((int(self._qoff[-1]), 6)) if want and kq is not None else None
+        capi.check(self._lib.icp_batch_estimate_covariances(self._h, km.ctypes.data_as(pi) if km is not None else None,
+                                                            kq.ctypes.data_as(pi) if kq is not None else None, reg, float(lam),
+                                                            om.ctypes.data_as(pd) if om is not None else None,
+                                                            oq.ctypes.data_as(pd) if oq is not None else None), "icp_batch_estimate_covariances")
+        if want:
+            return (self._cut6(om, self._moff) if om is not None else None, self._cut6(oq, self._qoff) if oq is not None else None)
+
+    def get_covariances(self):
+        """(moving, model): per pair the (points, 6) float64 covariances the batch holds (icp_batch_get_covariances)"""
+        pd = C.POINTER(C.c_double)
+        om, oq = np.empty((int(self._moff[-1]), 6)), np.empty((int(self._qoff[-1]), 6))
+        capi.check(self._lib.icp_batch_get_covariances(self._h, om.ctypes.data_as(pd), oq.ctypes.data_as(pd)), "icp_batch_get_covariances")
+        return self._cut6(om, self._moff), self._cut6(oq, self._qoff)
+
+    def diag_rotation(self, b):
+        """(3, 3): the rotation pair b's most recent matching pass of a generalized loop rotated its moving covariances by
+        (icp_diag_batch_rotation)"""
+        R = np.zeros(9)
+        capi.check(self._lib.icp_diag_batch_rotation(self._h, int(b), R.ctypes.data_as(C.POINTER(C.c_double))), "icp_diag_batch_rotation")
+        return R.reshape(3, 3)
+
     def set_max_distance(self, v):
         """the maximum correspondence distance: a scalar for every pair, one value per pair (inf: that pair is not gated), or
         None (no gate).  A match farther away than that enters no sum of its pass.  Discards a loop under way."""
@@ -834,7 +951,7 @@ class Batch:
 
     def begin(self, max_iter=40, tol=1e-6, fixed_iterations=False, metric=capi.ICP_POINT_TO_POINT):
         """start every pair's registration from the uploaded clouds, moved by the pair's initial transform where the batch holds
-        any (ICP_POINT_TO_PLANE: the batch must hold normals)"""
+        any (ICP_POINT_TO_PLANE: the batch must hold normals; ICP_GENERALIZED: covariances on both sides and no robust kernel)"""
         prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(self._dtype), int(metric))
         capi.check(self._lib.icp_batch_begin(self._h, C.byref(prm)), "icp_batch_begin")
         self._max_iter = int(max_iter)
@@ -937,6 +1054,17 @@ class Batch:
 
 
 # ---- host-only helpers (no device) -------------------------------------------------------------
+def covariances_from_normals(normals, eps=1e-3):
+    """(n, 6) float64: I - (1 - eps) n n^T per point as xx, xy, xz, yy, yz, zz -- the plane regularisation of the Generalized-ICP
+    paper (variance eps along the normal, 1 across it) for callers who have good unit normals (Batch.set_covariances)"""
+    N = np.asarray(normals, dtype=np.float64)
+    if N.ndim != 2 or N.shape[1] != 3:
+        raise ValueError("normals must be (n, 3)")
+    s = 1.0 - float(eps)
+    x, y, z = N[:, 0], N[:, 1], N[:, 2]
+    return np.ascontiguousarray(np.stack([1.0 - s * x * x, -s * x * y, -s * x * z, 1.0 - s * y * y, -s * y * z, 1.0 - s * z * z], axis=1))
+
+
 def solve_point_to_point(mom):
     lib = capi.load()
     mom = np.ascontiguousarray(mom, dtype=np.float64)

@@ -509,6 +509,57 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *         block per cloud; compaction into the new batch's planes) and two host waits: one for the kept count of every cloud,
  *         which the new batch's layout needs, one at the end with the optional outputs.  The scan is brute force, n^2 distances
  *         per cloud.
+ *   - the generalized metric (ICP_GENERALIZED, plane-to-plane; Segal et al., RSS 2009, in the fast_gicp formulation): every kept
+ *     match (p_i, q_j) pulls with the inverse of S = Cq_j + Rc Cp_i Rc^T, the local shape of BOTH clouds at the match.  The batch
+ *     holds one covariance per point of either side, given (icp_batch_set_covariances) or estimated on the device from a
+ *     neighbourhood of the caller's size (icp_batch_estimate_covariances); icp_batch_get_covariances reads them back.
+ *       storage: a covariance is 6 doubles per point, xx, xy, xz, yy, yz, zz -- always double, whatever the batch's precision --
+ *         concatenated in the layout of the clouds (moving_off, model_off).  The moving covariances belong to the cloud as
+ *         uploaded, in its own frame: the loop rotates them, the caller never does.
+ *       both calls follow icp_batch_set_model_normals / icp_batch_estimate_normals: any time after icp_batch_create; they replace
+ *         that side's set; a loop under way is discarded; a refused call leaves the batch as it was.  A pending pass on the
+ *         context: ICP_ERR_STATE.  A null batch: ICP_ERR_INVALID.  A NULL array on one side leaves that side untouched; both NULL
+ *         is ICP_ERR_INVALID.
+ *       icp_batch_set_covariances checks finiteness only: a NaN or an infinite value is ICP_ERR_INVALID and the message names the
+ *         pair and the side.  That every matrix is symmetric positive semi-definite is the caller's duty.
+ *       icp_batch_estimate_covariances: k_moving and k_model hold count ints each, every k within [ICP_COV_MIN_NEIGHBOURS,
+ *         ICP_COV_MAX_NEIGHBOURS]; a cloud of fewer than k + 1 points is ICP_ERR_INVALID (the message names the pair and the
+ *         side), and so is an unknown regularisation.  With ICP_COV_FROBENIUS lambda must be finite and > 0; with ICP_COV_NONE
+ *         it is not read.  The outputs are optional.  The rule for point i of a cloud, reproducible bit for bit in numpy
+ *         (tests/batch_gicp_ref.py does):
+ *           d2(i, j) is the matching's squared distance (dx*dx + dy*dy) + dz*dz in the batch's precision F.
+ *           tau_i is the k-th smallest d2(i, j) over j != i by index -- the statistical outlier rule's multiset: a coincident
+ *             point counts, at 0.
+ *           the neighbourhood is every j of the cloud with d2(i, j) <= tau_i, i itself included: all ties with the k-th are in,
+ *             the count c >= k + 1, and the set depends on no ordering of equal values.
+ *           sums, in double, from 0.0, over the neighbourhood in ascending j: e = ((double)x_j - (double)x_i, ...) -- differences
+ *             against the query, so a cloud far from the origin loses nothing; s_a += e_a; S_ab += e_a * e_b for the six a <= b.
+ *           C_ab = (S_ab - (s_a * s_b) / (double)c) / (double)c: each operation rounded on its own, nothing fused.
+ *           ICP_COV_FROBENIUS: f = sqrt(((xx*xx + yy*yy) + zz*zz) + 2.0 * ((xy*xy + xz*xz) + yz*yz)); f > 0: C'_ab = C_ab / f,
+ *             plus lambda on the diagonal; f == 0: C' = lambda I exactly.  ICP_COV_NONE: the raw covariance.
+ *           a cloud's result depends on that cloud, its k and the two parameters alone.
+ *         cost: one launch for all clouds of the sides asked for (one block per 64 points: the k-th distance in a register list,
+ *           then the sums in one pass over the cloud), no atomics, and one host wait only when an output array is wanted.
+ *       icp_batch_begin with ICP_GENERALIZED needs covariances on both sides (ICP_ERR_INVALID without), and a batch that holds
+ *         robust kernels refuses this metric with ICP_ERR_INVALID: weights on a Mahalanobis residual are a later change.
+ *         icp_batch_evaluate, the single-pair loops (icp_loop_begin, icp_point_to_*) and the one-call icp_point_to_*_batch
+ *         refuse the value as any unknown metric; icp_host_loop_create accepts it and solves as for point-to-plane.
+ *       a step always runs deferred: the point-to-point matching launch, [the reverse search,] [the trim's selection,]
+ *         batch_gicp_moments, the reduction up to ICP_MOM_B + 5 -- three launches, up to five, one download.  The kept decision is
+ *         the one of every deferred batch: gate, tau over all n distances, the mutual rule.  Front end, ICP_MOM_ERR (Euclidean,
+ *         over the points the previous matching pass kept), the err series, the stop rule, idx, masks, initial transforms and
+ *         the ICP_ERR_EMPTY / ICP_ERR_SINGULAR handling are those of the other metrics.
+ *       terms of a kept match of moving point i to model point j, every one in double from the widened coordinates p (the moved
+ *         point) and q:  Rc = the rotation part of the product of every motion applied to the cloud this pass matched on, the
+ *         initial transform as rounded to the batch's precision included, composed on the host in double as icp_batch_state
+ *         composes T (icp_diag_batch_rotation reads it).  Tm = Rc Cp_i, the full 3 x 3, each entry (r0*c0 + r1*c1) + r2*c2;
+ *         B_ab = (Tm_a0*Rc_b0 + Tm_a1*Rc_b1) + Tm_a2*Rc_b2 for a <= b; S = Cq_j + B.  Cofactors c00 = S11*S22 - S12*S12,
+ *         c01 = S02*S12 - S01*S22, c02 = S01*S12 - S02*S11, c11 = S00*S22 - S02*S02, c12 = S01*S02 - S00*S12, c22 = S00*S11 -
+ *         S01*S01; det = (S00*c00 + S01*c01) + S02*c02; M_ab = c_ab / det.  A match whose det is not finite or not > 0 is
+ *         rejected: it counts as not kept in mask, count and sums, like a gate rejection.  e = p - q; J columns j0 = (0, -pz,
+ *         py), j1 = (pz, 0, -px), j2 = (-py, px, 0), j3, j4, j5 the unit vectors; u_a = M j_a.  Slot C(a, c) += j_a . u_c for
+ *         a <= c; slot B(a) -= u_a . e; ICP_MOM_CNT = 1.  Every dot product is (x*x' + y*y') + z*z'.  With M = n n^T these are
+ *         the plane pass's statements.  A pair's bits depend on that pair and its options alone.
      Not gated, not trimmed and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the
  *     multi-GPU sums -- a single pair that needs any of them is a batch of one; nor do they weigh matches by a robust kernel.  Trimming is the only rejection by rank: there
  *     is no other percentile rejection (none by a multiple of the median or of the standard deviation of the distances). */
@@ -525,7 +576,8 @@ int icp_batch_set_model_normals(icp_batch* b, const void* nxyz_aos);
  * A pair's model of fewer than 5 points (k = 4 neighbours + self, as icp_estimate_normals): ICP_ERR_INVALID, the message
  * names the pair */
 int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighbours_out);
-/* prm->precision must be the batch's; prm->metric ICP_POINT_TO_POINT, or ICP_POINT_TO_PLANE on a batch that holds normals */
+/* prm->precision must be the batch's; prm->metric ICP_POINT_TO_POINT, or ICP_POINT_TO_PLANE on a batch that holds normals, or
+ * ICP_GENERALIZED on a batch that holds covariances on both sides and no robust kernel */
 int icp_batch_begin(icp_batch* b, const icp_params* prm);
 /* up to max_steps passes for every pair still running; *active (optional) = pairs not yet done */
 int icp_batch_run(icp_batch* b, int max_steps, int* steps_done, int* active);
@@ -584,6 +636,20 @@ int icp_batch_remove_outliers(icp_batch* src,
         double* moving_score_out, double* model_score_out,                  /* 1 per source point; may be NULL */
         double* stats_out,                                                  /* 2*count x 4, moving clouds first; may be NULL */
         icp_batch** out);
+/* the generalized metric (above): prm->metric of icp_batch_begin on a batch that holds covariances on both sides */
+#define ICP_GENERALIZED 2                 /* third value of icp_metric */
+#define ICP_COV_NONE 0                    /* the raw covariance */
+#define ICP_COV_FROBENIUS 1               /* C / ||C||_F + lambda I */
+#define ICP_COV_MIN_NEIGHBOURS 3
+#define ICP_COV_MAX_NEIGHBOURS 32
+/* 6 doubles per point (xx, xy, xz, yy, yz, zz), concatenated as the clouds; a NULL side is left untouched, both NULL: ICP_ERR_INVALID */
+int icp_batch_set_covariances(icp_batch* b, const double* moving_cov, const double* model_cov);
+/* k_moving / k_model: count ints each (NULL: that side is left untouched; both NULL: ICP_ERR_INVALID); lambda: read with
+ * ICP_COV_FROBENIUS only; the outputs (6 doubles per point) may be NULL */
+int icp_batch_estimate_covariances(icp_batch* b, const int* k_moving, const int* k_model, int regularisation, double lambda,
+                                   double* moving_cov_out, double* model_cov_out);
+/* the covariances the batch holds; either pointer may be NULL; ICP_ERR_STATE where a side that is asked for holds none */
+int icp_batch_get_covariances(icp_batch* b, double* moving_cov_out, double* model_cov_out);
 /* one call: create + begin + run to the end + results, then destroy.  Every output pointer may be NULL; per pair:
  * T16_out 16, iterations_out / passes_out / status_out 1, err_out max_iter+1 doubles; idx_out and moved_out (3 values per
  * point, precision of the run) concatenated as the moving clouds.  A failed pair is reported in status_out, not in the

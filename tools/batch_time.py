@@ -4,7 +4,7 @@ for all pairs) against a loop of Context.point_to_point / point_to_plane over th
 
   python3 tools/batch_time.py [--metric point|plane] [--reps 5] [--out FILE] [--only CASE,CASE] [--max-distance V] [--trim R]
                               [--reciprocal] [--robust KIND:SCALE] [--label TEXT] [--init | --premoved] [--evaluate] [--voxel V]
-                              [--outliers KIND:N:VALUE]
+                              [--outliers KIND:N:VALUE] [--generalized K]
 
 Cases, --metric point: 64 and 256 configs[0] pairs (synth_icp_cpu(32), fp64, tol 1e-5); 64 fp32 1 024-point grids
 (make_model_gpu, tol 1e-6); 16 Bunny_res pairs (rotated copies, fp32, tol 1e-6).  --metric plane: the fp32 case sets and the
@@ -69,6 +69,12 @@ cloud (the cases differ in scale by orders of magnitude; the row carries the rad
 65 536 normal points on the device alone (host_path_s null: the numpy brute force of 2 x 65 536^2 distances takes minutes).  The
 two paths must make the same bytes (same_bytes), or the tool exits non-zero.  With --profile-case the case's batch is filtered
 twice and nothing else is run.
+
+--generalized K times, for every case's batch, one covariance call (Batch.estimate_covariances with K neighbours on both sides: one
+launch, no host wait, closed by a get_moving download so that the clock sees the device finish) and the first and second step of a
+generalized loop (Batch.begin with ICP_GENERALIZED: the deferred route, three launches per step), beside the steps of the same batch
+under the case's own metric (step_s: what the rows of --evaluate report, and what a build without the generalized metric,
+ICP_LIB_PATH, reports alone) and under point-to-plane with device normals (plane_step_s).  Nothing sequential is run.
 """
 import argparse
 import json
@@ -135,6 +141,7 @@ def main():
     ap.add_argument("--evaluate", action="store_true", help="time one evaluation of every case's batch beside one step of the same batch")
     ap.add_argument("--voxel", type=float, default=None, metavar="V", help="time one device downsampling of every case's batch at V x the cloud's extent beside the host path")
     ap.add_argument("--outliers", default="", metavar="KIND:N:VALUE", help="time one device outlier removal of every case's batch beside the host path, e.g. statistical:16:1.0 or radius:4:0.05")
+    ap.add_argument("--generalized", type=int, default=None, metavar="K", help="time the covariance call (K neighbours) and the steps of a generalized loop of every case's batch beside its own steps")
     ap.add_argument("--profile-case", default="", help="run only this case's batched registration, once after a warm-up (for a kernel trace)")
     a = ap.parse_args()
     import torch  # noqa: F401  (torch first: it bundles the HIP runtime)
@@ -345,6 +352,51 @@ def main():
                         res = run_batched()
                     print(json.dumps(dict(case=name, pairs=len(pairs), pair_iterations=sum(r.passes for r in res),
                                           steps=max(r.passes for r in res) + 1)), flush=True)
+                continue
+
+            if a.generalized is not None:
+                med = lambda v: float(np.median(v))
+                have = hasattr(ctx._lib, "icp_batch_estimate_covariances")
+                with ctx.batch(pairs) as bt:
+                    def timed(fn):
+                        t0 = time.perf_counter()
+                        fn()
+                        return time.perf_counter() - t0
+
+                    def steps(m):   # (first step, second step) of a fresh loop
+                        bt.begin(max_iter=it, tol=tol, metric=m)
+                        return timed(lambda: bt.run(1)), timed(lambda: bt.run(1))
+
+                    def cov():
+                        bt.estimate_covariances(a.generalized)
+                        bt.get_moving()
+
+                    if plane:
+                        bt.set_model_normals(normals) if normals is not None else bt.estimate_normals()
+                    own, pl, gen, tc = [], [], [], []
+                    steps(metric)
+                    if not plane:
+                        bt.estimate_normals()
+                    steps(pkg.ICP_POINT_TO_PLANE)
+                    if have:
+                        cov()
+                        steps(pkg.ICP_GENERALIZED)
+                    for _ in range(a.reps):   # alternated, so that all see the same box
+                        own.append(steps(metric))
+                        pl.append(steps(pkg.ICP_POINT_TO_PLANE))
+                        if have:
+                            tc.append(timed(cov))
+                            gen.append(steps(pkg.ICP_GENERALIZED))
+                sec = lambda v, i: med([x[i] for x in v]) if v else None
+                row = dict(case=name, pairs=len(pairs), points=int(pairs[0][0].shape[0]), k=a.generalized,
+                           first_step_s=sec(own, 0), step_s=sec(own, 1), step_s_min=float(min(y for _, y in own)), step_s_max=float(max(y for _, y in own)),
+                           plane_first_step_s=sec(pl, 0), plane_step_s=sec(pl, 1),
+                           covariances_s=med(tc) if tc else None, covariances_s_min=float(min(tc)) if tc else None, covariances_s_max=float(max(tc)) if tc else None,
+                           generalized_first_step_s=sec(gen, 0), generalized_step_s=sec(gen, 1),
+                           generalized_step_s_min=float(min(y for _, y in gen)) if gen else None, generalized_step_s_max=float(max(y for _, y in gen)) if gen else None,
+                           reps=a.reps, pairs_stopping_apart=0, label=a.label)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
                 continue
 
             if a.evaluate:
