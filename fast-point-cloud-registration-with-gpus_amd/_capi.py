@@ -25,6 +25,7 @@ ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1
 ICP_GENERALIZED = 2   # the generalized (plane-to-plane) metric of a batch that holds covariances
 ICP_COV_NONE, ICP_COV_FROBENIUS = 0, 1   # icp_batch_estimate_covariances: the regularisation
 ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS = 3, 32
+ICP_FEATURE_BINS = 33   # doubles per FPFH descriptor (icp_batch_compute_features)
 ICP_NMOM = 32
 ICP_MOM_W = 29   # slot of a robust pass's weight sum
 ICP_ROBUST_NONE, ICP_ROBUST_HUBER, ICP_ROBUST_CAUCHY, ICP_ROBUST_TUKEY = 0, 1, 2, 3
@@ -53,6 +54,10 @@ class icp_result(C.Structure):
 
 class icp_outlier_rule(C.Structure):
     _fields_ = [("kind", C.c_int), ("neighbours", C.c_int), ("value", C.c_double)]
+
+
+class icp_ransac_params(C.Structure):
+    _fields_ = [("hypotheses", C.c_int), ("max_distance", C.c_double), ("edge_similarity", C.c_double)]
 
 
 _vp, _i, _pi = C.c_void_p, C.c_int, C.POINTER(C.c_int)
@@ -128,6 +133,11 @@ SIGNATURES = {
     "icp_batch_set_covariances": (_i, [_vp, _pd, _pd]),
     "icp_batch_estimate_covariances": (_i, [_vp, _pi, _pi, _i, C.c_double, _pd, _pd]),
     "icp_batch_get_covariances": (_i, [_vp, _pd, _pd]),
+    "icp_batch_compute_features": (_i, [_vp, _pi, _pi, _pd, _pd, _pd, _pd]),
+    "icp_batch_get_features": (_i, [_vp, _pd, _pd]),
+    "icp_batch_match_features": (_i, [_vp, _i, _pi32, _pi32, C.POINTER(C.c_uint8)]),
+    "icp_batch_score_transforms": (_i, [_vp, _i, _pd, _pd, _pi32]),
+    "icp_batch_ransac": (_i, [_vp, C.POINTER(icp_ransac_params), C.POINTER(C.c_uint64), _pd, _pi32, _pi32, _pi]),
     "icp_point_to_point_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_point_to_plane_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, _vp, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_comm_unique_id": (_i, [_vp]),
@@ -155,6 +165,9 @@ SIGNATURES = {
     "icp_diag_batch_reverse": (_i, [_vp, _pi32]),
     "icp_diag_batch_eval_moments": (_i, [_vp, _i, _pd]),
     "icp_diag_batch_rotation": (_i, [_vp, _i, _pd]),
+    "icp_diag_batch_set_features": (_i, [_vp, _pd, _pd]),
+    "icp_diag_batch_ransac": (_i, [_vp, _i, _pi32, C.POINTER(C.c_uint8), _pd, _pi32]),
+    "icp_solve_rigid": (_i, [_pd, _pd, _pd]),
     "icp_eigh3": (_i, [_pd, _pd, _pd]),
     "icp_synthetic_grid_f32": (_i, [_i, C.c_float, C.c_float, _vp]),
     "icp_synthetic_grid_f64": (_i, [_i, C.c_double, C.c_double, _vp]),

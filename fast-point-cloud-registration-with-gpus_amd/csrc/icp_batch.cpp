@@ -77,6 +77,15 @@
 // lay_out + allocate]  ->  batch_outlier_compact (the kept points' bytes into the new planes)  ->  the second wait, with the
 // optional outputs.  Three launches, two waits; the source is only read, its loop does not notice.
 //
+// A start pose for pairs in unknown relative pose (global registration; the rules, which numpy reproduces bit for bit, are stated in
+// include/icp_mi355x.h; kernels: icp_k_feat.hip): icp_batch_compute_features (batch_spfh_kernel -> batch_fpfh_kernel, one block
+// per 64 points of every cloud of both sides: a 33-bin FPFH per point, kept on the device)  ->  icp_batch_match_features
+// (batch_feature_match twice, the sides swapped; fwd and rev come down, kept and every pair's correspondence list are made on
+// the host and go back up)  ->  icp_batch_ransac (the hypotheses are drawn, screened and solved on the host -- icp::solve_rigid --
+// and scored by batch_score_transforms, kRansacChunk hypotheses of every pair per launch; the winner is refitted on its inliers and
+// scored once more)  ->  icp_batch_set_initial_transforms.  icp_batch_score_transforms scores the caller's own candidates.  All
+// of them read P0 and Q and buffers of their own: the loop does not notice.
+//
 // Point-to-plane needs the model normals of every pair, in planes laid out as the models: given by the caller
 // (icp_batch_set_model_normals) or made on the device by ONE neighbour launch + ONE normals launch for the whole batch
 // (icp_batch_estimate_normals: knn4_batch + normals_batch_kernel, icp_k_plane.hip).  The reference estimates them once per
@@ -96,6 +105,7 @@
 
 #include "../../include/icp_mi355x_diag.h"
 #include "icp_ctx.h"
+#include "icp_host_math.h"
 
 struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header only names it, as icp_ctx)
     icp_ctx* ctx = nullptr;
@@ -153,6 +163,18 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     DevBuf e_mode, e_thr, e_idx, e_dist, e_partials, e_mom;
     double* h_eval = nullptr;                // pinned: count x ICP_NMOM, the vectors of the latest evaluation
     bool eval_seen = false;                  // h_eval holds an evaluation
+    // global registration (icp_batch_compute_features, _match_features, _score_transforms, _ransac)
+    DevBuf feat[2];                          // every point's descriptor, moving clouds / models: ICP_FEATURE_BINS doubles at (the cloud's offset + i) * ICP_FEATURE_BINS
+    bool have_feat[2] = {false, false};
+    DevBuf f_fwd, f_rev, f_kept;             // the matches: fwd and kept laid out as idx, rev as the models
+    DevBuf f_ci, f_cj, f_cn;                 // every pair's correspondence list (moving index, model index: int32 at p_off + e) and its length (int per pair)
+    bool have_match = false;
+    std::vector<std::vector<int32_t>> corr_i, corr_j;   // the lists on the host
+    DevBuf s_cand, s_valid, s_thr, s_counts; // a scoring launch: candidates, their valid bytes, thresholds, counts
+    int rs_hyp = 0;                          // the last icp_batch_ransac run: hypotheses per pair, then per pair and hypothesis ...
+    std::vector<int32_t> rs_triples, rs_counts;   // ... the three list positions, the count (-1: invalid)
+    std::vector<uint8_t> rs_valid;
+    std::vector<double> rs_T;                // ... and the pose, 16 doubles
 };
 
 namespace {
@@ -194,7 +216,8 @@ void reset_loop_state(icp_batch* b)
 void release(icp_batch* b)
 {
     for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag,
-                      &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->rob_kind, &b->rob_k, &b->rob_k2, &b->weights, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom, &b->cov[0], &b->cov[1], &b->cov_args})
+                      &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->rob_kind, &b->rob_k, &b->rob_k2, &b->weights, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom, &b->cov[0], &b->cov[1], &b->cov_args,
+                      &b->feat[0], &b->feat[1], &b->f_fwd, &b->f_rev, &b->f_kept, &b->f_ci, &b->f_cj, &b->f_cn, &b->s_cand, &b->s_valid, &b->s_thr, &b->s_counts})
         d->release();
     if (b->cov_ev) (void)hipEventDestroy(b->cov_ev);
     if (b->h_cov_args) (void)hipHostFree(b->h_cov_args);
@@ -1703,6 +1726,547 @@ int icp_point_to_plane_batch(icp_ctx* c, int count, const void* moving_aos, cons
     if (prm->max_iter < 1) return fail(ICP_ERR_INVALID, "max_iter must be >= 1");
     return run_batch(c, count, moving_aos, moving_off, model_aos, model_off, true, normals_aos, prm, T16_out, iterations_out, passes_out,
                      err_out, idx_out, moved_out, status_out);
+}
+
+// ---- global registration: descriptors, matching, scoring, RANSAC (the rules: include/icp_mi355x.h; kernels: icp_k_feat.hip) ----
+extern "C++" {
+namespace {
+
+constexpr int kRansacChunk = 4096;   // hypotheses per pair and scoring launch of icp_batch_ransac
+
+// one side's normals: the caller's 3 doubles per point, concatenated as the clouds -> three planes laid out as the cloud's
+void normals_to_planes(const double* aos, const Side& s, std::vector<double>& planes)
+{
+    planes.assign(3 * (size_t)s.plane, 0.0);
+    for (size_t p = 0; p < s.dst.size(); ++p)
+        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
+            for (int k = 0; k < 3; ++k) planes[(size_t)(k * s.plane + s.dst[p] + i)] = aos[3 * (s.off[p] + i) + k];
+}
+
+// downloads the descriptors of the sides whose output pointer is given (one wait) and lays them out as the caller's
+int download_features(icp_batch* b, double* const out[2])
+{
+    std::vector<double> h[2];
+    for (int sd = 0; sd < 2; ++sd)
+        if (out[sd]) {
+            h[sd].resize(ICP_FEATURE_BINS * (size_t)(sd ? b->q_plane : b->p_plane));
+            HIP_TRY(hipMemcpyAsync(h[sd].data(), b->feat[sd].p, h[sd].size() * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
+        }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    for (int sd = 0; sd < 2; ++sd) {
+        if (!out[sd]) continue;
+        const Side s = ::side(b, sd != 0);
+        for (size_t p = 0; p < s.dst.size(); ++p)
+            std::memcpy(out[sd] + ICP_FEATURE_BINS * s.off[p], h[sd].data() + ICP_FEATURE_BINS * (size_t)s.dst[p],
+                        ICP_FEATURE_BINS * (size_t)(s.off[p + 1] - s.off[p]) * sizeof(double));
+    }
+    return ICP_OK;
+}
+
+// the candidates of one scoring launch (count x per_pair, 12 values of the batch's precision each; valid: count x per_pair bytes or
+// NULL) against the batch's correspondence lists: upload, one launch, download of the counts (one wait)
+int score_on_device(icp_batch* b, int per_pair, const std::vector<char>& cand, const uint8_t* valid, const std::vector<char>& thr, int32_t* counts)
+{
+    icp_ctx* c = b->ctx;
+    const size_t total = (size_t)b->count * per_pair;
+    HIP_TRY(b->s_cand.ensure(cand.size()));
+    HIP_TRY(b->s_valid.ensure(total));
+    HIP_TRY(b->s_thr.ensure(thr.size()));
+    HIP_TRY(b->s_counts.ensure(total * sizeof(int32_t)));
+    HIP_TRY(hipMemcpyAsync(b->s_cand.p, cand.data(), cand.size(), hipMemcpyHostToDevice, c->stream));
+    if (valid) HIP_TRY(hipMemcpyAsync(b->s_valid.p, valid, total, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b->s_thr.p, thr.data(), thr.size(), hipMemcpyHostToDevice, c->stream));
+    icp::BatchScoreArgs a{};
+    a.precision = b->prec;
+    a.pairs = (const icp::BatchPair*)b->pairs_d.p;
+    a.n_pairs = b->count;
+    a.cn = (const int*)b->f_cn.p;
+    a.ci = (const int32_t*)b->f_ci.p;
+    a.cj = (const int32_t*)b->f_cj.p;
+    a.P0 = b->P0.p;
+    a.p_plane = b->p_plane;
+    a.Q = b->Q.p;
+    a.q_plane = b->q_plane;
+    a.cand = b->s_cand.p;
+    a.valid = valid ? (const uint8_t*)b->s_valid.p : nullptr;
+    a.thr = b->s_thr.p;
+    a.per_pair = per_pair;
+    a.counts = (int32_t*)b->s_counts.p;
+    HIP_TRY(icp::launch_batch_score(a, c->stream));
+    HIP_TRY(hipMemcpyAsync(counts, b->s_counts.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ICP_OK;
+}
+
+// R, t of a row-major 4 x 4 -> the 12 values of candidate `at` in the batch's precision
+void put_candidate(const icp_batch* b, std::vector<char>& cand, size_t at, const double* T)
+{
+    double R[9], t[3];
+    for (int a = 0; a < 3; ++a) {
+        for (int c = 0; c < 3; ++c) R[a * 3 + c] = T[a * 4 + c];
+        t[a] = T[a * 4 + 3];
+    }
+    void* dst = cand.data() + at * 12 * b->esize;
+    if (b->prec == ICP_F64) put_rt<double>(dst, R, t);
+    else put_rt<float>(dst, R, t);
+}
+
+uint64_t ransac_mix(uint64_t x)
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// batch_score_transforms' decision for one list entry, restated on the host in the batch's precision (this unit is compiled with
+// contraction off): the moved point in the front end's arithmetic, the matching's squared distance, d <= thr
+template <typename F>
+bool host_hit(const double* T, const double* p, const double* q, double thr_d)
+{
+    const F x = (F)p[0], y = (F)p[1], z = (F)p[2];   // (exact: the points are values of F)
+    F o[3];
+    for (int a = 0; a < 3; ++a) {
+        F c = (F)T[a * 4 + 0] * x;
+        c = c + (F)T[a * 4 + 1] * y;
+        c = c + (F)T[a * 4 + 2] * z;
+        o[a] = c + (F)T[a * 4 + 3];
+    }
+    if (!std::isfinite(o[0]) || !std::isfinite(o[1]) || !std::isfinite(o[2])) return false;
+    F dx = (F)q[0] - o[0], dy = (F)q[1] - o[1], dz = (F)q[2] - o[2];
+    dx = dx * dx;
+    dy = dy * dy;
+    dz = dz * dz;
+    F d = dx + dy;
+    d = d + dz;
+    return d <= (F)thr_d;
+}
+
+double sqd(const double* a, const double* b)
+{
+    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// one match into the 32-double moment vector of icp_solve_rigid
+void add_match(double* mom, const double* p, const double* q)
+{
+    mom[ICP_MOM_CNT] += 1.0;
+    for (int a = 0; a < 3; ++a) {
+        mom[ICP_MOM_SP + a] += p[a];
+        mom[ICP_MOM_SQ + a] += q[a];
+        for (int c = 0; c < 3; ++c) mom[ICP_MOM_SQP + a * 3 + c] += q[a] * p[c];
+    }
+}
+
+void identity16(double* T)
+{
+    for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+}
+
+void pose16(const double* R, const double* t, double* T)
+{
+    for (int a = 0; a < 3; ++a) {
+        for (int c = 0; c < 3; ++c) T[a * 4 + c] = R[a * 3 + c];
+        T[a * 4 + 3] = t[a];
+    }
+    T[12] = T[13] = T[14] = 0.0;
+    T[15] = 1.0;
+}
+
+bool finite16(const icp_batch* b, const double* T)
+{
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(T[k]) || (b->prec == ICP_F32 && !std::isfinite((float)T[k]))) return false;
+    return true;
+}
+
+}  // namespace
+}  // extern "C++" (the templates above)
+
+int icp_batch_compute_features(icp_batch* b, const int* k_moving, const int* k_model, const double* moving_normals,
+                               const double* model_normals, double* moving_feat_out, double* model_feat_out)
+{
+    if (int rc = ready(b)) return rc;
+    const int* ks_given[2] = {k_moving, k_model};
+    const double* nrm_given[2] = {moving_normals, model_normals};
+    for (int sd = 0; sd < 2; ++sd) {
+        if (!ks_given[sd]) return fail(ICP_ERR_INVALID, std::string("descriptors need a k for both sides: ") + (sd ? "k_model" : "k_moving") + " == NULL");
+        if (!nrm_given[sd]) return fail(ICP_ERR_INVALID, std::string("descriptors need normals on both sides: ") + (sd ? "model_normals" : "moving_normals") + " == NULL");
+    }
+    const int count = b->count, n_clouds = 2 * count;
+    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
+    std::vector<icp::BatchItem> items;
+    std::vector<int> ks((size_t)n_clouds, 0);
+    int cap = 8;
+    for (int k = 0; k < n_clouds; ++k) {   // the 2 * count clouds, moving clouds first
+        const int sd = k < count ? 0 : 1, p = k - sd * count;
+        const icp::BatchPair& pr = b->pairs[p];
+        clouds[k] = icp::VoxelCloud{sd ? pr.q_off : pr.p_off, 0, 0, sd ? pr.m : pr.n, sd};
+        const int kk = ks_given[sd][p];
+        if (kk < ICP_COV_MIN_NEIGHBOURS || kk > ICP_COV_MAX_NEIGHBOURS)
+            return fail(ICP_ERR_INVALID, "the neighbours (k) of a descriptor must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]: pair " +
+                                             std::to_string(p) + side_name(sd));
+        if (clouds[k].n < kk + 1)
+            return fail(ICP_ERR_INVALID, "descriptors from k neighbours need a cloud of at least k + 1 points: pair " + std::to_string(p) + side_name(sd));
+        const int64_t* off = sd ? b->qoff.data() : b->moff.data();
+        for (int64_t i = 3 * off[p]; i < 3 * off[p + 1]; ++i)
+            if (!std::isfinite(nrm_given[sd][i]))
+                return fail(ICP_ERR_INVALID, "a normal has a NaN or an infinite value: pair " + std::to_string(p) + side_name(sd));
+        ks[k] = kk;
+        cap = std::max(cap, kk <= 8 ? 8 : kk <= 16 ? 16 : 32);
+        for (int first = 0; first < clouds[k].n; first += icp::BATCH_ITEM)
+            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, clouds[k].n - first), 0});
+    }
+    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    icp_ctx* c = b->ctx;
+    hipStream_t st = c->stream;
+    ScopedPin pin(c);
+    // the temporaries of the call: the normals, tau and the SPFH of both sides, the clouds, items and k.  The allocations come before
+    // the batch changes: a call refused for want of memory leaves it as it was
+    struct Temps {
+        DevBuf nrm[2], tau[2], spfh[2], args;
+        ~Temps() { for (DevBuf* d : {&nrm[0], &nrm[1], &tau[0], &tau[1], &spfh[0], &spfh[1], &args}) d->release(); }
+    } tmp;
+    auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
+    const size_t off_items = up16(clouds.size() * sizeof(icp::VoxelCloud));
+    const size_t off_k = off_items + up16(items.size() * sizeof(icp::BatchItem));
+    const size_t arg_bytes = off_k + ks.size() * sizeof(int);
+    std::vector<char> hs(arg_bytes, 0);
+    std::memcpy(hs.data(), clouds.data(), clouds.size() * sizeof(icp::VoxelCloud));
+    std::memcpy(hs.data() + off_items, items.data(), items.size() * sizeof(icp::BatchItem));
+    std::memcpy(hs.data() + off_k, ks.data(), ks.size() * sizeof(int));
+    HIP_TRY(tmp.args.ensure(arg_bytes));
+    std::vector<double> hn[2];
+    for (int sd = 0; sd < 2; ++sd) {
+        const size_t plane = (size_t)(sd ? b->q_plane : b->p_plane);
+        HIP_TRY(tmp.nrm[sd].ensure(3 * plane * sizeof(double)));
+        HIP_TRY(tmp.tau[sd].ensure(plane * b->esize));
+        HIP_TRY(tmp.spfh[sd].ensure(ICP_FEATURE_BINS * plane * sizeof(double)));
+        HIP_TRY(b->feat[sd].ensure(ICP_FEATURE_BINS * plane * sizeof(double)));
+        normals_to_planes(nrm_given[sd], ::side(b, sd != 0), hn[sd]);
+    }
+    b->have_feat[0] = b->have_feat[1] = false;
+    b->have_match = false;   // (matches of other descriptors)
+    HIP_TRY(hipMemcpyAsync(tmp.args.p, hs.data(), arg_bytes, hipMemcpyHostToDevice, st));
+    for (int sd = 0; sd < 2; ++sd) {
+        const size_t plane = (size_t)(sd ? b->q_plane : b->p_plane);
+        HIP_TRY(hipMemcpyAsync(tmp.nrm[sd].p, hn[sd].data(), hn[sd].size() * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(tmp.spfh[sd].p, 0, ICP_FEATURE_BINS * plane * sizeof(double), st));   // (the padding between the clouds: never read, never random)
+        HIP_TRY(hipMemsetAsync(b->feat[sd].p, 0, ICP_FEATURE_BINS * plane * sizeof(double), st));
+        HIP_TRY(hipMemsetAsync(tmp.tau[sd].p, 0, plane * b->esize, st));
+    }
+    const char* ds = static_cast<const char*>(tmp.args.p);
+    icp::BatchFeatArgs a{};
+    a.precision = b->prec;
+    a.cap = cap;
+    a.clouds = reinterpret_cast<const icp::VoxelCloud*>(ds);
+    a.items = reinterpret_cast<const icp::BatchItem*>(ds + off_items);
+    a.n_items = (int)items.size();
+    a.k = reinterpret_cast<const int*>(ds + off_k);
+    a.src[0] = b->P0.p;
+    a.src[1] = b->Q.p;
+    a.src_plane[0] = b->p_plane;
+    a.src_plane[1] = b->q_plane;
+    for (int sd = 0; sd < 2; ++sd) {
+        a.nrm[sd] = (const double*)tmp.nrm[sd].p;
+        a.tau[sd] = tmp.tau[sd].p;
+        a.spfh[sd] = (double*)tmp.spfh[sd].p;
+        a.feat[sd] = (double*)b->feat[sd].p;
+    }
+    const hipError_t le = icp::launch_batch_features(a, st);
+    const hipError_t se = hipStreamSynchronize(st);   // (the one wait: the temporaries and the host vectors go with the call)
+    HIP_TRY(le);
+    HIP_TRY(se);
+    b->have_feat[0] = b->have_feat[1] = true;
+    double* const out[2] = {moving_feat_out, model_feat_out};
+    if (out[0] || out[1]) return download_features(b, out);
+    return ICP_OK;
+}
+
+int icp_batch_get_features(icp_batch* b, double* moving_feat_out, double* model_feat_out)
+{
+    if (int rc = ready(b)) return rc;
+    double* const out[2] = {moving_feat_out, model_feat_out};
+    if (!out[0] && !out[1]) return fail(ICP_ERR_INVALID, "output pointer == NULL");
+    for (int sd = 0; sd < 2; ++sd)
+        if (out[sd] && !b->have_feat[sd]) return fail(ICP_ERR_STATE, std::string("the batch holds no descriptors of the ") + (sd ? "models" : "moving clouds") + " (icp_batch_compute_features first)");
+    return download_features(b, out);
+}
+
+int icp_diag_batch_set_features(icp_batch* b, const double* moving_feat, const double* model_feat)
+{
+    if (int rc = ready(b)) return rc;
+    const double* given[2] = {moving_feat, model_feat};
+    if (!given[0] || !given[1]) return fail(ICP_ERR_INVALID, "moving_feat == NULL or model_feat == NULL");
+    std::vector<double> h[2];
+    for (int sd = 0; sd < 2; ++sd) {
+        const Side s = ::side(b, sd != 0);
+        HIP_TRY(b->feat[sd].ensure(ICP_FEATURE_BINS * (size_t)s.plane * sizeof(double)));
+        h[sd].assign(ICP_FEATURE_BINS * (size_t)s.plane, 0.0);
+        for (size_t p = 0; p < s.dst.size(); ++p)
+            std::memcpy(h[sd].data() + ICP_FEATURE_BINS * (size_t)s.dst[p], given[sd] + ICP_FEATURE_BINS * s.off[p],
+                        ICP_FEATURE_BINS * (size_t)(s.off[p + 1] - s.off[p]) * sizeof(double));
+    }
+    b->have_feat[0] = b->have_feat[1] = false;
+    b->have_match = false;
+    for (int sd = 0; sd < 2; ++sd)
+        HIP_TRY(hipMemcpyAsync(b->feat[sd].p, h[sd].data(), h[sd].size() * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
+    b->have_feat[0] = b->have_feat[1] = true;
+    return ICP_OK;
+}
+
+int icp_batch_match_features(icp_batch* b, int mutual, int32_t* fwd_out, int32_t* rev_out, uint8_t* kept_out)
+{
+    if (int rc = ready(b)) return rc;
+    if (!b->have_feat[0] || !b->have_feat[1]) return fail(ICP_ERR_STATE, "the batch holds no descriptors (icp_batch_compute_features first)");
+    icp_ctx* c = b->ctx;
+    ScopedPin pin(c);
+    if (int rc = ensure_model_items(b)) return rc;
+    HIP_TRY(b->f_fwd.ensure((size_t)b->p_plane * sizeof(int32_t)));
+    HIP_TRY(b->f_rev.ensure((size_t)b->q_plane * sizeof(int32_t)));
+    HIP_TRY(b->f_kept.ensure((size_t)b->p_plane));
+    HIP_TRY(b->f_ci.ensure((size_t)b->p_plane * sizeof(int32_t)));
+    HIP_TRY(b->f_cj.ensure((size_t)b->p_plane * sizeof(int32_t)));
+    HIP_TRY(b->f_cn.ensure((size_t)b->count * sizeof(int)));
+    b->have_match = false;
+    HIP_TRY(hipMemsetAsync(b->f_fwd.p, 0, (size_t)b->p_plane * sizeof(int32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(b->f_rev.p, 0, (size_t)b->q_plane * sizeof(int32_t), c->stream));
+    icp::BatchFeatMatchArgs a{};
+    a.items[0] = (const icp::BatchItem*)b->items.p;
+    a.items[1] = (const icp::BatchItem*)b->q_items.p;
+    a.n_items[0] = b->n_items;
+    a.n_items[1] = b->n_q_items;
+    a.pairs = (const icp::BatchPair*)b->pairs_d.p;
+    a.feat[0] = (const double*)b->feat[0].p;
+    a.feat[1] = (const double*)b->feat[1].p;
+    a.fwd = (int32_t*)b->f_fwd.p;
+    a.rev = (int32_t*)b->f_rev.p;
+    HIP_TRY(icp::launch_batch_feature_match(a, c->stream));
+    std::vector<int32_t> hf((size_t)b->p_plane), hr((size_t)b->q_plane);
+    HIP_TRY(hipMemcpyAsync(hf.data(), b->f_fwd.p, hf.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hr.data(), b->f_rev.p, hr.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // kept and the correspondence lists, on the host; the lists go back for batch_score_transforms
+    std::vector<uint8_t> kept((size_t)b->p_plane, 0);
+    std::vector<int32_t> ci((size_t)b->p_plane, 0), cj((size_t)b->p_plane, 0);
+    std::vector<int> cn((size_t)b->count, 0);
+    std::vector<std::vector<int32_t>> li((size_t)b->count), lj((size_t)b->count);
+    for (int p = 0; p < b->count; ++p) {
+        const icp::BatchPair& pr = b->pairs[p];
+        for (int i = 0; i < pr.n; ++i) {
+            const int32_t j = hf[(size_t)pr.p_off + i];
+            const bool k = !mutual || hr[(size_t)pr.q_off + j] == i;
+            kept[(size_t)pr.p_off + i] = k ? 1 : 0;
+            if (!k) continue;
+            ci[(size_t)pr.p_off + cn[p]] = i;
+            cj[(size_t)pr.p_off + cn[p]] = j;
+            cn[p] += 1;
+            li[p].push_back(i);
+            lj[p].push_back(j);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(b->f_kept.p, kept.data(), kept.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b->f_ci.p, ci.data(), ci.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b->f_cj.p, cj.data(), cj.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b->f_cn.p, cn.data(), cn.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // (before the host vectors go)
+    for (int p = 0; p < b->count; ++p) {
+        const icp::BatchPair& pr = b->pairs[p];
+        if (fwd_out) std::memcpy(fwd_out + b->moff[p], hf.data() + pr.p_off, (size_t)pr.n * sizeof(int32_t));
+        if (kept_out) std::memcpy(kept_out + b->moff[p], kept.data() + pr.p_off, (size_t)pr.n);
+        if (rev_out) std::memcpy(rev_out + b->qoff[p], hr.data() + pr.q_off, (size_t)pr.m * sizeof(int32_t));
+    }
+    b->corr_i.swap(li);
+    b->corr_j.swap(lj);
+    b->have_match = true;
+    return ICP_OK;
+}
+
+int icp_batch_score_transforms(icp_batch* b, int per_pair, const double* T16, const double* max_dist, int32_t* count_out)
+{
+    if (int rc = ready(b)) return rc;
+    if (!b->have_match) return fail(ICP_ERR_STATE, "the batch holds no correspondence lists (icp_batch_match_features first)");
+    if (per_pair < 1 || per_pair > 65536) return fail(ICP_ERR_INVALID, "per_pair must lie in [1, 65536]");
+    if (!T16 || !count_out) return fail(ICP_ERR_INVALID, "T16 == NULL or count_out == NULL");
+    for (int p = 0; p < b->count; ++p) {
+        for (int k = 0; k < per_pair; ++k) {
+            const double* T = T16 + ((size_t)p * per_pair + k) * 16;
+            for (int e = 0; e < 16; ++e)
+                if (!std::isfinite(T[e]) || (b->prec == ICP_F32 && !std::isfinite((float)T[e])))
+                    return fail(ICP_ERR_INVALID, "a candidate transform has a NaN or an infinite value: pair " + std::to_string(p));
+            if (!(T[12] == 0.0 && T[13] == 0.0 && T[14] == 0.0 && T[15] == 1.0))
+                return fail(ICP_ERR_INVALID, "the bottom row of a candidate transform must be exactly 0 0 0 1: pair " + std::to_string(p));
+        }
+        if (max_dist && !(max_dist[p] > 0))
+            return fail(ICP_ERR_INVALID, "the scoring distance must be > 0 or +INFINITY: pair " + std::to_string(p));
+    }
+    ScopedPin pin(b->ctx);
+    const size_t total = (size_t)b->count * per_pair;
+    std::vector<char> cand(total * 12 * b->esize), thr((size_t)b->count * b->esize);
+    for (size_t at = 0; at < total; ++at) put_candidate(b, cand, at, T16 + at * 16);
+    for (int p = 0; p < b->count; ++p) put_scalar(b, thr.data(), (size_t)p, max_dist ? max_dist[p] * max_dist[p] : INFINITY);
+    return score_on_device(b, per_pair, cand, nullptr, thr, count_out);
+}
+
+int icp_batch_ransac(icp_batch* b, const icp_ransac_params* prm, const uint64_t* seed, double* T16_out, int32_t* inliers_out,
+                     int32_t* correspondences_out, int* status_out)
+{
+    if (int rc = ready(b)) return rc;
+    if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
+    if (!seed) return fail(ICP_ERR_INVALID, "seed == NULL");
+    if (prm->hypotheses < 1 || prm->hypotheses > 65536) return fail(ICP_ERR_INVALID, "hypotheses must lie in [1, 65536]");
+    if (!(std::isfinite(prm->max_distance) && prm->max_distance > 0.0)) return fail(ICP_ERR_INVALID, "max_distance must be finite and > 0");
+    if (!(prm->edge_similarity >= 0.0 && prm->edge_similarity < 1.0)) return fail(ICP_ERR_INVALID, "edge_similarity must lie in [0, 1)");
+    if (!b->have_match) return fail(ICP_ERR_STATE, "the batch holds no correspondence lists (icp_batch_match_features first)");
+    icp_ctx* c = b->ctx;
+    ScopedPin pin(c);
+    const int count = b->count, H = prm->hypotheses;
+    const double e = prm->edge_similarity;
+    // the clouds, widened: P0 and Q as the device holds them
+    std::vector<char> ps(3 * (size_t)b->p_plane * b->esize), qs(3 * (size_t)b->q_plane * b->esize);
+    HIP_TRY(hipMemcpyAsync(ps.data(), b->P0.p, ps.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(qs.data(), b->Q.p, qs.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    auto point = [b](const std::vector<char>& raw, long long plane, long long at, double* o) {
+        for (int k = 0; k < 3; ++k) o[k] = get_scalar(b, raw.data(), (size_t)(k * plane + at));
+    };
+    const double thr_d = prm->max_distance * prm->max_distance;
+    std::vector<char> thr((size_t)count * b->esize);
+    for (int p = 0; p < count; ++p) put_scalar(b, thr.data(), (size_t)p, thr_d);
+    const double thr_f = get_scalar(b, thr.data(), 0);   // (the threshold as the kernel reads it)
+
+    // the hypotheses of every pair: draws, edge check, solve
+    std::vector<int32_t> triples((size_t)count * H * 3, -1), counts((size_t)count * H, -1);
+    std::vector<uint8_t> valid((size_t)count * H, 0);
+    std::vector<double> Th((size_t)count * H * 16);
+    std::vector<std::vector<double>> LP((size_t)count), LQ((size_t)count);   // the list's points, 3 doubles per entry
+    for (int p = 0; p < count; ++p) {
+        const icp::BatchPair& pr = b->pairs[p];
+        const size_t C = b->corr_i[p].size();
+        LP[p].resize(3 * C);
+        LQ[p].resize(3 * C);
+        for (size_t k = 0; k < C; ++k) {
+            point(ps, b->p_plane, pr.p_off + b->corr_i[p][k], &LP[p][3 * k]);
+            point(qs, b->q_plane, pr.q_off + b->corr_j[p][k], &LQ[p][3 * k]);
+        }
+        const uint64_t s0 = ransac_mix(seed[p]);
+        for (int h = 0; h < H; ++h) {
+            const size_t at = (size_t)p * H + h;
+            identity16(&Th[at * 16]);
+            if (C < 3) continue;
+            const uint64_t base = ransac_mix(s0 + (uint64_t)h);
+            int32_t* slot = &triples[at * 3];
+            int got = 0;
+            for (int r = 0; r < 16 && got < 3; ++r) {
+                const int32_t v = (int32_t)(ransac_mix(base + (uint64_t)r) % (uint64_t)C);
+                bool seen = false;
+                for (int s = 0; s < got; ++s) seen = seen || slot[s] == v;
+                if (!seen) slot[got++] = v;
+            }
+            if (got < 3) continue;
+            bool ok = true;
+            if (e > 0.0) {
+                static const int ea[3] = {0, 1, 0}, eb[3] = {1, 2, 2};
+                for (int k = 0; k < 3 && ok; ++k) {
+                    const double la = std::sqrt(sqd(&LP[p][3 * slot[ea[k]]], &LP[p][3 * slot[eb[k]]]));
+                    const double lb = std::sqrt(sqd(&LQ[p][3 * slot[ea[k]]], &LQ[p][3 * slot[eb[k]]]));
+                    ok = la >= e * lb && lb >= e * la;
+                }
+            }
+            if (!ok) continue;
+            double mom[ICP_NMOM] = {0}, R[9], t[3];
+            for (int s = 0; s < 3; ++s) add_match(mom, &LP[p][3 * slot[s]], &LQ[p][3 * slot[s]]);
+            if (icp::solve_rigid(mom, R, t) != ICP_OK) continue;
+            double T[16];
+            pose16(R, t, T);
+            if (!finite16(b, T)) continue;
+            std::memcpy(&Th[at * 16], T, sizeof T);
+            valid[at] = 1;
+        }
+    }
+    // scoring: every pair's hypotheses [h0, h0 + per) in one launch
+    for (int h0 = 0; h0 < H; h0 += kRansacChunk) {
+        const int per = std::min(kRansacChunk, H - h0);
+        std::vector<char> cand((size_t)count * per * 12 * b->esize);
+        std::vector<uint8_t> ok((size_t)count * per);
+        std::vector<int32_t> got((size_t)count * per);
+        for (int p = 0; p < count; ++p)
+            for (int k = 0; k < per; ++k) {
+                const size_t at = (size_t)p * H + h0 + k;
+                put_candidate(b, cand, (size_t)p * per + k, &Th[at * 16]);
+                ok[(size_t)p * per + k] = valid[at];
+            }
+        if (int rc = score_on_device(b, per, cand, ok.data(), thr, got.data())) return rc;
+        for (int p = 0; p < count; ++p)
+            for (int k = 0; k < per; ++k) {
+                const size_t at = (size_t)p * H + h0 + k;
+                if (valid[at]) counts[at] = got[(size_t)p * per + k];
+            }
+    }
+    // winner, refit
+    std::vector<double> Tw((size_t)count * 16), Tr((size_t)count * 16);
+    std::vector<int32_t> cw((size_t)count, 0), cr((size_t)count, 0);
+    std::vector<int> status((size_t)count, ICP_ERR_EMPTY);
+    std::vector<uint8_t> refit_ok((size_t)count, 0);
+    for (int p = 0; p < count; ++p) {
+        identity16(&Tw[(size_t)p * 16]);
+        identity16(&Tr[(size_t)p * 16]);
+        int best = -1;
+        for (int h = 0; h < H; ++h)
+            if (valid[(size_t)p * H + h] && (best < 0 || counts[(size_t)p * H + h] > counts[(size_t)p * H + best])) best = h;
+        if (best < 0) continue;
+        status[p] = ICP_OK;
+        const double* T = &Th[((size_t)p * H + best) * 16];
+        std::memcpy(&Tw[(size_t)p * 16], T, 16 * sizeof(double));
+        cw[p] = counts[(size_t)p * H + best];
+        double mom[ICP_NMOM] = {0}, R[9], t[3];
+        const size_t C = b->corr_i[p].size();
+        for (size_t k = 0; k < C; ++k) {
+            const bool hit = b->prec == ICP_F64 ? host_hit<double>(T, &LP[p][3 * k], &LQ[p][3 * k], thr_f) : host_hit<float>(T, &LP[p][3 * k], &LQ[p][3 * k], thr_f);
+            if (hit) add_match(mom, &LP[p][3 * k], &LQ[p][3 * k]);
+        }
+        if (mom[ICP_MOM_CNT] >= 3.0 && icp::solve_rigid(mom, R, t) == ICP_OK) {
+            double T2[16];
+            pose16(R, t, T2);
+            if (finite16(b, T2)) {
+                std::memcpy(&Tr[(size_t)p * 16], T2, sizeof T2);
+                refit_ok[p] = 1;
+            }
+        }
+    }
+    {
+        std::vector<char> cand((size_t)count * 12 * b->esize);
+        for (int p = 0; p < count; ++p) put_candidate(b, cand, (size_t)p, &Tr[(size_t)p * 16]);
+        if (int rc = score_on_device(b, 1, cand, refit_ok.data(), thr, cr.data())) return rc;
+    }
+    for (int p = 0; p < count; ++p) {
+        const bool refit = status[p] == ICP_OK && refit_ok[p] && cr[p] >= cw[p];
+        if (T16_out) std::memcpy(T16_out + (size_t)p * 16, refit ? &Tr[(size_t)p * 16] : &Tw[(size_t)p * 16], 16 * sizeof(double));
+        if (inliers_out) inliers_out[p] = status[p] == ICP_OK ? (refit ? cr[p] : cw[p]) : 0;
+        if (correspondences_out) correspondences_out[p] = (int32_t)b->corr_i[p].size();
+        if (status_out) status_out[p] = status[p];
+    }
+    b->rs_hyp = H;
+    b->rs_triples.swap(triples);
+    b->rs_valid.swap(valid);
+    b->rs_T.swap(Th);
+    b->rs_counts.swap(counts);
+    return ICP_OK;
+}
+
+int icp_diag_batch_ransac(icp_batch* b, int pair, int32_t* triples, uint8_t* valid, double* T16, int32_t* counts)
+{
+    if (!b) return fail(ICP_ERR_INVALID, "null batch");
+    if (pair < 0 || pair >= b->count) return fail(ICP_ERR_INVALID, "pair out of range");
+    if (b->rs_hyp == 0) return fail(ICP_ERR_STATE, "no icp_batch_ransac run on this batch");
+    const size_t H = (size_t)b->rs_hyp, at = (size_t)pair * H;
+    if (triples) std::memcpy(triples, b->rs_triples.data() + at * 3, H * 3 * sizeof(int32_t));
+    if (valid) std::memcpy(valid, b->rs_valid.data() + at, H);
+    if (T16) std::memcpy(T16, b->rs_T.data() + at * 16, H * 16 * sizeof(double));
+    if (counts) std::memcpy(counts, b->rs_counts.data() + at, H * sizeof(int32_t));
+    return ICP_OK;
 }
 
 }  // extern "C"

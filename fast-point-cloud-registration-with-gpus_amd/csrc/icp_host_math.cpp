@@ -116,6 +116,37 @@ int solve_point_to_point(const double* mom, double* R, double* t)
     return ICP_OK;
 }
 
+// solve_point_to_point with the determinant fix (Kabsch / Umeyama): the singular values come out in descending order, so the last
+// column of U belongs to the smallest; flipping it when det(U Vt) < 0 gives the rotation nearest to the cross-covariance.
+int solve_rigid(const double* mom, double* R, double* t)
+{
+    const double n = mom[ICP_MOM_CNT];
+    if (!(n > 0)) return ICP_ERR_INVALID;
+    double pb[3], qb[3];
+    for (int a = 0; a < 3; ++a) {
+        pb[a] = mom[ICP_MOM_SP + a] / n;
+        qb[a] = mom[ICP_MOM_SQ + a] / n;
+    }
+    double N[9];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) N[a * 3 + b] = mom[ICP_MOM_SQP + a * 3 + b] - n * qb[a] * pb[b];
+    double U[9], S[3], Vt[9];
+    svd3_rows(N, U, S, Vt);
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) {
+                double s = 0;
+                for (int k = 0; k < 3; ++k) s += U[a * 3 + k] * Vt[k * 3 + b];
+                R[a * 3 + b] = s;
+            }
+        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+        if (!(det < 0)) break;
+        for (int a = 0; a < 3; ++a) U[a * 3 + 2] = -U[a * 3 + 2];
+    }
+    for (int a = 0; a < 3; ++a) t[a] = qb[a] - (R[a * 3 + 0] * pb[0] + R[a * 3 + 1] * pb[1] + R[a * 3 + 2] * pb[2]);
+    return ICP_OK;
+}
+
 // Upper Cholesky C = Ut*U of the 6x6 SPD matrix given by its upper triangle (row-major packed, 21).
 int solve_point_to_plane(const double* mom, double* R, double* t, double* x6)
 {
@@ -220,6 +251,11 @@ int icp_solve_point_to_point(const double* mom, double* R9, double* t3)
 {
     if (!mom || !R9 || !t3) return ICP_ERR_INVALID;
     return icp::solve_point_to_point(mom, R9, t3);
+}
+int icp_solve_rigid(const double* mom, double* R9, double* t3)
+{
+    if (!mom || !R9 || !t3) return ICP_ERR_INVALID;
+    return icp::solve_rigid(mom, R9, t3);
 }
 int icp_solve_point_to_plane(const double* mom, double* R9, double* t3, double* x6)
 {

@@ -490,6 +490,55 @@ struct BatchCovArgs {
     double* cov[2];            // double[6][src_plane[side]]: xx, xy, xz, yy, yz, zz, laid out as the clouds
 };
 hipError_t launch_batch_covariances(const BatchCovArgs& a, hipStream_t st);
+// global registration (icp_k_feat.hip; the rules: include/icp_mi355x.h).  Descriptors: the clouds, their numbering, the work items
+// and k are the covariance call's, over both sides; two launches, batch_spfh_kernel (-> spfh, tau) and batch_fpfh_kernel (-> feat).
+// A descriptor is ICP_FEATURE_BINS doubles; point i of a cloud has its own at [(src_off + i) * ICP_FEATURE_BINS].
+struct BatchFeatArgs {
+    int precision;             // ICP_F32 / ICP_F64
+    int cap;                   // 8, 16 or 32: the register capacity of the list, >= the largest k of the launch
+    const VoxelCloud* clouds;  // [2 * n_pairs]
+    const BatchItem* items;    // BatchItem::pair = the cloud's number
+    int n_items;
+    const int* k;              // int[2 * n_pairs]
+    const void* src[2];        // P0 and Q (read only)
+    long long src_plane[2];
+    const double* nrm[2];      // double[3][src_plane[side]]: the caller's normals, laid out as the clouds
+    void* tau[2];              // F[src_plane[side]]: the k-th smallest distance of every point (written by the first launch)
+    double* spfh[2];           // double[src_plane[side]][ICP_FEATURE_BINS] (written by the first launch, read by the second)
+    double* feat[2];           // double[src_plane[side]][ICP_FEATURE_BINS]
+};
+hipError_t launch_batch_features(const BatchFeatArgs& a, hipStream_t st);
+// batch_feature_match, twice: fwd[p_off + i] = the model point of pair p whose descriptor is nearest to moving point i's (the lowest
+// index on ties), rev[q_off + j] the same with the sides swapped.  items[0] / items[1]: the work items of the moving clouds / models.
+struct BatchFeatMatchArgs {
+    const BatchItem* items[2];
+    int n_items[2];
+    const BatchPair* pairs;
+    const double* feat[2];
+    int32_t* fwd;              // int32[p_plane]
+    int32_t* rev;              // int32[q_plane]
+};
+hipError_t launch_batch_feature_match(const BatchFeatMatchArgs& a, hipStream_t st);
+// batch_score_transforms: counts[pair * per_pair + c] = the entries e < cn[pair] of the pair's correspondence list (ci, cj: int32,
+// at p_off + e; indices within the pair's clouds) with dist2(cand . P0[ci[e]], Q[cj[e]]) <= thr[pair] and a finite moved point.
+struct BatchScoreArgs {
+    int precision;
+    const BatchPair* pairs;
+    int n_pairs;
+    const int* cn;             // int[n_pairs]
+    const int32_t* ci;
+    const int32_t* cj;
+    const void* P0;
+    long long p_plane;
+    const void* Q;
+    long long q_plane;
+    const void* cand;          // F[n_pairs][per_pair][12]: R row-major, then t
+    const uint8_t* valid;      // uint8[n_pairs][per_pair], or NULL: every candidate is scored
+    const void* thr;           // F[n_pairs]
+    int per_pair;
+    int32_t* counts;           // int32[n_pairs][per_pair]
+};
+hipError_t launch_batch_score(const BatchScoreArgs& a, hipStream_t st);
 
 // soa2 (optional): a second copy of the result (the pristine moving cloud); enc (optional, fp32): the cloud's bounding cube as six
 // ordered-integer words {~ord(min xyz), ord(max xyz)}, zero before the launch

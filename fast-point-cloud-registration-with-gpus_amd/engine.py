@@ -351,6 +351,43 @@ class Context:
                                   extra={"status": st["status"], "inliers": inl[b], "fitness": float(inl[b].sum()) / inl[b].size}))
             return out
 
+    def register_batch_global(self, pairs, voxel, k, hypotheses, max_distance, **options):
+        """register_batch for pairs in unknown relative pose: a start pose from descriptors first, then the local loop from it.
+        The pairs are uploaded once; a copy thinned at voxel (Batch.downsample; 0 or None: the clouds themselves) gets raw
+        covariances from k neighbours (ICP_COV_NONE), normals from them (oriented_normals, facing viewpoint -- None: each cloud's
+        own centroid, which no rigid motion changes), FPFH descriptors from the same k (Batch.compute_features), mutual matches
+        (Batch.match_features) and a RANSAC pose (Batch.ransac with hypotheses, max_distance and the options edge_similarity,
+        0.9, and seed, 0); register_batch then runs on the full pairs with init = those poses.  options: besides viewpoint,
+        edge_similarity, seed and mutual (True), register_batch's by keyword without init; gate is handed on as its max_distance.
+        The same list of Result, with extra["global"] added: the dict Batch.ransac returned for the pair."""
+        known = {"viewpoint", "edge_similarity", "seed", "mutual", "gate", "metric", "normals", "max_iter", "tol", "fixed_iterations", "trim", "reciprocal"}
+        unknown = set(options) - known
+        if unknown:
+            raise TypeError(f"register_batch_global: unknown option(s) {sorted(unknown)}")
+        pairs = list(pairs)
+        v = 0.0 if voxel is None else float(voxel)
+        with Batch(self, pairs) as full:
+            bt = full if v == 0.0 else full.downsample(v)
+            try:
+                cm, cq = bt.estimate_covariances(k, None, regularisation="none", want=True)
+                clouds = bt.get_clouds()
+                view = options.get("viewpoint")
+                eye = lambda X: X.astype(np.float64).mean(0) if view is None else view
+                nm = [oriented_normals(D, c, eye(D)) for (D, _), c in zip(clouds, cm)]
+                nq = [oriented_normals(M, c, eye(M)) for (_, M), c in zip(clouds, cq)]
+                bt.compute_features(k, (nm, nq))
+                bt.match_features(mutual=options.get("mutual", True))
+                start = bt.ransac(hypotheses, max_distance, edge_similarity=options.get("edge_similarity", 0.9), seed=options.get("seed", 0))
+            finally:
+                if bt is not full:
+                    bt.close()
+        T0 = np.stack([r["T"] for r in start])
+        rest = {o: options[o] for o in ("metric", "normals", "max_iter", "tol", "fixed_iterations", "trim", "reciprocal") if o in options}
+        out = self.register_batch(pairs, max_distance=options.get("gate"), init=T0, **rest)
+        for res, r in zip(out, start):
+            res.extra["global"] = r
+        return out
+
     def register_batch_multiscale(self, pairs, voxels, **options):
         """coarse-to-fine register_batch on a voxel pyramid made on the device: the pairs are uploaded once, and level l runs on
         that batch thinned at voxels[l] (Batch.downsample; 0 or None: full resolution, the uploaded batch itself).  voxels:
@@ -844,6 +881,116 @@ class Batch:
         capi.check(self._lib.icp_diag_batch_rotation(self._h, int(b), R.ctypes.data_as(C.POINTER(C.c_double))), "icp_diag_batch_rotation")
         return R.reshape(3, 3)
 
+    def _normals_side(self, normals, off, what):
+        """one (points, 3) float64 array per pair -> their concatenation in that side's layout"""
+        normals = [np.ascontiguousarray(a, dtype=np.float64) for a in normals]
+        if len(normals) != self.count:
+            raise ValueError(f"one array of {what} normals per pair")
+        for b, a in enumerate(normals):
+            if a.shape != (int(off[b + 1] - off[b]), 3):
+                raise ValueError(f"a pair's {what} normals must be (points, 3)")
+        return np.ascontiguousarray(np.concatenate(normals))
+
+    def _cut33(self, flat, off):
+        return [flat[off[b]:off[b + 1]].copy() for b in range(self.count)]
+
+    def compute_features(self, k, normals, k_model=None, want=False):
+        """a 33-bin FPFH descriptor of every point of both clouds of every pair, on the device in two launches
+        (icp_batch_compute_features): k neighbours per point (a scalar or one value per pair, each in [3, 32]; k_model: the same
+        for the models, None: as k) and normals = (moving, model), per side one (points, 3) float64 array of unit normals per pair,
+        consistently oriented (the caller's duty; oriented_normals makes them from covariances).  The clouds are those the batch
+        holds as uploaded, never the moved ones; a loop under way is left alone.  want: also return (moving, model), per pair the
+        (points, 33) float64 descriptors."""
+        moving, model = normals
+        km, kq = self._cov_k(k, "k"), self._cov_k(k if k_model is None else k_model, "model k")
+        nm, nq = self._normals_side(moving, self._moff, "moving"), self._normals_side(model, self._qoff, "model")
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        om = np.empty((int(self._moff[-1]), capi.ICP_FEATURE_BINS)) if want else None
+        oq = np.empty((int(self._qoff[-1]), capi.ICP_FEATURE_BINS)) if want else None
+        capi.check(self._lib.icp_batch_compute_features(self._h, km.ctypes.data_as(pi), kq.ctypes.data_as(pi), nm.ctypes.data_as(pd), nq.ctypes.data_as(pd),
+                                                        om.ctypes.data_as(pd) if want else None, oq.ctypes.data_as(pd) if want else None),
+                   "icp_batch_compute_features")
+        if want:
+            return self._cut33(om, self._moff), self._cut33(oq, self._qoff)
+
+    def get_features(self):
+        """(moving, model): per pair the (points, 33) float64 descriptors the batch holds (icp_batch_get_features)"""
+        pd = C.POINTER(C.c_double)
+        om = np.empty((int(self._moff[-1]), capi.ICP_FEATURE_BINS))
+        oq = np.empty((int(self._qoff[-1]), capi.ICP_FEATURE_BINS))
+        capi.check(self._lib.icp_batch_get_features(self._h, om.ctypes.data_as(pd), oq.ctypes.data_as(pd)), "icp_batch_get_features")
+        return self._cut33(om, self._moff), self._cut33(oq, self._qoff)
+
+    def diag_set_features(self, moving, model):
+        """descriptors of the caller's own, per side one (points, 33) float64 array per pair (icp_diag_batch_set_features): for tests"""
+        pd = C.POINTER(C.c_double)
+        a = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1, capi.ICP_FEATURE_BINS) for x in moving]))
+        q = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1, capi.ICP_FEATURE_BINS) for x in model]))
+        if a.shape[0] != int(self._moff[-1]) or q.shape[0] != int(self._qoff[-1]):
+            raise ValueError("one (points, 33) array of descriptors per cloud")
+        capi.check(self._lib.icp_diag_batch_set_features(self._h, a.ctypes.data_as(pd), q.ctypes.data_as(pd)), "icp_diag_batch_set_features")
+
+    def match_features(self, mutual=True):
+        """the nearest descriptor of the other cloud for every point, both ways (icp_batch_match_features): (fwd, rev, kept), per
+        pair fwd (n,) int32 -- the model point whose descriptor is nearest to moving point i's, the lowest index on ties -- rev
+        (m,) int32 the same from the models, kept (n,) uint8 = not mutual or rev[fwd[i]] == i.  A pair's correspondence list, what
+        score_transforms and ransac work on, is its kept i in ascending order, each with fwd[i]."""
+        p32 = C.POINTER(C.c_int32)
+        fwd = np.zeros(int(self._moff[-1]), dtype=np.int32)
+        rev = np.zeros(int(self._qoff[-1]), dtype=np.int32)
+        kept = np.zeros(int(self._moff[-1]), dtype=np.uint8)
+        capi.check(self._lib.icp_batch_match_features(self._h, 1 if mutual else 0, fwd.ctypes.data_as(p32), rev.ctypes.data_as(p32),
+                                                      kept.ctypes.data_as(C.POINTER(C.c_uint8))), "icp_batch_match_features")
+        return self._split(fwd), [rev[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)], self._split(kept)
+
+    def score_transforms(self, T, max_distance):
+        """(count, per_pair) int32: how many correspondences of every pair lie within max_distance (a scalar, one value per pair,
+        or None: no limit) of their match once the pair's moving cloud as uploaded is moved by each of its candidate poses
+        (icp_batch_score_transforms).  T: (count, per_pair, 4, 4), or (count, 4, 4) for one candidate per pair."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if T.ndim == 3:
+            T = T[:, None]
+        if T.ndim != 4 or T.shape[0] != self.count or T.shape[2:] != (4, 4) or T.shape[1] < 1:
+            raise ValueError("candidate transforms must be (count, per_pair, 4, 4)")
+        T = np.ascontiguousarray(T)
+        md = None if max_distance is None else self._per_pair(max_distance, "maximum distance")
+        pd = C.POINTER(C.c_double)
+        out = np.zeros((self.count, T.shape[1]), dtype=np.int32)
+        capi.check(self._lib.icp_batch_score_transforms(self._h, int(T.shape[1]), T.ctypes.data_as(pd), md.ctypes.data_as(pd) if md is not None else None,
+                                                        out.ctypes.data_as(C.POINTER(C.c_int32))), "icp_batch_score_transforms")
+        return out
+
+    def ransac(self, hypotheses, max_distance, edge_similarity=0.9, seed=0):
+        """a start pose for every pair from its correspondence list (icp_batch_ransac): hypotheses three-match samples per pair,
+        drawn by a counter-based generator from seed (a scalar for every pair, or one per pair), screened by the edge-length
+        check, solved on the host and scored on the device; the best is refitted on its inliers.  Per pair a dict of T (4, 4: maps
+        the moving cloud as uploaded into the model's frame -- what set_initial_transforms takes), inliers, correspondences and
+        status (ICP_OK, or ICP_ERR_EMPTY where fewer than three correspondences or no valid hypothesis exist: T is then the identity)."""
+        sd = np.asarray(seed)
+        sd = np.full(self.count, int(sd), dtype=np.uint64) if sd.ndim == 0 else np.ascontiguousarray(sd, dtype=np.uint64)
+        if sd.shape != (self.count,):
+            raise ValueError("one seed per pair (or a scalar)")
+        prm = capi.icp_ransac_params(int(hypotheses), float(max_distance), float(edge_similarity))
+        T = np.zeros((self.count, 4, 4))
+        inl, cor = np.zeros(self.count, dtype=np.int32), np.zeros(self.count, dtype=np.int32)
+        st = np.zeros(self.count, dtype=np.intc)
+        p32 = C.POINTER(C.c_int32)
+        capi.check(self._lib.icp_batch_ransac(self._h, C.byref(prm), sd.ctypes.data_as(C.POINTER(C.c_uint64)), T.ctypes.data_as(C.POINTER(C.c_double)),
+                                              inl.ctypes.data_as(p32), cor.ctypes.data_as(p32), st.ctypes.data_as(C.POINTER(C.c_int))), "icp_batch_ransac")
+        self._ransac_hyp = int(hypotheses)
+        return [dict(T=T[b].copy(), inliers=int(inl[b]), correspondences=int(cor[b]), status=int(st[b])) for b in range(self.count)]
+
+    def diag_ransac(self, b):
+        """the last ransac run's hypotheses of pair b (icp_diag_batch_ransac): dict of triples (H, 3) int32 -- positions in the
+        pair's correspondence list, -1 for an empty slot -- valid (H,) uint8, T (H, 4, 4) and counts (H,) int32 (-1: invalid)"""
+        H = int(getattr(self, "_ransac_hyp", 0))
+        tr, va = np.zeros((max(H, 1), 3), dtype=np.int32), np.zeros(max(H, 1), dtype=np.uint8)
+        T, cn = np.zeros((max(H, 1), 4, 4)), np.zeros(max(H, 1), dtype=np.int32)
+        p32 = C.POINTER(C.c_int32)
+        capi.check(self._lib.icp_diag_batch_ransac(self._h, int(b), tr.ctypes.data_as(p32), va.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   T.ctypes.data_as(C.POINTER(C.c_double)), cn.ctypes.data_as(p32)), "icp_diag_batch_ransac")
+        return dict(triples=tr[:H], valid=va[:H], T=T[:H], counts=cn[:H])
+
     def set_max_distance(self, v):
         """the maximum correspondence distance: a scalar for every pair, one value per pair (inf: that pair is not gated), or
         None (no gate).  A match farther away than that enters no sum of its pass.  Discards a loop under way."""
@@ -1063,6 +1210,29 @@ def covariances_from_normals(normals, eps=1e-3):
     s = 1.0 - float(eps)
     x, y, z = N[:, 0], N[:, 1], N[:, 2]
     return np.ascontiguousarray(np.stack([1.0 - s * x * x, -s * x * y, -s * x * z, 1.0 - s * y * y, -s * y * z, 1.0 - s * z * z], axis=1))
+
+
+def oriented_normals(points, covariances, viewpoint):
+    """(n, 3) float64 unit normals from per-point covariances ((n, 6): xx, xy, xz, yy, yz, zz, as Batch.estimate_covariances
+    returns them): the eigenvector of the smallest eigenvalue, flipped to face viewpoint (3,) -- what Batch.compute_features takes"""
+    C6 = np.ascontiguousarray(covariances, dtype=np.float64)
+    P = np.asarray(points, dtype=np.float64)
+    if C6.ndim != 2 or C6.shape[1] != 6 or P.shape != (C6.shape[0], 3):
+        raise ValueError("points must be (n, 3) and covariances (n, 6)")
+    _, Z = np.linalg.eigh(C6[:, np.array([[0, 1, 2], [1, 3, 4], [2, 4, 5]])])
+    N = Z[:, :, 0]
+    flip = (N * (np.asarray(viewpoint, dtype=np.float64)[None, :] - P)).sum(1) < 0
+    return np.ascontiguousarray(np.where(flip[:, None], -N, N))
+
+
+def solve_rigid(mom):
+    """icp_solve_rigid: the point-to-point solve with the determinant fix -- R is always a rotation"""
+    lib = capi.load()
+    mom = np.ascontiguousarray(mom, dtype=np.float64)
+    R, t = np.zeros(9), np.zeros(3)
+    pd = C.POINTER(C.c_double)
+    capi.check(lib.icp_solve_rigid(mom.ctypes.data_as(pd), R.ctypes.data_as(pd), t.ctypes.data_as(pd)), "icp_solve_rigid")
+    return R.reshape(3, 3), t
 
 
 def solve_point_to_point(mom):

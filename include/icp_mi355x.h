@@ -560,6 +560,79 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *         py), j1 = (pz, 0, -px), j2 = (-py, px, 0), j3, j4, j5 the unit vectors; u_a = M j_a.  Slot C(a, c) += j_a . u_c for
  *         a <= c; slot B(a) -= u_a . e; ICP_MOM_CNT = 1.  Every dot product is (x*x' + y*y') + z*z'.  With M = n n^T these are
  *         the plane pass's statements.  A pair's bits depend on that pair and its options alone.
+ *   - global registration (icp_batch_compute_features, icp_batch_match_features, icp_batch_score_transforms, icp_batch_ransac):
+ *     a start pose for pairs in unknown relative pose -- describe every point, match the descriptors, RANSAC over the matches; the
+ *     pose that comes out goes straight into icp_batch_set_initial_transforms.  One launch per stage for every pair of the batch;
+ *     every rule below is restated in numpy, bit for bit (tests/batch_feature_ref.py); a pair's bits depend on that pair alone.
+ *       descriptors (icp_batch_compute_features): a 33-bin FPFH (Rusu et al., ICRA 2009) per point, both clouds of every pair.
+ *         k_moving and k_model hold count ints each, every k within [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]; a cloud of
+ *         fewer than k + 1 points is ICP_ERR_INVALID, the message names the pair and the side.  moving_normals and model_normals
+ *         hold three doubles per point, laid out as the clouds -- always double, whatever the batch's precision; both sides are
+ *         required; a NaN or an infinite value is ICP_ERR_INVALID.  Unit length and a consistent orientation of the normals are
+ *         the caller's duty.  The batch does not keep the normals.  A descriptor is ICP_FEATURE_BINS doubles per point; the
+ *         outputs are optional, the batch keeps the descriptors on the device and icp_batch_get_features reads them back
+ *         (ICP_ERR_STATE where a side that is asked for holds none).  Source: the clouds as uploaded or as made by
+ *         icp_batch_downsample / icp_batch_remove_outliers, P0 and Q -- never the moved cloud.  The loop does not notice: the call
+ *         neither discards nor advances it.  A pending pass on the context: ICP_ERR_STATE.  A null batch: ICP_ERR_INVALID.  A
+ *         refused call leaves the batch as it was.  New descriptors discard the matches of icp_batch_match_features.
+ *         Every operation below is one IEEE double operation, nothing is fused, and the only functions used are
+ *         + - * / sqrt fabs floor.
+ *           neighbourhood: the covariance rule's.  d2(i, j) is the matching's squared distance in the batch's precision F; tau_i is
+ *             the k-th smallest over j != i by index; the neighbourhood of i is every j != i with d2(i, j) <= tau_i: all ties are in.
+ *           pair term of (i, j), from the widened coordinates: d = p_j - p_i, r2 = (dx*dx + dy*dy) + dz*dz; the pair is skipped if
+ *             r2 == 0 or r2 is not finite.  r = sqrt(r2); a1 = dot(n_i, d) / r; a2 = dot(n_j, d) / r.  If fabs(a1) < fabs(a2) the
+ *             roles swap: n1 = n_j, n2 = n_i, d = -d, f3 = -a2; otherwise n1 = n_i, n2 = n_j, f3 = a1.  v = d x n1, each component
+ *             a*b - c*d; vv = dot(v, v); the pair is skipped if vv == 0 or vv is not finite.  v = v / sqrt(vv), three divisions.
+ *             w = n1 x v; f2 = dot(v, n2); x = dot(n1, n2); y = dot(w, n2).  Every dot is (x*x' + y*y') + z*z'.
+ *           the third angle is binned in the diamond angle, not in atan2 -- a deliberate deviation from PCL: s = fabs(x) + fabs(y);
+ *             if s == 0 then t = 0, otherwise q = y / s and t = q if x >= 0, t = 2 - q if y >= 0, else t = -2 - q.  t is monotone
+ *             in atan2(y, x) and lies in [-2, 2]; it needs no transcendental, so no bin decision hangs on a libm.
+ *           bin(val, lo, width) = clamp((int)floor((11.0 * (val - lo)) / width), 0, 10), the clamp taken before the conversion (a
+ *             NaN lands in bin 0).  t uses (-2, 4) into bins 0-10, f2 uses (-1, 2) into bins 11-21, f3 uses (-1, 2) into bins 22-32.
+ *           SPFH: the bins are integer counts, so no summation order exists; c is the number of pair terms not skipped;
+ *             S_i[b] = (100.0 * (double)cnt_b) / (double)c, or all zeros where c == 0.
+ *           FPFH: A[b] = 0.0; for the neighbourhood of i in ascending j, skipping d2(i, j) == 0: wgt = 1.0 / (double)d2(i, j);
+ *             A[b] += S_j[b] * wgt.  Per sub-histogram of 11 bins: s is the sequential sum from 0.0 in ascending b;
+ *             F_i[b] = (A[b] * 100.0) / s, or 0.0 where s is not > 0 or not finite.
+ *           a cloud's descriptors depend on that cloud, its k and its normals alone.
+ *         cost: two launches for all clouds of both sides (batch_spfh_kernel, batch_fpfh_kernel: one block per 64 points), no
+ *           atomics, one host wait.
+ *       matching (icp_batch_match_features): D(i, j) = the sum of (F_i[b] - G_j[b])^2 from 0.0 over b = 0..32 in ascending b, in
+ *         double, each operation rounded on its own; F the moving cloud's descriptors, G the model's.  fwd[i] is the lowest j that
+ *         minimises D, rev[j] the lowest i (a NaN never wins; where no D is below +INFINITY the answer is 0).
+ *         kept[i] = !mutual || rev[fwd[i]] == i.  The batch keeps fwd, rev and kept on the device; a pair's correspondence list
+ *         is its kept i in ascending order, paired with fwd[i]; C_p is its length.  fwd_out and kept_out are concatenated as the
+ *         moving clouds, rev_out as the models; each may be NULL.  It needs descriptors on both sides (ICP_ERR_STATE otherwise).
+ *         Two launches of batch_feature_match (the sides swapped), n x m x 33 differences per pair, and one host wait.  The loop
+ *         does not notice.
+ *       scoring (icp_batch_score_transforms): per_pair in [1, 65536] candidate 4 x 4 matrices per pair (count x per_pair x 16 doubles,
+ *         row-major, bottom row 0 0 0 1, validated as icp_batch_set_initial_transforms validates).  Each is rounded once to F and
+ *         applied to P0 in the front end's arithmetic, ((r0 x + r1 y) + r2 z) + t, every operation rounded separately in F;
+ *         d = the matching's squared distance in F against Q[fwd[i]]; a correspondence counts iff d <= thr, thr = (F)(max_dist *
+ *         max_dist) by the gate's rule (max_dist: count doubles, each > 0 or +INFINITY; NULL: +INFINITY for every pair); a moved
+ *         point that is not finite is a miss.  count_out holds count x per_pair int32; integers have no summation order, so the
+ *         result is exact.  ICP_ERR_STATE without matches.  One launch of batch_score_transforms, one host wait.  The loop does
+ *         not notice.
+ *       RANSAC (icp_batch_ransac): hypotheses in [1, 65536]; max_distance finite and > 0; edge_similarity e in [0, 1), 0 switches
+ *         the edge check off; one seed per pair: a pair's result depends on that pair, its seed and the parameters alone.
+ *           draws: mix(x) is the splitmix64 finaliser on z = x + 0x9E3779B97F4A7C15: z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9,
+ *             z = (z ^ (z >> 27)) * 0x94D049BB133111EB, mix = z ^ (z >> 31), all modulo 2^64.
+ *             draw(h, r) = mix(mix(mix(seed_p) + h) + r) % C_p; the modulo bias is accepted.
+ *           hypothesis h: slots 0, 1 and 2 take the draws r = 0, 1, 2, ...; a draw equal to an earlier slot is skipped; at most 16
+ *             draws are used; fewer than three distinct picks make the hypothesis invalid.  A pick is a position in the
+ *             correspondence list.
+ *           edge check: for the three point pairs (0, 1), (1, 2) and (0, 2), la and lb are sqrt of the double squared distance
+ *             (dx*dx + dy*dy) + dz*dz between the widened moving points, and between the model points; the hypothesis is valid
+ *             iff la >= e*lb && lb >= e*la for all three.
+ *           solve: the 32-double moment vector of the three matches, added in slot order, goes through icp_solve_rigid (below).
+ *           score: every valid hypothesis through batch_score_transforms, a fixed number of hypotheses per launch.  Winner: the largest
+ *             count, the lowest h among equals.  Refit: the moments over the winner's inliers in ascending list order,
+ *             icp_solve_rigid, one more scoring launch; the refit is returned if its count is at least the winner's, else the winner.
+ *           per pair: status ICP_ERR_EMPTY where C_p < 3 or no hypothesis is valid -- then T is the identity and inliers is 0 --
+ *             otherwise ICP_OK.  T16_out (16 doubles per pair) maps P0 into the model's frame; inliers_out and
+ *             correspondences_out (C_p) hold one int32 per pair, status_out one int; every output may be NULL.
+ *         ICP_ERR_STATE without matches; ICP_ERR_INVALID for a null batch, null parameters, null seeds or a value out of range.
+ *         The loop does not notice.
      Not gated, not trimmed and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the
  *     multi-GPU sums -- a single pair that needs any of them is a batch of one; nor do they weigh matches by a robust kernel.  Trimming is the only rejection by rank: there
  *     is no other percentile rejection (none by a multiple of the median or of the standard deviation of the distances). */
@@ -650,6 +723,20 @@ int icp_batch_estimate_covariances(icp_batch* b, const int* k_moving, const int*
                                    double* moving_cov_out, double* model_cov_out);
 /* the covariances the batch holds; either pointer may be NULL; ICP_ERR_STATE where a side that is asked for holds none */
 int icp_batch_get_covariances(icp_batch* b, double* moving_cov_out, double* model_cov_out);
+/* global registration (above).  k_*: count ints each; *_normals: 3 doubles per point, laid out as the clouds; the outputs
+ * (ICP_FEATURE_BINS doubles per point) may be NULL */
+#define ICP_FEATURE_BINS 33
+int icp_batch_compute_features(icp_batch* b, const int* k_moving, const int* k_model, const double* moving_normals,
+                               const double* model_normals, double* moving_feat_out, double* model_feat_out);
+/* the descriptors the batch holds; either pointer may be NULL; ICP_ERR_STATE where a side that is asked for holds none */
+int icp_batch_get_features(icp_batch* b, double* moving_feat_out, double* model_feat_out);
+/* fwd_out / kept_out: 1 per moving point; rev_out: 1 per model point; each may be NULL */
+int icp_batch_match_features(icp_batch* b, int mutual, int32_t* fwd_out, int32_t* rev_out, uint8_t* kept_out);
+/* T16: count x per_pair x 16 doubles; max_dist: count doubles or NULL; count_out: count x per_pair int32 */
+int icp_batch_score_transforms(icp_batch* b, int per_pair, const double* T16, const double* max_dist, int32_t* count_out);
+typedef struct icp_ransac_params { int hypotheses; double max_distance; double edge_similarity; } icp_ransac_params;
+int icp_batch_ransac(icp_batch* b, const icp_ransac_params* prm, const uint64_t* seed /*count*/,
+                     double* T16_out, int32_t* inliers_out, int32_t* correspondences_out, int* status_out);
 /* one call: create + begin + run to the end + results, then destroy.  Every output pointer may be NULL; per pair:
  * T16_out 16, iterations_out / passes_out / status_out 1, err_out max_iter+1 doubles; idx_out and moved_out (3 values per
  * point, precision of the run) concatenated as the moving clouds.  A failed pair is reported in status_out, not in the
@@ -691,6 +778,10 @@ void icp_lcomm_destroy(icp_lcomm* comm);
  * (src/ICP_point_to_point.cu:356-397) / dgemm + LAPACKE_dgesvd (src/ICP_CPU.c:239-248).
  * R = U*Vt with NO reflection fix (the reference has none).  Returns ICP_OK. */
 int icp_solve_point_to_point(const double* mom /*ICP_NMOM*/, double* R9, double* t3);
+/* icp_solve_point_to_point with the determinant fix: the last column of U is flipped when det(U Vt) < 0, so R is always a
+ * rotation (det = +1) -- what a minimal sample needs: three points give a rank-2 cross-covariance, and without the fix about
+ * half the hypotheses of icp_batch_ransac would come out as reflections.  ICP_ERR_INVALID where ICP_MOM_CNT is not > 0. */
+int icp_solve_rigid(const double* mom /*ICP_NMOM*/, double* R9, double* t3);
 /* 6x6 normal equations: replaces cusolverDnSpotrf/Spotrs UPPER (src/ICP_point_to_plane.cu:576-581)
  * and LAPACKE_ssysv (CPU_ICP_point_to-plane.cpp:371); x = (alpha,beta,gamma,tx,ty,tz), then the
  * full (non-linearised) R = Rz(gamma) Ry(beta) Rx(alpha) (src/ICP_point_to_plane.cu:585-593). */

@@ -112,6 +112,17 @@ int icp_diag_batch_eval_moments(icp_batch* b, int pair, double* out32);
  * a matching pass. */
 int icp_diag_batch_rotation(icp_batch* b, int pair, double* R9);
 
+/* descriptors of the caller's own in place of icp_batch_compute_features' (ICP_FEATURE_BINS doubles per point, both sides, laid
+ * out as icp_batch_get_features returns them; nothing is checked): what lets a test match clouds too small to describe, or
+ * descriptors with planted ties.  Discards the matches. */
+int icp_diag_batch_set_features(icp_batch* b, const double* moving_feat, const double* model_feat);
+/* the last icp_batch_ransac run's hypotheses of pair `pair`, H = that run's prm->hypotheses of each: triples 3 x H int32 (the
+ * positions in the pair's correspondence list that slots 0, 1, 2 took; -1 for a slot left empty), valid H bytes (three distinct
+ * picks, the edge check passed and the solve succeeded), T16 16 x H doubles (the pose icp_solve_rigid gave, in double, before it
+ * is rounded to the batch's precision for scoring; the identity for an invalid hypothesis), counts H int32 (the inliers
+ * batch_score_transforms counted; -1 for an invalid hypothesis).  Host copies: nothing is downloaded.  Every output may be NULL.
+ * ICP_ERR_STATE before the first run. */
+int icp_diag_batch_ransac(icp_batch* b, int pair, int32_t* triples, uint8_t* valid, double* T16, int32_t* counts);
 #ifdef __cplusplus
 }
 #endif
