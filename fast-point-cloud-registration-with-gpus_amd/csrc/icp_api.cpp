@@ -449,7 +449,11 @@ int icp_nn_match_bench_ex(icp_ctx* c, int reps, int seeded, float* total_ms)
     for (int r = 0; r < reps; ++r)
         HIP_TRY(icp::launch_nn(c->plan, c->P.p, c->Q.p, c->part_d.p, (int32_t*)c->part_idx.p, nullptr, &cull, nullptr, c->stream));
     HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    // (behind the timed span) the last launch's partial results become the context's correspondences, as icp_nn_match_resident's
+    // do: icp_get_indices after a seeded launch answers for THAT launch, not for the pass that seeded it
+    HIP_TRY(icp::launch_merge(c->plan, c->part_d.p, (const int32_t*)c->part_idx.p, (int32_t*)c->idx[c->cur].p, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    c->idx_valid = true;
     HIP_TRY(hipEventElapsedTime(total_ms, c->ev0, c->ev1));
     return ICP_OK;
 }

@@ -434,7 +434,7 @@ __global__ __launch_bounds__(NN_BLOCK, (T == 2 ? 8 : 4)) void nn_match_f32_v2(co
             const unsigned long long key = __hip_atomic_load(&tail.keys[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             tail.keys[i] = ~0ull;  // ready for the next launch (nobody touches this row again in this one)
             int j = (int)(unsigned int)(key & 0xffffffffull);
-            j = ((unsigned)j < (unsigned)fuse.m) ? j : fuse.m - 1;  // unreachable clamp, keeps idx in range by construction
+            j = ((unsigned)j < (unsigned)fuse.m) ? j : 0;   // no wave of any segment lowered +inf (every squared distance overflowed): point 0, see merge_kernel
             if (i < fuse.n) {
                 tail.idx_out[i] = j;
                 const double ppx = (double)(t ? px[0].y : px[0].x), ppy = (double)(t ? py[0].y : py[0].x),
@@ -490,8 +490,10 @@ __global__ __launch_bounds__(NN_BLOCK, (T == 2 ? 8 : 4)) void nn_match_f32_v2(co
     }
 }
 
-// lexicographic (d, j) minimum over the S segment partials: segments are ascending model ranges,
-// so the first strict minimum in segment order is the lowest index.
+// lexicographic (d, j) minimum over the S segment partials.  The segments of the model's own order are ascending index ranges, and
+// there the first strict minimum in segment order is the lowest index already; the segments of a sorted view are ranges of the
+// curve, a tie between two of them can have its lower index in the later one, and the index decides.  (A segment without a
+// candidate holds (+inf, 0x7fffffff) or, from a sparse kernel, (+inf, 0): neither displaces anything finite.)
 template <typename F>
 __device__ __forceinline__ int merge_partials(const F* __restrict__ part_d, const int32_t* __restrict__ part_idx,
                                               int S, int n_pad, int i)
@@ -509,7 +511,7 @@ __device__ __forceinline__ int merge_partials(const F* __restrict__ part_d, cons
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-            if (d[u] < best) { best = d[u]; bi = j[u]; }
+            if (d[u] < best || (d[u] == best && j[u] < bi)) { best = d[u]; bi = j[u]; }
     }
     if (s < S) {  // tail: same 16 loads in flight, out-of-range slots replaced by +inf
         F d[8];
@@ -522,7 +524,7 @@ __device__ __forceinline__ int merge_partials(const F* __restrict__ part_d, cons
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-            if (s + u < S && d[u] < best) { best = d[u]; bi = j[u]; }
+            if (s + u < S && (d[u] < best || (d[u] == best && j[u] < bi))) { best = d[u]; bi = j[u]; }
     }
     return bi;
 }

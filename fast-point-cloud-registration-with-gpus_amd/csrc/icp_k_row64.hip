@@ -479,6 +479,20 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 1) void nn_match_row64(const
         atomicMin(&mkey[lane], key);
         mq[0][w][lane] = bq[0]; mq[1][w][lane] = bq[1]; mq[2][w][lane] = bq[2];
     }
+    if (w == 0) {
+        // A real point whose bound is still +inf here had no finite seed, no finite sample and no finite distance in any chunk
+        // this wave scanned (finite coordinates around 1e20 do that): the ascending scan of src/ICP_CPU.c:220-234 keeps its
+        // first point then, so wave 0 folds in model point 0 at +inf, with its coordinates.  Any finite candidate of another
+        // wave is a smaller key, and so is nothing else at +inf (a sorted view can publish one: `c0 <= best`, a higher index).
+        const bool none0 = real && best == inf_<float>();
+        if (__builtin_amdgcn_ballot_w64(none0) != 0ull) {
+            if (none0) {
+                const float* Qg = fuse.Q_gather;
+                atomicMin(&mkey[lane], (unsigned long long)0x7f800000u << 32);
+                mq[0][0][lane] = Qg[0]; mq[1][0][lane] = Qg[(size_t)m_pad]; mq[2][0][lane] = Qg[2 * (size_t)m_pad];
+            }
+        }
+    }
     ICP_PHASE(4)
     __syncthreads();
     ICP_PHASE(5)
@@ -487,7 +501,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 1) void nn_match_row64(const
     } else {
         // wave 0 finishes the row
         const unsigned long long key = mkey[lane];
-        const bool none = key == ~0ull;  // no wave found anything below the bound (padding lanes)
+        const bool none = key == ~0ull;  // no key at all: a padding lane (a real point without a finite distance carries point 0's)
         const unsigned int lo = (unsigned int)key;
         const float fb = none ? inf_<float>() : __uint_as_float((unsigned int)(key >> 32));
         int fj = none ? 0x7fffffff : (int)(lo >> 4);
@@ -498,7 +512,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 1) void nn_match_row64(const
             part_idx[pi] = fj;
             return;
         } else {
-            fj = ((unsigned)fj < (unsigned)fuse.m) ? fj : fuse.m - 1;  // unreachable clamp
+            fj = ((unsigned)fj < (unsigned)fuse.m) ? fj : 0;   // (out of range: a padding lane, whose index nobody reads)
             NNTail tl = tail;
             tl.tag = row_tag;
             tl.tag_lo = row_tag_lo;

@@ -947,6 +947,20 @@ __global__ __launch_bounds__(NWS * 64, NWS == 16 ? 1 : 4) void nn_match_sparse(c
             mq[0][w][lane + t * 64] = bq[t][0]; mq[1][w][lane + t * 64] = bq[t][1]; mq[2][w][lane + t * 64] = bq[t][2];
         }
     }
+    if (w == 0) {
+        // A real point whose bound is still +inf here had no finite seed, no finite sample and no finite distance in any chunk
+        // this wave scanned (finite coordinates around 1e20 do that): the ascending scan of src/ICP_CPU.c:220-234 keeps its
+        // first point then, so wave 0 folds in model point 0 at +inf, with its coordinates -- in every block that searches for
+        // the row (segments, parts).  Any finite candidate is a smaller key, and so is nothing else at +inf (a sorted view can
+        // publish one: `c0 <= best`, a higher index).
+        const bool none0 = real[0] && best[0] == inf_<float>(), none1 = real[1] && best[1] == inf_<float>();
+        if (__builtin_amdgcn_ballot_w64(none0 | none1) != 0ull) {
+            const float* Qg = fuse.Q_gather;
+            const float q0x = Qg[0], q0y = Qg[(size_t)m_pad], q0z = Qg[2 * (size_t)m_pad];
+            if (none0) { atomicMin(&mkey[lane], (unsigned long long)0x7f800000u << 32); mq[0][0][lane] = q0x; mq[1][0][lane] = q0y; mq[2][0][lane] = q0z; }
+            if (none1) { atomicMin(&mkey[lane + 64], (unsigned long long)0x7f800000u << 32); mq[0][0][lane + 64] = q0x; mq[1][0][lane + 64] = q0y; mq[2][0][lane + 64] = q0z; }
+        }
+    }
     ICP_PHASE(4)
     __syncthreads();
     ICP_PHASE(5)
@@ -959,7 +973,7 @@ __global__ __launch_bounds__(NWS * 64, NWS == 16 ? 1 : 4) void nn_match_sparse(c
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const unsigned long long key = mkey[lane + t * 64];
-        const bool none = key == ~0ull;  // no wave found anything below the bound (padding lanes)
+        const bool none = key == ~0ull;  // no key at all: a padding lane (a real point without a finite distance carries point 0's)
         const unsigned int lo = (unsigned int)key;
         fb[t] = none ? inf_<float>() : __uint_as_float((unsigned int)(key >> 32));
         fj[t] = none ? 0x7fffffff : (int)(lo >> 4);
@@ -1011,7 +1025,7 @@ __global__ __launch_bounds__(NWS * 64, NWS == 16 ? 1 : 4) void nn_match_sparse(c
         if constexpr (!HIER) { if (SP_SHARED && fuse.resident && lane == 0) role[5] = closer ? 0 : 1; }
         if (closer) {
 #pragma unroll
-        for (int t = 0; t < 2; ++t) fj[t] = ((unsigned)fj[t] < (unsigned)fuse.m) ? fj[t] : fuse.m - 1;  // unreachable clamp
+        for (int t = 0; t < 2; ++t) fj[t] = ((unsigned)fj[t] < (unsigned)fuse.m) ? fj[t] : 0;   // (out of range: a padding lane, whose index nobody reads)
         bool gather_in_tail = parts > 1;
         if constexpr (!HIER) {
             if (parts > 1 && fuse.resident && SP_SHARED) {

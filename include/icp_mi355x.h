@@ -13,7 +13,9 @@
  *     src/ICP_point_to_point.cu:139-152), float or double, HOST pointers unless a name says _dev.
  *   - correspondence semantics are those of the CPU path (src/ICP_CPU.c:227-232): squared
  *     distance (dx*dx + dy*dy) + dz*dz with every operation rounded separately (no FMA), the
- *     LOWEST model index wins ties, every idx[i] is always written.
+ *     LOWEST model index wins ties, every idx[i] is always written.  Finite coordinates can square to +inf (around 1e20 in
+ *     float, 1e160 in double): a point whose every distance overflowed matches model point 0 -- what an ascending scan with
+ *     a strict `<` keeps -- in both precisions, in every kernel, and the moment sums carry point 0's coordinates for it.
  *   - rotation matrices are row-major 3x3 (R maps moving -> model), transforms row-major 4x4.
  *   - non-finite input -- a DELIBERATE DEVIATION from the reference, listed in INTEGRATION.md under "entry points that change
  *     behaviour": a cloud (or normal set) with a NaN or an infinite coordinate is REFUSED -- icp_set_model, icp_set_moving,

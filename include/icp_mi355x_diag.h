@@ -17,7 +17,8 @@ extern "C" {
  * stream; total_ms / reps is the kernel's average launch duration (bench.py roofline leg) */
 int icp_nn_match_bench(icp_ctx* ctx, int reps, float* total_ms);
 /* same; seeded != 0 hands the kernel the most recent correspondences as its starting bound (what the ICP
- * loop does from its second pass on), seeded == 0 starts it cold (what icp_nn_match_* does) */
+ * loop does from its second pass on), seeded == 0 starts it cold (what icp_nn_match_* does).  Behind the timed span the last
+ * launch's results are merged: icp_get_indices then returns the correspondences of that launch */
 int icp_nn_match_bench_ex(icp_ctx* ctx, int reps, int seeded, float* total_ms);
 /* The reference's own kernel-timing method (src/CUDA/Matching_opt.cu:213-226: cudaEventRecord around every launch,
  * minimum of 10 after warm-up): `warmups` untimed launches, then `reps` launches with a hipEvent pair around each one;

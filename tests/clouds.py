@@ -113,9 +113,9 @@ FUZZ_SCALES = (1e-3, 1.0, 1e3)
 
 def fuzz_cloud(rng, n, kind, scale, dtype=np.float32, signed_zeros=False):
     """n points of one kind -- uniform / clustered with exact duplicates / integer lattice / line -- times scale.  float32 rounds
-    the float64 construction once; float64 keeps it as it is, mantissas full.  signed_zeros (float64 only): about half of the
-    exact zeros (lattice coordinates, a line's y and z) become -0.0 -- the same point to every comparison, other bits to a sort
-    by bit pattern.  The draws of the float32 form do not depend on the two options."""
+    the float64 construction once; float64 keeps it as it is, mantissas full.  signed_zeros: about half of the exact zeros
+    (lattice coordinates, a line's y and z) become -0.0 -- the same point to every comparison, other bits to a sort by bit
+    pattern; their draws come after all the others, so a cloud without them has the bytes it always had."""
     if kind == "uniform":
         X = rng.uniform(-1, 1, (n, 3))
     elif kind == "clustered":          # a few tight clusters with exact duplicates sprinkled in
@@ -129,12 +129,9 @@ def fuzz_cloud(rng, n, kind, scale, dtype=np.float32, signed_zeros=False):
         X = np.zeros((n, 3))
         X[:, 0] = rng.uniform(-1, 1, n)
     X = scale * X
-    if np.dtype(dtype) == np.float32:
-        assert not signed_zeros
-        return X.astype(np.float32)
     if signed_zeros:
         X[(X == 0.0) & (rng.random(X.shape) < 0.5)] = -0.0
-    return X
+    return X.astype(np.float32) if np.dtype(dtype) == np.float32 else X
 
 
 F64_FUZZ_SEEDS = {"1": 6401, "0": 6400}     # ICP_F64_SPARSE -> the seed of its cases
@@ -159,36 +156,39 @@ EIGHT_WAVE_N = 16448               # 257 rows of 64; padded to 17 408 points it 
 TIE_DIMS = (35, 35, 33)
 
 
-def straddling_tie_pair(n=700, replace=False, scale=1.0):
+def straddling_tie_pair(n=700, replace=False, scale=1.0, dtype=np.float64):
     """model: the 35 x 35 x 33 integer lattice (40 425 distinct points) in a fixed random order; cloud: n cell centres (+0.5) drawn
     by the same generator.  Every centre has 8 tied minima at d = 0.75, scattered over the model's indices: for four centres in
     five on both sides of point 32 768, where the first round ends.  scale 1e-170 / 1e160: every squared distance underflows to 0 /
-    overflows to +inf, and the first minimum of an ascending scan is point 0 for every centre."""
+    overflows to +inf, and the first minimum of an ascending scan is point 0 for every centre.  float32: the scaled float64
+    coordinates rounded once (F32_TIE_SCALES says what each scale does to the squared distances)."""
     rng = np.random.default_rng(6464)
     a, b, c = TIE_DIMS
     g = np.stack(np.meshgrid(np.arange(float(a)), np.arange(float(b)), np.arange(float(c)), indexing="ij"), -1).reshape(-1, 3)
     M = g[rng.permutation(g.shape[0])]
     cells = np.stack(np.meshgrid(np.arange(a - 1.0), np.arange(b - 1.0), np.arange(c - 1.0), indexing="ij"), -1).reshape(-1, 3) + 0.5
     P = cells[rng.choice(cells.shape[0], n, replace=replace)]
-    return np.ascontiguousarray(P * scale), np.ascontiguousarray(M * scale)
+    return np.ascontiguousarray((P * scale).astype(dtype, copy=False)), np.ascontiguousarray((M * scale).astype(dtype, copy=False))
 
 
 UNDERFLOW_SCALE, OVERFLOW_SCALE = 1e-170, 1e160
 
 
-def far_pair(n=700, m=40000):
+def far_pair(n=700, m=40000, dtype=np.float64):
     """model: m uniform float64 points in [-1, 1]^3; cloud: n picks of it shifted by (5, 5, 5) -- the bound a cold start gets from
-    any model point is wider than the model, so nearly every chunk of both rounds is a hit"""
+    any model point is wider than the model, so nearly every chunk of both rounds is a hit (float32: both rounded once)"""
     rng = np.random.default_rng(4000)
     M = rng.uniform(-1, 1, (m, 3))
-    return M[rng.integers(0, m, n)] + 5.0, M
+    return (M[rng.integers(0, m, n)] + 5.0).astype(dtype, copy=False), M.astype(dtype, copy=False)
 
 
-def twin_model(m=40000):
+def twin_model(m=40000, dtype=np.float64):
     """a model with exact twins, and a cloud that hits them: (P, M, want).  M is m uniform float64 points whose x or y is exactly 0
     for every fifth point (a -0.0 must not look nearer or farther than them either); groups of three model indices a < b < c hold one point -- b and c in a's chunk of 8, in other chunks of
     a's round, and (c, or b and c) in the other round --, the copies of a point with a zero coordinate with the zero's sign
-    flipped.  Every group is hit through its HIGHER members' coordinates (signed zeros included); want is the lowest member."""
+    flipped.  Every group is hit through its HIGHER members' coordinates (signed zeros included); want is the lowest member.
+    float32: the same model rounded once -- copies stay copies, zeros keep their signs, and tests/test_f32_clouds.py shows that no
+    two other points fell together."""
     rng = np.random.default_rng(2222)
     M = rng.uniform(-1, 1, (m, 3))
     M[::5, 0] = 0.0
@@ -228,4 +228,45 @@ def twin_model(m=40000):
         for j in (b, c):
             P.append(M[j].copy())
             want.append(a)
-    return np.array(P), M, np.array(want, dtype=np.int32)
+    return np.array(P).astype(dtype, copy=False), M.astype(dtype, copy=False), np.array(want, dtype=np.int32)
+
+
+# ---- float32 across its range (tests/test_gpu_f32_matching.py; conditions: tests/test_f32_clouds.py) ----------------------------
+# what a scale does to float32 squared distances, shown on the tie pair in tests/test_f32_clouds.py:
+#   1e-25        every squared distance is 0: the oracle answers point 0
+#   3e-22, 1e-20 every minimum is a non-zero subnormal (6.7e-44, 7.5e-41): a rounding is absolute there, all 8 ties survive
+#   1e19         nearly every squared distance is +inf, every minimum finite; the rounding of the coordinates thins the ties out
+#   1e20         every squared distance is +inf: the oracle answers point 0
+F32_ZERO_SCALE, F32_SUBNORMAL_SCALES, F32_PART_INF_SCALE, F32_INF_SCALE = 1e-25, (3e-22, 1e-20), 1e19, 1e20
+F32_TIE_SCALES = (1.0, 1e-20, 3e-22, 1e-25, 1e19, 1e20)
+F32_FUZZ_SCALES = (1e-25, 3e-22, 1e-20, 1e-3, 1.0, 1e3, 1e15, 1e19, 1e20)
+F32_FUZZ_CASES = 36
+F32_FUZZ_SEEDS = {"0": 3202, "1": 3201}     # ICP_SORT -> the seed of its cases (chosen in tests/test_f32_clouds.py)
+SUPER_BOX_POINTS = 32768                    # a level-3 box of the hierarchy: 64 x 64 chunks of 8 (and the m_pad border of the sample probe)
+
+
+def f32_matching_cases(seed, cases):
+    """the cases of the float32 matching fuzz, f64_matching_cases' in float32 over F32_FUZZ_SCALES: (n, m, kind of the cloud, kind of
+    the model, scale, P, Q), signed zeros in every second case"""
+    rng = np.random.default_rng(seed)
+    for case in range(cases):
+        n, m = int(rng.integers(1, 700)), int(rng.integers(1, 900))
+        kp, km = (str(k) for k in rng.choice(FUZZ_KINDS, 2))
+        scale = float(rng.choice(F32_FUZZ_SCALES))
+        sz = case % 2 == 1
+        yield n, m, kp, km, scale, fuzz_cloud(rng, n, kp, scale, np.float32, sz), fuzz_cloud(rng, m, km, scale, np.float32, sz)
+
+
+MIXED_OUTLIERS = (0, 63, 127, 128, 704)     # lanes 0 and 63 of a row of 64, both sides of the first row-of-128 border, the last point
+
+
+def mixed_overflow_pair(m=1000):
+    """float32.  model: m uniform points in [-1, 1]^3; cloud: 705 points -- noisy picks of the model, except the five at
+    MIXED_OUTLIERS, whose coordinates are about 2e19: every squared distance from them overflows to +inf (they match point 0),
+    while their neighbours in the same rows have finite minima"""
+    rng = np.random.default_rng(1919)
+    M = rng.uniform(-1, 1, (m, 3)).astype(np.float32)
+    P = (M[rng.integers(0, m, 705)] + (1e-2 * rng.standard_normal((705, 3))).astype(np.float32)).astype(np.float32)
+    for k, i in enumerate(MIXED_OUTLIERS):
+        P[i] = np.array([2e19, -2.5e19, 3e19], dtype=np.float32)[[k % 3, (k + 1) % 3, (k + 2) % 3]] * np.float32(1 + 0.125 * k)
+    return P, M
