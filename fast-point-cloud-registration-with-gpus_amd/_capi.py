@@ -23,6 +23,8 @@ ICP_ERR_NOMEM = -8
 ICP_F32, ICP_F64 = 0, 1
 ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1
 ICP_GENERALIZED = 2   # the generalized (plane-to-plane) metric of a batch that holds covariances
+ICP_COLORED = 3       # the colored metric of a batch that holds model normals, intensities and intensity gradients
+ICP_COLOR_LAMBDA_DEFAULT = 0.968
 ICP_COV_NONE, ICP_COV_FROBENIUS = 0, 1   # icp_batch_estimate_covariances: the regularisation
 ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS = 3, 32
 ICP_FEATURE_BINS = 33   # doubles per FPFH descriptor (icp_batch_compute_features)
@@ -133,6 +135,11 @@ SIGNATURES = {
     "icp_batch_set_covariances": (_i, [_vp, _pd, _pd]),
     "icp_batch_estimate_covariances": (_i, [_vp, _pi, _pi, _i, C.c_double, _pd, _pd]),
     "icp_batch_get_covariances": (_i, [_vp, _pd, _pd]),
+    "icp_batch_set_intensities": (_i, [_vp, _pd, _pd]),
+    "icp_batch_estimate_intensity_gradients": (_i, [_vp, _pi, _pd]),
+    "icp_batch_set_intensity_gradients": (_i, [_vp, _pd]),
+    "icp_batch_get_intensity_gradients": (_i, [_vp, _pd]),
+    "icp_batch_set_color_weight": (_i, [_vp, _pd]),
     "icp_batch_compute_features": (_i, [_vp, _pi, _pi, _pd, _pd, _pd, _pd]),
     "icp_batch_get_features": (_i, [_vp, _pd, _pd]),
     "icp_batch_match_features": (_i, [_vp, _i, _pi32, _pi32, C.POINTER(C.c_uint8)]),

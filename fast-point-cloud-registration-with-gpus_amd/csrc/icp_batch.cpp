@@ -49,7 +49,15 @@
 // on, is composed on the host as icp_batch_state composes T and travels with the step's control words (9 doubles per pair).
 // Three launches, up to five, one download.  The other metrics of such a batch run the steps they ran without covariances.
 //
+// A batch may also hold one intensity per point on both sides, one intensity gradient per model point and one weight per pair
+// (icp_batch_set_intensities, icp_batch_estimate_intensity_gradients: ONE launch of batch_intensity_gradient_kernel, icp_k_color.hip,
+// for all models -- the rule is stated in include/icp_mi355x.h and reproduced bit for bit in numpy).  icp_batch_begin then takes a
+// fourth metric, ICP_COLORED: the generalized metric's route with batch_color_moments in batch_gicp_moments' place -- the same
+// decision, then the geometric and the photometric terms of the 6 x 6 system into a plane pass's slots; every pair's HostLoop is
+// begun as a point-to-plane loop.  The other metrics of such a batch run the steps they ran without intensities.
+//
 //   batch kind             launches of a step
+//   colored metric         nn_match_batch<DEFER>, [nn_match_batch_rev,] [batch_trim_select,] batch_color_moments<MUTUAL?>, batch_finalize_kernel
 //   generalized metric     nn_match_batch<DEFER>, [nn_match_batch_rev,] [batch_trim_select,] batch_gicp_moments<MUTUAL?>, batch_finalize_kernel
 //   any robust pair        nn_match_batch<DEFER>, [nn_match_batch_rev,] [batch_trim_select,] batch_robust_moments<MUTUAL?>, batch_finalize_kernel
 //   any reciprocal pair    nn_match_batch<DEFER>, nn_match_batch_rev, [batch_trim_select,] batch_trim_moments<MUTUAL>, batch_finalize_kernel
@@ -147,6 +155,16 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     hipEvent_t cov_ev = nullptr;             // recorded behind the latest call's launch: the next call waits for it before it rewrites h_cov_args
     std::vector<double> rot;                 // count x 9: the rotation every pair's most recent matching pass of a generalized loop rotated its moving covariances by
     size_t rot_off = 0;                      // where those rotations sit in ctl and h_ctl, behind the modes (copied by a generalized step only)
+    DevBuf inten[2];                         // the colored metric: every point's intensity, moving clouds / models -- one plane of doubles, laid out as the clouds
+    bool have_int[2] = {false, false};       // that side holds intensities (icp_batch_set_intensities)
+    DevBuf grad;                             // every model point's intensity gradient: 3 planes of doubles, laid out as the models
+    bool have_grad = false;                  // the batch holds gradients (icp_batch_set_intensity_gradients, icp_batch_estimate_intensity_gradients); new model intensities or normals discard them
+    DevBuf grad_k;                           // icp_batch_estimate_intensity_gradients: every model's k of the latest call
+    int* h_grad_k = nullptr;                 // pinned: what that buffer is copied from (a call waits for nothing unless it wants an output)
+    hipEvent_t grad_ev = nullptr;            // recorded behind the latest call's launch: the next call waits for it before it rewrites h_grad_k
+    DevBuf color_w;                          // every pair's lambda (double), uploaded by icp_batch_set_color_weight or by the first colored begin
+    std::vector<double> lambda;              // the weights as given (empty: ICP_COLOR_LAMBDA_DEFAULT for every pair)
+    bool color_w_set = false;                // color_w holds what lambda says
     int metric = ICP_POINT_TO_POINT;         // of the loop under way
     void* h_ctl = nullptr;                   // pinned: R, t of every pair (12 values of the precision), then its mode (int)
     double* h_mom = nullptr;                 // pinned: count x ICP_NMOM
@@ -216,10 +234,12 @@ void reset_loop_state(icp_batch* b)
 void release(icp_batch* b)
 {
     for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag,
-                      &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->rob_kind, &b->rob_k, &b->rob_k2, &b->weights, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom, &b->cov[0], &b->cov[1], &b->cov_args,
+                      &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->rob_kind, &b->rob_k, &b->rob_k2, &b->weights, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom, &b->cov[0], &b->cov[1], &b->cov_args, &b->inten[0], &b->inten[1], &b->grad, &b->grad_k, &b->color_w,
                       &b->feat[0], &b->feat[1], &b->f_fwd, &b->f_rev, &b->f_kept, &b->f_ci, &b->f_cj, &b->f_cn, &b->s_cand, &b->s_valid, &b->s_thr, &b->s_counts})
         d->release();
     if (b->cov_ev) (void)hipEventDestroy(b->cov_ev);
+    if (b->grad_ev) (void)hipEventDestroy(b->grad_ev);
+    if (b->h_grad_k) (void)hipHostFree(b->h_grad_k);
     if (b->h_cov_args) (void)hipHostFree(b->h_cov_args);
     if (b->h_eval) (void)hipHostFree(b->h_eval);
     if (b->h_ctl) (void)hipHostFree(b->h_ctl);
@@ -744,7 +764,7 @@ int step(icp_batch* b)
     a.P_soa = b->P.p;
     a.p_plane = b->p_plane;
     a.Q_soa = b->Q.p;
-    a.N_soa = b->metric == ICP_POINT_TO_PLANE ? b->N.p : nullptr;
+    a.N_soa = b->metric == ICP_POINT_TO_PLANE || b->metric == ICP_COLORED ? b->N.p : nullptr;
     a.q_plane = b->q_plane;
     a.idx_prev = (const int32_t*)b->idx[cur ^ 1].p;
     a.idx_cur = (int32_t*)b->idx[cur].p;
@@ -767,6 +787,12 @@ int step(icp_batch* b)
         a.cov_q = (const double*)b->cov[1].p;
         a.rot = reinterpret_cast<const double*>(static_cast<const char*>(b->ctl.p) + b->rot_off);
     }
+    if (b->metric == ICP_COLORED) {
+        a.int_p = (const double*)b->inten[0].p;
+        a.int_q = (const double*)b->inten[1].p;
+        a.grad_q = (const double*)b->grad.p;
+        a.color_w = (const double*)b->color_w.p;
+    }
     HIP_TRY(icp::launch_batch_pass(a, c->stream));
     HIP_TRY(hipMemcpyAsync(b->h_mom, b->mom.p, (size_t)b->count * ICP_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -781,6 +807,18 @@ int step(icp_batch* b)
             b->H[p].done = true;
         }
     }
+    return ICP_OK;
+}
+
+// every pair's lambda as the batch holds it (ICP_COLOR_LAMBDA_DEFAULT where none was given) -> color_w
+int upload_color_weights(icp_batch* b)
+{
+    std::vector<double> w = b->lambda;
+    if (w.empty()) w.assign((size_t)b->count, ICP_COLOR_LAMBDA_DEFAULT);
+    HIP_TRY(b->color_w.ensure(w.size() * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(b->color_w.p, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
+    b->color_w_set = true;
     return ICP_OK;
 }
 
@@ -952,7 +990,8 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
 {
     if (int rc = ready(b)) return rc;
     if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
-    if (prm->metric != ICP_POINT_TO_POINT && prm->metric != ICP_POINT_TO_PLANE && prm->metric != ICP_GENERALIZED) return fail(ICP_ERR_INVALID, "unknown metric");
+    if (prm->metric != ICP_POINT_TO_POINT && prm->metric != ICP_POINT_TO_PLANE && prm->metric != ICP_GENERALIZED && prm->metric != ICP_COLORED)
+        return fail(ICP_ERR_INVALID, "unknown metric");
     if (prm->metric == ICP_POINT_TO_PLANE && !b->have_normals)
         return fail(ICP_ERR_INVALID, "a point-to-plane batch needs the model normals: icp_batch_set_model_normals or icp_batch_estimate_normals first");
     if (prm->metric == ICP_GENERALIZED) {
@@ -962,12 +1001,26 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
         if (b->robust) return fail(ICP_ERR_INVALID, "the generalized metric takes no robust kernels (icp_batch_set_robust(NULL) first)");
         HIP_TRY(b->dist.ensure((size_t)b->p_plane * b->esize));   // (the deferred route's winning distances)
     }
+    if (prm->metric == ICP_COLORED) {
+        const char* missing = !b->have_normals ? "the model normals (icp_batch_set_model_normals or icp_batch_estimate_normals)"
+                              : !b->have_int[0] ? "the intensities of the moving clouds (icp_batch_set_intensities)"
+                              : !b->have_int[1] ? "the intensities of the models (icp_batch_set_intensities)"
+                              : !b->have_grad   ? "the intensity gradients of the models (icp_batch_estimate_intensity_gradients or icp_batch_set_intensity_gradients)"
+                                                : nullptr;
+        if (missing) return fail(ICP_ERR_INVALID, std::string("a colored batch needs model normals, intensities on both sides and intensity gradients: it lacks ") + missing);
+        if (b->robust) return fail(ICP_ERR_INVALID, "the colored metric takes no robust kernels (icp_batch_set_robust(NULL) first)");
+        HIP_TRY(b->dist.ensure((size_t)b->p_plane * b->esize));   // (the deferred route's winning distances)
+        if (!b->color_w_set)
+            if (int rc = upload_color_weights(b)) return rc;
+    }
     if (prm->precision != b->prec) return fail(ICP_ERR_INVALID, "params precision differs from the batch's clouds");
     if (prm->max_iter < 1) return fail(ICP_ERR_INVALID, "max_iter must be >= 1");
     b->begun = false;
     b->metric = prm->metric;
+    icp_params hp = *prm;
+    if (hp.metric == ICP_COLORED) hp.metric = ICP_POINT_TO_PLANE;   // (the colored metric fills a plane pass's slots: the host loops are point-to-plane loops)
     for (int p = 0; p < b->count; ++p)
-        if (int rc = b->H[p].begin(*prm)) return fail(rc, "bad loop parameters");
+        if (int rc = b->H[p].begin(hp)) return fail(rc, "bad loop parameters");
     // (a generalized pass may keep nothing whatever the options: a match whose det(S) is not > 0 is rejected)
     for (int p = 0; p < b->count; ++p) b->H[p].gated = b->gated || b->trimmed || b->reciprocal || prm->metric == ICP_GENERALIZED;
     if (prm->metric == ICP_GENERALIZED) b->rot.assign((size_t)b->count * 9, 0.0);
@@ -1456,6 +1509,7 @@ int icp_batch_set_model_normals(icp_batch* b, const void* nxyz_aos)
     HIP_TRY(b->N.ensure(3 * (size_t)b->q_plane * b->esize));
     b->begun = false;   // a loop under way is discarded: its passes so far used other normals (or none)
     b->have_normals = false;
+    b->have_grad = false;   // (intensity gradients lie in the tangent planes of the normals they were made with)
     std::vector<char> ns;
     if (int rc = enqueue_planes(b, nxyz_aos, true, b->N.p, ns)) return rc;
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
@@ -1477,6 +1531,7 @@ int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighb
     HIP_TRY(b->N.ensure(qb));
     b->begun = false;   // a loop under way is discarded
     b->have_normals = false;
+    b->have_grad = false;   // (intensity gradients lie in the tangent planes of the normals they were made with)
     HIP_TRY(hipMemsetAsync(b->nbr.p, 0, nb, c->stream));   // (the padding between the clouds: never read, never random)
     HIP_TRY(hipMemsetAsync(b->N.p, 0, qb, c->stream));
     HIP_TRY(icp::launch_batch_normals(b->prec, (const icp::BatchItem*)b->q_items.p, b->n_q_items, (const icp::BatchPair*)b->pairs_d.p, b->Q.p,
@@ -1666,6 +1721,160 @@ int icp_batch_get_covariances(icp_batch* b, double* moving_cov_out, double* mode
     for (int side = 0; side < 2; ++side)
         if (out[side] && !b->have_cov[side]) return fail(ICP_ERR_STATE, std::string("the batch holds no covariances of the ") + (side ? "models" : "moving clouds"));
     return download_covariances(b, out);
+}
+
+namespace {
+
+// n doubles per point of one side, concatenated as the clouds <-> n planes laid out as the cloud's
+void dbl_to_planes(const double* aos, int per, const Side& s, std::vector<double>& planes)
+{
+    planes.assign((size_t)per * (size_t)s.plane, 0.0);
+    for (size_t p = 0; p < s.dst.size(); ++p)
+        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
+            for (int k = 0; k < per; ++k) planes[(size_t)(k * s.plane + s.dst[p] + i)] = aos[per * (s.off[p] + i) + k];
+}
+
+int download_gradients(icp_batch* b, double* out)
+{
+    std::vector<double> h(3 * (size_t)b->q_plane);
+    HIP_TRY(hipMemcpyAsync(h.data(), b->grad.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    const Side s = ::side(b, true);
+    for (size_t p = 0; p < s.dst.size(); ++p)
+        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
+            for (int k = 0; k < 3; ++k) out[3 * (s.off[p] + i) + k] = h[(size_t)(k * s.plane + s.dst[p] + i)];
+    return ICP_OK;
+}
+
+}  // namespace
+
+int icp_batch_set_intensities(icp_batch* b, const double* moving_I, const double* model_I)
+{
+    if (int rc = ready(b)) return rc;
+    const double* given[2] = {moving_I, model_I};
+    if (!given[0] && !given[1]) return fail(ICP_ERR_INVALID, "moving_I == NULL and model_I == NULL");
+    for (int side = 0; side < 2; ++side) {
+        if (!given[side]) continue;
+        const int64_t* off = side ? b->qoff.data() : b->moff.data();
+        for (int p = 0; p < b->count; ++p)
+            for (int64_t i = off[p]; i < off[p + 1]; ++i)
+                if (!std::isfinite(given[side][i]))
+                    return fail(ICP_ERR_INVALID, "an intensity has a NaN or an infinite value: pair " + std::to_string(p) + side_name(side));
+    }
+    // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
+    for (int side = 0; side < 2; ++side)
+        if (given[side]) HIP_TRY(b->inten[side].ensure((size_t)(side ? b->q_plane : b->p_plane) * sizeof(double)));
+    b->begun = false;   // a loop under way is discarded: its passes so far used other intensities (or none)
+    if (given[1]) b->have_grad = false;   // (gradients belong to the model intensities they were made from)
+    std::vector<double> h[2];
+    for (int side = 0; side < 2; ++side) {
+        if (!given[side]) continue;
+        b->have_int[side] = false;
+        dbl_to_planes(given[side], 1, ::side(b, side != 0), h[side]);
+        HIP_TRY(hipMemcpyAsync(b->inten[side].p, h[side].data(), h[side].size() * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
+    for (int side = 0; side < 2; ++side)
+        if (given[side]) b->have_int[side] = true;
+    return ICP_OK;
+}
+
+int icp_batch_estimate_intensity_gradients(icp_batch* b, const int* k_model, double* grad_out)
+{
+    if (int rc = ready(b)) return rc;
+    if (!k_model) return fail(ICP_ERR_INVALID, "k_model == NULL");
+    if (!b->have_int[1]) return fail(ICP_ERR_STATE, "intensity gradients need the intensities of the models: icp_batch_set_intensities first");
+    if (!b->have_normals) return fail(ICP_ERR_STATE, "intensity gradients need the model normals: icp_batch_set_model_normals or icp_batch_estimate_normals first");
+    static_assert(icp::COV_MAX_K == ICP_COV_MAX_NEIGHBOURS, "the kernel's list holds the largest k");
+    int cap = 8;
+    for (int p = 0; p < b->count; ++p) {
+        const int kk = k_model[p];
+        if (kk < ICP_COV_MIN_NEIGHBOURS || kk > ICP_COV_MAX_NEIGHBOURS)
+            return fail(ICP_ERR_INVALID, "the neighbours (k) of an intensity gradient must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]: pair " + std::to_string(p));
+        if (b->pairs[p].m < kk + 1)
+            return fail(ICP_ERR_INVALID, "intensity gradients from k neighbours need a model of at least k + 1 points: pair " + std::to_string(p));
+        cap = std::max(cap, kk <= 8 ? 8 : kk <= 16 ? 16 : 32);
+    }
+    icp_ctx* c = b->ctx;
+    hipStream_t st = c->stream;
+    ScopedPin pin(c);
+    // every model's k travels through one pinned host buffer of the batch's, so that nothing has to outlive the call on the stack:
+    // it returns without a host wait unless the output is wanted.  The allocations come before the batch changes
+    if (int rc = ensure_model_items(b)) return rc;   // (waits once, the first time a batch needs its models' work items)
+    if (b->grad_ev) HIP_TRY(hipEventSynchronize(b->grad_ev));   // (the call before has long read the host buffer: no wait in practice)
+    else HIP_TRY(hipEventCreateWithFlags(&b->grad_ev, hipEventDisableTiming));
+    if (!b->h_grad_k) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_grad_k), (size_t)b->count * sizeof(int), hipHostMallocDefault));
+    HIP_TRY(b->grad_k.ensure((size_t)b->count * sizeof(int)));
+    HIP_TRY(b->grad.ensure(3 * (size_t)b->q_plane * sizeof(double)));
+    b->begun = false;   // a loop under way is discarded
+    b->have_grad = false;
+    std::memcpy(b->h_grad_k, k_model, (size_t)b->count * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(b->grad_k.p, b->h_grad_k, (size_t)b->count * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(b->grad.p, 0, 3 * (size_t)b->q_plane * sizeof(double), st));   // (the padding between the models: never read, never random)
+    icp::BatchGradArgs a{};
+    a.precision = b->prec;
+    a.cap = cap;
+    a.items = (const icp::BatchItem*)b->q_items.p;
+    a.n_items = b->n_q_items;
+    a.pairs = (const icp::BatchPair*)b->pairs_d.p;
+    a.k = (const int*)b->grad_k.p;
+    a.Q_soa = b->Q.p;
+    a.N_soa = b->N.p;
+    a.q_plane = b->q_plane;
+    a.int_q = (const double*)b->inten[1].p;
+    a.grad = (double*)b->grad.p;
+    HIP_TRY(icp::launch_batch_intensity_gradients(a, st));
+    HIP_TRY(hipEventRecord(b->grad_ev, st));
+    if (grad_out)
+        if (int rc = download_gradients(b, grad_out)) return rc;   // (the one wait of a call that wants the output)
+    b->have_grad = true;
+    return ICP_OK;
+}
+
+int icp_batch_set_intensity_gradients(icp_batch* b, const double* grad)
+{
+    if (int rc = ready(b)) return rc;
+    if (!grad) return fail(ICP_ERR_INVALID, "grad == NULL");
+    for (int p = 0; p < b->count; ++p)
+        for (int64_t i = 3 * b->qoff[p]; i < 3 * b->qoff[p + 1]; ++i)
+            if (!std::isfinite(grad[i])) return fail(ICP_ERR_INVALID, "an intensity gradient has a NaN or an infinite value: pair " + std::to_string(p) + side_name(1));
+    HIP_TRY(b->grad.ensure(3 * (size_t)b->q_plane * sizeof(double)));
+    b->begun = false;   // a loop under way is discarded
+    b->have_grad = false;
+    std::vector<double> h;
+    dbl_to_planes(grad, 3, ::side(b, true), h);
+    HIP_TRY(hipMemcpyAsync(b->grad.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
+    b->have_grad = true;
+    return ICP_OK;
+}
+
+int icp_batch_get_intensity_gradients(icp_batch* b, double* grad_out)
+{
+    if (int rc = ready(b)) return rc;
+    if (!grad_out) return fail(ICP_ERR_INVALID, "output pointer == NULL");
+    if (!b->have_grad) return fail(ICP_ERR_STATE, "the batch holds no intensity gradients");
+    return download_gradients(b, grad_out);
+}
+
+int icp_batch_set_color_weight(icp_batch* b, const double* lambda)
+{
+    if (int rc = ready(b)) return rc;
+    if (lambda)
+        for (int p = 0; p < b->count; ++p)
+            if (!(lambda[p] >= 0.0 && lambda[p] <= 1.0))   // (NaN fails both)
+                return fail(ICP_ERR_INVALID, "a color weight (lambda) must lie in [0, 1]: pair " + std::to_string(p));
+    HIP_TRY(b->color_w.ensure((size_t)b->count * sizeof(double)));
+    b->begun = false;   // a loop under way is discarded
+    std::vector<double> keep = b->lambda;
+    if (lambda) b->lambda.assign(lambda, lambda + b->count);
+    else b->lambda.clear();
+    b->color_w_set = false;
+    if (int rc = upload_color_weights(b)) {
+        b->lambda.swap(keep);
+        return rc;
+    }
+    return ICP_OK;
 }
 
 int icp_diag_batch_rotation(icp_batch* b, int pair, double* R9)

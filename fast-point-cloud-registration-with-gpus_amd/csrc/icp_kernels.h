@@ -369,10 +369,19 @@ struct BatchPassArgs {
     const double* cov_p;       // double[6][p_plane]: xx, xy, xz, yy, yz, zz of every moving point, in the frame of the cloud as uploaded
     const double* cov_q;       // double[6][q_plane]: ... of every model point
     const double* rot;         // double[n_pairs][9]: row-major, the rotation that carries the uploaded cloud's frame into this pass's
+    // metric == ICP_COLORED (never with robust_kind): the generalized metric's launches with batch_color_moments<.., MUTUAL = recip
+    // given> (icp_k_color.hip) in batch_gicp_moments' place: kept as batch_trim_moments decides it, the geometric and the photometric
+    // terms of the 6 x 6 system into a plane pass's slots; the reduction runs to ICP_MOM_B + 5.  N_soa holds the model normals.
+    const double* int_p;       // double[p_plane]: every moving point's intensity, laid out as idx
+    const double* int_q;       // double[q_plane]: every model point's intensity, laid out as the models
+    const double* grad_q;      // double[3][q_plane]: every model point's intensity gradient
+    const double* color_w;     // double[n_pairs]: lambda, the weight of the geometric term, in [0, 1]
 };
 hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st);
 // batch_gicp_moments alone, on the buffers the deferred launches of launch_batch_pass left (called by it; icp_k_gicp.hip)
 hipError_t launch_batch_gicp_moments(const BatchPassArgs& a, hipStream_t st);
+// batch_color_moments alone, likewise (icp_k_color.hip)
+hipError_t launch_batch_color_moments(const BatchPassArgs& a, hipStream_t st);
 // evaluation of every pair whose mode is BATCH_MATCH at its present pose (icp_batch_evaluate): the deferred matching launch
 // (point-to-point instantiation whatever the metric, P only read) -> idx, dist; batch_eval_moments: kept = d <= thr[pair], rejected
 // matches marked in idx, the ICP_EVAL_* terms of the kept ones -> partials; batch_finalize_kernel -> mom[pair][ICP_NMOM] (pairs of
@@ -490,6 +499,23 @@ struct BatchCovArgs {
     double* cov[2];            // double[6][src_plane[side]]: xx, xy, xz, yy, yz, zz, laid out as the clouds
 };
 hipError_t launch_batch_covariances(const BatchCovArgs& a, hipStream_t st);
+// per-point intensity gradients of the models of a batch (icp_batch_estimate_intensity_gradients; the rule: include/icp_mi355x.h).
+// The work items are the models' (launch_batch_normals' q_items: BatchItem::pair = the pair, first within its model).  One launch,
+// icp_k_color.hip.
+struct BatchGradArgs {
+    int precision;             // ICP_F32 / ICP_F64
+    int cap;                   // 8, 16 or 32: the register capacity of the list, >= the largest k of the launch
+    const BatchItem* items;
+    int n_items;
+    const BatchPair* pairs;
+    const int* k;              // int[n_pairs]: the neighbours of every model
+    const void* Q_soa;         // the models (read only)
+    const void* N_soa;         // their normals, laid out as Q_soa
+    long long q_plane;
+    const double* int_q;       // double[q_plane]: the models' intensities
+    double* grad;              // double[3][q_plane]: x, y, z of every model point's gradient
+};
+hipError_t launch_batch_intensity_gradients(const BatchGradArgs& a, hipStream_t st);
 // global registration (icp_k_feat.hip; the rules: include/icp_mi355x.h).  Descriptors: the clouds, their numbering, the work items
 // and k are the covariance call's, over both sides; two launches, batch_spfh_kernel (-> spfh, tau) and batch_fpfh_kernel (-> feat).
 // A descriptor is ICP_FEATURE_BINS doubles; point i of a cloud has its own at [(src_off + i) * ICP_FEATURE_BINS].

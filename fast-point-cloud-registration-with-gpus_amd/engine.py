@@ -351,6 +351,36 @@ class Context:
                                   extra={"status": st["status"], "inliers": inl[b], "fitness": float(inl[b].sum()) / inl[b].size}))
             return out
 
+    def register_batch_colored(self, pairs, intensities, k=8, lam=capi.ICP_COLOR_LAMBDA_DEFAULT, normals=None, **options):
+        """register_batch with the colored metric (Park, Zhou, Koltun, ICCV 2017; Batch.begin with ICP_COLORED): every kept match
+        pulls with its point-to-plane residual, weighed by lam, and with the difference between the moving point's intensity and
+        the model's intensity field at the point's foot in the tangent plane, weighed by 1 - lam -- what registers flat or gently
+        curved textured surfaces, which geometry alone leaves free to slide.  intensities = (moving, model): per side one (points,)
+        float64 array per pair (intensity_from_rgb makes them from colours); k: the neighbours of the gradient estimate, a scalar
+        or one per pair; lam: a scalar or one per pair, in [0, 1]; normals: one (m, 3) array per pair, or None: estimated on the
+        device.  options: register_batch's, by keyword, without metric and normals; robust kernels are not combined with this
+        metric.  The same list of Result as register_batch."""
+        unknown = set(options) - {"max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal"}
+        if unknown:
+            raise TypeError(f"register_batch_colored: unknown option(s) {sorted(unknown)}")
+        max_iter = options.get("max_iter")
+        if max_iter is None:
+            max_iter = 50
+        moving, model = intensities
+
+        def prepare(bt):
+            if normals is not None:
+                bt.set_model_normals(normals)
+            else:
+                bt.estimate_normals()
+            bt.set_intensities(moving, model)
+            bt.estimate_intensity_gradients(k)
+            bt.set_color_weight(lam)
+
+        return self._run_batch_options(capi.ICP_COLORED, pairs, None, max_iter, options.get("tol", 1e-6), options.get("fixed_iterations", False),
+                                       options.get("max_distance"), options.get("init"), options.get("trim"), options.get("reciprocal"), None,
+                                       prepare=prepare)
+
     def register_batch_global(self, pairs, voxel, k, hypotheses, max_distance, **options):
         """register_batch for pairs in unknown relative pose: a start pose from descriptors first, then the local loop from it.
         The pairs are uploaded once; a copy thinned at voxel (Batch.downsample; 0 or None: the clouds themselves) gets raw
@@ -469,9 +499,12 @@ class Context:
         set_max_distance, set_initial_transforms, set_trim, set_reciprocal, begin, run to the end, results"""
         return self._run_batch_options(metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init, trim, reciprocal, None)
 
-    def _run_batch_options(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init, trim, reciprocal, robust):
-        """... and robust: None, or (kernel, scale) for set_robust -- the results then carry extra["weights"]"""
+    def _run_batch_options(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init, trim, reciprocal, robust, prepare=None):
+        """... and robust: None, or (kernel, scale) for set_robust -- the results then carry extra["weights"]; prepare: None, or a
+        callable that gives the new Batch what its metric needs beyond normals (the colored metric's intensities and gradients)"""
         with Batch(self, pairs) as bt:
+            if prepare is not None:
+                prepare(bt)
             if metric == capi.ICP_POINT_TO_PLANE:
                 if normals is not None:
                     bt.set_model_normals(normals)
@@ -874,6 +907,71 @@ class Batch:
         capi.check(self._lib.icp_batch_get_covariances(self._h, om.ctypes.data_as(pd), oq.ctypes.data_as(pd)), "icp_batch_get_covariances")
         return self._cut6(om, self._moff), self._cut6(oq, self._qoff)
 
+    def _scalar_side(self, vals, off, what):
+        """one (points,) float64 array per pair -> their concatenation in that side's layout (None: NULL)"""
+        if vals is None:
+            return None
+        vals = [np.ascontiguousarray(v, dtype=np.float64) for v in vals]
+        if len(vals) != self.count:
+            raise ValueError(f"one array of {what} intensities per pair")
+        for b, v in enumerate(vals):
+            if v.shape != (int(off[b + 1] - off[b]),):
+                raise ValueError(f"a pair's {what} intensities must be (points,)")
+        return np.ascontiguousarray(np.concatenate(vals))
+
+    def set_intensities(self, moving=None, model=None):
+        """the intensity of every point, what a colored begin needs on both sides: per side one (points,) float64 array per pair,
+        or None: that side is left as it is.  New model intensities discard the gradients.  Discards a loop under way."""
+        pd = C.POINTER(C.c_double)
+        a, q = self._scalar_side(moving, self._moff, "moving"), self._scalar_side(model, self._qoff, "model")
+        capi.check(self._lib.icp_batch_set_intensities(self._h, a.ctypes.data_as(pd) if a is not None else None,
+                                                       q.ctypes.data_as(pd) if q is not None else None), "icp_batch_set_intensities")
+
+    def estimate_intensity_gradients(self, k=8, want=False):
+        """the intensity gradient of every model point from its k nearest neighbours, on the device in one launch
+        (icp_batch_estimate_intensity_gradients): a least-squares fit of the intensity differences over the neighbourhood -- every
+        other point no farther than the k-th nearest, ties included -- in the tangent plane of the point's normal.  The batch
+        must hold model intensities and model normals.  k: a scalar or one value per pair, each in [3, 32].  want: also return
+        the per-pair list of (m, 3) float64 gradients.  Discards a loop under way."""
+        kq = self._cov_k(k, "k")
+        out = np.empty((int(self._qoff[-1]), 3)) if want else None
+        capi.check(self._lib.icp_batch_estimate_intensity_gradients(self._h, kq.ctypes.data_as(C.POINTER(C.c_int)),
+                                                                    out.ctypes.data_as(C.POINTER(C.c_double)) if want else None),
+                   "icp_batch_estimate_intensity_gradients")
+        if want:
+            return self._cut6(out, self._qoff)
+
+    def set_intensity_gradients(self, grads):
+        """the caller's own intensity gradients: one (m, 3) float64 array per pair, in the models' frame"""
+        grads = [np.ascontiguousarray(g, dtype=np.float64) for g in grads]
+        if len(grads) != self.count:
+            raise ValueError("one array of gradients per pair")
+        for b, g in enumerate(grads):
+            if g.shape != (int(self._qoff[b + 1] - self._qoff[b]), 3):
+                raise ValueError("a pair's gradients must be (model points, 3)")
+        g = np.ascontiguousarray(np.concatenate(grads))
+        capi.check(self._lib.icp_batch_set_intensity_gradients(self._h, g.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_intensity_gradients")
+
+    def get_intensity_gradients(self):
+        """per pair the (m, 3) float64 gradients the batch holds (icp_batch_get_intensity_gradients)"""
+        out = np.empty((int(self._qoff[-1]), 3))
+        capi.check(self._lib.icp_batch_get_intensity_gradients(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_get_intensity_gradients")
+        return self._cut6(out, self._qoff)
+
+    def set_color_weight(self, lam=None):
+        """lambda, the weight of the geometric term of the colored metric (1 - lambda weighs the photometric term): a scalar for
+        every pair, one value per pair, each in [0, 1], or None: ICP_COLOR_LAMBDA_DEFAULT.  Discards a loop under way."""
+        if lam is None:
+            capi.check(self._lib.icp_batch_set_color_weight(self._h, None), "icp_batch_set_color_weight")
+            return
+        a = np.asarray(lam, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(self.count, float(a))
+        a = np.ascontiguousarray(a)
+        if a.shape != (self.count,):
+            raise ValueError("one lambda per pair (or a scalar)")
+        capi.check(self._lib.icp_batch_set_color_weight(self._h, a.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_color_weight")
+
     def diag_rotation(self, b):
         """(3, 3): the rotation pair b's most recent matching pass of a generalized loop rotated its moving covariances by
         (icp_diag_batch_rotation)"""
@@ -1098,7 +1196,8 @@ class Batch:
 
     def begin(self, max_iter=40, tol=1e-6, fixed_iterations=False, metric=capi.ICP_POINT_TO_POINT):
         """start every pair's registration from the uploaded clouds, moved by the pair's initial transform where the batch holds
-        any (ICP_POINT_TO_PLANE: the batch must hold normals; ICP_GENERALIZED: covariances on both sides and no robust kernel)"""
+        any (ICP_POINT_TO_PLANE: the batch must hold normals; ICP_GENERALIZED: covariances on both sides and no robust kernel;
+        ICP_COLORED: normals, intensities on both sides, intensity gradients and no robust kernel)"""
         prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(self._dtype), int(metric))
         capi.check(self._lib.icp_batch_begin(self._h, C.byref(prm)), "icp_batch_begin")
         self._max_iter = int(max_iter)
@@ -1201,6 +1300,15 @@ class Batch:
 
 
 # ---- host-only helpers (no device) -------------------------------------------------------------
+def intensity_from_rgb(rgb):
+    """(n,) float64: the mean of the three channels of an (n, 3) colour array, (r + g) + b over 3.0 in double -- the intensity
+    Open3D's colored ICP takes (Batch.set_intensities)"""
+    c = np.asarray(rgb, dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError("rgb must be (n, 3)")
+    return np.ascontiguousarray(((c[:, 0] + c[:, 1]) + c[:, 2]) / 3.0)
+
+
 def covariances_from_normals(normals, eps=1e-3):
     """(n, 6) float64: I - (1 - eps) n n^T per point as xx, xy, xz, yy, yz, zz -- the plane regularisation of the Generalized-ICP
     paper (variance eps along the normal, 1 across it) for callers who have good unit normals (Batch.set_covariances)"""

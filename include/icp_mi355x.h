@@ -635,6 +635,59 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *             correspondences_out (C_p) hold one int32 per pair, status_out one int; every output may be NULL.
  *         ICP_ERR_STATE without matches; ICP_ERR_INVALID for a null batch, null parameters, null seeds or a value out of range.
  *         The loop does not notice.
+ *   - the colored metric (ICP_COLORED; Park, Zhou, Koltun, ICCV 2017; Open3D's registration_colored_icp): a flat or gently curved
+ *     textured surface leaves geometry alone three unknowns free; a scalar intensity per point (a reflectivity, the mean of an
+ *     RGB colour) fixes them.  Every kept match pulls with two residuals, the point-to-plane distance weighed by lambda and the
+ *     difference between the moving point's intensity and the model's intensity field at the point's foot in the tangent plane,
+ *     weighed by 1 - lambda.  The batch holds one intensity per point on both sides (icp_batch_set_intensities), one intensity
+ *     gradient per model point, estimated on the device (icp_batch_estimate_intensity_gradients) or given
+ *     (icp_batch_set_intensity_gradients; icp_batch_get_intensity_gradients reads them back), and one weight lambda per pair
+ *     (icp_batch_set_color_weight).
+ *       storage: an intensity is one double per point, a gradient three doubles per model point -- always double, whatever the
+ *         batch's precision -- concatenated in the layout of the clouds (moving_off, model_off).
+ *       the calls follow icp_batch_set_covariances: any time after icp_batch_create; a NULL side is left untouched, both NULL is
+ *         ICP_ERR_INVALID; a NaN or an infinite value is ICP_ERR_INVALID and the message names the pair and the side; a loop
+ *         under way is discarded; a refused call leaves the batch as it was.  A pending pass on the context: ICP_ERR_STATE.  A
+ *         null batch: ICP_ERR_INVALID.
+ *       gradients depend on the model's intensities and normals: new model intensities and new model normals
+ *         (icp_batch_set_model_normals, icp_batch_estimate_normals) discard them.
+ *       icp_batch_estimate_intensity_gradients needs model intensities and model normals (ICP_ERR_STATE otherwise); k_model holds
+ *         count ints within [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]; a model of fewer than k + 1 points is
+ *         ICP_ERR_INVALID, the message names the pair.  grad_out may be NULL: there is a host wait only when it is given.
+ *       icp_batch_set_color_weight takes count doubles in [0, 1]; NULL means ICP_COLOR_LAMBDA_DEFAULT for every pair, which is
+ *         also what a batch holds before the first call.
+ *       the gradient rule for model point i, reproducible bit for bit in numpy (tests/batch_color_ref.py does).  Every operation
+ *         is one IEEE double operation, nothing is fused, and the only functions used are + - * /.
+ *           neighbourhood: the FPFH rule's.  d2(i, j) is the matching's squared distance in the batch's precision F; tau_i is the
+ *             k-th smallest over j != i by index; every j != i with d2(i, j) <= tau_i is in; c is their number.
+ *           inputs, per neighbour j: n is the model normal of i, widened; e = q_j - q_i from the widened coordinates;
+ *             h = dot(e, n); u_a = e_a - h*n_a; g = I_j - I_i.
+ *           sums, from 0.0 in ascending j: A_ab += u_a*u_b for the six a <= b; r_a += u_a*g.
+ *           tangent constraint: w = (double)c * (double)c; A_ab += w*(n_a*n_b): the gradient has no part along the normal.
+ *           solve: the generalized metric's cofactor statements on A -- c00 = A11*A22 - A12*A12, c01 = A02*A12 - A01*A22,
+ *             c02 = A01*A12 - A02*A11, c11 = A00*A22 - A02*A02, c12 = A01*A02 - A00*A12, c22 = A00*A11 - A01*A01;
+ *             det = (A00*c00 + A01*c01) + A02*c02; M_ab = c_ab / det; d_a = (M_a0*r_0 + M_a1*r_1) + M_a2*r_2.
+ *           fallback: the gradient is exactly (0, 0, 0) where det is not finite or not > 0, or a component of d is not finite.
+ *           Every dot is (x*x' + y*y') + z*z'.  A model's gradients depend on that model, its normals, its intensities and its k alone.
+ *         cost: one launch for all models (batch_intensity_gradient_kernel: one block per 64 points, the k-th distance in a register
+ *           list, then the nine sums in one pass over the model), no atomics.
+ *       icp_batch_begin with ICP_COLORED needs model normals, intensities on both sides and gradients (ICP_ERR_INVALID without;
+ *         the message names what is missing), and a batch that holds robust kernels refuses this metric with ICP_ERR_INVALID, as
+ *         it refuses ICP_GENERALIZED.  Every pair's host loop solves as for point-to-plane.  icp_host_loop_create,
+ *         icp_batch_evaluate, the single-pair loops (icp_loop_begin, icp_point_to_*) and the one-call icp_point_to_*_batch refuse
+ *         the value as any unknown metric.  icp_batch_downsample and icp_batch_remove_outliers make batches that hold no
+ *         intensities: the caller carries them over with the maps.
+ *       a step always runs deferred: the point-to-point matching launch, [the reverse search,] [the trim's selection,]
+ *         batch_color_moments, the reduction up to ICP_MOM_B + 5 -- three launches, up to five, one download.  The kept decision
+ *         is the one of every deferred batch: gate, tau over all n distances, the mutual rule.  Front end, ICP_MOM_ERR (Euclidean,
+ *         over the points the previous matching pass kept), the err series, the stop rule, idx, masks, initial transforms and
+ *         the ICP_ERR_EMPTY / ICP_ERR_SINGULAR handling are those of the other metrics.
+ *       terms of a kept match of moving point i to model point j, every one in double from the widened moved point p, the model
+ *         point q, the normal n and the gradient d of j and the two intensities: e = p - q, h = dot(e, n); s = dot(d, n),
+ *         m_a = d_a - s*n_a; u_a = e_a - h*n_a; rI = (Iq_j + dot(d, u)) - Ip_i.  J columns j0 = (0, -pz, py), j1 = (pz, 0, -px),
+ *         j2 = (-py, px, 0), j3, j4, j5 the unit vectors; G_a = dot(j_a, n), K_a = dot(j_a, m).  lg = lambda[pair], lp = 1.0 - lg.
+ *         Slot C(a, c) += lg*(G_a*G_c) + lp*(K_a*K_c) for a <= c; slot B(a) -= lg*(G_a*h) + lp*(K_a*rI); ICP_MOM_CNT = 1.
+ *         With lg == 1 these are the plane pass's statements.  A pair's bits depend on that pair and its options alone.
      Not gated, not trimmed and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the
  *     multi-GPU sums -- a single pair that needs any of them is a batch of one; nor do they weigh matches by a robust kernel.  Trimming is the only rejection by rank: there
  *     is no other percentile rejection (none by a multiple of the median or of the standard deviation of the distances). */
@@ -652,7 +705,8 @@ int icp_batch_set_model_normals(icp_batch* b, const void* nxyz_aos);
  * names the pair */
 int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighbours_out);
 /* prm->precision must be the batch's; prm->metric ICP_POINT_TO_POINT, or ICP_POINT_TO_PLANE on a batch that holds normals, or
- * ICP_GENERALIZED on a batch that holds covariances on both sides and no robust kernel */
+ * ICP_GENERALIZED on a batch that holds covariances on both sides and no robust kernel, or ICP_COLORED on a batch that holds model
+ * normals, intensities on both sides, intensity gradients and no robust kernel */
 int icp_batch_begin(icp_batch* b, const icp_params* prm);
 /* up to max_steps passes for every pair still running; *active (optional) = pairs not yet done */
 int icp_batch_run(icp_batch* b, int max_steps, int* steps_done, int* active);
@@ -725,6 +779,19 @@ int icp_batch_estimate_covariances(icp_batch* b, const int* k_moving, const int*
                                    double* moving_cov_out, double* model_cov_out);
 /* the covariances the batch holds; either pointer may be NULL; ICP_ERR_STATE where a side that is asked for holds none */
 int icp_batch_get_covariances(icp_batch* b, double* moving_cov_out, double* model_cov_out);
+/* the colored metric (above): prm->metric of icp_batch_begin on a batch that holds model normals, intensities and gradients */
+#define ICP_COLORED 3                         /* fourth value of icp_metric */
+#define ICP_COLOR_LAMBDA_DEFAULT 0.968
+/* 1 double per point, concatenated as the clouds; a NULL side is left untouched, both NULL: ICP_ERR_INVALID */
+int icp_batch_set_intensities(icp_batch* b, const double* moving_I, const double* model_I);
+/* k_model: count ints; grad_out (3 doubles per model point) may be NULL */
+int icp_batch_estimate_intensity_gradients(icp_batch* b, const int* k_model, double* grad_out);
+/* 3 doubles per model point, concatenated as the models */
+int icp_batch_set_intensity_gradients(icp_batch* b, const double* grad);
+/* the gradients the batch holds; ICP_ERR_STATE where it holds none */
+int icp_batch_get_intensity_gradients(icp_batch* b, double* grad_out);
+/* count doubles in [0, 1]: the weight of the geometric term; NULL: ICP_COLOR_LAMBDA_DEFAULT for every pair */
+int icp_batch_set_color_weight(icp_batch* b, const double* lambda);
 /* global registration (above).  k_*: count ints each; *_normals: 3 doubles per point, laid out as the clouds; the outputs
  * (ICP_FEATURE_BINS doubles per point) may be NULL */
 #define ICP_FEATURE_BINS 33

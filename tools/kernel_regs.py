@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""register / scratch / LDS use of every kernel in build/icp_k_*.s, build/gicp_k.s and build/feat_k.s (optionally filtered by a substring)"""
+"""register / scratch / LDS use of every kernel in build/icp_k_*.s, build/gicp_k.s, build/feat_k.s and build/color_k.s (optionally filtered by a substring)"""
 import re
 import subprocess
 import sys
 
 import glob
-paths = sorted(glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/icp_k_*.s") + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/gicp_k.s") + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/feat_k.s"))
+paths = sorted(glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/icp_k_*.s") + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/gicp_k.s") + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/feat_k.s") + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/color_k.s"))
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
 s = "".join(open(p).read() for p in paths)
 rows = []
