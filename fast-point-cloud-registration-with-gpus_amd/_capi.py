@@ -62,6 +62,11 @@ class icp_ransac_params(C.Structure):
     _fields_ = [("hypotheses", C.c_int), ("max_distance", C.c_double), ("edge_similarity", C.c_double)]
 
 
+class icp_fgr_params(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("max_distance", C.c_double), ("division_factor", C.c_double), ("decrease_every", C.c_int),
+                ("tuples", C.c_int), ("tuple_similarity", C.c_double)]
+
+
 _vp, _i, _pi = C.c_void_p, C.c_int, C.POINTER(C.c_int)
 _pd, _pf, _pi32, _pu32 = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
 _pi64 = C.POINTER(C.c_int64)
@@ -145,6 +150,7 @@ SIGNATURES = {
     "icp_batch_match_features": (_i, [_vp, _i, _pi32, _pi32, C.POINTER(C.c_uint8)]),
     "icp_batch_score_transforms": (_i, [_vp, _i, _pd, _pd, _pi32]),
     "icp_batch_ransac": (_i, [_vp, C.POINTER(icp_ransac_params), C.POINTER(C.c_uint64), _pd, _pi32, _pi32, _pi]),
+    "icp_batch_fgr": (_i, [_vp, C.POINTER(icp_fgr_params), C.POINTER(C.c_uint64), _pd, _pd, _pi32, _pd, _pi]),
     "icp_point_to_point_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_point_to_plane_batch": (_i, [_vp, _i, _vp, _pi64, _vp, _pi64, _vp, C.POINTER(icp_params), _pd, _pi, _pi, _pd, _pi32, _vp, _pi]),
     "icp_comm_unique_id": (_i, [_vp]),
@@ -174,6 +180,8 @@ SIGNATURES = {
     "icp_diag_batch_rotation": (_i, [_vp, _i, _pd]),
     "icp_diag_batch_set_features": (_i, [_vp, _pd, _pd]),
     "icp_diag_batch_ransac": (_i, [_vp, _i, _pi32, C.POINTER(C.c_uint8), _pd, _pi32]),
+    "icp_diag_batch_fgr": (_i, [_vp, _i, _pi32, _pd, _pd, _pd]),
+    "icp_diag_batch_fgr_times": (_i, [_vp, _pd]),
     "icp_solve_rigid": (_i, [_pd, _pd, _pd]),
     "icp_eigh3": (_i, [_pd, _pd, _pd]),
     "icp_synthetic_grid_f32": (_i, [_i, C.c_float, C.c_float, _vp]),

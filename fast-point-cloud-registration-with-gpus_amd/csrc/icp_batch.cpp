@@ -91,7 +91,11 @@
 // (batch_feature_match twice, the sides swapped; fwd and rev come down, kept and every pair's correspondence list are made on
 // the host and go back up)  ->  icp_batch_ransac (the hypotheses are drawn, screened and solved on the host -- icp::solve_rigid --
 // and scored by batch_score_transforms, kRansacChunk hypotheses of every pair per launch; the winner is refitted on its inliers and
-// scored once more)  ->  icp_batch_set_initial_transforms.  icp_batch_score_transforms scores the caller's own candidates.  All
+// scored once more)  ->  icp_batch_set_initial_transforms.  icp_batch_score_transforms scores the caller's own candidates.
+// icp_batch_fgr takes RANSAC's place without hypotheses: the used list of every pair is made once on the host (with the tuple test:
+// RANSAC's draws and edge check) and uploaded; then per iteration FGR_CTL doubles per pair go up (T, mu, a flag), batch_fgr_terms +
+// batch_fgr_finalize run over the pairs still running, the vectors come down (the one wait) and the host solves every pair's 6 x 6
+// system (icp::solve_point_to_plane); a last launch at the final poses writes the weights.  All
 // of them read P0 and Q and buffers of their own: the loop does not notice.
 //
 // Point-to-plane needs the model normals of every pair, in planes laid out as the models: given by the caller
@@ -104,6 +108,7 @@
 // solved by the previous pass is applied in the front of the launch (note_applied when it is enqueued), and the loop's last,
 // error-only pass matches nothing.  The reference runs that loop once per program (src/ICP_point_to_point.cu:295-423,
 // src/ICP_CPU.c:217-271; point-to-plane src/ICP_point_to_plane.cu:517-631).
+#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -193,6 +198,14 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     std::vector<int32_t> rs_triples, rs_counts;   // ... the three list positions, the count (-1: invalid)
     std::vector<uint8_t> rs_valid;
     std::vector<double> rs_T;                // ... and the pose, 16 doubles
+    // Fast Global Registration (icp_batch_fgr): buffers of its own, allocated by the first call (the loop's are never written)
+    DevBuf g_ui, g_uj, g_items, g_item0;     // every pair's used list (int32 at p_off + e), its work items and where each pair's items start (count + 1 ints)
+    DevBuf g_ctl, g_partials, g_mom, g_w;    // FGR_CTL doubles per pair, a row per item, a vector per pair, every moving point's weight (p_plane doubles, laid out as idx)
+    double* h_fgr = nullptr;                 // pinned: count x FGR_CTL doubles (what g_ctl is copied from), then count x ICP_NMOM (what g_mom comes down into)
+    int fg_iter = 0;                         // the last icp_batch_fgr run: iterations, then per pair ...
+    std::vector<std::vector<int32_t>> fg_used;   // ... the used list positions
+    std::vector<double> fg_mu, fg_mom, fg_T; // ... and per iteration mu, the vector (ICP_NMOM) and the pose the terms were formed at (16)
+    double fg_sec[4] = {0, 0, 0, 0};         // ... and the host's seconds in the iterations: enqueue (fill, upload, launches, download), wait, solve; the iterations run
 };
 
 namespace {
@@ -235,13 +248,15 @@ void release(icp_batch* b)
 {
     for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag,
                       &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->rob_kind, &b->rob_k, &b->rob_k2, &b->weights, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom, &b->cov[0], &b->cov[1], &b->cov_args, &b->inten[0], &b->inten[1], &b->grad, &b->grad_k, &b->color_w,
-                      &b->feat[0], &b->feat[1], &b->f_fwd, &b->f_rev, &b->f_kept, &b->f_ci, &b->f_cj, &b->f_cn, &b->s_cand, &b->s_valid, &b->s_thr, &b->s_counts})
+                      &b->feat[0], &b->feat[1], &b->f_fwd, &b->f_rev, &b->f_kept, &b->f_ci, &b->f_cj, &b->f_cn, &b->s_cand, &b->s_valid, &b->s_thr, &b->s_counts,
+                      &b->g_ui, &b->g_uj, &b->g_items, &b->g_item0, &b->g_ctl, &b->g_partials, &b->g_mom, &b->g_w})
         d->release();
     if (b->cov_ev) (void)hipEventDestroy(b->cov_ev);
     if (b->grad_ev) (void)hipEventDestroy(b->grad_ev);
     if (b->h_grad_k) (void)hipHostFree(b->h_grad_k);
     if (b->h_cov_args) (void)hipHostFree(b->h_cov_args);
     if (b->h_eval) (void)hipHostFree(b->h_eval);
+    if (b->h_fgr) (void)hipHostFree(b->h_fgr);
     if (b->h_ctl) (void)hipHostFree(b->h_ctl);
     if (b->h_mom) (void)hipHostFree(b->h_mom);
     delete b;
@@ -2057,6 +2072,34 @@ double sqd(const double* a, const double* b)
     return (dx * dx + dy * dy) + dz * dz;
 }
 
+// hypothesis h of a pair whose seed mixed once is s0, over a list of C >= 3 entries: the picks of slots 0, 1, 2 (at most 16 draws, a
+// draw equal to an earlier slot is skipped).  false: fewer than three distinct picks (the empty slots keep what they held)
+bool draw_triple(uint64_t s0, int h, size_t C, int32_t* slot)
+{
+    const uint64_t base = ransac_mix(s0 + (uint64_t)h);
+    int got = 0;
+    for (int r = 0; r < 16 && got < 3; ++r) {
+        const int32_t v = (int32_t)(ransac_mix(base + (uint64_t)r) % (uint64_t)C);
+        bool seen = false;
+        for (int s = 0; s < got; ++s) seen = seen || slot[s] == v;
+        if (!seen) slot[got++] = v;
+    }
+    return got == 3;
+}
+
+// the edge check of a triple: LP, LQ hold the list's points, 3 doubles per entry; e == 0 switches it off
+bool edges_ok(const double* LP, const double* LQ, const int32_t* slot, double e)
+{
+    if (!(e > 0.0)) return true;
+    static const int ea[3] = {0, 1, 0}, eb[3] = {1, 2, 2};
+    for (int k = 0; k < 3; ++k) {
+        const double la = std::sqrt(sqd(&LP[3 * slot[ea[k]]], &LP[3 * slot[eb[k]]]));
+        const double lb = std::sqrt(sqd(&LQ[3 * slot[ea[k]]], &LQ[3 * slot[eb[k]]]));
+        if (!(la >= e * lb && lb >= e * la)) return false;
+    }
+    return true;
+}
+
 // one match into the 32-double moment vector of icp_solve_rigid
 void add_match(double* mom, const double* p, const double* q)
 {
@@ -2365,26 +2408,9 @@ int icp_batch_ransac(icp_batch* b, const icp_ransac_params* prm, const uint64_t*
             const size_t at = (size_t)p * H + h;
             identity16(&Th[at * 16]);
             if (C < 3) continue;
-            const uint64_t base = ransac_mix(s0 + (uint64_t)h);
             int32_t* slot = &triples[at * 3];
-            int got = 0;
-            for (int r = 0; r < 16 && got < 3; ++r) {
-                const int32_t v = (int32_t)(ransac_mix(base + (uint64_t)r) % (uint64_t)C);
-                bool seen = false;
-                for (int s = 0; s < got; ++s) seen = seen || slot[s] == v;
-                if (!seen) slot[got++] = v;
-            }
-            if (got < 3) continue;
-            bool ok = true;
-            if (e > 0.0) {
-                static const int ea[3] = {0, 1, 0}, eb[3] = {1, 2, 2};
-                for (int k = 0; k < 3 && ok; ++k) {
-                    const double la = std::sqrt(sqd(&LP[p][3 * slot[ea[k]]], &LP[p][3 * slot[eb[k]]]));
-                    const double lb = std::sqrt(sqd(&LQ[p][3 * slot[ea[k]]], &LQ[p][3 * slot[eb[k]]]));
-                    ok = la >= e * lb && lb >= e * la;
-                }
-            }
-            if (!ok) continue;
+            if (!draw_triple(s0, h, C, slot)) continue;
+            if (!edges_ok(LP[p].data(), LQ[p].data(), slot, e)) continue;
             double mom[ICP_NMOM] = {0}, R[9], t[3];
             for (int s = 0; s < 3; ++s) add_match(mom, &LP[p][3 * slot[s]], &LQ[p][3 * slot[s]]);
             if (icp::solve_rigid(mom, R, t) != ICP_OK) continue;
@@ -2475,6 +2501,253 @@ int icp_diag_batch_ransac(icp_batch* b, int pair, int32_t* triples, uint8_t* val
     if (valid) std::memcpy(valid, b->rs_valid.data() + at, H);
     if (T16) std::memcpy(T16, b->rs_T.data() + at * 16, H * 16 * sizeof(double));
     if (counts) std::memcpy(counts, b->rs_counts.data() + at, H * sizeof(int32_t));
+    return ICP_OK;
+}
+
+
+int icp_batch_fgr(icp_batch* b, const icp_fgr_params* prm, const uint64_t* seed, double* T16_out, double* weights_out, int32_t* used_out,
+                  double* objective_out, int* status_out)
+{
+    if (int rc = ready(b)) return rc;
+    if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
+    if (prm->iterations < 1 || prm->iterations > 1024) return fail(ICP_ERR_INVALID, "iterations must lie in [1, 1024]");
+    if (!(std::isfinite(prm->max_distance) && prm->max_distance > 0.0)) return fail(ICP_ERR_INVALID, "max_distance must be finite and > 0");
+    if (!(std::isfinite(prm->division_factor) && prm->division_factor > 1.0)) return fail(ICP_ERR_INVALID, "division_factor must be finite and > 1");
+    if (prm->decrease_every < 1) return fail(ICP_ERR_INVALID, "decrease_every must be >= 1");
+    if (prm->tuples < 0 || prm->tuples > 65536) return fail(ICP_ERR_INVALID, "tuples must lie in [0, 65536]");
+    if (prm->tuples > 0 && !(prm->tuple_similarity >= 0.0 && prm->tuple_similarity < 1.0)) return fail(ICP_ERR_INVALID, "tuple_similarity must lie in [0, 1)");
+    if (prm->tuples > 0 && !seed) return fail(ICP_ERR_INVALID, "seed == NULL with tuples > 0");
+    if (!b->have_match) return fail(ICP_ERR_STATE, "the batch holds no correspondence lists (icp_batch_match_features first)");
+    icp_ctx* c = b->ctx;
+    hipStream_t st = c->stream;
+    ScopedPin pin(c);
+    const int count = b->count, I = prm->iterations;
+    const double d2 = prm->max_distance * prm->max_distance;
+    // the clouds, widened: P0 and Q as the device holds them
+    std::vector<char> ps(3 * (size_t)b->p_plane * b->esize), qs(3 * (size_t)b->q_plane * b->esize);
+    HIP_TRY(hipMemcpyAsync(ps.data(), b->P0.p, ps.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(qs.data(), b->Q.p, qs.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    auto point = [b](const std::vector<char>& raw, long long plane, long long at, double* o) {
+        for (int k = 0; k < 3; ++k) o[k] = get_scalar(b, raw.data(), (size_t)(k * plane + at));
+    };
+    // the used list of every pair, its scale, its work items
+    std::vector<std::vector<int32_t>> used((size_t)count);
+    std::vector<int32_t> ui((size_t)b->p_plane, 0), uj((size_t)b->p_plane, 0);
+    std::vector<icp::BatchItem> items;
+    std::vector<int> item0((size_t)count + 1, 0), status((size_t)count, ICP_ERR_EMPTY);
+    std::vector<double> mu((size_t)count, 0.0);
+    for (int p = 0; p < count; ++p) {
+        const icp::BatchPair& pr = b->pairs[p];
+        const std::vector<int32_t>&li = b->corr_i[p], &lj = b->corr_j[p];
+        const size_t C = li.size();
+        item0[p] = (int)items.size();
+        if (prm->tuples == 0) {
+            used[p].resize(C);
+            for (size_t k = 0; k < C; ++k) used[p][k] = (int32_t)k;
+        } else if (C >= 3) {
+            std::vector<double> LP(3 * C), LQ(3 * C);
+            for (size_t k = 0; k < C; ++k) {
+                point(ps, b->p_plane, pr.p_off + li[k], &LP[3 * k]);
+                point(qs, b->q_plane, pr.q_off + lj[k], &LQ[3 * k]);
+            }
+            std::vector<uint8_t> in(C, 0);
+            const uint64_t s0 = ransac_mix(seed[p]);
+            for (int h = 0; h < prm->tuples; ++h) {
+                int32_t slot[3] = {-1, -1, -1};
+                if (!draw_triple(s0, h, C, slot) || !edges_ok(LP.data(), LQ.data(), slot, prm->tuple_similarity)) continue;
+                in[slot[0]] = in[slot[1]] = in[slot[2]] = 1;
+            }
+            for (size_t k = 0; k < C; ++k)
+                if (in[k]) used[p].push_back((int32_t)k);
+        }
+        const size_t U = used[p].size();
+        if (U < 3) continue;
+        // pbar, qbar: sequential sums in list order; D2: the largest squared distance of a used point from its side's mean
+        std::vector<double> UP(3 * U), UQ(3 * U);
+        double sp[3] = {0.0, 0.0, 0.0}, sq[3] = {0.0, 0.0, 0.0};
+        for (size_t k = 0; k < U; ++k) {
+            const int32_t i = li[used[p][k]], j = lj[used[p][k]];
+            ui[(size_t)pr.p_off + k] = i;
+            uj[(size_t)pr.p_off + k] = j;
+            point(ps, b->p_plane, pr.p_off + i, &UP[3 * k]);
+            point(qs, b->q_plane, pr.q_off + j, &UQ[3 * k]);
+            for (int a = 0; a < 3; ++a) {
+                sp[a] += UP[3 * k + a];
+                sq[a] += UQ[3 * k + a];
+            }
+        }
+        for (int a = 0; a < 3; ++a) {
+            sp[a] = sp[a] / (double)U;
+            sq[a] = sq[a] / (double)U;
+        }
+        double D2 = 0.0;
+        bool nan = false;
+        for (size_t k = 0; k < U; ++k) {
+            const double dp = sqd(&UP[3 * k], sp), dq = sqd(&UQ[3 * k], sq);
+            nan = nan || std::isnan(dp) || std::isnan(dq);
+            D2 = std::max(D2, std::max(dp, dq));
+        }
+        if (nan || !std::isfinite(D2) || !(D2 > 0.0)) continue;
+        status[p] = ICP_OK;
+        mu[p] = D2;
+        for (size_t first = 0; first < U; first += icp::BATCH_ITEM)
+            items.push_back(icp::BatchItem{p, (int)first, (int)std::min((size_t)icp::BATCH_ITEM, U - first), 0});
+    }
+    item0[count] = (int)items.size();
+    const int n_items = (int)items.size();
+    // the call's history and results on the host
+    std::vector<double> T((size_t)count * 16), objective((size_t)count, 0.0);
+    std::vector<double> h_mu((size_t)count * I, 0.0), h_mom((size_t)count * I * ICP_NMOM, 0.0), h_T((size_t)count * I * 16, 0.0);
+    for (int p = 0; p < count; ++p) identity16(&T[(size_t)p * 16]);
+    std::vector<double> wplane;
+    double sec[4] = {0.0, 0.0, 0.0, 0.0};
+    if (n_items > 0) {
+        const size_t ctl_bytes = (size_t)count * icp::FGR_CTL * sizeof(double), mom_bytes = (size_t)count * ICP_NMOM * sizeof(double);
+        if (!b->h_fgr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_fgr), ctl_bytes + mom_bytes, hipHostMallocDefault));
+        HIP_TRY(b->g_ui.ensure((size_t)b->p_plane * sizeof(int32_t)));
+        HIP_TRY(b->g_uj.ensure((size_t)b->p_plane * sizeof(int32_t)));
+        HIP_TRY(b->g_items.ensure((size_t)n_items * sizeof(icp::BatchItem)));
+        HIP_TRY(b->g_item0.ensure(item0.size() * sizeof(int)));
+        HIP_TRY(b->g_ctl.ensure(ctl_bytes));
+        HIP_TRY(b->g_partials.ensure((size_t)n_items * ICP_NMOM * sizeof(double)));
+        HIP_TRY(b->g_mom.ensure(mom_bytes));
+        HIP_TRY(b->g_w.ensure((size_t)b->p_plane * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(b->g_ui.p, ui.data(), ui.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b->g_uj.p, uj.data(), uj.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b->g_items.p, items.data(), (size_t)n_items * sizeof(icp::BatchItem), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b->g_item0.p, item0.data(), item0.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(b->g_w.p, 0, (size_t)b->p_plane * sizeof(double), st));   // (a point that is not used: 0.0)
+        HIP_TRY(hipStreamSynchronize(st));   // (before the host vectors could go with a failed call)
+        icp::BatchFgrArgs a{};
+        a.precision = b->prec;
+        a.items = (const icp::BatchItem*)b->g_items.p;
+        a.n_items = n_items;
+        a.pairs = (const icp::BatchPair*)b->pairs_d.p;
+        a.n_pairs = count;
+        a.item0 = (const int*)b->g_item0.p;
+        a.ui = (const int32_t*)b->g_ui.p;
+        a.uj = (const int32_t*)b->g_uj.p;
+        a.P0 = b->P0.p;
+        a.p_plane = b->p_plane;
+        a.Q = b->Q.p;
+        a.q_plane = b->q_plane;
+        a.ctl = (const double*)b->g_ctl.p;
+        a.partials = (double*)b->g_partials.p;
+        a.mom = (double*)b->g_mom.p;
+        a.weights = (double*)b->g_w.p;
+        double* ctl = b->h_fgr;
+        double* mom = b->h_fgr + (size_t)count * icp::FGR_CTL;
+        std::vector<char> run((size_t)count, 0);   // the pair is still iterating
+        int n_run = 0;
+        for (int p = 0; p < count; ++p) n_run += (run[p] = status[p] == ICP_OK ? 1 : 0);
+        auto fill_ctl = [&](const std::vector<char>& on) {
+            for (int p = 0; p < count; ++p) {
+                double* cp = ctl + (size_t)p * icp::FGR_CTL;
+                std::memcpy(cp, &T[(size_t)p * 16], 12 * sizeof(double));
+                cp[icp::FGR_CTL_MU] = mu[p];
+                cp[icp::FGR_CTL_RUN] = on[p] ? 1.0 : 0.0;
+            }
+        };
+        using clk = std::chrono::steady_clock;
+        auto secs = [](clk::time_point a, clk::time_point z) { return std::chrono::duration<double>(z - a).count(); };
+        for (int it = 0; it < I && n_run > 0; ++it) {
+            const clk::time_point t0 = clk::now();
+            for (int p = 0; p < count; ++p)
+                if (run[p] && it % prm->decrease_every == 0 && mu[p] > d2) mu[p] = std::max(mu[p] / prm->division_factor, d2);
+            fill_ctl(run);
+            HIP_TRY(hipMemcpyAsync(b->g_ctl.p, ctl, ctl_bytes, hipMemcpyHostToDevice, st));
+            HIP_TRY(icp::launch_batch_fgr_terms(a, st));
+            HIP_TRY(hipMemcpyAsync(mom, b->g_mom.p, mom_bytes, hipMemcpyDeviceToHost, st));
+            const clk::time_point t1 = clk::now();
+            HIP_TRY(hipStreamSynchronize(st));
+            const clk::time_point t2 = clk::now();
+            for (int p = 0; p < count; ++p) {
+                if (!run[p]) continue;
+                const double* m = mom + (size_t)p * ICP_NMOM;
+                double* Tp = &T[(size_t)p * 16];
+                const size_t at = (size_t)p * I + it;
+                h_mu[at] = mu[p];
+                std::memcpy(&h_mom[at * ICP_NMOM], m, ICP_NMOM * sizeof(double));
+                std::memcpy(&h_T[at * 16], Tp, 16 * sizeof(double));
+                objective[p] = m[ICP_MOM_ERR];
+                double R[9], t[3], Tn[16];
+                bool ok = icp::solve_point_to_plane(m, R, t, nullptr) == ICP_OK;
+                if (ok) {   // T = S T
+                    for (int r = 0; r < 3; ++r)
+                        for (int cc = 0; cc < 4; ++cc) {
+                            const double v = (R[3 * r] * Tp[cc] + R[3 * r + 1] * Tp[4 + cc]) + R[3 * r + 2] * Tp[8 + cc];
+                            Tn[4 * r + cc] = cc == 3 ? v + t[r] : v;
+                        }
+                    Tn[12] = Tn[13] = Tn[14] = 0.0;
+                    Tn[15] = 1.0;
+                    for (int k = 0; k < 12; ++k) ok = ok && std::isfinite(Tn[k]);
+                }
+                if (!ok) {
+                    status[p] = ICP_ERR_SINGULAR;
+                    run[p] = 0;
+                    n_run -= 1;
+                    continue;
+                }
+                std::memcpy(Tp, Tn, sizeof Tn);
+            }
+            sec[0] += secs(t0, t1);
+            sec[1] += secs(t1, t2);
+            sec[2] += secs(t2, clk::now());
+            sec[3] += 1.0;
+        }
+        // the weights at the final poses, of every pair that iterated
+        std::vector<char> on((size_t)count, 0);
+        for (int p = 0; p < count; ++p) on[p] = status[p] == ICP_OK || status[p] == ICP_ERR_SINGULAR;
+        fill_ctl(on);
+        HIP_TRY(hipMemcpyAsync(b->g_ctl.p, ctl, ctl_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(icp::launch_batch_fgr_weights(a, st));
+        if (weights_out) {
+            wplane.resize((size_t)b->p_plane);
+            HIP_TRY(hipMemcpyAsync(wplane.data(), b->g_w.p, wplane.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    for (int p = 0; p < count; ++p) {
+        const icp::BatchPair& pr = b->pairs[p];
+        if (T16_out) std::memcpy(T16_out + (size_t)p * 16, &T[(size_t)p * 16], 16 * sizeof(double));
+        if (weights_out) {
+            if (wplane.empty()) std::memset(weights_out + b->moff[p], 0, (size_t)pr.n * sizeof(double));
+            else std::memcpy(weights_out + b->moff[p], wplane.data() + pr.p_off, (size_t)pr.n * sizeof(double));
+        }
+        if (used_out) used_out[p] = (int32_t)used[p].size();
+        if (objective_out) objective_out[p] = objective[p];
+        if (status_out) status_out[p] = status[p];
+    }
+    b->fg_iter = I;
+    b->fg_used.swap(used);
+    b->fg_mu.swap(h_mu);
+    b->fg_mom.swap(h_mom);
+    b->fg_T.swap(h_T);
+    std::memcpy(b->fg_sec, sec, sizeof sec);
+    return ICP_OK;
+}
+
+int icp_diag_batch_fgr(icp_batch* b, int pair, int32_t* used_pos, double* mu_hist, double* mom_hist, double* T_hist)
+{
+    if (!b) return fail(ICP_ERR_INVALID, "null batch");
+    if (pair < 0 || pair >= b->count) return fail(ICP_ERR_INVALID, "pair out of range");
+    if (b->fg_iter == 0) return fail(ICP_ERR_STATE, "no icp_batch_fgr run on this batch");
+    const size_t I = (size_t)b->fg_iter, at = (size_t)pair * I;
+    const std::vector<int32_t>& u = b->fg_used[(size_t)pair];
+    if (used_pos && !u.empty()) std::memcpy(used_pos, u.data(), u.size() * sizeof(int32_t));
+    if (mu_hist) std::memcpy(mu_hist, b->fg_mu.data() + at, I * sizeof(double));
+    if (mom_hist) std::memcpy(mom_hist, b->fg_mom.data() + at * ICP_NMOM, I * ICP_NMOM * sizeof(double));
+    if (T_hist) std::memcpy(T_hist, b->fg_T.data() + at * 16, I * 16 * sizeof(double));
+    return ICP_OK;
+}
+
+int icp_diag_batch_fgr_times(icp_batch* b, double* seconds4)
+{
+    if (!b) return fail(ICP_ERR_INVALID, "null batch");
+    if (!seconds4) return fail(ICP_ERR_INVALID, "seconds4 == NULL");
+    if (b->fg_iter == 0) return fail(ICP_ERR_STATE, "no icp_batch_fgr run on this batch");
+    std::memcpy(seconds4, b->fg_sec, sizeof b->fg_sec);
     return ICP_OK;
 }
 

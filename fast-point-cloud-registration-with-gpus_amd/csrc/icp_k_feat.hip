@@ -1,7 +1,8 @@
 // icp_k_feat.hip -- gfx950 kernels of batched global registration (icp_batch.cpp): the 33-bin FPFH descriptor of every point of
 // every cloud of a batch (batch_spfh_kernel, batch_fpfh_kernel), the nearest descriptor of the other cloud (batch_feature_match)
-// and the inlier count of candidate poses over a correspondence list (batch_score_transforms).  The rules are stated in
-// include/icp_mi355x.h and restated in numpy (tests/batch_feature_ref.py); every step here is one statement of them.  The kernels
+// and the inlier count of candidate poses over a correspondence list (batch_score_transforms); the sums of one iteration of Fast
+// Global Registration over a used list, and its weights (batch_fgr_terms, batch_fgr_finalize).  The rules are stated in
+// include/icp_mi355x.h and restated in numpy (tests/batch_feature_ref.py, tests/batch_fgr_ref.py); every step here is one statement of them.  The kernels
 // of icp_k_gicp.hip keep their listings: what this file needs of batch_cov_kernel -- the register list behind tau_i -- is restated,
 // not shared.  Contraction is off for this file: nothing is fused.  No atomics anywhere.
 #include "icp_device.h"
@@ -510,6 +511,134 @@ hipError_t launch_batch_score(const BatchScoreArgs& a, hipStream_t st)
                        a.per_pair, groups, a.counts)
     if (a.precision == ICP_F64) ICP_SCORE_LAUNCH(double); else ICP_SCORE_LAUNCH(float);
 #undef ICP_SCORE_LAUNCH
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Fast Global Registration (icp_batch_fgr): the terms of one Gauss-Newton step of the Geman-McClure objective over every pair's
+// used list, in batch_gicp_moments' block shape -- one block per 64 list entries, wave 0 alone carries data, waves 1-3 add zeros,
+// block_sum_store writes the row.  Entry e of the pair's list: p0 = P0[ui[e]], q = Q[uj[e]], widened once; everything after that
+// is the header's rule in double, one operation per statement:
+//   p_a = ((T[a][0] x + T[a][1] y) + T[a][2] z) + T[a][3], e = p - q, r2 = (ex*ex + ey*ey) + ez*ez, s = mu / (mu + r2), l = s*s;
+//   cn_x = (0, pz, -py, 1, 0, 0), cn_y = (-pz, 0, px, 0, 1, 0), cn_z = (py, -px, 0, 0, 0, 1), w_a[r] = l * cn_a[r];
+//   C(r, c) += (w_x[r]*cn_x[c] + w_y[r]*cn_y[c]) + w_z[r]*cn_z[c] (r <= c), B(r) -= (w_x[r]*ex + w_y[r]*ey) + w_z[r]*ez,
+//   CNT += 1, W += l, ERR += l*r2 + mu*((1 - s)*(1 - s)).
+// An entry whose p or r2 is not finite adds nothing.  The products with the constant zeros and ones stay as written: 0 * x is +-0
+// for every finite x, and the statement is the rule numpy restates.  WEIGHTS: the same l at the pair's final pose into
+// weights[p_off + ui[e]] (0.0 for an entry that does not count) and nothing else -- the list holds a moving point once, so no two
+// lanes write one address.  A pair whose flag in ctl is 0.0 takes no part.  No LDS beyond block_sum_store's 4 x 30 doubles.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool fgr_finite(double v) { return __builtin_fabs(v) < __builtin_huge_val(); }   // (NaN: false)
+
+template <typename F, bool WEIGHTS>
+__global__ __launch_bounds__(NN_BLOCK) void batch_fgr_terms(const BatchItem* __restrict__ items, const BatchPair* __restrict__ pairs,
+                                                            const int32_t* __restrict__ ui, const int32_t* __restrict__ uj,
+                                                            const F* __restrict__ P0, long long p_plane, const F* __restrict__ Q,
+                                                            long long q_plane, const double* __restrict__ ctl,
+                                                            double* __restrict__ partials, double* __restrict__ weights)
+{
+    constexpr int NACC = ICP_MOM_W + 1;
+    static_assert(ICP_MOM_ERR == 0 && ICP_MOM_CNT == 1 && ICP_MOM_C == 2 && ICP_MOM_B == ICP_MOM_C + 21 && ICP_MOM_W == ICP_MOM_B + 6 && NACC <= ICP_NMOM,
+                  "a plane pass's slots, then the sum of the weights");
+    const BatchItem it = items[blockIdx.x];
+    const double* c = ctl + (size_t)FGR_CTL * it.pair;
+    if (c[FGR_CTL_RUN] == 0.0) return;   // (block-uniform)
+    const BatchPair pr = pairs[it.pair];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    if (w == 0 && lane < it.count) {
+        const long long e = pr.p_off + it.first + lane;            // (first + count <= U_p <= n: the host made the items from the list)
+        const long long gi = pr.p_off + ui[e], gj = pr.q_off + uj[e];   // (indices within [0, n) and [0, m): the host made the list)
+        const double x = (double)P0[gi], y = (double)P0[p_plane + gi], z = (double)P0[2 * p_plane + gi];
+        const double mu = c[FGR_CTL_MU];
+        double p[3], ev[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            p[a] = ((c[4 * a] * x + c[4 * a + 1] * y) + c[4 * a + 2] * z) + c[4 * a + 3];
+            ev[a] = p[a] - (double)Q[a * q_plane + gj];
+        }
+        const double r2 = (ev[0] * ev[0] + ev[1] * ev[1]) + ev[2] * ev[2];
+        const double s = mu / (mu + r2);
+        const double l = s * s;
+        const bool ok = fgr_finite(p[0]) && fgr_finite(p[1]) && fgr_finite(p[2]) && fgr_finite(r2);
+        if constexpr (WEIGHTS) {
+            weights[gi] = ok ? l : 0.0;
+        } else if (ok) {
+            const double cn[3][6] = {{0.0, p[2], -p[1], 1.0, 0.0, 0.0}, {-p[2], 0.0, p[0], 0.0, 1.0, 0.0}, {p[1], -p[0], 0.0, 0.0, 0.0, 1.0}};
+            double wr[3][6];
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int r = 0; r < 6; ++r) wr[a][r] = l * cn[a][r];
+            int o = ICP_MOM_C;
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int cc = r; cc < 6; ++cc) acc[o++] = (wr[0][r] * cn[0][cc] + wr[1][r] * cn[1][cc]) + wr[2][r] * cn[2][cc];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) acc[ICP_MOM_B + r] -= (wr[0][r] * ev[0] + wr[1][r] * ev[1]) + wr[2][r] * ev[2];
+            const double d = 1.0 - s;
+            acc[ICP_MOM_ERR] = l * r2 + mu * (d * d);
+            acc[ICP_MOM_CNT] = 1.0;
+            acc[ICP_MOM_W] = l;
+        }
+    }
+    if constexpr (!WEIGHTS) block_sum_store<NACC, NN_BLOCK>(acc, partials + (size_t)blockIdx.x * ICP_NMOM);
+}
+
+// one block per pair: batch_finalize_kernel's scheme and order over the pair's FGR items -- thread (k, part) adds items part,
+// part + 8, ... of slot k, the eight part sums are then added in part order; the slots behind ICP_MOM_W are written as zeros
+__global__ __launch_bounds__(256) void batch_fgr_finalize(const int* __restrict__ item0, const double* __restrict__ ctl,
+                                                          const double* __restrict__ partials, double* __restrict__ mom)
+{
+    __shared__ double red[8][ICP_NMOM];
+    if (ctl[(size_t)FGR_CTL * blockIdx.x + FGR_CTL_RUN] == 0.0) return;
+    const int k = threadIdx.x & 31, part = threadIdx.x >> 5;
+    const int i0 = item0[blockIdx.x], i1 = item0[blockIdx.x + 1];
+    double s = 0.0;
+    if (k <= ICP_MOM_W)
+        for (int i = i0 + part; i < i1; i += 8) s += partials[(size_t)i * ICP_NMOM + k];
+    red[part][k] = s;
+    __syncthreads();
+    if (threadIdx.x < ICP_NMOM) {
+        double tot = red[0][k];
+#pragma unroll
+        for (int p = 1; p < 8; ++p) tot += red[p][k];
+        mom[(size_t)blockIdx.x * ICP_NMOM + k] = tot;
+    }
+}
+
+static bool fgr_args_ok(const BatchFgrArgs& a)
+{
+    return a.items && a.pairs && a.item0 && a.ui && a.uj && a.P0 && a.Q && a.ctl;
+}
+
+hipError_t launch_batch_fgr_terms(const BatchFgrArgs& a, hipStream_t st)
+{
+    if (a.n_items <= 0 || a.n_pairs <= 0) return hipSuccess;
+    if (!fgr_args_ok(a) || !a.partials || !a.mom) return hipErrorInvalidValue;
+#define ICP_FGR_LAUNCH(F)                                                                                                      \
+    hipLaunchKernelGGL((batch_fgr_terms<F, false>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs, a.ui, a.uj,      \
+                       (const F*)a.P0, a.p_plane, (const F*)a.Q, a.q_plane, a.ctl, a.partials, (double*)nullptr)
+    if (a.precision == ICP_F64) ICP_FGR_LAUNCH(double); else ICP_FGR_LAUNCH(float);
+#undef ICP_FGR_LAUNCH
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(batch_fgr_finalize, dim3(a.n_pairs), dim3(256), 0, st, a.item0, a.ctl, (const double*)a.partials, a.mom);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_fgr_weights(const BatchFgrArgs& a, hipStream_t st)
+{
+    if (a.n_items <= 0 || a.n_pairs <= 0) return hipSuccess;
+    if (!fgr_args_ok(a) || !a.weights) return hipErrorInvalidValue;
+#define ICP_FGR_LAUNCH(F)                                                                                                      \
+    hipLaunchKernelGGL((batch_fgr_terms<F, true>), dim3(a.n_items), dim3(NN_BLOCK), 0, st, a.items, a.pairs, a.ui, a.uj,       \
+                       (const F*)a.P0, a.p_plane, (const F*)a.Q, a.q_plane, a.ctl, (double*)nullptr, a.weights)
+    if (a.precision == ICP_F64) ICP_FGR_LAUNCH(double); else ICP_FGR_LAUNCH(float);
+#undef ICP_FGR_LAUNCH
     return hipGetLastError();
 }
 

@@ -565,6 +565,36 @@ struct BatchScoreArgs {
     int32_t* counts;           // int32[n_pairs][per_pair]
 };
 hipError_t launch_batch_score(const BatchScoreArgs& a, hipStream_t st);
+// Fast Global Registration (icp_batch_fgr): one iteration's sums, or the weights at the final pose.  Every pair's used list is a
+// compacted (ui, uj) index list (int32 at p_off + e, e < U_p; indices within the pair's clouds); the work items cut it into
+// BATCH_ITEM entries (BatchItem::first = the first entry).  ctl holds FGR_CTL doubles per pair: the upper three rows of T
+// row-major (12), mu, and a flag -- 0.0: the pair takes no part, its blocks return and its row of mom is not written.
+//   launch_batch_fgr_terms    batch_fgr_terms<F, false> (one block per item: the terms of the header's rule -> a row of partials,
+//                             slots 0 .. ICP_MOM_W) + batch_fgr_finalize (one block per pair: its items' rows in
+//                             batch_finalize_kernel's fixed order -> mom[pair][ICP_NMOM], zeros behind ICP_MOM_W).  Two launches.
+//   launch_batch_fgr_weights  batch_fgr_terms<F, true>: weights[p_off + ui[e]] = l of entry e (0.0 where the moved point or r2 is
+//                             not finite); nothing else is written.  One launch.
+constexpr int FGR_CTL = 14, FGR_CTL_MU = 12, FGR_CTL_RUN = 13;
+struct BatchFgrArgs {
+    int precision;
+    const BatchItem* items;
+    int n_items;
+    const BatchPair* pairs;
+    int n_pairs;
+    const int* item0;          // int[n_pairs + 1]: items [item0[p], item0[p + 1]) belong to pair p, in list order
+    const int32_t* ui;
+    const int32_t* uj;
+    const void* P0;
+    long long p_plane;
+    const void* Q;
+    long long q_plane;
+    const double* ctl;         // double[n_pairs][FGR_CTL]
+    double* partials;          // [n_items][ICP_NMOM]
+    double* mom;               // [n_pairs][ICP_NMOM]
+    double* weights;           // double[p_plane], laid out as idx (written by launch_batch_fgr_weights only)
+};
+hipError_t launch_batch_fgr_terms(const BatchFgrArgs& a, hipStream_t st);
+hipError_t launch_batch_fgr_weights(const BatchFgrArgs& a, hipStream_t st);
 
 // soa2 (optional): a second copy of the result (the pristine moving cloud); enc (optional, fp32): the cloud's bounding cube as six
 // ordered-integer words {~ord(min xyz), ord(max xyz)}, zero before the launch

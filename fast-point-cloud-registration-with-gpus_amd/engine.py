@@ -389,11 +389,18 @@ class Context:
         (Batch.match_features) and a RANSAC pose (Batch.ransac with hypotheses, max_distance and the options edge_similarity,
         0.9, and seed, 0); register_batch then runs on the full pairs with init = those poses.  options: besides viewpoint,
         edge_similarity, seed and mutual (True), register_batch's by keyword without init; gate is handed on as its max_distance.
-        The same list of Result, with extra["global"] added: the dict Batch.ransac returned for the pair."""
-        known = {"viewpoint", "edge_similarity", "seed", "mutual", "gate", "metric", "normals", "max_iter", "tol", "fixed_iterations", "trim", "reciprocal"}
+        The same list of Result, with extra["global"] added: the dict Batch.ransac returned for the pair.
+        method="fgr" (the default is "ransac") runs Batch.fgr in RANSAC's place: hypotheses is read as tuples (0: every
+        correspondence) and max_distance as delta; the options iterations, division_factor, decrease_every and tuple_similarity are
+        handed on where given, seed too; extra["global"] is then the dict Batch.fgr returned."""
+        known = {"viewpoint", "edge_similarity", "seed", "mutual", "gate", "metric", "normals", "max_iter", "tol", "fixed_iterations", "trim", "reciprocal",
+                 "method", "iterations", "division_factor", "decrease_every", "tuple_similarity"}
         unknown = set(options) - known
         if unknown:
             raise TypeError(f"register_batch_global: unknown option(s) {sorted(unknown)}")
+        method = options.get("method", "ransac")
+        if method not in ("ransac", "fgr"):
+            raise ValueError(f"register_batch_global: method must be 'ransac' or 'fgr', not {method!r}")
         pairs = list(pairs)
         v = 0.0 if voxel is None else float(voxel)
         with Batch(self, pairs) as full:
@@ -407,7 +414,11 @@ class Context:
                 nq = [oriented_normals(M, c, eye(M)) for (_, M), c in zip(clouds, cq)]
                 bt.compute_features(k, (nm, nq))
                 bt.match_features(mutual=options.get("mutual", True))
-                start = bt.ransac(hypotheses, max_distance, edge_similarity=options.get("edge_similarity", 0.9), seed=options.get("seed", 0))
+                if method == "fgr":
+                    more = {o: options[o] for o in ("iterations", "division_factor", "decrease_every", "tuple_similarity") if o in options}
+                    start = bt.fgr(max_distance, tuples=hypotheses, seed=options.get("seed", 0), **more)
+                else:
+                    start = bt.ransac(hypotheses, max_distance, edge_similarity=options.get("edge_similarity", 0.9), seed=options.get("seed", 0))
             finally:
                 if bt is not full:
                     bt.close()
@@ -1088,6 +1099,57 @@ class Batch:
         capi.check(self._lib.icp_diag_batch_ransac(self._h, int(b), tr.ctypes.data_as(p32), va.ctypes.data_as(C.POINTER(C.c_uint8)),
                                                    T.ctypes.data_as(C.POINTER(C.c_double)), cn.ctypes.data_as(p32)), "icp_diag_batch_ransac")
         return dict(triples=tr[:H], valid=va[:H], T=T[:H], counts=cn[:H])
+
+    def fgr(self, max_distance, iterations=64, division_factor=1.4, decrease_every=4, tuples=0, tuple_similarity=0.95, seed=0):
+        """a start pose for every pair from its correspondence list by Fast Global Registration (icp_batch_fgr): no hypotheses --
+        iterations weighted Gauss-Newton steps on the Geman-McClure objective, whose scale mu starts at the squared extent of the
+        used points and is divided by division_factor every decrease_every iterations, never below max_distance squared.
+        tuples 0: every correspondence is used and the result needs no seed; tuples > 0: the correspondences that occur in a
+        triple of ransac's generator (seed: a scalar for every pair, or one per pair) that passes the edge check at
+        tuple_similarity.  Per pair a dict of T (4, 4: maps the moving cloud as uploaded into the model's frame -- what
+        set_initial_transforms takes), weights (n,) float64 -- the soft inlier weight of every moving point at T, 0 for a point
+        that was not used -- used (how many correspondences were), objective and status (ICP_OK; ICP_ERR_EMPTY where fewer than
+        three correspondences are used: T is then the identity; ICP_ERR_SINGULAR where a step's system was not positive definite:
+        T is then the pose reached so far)."""
+        sd = None
+        if int(tuples) > 0:
+            sd = np.asarray(seed)
+            sd = np.full(self.count, int(sd), dtype=np.uint64) if sd.ndim == 0 else np.ascontiguousarray(sd, dtype=np.uint64)
+            if sd.shape != (self.count,):
+                raise ValueError("one seed per pair (or a scalar)")
+        prm = capi.icp_fgr_params(int(iterations), float(max_distance), float(division_factor), int(decrease_every), int(tuples), float(tuple_similarity))
+        T = np.zeros((self.count, 4, 4))
+        w = np.zeros(int(self._moff[-1]))
+        used = np.zeros(self.count, dtype=np.int32)
+        obj = np.zeros(self.count)
+        st = np.zeros(self.count, dtype=np.intc)
+        pd = C.POINTER(C.c_double)
+        capi.check(self._lib.icp_batch_fgr(self._h, C.byref(prm), sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None, T.ctypes.data_as(pd),
+                                           w.ctypes.data_as(pd), used.ctypes.data_as(C.POINTER(C.c_int32)), obj.ctypes.data_as(pd),
+                                           st.ctypes.data_as(C.POINTER(C.c_int))), "icp_batch_fgr")
+        self._fgr_iter, self._fgr_used = int(iterations), used.copy()
+        return [dict(T=T[b].copy(), weights=w[self._moff[b]:self._moff[b + 1]].copy(), used=int(used[b]), objective=float(obj[b]), status=int(st[b]))
+                for b in range(self.count)]
+
+    def diag_fgr(self, b):
+        """the last fgr run's history of pair b (icp_diag_batch_fgr): dict of used_pos (U,) int32 -- positions in the pair's
+        correspondence list -- mu_hist (I,), mom_hist (I, 32) and T_hist (I, 4, 4), the pose every iteration's terms were formed
+        at; the iterations the pair did not run hold zeros"""
+        I = int(getattr(self, "_fgr_iter", 0))
+        U = int(self._fgr_used[int(b)]) if I else 0
+        up = np.zeros(max(U, 1), dtype=np.int32)
+        mu, mom, T = np.zeros(max(I, 1)), np.zeros((max(I, 1), capi.ICP_NMOM)), np.zeros((max(I, 1), 4, 4))
+        pd = C.POINTER(C.c_double)
+        capi.check(self._lib.icp_diag_batch_fgr(self._h, int(b), up.ctypes.data_as(C.POINTER(C.c_int32)), mu.ctypes.data_as(pd), mom.ctypes.data_as(pd),
+                                                T.ctypes.data_as(pd)), "icp_diag_batch_fgr")
+        return dict(used_pos=up[:U], mu_hist=mu[:I], mom_hist=mom[:I], T_hist=T[:I])
+
+    def diag_fgr_times(self):
+        """where the host's time went in the iterations of the last fgr run (icp_diag_batch_fgr_times): dict of enqueue_s, wait_s
+        and solve_s, summed over the iterations, and iterations, how many ran"""
+        t = np.zeros(4)
+        capi.check(self._lib.icp_diag_batch_fgr_times(self._h, t.ctypes.data_as(C.POINTER(C.c_double))), "icp_diag_batch_fgr_times")
+        return dict(enqueue_s=float(t[0]), wait_s=float(t[1]), solve_s=float(t[2]), iterations=int(t[3]))
 
     def set_max_distance(self, v):
         """the maximum correspondence distance: a scalar for every pair, one value per pair (inf: that pair is not gated), or

@@ -635,6 +635,46 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *             correspondences_out (C_p) hold one int32 per pair, status_out one int; every output may be NULL.
  *         ICP_ERR_STATE without matches; ICP_ERR_INVALID for a null batch, null parameters, null seeds or a value out of range.
  *         The loop does not notice.
+ *       Fast Global Registration (icp_batch_fgr; Zhou, Park, Koltun, ECCV 2016; Open3D's
+ *         registration_fgr_based_on_feature_matching): no hypotheses -- one robust objective (Geman-McClure, by graduated
+ *         non-convexity) over the correspondence list, minimised by `iterations` weighted Gauss-Newton steps.  iterations in
+ *         [1, 1024]; max_distance (delta) finite and > 0; division_factor finite and > 1; decrease_every >= 1; tuples in [0, 65536];
+ *         tuple_similarity in [0, 1), read only where tuples > 0; one seed per pair, read only where tuples > 0 (seed may be NULL
+ *         iff tuples == 0).  With tuples == 0 the call is deterministic without a seed.  Everything is in double, from coordinates
+ *         widened once; every operation is one IEEE double operation, nothing is fused; the only functions used are + - * /.
+ *           used list: tuples == 0: every correspondence, in list order.  tuples > 0: hypotheses h = 0 .. tuples-1 by RANSAC's own
+ *             draw, triple and edge check with e = tuple_similarity (a hypothesis is valid iff it has three distinct picks and
+ *             passes the edge check; nothing is solved); a list position is used iff it occurs in a valid triple, each position is
+ *             used once, however often it occurs -- a deliberate deviation from Open3D, which repeats them -- and the order is
+ *             ascending list position.  U_p is the length of the used list.  U_p < 3: status ICP_ERR_EMPTY, T the identity, every
+ *             weight 0, objective 0.
+ *           scale: pbar and qbar are the sequential sums of the used moving and model points, in list order, divided by U_p; D2 is
+ *             the largest of (dx*dx + dy*dy) + dz*dz over the used points of both sides, each against its own mean; mu = D2.
+ *             D2 == 0 or not finite: ICP_ERR_EMPTY, as above.
+ *           iteration it = 0 .. iterations-1, from T = the identity: if it % decrease_every == 0 and mu > delta*delta then
+ *             mu = max(mu / division_factor, delta*delta) -- mu is never lowered below delta^2.  Per used correspondence (p0, q):
+ *             p_a = ((T[a][0] x + T[a][1] y) + T[a][2] z) + T[a][3]; e_a = p_a - q_a; r2 = (ex*ex + ey*ey) + ez*ez;
+ *             s = mu / (mu + r2); l = s*s (s stands for sqrt(l): no sqrt is needed).  The three residual rows are
+ *             cn_x = (0, pz, -py, 1, 0, 0), cn_y = (-pz, 0, px, 0, 1, 0), cn_z = (py, -px, 0, 0, 0, 1); w_a[r] = l * cn_a[r].
+ *             The sums go into a plane pass's slots: C(r, c) += (w_x[r]*cn_x[c] + w_y[r]*cn_y[c]) + w_z[r]*cn_z[c] for r <= c;
+ *             B(r) -= (w_x[r]*ex + w_y[r]*ey) + w_z[r]*ez; ICP_MOM_CNT += 1; ICP_MOM_W += l;
+ *             ICP_MOM_ERR += l*r2 + mu*((1 - s)*(1 - s)); the slots behind ICP_MOM_W are 0.  A correspondence whose p or r2 is not
+ *             finite adds nothing and counts 0 (its weight is reported as 0.0).
+ *           solve: the vector goes through icp_solve_point_to_plane (below): R = Rz Ry Rx, unknowns (rx, ry, rz, tx, ty, tz);
+ *             T = S T with S = [R t; 0 1], every entry (s0 a + s1 b) + s2 c, the translation + t.  A system that is not positive
+ *             definite, or a product that is not finite, ends that pair with ICP_ERR_SINGULAR at the pose reached so far; the
+ *             other pairs go on.
+ *           results: T16_out maps P0 into the model's frame and goes straight into icp_batch_set_initial_transforms, as RANSAC's
+ *             pose does.  objective_out is ICP_MOM_ERR of the pair's last iteration.  A last weights-only launch at the final T
+ *             and the last mu gives weights_out, laid out as the moving clouds: a used point gets its l, every other point 0.0.
+ *             used_out is U_p.  Every output pointer may be NULL.
+ *           sums: per work item of 64 list entries, then per pair, in a fixed order; no floating-point atomics.  A pair's bits
+ *             depend on that pair, its seed and the parameters alone -- not on its neighbours or its position in the batch.
+ *           cost: per iteration one upload of 14 doubles per pair (T, mu, a flag), two launches (batch_fgr_terms, one block per 64
+ *             list entries; batch_fgr_finalize, one block per pair), one download, one host wait and the host's 6 x 6 solve.
+ *         ICP_ERR_STATE without matches or with a pending pass on the context; ICP_ERR_INVALID for a null batch, null parameters,
+ *         null seeds with tuples > 0 or a value out of range; a refused call leaves the batch as it was.  The loop does not notice:
+ *         the call reads P0 and Q, never the moved cloud, and neither discards nor advances a registration under way.
  *   - the colored metric (ICP_COLORED; Park, Zhou, Koltun, ICCV 2017; Open3D's registration_colored_icp): a flat or gently curved
  *     textured surface leaves geometry alone three unknowns free; a scalar intensity per point (a reflectivity, the mean of an
  *     RGB colour) fixes them.  Every kept match pulls with two residuals, the point-to-plane distance weighed by lambda and the
@@ -806,6 +846,18 @@ int icp_batch_score_transforms(icp_batch* b, int per_pair, const double* T16, co
 typedef struct icp_ransac_params { int hypotheses; double max_distance; double edge_similarity; } icp_ransac_params;
 int icp_batch_ransac(icp_batch* b, const icp_ransac_params* prm, const uint64_t* seed /*count*/,
                      double* T16_out, int32_t* inliers_out, int32_t* correspondences_out, int* status_out);
+/* Fast Global Registration over the correspondence lists (above) */
+typedef struct icp_fgr_params {
+    int iterations;           /* [1, 1024]; Open3D's default is 64 */
+    double max_distance;      /* delta: finite, > 0; mu is never lowered below delta^2 */
+    double division_factor;   /* finite, > 1; 1.4 */
+    int decrease_every;       /* >= 1; 4 */
+    int tuples;               /* [0, 65536]; 0 = use every correspondence */
+    double tuple_similarity;  /* [0, 1); read only where tuples > 0; 0.95 */
+} icp_fgr_params;
+int icp_batch_fgr(icp_batch* b, const icp_fgr_params* prm, const uint64_t* seed /* count; may be NULL iff tuples == 0 */,
+                  double* T16_out, double* weights_out /* 1 per moving point */, int32_t* used_out /* 1 per pair */,
+                  double* objective_out /* 1 per pair */, int* status_out);
 /* one call: create + begin + run to the end + results, then destroy.  Every output pointer may be NULL; per pair:
  * T16_out 16, iterations_out / passes_out / status_out 1, err_out max_iter+1 doubles; idx_out and moved_out (3 values per
  * point, precision of the run) concatenated as the moving clouds.  A failed pair is reported in status_out, not in the

@@ -124,6 +124,16 @@ int icp_diag_batch_set_features(icp_batch* b, const double* moving_feat, const d
  * batch_score_transforms counted; -1 for an invalid hypothesis).  Host copies: nothing is downloaded.  Every output may be NULL.
  * ICP_ERR_STATE before the first run. */
 int icp_diag_batch_ransac(icp_batch* b, int pair, int32_t* triples, uint8_t* valid, double* T16, int32_t* counts);
+/* the last icp_batch_fgr run's history of pair `pair`, I = that run's prm->iterations: used_pos U_p int32 (the positions in the
+ * pair's correspondence list that were used, ascending; U_p is the call's used_out), mu_hist I doubles (mu of every iteration),
+ * mom_hist I x ICP_NMOM doubles (the vector every iteration's solve read), T_hist I x 16 doubles (the pose that iteration's terms
+ * were formed at: the identity for iteration 0).  The iterations a pair did not run -- after ICP_ERR_SINGULAR, or all of them for
+ * ICP_ERR_EMPTY -- hold zeros.  Host copies: nothing is downloaded.  Every output may be NULL.  ICP_ERR_STATE before the first run. */
+int icp_diag_batch_fgr(icp_batch* b, int pair, int32_t* used_pos, double* mu_hist, double* mom_hist, double* T_hist);
+/* where the host's time went in the iterations of the last icp_batch_fgr run, summed over them, in seconds: [0] enqueue (the
+ * control block, its upload, the two launches, the download), [1] the wait for the vectors, [2] the solves of all pairs; [3] is
+ * the number of iterations that ran.  Three clock reads per iteration.  ICP_ERR_STATE before the first run. */
+int icp_diag_batch_fgr_times(icp_batch* b, double* seconds4);
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""register / scratch / LDS use of every kernel in build/icp_k_*.s, build/gicp_k.s, build/feat_k.s and build/color_k.s (optionally filtered by a substring)"""
+"""register / scratch / LDS use of every kernel in build/icp_k_*.s, build/gicp_k.s, build/feat_k.s and build/color_k.s (optionally filtered by a substring).
+build/feat_k.s holds the descriptor, matching and scoring kernels and those of Fast Global Registration: `kernel_regs.py fgr` lists
+batch_fgr_terms<F, false / true> and batch_fgr_finalize"""
 import re
 import subprocess
 import sys
