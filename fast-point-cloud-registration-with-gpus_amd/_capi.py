@@ -34,6 +34,7 @@ ICP_ROBUST_NONE, ICP_ROBUST_HUBER, ICP_ROBUST_CAUCHY, ICP_ROBUST_TUKEY = 0, 1, 2
 ICP_BATCH_MAX_POINTS = 65536   # per cloud of one pair of a batch
 ICP_OUTLIER_NONE, ICP_OUTLIER_STATISTICAL, ICP_OUTLIER_RADIUS = 0, 1, 2   # icp_outlier_rule.kind
 ICP_OUTLIER_MAX_NEIGHBOURS = 32
+ICP_KEYPOINT_NONE, ICP_KEYPOINT_ISS = 0, 1   # icp_keypoint_rule.kind
 # icp_diag_loop_moments: how the vector came about (include/icp_mi355x_diag.h)
 ROUTE_HOST_ROWS, ROUTE_COMPACT, ROUTE_AVX, ROUTE_FIN_LAUNCH, ROUTE_FIN_PINNED, ROUTE_FIN_KERNEL = 0x001, 0x002, 0x004, 0x008, 0x010, 0x020
 ROUTE_FIN_TWO_STAGE, ROUTE_FUSED_TAIL, ROUTE_MOMENTS_KERNEL, ROUTE_ERROR_ONLY, ROUTE_ARMED, ROUTE_RESIDENT = 0x040, 0x080, 0x100, 0x200, 0x400, 0x800
@@ -56,6 +57,11 @@ class icp_result(C.Structure):
 
 class icp_outlier_rule(C.Structure):
     _fields_ = [("kind", C.c_int), ("neighbours", C.c_int), ("value", C.c_double)]
+
+
+class icp_keypoint_rule(C.Structure):
+    _fields_ = [("kind", C.c_int), ("min_neighbours", C.c_int), ("salient_radius", C.c_double), ("non_max_radius", C.c_double),
+                ("gamma_21", C.c_double), ("gamma_32", C.c_double)]
 
 
 class icp_ransac_params(C.Structure):
@@ -136,6 +142,7 @@ SIGNATURES = {
     "icp_batch_downsample": (_i, [_vp, _pd, _pd, _pi32, _pi32, C.POINTER(_vp)]),
     "icp_batch_get_offsets": (_i, [_vp, _pi64, _pi64]),
     "icp_batch_remove_outliers": (_i, [_vp, C.POINTER(icp_outlier_rule), C.POINTER(icp_outlier_rule), _pi32, _pi32, _pd, _pd, _pd, C.POINTER(_vp)]),
+    "icp_batch_select_keypoints": (_i, [_vp, C.POINTER(icp_keypoint_rule), C.POINTER(icp_keypoint_rule), _pi32, _pi32, _pd, _pd, _pi32, C.POINTER(_vp)]),
     "icp_batch_get_clouds": (_i, [_vp, _vp, _vp]),
     "icp_batch_set_covariances": (_i, [_vp, _pd, _pd]),
     "icp_batch_estimate_covariances": (_i, [_vp, _pi, _pi, _i, C.c_double, _pd, _pd]),

@@ -98,6 +98,14 @@
 // system (icp::solve_point_to_plane); a last launch at the final poses writes the weights.  All
 // of them read P0 and Q and buffers of their own: the loop does not notice.
 //
+// The clouds of a batch are reduced to their salient points on the device (icp_batch_select_keypoints; kernels: icp_k_keypoint.hip):
+// a new batch on the same context whose clouds are the ISS keypoints of P0 and Q of the source, with the descriptors of the kept
+// points where the source holds descriptors, so that matching and RANSAC or FGR run on a few hundred points per cloud.
+// batch_iss_saliency (the smallest eigenvalue of every point's neighbourhood covariance)  ->  batch_iss_select (non-maximum
+// suppression)  ->  batch_keypoint_rank (maps and counts)  ->  [D2H: 2 x count counts, the first wait; lay_out + allocate]  ->
+// batch_keypoint_compact (coordinates and descriptors)  ->  the second wait, with the optional outputs.  Four launches, two waits;
+// the source is only read, its loop does not notice.
+//
 // Point-to-plane needs the model normals of every pair, in planes laid out as the models: given by the caller
 // (icp_batch_set_model_normals) or made on the device by ONE neighbour launch + ONE normals launch for the whole batch
 // (icp_batch_estimate_normals: knn4_batch + normals_batch_kernel, icp_k_plane.hip).  The reference estimates them once per
@@ -714,6 +722,134 @@ int remove_outliers(icp_batch* src, const std::vector<icp::OutlierRule>& rules, 
     return ICP_OK;
 }
 
+// the temporaries of one icp_batch_select_keypoints, released as VoxelTmp's are
+struct KeypointTmp {
+    hipStream_t st;
+    DevBuf clouds, items, rules, sal, map, count;
+    explicit KeypointTmp(hipStream_t s) : st(s) {}
+    ~KeypointTmp()
+    {
+        (void)hipStreamSynchronize(st);
+        for (DevBuf* d : {&clouds, &items, &rules, &sal, &map, &count}) d->release();
+    }
+};
+
+// icp_batch_select_keypoints after its argument checks; *made: the new batch as far as it got (the caller releases it on failure).
+// batch_iss_saliency  ->  batch_iss_select  ->  batch_keypoint_rank  ->  [D2H: 2 x count counts, the first wait; lay_out + allocate]
+// ->  batch_keypoint_compact  ->  the second wait, which brings the optional outputs.  Four launches, two waits; no output array is
+// written before the call can no longer be refused for its data.
+int select_keypoints(icp_batch* src, const std::vector<icp::KeypointRule>& rules, int32_t* moving_map_out, int32_t* model_map_out,
+                     double* moving_saliency_out, double* model_saliency_out, int32_t* count_out, icp_batch** made)
+{
+    icp_ctx* c = src->ctx;
+    hipStream_t st = c->stream;
+    const int count = src->count, n_clouds = 2 * count;
+    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
+    std::vector<icp::BatchItem> items, new_items;
+    std::vector<int32_t> kept((size_t)n_clouds), hmap;
+    std::vector<double> hsal;
+    long long tmp_plane = 0;
+    for (int k = 0; k < n_clouds; ++k) {
+        const int side = k < count ? 0 : 1;
+        const icp::BatchPair& pr = src->pairs[k - side * count];
+        icp::VoxelCloud& cl = clouds[k];
+        cl.side = side;
+        cl.n = side ? pr.m : pr.n;
+        cl.src_off = side ? pr.q_off : pr.p_off;
+        cl.tmp_off = tmp_plane;
+        cl.dst_off = 0;
+        tmp_plane += icp::round_up(cl.n, icp::BATCH_ALIGN);
+        for (int first = 0; first < cl.n; first += icp::BATCH_ITEM)
+            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, cl.n - first), 0});
+    }
+    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    KeypointTmp t(st);
+    HIP_TRY(t.clouds.ensure(clouds.size() * sizeof(icp::VoxelCloud)));
+    HIP_TRY(t.items.ensure(items.size() * sizeof(icp::BatchItem)));
+    HIP_TRY(t.rules.ensure(rules.size() * sizeof(icp::KeypointRule)));
+    HIP_TRY(t.sal.ensure((size_t)tmp_plane * sizeof(double)));
+    HIP_TRY(t.map.ensure((size_t)tmp_plane * sizeof(int32_t)));
+    HIP_TRY(t.count.ensure((size_t)n_clouds * sizeof(int32_t)));
+    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t.items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t.rules.p, rules.data(), rules.size() * sizeof(icp::KeypointRule), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(t.sal.p, 0, (size_t)tmp_plane * sizeof(double), st));   // (the padding between the clouds: never read, never random)
+    HIP_TRY(hipMemsetAsync(t.map.p, 0, (size_t)tmp_plane * sizeof(int32_t), st));
+    icp::BatchKeypointArgs a{};
+    a.precision = src->prec;
+    a.clouds = (const icp::VoxelCloud*)t.clouds.p;
+    a.n_clouds = n_clouds;
+    a.items = (const icp::BatchItem*)t.items.p;
+    a.n_items = (int)items.size();
+    a.rules = (const icp::KeypointRule*)t.rules.p;
+    a.src[0] = src->P0.p;
+    a.src[1] = src->Q.p;
+    a.src_plane[0] = src->p_plane;
+    a.src_plane[1] = src->q_plane;
+    a.tmp_plane = tmp_plane;
+    a.sal = (double*)t.sal.p;
+    a.map = (int32_t*)t.map.p;
+    a.count = (int32_t*)t.count.p;
+    HIP_TRY(icp::launch_batch_keypoint_select(a, st));
+    HIP_TRY(hipMemcpyAsync(kept.data(), t.count.p, kept.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the first wait: the new batch's layout needs every cloud's count
+    for (int p = 0; p < count; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const size_t k = (size_t)side * count + p;
+            const std::string where = std::string(": pair ") + std::to_string(p) + (side ? ", model" : ", moving cloud");
+            if (kept[k] < 1) return fail(ICP_ERR_EMPTY, "the rule keeps no point of the cloud" + where);
+            if (kept[k] > clouds[k].n) return fail(ICP_ERR_HIP, "icp_batch_select_keypoints: a cloud's kept count is out of range");   // (cannot happen)
+        }
+    std::vector<int64_t> moff((size_t)count + 1, 0), qoff((size_t)count + 1, 0);
+    for (int p = 0; p < count; ++p) {
+        moff[p + 1] = moff[p] + kept[p];
+        qoff[p + 1] = qoff[p] + kept[(size_t)count + p];
+    }
+    if (int rc = lay_out(c, count, src->prec, moff.data(), qoff.data(), made)) return rc;
+    icp_batch* nb = *made;
+    if (int rc = allocate(nb, new_items)) return rc;
+    for (int k = 0; k < n_clouds; ++k) clouds[k].dst_off = k < count ? nb->pairs[k].p_off : nb->pairs[k - count].q_off;
+    const size_t pb = 3 * (size_t)nb->p_plane * nb->esize, qb = 3 * (size_t)nb->q_plane * nb->esize;
+    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(nb->P0.p, 0, pb, st));   // (the padding between the clouds: all-zero bytes, as an upload leaves it)
+    HIP_TRY(hipMemsetAsync(nb->Q.p, 0, qb, st));
+    a.dst[0] = nb->P0.p;
+    a.dst[1] = nb->Q.p;
+    a.dst_plane[0] = nb->p_plane;
+    a.dst_plane[1] = nb->q_plane;
+    for (int sd = 0; sd < 2; ++sd) {   // the descriptors of the kept points, where the source holds that side's
+        if (!src->have_feat[sd]) continue;
+        const size_t fb = ICP_FEATURE_BINS * (size_t)(sd ? nb->q_plane : nb->p_plane) * sizeof(double);
+        HIP_TRY(nb->feat[sd].ensure(fb));
+        HIP_TRY(hipMemsetAsync(nb->feat[sd].p, 0, fb, st));   // (the padding, as icp_batch_compute_features leaves it)
+        a.src_feat[sd] = (const unsigned long long*)src->feat[sd].p;
+        a.dst_feat[sd] = (unsigned long long*)nb->feat[sd].p;
+    }
+    HIP_TRY(icp::launch_batch_keypoint_compact(a, st));
+    HIP_TRY(hipMemcpyAsync(nb->P.p, nb->P0.p, pb, hipMemcpyDeviceToDevice, st));
+    if (moving_map_out || model_map_out) {
+        hmap.resize((size_t)tmp_plane);
+        HIP_TRY(hipMemcpyAsync(hmap.data(), t.map.p, hmap.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    if (moving_saliency_out || model_saliency_out) {
+        hsal.resize((size_t)tmp_plane);
+        HIP_TRY(hipMemcpyAsync(hsal.data(), t.sal.p, hsal.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // the second wait: the host vectors go, the temporaries are freed
+    nb->have_feat[0] = src->have_feat[0];
+    nb->have_feat[1] = src->have_feat[1];
+    for (int p = 0; p < count; ++p) {
+        const size_t np = (size_t)src->pairs[p].n, mp = (size_t)src->pairs[p].m;
+        const long long to = clouds[p].tmp_off, tq = clouds[(size_t)count + p].tmp_off;
+        if (moving_map_out) std::memcpy(moving_map_out + src->moff[p], hmap.data() + to, np * sizeof(int32_t));
+        if (model_map_out) std::memcpy(model_map_out + src->qoff[p], hmap.data() + tq, mp * sizeof(int32_t));
+        if (moving_saliency_out) std::memcpy(moving_saliency_out + src->moff[p], hsal.data() + to, np * sizeof(double));
+        if (model_saliency_out) std::memcpy(model_saliency_out + src->qoff[p], hsal.data() + tq, mp * sizeof(double));
+    }
+    if (count_out) std::memcpy(count_out, kept.data(), kept.size() * sizeof(int32_t));
+    return ICP_OK;
+}
+
 // T of pair `pair` as icp_batch_state reports it: the loop's T, times the initial transform as rounded to the batch's precision
 // where the pair has one (T = T_loop . T0F, the product in HostLoop::note_applied's order)
 void composed_T(const icp_batch* b, int pair, double* T16)
@@ -958,6 +1094,44 @@ int icp_batch_remove_outliers(icp_batch* src, const icp_outlier_rule* moving, co
     ScopedPin pin(src->ctx);
     icp_batch* made = nullptr;
     const int rc = remove_outliers(src, rules, moving_map_out, model_map_out, moving_score_out, model_score_out, stats_out, &made);
+    if (rc != ICP_OK) {   // src was only read; what the call enqueued ends before its host vectors and the new batch go
+        (void)hipStreamSynchronize(src->ctx->stream);
+        (void)hipGetLastError();
+        if (made) release(made);
+        return rc;
+    }
+    *out = made;
+    return ICP_OK;
+}
+
+int icp_batch_select_keypoints(icp_batch* src, const icp_keypoint_rule* moving, const icp_keypoint_rule* model, int32_t* moving_map_out,
+                               int32_t* model_map_out, double* moving_saliency_out, double* model_saliency_out, int32_t* count_out,
+                               icp_batch** out)
+{
+    if (!out) return fail(ICP_ERR_INVALID, "out == NULL");
+    *out = nullptr;
+    if (int rc = ready(src)) return rc;
+    static_assert(sizeof(icp::KeypointRule) == sizeof(icp_keypoint_rule) && sizeof(icp_keypoint_rule) == 40, "the kernels read the caller's rules");
+    std::vector<icp::KeypointRule> rules(2 * (size_t)src->count, icp::KeypointRule{ICP_KEYPOINT_NONE, 0, 0.0, 0.0, 0.0, 0.0});   // the moving clouds', then the models'
+    for (int p = 0; p < src->count; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const icp_keypoint_rule* given = side ? model : moving;
+            if (!given) continue;
+            const icp_keypoint_rule& r = given[p];
+            const std::string where = std::string(": pair ") + std::to_string(p) + (side ? ", model" : ", moving cloud");
+            if (r.kind == ICP_KEYPOINT_NONE) continue;
+            if (r.kind != ICP_KEYPOINT_ISS) return fail(ICP_ERR_INVALID, "unknown keypoint rule kind" + where);
+            if (r.min_neighbours < 1 || r.min_neighbours > 65535)
+                return fail(ICP_ERR_INVALID, "a keypoint rule's least number of neighbours must lie in [1, 65535]" + where);
+            if (!(std::isfinite(r.salient_radius) && r.salient_radius > 0.0) || !(std::isfinite(r.non_max_radius) && r.non_max_radius > 0.0))   // (NaN fails both)
+                return fail(ICP_ERR_INVALID, "a radius must be finite and > 0" + where);
+            if (!(std::isfinite(r.gamma_21) && r.gamma_21 > 0.0) || !(std::isfinite(r.gamma_32) && r.gamma_32 > 0.0))
+                return fail(ICP_ERR_INVALID, "a gamma must be finite and > 0" + where);
+            rules[(size_t)side * src->count + p] = icp::KeypointRule{r.kind, r.min_neighbours, r.salient_radius, r.non_max_radius, r.gamma_21, r.gamma_32};
+        }
+    ScopedPin pin(src->ctx);
+    icp_batch* made = nullptr;
+    const int rc = select_keypoints(src, rules, moving_map_out, model_map_out, moving_saliency_out, model_saliency_out, count_out, &made);
     if (rc != ICP_OK) {   // src was only read; what the call enqueued ends before its host vectors and the new batch go
         (void)hipStreamSynchronize(src->ctx->stream);
         (void)hipGetLastError();

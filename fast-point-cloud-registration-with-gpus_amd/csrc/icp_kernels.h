@@ -595,6 +595,34 @@ struct BatchFgrArgs {
 };
 hipError_t launch_batch_fgr_terms(const BatchFgrArgs& a, hipStream_t st);
 hipError_t launch_batch_fgr_weights(const BatchFgrArgs& a, hipStream_t st);
+// keypoint selection of every cloud of a batch (icp_batch_select_keypoints; the rule: include/icp_mi355x.h; icp_k_keypoint.hip).
+// The clouds, their numbering, their stretches of the per-point temporaries and the work items are the outlier call's (VoxelCloud,
+// BatchItem::pair = the cloud's number).  rules[c] is the caller's icp_keypoint_rule of cloud c.
+struct KeypointRule { int kind, min_neighbours; double salient_radius, non_max_radius, gamma_21, gamma_32; };   // (the layout of icp_keypoint_rule)
+struct BatchKeypointArgs {
+    int precision;             // ICP_F32 / ICP_F64
+    const VoxelCloud* clouds;  // [2 * n_pairs]
+    int n_clouds;
+    const BatchItem* items;    // the work items of all clouds, in cloud order
+    int n_items;
+    const KeypointRule* rules; // [n_clouds]
+    const void* src[2];        // P0 and Q of the source batch (read only)
+    long long src_plane[2];
+    long long tmp_plane;       // elements of every per-point temporary
+    double* sal;               // [tmp]: sal_i, 0.0 for a copied cloud
+    int32_t* map;              // [tmp]: the index of a kept point in its new cloud, -1 for a dropped one (between the launches: the flag)
+    int32_t* count;            // int32[n_clouds]: kept points
+    void* dst[2];              // P0 and Q of the new batch (the compaction)
+    long long dst_plane[2];
+    const unsigned long long* src_feat[2];   // the source's descriptors of that side as 64-bit words ([src_plane][ICP_FEATURE_BINS]), or NULL: it holds none
+    unsigned long long* dst_feat[2];         // the new batch's, laid out by dst_off (read where src_feat is not NULL)
+};
+// batch_iss_saliency + batch_iss_select (one block of NN_BLOCK threads per work item: sal, then the flags) -> batch_keypoint_rank
+// (one block per cloud: map, count).  Three launches; dst and the descriptors are not read.
+hipError_t launch_batch_keypoint_select(const BatchKeypointArgs& a, hipStream_t st);
+// batch_keypoint_compact: a kept point's coordinates to dst[side][k * dst_plane + dst_off + map[i]], its descriptor to
+// dst_feat[side][(dst_off + map[i]) * ICP_FEATURE_BINS ..].  One launch.
+hipError_t launch_batch_keypoint_compact(const BatchKeypointArgs& a, hipStream_t st);
 
 // soa2 (optional): a second copy of the result (the pristine moving cloud); enc (optional, fp32): the cloud's bounding cube as six
 // ordered-integer words {~ord(min xyz), ord(max xyz)}, zero before the launch

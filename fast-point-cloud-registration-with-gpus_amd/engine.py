@@ -392,9 +392,13 @@ class Context:
         The same list of Result, with extra["global"] added: the dict Batch.ransac returned for the pair.
         method="fgr" (the default is "ransac") runs Batch.fgr in RANSAC's place: hypotheses is read as tuples (0: every
         correspondence) and max_distance as delta; the options iterations, division_factor, decrease_every and tuple_similarity are
-        handed on where given, seed too; extra["global"] is then the dict Batch.fgr returned."""
+        handed on where given, seed too; extra["global"] is then the dict Batch.fgr returned.
+        keypoints=rule (Batch.keypoints' rule, one for all pairs or one per pair; the default is None) matches and solves on the
+        ISS keypoints of the thinned clouds alone: the descriptors are computed on the whole thinned clouds as before, then
+        Batch.keypoints(moving=rule, model=rule) keeps the salient points with their descriptors, and matching and RANSAC or FGR
+        run on that batch; extra["global"] gains "keypoints": (n_kept, m_kept)."""
         known = {"viewpoint", "edge_similarity", "seed", "mutual", "gate", "metric", "normals", "max_iter", "tol", "fixed_iterations", "trim", "reciprocal",
-                 "method", "iterations", "division_factor", "decrease_every", "tuple_similarity"}
+                 "method", "iterations", "division_factor", "decrease_every", "tuple_similarity", "keypoints"}
         unknown = set(options) - known
         if unknown:
             raise TypeError(f"register_batch_global: unknown option(s) {sorted(unknown)}")
@@ -413,12 +417,23 @@ class Context:
                 nm = [oriented_normals(D, c, eye(D)) for (D, _), c in zip(clouds, cm)]
                 nq = [oriented_normals(M, c, eye(M)) for (_, M), c in zip(clouds, cq)]
                 bt.compute_features(k, (nm, nq))
-                bt.match_features(mutual=options.get("mutual", True))
-                if method == "fgr":
-                    more = {o: options[o] for o in ("iterations", "division_factor", "decrease_every", "tuple_similarity") if o in options}
-                    start = bt.fgr(max_distance, tuples=hypotheses, seed=options.get("seed", 0), **more)
-                else:
-                    start = bt.ransac(hypotheses, max_distance, edge_similarity=options.get("edge_similarity", 0.9), seed=options.get("seed", 0))
+                kb, kept = bt, None
+                if options.get("keypoints") is not None:   # match and solve on the salient points alone, with their descriptors
+                    kb, info = bt.keypoints(moving=options["keypoints"], model=options["keypoints"])
+                    kept = [(int(info["counts"][b]), int(info["counts"][bt.count + b])) for b in range(bt.count)]
+                try:
+                    kb.match_features(mutual=options.get("mutual", True))
+                    if method == "fgr":
+                        more = {o: options[o] for o in ("iterations", "division_factor", "decrease_every", "tuple_similarity") if o in options}
+                        start = kb.fgr(max_distance, tuples=hypotheses, seed=options.get("seed", 0), **more)
+                    else:
+                        start = kb.ransac(hypotheses, max_distance, edge_similarity=options.get("edge_similarity", 0.9), seed=options.get("seed", 0))
+                finally:
+                    if kb is not bt:
+                        kb.close()
+                if kept is not None:
+                    for r, c in zip(start, kept):
+                        r["keypoints"] = c
             finally:
                 if bt is not full:
                     bt.close()
@@ -801,6 +816,66 @@ class Batch:
             info["moving_map"], info["model_map"] = per_moving(mm), per_model(qm)
         if want_scores:
             info["moving_score"], info["model_score"] = per_moving(ms), per_model(qs)
+        return out, info
+
+    def _keypoint_rules(self, rules, what):
+        """one rule or one per pair -> a ctypes array of count icp_keypoint_rule (None: NULL, copy that side).  A rule is a tuple
+        (salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbours=5) or a dict of those names; None copies"""
+        if rules is None:
+            return None
+        one = isinstance(rules, dict) or (isinstance(rules, tuple) and len(rules) > 0 and np.isscalar(rules[0]))
+        rules = [rules] * self.count if one else list(rules)
+        if len(rules) != self.count:
+            raise ValueError(f"one {what} keypoint rule per pair (or a single rule)")
+        names = ("salient_radius", "non_max_radius", "gamma_21", "gamma_32", "min_neighbours")
+        arr = (capi.icp_keypoint_rule * self.count)()
+        for b, r in enumerate(rules):
+            if r is None:
+                arr[b] = capi.icp_keypoint_rule(capi.ICP_KEYPOINT_NONE, 0, 0.0, 0.0, 0.0, 0.0)
+                continue
+            if isinstance(r, dict):
+                unknown = set(r) - set(names)
+                if unknown or "salient_radius" not in r or "non_max_radius" not in r:
+                    raise ValueError(f"a keypoint rule needs salient_radius and non_max_radius, and may hold {names[2:]}")
+                r = tuple(r[k] for k in names[:2]) + tuple(r.get(k, d) for k, d in zip(names[2:], (0.975, 0.975, 5)))
+            r = tuple(r)
+            if not 2 <= len(r) <= 5:
+                raise ValueError("a keypoint rule is (salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbours=5)")
+            r = r + (0.975, 0.975, 5)[len(r) - 2:]
+            arr[b] = capi.icp_keypoint_rule(capi.ICP_KEYPOINT_ISS, int(r[4]), float(r[0]), float(r[1]), float(r[2]), float(r[3]))
+        return arr
+
+    def keypoints(self, moving=None, model=None, want_maps=False, want_saliency=False):
+        """a new Batch on the same context whose clouds are the ISS keypoints of this batch's clouds as uploaded, made on the
+        device (icp_batch_select_keypoints; the rule is stated in include/icp_mi355x.h).  moving, model: one rule or one per pair
+        -- (salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbours=5) or a dict of those names: a point's
+        saliency is the smallest eigenvalue of the covariance of the points within salient_radius, where the eigenvalue ratios are
+        below the gammas and at least min_neighbours points lie within; it is kept iff no point within non_max_radius has a
+        higher saliency; None: copy.  Kept points are copied, in the source order.  Where this batch holds descriptors
+        (compute_features) the new one holds those of the kept points, so match_features, ransac and fgr run on it as they
+        are.  This batch is only read, and its loop does not notice.  Returns (Batch, info): info["counts"] is a (2 * count,) int32
+        array of the kept points, the moving clouds first; want_maps adds "moving_map" and "model_map" (per pair, int32: the new
+        index of a kept point, -1 for a dropped one), want_saliency "moving_saliency" and "model_saliency" (per pair, float64)."""
+        rm, rq = self._keypoint_rules(moving, "moving"), self._keypoint_rules(model, "model")
+        pd, p32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        n, m = int(self._moff[-1]), int(self._qoff[-1])
+        mm = np.empty(n, dtype=np.int32) if want_maps else None
+        qm = np.empty(m, dtype=np.int32) if want_maps else None
+        ms = np.empty(n, dtype=np.float64) if want_saliency else None
+        qs = np.empty(m, dtype=np.float64) if want_saliency else None
+        counts = np.empty(2 * self.count, dtype=np.int32)
+        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        h = C.c_void_p()
+        capi.check(self._lib.icp_batch_select_keypoints(self._h, rm, rq, ptr(mm, p32), ptr(qm, p32), ptr(ms, pd), ptr(qs, pd), ptr(counts, p32),
+                                                        C.byref(h)), "icp_batch_select_keypoints")
+        out = Batch._from_handle(self._ctx, h, self.count, self._dtype)
+        info = {"counts": counts}
+        per_model = lambda a: [a[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
+        per_moving = lambda a: [a[self._moff[b]:self._moff[b + 1]].copy() for b in range(self.count)]
+        if want_maps:
+            info["moving_map"], info["model_map"] = per_moving(mm), per_model(qm)
+        if want_saliency:
+            info["moving_saliency"], info["model_saliency"] = per_moving(ms), per_model(qs)
         return out, info
 
     def get_clouds(self):

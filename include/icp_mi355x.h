@@ -675,6 +675,60 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *         ICP_ERR_STATE without matches or with a pending pass on the context; ICP_ERR_INVALID for a null batch, null parameters,
  *         null seeds with tuples > 0 or a value out of range; a refused call leaves the batch as it was.  The loop does not notice:
  *         the call reads P0 and Q, never the moved cloud, and neither discards nor advances a registration under way.
+ *       keypoints (icp_batch_select_keypoints): the descriptor scan of icp_batch_match_features grows with the product of both cloud
+ *         sizes; the answer (Open3D's, too) is to describe the whole cloud but to match only its salient points, chosen by ISS
+ *         (Intrinsic Shape Signatures; Zhong, ICCV Workshops 2009; Open3D's compute_iss_keypoints).  The call makes a new batch
+ *         on the device from the clouds a batch already holds -- same context, same count, same precision, every cloud reduced
+ *         to its keypoints -- and carries the descriptors of the kept points along.  Each cloud has a rule of its own
+ *         (icp_keypoint_rule).  Where the two overlap the call behaves as icp_batch_remove_outliers.
+ *           inputs: moving and model hold count rules each; a NULL array copies that side; kind ICP_KEYPOINT_NONE copies the
+ *             cloud, its bytes and its order.  ICP_KEYPOINT_ISS reads salient_radius, non_max_radius, gamma_21, gamma_32 and
+ *             min_neighbours.
+ *           source: P0 and Q, the clouds as uploaded or as made by an earlier call -- never the moved cloud.  The options, the
+ *             normals and the loop of src are not read.  The loop does not notice.
+ *           the rule for point i of a cloud, reproducible bit for bit in numpy (tests/batch_keypoint_ref.py does).  Every operation
+ *             is one IEEE operation, nothing is fused, nothing is multiplied by a reciprocal, and the only functions used are
+ *             + - * / sqrt fabs copysign.
+ *               distance: d2(i, j) is the matching's squared distance (dx*dx + dy*dy) + dz*dz in the batch's precision F;
+ *                 ts = (F)(salient_radius * salient_radius) and tn = (F)(non_max_radius * non_max_radius), each product formed in
+ *                 double and rounded once (the gate's rule).
+ *               salient neighbourhood: every j of the cloud with d2(i, j) <= ts, i itself included at distance 0; c is its size.
+ *                 A point exactly on the radius is in.
+ *               sums: the covariance rule's statements -- in double, from 0.0, over the neighbourhood in ascending j:
+ *                 e = (double)x_j - (double)x_i, s_a += e_a, S_ab += e_a * e_b for the six a <= b;
+ *                 C_ab = (S_ab - (s_a * s_b) / (double)c) / (double)c.
+ *               eigenvalues: icp_eigh3's statements (below) on the symmetric matrix built from C -- cyclic Jacobi over (0,1),
+ *                 (0,2), (1,2); at most 64 sweeps; the stop test off <= 1e-34 * dia || off == 0.0; the same theta, t, c, s and
+ *                 update statements; the same ascending order w0 <= w1 <= w2.  The eigenvectors are not formed: the eigenvalues do
+ *                 not depend on them.
+ *               saliency: sal_i = w0 iff c >= min_neighbours && (w1 / w2) < gamma_21 && (w0 / w1) < gamma_32 && w0 > 0, else
+ *                 sal_i is exactly 0.0.  A NaN fails every comparison.  The divisions are Open3D's.
+ *               selection: M_i is every j with d2(i, j) <= tn, i included.  i is a keypoint iff sal_i > 0 &&
+ *                 |M_i| >= min_neighbours && sal_j <= sal_i for every j in M_i.  Equal saliencies keep each other, as Open3D's
+ *                 IsLocalMaxima does: coincident points are kept or dropped together.
+ *           output cloud: the keypoints, copied, not computed, in the source order: a -0.0 survives.
+ *           outputs, all optional (NULL: not wanted): the maps hold one int32 per source point in src's layout -- the index of a
+ *             kept point within its new cloud, -1 for a dropped point, 0 .. n-1 for a copied cloud.  The saliencies hold one
+ *             double per source point, sal_i for kept and dropped points alike; 0.0 for a copied cloud.  count_out holds the
+ *             kept points of every cloud, the moving clouds first (2 * count int32).
+ *           refusals: on any refusal *out is NULL, nothing of src changes and no output array is written; where a pair is at
+ *             fault the message names the first offending pair and the side.  ICP_ERR_INVALID: a null src or a null out; an
+ *             unknown kind; min_neighbours outside [1, 65535]; a radius that is not finite or not > 0; a gamma that is not
+ *             finite or not > 0.  ICP_ERR_STATE: a pass pending on the context.  ICP_ERR_EMPTY: a cloud would keep no point
+ *             (known at the first host wait, before the new batch exists).
+ *           independence: a cloud's outputs depend on that cloud and its rule alone -- not on the other pairs, their order or
+ *             the batch size.
+ *           new batch: *out is a complete batch, as if icp_batch_create had been called with the output clouds: no options, no
+ *             normals, no loop under way, no matches.  Descriptors: where src holds descriptors on a side
+ *             (icp_batch_compute_features), the new batch holds the descriptors of the kept points of that side, copied on the
+ *             device byte for byte, in the kept order; icp_batch_match_features, icp_batch_ransac, icp_batch_fgr and
+ *             icp_batch_get_features work on it unchanged.  A side of src without descriptors gives a side without.
+ *           cost: four launches (batch_iss_saliency and batch_iss_select, one block per 64 points: the sums in one pass over the
+ *             cloud by one wave, then the neighbourhood count and the comparison by four; batch_keypoint_rank, one block per
+ *             cloud: maps and counts; batch_keypoint_compact: coordinates and descriptors into the new batch) and two host waits:
+ *             one for the kept count of every cloud, which the new batch's layout needs, one at the end with the optional
+ *             outputs.  Both scans are brute force, n^2 distances per cloud.  LDS per block: 24 KiB (saliency), 42 KiB in fp32
+ *             and 34 KiB in fp64 (selection), 16 bytes (rank), none (compaction).  No atomics.
  *   - the colored metric (ICP_COLORED; Park, Zhou, Koltun, ICCV 2017; Open3D's registration_colored_icp): a flat or gently curved
  *     textured surface leaves geometry alone three unknowns free; a scalar intensity per point (a reflectivity, the mean of an
  *     RGB colour) fixes them.  Every kept match pulls with two residuals, the point-to-plane distance weighed by lambda and the
@@ -858,6 +912,17 @@ typedef struct icp_fgr_params {
 int icp_batch_fgr(icp_batch* b, const icp_fgr_params* prm, const uint64_t* seed /* count; may be NULL iff tuples == 0 */,
                   double* T16_out, double* weights_out /* 1 per moving point */, int32_t* used_out /* 1 per pair */,
                   double* objective_out /* 1 per pair */, int* status_out);
+/* a new batch on src's context: same count and precision, every pair's clouds reduced to their keypoints, with the descriptors
+ * of the kept points where src holds descriptors (the rule: above) */
+#define ICP_KEYPOINT_NONE 0   /* copy the cloud: its bytes, its order */
+#define ICP_KEYPOINT_ISS  1
+typedef struct icp_keypoint_rule { int kind; int min_neighbours; double salient_radius; double non_max_radius; double gamma_21; double gamma_32; } icp_keypoint_rule;   /* 40 bytes */
+int icp_batch_select_keypoints(icp_batch* src,
+        const icp_keypoint_rule* moving, const icp_keypoint_rule* model,   /* count each; NULL = copy that side */
+        int32_t* moving_map_out, int32_t* model_map_out,                   /* 1 per source point, src's layout; may be NULL */
+        double* moving_saliency_out, double* model_saliency_out,           /* 1 per source point; may be NULL */
+        int32_t* count_out,                                                /* 2 * count, moving clouds first; may be NULL */
+        icp_batch** out);
 /* one call: create + begin + run to the end + results, then destroy.  Every output pointer may be NULL; per pair:
  * T16_out 16, iterations_out / passes_out / status_out 1, err_out max_iter+1 doubles; idx_out and moved_out (3 values per
  * point, precision of the run) concatenated as the moving clouds.  A failed pair is reported in status_out, not in the
