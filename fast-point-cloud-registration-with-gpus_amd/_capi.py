@@ -35,6 +35,7 @@ ICP_BATCH_MAX_POINTS = 65536   # per cloud of one pair of a batch
 ICP_OUTLIER_NONE, ICP_OUTLIER_STATISTICAL, ICP_OUTLIER_RADIUS = 0, 1, 2   # icp_outlier_rule.kind
 ICP_OUTLIER_MAX_NEIGHBOURS = 32
 ICP_KEYPOINT_NONE, ICP_KEYPOINT_ISS = 0, 1   # icp_keypoint_rule.kind
+ICP_ORIENT_NONE, ICP_ORIENT_VIEWPOINT, ICP_ORIENT_CENTROID = 0, 1, 2   # icp_batch_estimate_point_normals: the orientation
 # icp_diag_loop_moments: how the vector came about (include/icp_mi355x_diag.h)
 ROUTE_HOST_ROWS, ROUTE_COMPACT, ROUTE_AVX, ROUTE_FIN_LAUNCH, ROUTE_FIN_PINNED, ROUTE_FIN_KERNEL = 0x001, 0x002, 0x004, 0x008, 0x010, 0x020
 ROUTE_FIN_TWO_STAGE, ROUTE_FUSED_TAIL, ROUTE_MOMENTS_KERNEL, ROUTE_ERROR_ONLY, ROUTE_ARMED, ROUTE_RESIDENT = 0x040, 0x080, 0x100, 0x200, 0x400, 0x800
@@ -153,6 +154,10 @@ SIGNATURES = {
     "icp_batch_get_intensity_gradients": (_i, [_vp, _pd]),
     "icp_batch_set_color_weight": (_i, [_vp, _pd]),
     "icp_batch_compute_features": (_i, [_vp, _pi, _pi, _pd, _pd, _pd, _pd]),
+    "icp_batch_estimate_point_normals": (_i, [_vp, _i, _pd, _pd, _pd, _pd]),
+    "icp_batch_set_point_normals": (_i, [_vp, _pd, _pd]),
+    "icp_batch_get_point_normals": (_i, [_vp, _pd, _pd]),
+    "icp_batch_compute_features_stored": (_i, [_vp, _pi, _pi, _pd, _pd]),
     "icp_batch_get_features": (_i, [_vp, _pd, _pd]),
     "icp_batch_match_features": (_i, [_vp, _i, _pi32, _pi32, C.POINTER(C.c_uint8)]),
     "icp_batch_score_transforms": (_i, [_vp, _i, _pd, _pd, _pi32]),
@@ -189,6 +194,7 @@ SIGNATURES = {
     "icp_diag_batch_ransac": (_i, [_vp, _i, _pi32, C.POINTER(C.c_uint8), _pd, _pi32]),
     "icp_diag_batch_fgr": (_i, [_vp, _i, _pi32, _pd, _pd, _pd]),
     "icp_diag_batch_fgr_times": (_i, [_vp, _pd]),
+    "icp_diag_batch_centroids": (_i, [_vp, _pd]),
     "icp_solve_rigid": (_i, [_pd, _pd, _pd]),
     "icp_eigh3": (_i, [_pd, _pd, _pd]),
     "icp_synthetic_grid_f32": (_i, [_i, C.c_float, C.c_float, _vp]),

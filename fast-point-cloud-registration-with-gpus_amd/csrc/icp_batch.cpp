@@ -106,6 +106,11 @@
 // batch_keypoint_compact (coordinates and descriptors)  ->  the second wait, with the optional outputs.  Four launches, two waits;
 // the source is only read, its loop does not notice.
 //
+// The normals the descriptors are computed from are made on the device from the covariances the batch holds and kept there
+// (icp_batch_estimate_point_normals; kernels: icp_k_normals.hip): [batch_centroid_kernel, ICP_ORIENT_CENTROID only]  ->
+// batch_point_normals_kernel  ->  [D2H + one wait, only where an output is wanted].  icp_batch_compute_features_stored then
+// describes from them: icp_batch_compute_features' host body without the upload.  The loop does not notice either call.
+//
 // Point-to-plane needs the model normals of every pair, in planes laid out as the models: given by the caller
 // (icp_batch_set_model_normals) or made on the device by ONE neighbour launch + ONE normals launch for the whole batch
 // (icp_batch_estimate_normals: knn4_batch + normals_batch_kernel, icp_k_plane.hip).  The reference estimates them once per
@@ -197,6 +202,15 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     // global registration (icp_batch_compute_features, _match_features, _score_transforms, _ransac)
     DevBuf feat[2];                          // every point's descriptor, moving clouds / models: ICP_FEATURE_BINS doubles at (the cloud's offset + i) * ICP_FEATURE_BINS
     bool have_feat[2] = {false, false};
+    DevBuf pnrm[2];                          // the point normals the descriptors are computed from, moving clouds / models: 3 planes of doubles, laid out as the clouds (not the model normals N of point-to-plane)
+    bool have_pnrm[2] = {false, false};      // that side holds point normals (icp_batch_estimate_point_normals, icp_batch_set_point_normals)
+    DevBuf nrm_args, nrm_view, nrm_cent;     // icp_batch_estimate_point_normals: the 2 * count clouds and their work items (made once: the layout never changes); 3 doubles per cloud, the viewpoints of the latest call and the centroids of the latest ICP_ORIENT_CENTROID call
+    void* h_nrm_args = nullptr;              // pinned: what nrm_args was copied from
+    double* h_nrm_view = nullptr;            // pinned: what nrm_view is copied from (a call waits for nothing unless it wants an output)
+    size_t nrm_off_items = 0;                // where the items start in nrm_args
+    int n_nrm_items = 0;                     // 0: nrm_args is not made yet
+    hipEvent_t nrm_ev = nullptr;             // recorded behind the latest upload of the viewpoints: the next call waits for it before it rewrites h_nrm_view
+    bool have_cent = false;                  // nrm_cent holds the centroids of an ICP_ORIENT_CENTROID call
     DevBuf f_fwd, f_rev, f_kept;             // the matches: fwd and kept laid out as idx, rev as the models
     DevBuf f_ci, f_cj, f_cn;                 // every pair's correspondence list (moving index, model index: int32 at p_off + e) and its length (int per pair)
     bool have_match = false;
@@ -256,11 +270,15 @@ void release(icp_batch* b)
 {
     for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag,
                       &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->rob_kind, &b->rob_k, &b->rob_k2, &b->weights, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom, &b->cov[0], &b->cov[1], &b->cov_args, &b->inten[0], &b->inten[1], &b->grad, &b->grad_k, &b->color_w,
+                      &b->pnrm[0], &b->pnrm[1], &b->nrm_args, &b->nrm_view, &b->nrm_cent,
                       &b->feat[0], &b->feat[1], &b->f_fwd, &b->f_rev, &b->f_kept, &b->f_ci, &b->f_cj, &b->f_cn, &b->s_cand, &b->s_valid, &b->s_thr, &b->s_counts,
                       &b->g_ui, &b->g_uj, &b->g_items, &b->g_item0, &b->g_ctl, &b->g_partials, &b->g_mom, &b->g_w})
         d->release();
     if (b->cov_ev) (void)hipEventDestroy(b->cov_ev);
     if (b->grad_ev) (void)hipEventDestroy(b->grad_ev);
+    if (b->nrm_ev) (void)hipEventDestroy(b->nrm_ev);
+    if (b->h_nrm_args) (void)hipHostFree(b->h_nrm_args);
+    if (b->h_nrm_view) (void)hipHostFree(b->h_nrm_view);
     if (b->h_grad_k) (void)hipHostFree(b->h_grad_k);
     if (b->h_cov_args) (void)hipHostFree(b->h_cov_args);
     if (b->h_eval) (void)hipHostFree(b->h_eval);
@@ -2310,15 +2328,24 @@ bool finite16(const icp_batch* b, const double* T)
 }  // namespace
 }  // extern "C++" (the templates above)
 
-int icp_batch_compute_features(icp_batch* b, const int* k_moving, const int* k_model, const double* moving_normals,
-                               const double* model_normals, double* moving_feat_out, double* model_feat_out)
+namespace {
+
+// the one host body of icp_batch_compute_features (stored == false: the caller's normals, checked and uploaded) and of
+// icp_batch_compute_features_stored (stored == true: the point normals the batch holds; moving_normals and model_normals are not read)
+int compute_features(icp_batch* b, bool stored, const int* k_moving, const int* k_model, const double* moving_normals,
+                     const double* model_normals, double* moving_feat_out, double* model_feat_out)
 {
     if (int rc = ready(b)) return rc;
     const int* ks_given[2] = {k_moving, k_model};
     const double* nrm_given[2] = {moving_normals, model_normals};
     for (int sd = 0; sd < 2; ++sd) {
         if (!ks_given[sd]) return fail(ICP_ERR_INVALID, std::string("descriptors need a k for both sides: ") + (sd ? "k_model" : "k_moving") + " == NULL");
-        if (!nrm_given[sd]) return fail(ICP_ERR_INVALID, std::string("descriptors need normals on both sides: ") + (sd ? "model_normals" : "moving_normals") + " == NULL");
+        if (stored) {
+            if (!b->have_pnrm[sd])
+                return fail(ICP_ERR_STATE, std::string("the batch holds no point normals of the ") + (sd ? "models" : "moving clouds") +
+                                               " (icp_batch_estimate_point_normals or icp_batch_set_point_normals first)");
+        } else if (!nrm_given[sd])
+            return fail(ICP_ERR_INVALID, std::string("descriptors need normals on both sides: ") + (sd ? "model_normals" : "moving_normals") + " == NULL");
     }
     const int count = b->count, n_clouds = 2 * count;
     std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
@@ -2336,7 +2363,7 @@ int icp_batch_compute_features(icp_batch* b, const int* k_moving, const int* k_m
         if (clouds[k].n < kk + 1)
             return fail(ICP_ERR_INVALID, "descriptors from k neighbours need a cloud of at least k + 1 points: pair " + std::to_string(p) + side_name(sd));
         const int64_t* off = sd ? b->qoff.data() : b->moff.data();
-        for (int64_t i = 3 * off[p]; i < 3 * off[p + 1]; ++i)
+        for (int64_t i = 3 * off[p]; !stored && i < 3 * off[p + 1]; ++i)
             if (!std::isfinite(nrm_given[sd][i]))
                 return fail(ICP_ERR_INVALID, "a normal has a NaN or an infinite value: pair " + std::to_string(p) + side_name(sd));
         ks[k] = kk;
@@ -2366,18 +2393,18 @@ int icp_batch_compute_features(icp_batch* b, const int* k_moving, const int* k_m
     std::vector<double> hn[2];
     for (int sd = 0; sd < 2; ++sd) {
         const size_t plane = (size_t)(sd ? b->q_plane : b->p_plane);
-        HIP_TRY(tmp.nrm[sd].ensure(3 * plane * sizeof(double)));
+        if (!stored) HIP_TRY(tmp.nrm[sd].ensure(3 * plane * sizeof(double)));
         HIP_TRY(tmp.tau[sd].ensure(plane * b->esize));
         HIP_TRY(tmp.spfh[sd].ensure(ICP_FEATURE_BINS * plane * sizeof(double)));
         HIP_TRY(b->feat[sd].ensure(ICP_FEATURE_BINS * plane * sizeof(double)));
-        normals_to_planes(nrm_given[sd], ::side(b, sd != 0), hn[sd]);
+        if (!stored) normals_to_planes(nrm_given[sd], ::side(b, sd != 0), hn[sd]);
     }
     b->have_feat[0] = b->have_feat[1] = false;
     b->have_match = false;   // (matches of other descriptors)
     HIP_TRY(hipMemcpyAsync(tmp.args.p, hs.data(), arg_bytes, hipMemcpyHostToDevice, st));
     for (int sd = 0; sd < 2; ++sd) {
         const size_t plane = (size_t)(sd ? b->q_plane : b->p_plane);
-        HIP_TRY(hipMemcpyAsync(tmp.nrm[sd].p, hn[sd].data(), hn[sd].size() * sizeof(double), hipMemcpyHostToDevice, st));
+        if (!stored) HIP_TRY(hipMemcpyAsync(tmp.nrm[sd].p, hn[sd].data(), hn[sd].size() * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(tmp.spfh[sd].p, 0, ICP_FEATURE_BINS * plane * sizeof(double), st));   // (the padding between the clouds: never read, never random)
         HIP_TRY(hipMemsetAsync(b->feat[sd].p, 0, ICP_FEATURE_BINS * plane * sizeof(double), st));
         HIP_TRY(hipMemsetAsync(tmp.tau[sd].p, 0, plane * b->esize, st));
@@ -2395,7 +2422,7 @@ int icp_batch_compute_features(icp_batch* b, const int* k_moving, const int* k_m
     a.src_plane[0] = b->p_plane;
     a.src_plane[1] = b->q_plane;
     for (int sd = 0; sd < 2; ++sd) {
-        a.nrm[sd] = (const double*)tmp.nrm[sd].p;
+        a.nrm[sd] = (const double*)(stored ? b->pnrm[sd].p : tmp.nrm[sd].p);
         a.tau[sd] = tmp.tau[sd].p;
         a.spfh[sd] = (double*)tmp.spfh[sd].p;
         a.feat[sd] = (double*)b->feat[sd].p;
@@ -2407,6 +2434,195 @@ int icp_batch_compute_features(icp_batch* b, const int* k_moving, const int* k_m
     b->have_feat[0] = b->have_feat[1] = true;
     double* const out[2] = {moving_feat_out, model_feat_out};
     if (out[0] || out[1]) return download_features(b, out);
+    return ICP_OK;
+}
+
+// downloads the point-normal planes of the sides whose output pointer is given (one wait) and lays them out as the caller's
+int download_point_normals(icp_batch* b, double* const out[2])
+{
+    std::vector<double> h[2];
+    for (int sd = 0; sd < 2; ++sd)
+        if (out[sd]) {
+            h[sd].resize(3 * (size_t)(sd ? b->q_plane : b->p_plane));
+            HIP_TRY(hipMemcpyAsync(h[sd].data(), b->pnrm[sd].p, h[sd].size() * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
+        }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    for (int sd = 0; sd < 2; ++sd) {
+        if (!out[sd]) continue;
+        const Side s = ::side(b, sd != 0);
+        for (size_t p = 0; p < s.dst.size(); ++p)
+            for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
+                for (int k = 0; k < 3; ++k) out[sd][3 * (s.off[p] + i) + k] = h[sd][(size_t)(k * s.plane + s.dst[p] + i)];
+    }
+    return ICP_OK;
+}
+
+// room for the point normals of one side; new room is zeroed, so that the padding between the clouds is never random
+int ensure_point_normals(icp_batch* b, int sd)
+{
+    const size_t bytes = 3 * (size_t)(sd ? b->q_plane : b->p_plane) * sizeof(double);
+    if (b->pnrm[sd].p && bytes <= b->pnrm[sd].cap) return ICP_OK;
+    HIP_TRY(b->pnrm[sd].ensure(bytes));
+    HIP_TRY(hipMemsetAsync(b->pnrm[sd].p, 0, bytes, b->ctx->stream));
+    return ICP_OK;
+}
+
+// the 2 * count clouds, moving clouds first, and the work items of all of them on the device (nrm_args), with the pinned buffers
+// and the event of icp_batch_estimate_point_normals: made by the first call -- the layout of a batch never changes
+int ensure_normals_args(icp_batch* b)
+{
+    if (b->n_nrm_items != 0) return ICP_OK;
+    const int count = b->count, n_clouds = 2 * count;
+    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
+    std::vector<icp::BatchItem> items;
+    for (int k = 0; k < n_clouds; ++k) {
+        const int sd = k < count ? 0 : 1, p = k - sd * count;
+        const icp::BatchPair& pr = b->pairs[p];
+        clouds[k] = icp::VoxelCloud{sd ? pr.q_off : pr.p_off, 0, 0, sd ? pr.m : pr.n, sd};
+        for (int first = 0; first < clouds[k].n; first += icp::BATCH_ITEM)
+            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, clouds[k].n - first), 0});
+    }
+    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    const size_t off_items = (clouds.size() * sizeof(icp::VoxelCloud) + 15) / 16 * 16;
+    const size_t arg_bytes = off_items + items.size() * sizeof(icp::BatchItem);
+    if (!b->nrm_ev) HIP_TRY(hipEventCreateWithFlags(&b->nrm_ev, hipEventDisableTiming));
+    if (!b->h_nrm_view) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_nrm_view), (size_t)n_clouds * 3 * sizeof(double), hipHostMallocDefault));
+    if (!b->h_nrm_args) HIP_TRY(hipHostMalloc(&b->h_nrm_args, arg_bytes, hipHostMallocDefault));
+    HIP_TRY(b->nrm_args.ensure(arg_bytes));
+    HIP_TRY(b->nrm_view.ensure((size_t)n_clouds * 3 * sizeof(double)));
+    HIP_TRY(b->nrm_cent.ensure((size_t)n_clouds * 3 * sizeof(double)));
+    char* hs = static_cast<char*>(b->h_nrm_args);
+    std::memset(hs, 0, arg_bytes);
+    std::memcpy(hs, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud));
+    std::memcpy(hs + off_items, items.data(), items.size() * sizeof(icp::BatchItem));
+    HIP_TRY(hipMemcpyAsync(b->nrm_args.p, hs, arg_bytes, hipMemcpyHostToDevice, b->ctx->stream));   // (from a pinned buffer the batch keeps: no wait)
+    b->nrm_off_items = off_items;
+    b->n_nrm_items = (int)items.size();
+    return ICP_OK;
+}
+
+}  // namespace
+
+int icp_batch_compute_features(icp_batch* b, const int* k_moving, const int* k_model, const double* moving_normals,
+                               const double* model_normals, double* moving_feat_out, double* model_feat_out)
+{
+    return compute_features(b, false, k_moving, k_model, moving_normals, model_normals, moving_feat_out, model_feat_out);
+}
+
+int icp_batch_compute_features_stored(icp_batch* b, const int* k_moving, const int* k_model, double* moving_feat_out, double* model_feat_out)
+{
+    return compute_features(b, true, k_moving, k_model, nullptr, nullptr, moving_feat_out, model_feat_out);
+}
+
+int icp_batch_estimate_point_normals(icp_batch* b, int orient, const double* moving_viewpoints, const double* model_viewpoints,
+                                     double* moving_normals_out, double* model_normals_out)
+{
+    if (int rc = ready(b)) return rc;
+    if (orient != ICP_ORIENT_NONE && orient != ICP_ORIENT_VIEWPOINT && orient != ICP_ORIENT_CENTROID)
+        return fail(ICP_ERR_INVALID, "unknown orientation of the point normals");
+    for (int sd = 0; sd < 2; ++sd)
+        if (!b->have_cov[sd])
+            return fail(ICP_ERR_STATE, std::string("point normals need the covariances of both sides: the batch holds none of the ") + (sd ? "models" : "moving clouds") +
+                                           " (icp_batch_set_covariances or icp_batch_estimate_covariances first)");
+    const double* views[2] = {moving_viewpoints, model_viewpoints};
+    const int count = b->count, n_clouds = 2 * count;
+    if (orient == ICP_ORIENT_VIEWPOINT) {
+        for (int sd = 0; sd < 2; ++sd)
+            if (!views[sd]) return fail(ICP_ERR_INVALID, std::string("ICP_ORIENT_VIEWPOINT needs a viewpoint for both sides: ") + (sd ? "model_viewpoints" : "moving_viewpoints") + " == NULL");
+        for (int sd = 0; sd < 2; ++sd)
+            for (int p = 0; p < count; ++p)
+                for (int k = 0; k < 3; ++k)
+                    if (!std::isfinite(views[sd][3 * p + k]))
+                        return fail(ICP_ERR_INVALID, "a viewpoint has a NaN or an infinite value: pair " + std::to_string(p) + side_name(sd));
+    }
+    icp_ctx* c = b->ctx;
+    hipStream_t st = c->stream;
+    ScopedPin pin(c);
+    // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
+    if (int rc = ensure_normals_args(b)) return rc;
+    for (int sd = 0; sd < 2; ++sd)
+        if (int rc = ensure_point_normals(b, sd)) return rc;
+    if (orient == ICP_ORIENT_VIEWPOINT) {
+        HIP_TRY(hipEventSynchronize(b->nrm_ev));   // (the call before has long read the host buffer: no wait in practice; a new event is complete)
+        for (int sd = 0; sd < 2; ++sd) std::memcpy(b->h_nrm_view + (size_t)sd * count * 3, views[sd], (size_t)count * 3 * sizeof(double));
+        HIP_TRY(hipMemcpyAsync(b->nrm_view.p, b->h_nrm_view, (size_t)n_clouds * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(b->nrm_ev, st));
+    }
+    const char* ds = static_cast<const char*>(b->nrm_args.p);
+    icp::BatchNormalsArgs a{};
+    a.precision = b->prec;
+    a.orient = orient;
+    a.clouds = reinterpret_cast<const icp::VoxelCloud*>(ds);
+    a.n_clouds = n_clouds;
+    a.items = reinterpret_cast<const icp::BatchItem*>(ds + b->nrm_off_items);
+    a.n_items = b->n_nrm_items;
+    a.src[0] = b->P0.p;
+    a.src[1] = b->Q.p;
+    a.src_plane[0] = b->p_plane;
+    a.src_plane[1] = b->q_plane;
+    a.cent = (double*)b->nrm_cent.p;
+    a.view = orient == ICP_ORIENT_CENTROID ? (const double*)b->nrm_cent.p : orient == ICP_ORIENT_VIEWPOINT ? (const double*)b->nrm_view.p : nullptr;
+    for (int sd = 0; sd < 2; ++sd) {
+        a.cov[sd] = (const double*)b->cov[sd].p;
+        a.nrm[sd] = (double*)b->pnrm[sd].p;
+    }
+    HIP_TRY(icp::launch_batch_point_normals(a, st));
+    b->have_pnrm[0] = b->have_pnrm[1] = true;
+    if (orient == ICP_ORIENT_CENTROID) b->have_cent = true;
+    double* const out[2] = {moving_normals_out, model_normals_out};
+    if (out[0] || out[1]) return download_point_normals(b, out);   // (the one wait of a call that wants an output)
+    return ICP_OK;
+}
+
+int icp_batch_set_point_normals(icp_batch* b, const double* moving_normals, const double* model_normals)
+{
+    if (int rc = ready(b)) return rc;
+    const double* given[2] = {moving_normals, model_normals};
+    if (!given[0] && !given[1]) return fail(ICP_ERR_INVALID, "moving_normals == NULL and model_normals == NULL");
+    for (int sd = 0; sd < 2; ++sd) {
+        if (!given[sd]) continue;
+        const int64_t* off = sd ? b->qoff.data() : b->moff.data();
+        for (int p = 0; p < b->count; ++p)
+            for (int64_t i = 3 * off[p]; i < 3 * off[p + 1]; ++i)
+                if (!std::isfinite(given[sd][i]))
+                    return fail(ICP_ERR_INVALID, "a normal has a NaN or an infinite value: pair " + std::to_string(p) + side_name(sd));
+    }
+    // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
+    for (int sd = 0; sd < 2; ++sd)
+        if (given[sd])
+            if (int rc = ensure_point_normals(b, sd)) return rc;
+    std::vector<double> h[2];
+    for (int sd = 0; sd < 2; ++sd) {
+        if (!given[sd]) continue;
+        b->have_pnrm[sd] = false;
+        normals_to_planes(given[sd], ::side(b, sd != 0), h[sd]);
+        HIP_TRY(hipMemcpyAsync(b->pnrm[sd].p, h[sd].data(), h[sd].size() * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
+    for (int sd = 0; sd < 2; ++sd)
+        if (given[sd]) b->have_pnrm[sd] = true;
+    return ICP_OK;
+}
+
+int icp_batch_get_point_normals(icp_batch* b, double* moving_normals_out, double* model_normals_out)
+{
+    if (int rc = ready(b)) return rc;
+    double* const out[2] = {moving_normals_out, model_normals_out};
+    if (!out[0] && !out[1]) return fail(ICP_ERR_INVALID, "output pointer == NULL");
+    for (int sd = 0; sd < 2; ++sd)
+        if (out[sd] && !b->have_pnrm[sd])
+            return fail(ICP_ERR_STATE, std::string("the batch holds no point normals of the ") + (sd ? "models" : "moving clouds") +
+                                           " (icp_batch_estimate_point_normals or icp_batch_set_point_normals first)");
+    return download_point_normals(b, out);
+}
+
+int icp_diag_batch_centroids(icp_batch* b, double* out)
+{
+    if (int rc = ready(b)) return rc;
+    if (!out) return fail(ICP_ERR_INVALID, "output pointer == NULL");
+    if (!b->have_cent) return fail(ICP_ERR_STATE, "no icp_batch_estimate_point_normals call with ICP_ORIENT_CENTROID on this batch");
+    HIP_TRY(hipMemcpyAsync(out, b->nrm_cent.p, (size_t)b->count * 6 * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
     return ICP_OK;
 }
 

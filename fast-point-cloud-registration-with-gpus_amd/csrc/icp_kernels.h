@@ -623,6 +623,27 @@ hipError_t launch_batch_keypoint_select(const BatchKeypointArgs& a, hipStream_t 
 // batch_keypoint_compact: a kept point's coordinates to dst[side][k * dst_plane + dst_off + map[i]], its descriptor to
 // dst_feat[side][(dst_off + map[i]) * ICP_FEATURE_BINS ..].  One launch.
 hipError_t launch_batch_keypoint_compact(const BatchKeypointArgs& a, hipStream_t st);
+// point normals of every cloud of a batch from its stored covariances (icp_batch_estimate_point_normals; the rule:
+// include/icp_mi355x.h; icp_k_normals.hip).  The clouds and their numbering are the covariance call's (moving clouds first;
+// VoxelCloud::src_off is where the cloud starts in its coordinate, covariance and normal planes); the work items cover every cloud of
+// both sides (BatchItem::pair = the cloud's number).
+struct BatchNormalsArgs {
+    int precision;             // ICP_F32 / ICP_F64
+    int orient;                // ICP_ORIENT_NONE / _VIEWPOINT / _CENTROID
+    const VoxelCloud* clouds;  // [2 * n_pairs]
+    int n_clouds;
+    const BatchItem* items;
+    int n_items;
+    const void* src[2];        // P0 and Q (read only)
+    long long src_plane[2];
+    const double* cov[2];      // double[6][src_plane[side]]: xx, xy, xz, yy, yz, zz
+    const double* view;        // double[n_clouds][3]: what the normals of each cloud face (ICP_ORIENT_CENTROID: == cent); not read with ICP_ORIENT_NONE
+    double* cent;              // double[n_clouds][3]: written by batch_centroid_kernel (ICP_ORIENT_CENTROID only)
+    double* nrm[2];            // double[3][src_plane[side]]: x, y, z, laid out as the clouds
+};
+// [batch_centroid_kernel (one block per cloud: cent), ICP_ORIENT_CENTROID only ->] batch_point_normals_kernel (one wave per work
+// item: nrm).  One launch, or two.
+hipError_t launch_batch_point_normals(const BatchNormalsArgs& a, hipStream_t st);
 
 // soa2 (optional): a second copy of the result (the pristine moving cloud); enc (optional, fp32): the cloud's bounding cube as six
 // ordered-integer words {~ord(min xyz), ord(max xyz)}, zero before the launch

@@ -396,9 +396,13 @@ class Context:
         keypoints=rule (Batch.keypoints' rule, one for all pairs or one per pair; the default is None) matches and solves on the
         ISS keypoints of the thinned clouds alone: the descriptors are computed on the whole thinned clouds as before, then
         Batch.keypoints(moving=rule, model=rule) keeps the salient points with their descriptors, and matching and RANSAC or FGR
-        run on that batch; extra["global"] gains "keypoints": (n_kept, m_kept)."""
+        run on that batch; extra["global"] gains "keypoints": (n_kept, m_kept).
+        device_normals=True (the default is False) makes the normals on the device from the covariances
+        (Batch.estimate_point_normals, facing the centroids, or viewpoint where given) and describes from them
+        (Batch.compute_features_stored): no clouds and no covariances come down, no normals go up.  The Jacobi's and LAPACK's
+        vectors differ in the last bits, so descriptors and poses can differ from the default route's."""
         known = {"viewpoint", "edge_similarity", "seed", "mutual", "gate", "metric", "normals", "max_iter", "tol", "fixed_iterations", "trim", "reciprocal",
-                 "method", "iterations", "division_factor", "decrease_every", "tuple_similarity", "keypoints"}
+                 "method", "iterations", "division_factor", "decrease_every", "tuple_similarity", "keypoints", "device_normals"}
         unknown = set(options) - known
         if unknown:
             raise TypeError(f"register_batch_global: unknown option(s) {sorted(unknown)}")
@@ -410,13 +414,18 @@ class Context:
         with Batch(self, pairs) as full:
             bt = full if v == 0.0 else full.downsample(v)
             try:
-                cm, cq = bt.estimate_covariances(k, None, regularisation="none", want=True)
-                clouds = bt.get_clouds()
                 view = options.get("viewpoint")
-                eye = lambda X: X.astype(np.float64).mean(0) if view is None else view
-                nm = [oriented_normals(D, c, eye(D)) for (D, _), c in zip(clouds, cm)]
-                nq = [oriented_normals(M, c, eye(M)) for (_, M), c in zip(clouds, cq)]
-                bt.compute_features(k, (nm, nq))
+                if options.get("device_normals", False):   # nothing comes down, nothing goes up
+                    bt.estimate_covariances(k, None, regularisation="none", want=False)
+                    bt.estimate_point_normals("centroid" if view is None else "viewpoint", viewpoints=view)
+                    bt.compute_features_stored(k)
+                else:
+                    cm, cq = bt.estimate_covariances(k, None, regularisation="none", want=True)
+                    clouds = bt.get_clouds()
+                    eye = lambda X: X.astype(np.float64).mean(0) if view is None else view
+                    nm = [oriented_normals(D, c, eye(D)) for (D, _), c in zip(clouds, cm)]
+                    nq = [oriented_normals(M, c, eye(M)) for (_, M), c in zip(clouds, cq)]
+                    bt.compute_features(k, (nm, nq))
                 kb, kept = bt, None
                 if options.get("keypoints") is not None:   # match and solve on the salient points alone, with their descriptors
                     kb, info = bt.keypoints(moving=options["keypoints"], model=options["keypoints"])
@@ -1096,6 +1105,77 @@ class Batch:
                    "icp_batch_compute_features")
         if want:
             return self._cut33(om, self._moff), self._cut33(oq, self._qoff)
+
+    def _viewpoints(self, viewpoints):
+        """(moving, model), each (count, 3) float64: one (3,) viewpoint for every cloud, or a (moving, model) pair of per-pair arrays"""
+        if isinstance(viewpoints, (tuple, list)) and len(viewpoints) == 2 and np.ndim(viewpoints[0]) == 2:
+            vm, vq = (np.ascontiguousarray(v, dtype=np.float64) for v in viewpoints)
+        else:
+            one = np.asarray(viewpoints, dtype=np.float64)
+            if one.shape != (3,):
+                raise ValueError("viewpoints must be one (3,) point or a (moving, model) pair of (count, 3) arrays")
+            vm = vq = np.ascontiguousarray(np.tile(one, (self.count, 1)))
+        if vm.shape != (self.count, 3) or vq.shape != (self.count, 3):
+            raise ValueError("one (3,) viewpoint per pair and side")
+        return vm, vq
+
+    def estimate_point_normals(self, orient="centroid", viewpoints=None, want=False):
+        """the normal of every point of both clouds of every pair from the covariances the batch holds, on the device
+        (icp_batch_estimate_point_normals): the eigenvector of the smallest eigenvalue by icp_eigh3's Jacobi, exactly (0, 0, 0) where
+        it is not finite, kept on the device for compute_features_stored.  orient: "centroid" faces each cloud's own centroid,
+        "viewpoint" faces viewpoints -- one (3,) point for every cloud, or a (moving, model) pair of (count, 3) arrays, each in that
+        cloud's own frame -- "none" or None leaves the eigenvector as it is.  want: also return (moving, model), per pair the
+        (points, 3) float64 normals.  One launch, two for "centroid"; a host wait only with want.  A loop under way is left alone."""
+        mode = {"none": capi.ICP_ORIENT_NONE, None: capi.ICP_ORIENT_NONE, "viewpoint": capi.ICP_ORIENT_VIEWPOINT,
+                "centroid": capi.ICP_ORIENT_CENTROID}[orient] if (orient is None or isinstance(orient, str)) else int(orient)
+        pd = C.POINTER(C.c_double)
+        vm = vq = None
+        if mode == capi.ICP_ORIENT_VIEWPOINT and viewpoints is not None:
+            vm, vq = self._viewpoints(viewpoints)
+        om = np.empty((int(self._moff[-1]), 3)) if want else None
+        oq = np.empty((int(self._qoff[-1]), 3)) if want else None
+        capi.check(self._lib.icp_batch_estimate_point_normals(self._h, mode, vm.ctypes.data_as(pd) if vm is not None else None,
+                                                              vq.ctypes.data_as(pd) if vq is not None else None,
+                                                              om.ctypes.data_as(pd) if want else None, oq.ctypes.data_as(pd) if want else None),
+                   "icp_batch_estimate_point_normals")
+        if want:
+            return self._cut33(om, self._moff), self._cut33(oq, self._qoff)
+
+    def set_point_normals(self, moving=None, model=None):
+        """point normals of the caller's own (icp_batch_set_point_normals): per side one (points, 3) float64 array per pair, or
+        None: that side is left as it is.  Only finiteness is checked."""
+        pd = C.POINTER(C.c_double)
+        a = self._normals_side(moving, self._moff, "moving") if moving is not None else None
+        q = self._normals_side(model, self._qoff, "model") if model is not None else None
+        capi.check(self._lib.icp_batch_set_point_normals(self._h, a.ctypes.data_as(pd) if a is not None else None,
+                                                         q.ctypes.data_as(pd) if q is not None else None), "icp_batch_set_point_normals")
+
+    def get_point_normals(self):
+        """(moving, model): per pair the (points, 3) float64 point normals the batch holds (icp_batch_get_point_normals)"""
+        pd = C.POINTER(C.c_double)
+        om, oq = np.empty((int(self._moff[-1]), 3)), np.empty((int(self._qoff[-1]), 3))
+        capi.check(self._lib.icp_batch_get_point_normals(self._h, om.ctypes.data_as(pd), oq.ctypes.data_as(pd)), "icp_batch_get_point_normals")
+        return self._cut33(om, self._moff), self._cut33(oq, self._qoff)
+
+    def compute_features_stored(self, k, k_model=None, want=False):
+        """compute_features from the point normals the batch holds (estimate_point_normals, set_point_normals): the same two
+        launches, nothing uploaded (icp_batch_compute_features_stored)"""
+        km, kq = self._cov_k(k, "k"), self._cov_k(k if k_model is None else k_model, "model k")
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        om = np.empty((int(self._moff[-1]), capi.ICP_FEATURE_BINS)) if want else None
+        oq = np.empty((int(self._qoff[-1]), capi.ICP_FEATURE_BINS)) if want else None
+        capi.check(self._lib.icp_batch_compute_features_stored(self._h, km.ctypes.data_as(pi), kq.ctypes.data_as(pi),
+                                                               om.ctypes.data_as(pd) if want else None, oq.ctypes.data_as(pd) if want else None),
+                   "icp_batch_compute_features_stored")
+        if want:
+            return self._cut33(om, self._moff), self._cut33(oq, self._qoff)
+
+    def diag_centroids(self):
+        """(moving, model), each (count, 3) float64: the centroids of the last estimate_point_normals("centroid")
+        (icp_diag_batch_centroids)"""
+        out = np.empty((2 * self.count, 3))
+        capi.check(self._lib.icp_diag_batch_centroids(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), "icp_diag_batch_centroids")
+        return out[:self.count].copy(), out[self.count:].copy()
 
     def get_features(self):
         """(moving, model): per pair the (points, 33) float64 descriptors the batch holds (icp_batch_get_features)"""

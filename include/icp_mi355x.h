@@ -599,6 +599,46 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *           a cloud's descriptors depend on that cloud, its k and its normals alone.
  *         cost: two launches for all clouds of both sides (batch_spfh_kernel, batch_fpfh_kernel: one block per 64 points), no
  *           atomics, one host wait.
+ *       point normals (icp_batch_estimate_point_normals, icp_batch_set_point_normals, icp_batch_get_point_normals,
+ *         icp_batch_compute_features_stored): the normals the descriptors are computed from, made on the device from the
+ *         covariances the batch holds and kept there -- what Open3D's estimate_normals + orient_normals_towards_camera_location
+ *         give.  Three planes of doubles per side, laid out as the clouds; always double, whatever the batch's precision; separate
+ *         from the model normals of point-to-plane (icp_batch_set_model_normals), which are not touched.
+ *           icp_batch_estimate_point_normals computes both sides, always.  It needs covariances on both sides, given or estimated,
+ *             with any regularisation (ICP_ERR_STATE otherwise; the message names the side).  orient: ICP_ORIENT_NONE,
+ *             ICP_ORIENT_VIEWPOINT or ICP_ORIENT_CENTROID; an unknown value is ICP_ERR_INVALID.  With ICP_ORIENT_VIEWPOINT
+ *             moving_viewpoints and model_viewpoints are both required: 3 doubles per pair, each in that cloud's own frame; a NULL
+ *             array, a NaN or an infinite value is ICP_ERR_INVALID and the message names the pair and the side.  In the other
+ *             modes the arrays are not read.  The outputs are optional: 3 doubles per point, laid out as the clouds, as
+ *             icp_batch_compute_features takes them; there is a host wait only when one is given.  A pending pass on the
+ *             context: ICP_ERR_STATE.  A null batch: ICP_ERR_INVALID.  A refused call leaves the previous normals and everything
+ *             else as they were.  The loop does not notice: the call neither discards nor advances it.  The normals are a
+ *             snapshot: later covariance calls leave them in place.  The batches icp_batch_downsample, icp_batch_remove_outliers
+ *             and icp_batch_select_keypoints make hold none.
+ *           the rule for point i of a cloud, reproducible bit for bit in numpy (tests/batch_normals_ref.py does).  Every operation
+ *             is one IEEE double operation, nothing is fused, and the only functions used are + - * / sqrt fabs copysign.
+ *               eigenvector: icp_eigh3's statements (below) on the symmetric matrix built from the stored xx, xy, xz, yy, yz, zz,
+ *                 the updates of v included -- cyclic Jacobi over (0,1), (0,2), (1,2) from v = I; at most 64 sweeps; the stop test
+ *                 off <= 1e-34 * dia || off == 0.0; the same theta, t, c, s; the same three compare-and-swaps of the order with the
+ *                 strict <.  n is column ord[0] of v, not renormalised.  A zero matrix gives (1, 0, 0); equal smallest
+ *                 eigenvalues give whatever these statements give.
+ *               non-finite rule: if any component of n is not finite, n is exactly (0.0, 0.0, 0.0) -- the kept normals are always
+ *                 finite, which is what icp_batch_compute_features demands of the caller's.
+ *               orientation: to_a = v_a - (double)x_a for the cloud's viewpoint v; dt = (n_x*to_x + n_y*to_y) + n_z*to_z; n is
+ *                 negated iff dt < 0: dt == 0 and a NaN keep it.  With ICP_ORIENT_NONE nothing is negated.
+ *               centroid (ICP_ORIENT_CENTROID: v is the cloud's own centroid, which no rigid motion changes), per cloud and axis:
+ *                 s_t = 0.0 and s_t += (double)x_j for j = t, t + 256, ... below n, for t = 0 .. 255; total = 0.0 and
+ *                 total += s_t for t ascending; v = total / (double)n.
+ *             A cloud's normals depend on that cloud, its covariances and its viewpoint alone.
+ *           icp_batch_set_point_normals and icp_batch_get_point_normals follow icp_batch_set_covariances and
+ *             icp_batch_get_covariances: a NULL side is left untouched, both NULL is ICP_ERR_INVALID; the setter checks finiteness
+ *             only (ICP_ERR_INVALID, the message names the pair and the side); get on a side without normals is ICP_ERR_STATE.
+ *             Neither touches the loop.
+ *           icp_batch_compute_features_stored is icp_batch_compute_features with the kept normals in place of the host arrays:
+ *             the same two launches and the one wait, no upload of normals; a side without normals is ICP_ERR_STATE.
+ *           cost: one launch for all clouds of both sides (batch_point_normals_kernel: one wave per 64 points, one point per
+ *             lane), two with ICP_ORIENT_CENTROID (batch_centroid_kernel first: one block of 256 per cloud, 6 KiB of LDS); no
+ *             atomics; a host wait only when an output is wanted.
  *       matching (icp_batch_match_features): D(i, j) = the sum of (F_i[b] - G_j[b])^2 from 0.0 over b = 0..32 in ascending b, in
  *         double, each operation rounded on its own; F the moving cloud's descriptors, G the model's.  fwd[i] is the lowest j that
  *         minimises D, rev[j] the lowest i (a NaN never wins; where no D is below +INFINITY the answer is 0).
@@ -891,6 +931,17 @@ int icp_batch_set_color_weight(icp_batch* b, const double* lambda);
 #define ICP_FEATURE_BINS 33
 int icp_batch_compute_features(icp_batch* b, const int* k_moving, const int* k_model, const double* moving_normals,
                                const double* model_normals, double* moving_feat_out, double* model_feat_out);
+/* point normals on the device (above).  *_viewpoints: 3 doubles per pair, read with ICP_ORIENT_VIEWPOINT only; the normals:
+ * 3 doubles per point, laid out as the clouds; the outputs may be NULL */
+#define ICP_ORIENT_NONE 0        /* the eigenvector as the Jacobi leaves it */
+#define ICP_ORIENT_VIEWPOINT 1   /* facing the caller's viewpoint of each cloud */
+#define ICP_ORIENT_CENTROID 2    /* facing each cloud's own centroid */
+int icp_batch_estimate_point_normals(icp_batch* b, int orient, const double* moving_viewpoints, const double* model_viewpoints,
+                                     double* moving_normals_out, double* model_normals_out);
+int icp_batch_set_point_normals(icp_batch* b, const double* moving_normals, const double* model_normals);
+int icp_batch_get_point_normals(icp_batch* b, double* moving_normals_out, double* model_normals_out);
+/* icp_batch_compute_features from the point normals the batch holds */
+int icp_batch_compute_features_stored(icp_batch* b, const int* k_moving, const int* k_model, double* moving_feat_out, double* model_feat_out);
 /* the descriptors the batch holds; either pointer may be NULL; ICP_ERR_STATE where a side that is asked for holds none */
 int icp_batch_get_features(icp_batch* b, double* moving_feat_out, double* model_feat_out);
 /* fwd_out / kept_out: 1 per moving point; rev_out: 1 per model point; each may be NULL */

@@ -134,6 +134,9 @@ int icp_diag_batch_fgr(icp_batch* b, int pair, int32_t* used_pos, double* mu_his
  * control block, its upload, the two launches, the download), [1] the wait for the vectors, [2] the solves of all pairs; [3] is
  * the number of iterations that ran.  Three clock reads per iteration.  ICP_ERR_STATE before the first run. */
 int icp_diag_batch_fgr_times(icp_batch* b, double* seconds4);
+/* the centroids batch_centroid_kernel made in the last icp_batch_estimate_point_normals call with ICP_ORIENT_CENTROID: 3 doubles
+ * per cloud, 2 * count clouds, the moving clouds first.  One download, one wait.  ICP_ERR_STATE after no such call. */
+int icp_diag_batch_centroids(icp_batch* b, double* out /* 2 * count * 3 */);
 #ifdef __cplusplus
 }
 #endif
