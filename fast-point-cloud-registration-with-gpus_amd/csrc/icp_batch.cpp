@@ -70,20 +70,19 @@
 // pair: three launches, none of which writes idx, mom, tau, thr or ctl of the loop.  Fitness, inlier RMSE and the 6 x 6 information
 // matrix are assembled on the host from that vector alone.  The loop does not notice the call.
 //
-// A batch is thinned on the device (icp_batch_downsample): a new batch on the same context whose clouds are P0 and Q of the source,
-// reduced to one point per occupied cell of a voxel grid per cloud -- the rule, which numpy reproduces bit for bit, is stated in
-// include/icp_mi355x.h.  batch_voxel_keys (bounds, range check, keys)  ->  batch_voxel_group (first point of every cell, the
-// sequential sums)  ->  batch_voxel_rank (output ranks, counts, maps)  ->  [D2H: 2 x count counts and range flags, the first wait;
-// the new batch is laid out and allocated as icp_batch_create does it: lay_out + allocate]  ->  batch_voxel_compact (the centroids
-// into the new planes)  ->  the second wait.  Four launches, two waits; the source is only read, its loop does not notice, and the
-// temporaries live for the call.
-//
-// Isolated points are removed on the device (icp_batch_remove_outliers): a new batch on the same context whose clouds are P0 and Q
-// of the source without the points a statistical or a radius rule per cloud rejects -- the rules, which numpy reproduces bit for
-// bit, are stated in include/icp_mi355x.h.  batch_outlier_scan (every point's mean neighbour distance or neighbour count)  ->
-// batch_outlier_decide (the ordered sums, the threshold, maps and counts)  ->  [D2H: 2 x count counts and flags, the first wait;
-// lay_out + allocate]  ->  batch_outlier_compact (the kept points' bytes into the new planes)  ->  the second wait, with the
-// optional outputs.  Three launches, two waits; the source is only read, its loop does not notice.
+// A batch is thinned on the device into a new batch on the same context, whose clouds are P0 and Q of the source reduced by a rule
+// per cloud (the rules, which numpy reproduces bit for bit, are stated in include/icp_mi355x.h).  The three calls share one sequence
+// (the thin_* functions below; the clouds and their work items: icp_batch_clouds.h):  the 2 x count clouds, their work items and
+// their rules go up  ->  the call's select launches (every cloud's count, every point's output index)  ->  [D2H: 2 x count counts
+// and flags, the first wait; the data-dependent refusals; the new batch is laid out and allocated as icp_batch_create does it:
+// lay_out + allocate]  ->  the call's compact launch into the new, zeroed planes  ->  P0 -> P  ->  the second wait, which brings
+// the optional outputs.  Two waits; the source is only read, its loop does not notice, the temporaries live for the call, and no
+// output array is written before the call can no longer be refused.
+//   icp_batch_downsample        one point per occupied voxel: batch_voxel_keys, _group, _rank  ->  batch_voxel_compact (the centroids)
+//   icp_batch_remove_outliers   a statistical or a radius rule: batch_outlier_scan, _decide  ->  batch_outlier_compact (the kept points' bytes)
+//   icp_batch_select_keypoints  ISS keypoints (icp_k_keypoint.hip): batch_iss_saliency, batch_iss_select, batch_keypoint_rank  ->
+//                               batch_keypoint_compact (coordinates, and the kept points' descriptors where the source holds descriptors,
+//                               so that matching and RANSAC or FGR run on a few hundred points per cloud)
 //
 // A start pose for pairs in unknown relative pose (global registration; the rules, which numpy reproduces bit for bit, are stated in
 // include/icp_mi355x.h; kernels: icp_k_feat.hip): icp_batch_compute_features (batch_spfh_kernel -> batch_fpfh_kernel, one block
@@ -97,14 +96,6 @@
 // batch_fgr_finalize run over the pairs still running, the vectors come down (the one wait) and the host solves every pair's 6 x 6
 // system (icp::solve_point_to_plane); a last launch at the final poses writes the weights.  All
 // of them read P0 and Q and buffers of their own: the loop does not notice.
-//
-// The clouds of a batch are reduced to their salient points on the device (icp_batch_select_keypoints; kernels: icp_k_keypoint.hip):
-// a new batch on the same context whose clouds are the ISS keypoints of P0 and Q of the source, with the descriptors of the kept
-// points where the source holds descriptors, so that matching and RANSAC or FGR run on a few hundred points per cloud.
-// batch_iss_saliency (the smallest eigenvalue of every point's neighbourhood covariance)  ->  batch_iss_select (non-maximum
-// suppression)  ->  batch_keypoint_rank (maps and counts)  ->  [D2H: 2 x count counts, the first wait; lay_out + allocate]  ->
-// batch_keypoint_compact (coordinates and descriptors)  ->  the second wait, with the optional outputs.  Four launches, two waits;
-// the source is only read, its loop does not notice.
 //
 // The normals the descriptors are computed from are made on the device from the covariances the batch holds and kept there
 // (icp_batch_estimate_point_normals; kernels: icp_k_normals.hip): [batch_centroid_kernel, ICP_ORIENT_CENTROID only]  ->
@@ -130,6 +121,7 @@
 #include <vector>
 
 #include "../../include/icp_mi355x_diag.h"
+#include "icp_batch_clouds.h"
 #include "icp_ctx.h"
 #include "icp_host_math.h"
 
@@ -232,6 +224,15 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
 
 namespace {
 
+// which cloud a refusal speaks of: ": pair 3, model"
+std::string where(int p, int side) { return ": pair " + std::to_string(p) + (side ? ", model" : ", moving cloud"); }
+
+// 8, 16 or 32: the register capacity of a neighbour list that holds k entries (the kernels' cap)
+int list_cap(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : 32; }
+
+// elements per plane of the moving clouds (sd == 0) / of the models
+size_t plane_elems(const icp_batch* b, int sd) { return (size_t)(sd ? b->q_plane : b->p_plane); }
+
 bool running(const icp_batch* b, int p) { return b->begun && !b->H[p].done && b->status[p] == ICP_OK; }
 
 int count_running(const icp_batch* b)
@@ -322,44 +323,69 @@ Side side(const icp_batch* b, bool model)
     return s;
 }
 
-// the pairs' AoS clouds -> padded SoA planes, every cloud at its offset (the padding is never read), and back
-template <typename F>
+// V values of type E per point of one side (coordinates, normals, covariances, intensities, gradients): the caller's AoS,
+// concatenated as the clouds -> V padded planes, every cloud at its offset (the padding: all-zero bytes, 0.0 in both precisions,
+// never read), and back
+template <typename E, int V>
 void to_planes(const void* aos, const Side& s, std::vector<char>& raw)
 {
-    const F* a = static_cast<const F*>(aos);
-    F* out = reinterpret_cast<F*>(raw.data());
+    raw.assign(V * (size_t)s.plane * sizeof(E), 0);
+    const E* a = static_cast<const E*>(aos);
+    E* out = reinterpret_cast<E*>(raw.data());
     for (size_t p = 0; p < s.dst.size(); ++p)
         for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
-            for (int k = 0; k < 3; ++k) out[(size_t)(k * s.plane + s.dst[p] + i)] = a[3 * (s.off[p] + i) + k];
+            for (int k = 0; k < V; ++k) out[(size_t)(k * s.plane + s.dst[p] + i)] = a[V * (s.off[p] + i) + k];
 }
 
-template <typename F>
+template <typename E, int V>
 void from_planes(const std::vector<char>& raw, const Side& s, void* aos)
 {
-    const F* in = reinterpret_cast<const F*>(raw.data());
-    F* o = static_cast<F*>(aos);
+    const E* in = reinterpret_cast<const E*>(raw.data());
+    E* o = static_cast<E*>(aos);
     for (size_t p = 0; p < s.dst.size(); ++p)
         for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
-            for (int k = 0; k < 3; ++k) o[3 * (s.off[p] + i) + k] = in[(size_t)(k * s.plane + s.dst[p] + i)];
+            for (int k = 0; k < V; ++k) o[V * (s.off[p] + i) + k] = in[(size_t)(k * s.plane + s.dst[p] + i)];
+}
+
+// downloads the V planes of the sides whose output pointer is given (moving clouds: dev_p -> out_p, models: dev_q -> out_q), waits
+// once and lays them out as the caller's
+template <typename E, int V>
+int download_planes(icp_batch* b, const void* dev_p, const void* dev_q, void* out_p, void* out_q)
+{
+    const void* const dev[2] = {dev_p, dev_q};
+    void* const out[2] = {out_p, out_q};
+    std::vector<char> h[2];
+    for (int sd = 0; sd < 2; ++sd)
+        if (out[sd]) {
+            h[sd].resize(V * plane_elems(b, sd) * sizeof(E));
+            HIP_TRY(hipMemcpyAsync(h[sd].data(), dev[sd], h[sd].size(), hipMemcpyDeviceToHost, b->ctx->stream));
+        }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    for (int sd = 0; sd < 2; ++sd)
+        if (out[sd]) from_planes<E, V>(h[sd], side(b, sd != 0), out[sd]);
+    return ICP_OK;
 }
 
 // the moving clouds' (the models') layout, in the batch's precision: AoS as the caller holds it -> the planes of `dev`.  Enqueues
 // the copy from `host`, which must outlive it: the caller synchronises.
 int enqueue_planes(icp_batch* b, const void* aos, bool model, void* dev, std::vector<char>& host)
 {
-    const Side s = side(b, model);
-    host.assign(3 * (size_t)s.plane * b->esize, 0);   // (all-zero bytes: 0.0 in both precisions)
-    if (b->prec == ICP_F64) to_planes<double>(aos, s, host);
-    else to_planes<float>(aos, s, host);
+    if (b->prec == ICP_F64) to_planes<double, 3>(aos, side(b, model), host);
+    else to_planes<float, 3>(aos, side(b, model), host);
     HIP_TRY(hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, b->ctx->stream));
     return ICP_OK;
 }
 
-// ... and back: planes downloaded into `raw` -> AoS in the caller's layout
+// ... and back: such planes downloaded into `raw` -> AoS in the caller's layout
 void planes_to_aos(const icp_batch* b, const std::vector<char>& raw, bool model, void* aos)
 {
-    if (b->prec == ICP_F64) from_planes<double>(raw, side(b, model), aos);
-    else from_planes<float>(raw, side(b, model), aos);
+    if (b->prec == ICP_F64) from_planes<double, 3>(raw, side(b, model), aos);
+    else from_planes<float, 3>(raw, side(b, model), aos);
+}
+
+int download_clouds(icp_batch* b, const void* dev_p, const void* dev_q, void* out_p, void* out_q)
+{
+    return b->prec == ICP_F64 ? download_planes<double, 3>(b, dev_p, dev_q, out_p, out_q) : download_planes<float, 3>(b, dev_p, dev_q, out_p, out_q);
 }
 
 // element i of an array in the batch's precision: written from a double (rounded once), read back as a double
@@ -495,376 +521,274 @@ int upload(icp_batch* b, const void* moving, const void* model)
     return ICP_OK;
 }
 
-// the per-point temporaries of one icp_batch_downsample: released when the call returns, whichever way -- after what the call
-// enqueued has ended (the host vectors of its copies are declared before this and so outlive it)
-struct VoxelTmp {
+// the device temporaries of one call: released when the call returns, whichever way -- after what the call enqueued has ended
+// (host vectors that its copies read or write are declared before this and so outlive it)
+struct Temps {
     hipStream_t st;
-    DevBuf clouds, items, voxel, keys, too_fine, first, cent, rank, map, count;
-    explicit VoxelTmp(hipStream_t s) : st(s) {}
-    ~VoxelTmp()
+    DevBuf buf[12];
+    explicit Temps(hipStream_t s) : st(s) {}
+    ~Temps()
     {
         (void)hipStreamSynchronize(st);
-        for (DevBuf* d : {&clouds, &items, &voxel, &keys, &too_fine, &first, &cent, &rank, &map, &count}) d->release();
+        for (DevBuf& d : buf) d.release();
     }
+    Temps(const Temps&) = delete;
+    Temps& operator=(const Temps&) = delete;
 };
 
-// icp_batch_downsample after its argument checks; *made: the new batch as far as it got (the caller releases it on failure)
-int downsample(icp_batch* src, const std::vector<double>& voxel, int32_t* moving_map_out, int32_t* model_map_out, icp_batch** made)
+// ---- thinning a batch into a new batch: what icp_batch_downsample, icp_batch_remove_outliers and icp_batch_select_keypoints share.
+// A call runs  thin_begin, [its own temporaries,] thin_upload, thin_args + its select launches, thin_counts, [its refusals,]
+// thin_allocate, thin_args + its compact launch, thin_download, [its own downloads,] thin_finish  -- the sequence of the head comment.
+enum { T_CLOUDS, T_ITEMS, T_RULES, T_MAP, T_COUNT, T_FLAG, T_VALUE, T_OWN };   // Temps::buf of a thinning call; from T_OWN on: the call's own
+
+struct Thin {
+    icp_batch* src;
+    hipStream_t st;
+    int count;                               // pairs; cloud k < count: the moving cloud of pair k, cloud count + p: the model of pair p
+    icp_batch* nb = nullptr;                 // the new batch, once thin_allocate has made it
+    icp::CloudList cl;
+    std::vector<icp::BatchItem> new_items;
+    std::vector<int> flag;                   // per cloud, after thin_counts: the select launches refuse the cloud (T_FLAG; calls that have one)
+    std::vector<int32_t> kept, hmap;         // per cloud, after thin_counts: its points in the new batch (T_COUNT); per point: its new index (T_MAP)
+    std::vector<double> hvalue;              // per point: the call's score (T_VALUE; calls that have one)
+    int32_t* map_out[2] = {nullptr, nullptr};      // the caller's arrays for hmap and hvalue, moving clouds / models (NULL: not wanted)
+    double* value_out[2] = {nullptr, nullptr};
+    Temps t;                                 // (last: gone first)
+    explicit Thin(icp_batch* s) : src(s), st(s->ctx->stream), count(s->count), t(s->ctx->stream) {}
+};
+
+// the clouds, the work items and the temporaries every thinning call has (rule_bytes: the call's rules of all clouds; value: the call
+// keeps a double per point; flag: an int per cloud)
+int thin_begin(Thin& th, size_t rule_bytes, bool value, bool flag)
 {
-    icp_ctx* c = src->ctx;
-    hipStream_t st = c->stream;
-    const int count = src->count, n_clouds = 2 * count;
-    // the 2 * count clouds, moving clouds first, and their work items; every cloud owns a stretch of the temporaries
-    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
-    std::vector<icp::BatchItem> items, new_items;
-    std::vector<int> too_fine((size_t)n_clouds);
-    std::vector<int32_t> cells((size_t)n_clouds), hmap;
-    long long tmp_plane = 0;
-    for (int k = 0; k < n_clouds; ++k) {
-        const int side = k < count ? 0 : 1;
-        const icp::BatchPair& pr = src->pairs[k - side * count];
-        icp::VoxelCloud& cl = clouds[k];
-        cl.side = side;
-        cl.n = side ? pr.m : pr.n;
-        cl.src_off = side ? pr.q_off : pr.p_off;
-        cl.tmp_off = tmp_plane;
-        cl.dst_off = 0;
-        tmp_plane += icp::round_up(cl.n, icp::BATCH_ALIGN);
-        for (int first = 0; first < cl.n; first += icp::BATCH_ITEM)
-            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, cl.n - first), 0});
-    }
-    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
-    VoxelTmp t(st);
-    HIP_TRY(t.clouds.ensure(clouds.size() * sizeof(icp::VoxelCloud)));
-    HIP_TRY(t.items.ensure(items.size() * sizeof(icp::BatchItem)));
-    HIP_TRY(t.voxel.ensure(voxel.size() * sizeof(double)));
-    HIP_TRY(t.keys.ensure((size_t)tmp_plane * sizeof(unsigned long long)));
-    HIP_TRY(t.too_fine.ensure((size_t)n_clouds * sizeof(int)));
-    HIP_TRY(t.first.ensure((size_t)tmp_plane * sizeof(int32_t)));
-    HIP_TRY(t.cent.ensure(3 * (size_t)tmp_plane * src->esize));
-    HIP_TRY(t.rank.ensure((size_t)tmp_plane * sizeof(int32_t)));
-    HIP_TRY(t.map.ensure((size_t)tmp_plane * sizeof(int32_t)));
-    HIP_TRY(t.count.ensure((size_t)n_clouds * sizeof(int32_t)));
-    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(t.items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(t.voxel.p, voxel.data(), voxel.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    icp::BatchVoxelArgs a{};
-    a.precision = src->prec;
-    a.clouds = (const icp::VoxelCloud*)t.clouds.p;
-    a.n_clouds = n_clouds;
-    a.items = (const icp::BatchItem*)t.items.p;
-    a.n_items = (int)items.size();
-    a.voxel = (const double*)t.voxel.p;
-    a.src[0] = src->P0.p;
-    a.src[1] = src->Q.p;
-    a.src_plane[0] = src->p_plane;
-    a.src_plane[1] = src->q_plane;
-    a.tmp_plane = tmp_plane;
-    a.keys = (unsigned long long*)t.keys.p;
-    a.too_fine = (int*)t.too_fine.p;
-    a.first = (int32_t*)t.first.p;
-    a.cent = t.cent.p;
-    a.rank = (int32_t*)t.rank.p;
-    a.map = (int32_t*)t.map.p;
-    a.count = (int32_t*)t.count.p;
-    HIP_TRY(icp::launch_batch_voxel_group(a, st));
-    HIP_TRY(hipMemcpyAsync(too_fine.data(), t.too_fine.p, too_fine.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(cells.data(), t.count.p, cells.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));   // the first wait: the new batch's layout needs every cloud's count
-    for (int p = 0; p < count; ++p)
-        for (int side = 0; side < 2; ++side)
-            if (too_fine[(size_t)side * count + p])
-                return fail(ICP_ERR_INVALID, "the voxel grid is too fine for the cloud's extent (a cell index above 2097151): pair " + std::to_string(p) +
-                                                 (side ? ", model" : ", moving cloud"));
+    const bool both[2] = {true, true};
+    if (!icp::list_clouds(th.src->pairs, both, th.cl)) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    const size_t n_clouds = th.cl.clouds.size(), tmp = (size_t)th.cl.tmp_plane;
+    HIP_TRY(th.t.buf[T_CLOUDS].ensure(n_clouds * sizeof(icp::VoxelCloud)));
+    HIP_TRY(th.t.buf[T_ITEMS].ensure(th.cl.items.size() * sizeof(icp::BatchItem)));
+    HIP_TRY(th.t.buf[T_RULES].ensure(rule_bytes));
+    if (value) HIP_TRY(th.t.buf[T_VALUE].ensure(tmp * sizeof(double)));
+    HIP_TRY(th.t.buf[T_MAP].ensure(tmp * sizeof(int32_t)));
+    HIP_TRY(th.t.buf[T_COUNT].ensure(n_clouds * sizeof(int32_t)));
+    if (flag) HIP_TRY(th.t.buf[T_FLAG].ensure(n_clouds * sizeof(int)));
+    return ICP_OK;
+}
+
+int thin_upload(Thin& th, const void* rules, size_t rule_bytes)
+{
+    HIP_TRY(hipMemcpyAsync(th.t.buf[T_CLOUDS].p, th.cl.clouds.data(), th.cl.clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, th.st));
+    HIP_TRY(hipMemcpyAsync(th.t.buf[T_ITEMS].p, th.cl.items.data(), th.cl.items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, th.st));
+    HIP_TRY(hipMemcpyAsync(th.t.buf[T_RULES].p, rules, rule_bytes, hipMemcpyHostToDevice, th.st));
+    return ICP_OK;
+}
+
+// what BatchVoxelArgs, BatchOutlierArgs and BatchKeypointArgs have in common; dst: once the new batch is there
+template <typename Args>
+void thin_args(Args& a, const Thin& th)
+{
+    a.precision = th.src->prec;
+    a.clouds = (const icp::VoxelCloud*)th.t.buf[T_CLOUDS].p;
+    a.n_clouds = (int)th.cl.clouds.size();
+    a.items = (const icp::BatchItem*)th.t.buf[T_ITEMS].p;
+    a.n_items = (int)th.cl.items.size();
+    a.src[0] = th.src->P0.p;
+    a.src[1] = th.src->Q.p;
+    a.src_plane[0] = th.src->p_plane;
+    a.src_plane[1] = th.src->q_plane;
+    a.tmp_plane = th.cl.tmp_plane;
+    a.map = (int32_t*)th.t.buf[T_MAP].p;
+    a.count = (int32_t*)th.t.buf[T_COUNT].p;
+    if (!th.nb) return;
+    a.dst[0] = th.nb->P0.p;
+    a.dst[1] = th.nb->Q.p;
+    a.dst_plane[0] = th.nb->p_plane;
+    a.dst_plane[1] = th.nb->q_plane;
+}
+
+// the flags (calls that have them) and the counts of the select launches come down: the first wait
+int thin_counts(Thin& th)
+{
+    th.flag.assign(th.cl.clouds.size(), 0);
+    th.kept.resize(th.cl.clouds.size());
+    if (th.t.buf[T_FLAG].p) HIP_TRY(hipMemcpyAsync(th.flag.data(), th.t.buf[T_FLAG].p, th.flag.size() * sizeof(int), hipMemcpyDeviceToHost, th.st));
+    HIP_TRY(hipMemcpyAsync(th.kept.data(), th.t.buf[T_COUNT].p, th.kept.size() * sizeof(int32_t), hipMemcpyDeviceToHost, th.st));
+    HIP_TRY(hipStreamSynchronize(th.st));   // the first wait: the new batch's layout needs every cloud's count
+    return ICP_OK;
+}
+
+// the new batch from the counts (every one in [1, the cloud's points]: the caller has checked), its planes zeroed, and where every
+// cloud goes in it on the device; *made: the new batch as far as it got (the caller's caller releases it on failure)
+int thin_allocate(Thin& th, icp_batch** made)
+{
+    const int count = th.count;
     std::vector<int64_t> moff((size_t)count + 1, 0), qoff((size_t)count + 1, 0);
     for (int p = 0; p < count; ++p) {
-        if (cells[p] < 1 || cells[p] > src->pairs[p].n || cells[(size_t)count + p] < 1 || cells[(size_t)count + p] > src->pairs[p].m)
-            return fail(ICP_ERR_HIP, "icp_batch_downsample: a cloud's cell count is out of range");   // (cannot happen: every cloud has a point)
-        moff[p + 1] = moff[p] + cells[p];
-        qoff[p + 1] = qoff[p] + cells[(size_t)count + p];
+        moff[p + 1] = moff[p] + th.kept[p];
+        qoff[p + 1] = qoff[p] + th.kept[(size_t)count + p];
     }
-    if (int rc = lay_out(c, count, src->prec, moff.data(), qoff.data(), made)) return rc;
-    icp_batch* nb = *made;
-    if (int rc = allocate(nb, new_items)) return rc;
-    for (int k = 0; k < n_clouds; ++k) clouds[k].dst_off = k < count ? nb->pairs[k].p_off : nb->pairs[k - count].q_off;
-    const size_t pb = 3 * (size_t)nb->p_plane * nb->esize, qb = 3 * (size_t)nb->q_plane * nb->esize;
-    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(nb->P0.p, 0, pb, st));   // (the padding between the clouds: all-zero bytes, as an upload leaves it)
-    HIP_TRY(hipMemsetAsync(nb->Q.p, 0, qb, st));
-    a.dst[0] = nb->P0.p;
-    a.dst[1] = nb->Q.p;
-    a.dst_plane[0] = nb->p_plane;
-    a.dst_plane[1] = nb->q_plane;
-    HIP_TRY(icp::launch_batch_voxel_compact(a, st));
-    HIP_TRY(hipMemcpyAsync(nb->P.p, nb->P0.p, pb, hipMemcpyDeviceToDevice, st));
-    if (moving_map_out || model_map_out) {
-        hmap.resize((size_t)tmp_plane);
-        HIP_TRY(hipMemcpyAsync(hmap.data(), t.map.p, hmap.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (int rc = lay_out(th.src->ctx, count, th.src->prec, moff.data(), qoff.data(), made)) return rc;
+    icp_batch* nb = th.nb = *made;
+    if (int rc = allocate(nb, th.new_items)) return rc;
+    for (int k = 0; k < 2 * count; ++k) th.cl.clouds[k].dst_off = k < count ? nb->pairs[k].p_off : nb->pairs[k - count].q_off;
+    HIP_TRY(hipMemcpyAsync(th.t.buf[T_CLOUDS].p, th.cl.clouds.data(), th.cl.clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, th.st));
+    HIP_TRY(hipMemsetAsync(nb->P0.p, 0, 3 * plane_elems(nb, 0) * nb->esize, th.st));   // (the padding between the clouds: all-zero bytes, as an upload leaves it)
+    HIP_TRY(hipMemsetAsync(nb->Q.p, 0, 3 * plane_elems(nb, 1) * nb->esize, th.st));
+    return ICP_OK;
+}
+
+// behind the compact launch: the new batch's P, and the per-point outputs that are wanted start their way down
+int thin_download(Thin& th)
+{
+    HIP_TRY(hipMemcpyAsync(th.nb->P.p, th.nb->P0.p, 3 * plane_elems(th.nb, 0) * th.nb->esize, hipMemcpyDeviceToDevice, th.st));
+    if (th.map_out[0] || th.map_out[1]) {
+        th.hmap.resize((size_t)th.cl.tmp_plane);
+        HIP_TRY(hipMemcpyAsync(th.hmap.data(), th.t.buf[T_MAP].p, th.hmap.size() * sizeof(int32_t), hipMemcpyDeviceToHost, th.st));
     }
-    HIP_TRY(hipStreamSynchronize(st));   // the second wait: the host vectors go, the temporaries are freed
-    for (int p = 0; p < count; ++p) {
-        if (moving_map_out) std::memcpy(moving_map_out + src->moff[p], hmap.data() + clouds[p].tmp_off, (size_t)src->pairs[p].n * sizeof(int32_t));
-        if (model_map_out)
-            std::memcpy(model_map_out + src->qoff[p], hmap.data() + clouds[(size_t)count + p].tmp_off, (size_t)src->pairs[p].m * sizeof(int32_t));
+    if (th.value_out[0] || th.value_out[1]) {
+        th.hvalue.resize((size_t)th.cl.tmp_plane);
+        HIP_TRY(hipMemcpyAsync(th.hvalue.data(), th.t.buf[T_VALUE].p, th.hvalue.size() * sizeof(double), hipMemcpyDeviceToHost, th.st));
     }
     return ICP_OK;
 }
 
-// the temporaries of one icp_batch_remove_outliers, released as VoxelTmp's are
-struct OutlierTmp {
-    hipStream_t st;
-    DevBuf clouds, items, rules, score, map, stats, count, bad;
-    explicit OutlierTmp(hipStream_t s) : st(s) {}
-    ~OutlierTmp()
-    {
-        (void)hipStreamSynchronize(st);
-        for (DevBuf* d : {&clouds, &items, &rules, &score, &map, &stats, &count, &bad}) d->release();
+// the second wait, then every cloud's stretch of the per-point outputs into the caller's arrays
+int thin_finish(Thin& th)
+{
+    HIP_TRY(hipStreamSynchronize(th.st));   // the second wait: the host vectors go, the temporaries are freed
+    for (size_t k = 0; k < th.cl.clouds.size(); ++k) {
+        const icp::VoxelCloud& c = th.cl.clouds[k];
+        const size_t p = k - (size_t)c.side * th.count;
+        const int64_t at = c.side ? th.src->qoff[p] : th.src->moff[p];
+        if (th.map_out[c.side]) std::memcpy(th.map_out[c.side] + at, th.hmap.data() + c.tmp_off, (size_t)c.n * sizeof(int32_t));
+        if (th.value_out[c.side]) std::memcpy(th.value_out[c.side] + at, th.hvalue.data() + c.tmp_off, (size_t)c.n * sizeof(double));
     }
-};
+    return ICP_OK;
+}
 
-// icp_batch_remove_outliers after its argument checks; *made: the new batch as far as it got (the caller releases it on failure).
-// batch_outlier_scan (every point's score)  ->  batch_outlier_decide (the ordered sums, the threshold, maps and counts)  ->  [D2H:
-// 2 x count counts and flags, the first wait; lay_out + allocate]  ->  batch_outlier_compact  ->  the second wait, which brings the
-// optional outputs.  Three launches, two waits; no output array is written before the call can no longer be refused for its data.
+// icp_batch_downsample after its argument checks
+int downsample(icp_batch* src, const std::vector<double>& voxel, int32_t* moving_map_out, int32_t* model_map_out, icp_batch** made)
+{
+    enum { KEYS = T_OWN, FIRST, CENT, RANK };
+    Thin th(src);
+    th.map_out[0] = moving_map_out;
+    th.map_out[1] = model_map_out;
+    if (int rc = thin_begin(th, voxel.size() * sizeof(double), false, true)) return rc;
+    const size_t tmp = (size_t)th.cl.tmp_plane;
+    HIP_TRY(th.t.buf[KEYS].ensure(tmp * sizeof(unsigned long long)));
+    HIP_TRY(th.t.buf[FIRST].ensure(tmp * sizeof(int32_t)));
+    HIP_TRY(th.t.buf[CENT].ensure(3 * tmp * src->esize));
+    HIP_TRY(th.t.buf[RANK].ensure(tmp * sizeof(int32_t)));
+    if (int rc = thin_upload(th, voxel.data(), voxel.size() * sizeof(double))) return rc;
+    icp::BatchVoxelArgs a{};
+    thin_args(a, th);
+    a.voxel = (const double*)th.t.buf[T_RULES].p;
+    a.keys = (unsigned long long*)th.t.buf[KEYS].p;
+    a.too_fine = (int*)th.t.buf[T_FLAG].p;
+    a.first = (int32_t*)th.t.buf[FIRST].p;
+    a.cent = th.t.buf[CENT].p;
+    a.rank = (int32_t*)th.t.buf[RANK].p;
+    HIP_TRY(icp::launch_batch_voxel_group(a, th.st));
+    if (int rc = thin_counts(th)) return rc;
+    for (int p = 0; p < th.count; ++p)
+        for (int side = 0; side < 2; ++side)
+            if (th.flag[(size_t)side * th.count + p])
+                return fail(ICP_ERR_INVALID, "the voxel grid is too fine for the cloud's extent (a cell index above 2097151)" + where(p, side));
+    for (int p = 0; p < th.count; ++p)
+        if (th.kept[p] < 1 || th.kept[p] > src->pairs[p].n || th.kept[(size_t)th.count + p] < 1 || th.kept[(size_t)th.count + p] > src->pairs[p].m)
+            return fail(ICP_ERR_HIP, "icp_batch_downsample: a cloud's cell count is out of range");   // (cannot happen: every cloud has a point)
+    if (int rc = thin_allocate(th, made)) return rc;
+    thin_args(a, th);
+    HIP_TRY(icp::launch_batch_voxel_compact(a, th.st));
+    if (int rc = thin_download(th)) return rc;
+    return thin_finish(th);
+}
+
+// icp_batch_remove_outliers after its argument checks
 int remove_outliers(icp_batch* src, const std::vector<icp::OutlierRule>& rules, int32_t* moving_map_out, int32_t* model_map_out,
                     double* moving_score_out, double* model_score_out, double* stats_out, icp_batch** made)
 {
-    icp_ctx* c = src->ctx;
-    hipStream_t st = c->stream;
-    const int count = src->count, n_clouds = 2 * count;
-    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
-    std::vector<icp::BatchItem> items, new_items;
-    std::vector<int> bad((size_t)n_clouds);
-    std::vector<int32_t> kept((size_t)n_clouds), hmap;
-    std::vector<double> hscore, hstats;
-    long long tmp_plane = 0;
-    int cap = 8;
-    for (int k = 0; k < n_clouds; ++k) {
-        const int side = k < count ? 0 : 1;
-        const icp::BatchPair& pr = src->pairs[k - side * count];
-        icp::VoxelCloud& cl = clouds[k];
-        cl.side = side;
-        cl.n = side ? pr.m : pr.n;
-        cl.src_off = side ? pr.q_off : pr.p_off;
-        cl.tmp_off = tmp_plane;
-        cl.dst_off = 0;
-        tmp_plane += icp::round_up(cl.n, icp::BATCH_ALIGN);
-        for (int first = 0; first < cl.n; first += icp::BATCH_ITEM)
-            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, cl.n - first), 0});
-        if (rules[k].kind == ICP_OUTLIER_STATISTICAL) cap = std::max(cap, rules[k].neighbours <= 8 ? 8 : rules[k].neighbours <= 16 ? 16 : 32);
-    }
-    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
-    OutlierTmp t(st);
-    HIP_TRY(t.clouds.ensure(clouds.size() * sizeof(icp::VoxelCloud)));
-    HIP_TRY(t.items.ensure(items.size() * sizeof(icp::BatchItem)));
-    HIP_TRY(t.rules.ensure(rules.size() * sizeof(icp::OutlierRule)));
-    HIP_TRY(t.score.ensure((size_t)tmp_plane * sizeof(double)));
-    HIP_TRY(t.map.ensure((size_t)tmp_plane * sizeof(int32_t)));
-    HIP_TRY(t.stats.ensure(4 * (size_t)n_clouds * sizeof(double)));
-    HIP_TRY(t.count.ensure((size_t)n_clouds * sizeof(int32_t)));
-    HIP_TRY(t.bad.ensure((size_t)n_clouds * sizeof(int)));
-    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(t.items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(t.rules.p, rules.data(), rules.size() * sizeof(icp::OutlierRule), hipMemcpyHostToDevice, st));
+    enum { STATS = T_OWN };
+    std::vector<double> hstats;
+    Thin th(src);
+    th.map_out[0] = moving_map_out;
+    th.map_out[1] = model_map_out;
+    th.value_out[0] = moving_score_out;
+    th.value_out[1] = model_score_out;
+    if (int rc = thin_begin(th, rules.size() * sizeof(icp::OutlierRule), true, true)) return rc;
+    HIP_TRY(th.t.buf[STATS].ensure(4 * rules.size() * sizeof(double)));
+    if (int rc = thin_upload(th, rules.data(), rules.size() * sizeof(icp::OutlierRule))) return rc;
     icp::BatchOutlierArgs a{};
-    a.precision = src->prec;
-    a.cap = cap;
-    a.clouds = (const icp::VoxelCloud*)t.clouds.p;
-    a.n_clouds = n_clouds;
-    a.items = (const icp::BatchItem*)t.items.p;
-    a.n_items = (int)items.size();
-    a.rules = (const icp::OutlierRule*)t.rules.p;
-    a.src[0] = src->P0.p;
-    a.src[1] = src->Q.p;
-    a.src_plane[0] = src->p_plane;
-    a.src_plane[1] = src->q_plane;
-    a.tmp_plane = tmp_plane;
-    a.score = (double*)t.score.p;
-    a.map = (int32_t*)t.map.p;
-    a.stats = (double*)t.stats.p;
-    a.count = (int32_t*)t.count.p;
-    a.bad = (int*)t.bad.p;
-    HIP_TRY(icp::launch_batch_outlier_scan(a, st));
-    HIP_TRY(hipMemcpyAsync(bad.data(), t.bad.p, bad.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(kept.data(), t.count.p, kept.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));   // the first wait: the new batch's layout needs every cloud's count
-    for (int p = 0; p < count; ++p)
+    thin_args(a, th);
+    a.cap = 8;
+    for (const icp::OutlierRule& r : rules)
+        if (r.kind == ICP_OUTLIER_STATISTICAL) a.cap = std::max(a.cap, list_cap(r.neighbours));
+    a.rules = (const icp::OutlierRule*)th.t.buf[T_RULES].p;
+    a.score = (double*)th.t.buf[T_VALUE].p;
+    a.stats = (double*)th.t.buf[STATS].p;
+    a.bad = (int*)th.t.buf[T_FLAG].p;
+    HIP_TRY(icp::launch_batch_outlier_scan(a, th.st));
+    if (int rc = thin_counts(th)) return rc;
+    for (int p = 0; p < th.count; ++p)
         for (int side = 0; side < 2; ++side) {
-            const size_t k = (size_t)side * count + p;
-            const std::string where = std::string(": pair ") + std::to_string(p) + (side ? ", model" : ", moving cloud");
-            if (bad[k]) return fail(ICP_ERR_INVALID, "the mean or the deviation of a cloud's neighbour distances is not finite" + where);
-            if (kept[k] < 1) return fail(ICP_ERR_EMPTY, "the rule keeps no point of the cloud" + where);
-            if (kept[k] > clouds[k].n) return fail(ICP_ERR_HIP, "icp_batch_remove_outliers: a cloud's kept count is out of range");   // (cannot happen)
+            const size_t k = (size_t)side * th.count + p;
+            if (th.flag[k]) return fail(ICP_ERR_INVALID, "the mean or the deviation of a cloud's neighbour distances is not finite" + where(p, side));
+            if (th.kept[k] < 1) return fail(ICP_ERR_EMPTY, "the rule keeps no point of the cloud" + where(p, side));
+            if (th.kept[k] > th.cl.clouds[k].n) return fail(ICP_ERR_HIP, "icp_batch_remove_outliers: a cloud's kept count is out of range");   // (cannot happen)
         }
-    std::vector<int64_t> moff((size_t)count + 1, 0), qoff((size_t)count + 1, 0);
-    for (int p = 0; p < count; ++p) {
-        moff[p + 1] = moff[p] + kept[p];
-        qoff[p + 1] = qoff[p] + kept[(size_t)count + p];
-    }
-    if (int rc = lay_out(c, count, src->prec, moff.data(), qoff.data(), made)) return rc;
-    icp_batch* nb = *made;
-    if (int rc = allocate(nb, new_items)) return rc;
-    for (int k = 0; k < n_clouds; ++k) clouds[k].dst_off = k < count ? nb->pairs[k].p_off : nb->pairs[k - count].q_off;
-    const size_t pb = 3 * (size_t)nb->p_plane * nb->esize, qb = 3 * (size_t)nb->q_plane * nb->esize;
-    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(nb->P0.p, 0, pb, st));   // (the padding between the clouds: all-zero bytes, as an upload leaves it)
-    HIP_TRY(hipMemsetAsync(nb->Q.p, 0, qb, st));
-    a.dst[0] = nb->P0.p;
-    a.dst[1] = nb->Q.p;
-    a.dst_plane[0] = nb->p_plane;
-    a.dst_plane[1] = nb->q_plane;
-    HIP_TRY(icp::launch_batch_outlier_compact(a, st));
-    HIP_TRY(hipMemcpyAsync(nb->P.p, nb->P0.p, pb, hipMemcpyDeviceToDevice, st));
-    if (moving_map_out || model_map_out) {
-        hmap.resize((size_t)tmp_plane);
-        HIP_TRY(hipMemcpyAsync(hmap.data(), t.map.p, hmap.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    if (moving_score_out || model_score_out) {
-        hscore.resize((size_t)tmp_plane);
-        HIP_TRY(hipMemcpyAsync(hscore.data(), t.score.p, hscore.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
+    if (int rc = thin_allocate(th, made)) return rc;
+    thin_args(a, th);
+    HIP_TRY(icp::launch_batch_outlier_compact(a, th.st));
+    if (int rc = thin_download(th)) return rc;
     if (stats_out) {
-        hstats.resize(4 * (size_t)n_clouds);
-        HIP_TRY(hipMemcpyAsync(hstats.data(), t.stats.p, hstats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        hstats.resize(4 * rules.size());
+        HIP_TRY(hipMemcpyAsync(hstats.data(), th.t.buf[STATS].p, hstats.size() * sizeof(double), hipMemcpyDeviceToHost, th.st));
     }
-    HIP_TRY(hipStreamSynchronize(st));   // the second wait: the host vectors go, the temporaries are freed
-    for (int p = 0; p < count; ++p) {
-        const size_t np = (size_t)src->pairs[p].n, mp = (size_t)src->pairs[p].m;
-        const long long to = clouds[p].tmp_off, tq = clouds[(size_t)count + p].tmp_off;
-        if (moving_map_out) std::memcpy(moving_map_out + src->moff[p], hmap.data() + to, np * sizeof(int32_t));
-        if (model_map_out) std::memcpy(model_map_out + src->qoff[p], hmap.data() + tq, mp * sizeof(int32_t));
-        if (moving_score_out) std::memcpy(moving_score_out + src->moff[p], hscore.data() + to, np * sizeof(double));
-        if (model_score_out) std::memcpy(model_score_out + src->qoff[p], hscore.data() + tq, mp * sizeof(double));
-    }
+    if (int rc = thin_finish(th)) return rc;
     if (stats_out) std::memcpy(stats_out, hstats.data(), hstats.size() * sizeof(double));
     return ICP_OK;
 }
 
-// the temporaries of one icp_batch_select_keypoints, released as VoxelTmp's are
-struct KeypointTmp {
-    hipStream_t st;
-    DevBuf clouds, items, rules, sal, map, count;
-    explicit KeypointTmp(hipStream_t s) : st(s) {}
-    ~KeypointTmp()
-    {
-        (void)hipStreamSynchronize(st);
-        for (DevBuf* d : {&clouds, &items, &rules, &sal, &map, &count}) d->release();
-    }
-};
-
-// icp_batch_select_keypoints after its argument checks; *made: the new batch as far as it got (the caller releases it on failure).
-// batch_iss_saliency  ->  batch_iss_select  ->  batch_keypoint_rank  ->  [D2H: 2 x count counts, the first wait; lay_out + allocate]
-// ->  batch_keypoint_compact  ->  the second wait, which brings the optional outputs.  Four launches, two waits; no output array is
-// written before the call can no longer be refused for its data.
+// icp_batch_select_keypoints after its argument checks
 int select_keypoints(icp_batch* src, const std::vector<icp::KeypointRule>& rules, int32_t* moving_map_out, int32_t* model_map_out,
                      double* moving_saliency_out, double* model_saliency_out, int32_t* count_out, icp_batch** made)
 {
-    icp_ctx* c = src->ctx;
-    hipStream_t st = c->stream;
-    const int count = src->count, n_clouds = 2 * count;
-    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
-    std::vector<icp::BatchItem> items, new_items;
-    std::vector<int32_t> kept((size_t)n_clouds), hmap;
-    std::vector<double> hsal;
-    long long tmp_plane = 0;
-    for (int k = 0; k < n_clouds; ++k) {
-        const int side = k < count ? 0 : 1;
-        const icp::BatchPair& pr = src->pairs[k - side * count];
-        icp::VoxelCloud& cl = clouds[k];
-        cl.side = side;
-        cl.n = side ? pr.m : pr.n;
-        cl.src_off = side ? pr.q_off : pr.p_off;
-        cl.tmp_off = tmp_plane;
-        cl.dst_off = 0;
-        tmp_plane += icp::round_up(cl.n, icp::BATCH_ALIGN);
-        for (int first = 0; first < cl.n; first += icp::BATCH_ITEM)
-            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, cl.n - first), 0});
-    }
-    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
-    KeypointTmp t(st);
-    HIP_TRY(t.clouds.ensure(clouds.size() * sizeof(icp::VoxelCloud)));
-    HIP_TRY(t.items.ensure(items.size() * sizeof(icp::BatchItem)));
-    HIP_TRY(t.rules.ensure(rules.size() * sizeof(icp::KeypointRule)));
-    HIP_TRY(t.sal.ensure((size_t)tmp_plane * sizeof(double)));
-    HIP_TRY(t.map.ensure((size_t)tmp_plane * sizeof(int32_t)));
-    HIP_TRY(t.count.ensure((size_t)n_clouds * sizeof(int32_t)));
-    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(t.items.p, items.data(), items.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(t.rules.p, rules.data(), rules.size() * sizeof(icp::KeypointRule), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(t.sal.p, 0, (size_t)tmp_plane * sizeof(double), st));   // (the padding between the clouds: never read, never random)
-    HIP_TRY(hipMemsetAsync(t.map.p, 0, (size_t)tmp_plane * sizeof(int32_t), st));
+    Thin th(src);
+    th.map_out[0] = moving_map_out;
+    th.map_out[1] = model_map_out;
+    th.value_out[0] = moving_saliency_out;
+    th.value_out[1] = model_saliency_out;
+    if (int rc = thin_begin(th, rules.size() * sizeof(icp::KeypointRule), true, false)) return rc;
+    if (int rc = thin_upload(th, rules.data(), rules.size() * sizeof(icp::KeypointRule))) return rc;
+    HIP_TRY(hipMemsetAsync(th.t.buf[T_VALUE].p, 0, (size_t)th.cl.tmp_plane * sizeof(double), th.st));   // (the padding between the clouds: never read, never random)
+    HIP_TRY(hipMemsetAsync(th.t.buf[T_MAP].p, 0, (size_t)th.cl.tmp_plane * sizeof(int32_t), th.st));
     icp::BatchKeypointArgs a{};
-    a.precision = src->prec;
-    a.clouds = (const icp::VoxelCloud*)t.clouds.p;
-    a.n_clouds = n_clouds;
-    a.items = (const icp::BatchItem*)t.items.p;
-    a.n_items = (int)items.size();
-    a.rules = (const icp::KeypointRule*)t.rules.p;
-    a.src[0] = src->P0.p;
-    a.src[1] = src->Q.p;
-    a.src_plane[0] = src->p_plane;
-    a.src_plane[1] = src->q_plane;
-    a.tmp_plane = tmp_plane;
-    a.sal = (double*)t.sal.p;
-    a.map = (int32_t*)t.map.p;
-    a.count = (int32_t*)t.count.p;
-    HIP_TRY(icp::launch_batch_keypoint_select(a, st));
-    HIP_TRY(hipMemcpyAsync(kept.data(), t.count.p, kept.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));   // the first wait: the new batch's layout needs every cloud's count
-    for (int p = 0; p < count; ++p)
+    thin_args(a, th);
+    a.rules = (const icp::KeypointRule*)th.t.buf[T_RULES].p;
+    a.sal = (double*)th.t.buf[T_VALUE].p;
+    HIP_TRY(icp::launch_batch_keypoint_select(a, th.st));
+    if (int rc = thin_counts(th)) return rc;
+    for (int p = 0; p < th.count; ++p)
         for (int side = 0; side < 2; ++side) {
-            const size_t k = (size_t)side * count + p;
-            const std::string where = std::string(": pair ") + std::to_string(p) + (side ? ", model" : ", moving cloud");
-            if (kept[k] < 1) return fail(ICP_ERR_EMPTY, "the rule keeps no point of the cloud" + where);
-            if (kept[k] > clouds[k].n) return fail(ICP_ERR_HIP, "icp_batch_select_keypoints: a cloud's kept count is out of range");   // (cannot happen)
+            const size_t k = (size_t)side * th.count + p;
+            if (th.kept[k] < 1) return fail(ICP_ERR_EMPTY, "the rule keeps no point of the cloud" + where(p, side));
+            if (th.kept[k] > th.cl.clouds[k].n) return fail(ICP_ERR_HIP, "icp_batch_select_keypoints: a cloud's kept count is out of range");   // (cannot happen)
         }
-    std::vector<int64_t> moff((size_t)count + 1, 0), qoff((size_t)count + 1, 0);
-    for (int p = 0; p < count; ++p) {
-        moff[p + 1] = moff[p] + kept[p];
-        qoff[p + 1] = qoff[p] + kept[(size_t)count + p];
-    }
-    if (int rc = lay_out(c, count, src->prec, moff.data(), qoff.data(), made)) return rc;
-    icp_batch* nb = *made;
-    if (int rc = allocate(nb, new_items)) return rc;
-    for (int k = 0; k < n_clouds; ++k) clouds[k].dst_off = k < count ? nb->pairs[k].p_off : nb->pairs[k - count].q_off;
-    const size_t pb = 3 * (size_t)nb->p_plane * nb->esize, qb = 3 * (size_t)nb->q_plane * nb->esize;
-    HIP_TRY(hipMemcpyAsync(t.clouds.p, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(nb->P0.p, 0, pb, st));   // (the padding between the clouds: all-zero bytes, as an upload leaves it)
-    HIP_TRY(hipMemsetAsync(nb->Q.p, 0, qb, st));
-    a.dst[0] = nb->P0.p;
-    a.dst[1] = nb->Q.p;
-    a.dst_plane[0] = nb->p_plane;
-    a.dst_plane[1] = nb->q_plane;
+    if (int rc = thin_allocate(th, made)) return rc;
+    thin_args(a, th);
     for (int sd = 0; sd < 2; ++sd) {   // the descriptors of the kept points, where the source holds that side's
         if (!src->have_feat[sd]) continue;
-        const size_t fb = ICP_FEATURE_BINS * (size_t)(sd ? nb->q_plane : nb->p_plane) * sizeof(double);
-        HIP_TRY(nb->feat[sd].ensure(fb));
-        HIP_TRY(hipMemsetAsync(nb->feat[sd].p, 0, fb, st));   // (the padding, as icp_batch_compute_features leaves it)
+        const size_t fb = ICP_FEATURE_BINS * plane_elems(th.nb, sd) * sizeof(double);
+        HIP_TRY(th.nb->feat[sd].ensure(fb));
+        HIP_TRY(hipMemsetAsync(th.nb->feat[sd].p, 0, fb, th.st));   // (the padding, as icp_batch_compute_features leaves it)
         a.src_feat[sd] = (const unsigned long long*)src->feat[sd].p;
-        a.dst_feat[sd] = (unsigned long long*)nb->feat[sd].p;
+        a.dst_feat[sd] = (unsigned long long*)th.nb->feat[sd].p;
     }
-    HIP_TRY(icp::launch_batch_keypoint_compact(a, st));
-    HIP_TRY(hipMemcpyAsync(nb->P.p, nb->P0.p, pb, hipMemcpyDeviceToDevice, st));
-    if (moving_map_out || model_map_out) {
-        hmap.resize((size_t)tmp_plane);
-        HIP_TRY(hipMemcpyAsync(hmap.data(), t.map.p, hmap.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    if (moving_saliency_out || model_saliency_out) {
-        hsal.resize((size_t)tmp_plane);
-        HIP_TRY(hipMemcpyAsync(hsal.data(), t.sal.p, hsal.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));   // the second wait: the host vectors go, the temporaries are freed
-    nb->have_feat[0] = src->have_feat[0];
-    nb->have_feat[1] = src->have_feat[1];
-    for (int p = 0; p < count; ++p) {
-        const size_t np = (size_t)src->pairs[p].n, mp = (size_t)src->pairs[p].m;
-        const long long to = clouds[p].tmp_off, tq = clouds[(size_t)count + p].tmp_off;
-        if (moving_map_out) std::memcpy(moving_map_out + src->moff[p], hmap.data() + to, np * sizeof(int32_t));
-        if (model_map_out) std::memcpy(model_map_out + src->qoff[p], hmap.data() + tq, mp * sizeof(int32_t));
-        if (moving_saliency_out) std::memcpy(moving_saliency_out + src->moff[p], hsal.data() + to, np * sizeof(double));
-        if (model_saliency_out) std::memcpy(model_saliency_out + src->qoff[p], hsal.data() + tq, mp * sizeof(double));
-    }
-    if (count_out) std::memcpy(count_out, kept.data(), kept.size() * sizeof(int32_t));
+    HIP_TRY(icp::launch_batch_keypoint_compact(a, th.st));
+    if (int rc = thin_download(th)) return rc;
+    if (int rc = thin_finish(th)) return rc;
+    th.nb->have_feat[0] = src->have_feat[0];
+    th.nb->have_feat[1] = src->have_feat[1];
+    if (count_out) std::memcpy(count_out, th.kept.data(), th.kept.size() * sizeof(int32_t));
     return ICP_OK;
 }
 
@@ -1015,6 +939,20 @@ int download_indices(icp_batch* b, bool contributing, int32_t* out, uint8_t* mas
     return ICP_OK;
 }
 
+// the end of a call that thins src into `made`: the new batch to the caller, or -- src was only read -- what the call enqueued ends
+// before its host vectors and the new batch go
+int hand_over(icp_batch* src, int rc, icp_batch* made, icp_batch** out)
+{
+    if (rc != ICP_OK) {
+        (void)hipStreamSynchronize(src->ctx->stream);
+        (void)hipGetLastError();
+        if (made) release(made);
+        return rc;
+    }
+    *out = made;
+    return ICP_OK;
+}
+
 }  // namespace
 
 #pragma GCC visibility push(default)   // (the C ABI)
@@ -1060,21 +998,13 @@ int icp_batch_downsample(icp_batch* src, const double* voxel_moving, const doubl
             const double* given = side ? voxel_model : voxel_moving;
             const double v = given ? given[p] : 0.0;
             if (!(std::isfinite(v) && v >= 0.0))   // (NaN fails both)
-                return fail(ICP_ERR_INVALID, std::string("a voxel edge must be finite and > 0, or exactly 0 (copy): pair ") + std::to_string(p) +
-                                                 (side ? ", model" : ", moving cloud"));
+                return fail(ICP_ERR_INVALID, "a voxel edge must be finite and > 0, or exactly 0 (copy)" + where(p, side));
             voxel[(size_t)side * src->count + p] = v;
         }
     ScopedPin pin(src->ctx);
     icp_batch* made = nullptr;
     const int rc = downsample(src, voxel, moving_map_out, model_map_out, &made);
-    if (rc != ICP_OK) {   // src was only read; what the call enqueued ends before its host vectors and the new batch go
-        (void)hipStreamSynchronize(src->ctx->stream);
-        (void)hipGetLastError();
-        if (made) release(made);
-        return rc;
-    }
-    *out = made;
-    return ICP_OK;
+    return hand_over(src, rc, made, out);
 }
 
 int icp_batch_remove_outliers(icp_batch* src, const icp_outlier_rule* moving, const icp_outlier_rule* model, int32_t* moving_map_out,
@@ -1092,34 +1022,27 @@ int icp_batch_remove_outliers(icp_batch* src, const icp_outlier_rule* moving, co
             if (!given) continue;
             const icp_outlier_rule& r = given[p];
             const int n = side ? src->pairs[p].m : src->pairs[p].n;
-            const std::string where = std::string(": pair ") + std::to_string(p) + (side ? ", model" : ", moving cloud");
+            const std::string at = where(p, side);
             if (r.kind == ICP_OUTLIER_NONE) continue;
             if (r.kind == ICP_OUTLIER_STATISTICAL) {
                 if (r.neighbours < 1 || r.neighbours > ICP_OUTLIER_MAX_NEIGHBOURS)
-                    return fail(ICP_ERR_INVALID, "a statistical rule's neighbours (k) must lie in [1, ICP_OUTLIER_MAX_NEIGHBOURS]" + where);
-                if (n < r.neighbours + 1) return fail(ICP_ERR_INVALID, "a statistical rule needs a cloud of at least k + 1 points" + where);
+                    return fail(ICP_ERR_INVALID, "a statistical rule's neighbours (k) must lie in [1, ICP_OUTLIER_MAX_NEIGHBOURS]" + at);
+                if (n < r.neighbours + 1) return fail(ICP_ERR_INVALID, "a statistical rule needs a cloud of at least k + 1 points" + at);
                 if (!(std::isfinite(r.value) && r.value >= 0.0))   // (NaN fails both)
-                    return fail(ICP_ERR_INVALID, "a statistical rule's ratio must be finite and >= 0" + where);
+                    return fail(ICP_ERR_INVALID, "a statistical rule's ratio must be finite and >= 0" + at);
             } else if (r.kind == ICP_OUTLIER_RADIUS) {
-                if (!(std::isfinite(r.value) && r.value > 0.0)) return fail(ICP_ERR_INVALID, "a radius must be finite and > 0" + where);
+                if (!(std::isfinite(r.value) && r.value > 0.0)) return fail(ICP_ERR_INVALID, "a radius must be finite and > 0" + at);
                 if (r.neighbours < 1 || r.neighbours > 65535)
-                    return fail(ICP_ERR_INVALID, "a radius rule's least number of neighbours must lie in [1, 65535]" + where);
+                    return fail(ICP_ERR_INVALID, "a radius rule's least number of neighbours must lie in [1, 65535]" + at);
             } else {
-                return fail(ICP_ERR_INVALID, "unknown outlier rule kind" + where);
+                return fail(ICP_ERR_INVALID, "unknown outlier rule kind" + at);
             }
             rules[(size_t)side * src->count + p] = icp::OutlierRule{r.kind, r.neighbours, r.value};
         }
     ScopedPin pin(src->ctx);
     icp_batch* made = nullptr;
     const int rc = remove_outliers(src, rules, moving_map_out, model_map_out, moving_score_out, model_score_out, stats_out, &made);
-    if (rc != ICP_OK) {   // src was only read; what the call enqueued ends before its host vectors and the new batch go
-        (void)hipStreamSynchronize(src->ctx->stream);
-        (void)hipGetLastError();
-        if (made) release(made);
-        return rc;
-    }
-    *out = made;
-    return ICP_OK;
+    return hand_over(src, rc, made, out);
 }
 
 int icp_batch_select_keypoints(icp_batch* src, const icp_keypoint_rule* moving, const icp_keypoint_rule* model, int32_t* moving_map_out,
@@ -1136,28 +1059,21 @@ int icp_batch_select_keypoints(icp_batch* src, const icp_keypoint_rule* moving, 
             const icp_keypoint_rule* given = side ? model : moving;
             if (!given) continue;
             const icp_keypoint_rule& r = given[p];
-            const std::string where = std::string(": pair ") + std::to_string(p) + (side ? ", model" : ", moving cloud");
+            const std::string at = where(p, side);
             if (r.kind == ICP_KEYPOINT_NONE) continue;
-            if (r.kind != ICP_KEYPOINT_ISS) return fail(ICP_ERR_INVALID, "unknown keypoint rule kind" + where);
+            if (r.kind != ICP_KEYPOINT_ISS) return fail(ICP_ERR_INVALID, "unknown keypoint rule kind" + at);
             if (r.min_neighbours < 1 || r.min_neighbours > 65535)
-                return fail(ICP_ERR_INVALID, "a keypoint rule's least number of neighbours must lie in [1, 65535]" + where);
+                return fail(ICP_ERR_INVALID, "a keypoint rule's least number of neighbours must lie in [1, 65535]" + at);
             if (!(std::isfinite(r.salient_radius) && r.salient_radius > 0.0) || !(std::isfinite(r.non_max_radius) && r.non_max_radius > 0.0))   // (NaN fails both)
-                return fail(ICP_ERR_INVALID, "a radius must be finite and > 0" + where);
+                return fail(ICP_ERR_INVALID, "a radius must be finite and > 0" + at);
             if (!(std::isfinite(r.gamma_21) && r.gamma_21 > 0.0) || !(std::isfinite(r.gamma_32) && r.gamma_32 > 0.0))
-                return fail(ICP_ERR_INVALID, "a gamma must be finite and > 0" + where);
+                return fail(ICP_ERR_INVALID, "a gamma must be finite and > 0" + at);
             rules[(size_t)side * src->count + p] = icp::KeypointRule{r.kind, r.min_neighbours, r.salient_radius, r.non_max_radius, r.gamma_21, r.gamma_32};
         }
     ScopedPin pin(src->ctx);
     icp_batch* made = nullptr;
     const int rc = select_keypoints(src, rules, moving_map_out, model_map_out, moving_saliency_out, model_saliency_out, count_out, &made);
-    if (rc != ICP_OK) {   // src was only read; what the call enqueued ends before its host vectors and the new batch go
-        (void)hipStreamSynchronize(src->ctx->stream);
-        (void)hipGetLastError();
-        if (made) release(made);
-        return rc;
-    }
-    *out = made;
-    return ICP_OK;
+    return hand_over(src, rc, made, out);
 }
 
 int icp_batch_get_offsets(icp_batch* b, int64_t* moving_off_out, int64_t* model_off_out)
@@ -1171,19 +1087,7 @@ int icp_batch_get_offsets(icp_batch* b, int64_t* moving_off_out, int64_t* model_
 int icp_batch_get_clouds(icp_batch* b, void* moving_aos_out, void* model_aos_out)
 {
     if (int rc = ready(b)) return rc;
-    std::vector<char> ps, qs;
-    if (moving_aos_out) {
-        ps.resize(3 * (size_t)b->p_plane * b->esize);
-        HIP_TRY(hipMemcpyAsync(ps.data(), b->P0.p, ps.size(), hipMemcpyDeviceToHost, b->ctx->stream));
-    }
-    if (model_aos_out) {
-        qs.resize(3 * (size_t)b->q_plane * b->esize);
-        HIP_TRY(hipMemcpyAsync(qs.data(), b->Q.p, qs.size(), hipMemcpyDeviceToHost, b->ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    if (moving_aos_out) planes_to_aos(b, ps, false, moving_aos_out);
-    if (model_aos_out) planes_to_aos(b, qs, true, model_aos_out);
-    return ICP_OK;
+    return download_clouds(b, b->P0.p, b->Q.p, moving_aos_out, model_aos_out);
 }
 
 void icp_batch_destroy(icp_batch* b)
@@ -1450,11 +1354,7 @@ int icp_batch_get_moving(icp_batch* b, void* aos_out)
 {
     if (int rc = ready(b)) return rc;
     if (!aos_out) return fail(ICP_ERR_INVALID, "aos_out == NULL");
-    std::vector<char> raw(3 * (size_t)b->p_plane * b->esize);
-    HIP_TRY(hipMemcpyAsync(raw.data(), b->P.p, raw.size(), hipMemcpyDeviceToHost, b->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    planes_to_aos(b, raw, false, aos_out);
-    return ICP_OK;
+    return download_clouds(b, b->P.p, nullptr, aos_out, nullptr);
 }
 
 int icp_batch_get_indices(icp_batch* b, int32_t* idx_out) { return download_indices(b, false, idx_out); }
@@ -1764,38 +1664,14 @@ int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighb
 
 namespace {
 
-// one side's covariances: the caller's 6 doubles per point, concatenated as the clouds <-> six planes laid out as the cloud's
-void cov_to_planes(const double* aos, const Side& s, std::vector<double>& planes)
+// the clouds, the work items and (ks: not NULL) every cloud's k of a launch into one buffer, as lay_out_args places them
+void pack_args(void* dst, const icp::ArgsLayout& lay, const icp::CloudList& cl, const std::vector<int>* ks)
 {
-    planes.assign(6 * (size_t)s.plane, 0.0);
-    for (size_t p = 0; p < s.dst.size(); ++p)
-        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
-            for (int k = 0; k < 6; ++k) planes[(size_t)(k * s.plane + s.dst[p] + i)] = aos[6 * (s.off[p] + i) + k];
+    char* d = static_cast<char*>(dst);
+    std::memcpy(d, cl.clouds.data(), cl.clouds.size() * sizeof(icp::VoxelCloud));
+    std::memcpy(d + lay.off_items, cl.items.data(), cl.items.size() * sizeof(icp::BatchItem));
+    if (ks) std::memcpy(d + lay.off_ints, ks->data(), ks->size() * sizeof(int));
 }
-
-void cov_from_planes(const std::vector<double>& planes, const Side& s, double* aos)
-{
-    for (size_t p = 0; p < s.dst.size(); ++p)
-        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
-            for (int k = 0; k < 6; ++k) aos[6 * (s.off[p] + i) + k] = planes[(size_t)(k * s.plane + s.dst[p] + i)];
-}
-
-// downloads the covariance planes of the sides whose output pointer is given (one wait) and lays them out as the caller's
-int download_covariances(icp_batch* b, double* const out[2])
-{
-    std::vector<double> h[2];
-    for (int side = 0; side < 2; ++side)
-        if (out[side]) {
-            h[side].resize(6 * (size_t)(side ? b->q_plane : b->p_plane));
-            HIP_TRY(hipMemcpyAsync(h[side].data(), b->cov[side].p, h[side].size() * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
-        }
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    for (int side = 0; side < 2; ++side)
-        if (out[side]) cov_from_planes(h[side], ::side(b, side != 0), out[side]);
-    return ICP_OK;
-}
-
-const char* side_name(int side) { return side ? ", model" : ", moving cloud"; }
 
 }  // namespace
 
@@ -1810,18 +1686,18 @@ int icp_batch_set_covariances(icp_batch* b, const double* moving_cov, const doub
         for (int p = 0; p < b->count; ++p)
             for (int64_t i = 6 * off[p]; i < 6 * off[p + 1]; ++i)
                 if (!std::isfinite(given[side][i]))
-                    return fail(ICP_ERR_INVALID, "a covariance has a NaN or an infinite value: pair " + std::to_string(p) + side_name(side));
+                    return fail(ICP_ERR_INVALID, "a covariance has a NaN or an infinite value" + where(p, side));
     }
     // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
     for (int side = 0; side < 2; ++side)
-        if (given[side]) HIP_TRY(b->cov[side].ensure(6 * (size_t)(side ? b->q_plane : b->p_plane) * sizeof(double)));
+        if (given[side]) HIP_TRY(b->cov[side].ensure(6 * plane_elems(b, side) * sizeof(double)));
     b->begun = false;   // a loop under way is discarded: its passes so far used other covariances (or none)
-    std::vector<double> h[2];
+    std::vector<char> h[2];
     for (int side = 0; side < 2; ++side) {
         if (!given[side]) continue;
         b->have_cov[side] = false;
-        cov_to_planes(given[side], ::side(b, side != 0), h[side]);
-        HIP_TRY(hipMemcpyAsync(b->cov[side].p, h[side].data(), h[side].size() * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+        to_planes<double, 6>(given[side], ::side(b, side != 0), h[side]);
+        HIP_TRY(hipMemcpyAsync(b->cov[side].p, h[side].data(), h[side].size(), hipMemcpyHostToDevice, b->ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
     for (int side = 0; side < 2; ++side)
@@ -1839,60 +1715,48 @@ int icp_batch_estimate_covariances(icp_batch* b, const int* k_moving, const int*
     if (regularisation == ICP_COV_FROBENIUS && !(std::isfinite(lambda) && lambda > 0.0))   // (NaN fails both)
         return fail(ICP_ERR_INVALID, "the lambda of ICP_COV_FROBENIUS must be finite and > 0");
     static_assert(icp::COV_MAX_K == ICP_COV_MAX_NEIGHBOURS, "the kernel's list holds the largest k");
-    const int count = b->count, n_clouds = 2 * count;
-    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
-    std::vector<icp::BatchItem> items;
-    std::vector<int> ks((size_t)n_clouds, 0);
+    const int count = b->count;
+    std::vector<int> ks(2 * (size_t)count, 0);   // every cloud's k, moving clouds first (0: its side is not asked for)
     int cap = 8;
-    for (int k = 0; k < n_clouds; ++k) {   // the 2 * count clouds, moving clouds first; work items for the sides asked for
-        const int side = k < count ? 0 : 1, p = k - side * count;
-        const icp::BatchPair& pr = b->pairs[p];
-        clouds[k] = icp::VoxelCloud{side ? pr.q_off : pr.p_off, 0, 0, side ? pr.m : pr.n, side};
-        if (!given[side]) continue;
-        const int kk = given[side][p];
-        if (kk < ICP_COV_MIN_NEIGHBOURS || kk > ICP_COV_MAX_NEIGHBOURS)
-            return fail(ICP_ERR_INVALID, "the neighbours (k) of a covariance must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]: pair " +
-                                             std::to_string(p) + side_name(side));
-        if (clouds[k].n < kk + 1)
-            return fail(ICP_ERR_INVALID, "covariances from k neighbours need a cloud of at least k + 1 points: pair " + std::to_string(p) + side_name(side));
-        ks[k] = kk;
-        cap = std::max(cap, kk <= 8 ? 8 : kk <= 16 ? 16 : 32);
-        for (int first = 0; first < clouds[k].n; first += icp::BATCH_ITEM)
-            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, clouds[k].n - first), 0});
-    }
-    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    for (int side = 0; side < 2; ++side)
+        for (int p = 0; given[side] && p < count; ++p) {
+            const int kk = given[side][p];
+            if (kk < ICP_COV_MIN_NEIGHBOURS || kk > ICP_COV_MAX_NEIGHBOURS)
+                return fail(ICP_ERR_INVALID, "the neighbours (k) of a covariance must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]" + where(p, side));
+            if ((side ? b->pairs[p].m : b->pairs[p].n) < kk + 1)
+                return fail(ICP_ERR_INVALID, "covariances from k neighbours need a cloud of at least k + 1 points" + where(p, side));
+            ks[(size_t)side * count + p] = kk;
+            cap = std::max(cap, list_cap(kk));
+        }
+    const bool want[2] = {given[0] != nullptr, given[1] != nullptr};   // work items for the sides asked for
+    icp::CloudList cl;
+    if (!icp::list_clouds(b->pairs, want, cl)) return fail(ICP_ERR_INVALID, "too many work items for one batch");
     icp_ctx* c = b->ctx;
     hipStream_t st = c->stream;
     ScopedPin pin(c);
     // one device buffer and one pinned host buffer of the batch's hold the clouds, the items and the k of the call, so that nothing
     // has to outlive it on the stack: the call returns without a host wait unless an output is wanted.  The allocations come
     // before the batch changes: a call refused for want of memory leaves it as it was
-    auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-    const size_t off_items = up16(clouds.size() * sizeof(icp::VoxelCloud));
-    const size_t off_k = off_items + up16(items.size() * sizeof(icp::BatchItem));
-    const size_t arg_bytes = off_k + ks.size() * sizeof(int);
+    const icp::ArgsLayout lay = icp::lay_out_args(cl.clouds.size(), cl.items.size(), ks.size());
     if (b->cov_ev) HIP_TRY(hipEventSynchronize(b->cov_ev));   // (the call before has long read the host buffer: no wait in practice)
     else HIP_TRY(hipEventCreateWithFlags(&b->cov_ev, hipEventDisableTiming));
-    if (arg_bytes > b->h_cov_cap) {
+    if (lay.bytes > b->h_cov_cap) {
         if (b->h_cov_args) (void)hipHostFree(b->h_cov_args);
         b->h_cov_args = nullptr;
         b->h_cov_cap = 0;
-        HIP_TRY(hipHostMalloc(&b->h_cov_args, arg_bytes, hipHostMallocDefault));
-        b->h_cov_cap = arg_bytes;
+        HIP_TRY(hipHostMalloc(&b->h_cov_args, lay.bytes, hipHostMallocDefault));
+        b->h_cov_cap = lay.bytes;
     }
-    HIP_TRY(b->cov_args.ensure(arg_bytes));
+    HIP_TRY(b->cov_args.ensure(lay.bytes));
     for (int side = 0; side < 2; ++side)
-        if (given[side]) HIP_TRY(b->cov[side].ensure(6 * (size_t)(side ? b->q_plane : b->p_plane) * sizeof(double)));
+        if (given[side]) HIP_TRY(b->cov[side].ensure(6 * plane_elems(b, side) * sizeof(double)));
     b->begun = false;   // a loop under way is discarded
     for (int side = 0; side < 2; ++side)
         if (given[side]) b->have_cov[side] = false;
-    char* hs = static_cast<char*>(b->h_cov_args);
-    std::memcpy(hs, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud));
-    std::memcpy(hs + off_items, items.data(), items.size() * sizeof(icp::BatchItem));
-    std::memcpy(hs + off_k, ks.data(), ks.size() * sizeof(int));
-    HIP_TRY(hipMemcpyAsync(b->cov_args.p, hs, arg_bytes, hipMemcpyHostToDevice, st));
+    pack_args(b->h_cov_args, lay, cl, &ks);
+    HIP_TRY(hipMemcpyAsync(b->cov_args.p, b->h_cov_args, lay.bytes, hipMemcpyHostToDevice, st));
     for (int side = 0; side < 2; ++side)   // (the padding between the clouds: never read, never random)
-        if (given[side]) HIP_TRY(hipMemsetAsync(b->cov[side].p, 0, 6 * (size_t)(side ? b->q_plane : b->p_plane) * sizeof(double), st));
+        if (given[side]) HIP_TRY(hipMemsetAsync(b->cov[side].p, 0, 6 * plane_elems(b, side) * sizeof(double), st));
     const char* ds = static_cast<const char*>(b->cov_args.p);
     icp::BatchCovArgs a{};
     a.precision = b->prec;
@@ -1900,9 +1764,9 @@ int icp_batch_estimate_covariances(icp_batch* b, const int* k_moving, const int*
     a.regularisation = regularisation;
     a.lambda = regularisation == ICP_COV_FROBENIUS ? lambda : 0.0;
     a.clouds = reinterpret_cast<const icp::VoxelCloud*>(ds);
-    a.items = reinterpret_cast<const icp::BatchItem*>(ds + off_items);
-    a.n_items = (int)items.size();
-    a.k = reinterpret_cast<const int*>(ds + off_k);
+    a.items = reinterpret_cast<const icp::BatchItem*>(ds + lay.off_items);
+    a.n_items = (int)cl.items.size();
+    a.k = reinterpret_cast<const int*>(ds + lay.off_ints);
     a.src[0] = b->P0.p;
     a.src[1] = b->Q.p;
     a.src_plane[0] = b->p_plane;
@@ -1913,7 +1777,7 @@ int icp_batch_estimate_covariances(icp_batch* b, const int* k_moving, const int*
     HIP_TRY(hipEventRecord(b->cov_ev, st));
     double* const out[2] = {given[0] ? moving_cov_out : nullptr, given[1] ? model_cov_out : nullptr};
     if (out[0] || out[1]) {
-        if (int rc = download_covariances(b, out)) return rc;   // (the one wait of a call that wants an output)
+        if (int rc = download_planes<double, 6>(b, b->cov[0].p, b->cov[1].p, out[0], out[1])) return rc;   // (the one wait of a call that wants an output)
     }
     for (int side = 0; side < 2; ++side)
         if (given[side]) b->have_cov[side] = true;
@@ -1927,33 +1791,8 @@ int icp_batch_get_covariances(icp_batch* b, double* moving_cov_out, double* mode
     if (!out[0] && !out[1]) return fail(ICP_ERR_INVALID, "output pointer == NULL");
     for (int side = 0; side < 2; ++side)
         if (out[side] && !b->have_cov[side]) return fail(ICP_ERR_STATE, std::string("the batch holds no covariances of the ") + (side ? "models" : "moving clouds"));
-    return download_covariances(b, out);
+    return download_planes<double, 6>(b, b->cov[0].p, b->cov[1].p, out[0], out[1]);
 }
-
-namespace {
-
-// n doubles per point of one side, concatenated as the clouds <-> n planes laid out as the cloud's
-void dbl_to_planes(const double* aos, int per, const Side& s, std::vector<double>& planes)
-{
-    planes.assign((size_t)per * (size_t)s.plane, 0.0);
-    for (size_t p = 0; p < s.dst.size(); ++p)
-        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
-            for (int k = 0; k < per; ++k) planes[(size_t)(k * s.plane + s.dst[p] + i)] = aos[per * (s.off[p] + i) + k];
-}
-
-int download_gradients(icp_batch* b, double* out)
-{
-    std::vector<double> h(3 * (size_t)b->q_plane);
-    HIP_TRY(hipMemcpyAsync(h.data(), b->grad.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    const Side s = ::side(b, true);
-    for (size_t p = 0; p < s.dst.size(); ++p)
-        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
-            for (int k = 0; k < 3; ++k) out[3 * (s.off[p] + i) + k] = h[(size_t)(k * s.plane + s.dst[p] + i)];
-    return ICP_OK;
-}
-
-}  // namespace
 
 int icp_batch_set_intensities(icp_batch* b, const double* moving_I, const double* model_I)
 {
@@ -1966,19 +1805,19 @@ int icp_batch_set_intensities(icp_batch* b, const double* moving_I, const double
         for (int p = 0; p < b->count; ++p)
             for (int64_t i = off[p]; i < off[p + 1]; ++i)
                 if (!std::isfinite(given[side][i]))
-                    return fail(ICP_ERR_INVALID, "an intensity has a NaN or an infinite value: pair " + std::to_string(p) + side_name(side));
+                    return fail(ICP_ERR_INVALID, "an intensity has a NaN or an infinite value" + where(p, side));
     }
     // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
     for (int side = 0; side < 2; ++side)
-        if (given[side]) HIP_TRY(b->inten[side].ensure((size_t)(side ? b->q_plane : b->p_plane) * sizeof(double)));
+        if (given[side]) HIP_TRY(b->inten[side].ensure(plane_elems(b, side) * sizeof(double)));
     b->begun = false;   // a loop under way is discarded: its passes so far used other intensities (or none)
     if (given[1]) b->have_grad = false;   // (gradients belong to the model intensities they were made from)
-    std::vector<double> h[2];
+    std::vector<char> h[2];
     for (int side = 0; side < 2; ++side) {
         if (!given[side]) continue;
         b->have_int[side] = false;
-        dbl_to_planes(given[side], 1, ::side(b, side != 0), h[side]);
-        HIP_TRY(hipMemcpyAsync(b->inten[side].p, h[side].data(), h[side].size() * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+        to_planes<double, 1>(given[side], ::side(b, side != 0), h[side]);
+        HIP_TRY(hipMemcpyAsync(b->inten[side].p, h[side].data(), h[side].size(), hipMemcpyHostToDevice, b->ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
     for (int side = 0; side < 2; ++side)
@@ -2000,7 +1839,7 @@ int icp_batch_estimate_intensity_gradients(icp_batch* b, const int* k_model, dou
             return fail(ICP_ERR_INVALID, "the neighbours (k) of an intensity gradient must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]: pair " + std::to_string(p));
         if (b->pairs[p].m < kk + 1)
             return fail(ICP_ERR_INVALID, "intensity gradients from k neighbours need a model of at least k + 1 points: pair " + std::to_string(p));
-        cap = std::max(cap, kk <= 8 ? 8 : kk <= 16 ? 16 : 32);
+        cap = std::max(cap, list_cap(kk));
     }
     icp_ctx* c = b->ctx;
     hipStream_t st = c->stream;
@@ -2033,7 +1872,7 @@ int icp_batch_estimate_intensity_gradients(icp_batch* b, const int* k_model, dou
     HIP_TRY(icp::launch_batch_intensity_gradients(a, st));
     HIP_TRY(hipEventRecord(b->grad_ev, st));
     if (grad_out)
-        if (int rc = download_gradients(b, grad_out)) return rc;   // (the one wait of a call that wants the output)
+        if (int rc = download_planes<double, 3>(b, nullptr, b->grad.p, nullptr, grad_out)) return rc;   // (the one wait of a call that wants the output)
     b->have_grad = true;
     return ICP_OK;
 }
@@ -2044,13 +1883,13 @@ int icp_batch_set_intensity_gradients(icp_batch* b, const double* grad)
     if (!grad) return fail(ICP_ERR_INVALID, "grad == NULL");
     for (int p = 0; p < b->count; ++p)
         for (int64_t i = 3 * b->qoff[p]; i < 3 * b->qoff[p + 1]; ++i)
-            if (!std::isfinite(grad[i])) return fail(ICP_ERR_INVALID, "an intensity gradient has a NaN or an infinite value: pair " + std::to_string(p) + side_name(1));
+            if (!std::isfinite(grad[i])) return fail(ICP_ERR_INVALID, "an intensity gradient has a NaN or an infinite value" + where(p, 1));
     HIP_TRY(b->grad.ensure(3 * (size_t)b->q_plane * sizeof(double)));
     b->begun = false;   // a loop under way is discarded
     b->have_grad = false;
-    std::vector<double> h;
-    dbl_to_planes(grad, 3, ::side(b, true), h);
-    HIP_TRY(hipMemcpyAsync(b->grad.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+    std::vector<char> h;
+    to_planes<double, 3>(grad, ::side(b, true), h);
+    HIP_TRY(hipMemcpyAsync(b->grad.p, h.data(), h.size(), hipMemcpyHostToDevice, b->ctx->stream));
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
     b->have_grad = true;
     return ICP_OK;
@@ -2061,7 +1900,7 @@ int icp_batch_get_intensity_gradients(icp_batch* b, double* grad_out)
     if (int rc = ready(b)) return rc;
     if (!grad_out) return fail(ICP_ERR_INVALID, "output pointer == NULL");
     if (!b->have_grad) return fail(ICP_ERR_STATE, "the batch holds no intensity gradients");
-    return download_gradients(b, grad_out);
+    return download_planes<double, 3>(b, nullptr, b->grad.p, nullptr, grad_out);
 }
 
 int icp_batch_set_color_weight(icp_batch* b, const double* lambda)
@@ -2150,22 +1989,13 @@ namespace {
 
 constexpr int kRansacChunk = 4096;   // hypotheses per pair and scoring launch of icp_batch_ransac
 
-// one side's normals: the caller's 3 doubles per point, concatenated as the clouds -> three planes laid out as the cloud's
-void normals_to_planes(const double* aos, const Side& s, std::vector<double>& planes)
-{
-    planes.assign(3 * (size_t)s.plane, 0.0);
-    for (size_t p = 0; p < s.dst.size(); ++p)
-        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
-            for (int k = 0; k < 3; ++k) planes[(size_t)(k * s.plane + s.dst[p] + i)] = aos[3 * (s.off[p] + i) + k];
-}
-
 // downloads the descriptors of the sides whose output pointer is given (one wait) and lays them out as the caller's
 int download_features(icp_batch* b, double* const out[2])
 {
     std::vector<double> h[2];
     for (int sd = 0; sd < 2; ++sd)
         if (out[sd]) {
-            h[sd].resize(ICP_FEATURE_BINS * (size_t)(sd ? b->q_plane : b->p_plane));
+            h[sd].resize(ICP_FEATURE_BINS * plane_elems(b, sd));
             HIP_TRY(hipMemcpyAsync(h[sd].data(), b->feat[sd].p, h[sd].size() * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
         }
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
@@ -2347,84 +2177,70 @@ int compute_features(icp_batch* b, bool stored, const int* k_moving, const int* 
         } else if (!nrm_given[sd])
             return fail(ICP_ERR_INVALID, std::string("descriptors need normals on both sides: ") + (sd ? "model_normals" : "moving_normals") + " == NULL");
     }
-    const int count = b->count, n_clouds = 2 * count;
-    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
-    std::vector<icp::BatchItem> items;
-    std::vector<int> ks((size_t)n_clouds, 0);
+    const int count = b->count;
+    std::vector<int> ks(2 * (size_t)count, 0);   // every cloud's k, moving clouds first
     int cap = 8;
-    for (int k = 0; k < n_clouds; ++k) {   // the 2 * count clouds, moving clouds first
-        const int sd = k < count ? 0 : 1, p = k - sd * count;
-        const icp::BatchPair& pr = b->pairs[p];
-        clouds[k] = icp::VoxelCloud{sd ? pr.q_off : pr.p_off, 0, 0, sd ? pr.m : pr.n, sd};
-        const int kk = ks_given[sd][p];
-        if (kk < ICP_COV_MIN_NEIGHBOURS || kk > ICP_COV_MAX_NEIGHBOURS)
-            return fail(ICP_ERR_INVALID, "the neighbours (k) of a descriptor must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]: pair " +
-                                             std::to_string(p) + side_name(sd));
-        if (clouds[k].n < kk + 1)
-            return fail(ICP_ERR_INVALID, "descriptors from k neighbours need a cloud of at least k + 1 points: pair " + std::to_string(p) + side_name(sd));
-        const int64_t* off = sd ? b->qoff.data() : b->moff.data();
-        for (int64_t i = 3 * off[p]; !stored && i < 3 * off[p + 1]; ++i)
-            if (!std::isfinite(nrm_given[sd][i]))
-                return fail(ICP_ERR_INVALID, "a normal has a NaN or an infinite value: pair " + std::to_string(p) + side_name(sd));
-        ks[k] = kk;
-        cap = std::max(cap, kk <= 8 ? 8 : kk <= 16 ? 16 : 32);
-        for (int first = 0; first < clouds[k].n; first += icp::BATCH_ITEM)
-            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, clouds[k].n - first), 0});
-    }
-    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    for (int sd = 0; sd < 2; ++sd)
+        for (int p = 0; p < count; ++p) {
+            const int kk = ks_given[sd][p];
+            if (kk < ICP_COV_MIN_NEIGHBOURS || kk > ICP_COV_MAX_NEIGHBOURS)
+                return fail(ICP_ERR_INVALID, "the neighbours (k) of a descriptor must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]" + where(p, sd));
+            if ((sd ? b->pairs[p].m : b->pairs[p].n) < kk + 1)
+                return fail(ICP_ERR_INVALID, "descriptors from k neighbours need a cloud of at least k + 1 points" + where(p, sd));
+            const int64_t* off = sd ? b->qoff.data() : b->moff.data();
+            for (int64_t i = 3 * off[p]; !stored && i < 3 * off[p + 1]; ++i)
+                if (!std::isfinite(nrm_given[sd][i])) return fail(ICP_ERR_INVALID, "a normal has a NaN or an infinite value" + where(p, sd));
+            ks[(size_t)sd * count + p] = kk;
+            cap = std::max(cap, list_cap(kk));
+        }
+    const bool both[2] = {true, true};
+    icp::CloudList cl;
+    if (!icp::list_clouds(b->pairs, both, cl)) return fail(ICP_ERR_INVALID, "too many work items for one batch");
     icp_ctx* c = b->ctx;
     hipStream_t st = c->stream;
     ScopedPin pin(c);
     // the temporaries of the call: the normals, tau and the SPFH of both sides, the clouds, items and k.  The allocations come before
     // the batch changes: a call refused for want of memory leaves it as it was
-    struct Temps {
-        DevBuf nrm[2], tau[2], spfh[2], args;
-        ~Temps() { for (DevBuf* d : {&nrm[0], &nrm[1], &tau[0], &tau[1], &spfh[0], &spfh[1], &args}) d->release(); }
-    } tmp;
-    auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-    const size_t off_items = up16(clouds.size() * sizeof(icp::VoxelCloud));
-    const size_t off_k = off_items + up16(items.size() * sizeof(icp::BatchItem));
-    const size_t arg_bytes = off_k + ks.size() * sizeof(int);
-    std::vector<char> hs(arg_bytes, 0);
-    std::memcpy(hs.data(), clouds.data(), clouds.size() * sizeof(icp::VoxelCloud));
-    std::memcpy(hs.data() + off_items, items.data(), items.size() * sizeof(icp::BatchItem));
-    std::memcpy(hs.data() + off_k, ks.data(), ks.size() * sizeof(int));
-    HIP_TRY(tmp.args.ensure(arg_bytes));
-    std::vector<double> hn[2];
+    enum { NRM, TAU = 2, SPFH = 4, ARGS = 6 };   // (+ sd)
+    const icp::ArgsLayout lay = icp::lay_out_args(cl.clouds.size(), cl.items.size(), ks.size());
+    std::vector<char> hs(lay.bytes, 0), hn[2];
+    Temps tmp(st);
+    pack_args(hs.data(), lay, cl, &ks);
+    HIP_TRY(tmp.buf[ARGS].ensure(lay.bytes));
     for (int sd = 0; sd < 2; ++sd) {
-        const size_t plane = (size_t)(sd ? b->q_plane : b->p_plane);
-        if (!stored) HIP_TRY(tmp.nrm[sd].ensure(3 * plane * sizeof(double)));
-        HIP_TRY(tmp.tau[sd].ensure(plane * b->esize));
-        HIP_TRY(tmp.spfh[sd].ensure(ICP_FEATURE_BINS * plane * sizeof(double)));
+        const size_t plane = plane_elems(b, sd);
+        if (!stored) HIP_TRY(tmp.buf[NRM + sd].ensure(3 * plane * sizeof(double)));
+        HIP_TRY(tmp.buf[TAU + sd].ensure(plane * b->esize));
+        HIP_TRY(tmp.buf[SPFH + sd].ensure(ICP_FEATURE_BINS * plane * sizeof(double)));
         HIP_TRY(b->feat[sd].ensure(ICP_FEATURE_BINS * plane * sizeof(double)));
-        if (!stored) normals_to_planes(nrm_given[sd], ::side(b, sd != 0), hn[sd]);
+        if (!stored) to_planes<double, 3>(nrm_given[sd], ::side(b, sd != 0), hn[sd]);
     }
     b->have_feat[0] = b->have_feat[1] = false;
     b->have_match = false;   // (matches of other descriptors)
-    HIP_TRY(hipMemcpyAsync(tmp.args.p, hs.data(), arg_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(tmp.buf[ARGS].p, hs.data(), lay.bytes, hipMemcpyHostToDevice, st));
     for (int sd = 0; sd < 2; ++sd) {
-        const size_t plane = (size_t)(sd ? b->q_plane : b->p_plane);
-        if (!stored) HIP_TRY(hipMemcpyAsync(tmp.nrm[sd].p, hn[sd].data(), hn[sd].size() * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(tmp.spfh[sd].p, 0, ICP_FEATURE_BINS * plane * sizeof(double), st));   // (the padding between the clouds: never read, never random)
+        const size_t plane = plane_elems(b, sd);
+        if (!stored) HIP_TRY(hipMemcpyAsync(tmp.buf[NRM + sd].p, hn[sd].data(), hn[sd].size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(tmp.buf[SPFH + sd].p, 0, ICP_FEATURE_BINS * plane * sizeof(double), st));   // (the padding between the clouds: never read, never random)
         HIP_TRY(hipMemsetAsync(b->feat[sd].p, 0, ICP_FEATURE_BINS * plane * sizeof(double), st));
-        HIP_TRY(hipMemsetAsync(tmp.tau[sd].p, 0, plane * b->esize, st));
+        HIP_TRY(hipMemsetAsync(tmp.buf[TAU + sd].p, 0, plane * b->esize, st));
     }
-    const char* ds = static_cast<const char*>(tmp.args.p);
+    const char* ds = static_cast<const char*>(tmp.buf[ARGS].p);
     icp::BatchFeatArgs a{};
     a.precision = b->prec;
     a.cap = cap;
     a.clouds = reinterpret_cast<const icp::VoxelCloud*>(ds);
-    a.items = reinterpret_cast<const icp::BatchItem*>(ds + off_items);
-    a.n_items = (int)items.size();
-    a.k = reinterpret_cast<const int*>(ds + off_k);
+    a.items = reinterpret_cast<const icp::BatchItem*>(ds + lay.off_items);
+    a.n_items = (int)cl.items.size();
+    a.k = reinterpret_cast<const int*>(ds + lay.off_ints);
     a.src[0] = b->P0.p;
     a.src[1] = b->Q.p;
     a.src_plane[0] = b->p_plane;
     a.src_plane[1] = b->q_plane;
     for (int sd = 0; sd < 2; ++sd) {
-        a.nrm[sd] = (const double*)(stored ? b->pnrm[sd].p : tmp.nrm[sd].p);
-        a.tau[sd] = tmp.tau[sd].p;
-        a.spfh[sd] = (double*)tmp.spfh[sd].p;
+        a.nrm[sd] = (const double*)(stored ? b->pnrm[sd].p : tmp.buf[NRM + sd].p);
+        a.tau[sd] = tmp.buf[TAU + sd].p;
+        a.spfh[sd] = (double*)tmp.buf[SPFH + sd].p;
         a.feat[sd] = (double*)b->feat[sd].p;
     }
     const hipError_t le = icp::launch_batch_features(a, st);
@@ -2437,30 +2253,10 @@ int compute_features(icp_batch* b, bool stored, const int* k_moving, const int* 
     return ICP_OK;
 }
 
-// downloads the point-normal planes of the sides whose output pointer is given (one wait) and lays them out as the caller's
-int download_point_normals(icp_batch* b, double* const out[2])
-{
-    std::vector<double> h[2];
-    for (int sd = 0; sd < 2; ++sd)
-        if (out[sd]) {
-            h[sd].resize(3 * (size_t)(sd ? b->q_plane : b->p_plane));
-            HIP_TRY(hipMemcpyAsync(h[sd].data(), b->pnrm[sd].p, h[sd].size() * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
-        }
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    for (int sd = 0; sd < 2; ++sd) {
-        if (!out[sd]) continue;
-        const Side s = ::side(b, sd != 0);
-        for (size_t p = 0; p < s.dst.size(); ++p)
-            for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
-                for (int k = 0; k < 3; ++k) out[sd][3 * (s.off[p] + i) + k] = h[sd][(size_t)(k * s.plane + s.dst[p] + i)];
-    }
-    return ICP_OK;
-}
-
 // room for the point normals of one side; new room is zeroed, so that the padding between the clouds is never random
 int ensure_point_normals(icp_batch* b, int sd)
 {
-    const size_t bytes = 3 * (size_t)(sd ? b->q_plane : b->p_plane) * sizeof(double);
+    const size_t bytes = 3 * plane_elems(b, sd) * sizeof(double);
     if (b->pnrm[sd].p && bytes <= b->pnrm[sd].cap) return ICP_OK;
     HIP_TRY(b->pnrm[sd].ensure(bytes));
     HIP_TRY(hipMemsetAsync(b->pnrm[sd].p, 0, bytes, b->ctx->stream));
@@ -2472,32 +2268,22 @@ int ensure_point_normals(icp_batch* b, int sd)
 int ensure_normals_args(icp_batch* b)
 {
     if (b->n_nrm_items != 0) return ICP_OK;
-    const int count = b->count, n_clouds = 2 * count;
-    std::vector<icp::VoxelCloud> clouds((size_t)n_clouds);
-    std::vector<icp::BatchItem> items;
-    for (int k = 0; k < n_clouds; ++k) {
-        const int sd = k < count ? 0 : 1, p = k - sd * count;
-        const icp::BatchPair& pr = b->pairs[p];
-        clouds[k] = icp::VoxelCloud{sd ? pr.q_off : pr.p_off, 0, 0, sd ? pr.m : pr.n, sd};
-        for (int first = 0; first < clouds[k].n; first += icp::BATCH_ITEM)
-            items.push_back(icp::BatchItem{k, first, std::min(icp::BATCH_ITEM, clouds[k].n - first), 0});
-    }
-    if (items.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
-    const size_t off_items = (clouds.size() * sizeof(icp::VoxelCloud) + 15) / 16 * 16;
-    const size_t arg_bytes = off_items + items.size() * sizeof(icp::BatchItem);
+    const bool both[2] = {true, true};
+    icp::CloudList cl;
+    if (!icp::list_clouds(b->pairs, both, cl)) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+    const icp::ArgsLayout lay = icp::lay_out_args(cl.clouds.size(), cl.items.size(), 0);
+    const size_t view_bytes = cl.clouds.size() * 3 * sizeof(double);
     if (!b->nrm_ev) HIP_TRY(hipEventCreateWithFlags(&b->nrm_ev, hipEventDisableTiming));
-    if (!b->h_nrm_view) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_nrm_view), (size_t)n_clouds * 3 * sizeof(double), hipHostMallocDefault));
-    if (!b->h_nrm_args) HIP_TRY(hipHostMalloc(&b->h_nrm_args, arg_bytes, hipHostMallocDefault));
-    HIP_TRY(b->nrm_args.ensure(arg_bytes));
-    HIP_TRY(b->nrm_view.ensure((size_t)n_clouds * 3 * sizeof(double)));
-    HIP_TRY(b->nrm_cent.ensure((size_t)n_clouds * 3 * sizeof(double)));
-    char* hs = static_cast<char*>(b->h_nrm_args);
-    std::memset(hs, 0, arg_bytes);
-    std::memcpy(hs, clouds.data(), clouds.size() * sizeof(icp::VoxelCloud));
-    std::memcpy(hs + off_items, items.data(), items.size() * sizeof(icp::BatchItem));
-    HIP_TRY(hipMemcpyAsync(b->nrm_args.p, hs, arg_bytes, hipMemcpyHostToDevice, b->ctx->stream));   // (from a pinned buffer the batch keeps: no wait)
-    b->nrm_off_items = off_items;
-    b->n_nrm_items = (int)items.size();
+    if (!b->h_nrm_view) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_nrm_view), view_bytes, hipHostMallocDefault));
+    if (!b->h_nrm_args) HIP_TRY(hipHostMalloc(&b->h_nrm_args, lay.bytes, hipHostMallocDefault));
+    HIP_TRY(b->nrm_args.ensure(lay.bytes));
+    HIP_TRY(b->nrm_view.ensure(view_bytes));
+    HIP_TRY(b->nrm_cent.ensure(view_bytes));
+    std::memset(b->h_nrm_args, 0, lay.bytes);
+    pack_args(b->h_nrm_args, lay, cl, nullptr);
+    HIP_TRY(hipMemcpyAsync(b->nrm_args.p, b->h_nrm_args, lay.bytes, hipMemcpyHostToDevice, b->ctx->stream));   // (from a pinned buffer the batch keeps: no wait)
+    b->nrm_off_items = lay.off_items;
+    b->n_nrm_items = (int)cl.items.size();
     return ICP_OK;
 }
 
@@ -2533,7 +2319,7 @@ int icp_batch_estimate_point_normals(icp_batch* b, int orient, const double* mov
             for (int p = 0; p < count; ++p)
                 for (int k = 0; k < 3; ++k)
                     if (!std::isfinite(views[sd][3 * p + k]))
-                        return fail(ICP_ERR_INVALID, "a viewpoint has a NaN or an infinite value: pair " + std::to_string(p) + side_name(sd));
+                        return fail(ICP_ERR_INVALID, "a viewpoint has a NaN or an infinite value" + where(p, sd));
     }
     icp_ctx* c = b->ctx;
     hipStream_t st = c->stream;
@@ -2570,7 +2356,7 @@ int icp_batch_estimate_point_normals(icp_batch* b, int orient, const double* mov
     b->have_pnrm[0] = b->have_pnrm[1] = true;
     if (orient == ICP_ORIENT_CENTROID) b->have_cent = true;
     double* const out[2] = {moving_normals_out, model_normals_out};
-    if (out[0] || out[1]) return download_point_normals(b, out);   // (the one wait of a call that wants an output)
+    if (out[0] || out[1]) return download_planes<double, 3>(b, b->pnrm[0].p, b->pnrm[1].p, out[0], out[1]);   // (the one wait of a call that wants an output)
     return ICP_OK;
 }
 
@@ -2584,19 +2370,18 @@ int icp_batch_set_point_normals(icp_batch* b, const double* moving_normals, cons
         const int64_t* off = sd ? b->qoff.data() : b->moff.data();
         for (int p = 0; p < b->count; ++p)
             for (int64_t i = 3 * off[p]; i < 3 * off[p + 1]; ++i)
-                if (!std::isfinite(given[sd][i]))
-                    return fail(ICP_ERR_INVALID, "a normal has a NaN or an infinite value: pair " + std::to_string(p) + side_name(sd));
+                if (!std::isfinite(given[sd][i])) return fail(ICP_ERR_INVALID, "a normal has a NaN or an infinite value" + where(p, sd));
     }
     // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
     for (int sd = 0; sd < 2; ++sd)
         if (given[sd])
             if (int rc = ensure_point_normals(b, sd)) return rc;
-    std::vector<double> h[2];
+    std::vector<char> h[2];
     for (int sd = 0; sd < 2; ++sd) {
         if (!given[sd]) continue;
         b->have_pnrm[sd] = false;
-        normals_to_planes(given[sd], ::side(b, sd != 0), h[sd]);
-        HIP_TRY(hipMemcpyAsync(b->pnrm[sd].p, h[sd].data(), h[sd].size() * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
+        to_planes<double, 3>(given[sd], ::side(b, sd != 0), h[sd]);
+        HIP_TRY(hipMemcpyAsync(b->pnrm[sd].p, h[sd].data(), h[sd].size(), hipMemcpyHostToDevice, b->ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
     for (int sd = 0; sd < 2; ++sd)
@@ -2613,7 +2398,7 @@ int icp_batch_get_point_normals(icp_batch* b, double* moving_normals_out, double
         if (out[sd] && !b->have_pnrm[sd])
             return fail(ICP_ERR_STATE, std::string("the batch holds no point normals of the ") + (sd ? "models" : "moving clouds") +
                                            " (icp_batch_estimate_point_normals or icp_batch_set_point_normals first)");
-    return download_point_normals(b, out);
+    return download_planes<double, 3>(b, b->pnrm[0].p, b->pnrm[1].p, out[0], out[1]);
 }
 
 int icp_diag_batch_centroids(icp_batch* b, double* out)
