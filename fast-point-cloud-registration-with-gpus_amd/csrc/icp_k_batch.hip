@@ -8,7 +8,7 @@
 // normals (knn4_batch, normals_batch_kernel) live with the single-pair ones in icp_k_plane.hip.  Reference statements: the loop a
 // pair runs is src/ICP_point_to_point.cu:295-423 / src/ICP_point_to_plane.cu:517-631; the kernels restate nn_match_kernel,
 // moments_kernel and transform_error_kernel (icp_k_dense.hip) per work item.
-#include "icp_device.h"
+#include "icp_device_batch.h"
 #include "../../include/icp_mi355x_diag.h"
 #include <math.h>
 #include <stdlib.h>
@@ -39,9 +39,6 @@ namespace icp {
 //     reads that entry anyway (idx_prev) and adds the point's error only if the bit is clear.  Downloads strip the bit.
 // A pair's blocks, their geometry and every sum depend on that pair alone (no atomics): its bits do not depend on the batch.
 // ------------------------------------------------------------------------------------------------
-template <typename F> struct BatchCfg;
-template <> struct BatchCfg<float> { static constexpr int TW = 512; };    // model points per wave and tile: 6 KiB per wave
-template <> struct BatchCfg<double> { static constexpr int TW = 256; };
 static_assert(sizeof(RT<float>) == 12 * sizeof(float) && sizeof(RT<double>) == 12 * sizeof(double), "the host writes R, t as 12 values per pair");
 
 // slots of the moment vector a batch pass fills: error, count, sum p, sum q, sum q p^T, |p|^2, |q|^2 -- or error, count, C (21), b (6)
@@ -400,7 +397,7 @@ __global__ __launch_bounds__(TRIM_BLOCK) void batch_trim_select(const BatchPair*
 }
 
 // one block per work item, over nn_match_batch's items and in its block shape (wave 0 alone carries data, waves 1-3 add zeros, so
-// that block_sum_store adds a row in the fused pass's order): kept = d <= tau[pair] && (no gate || d <= thr[pair]); a rejected
+// that block_sum_store adds a row in the fused pass's order): kept = batch_kept's d <= tau[pair] && (no gate || d <= thr[pair]); a rejected
 // point's idx entry gets BATCH_IDX_REJECTED; the kept points' terms go to slots 1 .. of the item's row.  Slot ICP_MOM_ERR, which
 // nn_match_batch<.., DEFER> wrote, is not touched.
 // MUTUAL (its own instantiations, for a batch with a reciprocal pair; the others keep their code and never read rev or recip):
@@ -430,15 +427,8 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_trim_moments(const BatchItem* 
     if (w == 0 && lane < it.count) {
         const long long gi = pr.p_off + it.first + lane;
         const F* Qx = Q + pr.q_off;
-        const F b = dist[gi];
         const int j = idx_cur[gi];
-        bool kept;
-        if constexpr (MUTUAL) {
-            const bool mutual = recip[it.pair] == 0 || rev[pr.q_off + j] == it.first + lane;
-            kept = mutual && (tau == nullptr || b <= tau[it.pair]) && (thr == nullptr || b <= thr[it.pair]);
-        } else {
-            kept = b <= tau[it.pair] && (thr == nullptr || b <= thr[it.pair]);
-        }
+        const bool kept = batch_kept<F, MUTUAL, !MUTUAL>(dist[gi], it.pair, tau, thr, recip, rev, pr.q_off + j, it.first + lane);
         if (!kept) idx_cur[gi] = j | BATCH_IDX_REJECTED;
         const F* Qy = Qx + q_plane;
         const F* Qz = Qx + 2 * q_plane;
@@ -456,9 +446,7 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_trim_moments(const BatchItem* 
 // robust kernels (icp_batch_set_robust): the decision, the residual, the weight and the weighted terms of a step of a batch that
 // holds a robust pair -- batch_trim_moments' place on the deferred route, over the same items and in its block shape (wave 0 alone
 // carries data, waves 1-3 add zeros, block_sum_store adds a row in the fused pass's order).
-//   kept: batch_trim_moments' tests, restated -- (tau == NULL || d <= tau[pair]) && (thr == NULL || d <= thr[pair]), and with
-//     MUTUAL (its own instantiations: the others never read rev or recip) && (recip[pair] == 0 || rev[idx[i]] == i).  A rejected
-//     point's idx entry gets BATCH_IDX_REJECTED and its weight entry 0.0.
+//   kept: batch_kept, batch_trim_moments' decision.  A rejected point's idx entry gets BATCH_IDX_REJECTED and its weight entry 0.0.
 //   residual, in double from the widened coordinates: point-to-point r2 = dx*dx + dy*dy + dz*dz, d = q - p (the front end's error
 //     arithmetic); point-to-plane r2 = bi * bi, the bi of the plane terms.
 //   weight w, in double, from kind[pair], k[pair], k2[pair] = k * k (the host's product): Huber r2 <= k2 ? 1 : k / sqrt(r2), Cauchy
@@ -498,10 +486,8 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_robust_moments(const BatchItem
         const F* Qx = Q + pr.q_off;
         const F* Qy = Qx + q_plane;
         const F* Qz = Qx + 2 * q_plane;
-        const F b = dist[gi];
         const int j = idx_cur[gi];   // in [0, m): the matching launch wrote it
-        bool kept = (tau == nullptr || b <= tau[it.pair]) && (thr == nullptr || b <= thr[it.pair]);
-        if constexpr (MUTUAL) kept = kept && (recip[it.pair] == 0 || rev[pr.q_off + j] == it.first + lane);
+        const bool kept = batch_kept<F, MUTUAL>(dist[gi], it.pair, tau, thr, recip, rev, pr.q_off + j, it.first + lane);
         double wgt = 0.0;
         if (!kept) {
             idx_cur[gi] = j | BATCH_IDX_REJECTED;   // (a rejected point adds nothing: every accumulator stays 0, the count included)
@@ -1003,31 +989,9 @@ __global__ __launch_bounds__(VOXEL_SCAN_BLOCK) void batch_voxel_rank(const Batch
         if (threadIdx.x == 0) a.count[cloud] = c.n;
         return;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < c.n; base += VOXEL_SCAN_BLOCK) {
-        const int i = base + threadIdx.x;
-        const int flag = (i < c.n && first[i] == i) ? 1 : 0;
-        int incl = flag;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < VOXEL_SCAN_BLOCK / 64; ++w) {
-            before += w < wave ? s_wave[w] : 0;
-            total += s_wave[w];
-        }
-        if (i < c.n) rank[i] = carry + before + incl - flag;
-        carry += total;
-        __syncthreads();   // (s_wave is rewritten by the next chunk; after the last one: the block's ranks are written)
-    }
-    if (threadIdx.x == 0) a.count[cloud] = carry;
-    for (int i = threadIdx.x; i < c.n; i += VOXEL_SCAN_BLOCK) map[i] = rank[first[i]];
+    const int cells = block_rank_flags(c.n, s_wave, [&](int i) { return first[i] == i ? 1 : 0; }, [&](int i, int, int r) { rank[i] = r; });
+    if (threadIdx.x == 0) a.count[cloud] = cells;
+    for (int i = threadIdx.x; i < c.n; i += VOXEL_SCAN_BLOCK) map[i] = rank[first[i]];   // (the block's ranks are written: the scan ends on a barrier)
 }
 
 template <typename F>
@@ -1071,58 +1035,29 @@ hipError_t launch_batch_voxel_compact(const BatchVoxelArgs& a, hipStream_t st)
 // ------------------------------------------------------------------------------------------------
 // statistical and radius outlier removal of every cloud of a batch (icp_batch_remove_outliers, icp_batch.cpp; the rule is stated
 // in include/icp_mi355x.h and every step here is one statement of it).  The clouds and work items are the voxel call's.
-//   batch_outlier_scan    one block of NN_BLOCK threads per work item, one query per lane: the four waves stream the four
-//                         contiguous quarters of the query's own cloud through their LDS sub-tiles, as knn4_batch does.  Places
-//                         past a quarter's end hold +inf (a list) or NaN (a count): such a distance enters nothing.  The rule is
-//                         uniform per block.  A statistical cloud keeps the k smallest dist2<F> -- distances only -- ascending in the TOP k
-//                         of CAP registers (the slots below hold -inf, which nothing displaces: bd[CAP - 1] is the k-th smallest
-//                         at a compile-time index and the insertion is CAP medians of three, fully unrolled: outlier_insert); it is
-//                         entered under a wave-uniform test of the chunk's minimum.  The query itself (j == i, by index: a
-//                         coincident point counts) is masked to +inf in the chunks that overlap the item, a wave-uniform test.
-//                         Waves 1-3 leave their lists in LDS (over the sub-tiles, after a barrier) and wave 0 inserts them into
-//                         its own: a multiset has one order.  Then dbar = (sum of sqrt((double)d), ascending, from 0.0) / (double)k.
+//   batch_outlier_scan    one block of NN_BLOCK threads per work item, one query per lane: phase 1's steps (icp_device_batch.h)
+//                         in a loop of its own, because the two rules share it.  Places past a quarter's end hold +inf (a list)
+//                         or NaN (a count): such a distance enters nothing.  The rule is uniform per block.  A statistical cloud
+//                         keeps the list of the k smallest dist2<F> -- distances only -- as kth_distance does, and then
+//                         dbar = (sum of sqrt((double)d), ascending, from 0.0) / (double)k.
 //                         A radius cloud counts dist2 <= thr2 per wave, the query included (its distance is exactly 0), and
 //                         wave 0 adds the four counts and takes the query out.  score[i] = dbar or (double)c; 0.0 where copied.
 //   batch_outlier_decide  one block per cloud: granule sums (64 consecutive points from 0.0 in ascending index, one thread per
 //                         granule), thread 0 adds them from 0.0 in ascending order: S, then Qsum the same way; mean, std, thr;
-//                         the keep flags, their exclusive scan (batch_voxel_rank's), map, count, stats.
+//                         the keep flags, their exclusive scan, map, count, stats.
 //   batch_outlier_compact one wave per work item: a kept point's bytes go to the new batch's planes at dst_off + map
 // No atomics of any kind; nothing is fused (contraction is off for this file), nothing multiplied by a reciprocal.
 // ------------------------------------------------------------------------------------------------
-constexpr int OUTLIER_CHUNK = 8;   // points per early-out chunk
-
-template <typename F> __device__ __forceinline__ F nan_();
-template <> __device__ __forceinline__ float nan_<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double nan_<double>() { return __builtin_nan(""); }
-
-// d into the ascending list bd[0 .. CAP-1], the largest entry falling off: bd[r] = median(bd[r-1], d, bd[r]) -- bd[r-1] where d
-// lies below it, d where it lies between the two, bd[r] where it lies above -- from the top slot down, so that every step reads
-// its lower neighbour as it was.  One v_med3_f32, or one max and one min in double, per slot: selections only, no branch, no
-// predicate; equal values change nothing of the multiset.  d is never NaN here (+inf: the list is left as it is).
-__device__ __forceinline__ float outlier_med3(float lo, float d, float hi) { return __builtin_amdgcn_fmed3f(lo, d, hi); }
-__device__ __forceinline__ double outlier_med3(double lo, double d, double hi) { return __builtin_fmin(hi, __builtin_fmax(lo, d)); }
-template <typename F, int CAP>
-__device__ __forceinline__ void outlier_insert(F (&bd)[CAP], F d)
-{
-#pragma unroll
-    for (int r = CAP - 1; r >= 1; --r) bd[r] = outlier_med3(bd[r - 1], d, bd[r]);
-    bd[0] = fmin_(bd[0], d);
-}
-
 template <typename F, int CAP>
 __global__ __launch_bounds__(NN_BLOCK) void batch_outlier_scan(const BatchOutlierArgs a)
 {
-    using V = typename Vec16<F>::type;
-    constexpr int VN = Vec16<F>::N;
-    constexpr int TW = BatchCfg<F>::TW, C = OUTLIER_CHUNK;
+    constexpr int TW = BatchCfg<F>::TW, C = KNN_CHUNK;
     constexpr size_t TILE_BYTES = sizeof(F) * 4 * 3 * TW, LIST_BYTES = sizeof(F) * 3 * CAP * BATCH_ITEM;
-    static_assert(BATCH_ITEM == 64 && NN_BLOCK == 4 * BATCH_ITEM && TW % C == 0 && C % VN == 0, "one query per lane, four waves per item");
     static_assert(CAP >= 1 && CAP <= OUTLIER_MAX_K, "the list's capacity");
     // the sub-tiles during the scan, the lists of waves 1-3 after it
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[TILE_BYTES > LIST_BYTES ? TILE_BYTES : LIST_BYTES];
     __shared__ int s_cnt[4][BATCH_ITEM];
     F(*sq)[3][TW] = reinterpret_cast<F(*)[3][TW]>(s_raw);
-    F(*ld)[CAP][BATCH_ITEM] = reinterpret_cast<F(*)[CAP][BATCH_ITEM]>(s_raw);
 
     const BatchItem it = a.items[blockIdx.x];
     const OutlierRule rule = a.rules[it.pair];
@@ -1141,10 +1076,7 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_outlier_scan(const BatchOutlie
     const F* Sy = Sx + sp;
     const F* Sz = Sx + 2 * sp;
     const F px = Sx[i], py = Sy[i], pz = Sz[i];
-    const int n = c.n;
-    const int wseg = ((n + 3) / 4 + C - 1) / C * C;   // points per wave, whole chunks
-    const int my0 = w * wseg, my1 = min(my0 + wseg, n);  // may be empty (my1 <= my0)
-    const int ntile = (wseg + TW - 1) / TW;           // the same for every wave: the barriers pair up
+    const WaveQuarter q = wave_quarter<F>(c.n, w);
     const bool radius = rule.kind == ICP_OUTLIER_RADIUS;
     const F thr2 = (F)(rule.value * rule.value);      // (the radius rule's; the product in double, rounded once)
     const int k = rule.neighbours;
@@ -1153,51 +1085,23 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_outlier_scan(const BatchOutlie
     const F pad = radius ? nan_<F>() : inf_<F>();
     int cnt = 0;
     F bd[CAP];
-#pragma unroll
-    for (int r = 0; r < CAP; ++r) bd[r] = (r >= CAP - k) ? inf_<F>() : -inf_<F>();
+    knn_list_init<F, CAP>(bd, k);
 
-    for (int t = 0; t < ntile; ++t) {
-        const int t0 = my0 + t * TW;
+    for (int t = 0; t < q.ntile; ++t) {
+        const int t0 = q.first + t * TW;
         __syncthreads();
-        for (int e = lane; e < TW; e += 64) {
-            const int j = t0 + e;
-            F qx = pad, qy = pad, qz = pad;
-            if (j < my1) { qx = Sx[j]; qy = Sy[j]; qz = Sz[j]; }
-            sq[w][0][e] = qx;
-            sq[w][1][e] = qy;
-            sq[w][2][e] = qz;
-        }
+        load_subtile<F, TW>(sq[w], Sx, Sy, Sz, t0, q.end, pad);
         __syncthreads();
-        const int len = min(TW, my1 - t0);   // <= 0: this wave's quarter is exhausted
+        const int len = min(TW, q.end - t0);   // <= 0: this wave's quarter is exhausted
         for (int cc = 0; cc < len; cc += C) {
             F dd[C];
-#pragma unroll
-            for (int kk = 0; kk < C; kk += VN) {
-                const V qx = *reinterpret_cast<const V*>(&sq[w][0][cc + kk]);
-                const V qy = *reinterpret_cast<const V*>(&sq[w][1][cc + kk]);
-                const V qz = *reinterpret_cast<const V*>(&sq[w][2][cc + kk]);
-#pragma unroll
-                for (int v = 0; v < VN; ++v) dd[kk + v] = dist2<F>(px, py, pz, vget(qx, v), vget(qy, v), vget(qz, v));
-            }
+            chunk_dist2<F, TW>(sq[w], cc, px, py, pz, dd);
             if (radius) {
 #pragma unroll
                 for (int kk = 0; kk < C; ++kk) cnt += (dd[kk] <= thr2) ? 1 : 0;
                 continue;
             }
-            const int j0 = t0 + cc;
-            if (j0 + C > it.first && j0 < it.first + BATCH_ITEM) {   // (wave-uniform) the chunk holds queries of this item: j != i
-#pragma unroll
-                for (int kk = 0; kk < C; ++kk) dd[kk] = (j0 + kk == i) ? inf_<F>() : dd[kk];
-            }
-            F cmin = inf_<F>();
-#pragma unroll
-            for (int kk = 0; kk < C; ++kk) cmin = fmin_(cmin, dd[kk]);
-            if (__builtin_amdgcn_ballot_w64(cmin < bd[CAP - 1]) == 0ull) continue;
-#pragma unroll
-            for (int kk = 0; kk < C; ++kk) {
-                const F d = dd[kk];
-                outlier_insert<F, CAP>(bd, d);
-            }
+            knn_chunk<F, CAP>(bd, dd, t0 + cc, it, i);
         }
     }
     if (radius) {
@@ -1206,21 +1110,8 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_outlier_scan(const BatchOutlie
         if (w == 0 && live) score[i] = (double)(s_cnt[0][lane] + s_cnt[1][lane] + s_cnt[2][lane] + s_cnt[3][lane] - 1);
         return;
     }
-    __syncthreads();   // every wave has read its last sub-tile: the lists go over them
-    if (w > 0) {
-#pragma unroll
-        for (int r = 0; r < CAP; ++r) ld[w - 1][r][lane] = bd[r];
-    }
-    __syncthreads();
+    knn_merge<F, CAP>(s_raw, bd, k);
     if (w != 0) return;
-    for (int ww = 0; ww < 3; ++ww) {
-#pragma unroll 1
-        for (int s = CAP - k; s < CAP; ++s) {
-            const F d = ld[ww][s][lane];
-            if (__builtin_amdgcn_ballot_w64(d < bd[CAP - 1]) == 0ull) break;   // (ascending lists: no later entry of this wave's enters any lane's)
-            outlier_insert<F, CAP>(bd, d);
-        }
-    }
     double s = 0.0;
 #pragma unroll
     for (int r = 0; r < CAP; ++r) {
@@ -1306,33 +1197,13 @@ __global__ __launch_bounds__(VOXEL_SCAN_BLOCK) void batch_outlier_decide(const B
     }
     const bool radius = rule.kind == ICP_OUTLIER_RADIUS;
     const double least = (double)rule.neighbours;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < n; base += VOXEL_SCAN_BLOCK) {
-        const int i = base + threadIdx.x;
-        int flag = 0;
-        if (i < n) {
+    const int carry = block_rank_flags(
+        n, s_wave,
+        [&](int i) {
             const double sc = score[i];
-            flag = (radius ? sc >= least : sc <= thr) ? 1 : 0;
-        }
-        int incl = flag;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < VOXEL_SCAN_BLOCK / 64; ++w) {
-            before += w < wave ? s_wave[w] : 0;
-            total += s_wave[w];
-        }
-        if (i < n) map[i] = flag ? carry + before + incl - flag : -1;
-        carry += total;
-        __syncthreads();   // (s_wave is rewritten by the next chunk)
-    }
+            return (radius ? sc >= least : sc <= thr) ? 1 : 0;
+        },
+        [&](int i, int flag, int rank) { map[i] = flag ? rank : -1; });
     if (threadIdx.x == 0) {
         a.count[cloud] = carry;
         a.bad[cloud] = 0;
@@ -1353,11 +1224,8 @@ __global__ __launch_bounds__(BATCH_ITEM) void batch_outlier_compact(const BatchO
     const int i = it.first + lane;
     const int32_t to = a.map[c.tmp_off + i];
     if (to < 0) return;
-    const F* S = static_cast<const F*>(a.src[c.side]) + c.src_off + i;
-    F* D = static_cast<F*>(a.dst[c.side]) + c.dst_off + to;
-    const long long sp = a.src_plane[c.side], dp = a.dst_plane[c.side];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) D[k * dp] = S[k * sp];
+    copy_kept_point<F>(static_cast<const F*>(a.src[c.side]) + c.src_off + i, a.src_plane[c.side], static_cast<F*>(a.dst[c.side]) + c.dst_off + to,
+                       a.dst_plane[c.side]);
 }
 
 hipError_t launch_batch_outlier_scan(const BatchOutlierArgs& a, hipStream_t st)

@@ -1,46 +1,20 @@
 // icp_k_color.hip -- gfx950 kernels of the colored metric of batched ICP (icp_batch.cpp; Park, Zhou, Koltun, ICCV 2017): the
 // per-point intensity gradients of every model of a batch (batch_intensity_gradient_kernel) and the decision and the terms of a
 // colored step (batch_color_moments, batch_gicp_moments' sibling on the deferred route).  The rules are stated in
-// include/icp_mi355x.h and restated in numpy (tests/batch_color_ref.py); every step here is one statement of them.  The kernels of
-// icp_k_batch.hip and icp_k_gicp.hip keep their listings: what this file needs of them -- the register list of batch_cov_kernel,
-// the kept decision of batch_trim_moments -- is restated, not shared.  Contraction is off for this file: nothing is fused.
-#include "icp_device.h"
-#include <math.h>
+// include/icp_mi355x.h and restated in numpy (tests/batch_color_ref.py); every step here is one statement of them.  The scan, the
+// walk and the kept decision are icp_device_batch.h's.  Contraction is off for this file: nothing is fused.
+#include "icp_device_batch.h"
 
 namespace icp {
-
-template <typename F> struct ColorCfg;
-template <> struct ColorCfg<float> { static constexpr int TW = 512; };    // points per wave and sub-tile (GicpCfg's)
-template <> struct ColorCfg<double> { static constexpr int TW = 256; };
-constexpr int GRAD_CHUNK = 8;   // points per early-out chunk
-
-// batch_cov_kernel's list, restated: d into the ascending list bd[0 .. CAP-1], the largest entry falling off
-__device__ __forceinline__ float grad_med3(float lo, float d, float hi) { return __builtin_amdgcn_fmed3f(lo, d, hi); }
-__device__ __forceinline__ double grad_med3(double lo, double d, double hi) { return __builtin_fmin(hi, __builtin_fmax(lo, d)); }
-template <typename F, int CAP>
-__device__ __forceinline__ void grad_insert(F (&bd)[CAP], F d)
-{
-#pragma unroll
-    for (int r = CAP - 1; r >= 1; --r) bd[r] = grad_med3(bd[r - 1], d, bd[r]);
-    bd[0] = fmin_(bd[0], d);
-}
-
-template <typename F> __device__ __forceinline__ F grad_nan();
-template <> __device__ __forceinline__ float grad_nan<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double grad_nan<double>() { return __builtin_nan(""); }
-
-__device__ __forceinline__ double cdot(double x, double y, double z, double a, double b, double c) { return (x * a + y * b) + z * c; }
 
 // ------------------------------------------------------------------------------------------------
 // per-point intensity gradients (icp_batch_estimate_intensity_gradients): one block of NN_BLOCK threads per work item of a model,
 // one query per lane -- batch_cov_kernel's shape.
-//   phase 1  tau_i = the k-th smallest d2(i, j) over j != i by index: batch_cov_kernel's phase 1 statement for statement (four
-//            waves, four quarters of the model through LDS sub-tiles, the k smallest in the top k of CAP registers, wave 0 merges).
-//   phase 2  the block loads the model again, 4 * TW points per tile and their intensities beside them (a fourth LDS plane of
-//            doubles: the neighbour's intensity comes from the tile, as its coordinates do), and wave 0 walks every tile in
-//            ascending j: a point j != i with d2(i, j) <= tau_i adds u u^T to A and u g to r, u the part of e = q_j - q_i across
-//            the normal of i, g = I_j - I_i -- nine running sums per lane, ascending j by construction.  A chunk in which no lane's
-//            test passes is skipped (wave-uniform).  Places past the model's end hold NaN: such a distance passes no test.
+//   phase 1  tau_i = kth_distance over the query's own model.
+//   phase 2  walk_tiles, 4 * TW points per tile and their intensities beside them (a fourth LDS plane of doubles: the neighbour's
+//            intensity comes from the tile, as its coordinates do), wave 0: a point j != i with d2(i, j) <= tau_i adds u u^T to A
+//            and u g to r, u the part of e = q_j - q_i across the normal of i, g = I_j - I_i -- nine running sums per lane,
+//            ascending j by construction.
 //   then     A += c^2 n n^T (the gradient has no part along the normal), d = A^-1 r by cofactors, (0, 0, 0) where det is not finite
 //            and > 0 or a component is not finite, and three stores into the model's gradient planes.
 // The k of the block's model is uniform; the result depends on the model, its normals, its intensities and its k alone -- not on
@@ -51,17 +25,11 @@ __device__ __forceinline__ double cdot(double x, double y, double z, double a, d
 template <typename F, int CAP>
 __global__ __launch_bounds__(NN_BLOCK) void batch_intensity_gradient_kernel(const BatchGradArgs a)
 {
-    using V = typename Vec16<F>::type;
-    constexpr int VN = Vec16<F>::N;
-    constexpr int TW = ColorCfg<F>::TW, C = GRAD_CHUNK, T2 = 4 * TW;
+    constexpr int TW = BatchCfg<F>::TW, C = KNN_CHUNK, T2 = 4 * TW;
     constexpr size_t TILE_BYTES = sizeof(F) * 4 * 3 * TW, INT_BYTES = sizeof(double) * T2, LIST_BYTES = sizeof(F) * 3 * CAP * BATCH_ITEM;
-    static_assert(BATCH_ITEM == 64 && NN_BLOCK == 4 * BATCH_ITEM && TW % C == 0 && C % VN == 0, "one query per lane, four waves per item");
     static_assert(CAP >= 1 && CAP <= COV_MAX_K && TILE_BYTES % 16 == 0, "the list's capacity");
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[TILE_BYTES + INT_BYTES > LIST_BYTES ? TILE_BYTES + INT_BYTES : LIST_BYTES];
-    F(*sq)[3][TW] = reinterpret_cast<F(*)[3][TW]>(s_raw);                    // phase 1: a sub-tile per wave
-    F(*ld)[CAP][BATCH_ITEM] = reinterpret_cast<F(*)[CAP][BATCH_ITEM]>(s_raw);  // ... then the lists of waves 1-3
-    F(*st)[T2] = reinterpret_cast<F(*)[T2]>(s_raw);                          // phase 2: one tile of the block
-    double* si = reinterpret_cast<double*>(s_raw + TILE_BYTES);              // ... and its intensities
+    double* si = reinterpret_cast<double*>(s_raw + TILE_BYTES);   // phase 2: the tile's intensities, behind its coordinates
 
     const BatchItem it = a.items[blockIdx.x];
     const BatchPair pr = a.pairs[it.pair];
@@ -78,116 +46,23 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_intensity_gradient_kernel(cons
     const F px = Sx[i], py = Sy[i], pz = Sz[i];
     const int n = pr.m;
 
-    // ---- phase 1: the k-th smallest distance
-    const int wseg = ((n + 3) / 4 + C - 1) / C * C;   // points per wave, whole chunks
-    const int my0 = w * wseg, my1 = min(my0 + wseg, n);  // may be empty (my1 <= my0)
-    const int ntile = (wseg + TW - 1) / TW;           // the same for every wave: the barriers pair up
-    F bd[CAP];
-#pragma unroll
-    for (int r = 0; r < CAP; ++r) bd[r] = (r >= CAP - k) ? inf_<F>() : -inf_<F>();
-    for (int t = 0; t < ntile; ++t) {
-        const int t0 = my0 + t * TW;
-        __syncthreads();
-        for (int e = lane; e < TW; e += 64) {
-            const int j = t0 + e;
-            F qx = inf_<F>(), qy = inf_<F>(), qz = inf_<F>();
-            if (j < my1) { qx = Sx[j]; qy = Sy[j]; qz = Sz[j]; }
-            sq[w][0][e] = qx;
-            sq[w][1][e] = qy;
-            sq[w][2][e] = qz;
-        }
-        __syncthreads();
-        const int len = min(TW, my1 - t0);   // <= 0: this wave's quarter is exhausted
-        for (int cc = 0; cc < len; cc += C) {
-            F dd[C];
-#pragma unroll
-            for (int kk = 0; kk < C; kk += VN) {
-                const V qx = *reinterpret_cast<const V*>(&sq[w][0][cc + kk]);
-                const V qy = *reinterpret_cast<const V*>(&sq[w][1][cc + kk]);
-                const V qz = *reinterpret_cast<const V*>(&sq[w][2][cc + kk]);
-#pragma unroll
-                for (int v = 0; v < VN; ++v) dd[kk + v] = dist2<F>(px, py, pz, vget(qx, v), vget(qy, v), vget(qz, v));
-            }
-            const int j0 = t0 + cc;
-            if (j0 + C > it.first && j0 < it.first + BATCH_ITEM) {   // (wave-uniform) the chunk holds queries of this item: j != i
-#pragma unroll
-                for (int kk = 0; kk < C; ++kk) dd[kk] = (j0 + kk == i) ? inf_<F>() : dd[kk];
-            }
-            F cmin = inf_<F>();
-#pragma unroll
-            for (int kk = 0; kk < C; ++kk) cmin = fmin_(cmin, dd[kk]);
-            if (__builtin_amdgcn_ballot_w64(cmin < bd[CAP - 1]) == 0ull) continue;
-#pragma unroll
-            for (int kk = 0; kk < C; ++kk) grad_insert<F, CAP>(bd, dd[kk]);
-        }
-    }
-    __syncthreads();   // every wave has read its last sub-tile: the lists go over them
-    if (w > 0) {
-#pragma unroll
-        for (int r = 0; r < CAP; ++r) ld[w - 1][r][lane] = bd[r];
-    }
-    __syncthreads();
-    F tau = inf_<F>();
-    if (w == 0) {
-        for (int ww = 0; ww < 3; ++ww) {
-#pragma unroll 1
-            for (int s = CAP - k; s < CAP; ++s) {
-                const F d = ld[ww][s][lane];
-                if (__builtin_amdgcn_ballot_w64(d < bd[CAP - 1]) == 0ull) break;   // (ascending lists: no later entry of this wave's enters any lane's)
-                grad_insert<F, CAP>(bd, d);
-            }
-        }
-        tau = bd[CAP - 1];
-    }
+    const F tau = kth_distance<F, CAP>(s_raw, Sx, Sy, Sz, n, k, it, i, px, py, pz);
 
-    // ---- phase 2: the sums over the neighbourhood, ascending j, wave 0
     const F* Nx = static_cast<const F*>(a.N_soa) + pr.q_off;
     const double xi = (double)px, yi = (double)py, zi = (double)pz;
     const double nx = (double)Nx[i], ny = (double)Nx[sp + i], nz = (double)Nx[2 * sp + i];
     const double Ii = SI[i];
     double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, r0 = 0.0, r1 = 0.0, r2 = 0.0;
     int cnt = 0;
-    const int ntile2 = (n + T2 - 1) / T2;
-    for (int t = 0; t < ntile2; ++t) {
-        const int t0 = t * T2;
-        __syncthreads();   // (the first: wave 0 has read the lists)
-        for (int e = threadIdx.x; e < T2; e += NN_BLOCK) {
-            const int j = t0 + e;
-            F qx = grad_nan<F>(), qy = grad_nan<F>(), qz = grad_nan<F>();
-            double qi = 0.0;
-            if (j < n) { qx = Sx[j]; qy = Sy[j]; qz = Sz[j]; qi = SI[j]; }
-            st[0][e] = qx;
-            st[1][e] = qy;
-            st[2][e] = qz;
-            si[e] = qi;
-        }
-        __syncthreads();
-        if (w != 0) continue;
-        const int len = min(T2, n - t0);
-        for (int cc = 0; cc < len; cc += C) {
-            F qq[3][C];
-            bool in[C];
-            bool any = false;
-#pragma unroll
-            for (int kk = 0; kk < C; kk += VN) {
-                const V qx = *reinterpret_cast<const V*>(&st[0][cc + kk]);
-                const V qy = *reinterpret_cast<const V*>(&st[1][cc + kk]);
-                const V qz = *reinterpret_cast<const V*>(&st[2][cc + kk]);
-#pragma unroll
-                for (int v = 0; v < VN; ++v) {
-                    qq[0][kk + v] = vget(qx, v);
-                    qq[1][kk + v] = vget(qy, v);
-                    qq[2][kk + v] = vget(qz, v);
-                    in[kk + v] = dist2<F>(px, py, pz, qq[0][kk + v], qq[1][kk + v], qq[2][kk + v]) <= tau && (t0 + cc + kk + v != i);   // (NaN: false)
-                    any = any || in[kk + v];
-                }
-            }
-            if (__builtin_amdgcn_ballot_w64(any) == 0ull) continue;
+    walk_tiles<F, T2>(
+        reinterpret_cast<F(*)[T2]>(s_raw), Sx, Sy, Sz, n, px, py, pz, [&](int e, int j, bool inside) { si[e] = inside ? SI[j] : 0.0; },
+        [&](F d, int j) { return d <= tau && j != i; },
+        [&](int cc, const bool(&in)[C], const F(&qq)[3][C]) {
 #pragma unroll
             for (int kk = 0; kk < C; ++kk) {
                 if (in[kk]) {
                     const double ex = (double)qq[0][kk] - xi, ey = (double)qq[1][kk] - yi, ez = (double)qq[2][kk] - zi;
-                    const double h = cdot(ex, ey, ez, nx, ny, nz);
+                    const double h = dot3(ex, ey, ez, nx, ny, nz);
                     const double ux = ex - h * nx, uy = ey - h * ny, uz = ez - h * nz;
                     const double g = si[cc + kk] - Ii;
                     A00 += ux * ux; A01 += ux * uy; A02 += ux * uz;
@@ -196,8 +71,7 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_intensity_gradient_kernel(cons
                     cnt += 1;
                 }
             }
-        }
-    }
+        });
     if (w != 0 || !live) return;
     const double wn = (double)cnt * (double)cnt;   // the tangent constraint's weight
     A00 += wn * (nx * nx); A01 += wn * (nx * ny); A02 += wn * (nx * nz);
@@ -208,11 +82,10 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_intensity_gradient_kernel(cons
     double d0 = 0.0, d1 = 0.0, d2 = 0.0;
     if (det > 0.0 && det < __builtin_huge_val()) {   // (NaN fails both)
         const double M00 = c00 / det, M01 = c01 / det, M02 = c02 / det, M11 = c11 / det, M12 = c12 / det, M22 = c22 / det;
-        d0 = (M00 * r0 + M01 * r1) + M02 * r2;
-        d1 = (M01 * r0 + M11 * r1) + M12 * r2;
-        d2 = (M02 * r0 + M12 * r1) + M22 * r2;
-        const double lim = __builtin_huge_val();
-        if (!(__builtin_fabs(d0) < lim && __builtin_fabs(d1) < lim && __builtin_fabs(d2) < lim)) { d0 = 0.0; d1 = 0.0; d2 = 0.0; }
+        d0 = dot3(M00, M01, M02, r0, r1, r2);
+        d1 = dot3(M01, M11, M12, r0, r1, r2);
+        d2 = dot3(M02, M12, M22, r0, r1, r2);
+        if (!(finite_(d0) && finite_(d1) && finite_(d2))) { d0 = 0.0; d1 = 0.0; d2 = 0.0; }
     }
     double* gv = a.grad + pr.q_off + i;   // the planes are laid out as the model's
     gv[0] = d0; gv[sp] = d1; gv[2 * sp] = d2;
@@ -239,14 +112,12 @@ hipError_t launch_batch_intensity_gradients(const BatchGradArgs& a, hipStream_t 
 // the colored step (icp_batch_begin with ICP_COLORED): the decision and the terms of every kept match -- batch_gicp_moments' place
 // on the deferred route, over the same items and in its block shape (wave 0 alone carries data, waves 1-3 add zeros,
 // block_sum_store adds a row in the fused pass's order).
-//   kept: batch_trim_moments' tests, restated -- (tau == NULL || d <= tau[pair]) && (thr == NULL || d <= thr[pair]), and with MUTUAL
-//     (its own instantiations: the others never read rev or recip) && (recip[pair] == 0 || rev[idx[i]] == i).  A rejected point's
-//     idx entry gets BATCH_IDX_REJECTED.
+//   kept: batch_kept.  A rejected point's idx entry gets BATCH_IDX_REJECTED.
 //   terms, in double from the widened coordinates p (the moved point), q = Q[idx], the normal n and the gradient d of model point
 //     idx and the two intensities: e = p - q, h = e . n, s = d . n, m = d - s n, u = e - h n, rI = (Iq + d . u) - Ip; G_a = j_a . n,
 //     K_a = j_a . m for the six columns j_a of J = [-[p]x | I]; lg = lambda[pair], lp = 1.0 - lg;
-//     C(a, c) += lg (G_a G_c) + lp (K_a K_c) (a <= c), B(a) -= lg (G_a h) + lp (K_a rI), CNT = 1.  Every dot product is
-//     (x*x' + y*y') + z*z', each operation rounded on its own; with lg == 1 these are the plane pass's statements.
+//     C(a, c) += lg (G_a G_c) + lp (K_a K_c) (a <= c), B(a) -= lg (G_a h) + lp (K_a rI), CNT = 1.  Every dot product is dot3; with
+//     lg == 1 these are the plane pass's statements.
 // The block writes slots 1 .. ICP_MOM_B + 5 of its row and leaves ICP_MOM_ERR, the matching launch's.  A pair that takes part in the
 // step without matching (the loop's error-only last pass) gets zeros throughout.  No LDS beyond block_sum_store's.
 // ------------------------------------------------------------------------------------------------
@@ -274,28 +145,26 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_color_moments(const BatchItem*
     for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
     if ((pm & BATCH_MATCH) && w == 0 && lane < it.count) {
         const long long gi = pr.p_off + it.first + lane;
-        const F b = dist[gi];
         const int j = idx_cur[gi];   // in [0, m): the matching launch wrote it
-        bool kept = (tau == nullptr || b <= tau[it.pair]) && (thr == nullptr || b <= thr[it.pair]);
-        if constexpr (MUTUAL) kept = kept && (recip[it.pair] == 0 || rev[pr.q_off + j] == it.first + lane);
+        const bool kept = batch_kept<F, MUTUAL>(dist[gi], it.pair, tau, thr, recip, rev, pr.q_off + j, it.first + lane);
         if (kept) {
             const long long gj = pr.q_off + j;
             const double px = (double)P[gi], py = (double)P[p_plane + gi], pz = (double)P[2 * p_plane + gi];
             const double ex = px - (double)Q[gj], ey = py - (double)Q[q_plane + gj], ez = pz - (double)Q[2 * q_plane + gj];
             const double nx = (double)N[gj], ny = (double)N[q_plane + gj], nz = (double)N[2 * q_plane + gj];
             const double dx = grad_q[gj], dy = grad_q[q_plane + gj], dz = grad_q[2 * q_plane + gj];
-            const double h = cdot(ex, ey, ez, nx, ny, nz);
-            const double s = cdot(dx, dy, dz, nx, ny, nz);
+            const double h = dot3(ex, ey, ez, nx, ny, nz);
+            const double s = dot3(dx, dy, dz, nx, ny, nz);
             const double mx = dx - s * nx, my = dy - s * ny, mz = dz - s * nz;
             const double ux = ex - h * nx, uy = ey - h * ny, uz = ez - h * nz;
-            const double rI = (int_q[gj] + cdot(dx, dy, dz, ux, uy, uz)) - int_p[gi];
+            const double rI = (int_q[gj] + dot3(dx, dy, dz, ux, uy, uz)) - int_p[gi];
             const double lg = color_w[it.pair], lp = 1.0 - lg;
             const double J[6][3] = {{0.0, -pz, py}, {pz, 0.0, -px}, {-py, px, 0.0}, {1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
             double G[6], K[6];
 #pragma unroll
             for (int c = 0; c < 6; ++c) {
-                G[c] = cdot(J[c][0], J[c][1], J[c][2], nx, ny, nz);
-                K[c] = cdot(J[c][0], J[c][1], J[c][2], mx, my, mz);
+                G[c] = dot3(J[c][0], J[c][1], J[c][2], nx, ny, nz);
+                K[c] = dot3(J[c][0], J[c][1], J[c][2], mx, my, mz);
             }
             acc[ICP_MOM_CNT] = 1.0;
             int o = ICP_MOM_C;

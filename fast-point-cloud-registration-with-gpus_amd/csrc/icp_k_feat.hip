@@ -2,38 +2,13 @@
 // every cloud of a batch (batch_spfh_kernel, batch_fpfh_kernel), the nearest descriptor of the other cloud (batch_feature_match)
 // and the inlier count of candidate poses over a correspondence list (batch_score_transforms); the sums of one iteration of Fast
 // Global Registration over a used list, and its weights (batch_fgr_terms, batch_fgr_finalize).  The rules are stated in
-// include/icp_mi355x.h and restated in numpy (tests/batch_feature_ref.py, tests/batch_fgr_ref.py); every step here is one statement of them.  The kernels
-// of icp_k_gicp.hip keep their listings: what this file needs of batch_cov_kernel -- the register list behind tau_i -- is restated,
-// not shared.  Contraction is off for this file: nothing is fused.  No atomics anywhere.
-#include "icp_device.h"
-#include <math.h>
+// include/icp_mi355x.h and restated in numpy (tests/batch_feature_ref.py, tests/batch_fgr_ref.py); every step here is one statement of them.  The scan
+// and the walk are icp_device_batch.h's.  Contraction is off for this file: nothing is fused.  No atomics anywhere.
+#include "icp_device_batch.h"
 
 namespace icp {
 
-template <typename F> struct FeatCfg;
-template <> struct FeatCfg<float> { static constexpr int TW = 512; };    // phase 1: points per wave and sub-tile (GicpCfg's: 6 KiB per wave)
-template <> struct FeatCfg<double> { static constexpr int TW = 256; };
-constexpr int FEAT_CHUNK = 8;     // points per early-out chunk
 constexpr int FEAT_TILE = 512;    // points per LDS tile of the neighbourhood walks: coordinates (and, in batch_spfh_kernel, normals)
-
-// batch_cov_kernel's list, restated: d into the ascending list bd[0 .. CAP-1], the largest entry falling off
-__device__ __forceinline__ float feat_med3(float lo, float d, float hi) { return __builtin_amdgcn_fmed3f(lo, d, hi); }
-__device__ __forceinline__ double feat_med3(double lo, double d, double hi) { return __builtin_fmin(hi, __builtin_fmax(lo, d)); }
-template <typename F, int CAP>
-__device__ __forceinline__ void feat_insert(F (&bd)[CAP], F d)
-{
-#pragma unroll
-    for (int r = CAP - 1; r >= 1; --r) bd[r] = feat_med3(bd[r - 1], d, bd[r]);
-    bd[0] = fmin_(bd[0], d);
-}
-
-template <typename F> __device__ __forceinline__ F feat_nan();
-template <> __device__ __forceinline__ float feat_nan<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double feat_nan<double>() { return __builtin_nan(""); }
-
-__device__ __forceinline__ double fdot(double x, double y, double z, double a, double b, double c) { return (x * a + y * b) + z * c; }
-__device__ __forceinline__ bool ffinite(double v) { return __builtin_fabs(v) < __builtin_huge_val(); }   // (NaN: false)
-__device__ __forceinline__ bool ffinite(float v) { return __builtin_fabsf(v) < __builtin_huge_valf(); }
 
 // bin(val, lo, width) = clamp((int)floor((11.0 * (val - lo)) / width), 0, 10); the clamp is taken in double, a NaN lands in bin 0
 __device__ __forceinline__ int feat_bin(double val, double lo, double width)
@@ -44,13 +19,12 @@ __device__ __forceinline__ int feat_bin(double val, double lo, double width)
 
 // ------------------------------------------------------------------------------------------------
 // SPFH of every point (icp_batch_compute_features, first launch): one block of NN_BLOCK threads per work item, one query per lane.
-//   phase 1  tau_i = the k-th smallest d2(i, j) over j != i by index: batch_cov_kernel's phase 1, statement for statement (four
-//            waves over four quarters of the cloud, the k smallest in the top k of CAP registers, wave 0 merges the lists).
-//   phase 2  the block loads the cloud again, FEAT_TILE points per tile with their normals (always double), and wave 0 walks every
-//            tile: a point with d2(i, j) <= tau_i gives one pair term (the query itself has r2 == 0 and is skipped with every other
-//            coincident point), three bins, three integer counters of the lane's 33 in LDS (s_cnt[bin][lane]: a lane owns a bank).
-//            Counts have no order.  A chunk in which no lane's test passes is skipped (wave-uniform).  Places past the cloud's end
-//            hold NaN: such a distance passes no test.
+//   phase 1  tau_i = kth_distance over the query's own cloud.
+//   phase 2  load_tile, FEAT_TILE points per tile with their normals (always double), and a walk of its own by wave 0 (a chunk in
+//            which no lane's test passes is skipped; through walk_tiles the kernel needs more registers): a point with d2(i, j) <= tau_i gives
+//            one pair term (the query itself has r2 == 0 and is skipped with every other coincident point), three bins, three
+//            integer counters of the lane's 33 in LDS (s_cnt[bin][lane]: a lane owns a bank).  Counts have no order.  The chunk's
+//            points are read from the tile one by one (a rolled loop: no runtime-indexed register array).
 //   then     S_i[b] = (100.0 * (double)cnt_b) / (double)c, or zeros where c == 0; tau_i is stored for the second launch.
 // LDS: phase 1 as batch_cov_kernel (24 KiB of sub-tiles, reused for the lists: <= 48 KiB for CAP 32, fp64); phase 2 over the same
 // bytes FEAT_TILE x (3 sizeof(F) + 24) = 18 / 24 KiB; beside them the counters, 33 x 64 x 4 = 8.25 KiB.
@@ -58,18 +32,13 @@ __device__ __forceinline__ int feat_bin(double val, double lo, double width)
 template <typename F, int CAP>
 __global__ __launch_bounds__(NN_BLOCK) void batch_spfh_kernel(const BatchFeatArgs a)
 {
-    using V = typename Vec16<F>::type;
-    constexpr int VN = Vec16<F>::N;
-    constexpr int TW = FeatCfg<F>::TW, C = FEAT_CHUNK, T2 = FEAT_TILE;
+    constexpr int TW = BatchCfg<F>::TW, C = KNN_CHUNK, T2 = FEAT_TILE;
     constexpr size_t TILE_BYTES = sizeof(F) * 4 * 3 * TW, LIST_BYTES = sizeof(F) * 3 * CAP * BATCH_ITEM;
     constexpr size_t WALK_BYTES = (sizeof(F) + sizeof(double)) * 3 * T2;
     constexpr size_t RAW_A = TILE_BYTES > LIST_BYTES ? TILE_BYTES : LIST_BYTES, RAW = RAW_A > WALK_BYTES ? RAW_A : WALK_BYTES;
-    static_assert(BATCH_ITEM == 64 && NN_BLOCK == 4 * BATCH_ITEM && TW % C == 0 && C % VN == 0 && T2 % C == 0, "one query per lane, four waves per item");
     static_assert(CAP >= 1 && CAP <= COV_MAX_K, "the list's capacity");
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[RAW];
     __shared__ int s_cnt[ICP_FEATURE_BINS][BATCH_ITEM];
-    F(*sq)[3][TW] = reinterpret_cast<F(*)[3][TW]>(s_raw);                    // phase 1: a sub-tile per wave
-    F(*ld)[CAP][BATCH_ITEM] = reinterpret_cast<F(*)[CAP][BATCH_ITEM]>(s_raw);  // ... then the lists of waves 1-3
     double(*sn)[T2] = reinterpret_cast<double(*)[T2]>(s_raw);                // phase 2: the tile's normals ...
     F(*st)[T2] = reinterpret_cast<F(*)[T2]>(s_raw + sizeof(double) * 3 * T2);  // ... and its coordinates
 
@@ -90,66 +59,8 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_spfh_kernel(const BatchFeatArg
     const F px = Sx[i], py = Sy[i], pz = Sz[i];
     const int n = c.n;
 
-    // ---- phase 1: the k-th smallest distance
-    const int wseg = ((n + 3) / 4 + C - 1) / C * C;   // points per wave, whole chunks
-    const int my0 = w * wseg, my1 = min(my0 + wseg, n);  // may be empty (my1 <= my0)
-    const int ntile = (wseg + TW - 1) / TW;           // the same for every wave: the barriers pair up
-    F bd[CAP];
-#pragma unroll
-    for (int r = 0; r < CAP; ++r) bd[r] = (r >= CAP - k) ? inf_<F>() : -inf_<F>();
-    for (int t = 0; t < ntile; ++t) {
-        const int t0 = my0 + t * TW;
-        __syncthreads();
-        for (int e = lane; e < TW; e += 64) {
-            const int j = t0 + e;
-            F qx = inf_<F>(), qy = inf_<F>(), qz = inf_<F>();
-            if (j < my1) { qx = Sx[j]; qy = Sy[j]; qz = Sz[j]; }
-            sq[w][0][e] = qx;
-            sq[w][1][e] = qy;
-            sq[w][2][e] = qz;
-        }
-        __syncthreads();
-        const int len = min(TW, my1 - t0);   // <= 0: this wave's quarter is exhausted
-        for (int cc = 0; cc < len; cc += C) {
-            F dd[C];
-#pragma unroll
-            for (int kk = 0; kk < C; kk += VN) {
-                const V qx = *reinterpret_cast<const V*>(&sq[w][0][cc + kk]);
-                const V qy = *reinterpret_cast<const V*>(&sq[w][1][cc + kk]);
-                const V qz = *reinterpret_cast<const V*>(&sq[w][2][cc + kk]);
-#pragma unroll
-                for (int v = 0; v < VN; ++v) dd[kk + v] = dist2<F>(px, py, pz, vget(qx, v), vget(qy, v), vget(qz, v));
-            }
-            const int j0 = t0 + cc;
-            if (j0 + C > it.first && j0 < it.first + BATCH_ITEM) {   // (wave-uniform) the chunk holds queries of this item: j != i
-#pragma unroll
-                for (int kk = 0; kk < C; ++kk) dd[kk] = (j0 + kk == i) ? inf_<F>() : dd[kk];
-            }
-            F cmin = inf_<F>();
-#pragma unroll
-            for (int kk = 0; kk < C; ++kk) cmin = fmin_(cmin, dd[kk]);
-            if (__builtin_amdgcn_ballot_w64(cmin < bd[CAP - 1]) == 0ull) continue;
-#pragma unroll
-            for (int kk = 0; kk < C; ++kk) feat_insert<F, CAP>(bd, dd[kk]);
-        }
-    }
-    __syncthreads();   // every wave has read its last sub-tile: the lists go over them
-    if (w > 0) {
-#pragma unroll
-        for (int r = 0; r < CAP; ++r) ld[w - 1][r][lane] = bd[r];
-    }
-    __syncthreads();
-    F tau = inf_<F>();
+    const F tau = kth_distance<F, CAP>(s_raw, Sx, Sy, Sz, n, k, it, i, px, py, pz);
     if (w == 0) {
-        for (int ww = 0; ww < 3; ++ww) {
-#pragma unroll 1
-            for (int s = CAP - k; s < CAP; ++s) {
-                const F d = ld[ww][s][lane];
-                if (__builtin_amdgcn_ballot_w64(d < bd[CAP - 1]) == 0ull) break;   // (ascending lists: no later entry of this wave's enters any lane's)
-                feat_insert<F, CAP>(bd, d);
-            }
-        }
-        tau = bd[CAP - 1];
 #pragma unroll 1
         for (int b = 0; b < ICP_FEATURE_BINS; ++b) s_cnt[b][lane] = 0;
     }
@@ -158,47 +69,33 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_spfh_kernel(const BatchFeatArg
     const double xi = (double)px, yi = (double)py, zi = (double)pz;
     const double nix = Nx[i], niy = Ny[i], niz = Nz[i];
     int cnt = 0;
-    const int ntile2 = (n + T2 - 1) / T2;
-    for (int t = 0; t < ntile2; ++t) {
+    const int ntile = (n + T2 - 1) / T2;
+    for (int t = 0; t < ntile; ++t) {
         const int t0 = t * T2;
-        __syncthreads();   // (the first: wave 0 has read the lists)
-        for (int e = threadIdx.x; e < T2; e += NN_BLOCK) {
-            const int j = t0 + e;
-            F qx = feat_nan<F>(), qy = feat_nan<F>(), qz = feat_nan<F>();
-            double ux = 0.0, uy = 0.0, uz = 0.0;
-            if (j < n) { qx = Sx[j]; qy = Sy[j]; qz = Sz[j]; ux = Nx[j]; uy = Ny[j]; uz = Nz[j]; }
-            st[0][e] = qx;
-            st[1][e] = qy;
-            st[2][e] = qz;
-            sn[0][e] = ux;
-            sn[1][e] = uy;
-            sn[2][e] = uz;
-        }
-        __syncthreads();
+        load_tile<F, T2>(st, Sx, Sy, Sz, t0, n, [&](int e, int j, bool inside) {
+            sn[0][e] = inside ? Nx[j] : 0.0;
+            sn[1][e] = inside ? Ny[j] : 0.0;
+            sn[2][e] = inside ? Nz[j] : 0.0;
+        });
         if (w != 0) continue;
         const int len = min(T2, n - t0);
         for (int cc = 0; cc < len; cc += C) {
+            F dd[C];
+            chunk_dist2<F, T2>(st, cc, px, py, pz, dd);
             unsigned in = 0u;
 #pragma unroll
-            for (int kk = 0; kk < C; kk += VN) {
-                const V qx = *reinterpret_cast<const V*>(&st[0][cc + kk]);
-                const V qy = *reinterpret_cast<const V*>(&st[1][cc + kk]);
-                const V qz = *reinterpret_cast<const V*>(&st[2][cc + kk]);
-#pragma unroll
-                for (int v = 0; v < VN; ++v)
-                    in |= (dist2<F>(px, py, pz, vget(qx, v), vget(qy, v), vget(qz, v)) <= tau) ? (1u << (kk + v)) : 0u;   // (NaN: false)
-            }
+            for (int kk = 0; kk < C; ++kk) in |= (dd[kk] <= tau) ? (1u << kk) : 0u;   // (NaN: false)
             if (__builtin_amdgcn_ballot_w64(in != 0u) == 0ull) continue;
 #pragma unroll 1
             for (int kk = 0; kk < C; ++kk) {
                 if (!((in >> kk) & 1u)) continue;
                 const int e = cc + kk;
                 double dx = (double)st[0][e] - xi, dy = (double)st[1][e] - yi, dz = (double)st[2][e] - zi;
-                const double r2 = (dx * dx + dy * dy) + dz * dz;
-                if (r2 == 0.0 || !ffinite(r2)) continue;
+                const double r2 = dot3(dx, dy, dz, dx, dy, dz);
+                if (r2 == 0.0 || !finite_(r2)) continue;
                 const double r = sqrt(r2);
                 const double njx = sn[0][e], njy = sn[1][e], njz = sn[2][e];
-                const double a1 = fdot(nix, niy, niz, dx, dy, dz) / r, a2 = fdot(njx, njy, njz, dx, dy, dz) / r;
+                const double a1 = dot3(nix, niy, niz, dx, dy, dz) / r, a2 = dot3(njx, njy, njz, dx, dy, dz) / r;
                 double n1x, n1y, n1z, n2x, n2y, n2z, f3;
                 if (__builtin_fabs(a1) < __builtin_fabs(a2)) {
                     n1x = njx; n1y = njy; n1z = njz; n2x = nix; n2y = niy; n2z = niz;
@@ -209,13 +106,13 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_spfh_kernel(const BatchFeatArg
                     f3 = a1;
                 }
                 double vx = dy * n1z - dz * n1y, vy = dz * n1x - dx * n1z, vz = dx * n1y - dy * n1x;
-                const double vv = fdot(vx, vy, vz, vx, vy, vz);
-                if (vv == 0.0 || !ffinite(vv)) continue;
+                const double vv = dot3(vx, vy, vz, vx, vy, vz);
+                if (vv == 0.0 || !finite_(vv)) continue;
                 const double sv = sqrt(vv);
                 vx = vx / sv; vy = vy / sv; vz = vz / sv;
                 const double wx = n1y * vz - n1z * vy, wy = n1z * vx - n1x * vz, wz = n1x * vy - n1y * vx;
-                const double f2 = fdot(vx, vy, vz, n2x, n2y, n2z);
-                const double x = fdot(n1x, n1y, n1z, n2x, n2y, n2z), y = fdot(wx, wy, wz, n2x, n2y, n2z);
+                const double f2 = dot3(vx, vy, vz, n2x, n2y, n2z);
+                const double x = dot3(n1x, n1y, n1z, n2x, n2y, n2z), y = dot3(wx, wy, wz, n2x, n2y, n2z);
                 const double s = __builtin_fabs(x) + __builtin_fabs(y);
                 double tt = 0.0;
                 if (!(s == 0.0)) {
@@ -250,7 +147,8 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_fpfh_kernel(const BatchFeatArg
 {
     using V = typename Vec16<F>::type;
     constexpr int VN = Vec16<F>::N;
-    constexpr int C = FEAT_CHUNK, T2 = FEAT_TILE, NB = (ICP_FEATURE_BINS + 3) / 4;
+    constexpr int C = KNN_CHUNK, T2 = FEAT_TILE, NB = (ICP_FEATURE_BINS + 3) / 4;
+    static_assert(T2 % C == 0 && C % VN == 0, "whole chunks, whole vectors");
     __shared__ __attribute__((aligned(16))) F st[3][T2];
     __shared__ double s_acc[ICP_FEATURE_BINS][BATCH_ITEM];
 
@@ -274,19 +172,10 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_fpfh_kernel(const BatchFeatArg
     const int ntile = (n + T2 - 1) / T2;
     for (int t = 0; t < ntile; ++t) {
         const int t0 = t * T2;
-        __syncthreads();
-        for (int e = threadIdx.x; e < T2; e += NN_BLOCK) {
-            const int j = t0 + e;
-            F qx = feat_nan<F>(), qy = feat_nan<F>(), qz = feat_nan<F>();
-            if (j < n) { qx = Sx[j]; qy = Sy[j]; qz = Sz[j]; }
-            st[0][e] = qx;
-            st[1][e] = qy;
-            st[2][e] = qz;
-        }
-        __syncthreads();
+        load_tile<F, T2>(st, Sx, Sy, Sz, t0, n);
         const int len = min(T2, n - t0);
         for (int cc = 0; cc < len; cc += C) {
-            bool any = false;
+            bool any = false;   // (the test alone, vector by vector: with chunk_dist2's eight distances held, the kernel needs 19 registers more)
 #pragma unroll
             for (int kk = 0; kk < C; kk += VN) {
                 const V qx = *reinterpret_cast<const V*>(&st[0][cc + kk]);
@@ -484,7 +373,7 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_score_transforms(const BatchPa
             F mx, my, mz;
             apply_rt<F>(s_rt[g], x, y, z, mx, my, mz);
             const F d = dist2<F>(mx, my, mz, qx, qy, qz);
-            const bool hit = have && ffinite(mx) && ffinite(my) && ffinite(mz) && d <= th;
+            const bool hit = have && finite_(mx) && finite_(my) && finite_(mz) && d <= th;
             cnt[g] += __builtin_popcountll(__builtin_amdgcn_ballot_w64(hit));
         }
     }
@@ -528,8 +417,6 @@ hipError_t launch_batch_score(const BatchScoreArgs& a, hipStream_t st)
 // weights[p_off + ui[e]] (0.0 for an entry that does not count) and nothing else -- the list holds a moving point once, so no two
 // lanes write one address.  A pair whose flag in ctl is 0.0 takes no part.  No LDS beyond block_sum_store's 4 x 30 doubles.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool fgr_finite(double v) { return __builtin_fabs(v) < __builtin_huge_val(); }   // (NaN: false)
-
 template <typename F, bool WEIGHTS>
 __global__ __launch_bounds__(NN_BLOCK) void batch_fgr_terms(const BatchItem* __restrict__ items, const BatchPair* __restrict__ pairs,
                                                             const int32_t* __restrict__ ui, const int32_t* __restrict__ uj,
@@ -563,7 +450,7 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_fgr_terms(const BatchItem* __r
         const double r2 = (ev[0] * ev[0] + ev[1] * ev[1]) + ev[2] * ev[2];
         const double s = mu / (mu + r2);
         const double l = s * s;
-        const bool ok = fgr_finite(p[0]) && fgr_finite(p[1]) && fgr_finite(p[2]) && fgr_finite(r2);
+        const bool ok = finite_(p[0]) && finite_(p[1]) && finite_(p[2]) && finite_(r2);
         if constexpr (WEIGHTS) {
             weights[gi] = ok ? l : 0.0;
         } else if (ok) {

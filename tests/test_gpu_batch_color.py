@@ -102,6 +102,24 @@ def test_gradients_bit_for_bit(ctx, pkg, dtype, k):
 
 
 @DTYPES
+def test_gradients_over_sub_tiles(ctx, pkg, dtype):
+    """2100 points -- more than one LDS sub-tile per wave in either precision (the sizes above reach a second one in fp64 alone), a
+    last chunk that is padded, work items that straddle the quarters -- beside k + 1 points, at both edges of a list capacity"""
+    models = [fine(gr.blob(61, 2100, dtype), 62), fine(gr.blob(63, 17, dtype), 64), fine(gr.blob(65, 10, dtype), 66)]
+    ks = [9, 16, 9]
+    Ns = [unit_normals(220 + b, M.shape[0], dtype) for b, M in enumerate(models)]
+    Is = [intensities(320 + b, M.shape[0]) for b, M in enumerate(models)]
+    with ctx.batch(list(zip(tiny_movers(len(models), dtype), models))) as bt:
+        bt.set_model_normals(Ns)
+        bt.set_intensities(model=Is)
+        got = bt.estimate_intensity_gradients(ks, want=True)
+        for b, M in enumerate(models):
+            want = ref_grad(M, Ns[b], Is[b], ks[b])[0]
+            bad = np.flatnonzero((got[b].view(np.uint64) != want.view(np.uint64)).any(axis=1))
+            assert bad.size == 0, f"pair {b} k {ks[b]}: {bad.size} of {M.shape[0]} points differ, first {bad[0]}: {got[b][bad[0]]!r} / {want[bad[0]]!r}"
+
+
+@DTYPES
 def test_a_pairs_gradients_do_not_depend_on_the_batch(ctx, pkg, dtype):
     X, Y, Z = fine(gr.blob(7, 300, dtype), 8), orf.lattice(dtype, side=5, step=0.25), fine(gr.blob(15, 513, dtype), 16)
     N = {id(M): unit_normals(60 + b, M.shape[0], dtype) for b, M in enumerate((X, Y, Z))}

@@ -88,6 +88,23 @@ def test_descriptors_bit_for_bit(ctx, pkg, dtype, k):
 
 
 @DTYPES
+def test_descriptors_capacity_16_over_sub_tiles(ctx, pkg, dtype):
+    """the list capacity the cases above leave out, at both of its edges (k = 16 and k = 9), on the shapes at which the scan takes
+    another path: 2100 points -- more than one LDS sub-tile per wave in either precision, a last chunk that is padded, work items
+    that straddle the quarters -- and k + 1 points, three quarters nearly or wholly empty"""
+    movers = [cloud(41, 2100, dtype), cloud(43, 10, dtype)]
+    models = [cloud(45, 17, dtype), cloud(47, 2100, dtype)]
+    ks, kq = [16, 9], [16, 9]
+    with ctx.batch([(A, M) for (A, _), (M, _) in zip(movers, models)]) as bt:
+        fm, fq = bt.compute_features(ks, ([N for _, N in movers], [N for _, N in models]), k_model=kq, want=True)
+        for b, ((A, NA), (M, NM)) in enumerate(zip(movers, models)):
+            for got, want, what in ((fm[b], ref_fpfh(A, NA, ks[b]), "moving"), (fq[b], ref_fpfh(M, NM, kq[b]), "model")):
+                assert got.dtype == np.float64 and got.shape == want.shape
+                bad = differing(got, want)
+                assert bad.size == 0, f"pair {b} {what} k {ks[b]}/{kq[b]}: {bad.size} points differ, first {bad[0]}: {got[bad[0]]!r} / {want[bad[0]]!r}"
+
+
+@DTYPES
 def test_a_pairs_descriptors_do_not_depend_on_the_batch(ctx, pkg, dtype):
     (XA, XN), (XM, XMN) = cloud(7, 300, dtype), (orf.lattice(dtype, side=5, step=0.25), unit(5, 125))
     (YA, YN), (YM, YMN) = cloud(9, 130, dtype), cloud(11, 65, dtype)

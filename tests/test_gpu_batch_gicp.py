@@ -85,6 +85,23 @@ def test_covariances_bit_for_bit(ctx, pkg, dtype, k, reg):
             assert bits_equal(gm2[b], cm[b]) and bits_equal(gq2[b], ref_cov(M, k, regc, lam)[0])
 
 
+@DTYPES
+def test_covariances_over_sub_tiles(ctx, pkg, dtype):
+    """2100 points -- more than one LDS sub-tile per wave in either precision (the sizes above reach a second one in fp64 alone), a
+    last chunk that is padded, work items that straddle the quarters -- beside k + 1 points, at both edges of a list capacity"""
+    lam = 1e-3
+    movers = [fine(gr.blob(51, 2100, dtype), 52), fine(gr.blob(53, 10, dtype), 54)]
+    models = [fine(gr.blob(55, 17, dtype), 56), fine(gr.blob(57, 2100, dtype), 58)]
+    ks = [16, 9]
+    with ctx.batch(list(zip(movers, models))) as bt:
+        cm, cq = bt.estimate_covariances(ks, ks, regularisation="frobenius", lam=lam, want=True)
+        for b in range(2):
+            for got, X, what in ((cm[b], movers[b], "moving"), (cq[b], models[b], "model")):
+                want = ref_cov(X, ks[b], gr.COV_FROBENIUS, lam)[0]
+                bad = np.flatnonzero((got.view(np.uint64) != want.view(np.uint64)).any(axis=1))
+                assert bad.size == 0, f"pair {b} {what} k {ks[b]}: {bad.size} points differ, first {bad[0]}: {got[bad[0]]!r} / {want[bad[0]]!r}"
+
+
 def test_duplicates_give_lambda_identity_on_the_device(ctx, pkg):
     X = orf.coincident(np.float32)
     with ctx.batch([(X, X.copy())]) as bt:
