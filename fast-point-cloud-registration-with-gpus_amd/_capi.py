@@ -184,6 +184,7 @@ SIGNATURES = {
     "icp_shard_range": (_i, [C.c_int64, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "icp_share_rows_plan": (_i, [_pu32, _i, _i, _i, _i, _pi32, _pu32]),
     "icp_diag_row_roles": (_i, [_vp, _pu32, _i, _i, _i, _i, _pi32]),
+    "icp_diag_knn4_geometry": (_i, [_vp, _i, _pi]),
     "icp_diag_loop_moments": (_i, [_vp, _pd, _pi]),
     "icp_diag_batch_moments": (_i, [_vp, _i, _pd]),
     "icp_diag_batch_trim": (_i, [_vp, _i, _pd, _pi]),

@@ -582,6 +582,15 @@ int icp_nn_match_f64(icp_ctx* c, const double* P, int n, const double* Q, int m,
 }
 
 // ---- normals -----------------------------------------------------------------------------------
+int icp_diag_knn4_geometry(icp_ctx* c, int m, int out[5])
+{
+    if (!c) return fail(ICP_ERR_INVALID, "null context");
+    if (!out || m < 5) return fail(ICP_ERR_INVALID, "icp_diag_knn4_geometry: bad arguments");
+    icp::knn4_v2_geometry(m, c->num_cus, &out[0], &out[1], &out[2], &out[3]);
+    out[4] = icp::knn4_v2_wave_tiles(out[3]);
+    return ICP_OK;
+}
+
 int icp_estimate_normals(icp_ctx* c, void* nxyz_out, int32_t* nbr_out)
 {
     if (int rc = use(c)) return rc;

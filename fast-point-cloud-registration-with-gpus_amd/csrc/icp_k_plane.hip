@@ -220,7 +220,9 @@ __global__ __launch_bounds__(NN_BLOCK, 4) void knn4_f32_v2(const float* __restri
 }
 
 // merge the S per-segment top-5 lists of every query (ascending segments, earlier segment first on equal d),
-// drop rank 0, store the 4 neighbour indices
+// drop rank 0, store the 4 neighbour indices.  A rank that does not exist (fewer than five candidates with d < +inf) still holds
+// knn4_f32_v2's 0x7fffffff here; it leaves as index 0, as knn4_kernel and knn4_batch leave it (include/icp_mi355x.h,
+// icp_estimate_normals): every stored index is in range
 __global__ void knn4_merge_kernel(const float* __restrict__ part_d, const int32_t* __restrict__ part_j, int S, int n_pad,
                                   int m, int32_t* __restrict__ nbr)
 {
@@ -238,7 +240,7 @@ __global__ void knn4_merge_kernel(const float* __restrict__ part_d, const int32_
         }
     }
 #pragma unroll
-    for (int r = 1; r < 5; ++r) nbr[(size_t)i * 4 + (r - 1)] = L.j[r];
+    for (int r = 1; r < 5; ++r) nbr[(size_t)i * 4 + (r - 1)] = ((unsigned)L.j[r] < (unsigned)m) ? L.j[r] : 0;
 }
 
 __device__ __forceinline__ float mag_(float v) { return fabsf(v); }
@@ -275,8 +277,32 @@ __device__ __forceinline__ void pca_normal(const F* __restrict__ Qx, const F* __
         A[0] += dx * dx; A[1] += dx * dy; A[2] += dx * dz;
         A[3] += dy * dy; A[4] += dy * dz; A[5] += dz * dz;
     }
+    // a covariance with an entry that is not finite in F (neighbours so far apart that a product overflows) has no normal: exactly
+    // (+0, +0, +0), icp_batch_estimate_point_normals' rule -- such a point adds nothing to a plane pass's sums, where the NaNs a
+    // Jacobi on it would store poison every one of them
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) finite = finite && (mag_(A[k]) < inf_<F>());   // (false for NaN too)
+    if (!finite) {
+        nx = ny = nz = 0.0;
+        return;
+    }
     // symmetric 3x3 in named scalars (no runtime-indexed arrays -> no scratch)
     double a00 = A[0], a01 = A[1], a02 = A[2], a11 = A[3], a12 = A[4], a22 = A[5];
+    // double clouds only: the stop test below squares the entries, and the squares of a covariance beyond 2^+-400 leave the range
+    // (off = inf stops the sweeps at once, off = 0 likewise: the identity would come out whatever the matrix).  Such a matrix is
+    // brought to the middle of the range by an exact power of two, which changes no rotation, and its eigenvalues are scaled
+    // back before they are compared in F; every other matrix goes through as it is, bit for bit.  (A float covariance widened
+    // to double has squares within [2^-298, 2^256].)
+    double unscale = 1.0;
+    if constexpr (sizeof(F) == 8) {
+        const double amax = fmax(fmax(fmax(fabs(a00), fabs(a01)), fmax(fabs(a02), fabs(a11))), fmax(fabs(a12), fabs(a22)));
+        if (amax > 0x1p+400 || (amax < 0x1p-400 && amax > 0.0)) {
+            const double sc = amax > 1.0 ? 0x1p-600 : 0x1p+600;
+            unscale = amax > 1.0 ? 0x1p+600 : 0x1p-600;
+            a00 *= sc; a01 *= sc; a02 *= sc; a11 *= sc; a12 *= sc; a22 *= sc;
+        }
+    }
     double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;
     for (int sweep = 0; sweep < 32; ++sweep) {
         const double off = a01 * a01 + a02 * a02 + a12 * a12;
@@ -331,6 +357,7 @@ __device__ __forceinline__ void pca_normal(const F* __restrict__ Qx, const F* __
     ICP_SWAP_EIG(w0, e0x, e0y, e0z, w2, e2x, e2y, e2z)
     ICP_SWAP_EIG(w1, e1x, e1y, e1z, w2, e2x, e2y, e2z)
 #undef ICP_SWAP_EIG
+    if constexpr (sizeof(F) == 8) { w0 *= unscale; w1 *= unscale; w2 *= unscale; }
     nx = e0x; ny = e0y; nz = e0z;
     F wm = mag_((F)w0);
     if (mag_((F)w1) < wm) { wm = mag_((F)w1); nx = e1x; ny = e1y; nz = e1z; }
@@ -576,6 +603,8 @@ void knn4_v2_geometry(int m, int num_cus, int* n_pad, int* blocks_x, int* splits
     *splits = (m_pad + seg - 1) / seg;
     *seg_len = seg;
 }
+
+int knn4_v2_wave_tiles(int seg_len) { return ((seg_len >> 2) + NN2_TQW - 1) / NN2_TQW; }   // knn4_f32_v2's ntile
 
 hipError_t launch_knn4_v2(const void* Q, int m, int num_cus, float* part_d, int32_t* part_j, int32_t* nbr, hipStream_t st)
 {

@@ -205,6 +205,13 @@ class Context:
         capi.check(self._lib.icp_diag_loop_moments(self._h, mom.ctypes.data_as(C.POINTER(C.c_double)), C.byref(route)), "icp_diag_loop_moments")
         return mom, route.value
 
+    def diag_knn4_geometry(self, m):
+        """the launch shape of the fp32 neighbour search of an m-point model on this context (icp_diag_knn4_geometry): dict of
+        n_pad, blocks_x, splits, seg_len and tiles (LDS tiles per wave); arithmetic alone, nothing is launched"""
+        out = (C.c_int * 5)()
+        capi.check(self._lib.icp_diag_knn4_geometry(self._h, int(m), out), "icp_diag_knn4_geometry")
+        return dict(zip(("n_pad", "blocks_x", "splits", "seg_len", "tiles"), (int(x) for x in out)))
+
     def nn_launch_info(self):
         v = [C.c_int(0) for _ in range(5)]
         capi.check(self._lib.icp_nn_launch_info(self._h, *[C.byref(x) for x in v]), "icp_nn_launch_info")

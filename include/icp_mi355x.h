@@ -156,7 +156,19 @@ int icp_set_exclusive(icp_ctx* ctx, int on);
  *      src/CUDA/GPU_point_to_plane_real.cu:54-188,391-423 (k = 4 neighbours, self excluded).
  *      Works on the resident model; results stay resident and are optionally returned.
  *      Neighbours, mean and covariance are formed in the model's own precision: an ICP_F64 model (survey coordinates,
- *      a small patch far from the origin) gets its normals from double arithmetic throughout. ------- */
+ *      a small patch far from the origin) gets its normals from double arithmetic throughout.
+ *      The rule, over the whole range of the model's precision F (tests/knn_ref.py states it in numpy):
+ *      Neighbours.  d(i, j) = (dx*dx + dy*dy) + dz*dz, every operation rounded separately in F.  The candidates of query i
+ *      are all j in [0, m), i included, with d(i, j) < +inf, ordered by (d, j) ascending; rank 0 is dropped, ranks 1-4 are the
+ *      neighbours.  A rank that does not exist (fewer than five candidates: the points are so far apart that the squared
+ *      distances overflow) holds index 0: every index returned, and every index the normals read, lies in [0, m).  The rule
+ *      has no sentinel; it is the reference's k+1 passes of first-arg-min with overwrite-by-10000 exactly where every query's
+ *      fifth-smallest distance is below 10000.
+ *      Normals.  bar = (sum of the four neighbours) * 0.25, then the six sums A += (x - bar)(y - bar) over them, in F.  If
+ *      an entry of that covariance is not finite, the normal is exactly (+0, +0, +0) -- the rule of
+ *      icp_batch_estimate_point_normals -- and the point adds nothing to the sums of a point-to-plane pass.  Otherwise it
+ *      is the unit eigenvector of the eigenvalue of smallest magnitude (magnitudes compared in F, the first of the ascending
+ *      eigenvalues on ties); a zero covariance gives the first axis. ------- */
 int icp_estimate_normals(icp_ctx* ctx, void* nxyz_aos_out /*3m or NULL*/, int32_t* neighbours_out /*4m or NULL*/);
 
 /* ---- the ICP loops: replace main()'s while-loops
@@ -835,6 +847,8 @@ void icp_batch_destroy(icp_batch* b);
 int icp_batch_set_model_normals(icp_batch* b, const void* nxyz_aos);
 /* kNN(4) + PCA normals of every pair's model on the device: one neighbour launch + one normals launch for the whole batch.
  * nxyz_aos_out (3 per model point) and neighbours_out (4 per model point, indices WITHIN that pair's model) may be NULL.
+ * Neighbours and normals follow the rule stated at icp_estimate_normals -- a rank that does not exist holds index 0, a
+ * covariance that is not finite gives (+0, +0, +0) -- and are that call's on each model alone, bit for bit, over the whole range.
  * A pair's model of fewer than 5 points (k = 4 neighbours + self, as icp_estimate_normals): ICP_ERR_INVALID, the message
  * names the pair */
 int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighbours_out);

@@ -28,6 +28,12 @@ int icp_nn_match_bench_ex(icp_ctx* ctx, int reps, int seeded, float* total_ms);
 int icp_nn_match_bench_launches(icp_ctx* ctx, int reps, int warmups, int mode, float* each_ms);
 /* ... of the launch the resident clouds get from the production plan (dense == 0) or from the dense packed kernel */
 int icp_nn_launch_info_ex(icp_ctx* ctx, int dense, int* splits, int* blocks, int* threads, int* n_pad, int* m_pad);
+/* the launch shape icp_estimate_normals gives the fp32 neighbour search (knn4_f32_v2) of a model of m >= 5 points on this context's
+ * CU count: out = { n_pad (queries, padded to blocks of 128), blocks_x (query blocks), splits (model segments = grid.y),
+ * seg_len (model points per segment; wave w of a block scans the points [s * seg_len + w * seg_len / 4, + seg_len / 4) of segment
+ * s), tiles (LDS tiles each wave streams its quarter through) }.  Arithmetic alone: nothing is launched, no cloud need be
+ * resident.  What lets a test put equal distances on both sides of every border at which two lists are merged. */
+int icp_diag_knn4_geometry(icp_ctx* ctx, int m, int out[5]);
 /* Executed-work accounting of the sparse matching kernel (it returns the brute-force answer of Matching<<<>>> without
  * evaluating most pairs, so the roofline of EXECUTED arithmetic needs a count).  enable != 0: every following sparse
  * launch of this context runs its instrumented instantiation and adds wave-level tallies to 8 device counters;

@@ -659,7 +659,9 @@ int orc_icp_p2plane_f32x(const float* D, const float* M, int n, int m, const flo
  * first five of the (d, j)-ascending order of the model, rank 0 (self or an equal-distance lower
  * index) dropped.  The order is stated directly -- a sorted top-5 kept over one ascending scan,
  * a candidate going behind every entry with d_e <= d -- instead of the fp32 twin's k+1 passes of
- * first-argmin with overwrite-by-10000, which stop being that order once distances exceed 10000. */
+ * first-argmin with overwrite-by-10000, which stop being that order once distances exceed 10000.
+ * The candidates are the points with d < +inf (include/icp_mi355x.h, icp_estimate_normals): an
+ * overflowed distance enters nothing, and a rank that does not exist holds index 0. */
 void orc_knn4_f64(const double* q, int m, int* neighborIds /* m*4 */)
 {
     const size_t ms = (size_t)m;
@@ -672,6 +674,7 @@ void orc_knn4_f64(const double* q, int m, int* neighborIds /* m*4 */)
             dx = dx * dx; dy = dy * dy; dz = dz * dz;
             double d = dx + dy;
             d = d + dz;
+            if (!(d < INFINITY)) continue;
             if (have == 5 && !(d < bd[4])) continue;
             int r = have < 5 ? have : 4;              /* the slot that opens at the end */
             while (r > 0 && d < bd[r - 1]) { bd[r] = bd[r - 1]; bj[r] = bj[r - 1]; r--; }
@@ -712,8 +715,16 @@ void orc_normals_f64(const double* q, int m, const int* neighborIds, double* nor
             A[8] += (zi - bar[2]) * (zi - bar[2]);
         }
         if (A_out) memcpy(A_out + 9 * (size_t)i, A, sizeof A);
-        double w[3], Z[9];
-        orc_eigh3(A, w, Z);
+        /* orc_eigh3's stop test has an absolute floor (1e-300) and adds magnitudes: a covariance
+         * beyond 2^+-400 is handed over times an exact power of two, which changes no rotation,
+         * and its eigenvalues are scaled back; every other one goes through as it is. */
+        double As[9], w[3], Z[9], amax = 0.0, sc = 1.0;
+        for (int e = 0; e < 9; e++) if (fabs(A[e]) > amax) amax = fabs(A[e]);
+        if (amax > 0x1p+400) sc = 0x1p-600;
+        else if (amax < 0x1p-400 && amax > 0.0) sc = 0x1p+600;
+        for (int e = 0; e < 9; e++) As[e] = A[e] * sc;
+        orc_eigh3(As, w, Z);
+        for (int e = 0; e < 3; e++) w[e] *= 1.0 / sc;
         int idx_min = 0;
         for (int e = 1; e < 3; e++) if (fabs(w[e]) < fabs(w[idx_min])) idx_min = e;
         for (int j = 0; j < 3; j++) normals[i + ms * j] = Z[j * 3 + idx_min];

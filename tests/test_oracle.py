@@ -260,6 +260,16 @@ def test_knn4_f64_beyond_the_fp32_twins_sentinel(orc):
     assert (np.sort(nbr, axis=1)[:, 1:] != np.sort(nbr, axis=1)[:, :-1]).all() and (nbr != np.arange(300)[:, None]).all()
 
 
+def test_knn4_f64_overflowed_distance_enters_nothing(orc):
+    """the candidates are the points with d < +inf: five points on a line, 2^511 apart -- d is 2^1022 to the next point and +inf to
+    every other -- so the end points have one neighbour, the inner points two, and every rank that does not exist holds index 0
+    (before, a +inf distance was let in while fewer than five entries were held: the lowest indices filled the list)"""
+    M = np.zeros((5, 3))
+    M[:, 0] = 2.0 ** 511 * np.arange(5)
+    assert np.array_equal(orc.knn4(M), [[1, 0, 0, 0], [0, 2, 0, 0], [1, 3, 0, 0], [2, 4, 0, 0], [3, 0, 0, 0]])
+    assert np.array_equal(orc.knn4(1e10 * M), np.zeros((5, 4), dtype=np.int32))     # every distance off the diagonal is +inf
+
+
 def plane_pairs_f64(pkg, golden):
     from batch_ref import five_pairs
     return cl.widen_pairs(five_pairs(pkg, golden))
