@@ -107,6 +107,12 @@
 // (icp_batch_estimate_normals: knn4_batch + normals_batch_kernel, icp_k_plane.hip).  The reference estimates them once per
 // program, before its loop (src/ICP_point_to_plane.cu:391-438).
 //
+// Whatever a batch holds per point -- covariances, intensities, gradients, point normals, descriptors, the model normals -- is a
+// PointAttr, and every set and get call goes one way: attr_reserve (scan, allocate; a refusal leaves the batch untouched), the
+// call's own invalidations, attr_commit (encode, copy, one wait); attr_get (the refusals, then fetch: download, one wait, decode).
+// The packing is icp_batch_clouds.h's encode / decode, the clouds' own included.  Everything the batch owns -- DevBuf, PinnedBuf,
+// Event, Staged (icp_ctx.h) -- frees itself: icp_batch_destroy is `delete`.
+//
 // Every pair runs its own icp::HostLoop, the single-pair loop's host half (icp_host_loop.cpp): the same stop rule, the same
 // composition of T, the same err series.  A pass of a pair is what loop_enqueue_body (icp_loop.cpp) makes of it: the motion
 // solved by the previous pass is applied in the front of the launch (note_applied when it is enqueued), and the loop's last,
@@ -125,6 +131,16 @@
 #include "icp_ctx.h"
 #include "icp_host_math.h"
 
+// a value per point that a batch holds for one or both sides (0: the moving clouds, 1: the models)
+struct __attribute__((visibility("hidden"))) PointAttr {
+    const char* noun;                        // what a refusal calls the values
+    icp::Format fmt;                         // how the device holds them
+    bool zero_new = false;                   // new room is zeroed, so that the padding between the clouds is never random
+    DevBuf buf[2];
+    bool have[2] = {false, false};
+    PointAttr(const char* n, icp::Format f, bool z = false) : noun(n), fmt(f), zero_new(z) {}
+};
+
 struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header only names it, as icp_ctx)
     icp_ctx* ctx = nullptr;
     int count = 0;
@@ -136,9 +152,11 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     int n_items = 0;
     long long p_plane = 0, q_plane = 0;      // elements per SoA plane of the moving / model clouds
     DevBuf P, P0, Q, items, pairs_d, ctl, idx[2], partials, mom;   // P0: the moving clouds as uploaded (icp_batch_begin)
-    DevBuf N, q_items, nbr;                  // point-to-plane: the model normals (planes as Q), the model's work items, 4 neighbours per model point
+    // a value per point of one or both sides (PointAttr: the two buffers, whether each side holds the values, the packed format).
+    // N: point-to-plane's model normals, 3 planes in the batch's precision (model-only, as grad: side 0 is never used)
+    PointAttr N{"model normals", {3, icp::PLANES, sizeof(float)}};
+    DevBuf q_items, nbr;                     // the model's work items, 4 neighbours per model point (icp_batch_estimate_normals)
     int n_q_items = 0;
-    bool have_normals = false;
     DevBuf thr;                              // the gate: every pair's squared maximum correspondence distance, in the batch's precision
     bool gated = false;                      // the batch holds thresholds (icp_batch_set_max_distance): the passes run the gated kernels
     DevBuf trim_rank, tau, dist;             // trimming: every pair's rank K (0: not trimmed), its K-th smallest squared distance of the latest matching pass, every point's winning squared distance (laid out as idx)
@@ -157,27 +175,19 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     bool have_init = false;                  // the batch holds initial transforms (icp_batch_set_initial_transforms)
     std::vector<double> T0F;                 // count x 16: every pair's transform as rounded to the batch's precision, read back in double
     std::vector<char> init_copy;             // the pair's 16 doubles were exactly the identity: its cloud is copied, its T is the loop's
-    DevBuf cov[2];                           // the generalized metric: every point's covariance, moving clouds / models -- 6 planes of doubles (xx, xy, xz, yy, yz, zz), laid out as the clouds
-    bool have_cov[2] = {false, false};       // that side holds covariances (icp_batch_set_covariances, icp_batch_estimate_covariances)
-    DevBuf cov_args;                         // icp_batch_estimate_covariances: the clouds, their work items and their k of the latest call, as one buffer
-    void* h_cov_args = nullptr;              // pinned: what that buffer is copied from (a call waits for nothing unless it wants an output)
-    size_t h_cov_cap = 0;
-    hipEvent_t cov_ev = nullptr;             // recorded behind the latest call's launch: the next call waits for it before it rewrites h_cov_args
+    PointAttr cov{"covariances", {6, icp::PLANES, sizeof(double)}};   // the generalized metric: 6 planes of doubles (xx, xy, xz, yy, yz, zz), laid out as the clouds (icp_batch_set_covariances, icp_batch_estimate_covariances)
+    Staged cov_args;                         // icp_batch_estimate_covariances: the clouds, their work items and their k of the latest call, as one buffer; recorded behind the call's launch
     std::vector<double> rot;                 // count x 9: the rotation every pair's most recent matching pass of a generalized loop rotated its moving covariances by
     size_t rot_off = 0;                      // where those rotations sit in ctl and h_ctl, behind the modes (copied by a generalized step only)
-    DevBuf inten[2];                         // the colored metric: every point's intensity, moving clouds / models -- one plane of doubles, laid out as the clouds
-    bool have_int[2] = {false, false};       // that side holds intensities (icp_batch_set_intensities)
-    DevBuf grad;                             // every model point's intensity gradient: 3 planes of doubles, laid out as the models
-    bool have_grad = false;                  // the batch holds gradients (icp_batch_set_intensity_gradients, icp_batch_estimate_intensity_gradients); new model intensities or normals discard them
-    DevBuf grad_k;                           // icp_batch_estimate_intensity_gradients: every model's k of the latest call
-    int* h_grad_k = nullptr;                 // pinned: what that buffer is copied from (a call waits for nothing unless it wants an output)
-    hipEvent_t grad_ev = nullptr;            // recorded behind the latest call's launch: the next call waits for it before it rewrites h_grad_k
+    PointAttr inten{"intensities", {1, icp::PLANES, sizeof(double)}};   // the colored metric: one plane of doubles, laid out as the clouds (icp_batch_set_intensities)
+    PointAttr grad{"intensity gradients", {3, icp::PLANES, sizeof(double)}};   // ... of the models: 3 planes of doubles (icp_batch_set_intensity_gradients, icp_batch_estimate_intensity_gradients); new model intensities or normals discard them
+    Staged grad_k;                           // icp_batch_estimate_intensity_gradients: every model's k of the latest call; recorded behind the call's launch
     DevBuf color_w;                          // every pair's lambda (double), uploaded by icp_batch_set_color_weight or by the first colored begin
     std::vector<double> lambda;              // the weights as given (empty: ICP_COLOR_LAMBDA_DEFAULT for every pair)
     bool color_w_set = false;                // color_w holds what lambda says
     int metric = ICP_POINT_TO_POINT;         // of the loop under way
-    void* h_ctl = nullptr;                   // pinned: R, t of every pair (12 values of the precision), then its mode (int)
-    double* h_mom = nullptr;                 // pinned: count x ICP_NMOM
+    PinnedBuf h_ctl;                         // R, t of every pair (12 values of the precision), then its mode (int)
+    PinnedBuf h_mom;                         // count x ICP_NMOM doubles
     size_t rt_bytes = 0, ctl_bytes = 0;
     bool begun = false;                      // a loop is under way (or has ended) and its state is readable
     long long steps = 0;                     // steps since icp_batch_begin: step k matches into idx[k & 1]
@@ -189,19 +199,15 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     std::vector<char> refused;               // icp_batch_begin refused the pair's start cloud (not finite): it is not evaluated
     // icp_batch_evaluate: buffers of its own, allocated by the first call (the loop's are never written)
     DevBuf e_mode, e_thr, e_idx, e_dist, e_partials, e_mom;
-    double* h_eval = nullptr;                // pinned: count x ICP_NMOM, the vectors of the latest evaluation
+    PinnedBuf h_eval;                        // count x ICP_NMOM doubles, the vectors of the latest evaluation
     bool eval_seen = false;                  // h_eval holds an evaluation
     // global registration (icp_batch_compute_features, _match_features, _score_transforms, _ransac)
-    DevBuf feat[2];                          // every point's descriptor, moving clouds / models: ICP_FEATURE_BINS doubles at (the cloud's offset + i) * ICP_FEATURE_BINS
-    bool have_feat[2] = {false, false};
-    DevBuf pnrm[2];                          // the point normals the descriptors are computed from, moving clouds / models: 3 planes of doubles, laid out as the clouds (not the model normals N of point-to-plane)
-    bool have_pnrm[2] = {false, false};      // that side holds point normals (icp_batch_estimate_point_normals, icp_batch_set_point_normals)
-    DevBuf nrm_args, nrm_view, nrm_cent;     // icp_batch_estimate_point_normals: the 2 * count clouds and their work items (made once: the layout never changes); 3 doubles per cloud, the viewpoints of the latest call and the centroids of the latest ICP_ORIENT_CENTROID call
-    void* h_nrm_args = nullptr;              // pinned: what nrm_args was copied from
-    double* h_nrm_view = nullptr;            // pinned: what nrm_view is copied from (a call waits for nothing unless it wants an output)
+    PointAttr feat{"descriptors", {ICP_FEATURE_BINS, icp::ROWS, sizeof(double)}};   // ICP_FEATURE_BINS doubles at (the cloud's offset + i) * ICP_FEATURE_BINS
+    PointAttr pnrm{"point normals", {3, icp::PLANES, sizeof(double)}, true};   // what the descriptors are computed from: 3 planes of doubles, laid out as the clouds (icp_batch_estimate_point_normals, icp_batch_set_point_normals; not the model normals N)
+    Staged nrm_args, nrm_view;               // icp_batch_estimate_point_normals: the 2 * count clouds and their work items (made once: the layout never changes); 3 doubles per cloud, the viewpoints of the latest call, recorded behind their upload
+    DevBuf nrm_cent;                         // ... and the centroids of the latest ICP_ORIENT_CENTROID call
     size_t nrm_off_items = 0;                // where the items start in nrm_args
     int n_nrm_items = 0;                     // 0: nrm_args is not made yet
-    hipEvent_t nrm_ev = nullptr;             // recorded behind the latest upload of the viewpoints: the next call waits for it before it rewrites h_nrm_view
     bool have_cent = false;                  // nrm_cent holds the centroids of an ICP_ORIENT_CENTROID call
     DevBuf f_fwd, f_rev, f_kept;             // the matches: fwd and kept laid out as idx, rev as the models
     DevBuf f_ci, f_cj, f_cn;                 // every pair's correspondence list (moving index, model index: int32 at p_off + e) and its length (int per pair)
@@ -215,7 +221,7 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     // Fast Global Registration (icp_batch_fgr): buffers of its own, allocated by the first call (the loop's are never written)
     DevBuf g_ui, g_uj, g_items, g_item0;     // every pair's used list (int32 at p_off + e), its work items and where each pair's items start (count + 1 ints)
     DevBuf g_ctl, g_partials, g_mom, g_w;    // FGR_CTL doubles per pair, a row per item, a vector per pair, every moving point's weight (p_plane doubles, laid out as idx)
-    double* h_fgr = nullptr;                 // pinned: count x FGR_CTL doubles (what g_ctl is copied from), then count x ICP_NMOM (what g_mom comes down into)
+    PinnedBuf h_fgr;                         // count x FGR_CTL doubles (what g_ctl is copied from), then count x ICP_NMOM (what g_mom comes down into)
     int fg_iter = 0;                         // the last icp_batch_fgr run: iterations, then per pair ...
     std::vector<std::vector<int32_t>> fg_used;   // ... the used list positions
     std::vector<double> fg_mu, fg_mom, fg_T; // ... and per iteration mu, the vector (ICP_NMOM) and the pose the terms were formed at (16)
@@ -229,6 +235,17 @@ std::string where(int p, int side) { return ": pair " + std::to_string(p) + (sid
 
 // 8, 16 or 32: the register capacity of a neighbour list that holds k entries (the kernels' cap)
 int list_cap(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : 32; }
+
+// a cloud's k of a neighbourhood call (covariances, intensity gradients, descriptors): in the range, and the cloud has k + 1
+// points; cap grows to the list that holds k.  (A statistical outlier rule's k starts at 1 and a keypoint rule has none: their own.)
+int check_k(int kk, int points, const char* one, const char* many, const std::string& at, int& cap)
+{
+    if (kk < ICP_COV_MIN_NEIGHBOURS || kk > ICP_COV_MAX_NEIGHBOURS)
+        return fail(ICP_ERR_INVALID, std::string("the neighbours (k) of ") + one + " must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]" + at);
+    if (points < kk + 1) return fail(ICP_ERR_INVALID, std::string(many) + " from k neighbours need a cloud of at least k + 1 points" + at);
+    cap = std::max(cap, list_cap(kk));
+    return ICP_OK;
+}
 
 // elements per plane of the moving clouds (sd == 0) / of the models
 size_t plane_elems(const icp_batch* b, int sd) { return (size_t)(sd ? b->q_plane : b->p_plane); }
@@ -267,28 +284,6 @@ void reset_loop_state(icp_batch* b)
     b->refused.assign((size_t)b->count, 0);
 }
 
-void release(icp_batch* b)
-{
-    for (DevBuf* d : {&b->P, &b->P0, &b->Q, &b->items, &b->pairs_d, &b->ctl, &b->idx[0], &b->idx[1], &b->partials, &b->mom, &b->N, &b->q_items, &b->nbr, &b->thr, &b->rt0, &b->init_kind, &b->init_flag,
-                      &b->trim_rank, &b->tau, &b->dist, &b->recip_d, &b->rev, &b->rob_kind, &b->rob_k, &b->rob_k2, &b->weights, &b->e_mode, &b->e_thr, &b->e_idx, &b->e_dist, &b->e_partials, &b->e_mom, &b->cov[0], &b->cov[1], &b->cov_args, &b->inten[0], &b->inten[1], &b->grad, &b->grad_k, &b->color_w,
-                      &b->pnrm[0], &b->pnrm[1], &b->nrm_args, &b->nrm_view, &b->nrm_cent,
-                      &b->feat[0], &b->feat[1], &b->f_fwd, &b->f_rev, &b->f_kept, &b->f_ci, &b->f_cj, &b->f_cn, &b->s_cand, &b->s_valid, &b->s_thr, &b->s_counts,
-                      &b->g_ui, &b->g_uj, &b->g_items, &b->g_item0, &b->g_ctl, &b->g_partials, &b->g_mom, &b->g_w})
-        d->release();
-    if (b->cov_ev) (void)hipEventDestroy(b->cov_ev);
-    if (b->grad_ev) (void)hipEventDestroy(b->grad_ev);
-    if (b->nrm_ev) (void)hipEventDestroy(b->nrm_ev);
-    if (b->h_nrm_args) (void)hipHostFree(b->h_nrm_args);
-    if (b->h_nrm_view) (void)hipHostFree(b->h_nrm_view);
-    if (b->h_grad_k) (void)hipHostFree(b->h_grad_k);
-    if (b->h_cov_args) (void)hipHostFree(b->h_cov_args);
-    if (b->h_eval) (void)hipHostFree(b->h_eval);
-    if (b->h_fgr) (void)hipHostFree(b->h_fgr);
-    if (b->h_ctl) (void)hipHostFree(b->h_ctl);
-    if (b->h_mom) (void)hipHostFree(b->h_mom);
-    delete b;
-}
-
 int check_offsets(const int64_t* off, int count, const char* what)
 {
     if (off[0] != 0) return fail(ICP_ERR_INVALID, std::string(what) + " offsets must start at 0");
@@ -309,83 +304,135 @@ bool all_finite(const void* aos, int64_t points)
     return true;
 }
 
-// one side of the batch -- the moving clouds or the models: the caller's offsets, where each cloud starts in its plane, the plane
-struct Side {
-    const int64_t* off;
-    std::vector<long long> dst;
-    long long plane;
+using icp::Side;
+
+Side side(const icp_batch* b, bool model) { return icp::make_side(b->pairs, model ? b->qoff.data() : b->moff.data(), model ? b->q_plane : b->p_plane, model); }
+
+// the clouds themselves: 3 planes of the batch's precision
+icp::Format cloud_format(const icp_batch* b) { return icp::Format{3, icp::PLANES, b->esize}; }
+
+// packed values (icp_batch_clouds.h) on their way down: download enqueues the copies of the sides whose output pointer is given,
+// the caller waits, deliver lays them out as the caller's
+struct Download {
+    std::vector<char> h[2];
 };
 
-Side side(const icp_batch* b, bool model)
+int download(icp_batch* b, const icp::Format& f, const void* const dev[2], void* const out[2], Download& d)
 {
-    Side s{model ? b->qoff.data() : b->moff.data(), std::vector<long long>((size_t)b->count), model ? b->q_plane : b->p_plane};
-    for (int p = 0; p < b->count; ++p) s.dst[p] = model ? b->pairs[p].q_off : b->pairs[p].p_off;
-    return s;
-}
-
-// V values of type E per point of one side (coordinates, normals, covariances, intensities, gradients): the caller's AoS,
-// concatenated as the clouds -> V padded planes, every cloud at its offset (the padding: all-zero bytes, 0.0 in both precisions,
-// never read), and back
-template <typename E, int V>
-void to_planes(const void* aos, const Side& s, std::vector<char>& raw)
-{
-    raw.assign(V * (size_t)s.plane * sizeof(E), 0);
-    const E* a = static_cast<const E*>(aos);
-    E* out = reinterpret_cast<E*>(raw.data());
-    for (size_t p = 0; p < s.dst.size(); ++p)
-        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
-            for (int k = 0; k < V; ++k) out[(size_t)(k * s.plane + s.dst[p] + i)] = a[V * (s.off[p] + i) + k];
-}
-
-template <typename E, int V>
-void from_planes(const std::vector<char>& raw, const Side& s, void* aos)
-{
-    const E* in = reinterpret_cast<const E*>(raw.data());
-    E* o = static_cast<E*>(aos);
-    for (size_t p = 0; p < s.dst.size(); ++p)
-        for (int64_t i = 0; i < s.off[p + 1] - s.off[p]; ++i)
-            for (int k = 0; k < V; ++k) o[V * (s.off[p] + i) + k] = in[(size_t)(k * s.plane + s.dst[p] + i)];
-}
-
-// downloads the V planes of the sides whose output pointer is given (moving clouds: dev_p -> out_p, models: dev_q -> out_q), waits
-// once and lays them out as the caller's
-template <typename E, int V>
-int download_planes(icp_batch* b, const void* dev_p, const void* dev_q, void* out_p, void* out_q)
-{
-    const void* const dev[2] = {dev_p, dev_q};
-    void* const out[2] = {out_p, out_q};
-    std::vector<char> h[2];
     for (int sd = 0; sd < 2; ++sd)
         if (out[sd]) {
-            h[sd].resize(V * plane_elems(b, sd) * sizeof(E));
-            HIP_TRY(hipMemcpyAsync(h[sd].data(), dev[sd], h[sd].size(), hipMemcpyDeviceToHost, b->ctx->stream));
+            d.h[sd].resize(f.bytes((long long)plane_elems(b, sd)));
+            HIP_TRY(hipMemcpyAsync(d.h[sd].data(), dev[sd], d.h[sd].size(), hipMemcpyDeviceToHost, b->ctx->stream));
         }
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    for (int sd = 0; sd < 2; ++sd)
-        if (out[sd]) from_planes<E, V>(h[sd], side(b, sd != 0), out[sd]);
     return ICP_OK;
 }
 
-// the moving clouds' (the models') layout, in the batch's precision: AoS as the caller holds it -> the planes of `dev`.  Enqueues
-// the copy from `host`, which must outlive it: the caller synchronises.
-int enqueue_planes(icp_batch* b, const void* aos, bool model, void* dev, std::vector<char>& host)
+void deliver(const icp_batch* b, const icp::Format& f, const Download& d, void* const out[2])
 {
-    if (b->prec == ICP_F64) to_planes<double, 3>(aos, side(b, model), host);
-    else to_planes<float, 3>(aos, side(b, model), host);
+    for (int sd = 0; sd < 2; ++sd)
+        if (out[sd]) icp::decode(f, side(b, sd != 0), d.h[sd].data(), out[sd]);
+}
+
+// ... both, around the one wait
+int fetch(icp_batch* b, const icp::Format& f, const void* const dev[2], void* const out[2])
+{
+    Download d;
+    if (int rc = download(b, f, dev, out, d)) return rc;
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    deliver(b, f, d, out);
+    return ICP_OK;
+}
+
+int fetch(icp_batch* b, const PointAttr& a, void* const out[2])
+{
+    const void* const dev[2] = {a.buf[0].p, a.buf[1].p};
+    return fetch(b, a.fmt, dev, out);
+}
+
+int fetch_clouds(icp_batch* b, const void* dev_p, const void* dev_q, void* out_p, void* out_q)
+{
+    const void* const dev[2] = {dev_p, dev_q};
+    void* const out[2] = {out_p, out_q};
+    return fetch(b, cloud_format(b), dev, out);
+}
+
+// the caller's values of one side -> `host`, packed, and on their way to `dev`.  `host` must outlive the copy: the caller waits
+int enqueue_packed(icp_batch* b, const icp::Format& f, const void* own, bool model, void* dev, std::vector<char>& host)
+{
+    icp::encode(f, side(b, model), own, host);
     HIP_TRY(hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, b->ctx->stream));
     return ICP_OK;
 }
 
-// ... and back: such planes downloaded into `raw` -> AoS in the caller's layout
-void planes_to_aos(const icp_batch* b, const std::vector<char>& raw, bool model, void* aos)
+constexpr const char* kPointNormalsFirst = " (icp_batch_estimate_point_normals or icp_batch_set_point_normals first)";
+
+// ---- a value per point (PointAttr).  A set call is  attr_reserve, [what the call invalidates,] attr_commit;  a get call is attr_get.
+size_t attr_bytes(const icp_batch* b, const PointAttr& a, int sd) { return a.fmt.bytes((long long)plane_elems(b, sd)); }
+
+// room for one side's values
+int attr_room(icp_batch* b, PointAttr& a, int sd)
 {
-    if (b->prec == ICP_F64) from_planes<double, 3>(raw, side(b, model), aos);
-    else from_planes<float, 3>(raw, side(b, model), aos);
+    const size_t bytes = attr_bytes(b, a, sd);
+    if (!a.zero_new) {
+        HIP_TRY(a.buf[sd].ensure(bytes));
+        return ICP_OK;
+    }
+    if (a.buf[sd].p && bytes <= a.buf[sd].cap) return ICP_OK;
+    HIP_TRY(a.buf[sd].ensure(bytes));
+    HIP_TRY(hipMemsetAsync(a.buf[sd].p, 0, bytes, b->ctx->stream));
+    return ICP_OK;
 }
 
-int download_clouds(icp_batch* b, const void* dev_p, const void* dev_q, void* out_p, void* out_q)
+// the values given (doubles) are finite -- `one`, not NULL, is what the refusal calls a value -- and the sides given have room.
+// A refusal leaves the batch as it was
+int attr_reserve(icp_batch* b, PointAttr& a, const void* const given[2], const char* one)
 {
-    return b->prec == ICP_F64 ? download_planes<double, 3>(b, dev_p, dev_q, out_p, out_q) : download_planes<float, 3>(b, dev_p, dev_q, out_p, out_q);
+    for (int sd = 0; one && sd < 2; ++sd) {
+        if (!given[sd]) continue;
+        const double* v = static_cast<const double*>(given[sd]);
+        const int64_t* off = sd ? b->qoff.data() : b->moff.data();
+        const int w = a.fmt.width;
+        for (int p = 0; p < b->count; ++p)
+            for (int64_t i = w * off[p]; i < w * off[p + 1]; ++i)
+                if (!std::isfinite(v[i])) return fail(ICP_ERR_INVALID, std::string(one) + " has a NaN or an infinite value" + where(p, sd));
+    }
+    for (int sd = 0; sd < 2; ++sd)
+        if (given[sd])
+            if (int rc = attr_room(b, a, sd)) return rc;
+    return ICP_OK;
+}
+
+// the sides given hold nothing, are encoded and copied; one wait; they hold the values
+int attr_commit(icp_batch* b, PointAttr& a, const void* const given[2])
+{
+    std::vector<char> h[2];
+    for (int sd = 0; sd < 2; ++sd) {
+        if (!given[sd]) continue;
+        a.have[sd] = false;
+        if (int rc = enqueue_packed(b, a.fmt, given[sd], sd != 0, a.buf[sd].p, h[sd])) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
+    for (int sd = 0; sd < 2; ++sd)
+        if (given[sd]) a.have[sd] = true;
+    return ICP_OK;
+}
+
+// "the batch holds no point normals of the models (... first)", for the first side asked for that holds none
+int attr_held(const PointAttr& a, const bool asked[2], const char* hint)
+{
+    for (int sd = 0; sd < 2; ++sd)
+        if (asked[sd] && !a.have[sd])
+            return fail(ICP_ERR_STATE, std::string("the batch holds no ") + a.noun + " of the " + (sd ? "models" : "moving clouds") + hint);
+    return ICP_OK;
+}
+
+int attr_get(icp_batch* b, const PointAttr& a, void* const out[2], const char* hint)
+{
+    if (int rc = ready(b)) return rc;
+    if (!out[0] && !out[1]) return fail(ICP_ERR_INVALID, "output pointer == NULL");
+    const bool asked[2] = {out[0] != nullptr, out[1] != nullptr};
+    if (int rc = attr_held(a, asked, hint)) return rc;
+    return fetch(b, a, out);
 }
 
 // element i of an array in the batch's precision: written from a double (rounded once), read back as a double
@@ -446,6 +493,7 @@ int lay_out(icp_ctx* c, int count, int precision, const int64_t* moving_off, con
     b->count = count;
     b->prec = precision;
     b->esize = precision == ICP_F64 ? sizeof(double) : sizeof(float);
+    b->N.fmt.esize = b->esize;
     b->moff.assign(moving_off, moving_off + count + 1);
     b->qoff.assign(model_off, model_off + count + 1);
     b->pairs.resize((size_t)count);
@@ -498,9 +546,9 @@ int allocate(icp_batch* b, std::vector<icp::BatchItem>& items)
     b->rot_off = (b->ctl_bytes + 7) / 8 * 8;   // (room for 9 doubles per pair behind the control words: a generalized step's rotations)
     const size_t ctl_room = b->rot_off + (size_t)b->count * 9 * sizeof(double);
     HIP_TRY(b->ctl.ensure(ctl_room));
-    HIP_TRY(hipHostMalloc(&b->h_ctl, ctl_room, hipHostMallocDefault));
-    std::memset(b->h_ctl, 0, ctl_room);
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_mom), (size_t)b->count * ICP_NMOM * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(b->h_ctl.ensure(ctl_room));
+    std::memset(b->h_ctl.p, 0, ctl_room);
+    HIP_TRY(b->h_mom.ensure((size_t)b->count * ICP_NMOM * sizeof(double)));
     return ICP_OK;
 }
 
@@ -511,8 +559,8 @@ int upload(icp_batch* b, const void* moving, const void* model)
     std::vector<icp::BatchItem> items;
     std::vector<char> ps, qs;
     int rc = allocate(b, items);
-    if (rc == ICP_OK) rc = enqueue_planes(b, moving, false, b->P0.p, ps);
-    if (rc == ICP_OK) rc = enqueue_planes(b, model, true, b->Q.p, qs);
+    if (rc == ICP_OK) rc = enqueue_packed(b, cloud_format(b), moving, false, b->P0.p, ps);
+    if (rc == ICP_OK) rc = enqueue_packed(b, cloud_format(b), model, true, b->Q.p, qs);
     const hipError_t es = hipStreamSynchronize(c->stream);   // (always, a refusal included: before the host vectors go)
     if (rc != ICP_OK) return rc;
     HIP_TRY(es);
@@ -776,18 +824,18 @@ int select_keypoints(icp_batch* src, const std::vector<icp::KeypointRule>& rules
     if (int rc = thin_allocate(th, made)) return rc;
     thin_args(a, th);
     for (int sd = 0; sd < 2; ++sd) {   // the descriptors of the kept points, where the source holds that side's
-        if (!src->have_feat[sd]) continue;
-        const size_t fb = ICP_FEATURE_BINS * plane_elems(th.nb, sd) * sizeof(double);
-        HIP_TRY(th.nb->feat[sd].ensure(fb));
-        HIP_TRY(hipMemsetAsync(th.nb->feat[sd].p, 0, fb, th.st));   // (the padding, as icp_batch_compute_features leaves it)
-        a.src_feat[sd] = (const unsigned long long*)src->feat[sd].p;
-        a.dst_feat[sd] = (unsigned long long*)th.nb->feat[sd].p;
+        if (!src->feat.have[sd]) continue;
+        const size_t fb = attr_bytes(th.nb, th.nb->feat, sd);
+        HIP_TRY(th.nb->feat.buf[sd].ensure(fb));
+        HIP_TRY(hipMemsetAsync(th.nb->feat.buf[sd].p, 0, fb, th.st));   // (the padding, as icp_batch_compute_features leaves it)
+        a.src_feat[sd] = (const unsigned long long*)src->feat.buf[sd].p;
+        a.dst_feat[sd] = (unsigned long long*)th.nb->feat.buf[sd].p;
     }
     HIP_TRY(icp::launch_batch_keypoint_compact(a, th.st));
     if (int rc = thin_download(th)) return rc;
     if (int rc = thin_finish(th)) return rc;
-    th.nb->have_feat[0] = src->have_feat[0];
-    th.nb->have_feat[1] = src->have_feat[1];
+    th.nb->feat.have[0] = src->feat.have[0];
+    th.nb->feat.have[1] = src->feat.have[1];
     if (count_out) std::memcpy(count_out, th.kept.data(), th.kept.size() * sizeof(int32_t));
     return ICP_OK;
 }
@@ -816,7 +864,7 @@ int step(icp_batch* b)
     icp_ctx* c = b->ctx;
     const int cur = (int)(b->steps & 1);
     const bool generalized = b->metric == ICP_GENERALIZED;
-    int* mode = reinterpret_cast<int*>(static_cast<char*>(b->h_ctl) + b->rt_bytes);
+    int* mode = reinterpret_cast<int*>(b->h_ctl.as<char>() + b->rt_bytes);
     for (int p = 0; p < b->count; ++p) {
         mode[p] = 0;
         if (!running(b, p)) continue;
@@ -824,7 +872,7 @@ int step(icp_batch* b)
         const bool apply = H.have_rt;
         const bool final_only = H.next_is_final();   // the loop ends after this error whatever it is: nothing is matched
         if (apply) {
-            void* rt = static_cast<char*>(b->h_ctl) + (size_t)p * 12 * b->esize;
+            void* rt = b->h_ctl.as<char>() + (size_t)p * 12 * b->esize;
             if (b->prec == ICP_F64) put_rt<double>(rt, H.R, H.t);
             else put_rt<float>(rt, H.R, H.t);
             b->applied_buf[p] = b->last_match[p];
@@ -843,8 +891,8 @@ int step(icp_batch* b)
             }
         }
     }
-    if (generalized) std::memcpy(static_cast<char*>(b->h_ctl) + b->rot_off, b->rot.data(), b->rot.size() * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(b->ctl.p, b->h_ctl, generalized ? b->rot_off + b->rot.size() * sizeof(double) : b->ctl_bytes, hipMemcpyHostToDevice, c->stream));
+    if (generalized) std::memcpy(b->h_ctl.as<char>() + b->rot_off, b->rot.data(), b->rot.size() * sizeof(double));
+    HIP_TRY(hipMemcpyAsync(b->ctl.p, b->h_ctl.p, generalized ? b->rot_off + b->rot.size() * sizeof(double) : b->ctl_bytes, hipMemcpyHostToDevice, c->stream));
     icp::BatchPassArgs a{};
     a.precision = b->prec;
     a.metric = b->metric;
@@ -857,7 +905,7 @@ int step(icp_batch* b)
     a.P_soa = b->P.p;
     a.p_plane = b->p_plane;
     a.Q_soa = b->Q.p;
-    a.N_soa = b->metric == ICP_POINT_TO_PLANE || b->metric == ICP_COLORED ? b->N.p : nullptr;
+    a.N_soa = b->metric == ICP_POINT_TO_PLANE || b->metric == ICP_COLORED ? b->N.buf[1].p : nullptr;
     a.q_plane = b->q_plane;
     a.idx_prev = (const int32_t*)b->idx[cur ^ 1].p;
     a.idx_cur = (int32_t*)b->idx[cur].p;
@@ -876,25 +924,25 @@ int step(icp_batch* b)
     a.robust_k2 = (const double*)b->rob_k2.p;
     a.weights = (double*)b->weights.p;
     if (generalized) {
-        a.cov_p = (const double*)b->cov[0].p;
-        a.cov_q = (const double*)b->cov[1].p;
+        a.cov_p = (const double*)b->cov.buf[0].p;
+        a.cov_q = (const double*)b->cov.buf[1].p;
         a.rot = reinterpret_cast<const double*>(static_cast<const char*>(b->ctl.p) + b->rot_off);
     }
     if (b->metric == ICP_COLORED) {
-        a.int_p = (const double*)b->inten[0].p;
-        a.int_q = (const double*)b->inten[1].p;
-        a.grad_q = (const double*)b->grad.p;
+        a.int_p = (const double*)b->inten.buf[0].p;
+        a.int_q = (const double*)b->inten.buf[1].p;
+        a.grad_q = (const double*)b->grad.buf[1].p;
         a.color_w = (const double*)b->color_w.p;
     }
     HIP_TRY(icp::launch_batch_pass(a, c->stream));
-    HIP_TRY(hipMemcpyAsync(b->h_mom, b->mom.p, (size_t)b->count * ICP_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(b->h_mom.p, b->mom.p, (size_t)b->count * ICP_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     b->steps += 1;
     for (int p = 0; p < b->count; ++p) {
         if (mode[p] == 0) continue;
         if (mode[p] & icp::BATCH_MATCH) b->tau_seen[p] = 1;
         b->mom_seen[p] = 1;   // (a pair that takes no part in a later step keeps this row: batch_finalize_kernel skips it)
-        const int rc = b->H[p].advance(b->h_mom + (size_t)p * ICP_NMOM);
+        const int rc = b->H[p].advance(b->h_mom.as<double>() + (size_t)p * ICP_NMOM);
         if (rc != ICP_OK) {   // a numeric failure ends this pair only; what its completed passes produced stays readable
             b->status[p] = rc;
             b->H[p].done = true;
@@ -946,7 +994,7 @@ int hand_over(icp_batch* src, int rc, icp_batch* made, icp_batch** out)
     if (rc != ICP_OK) {
         (void)hipStreamSynchronize(src->ctx->stream);
         (void)hipGetLastError();
-        if (made) release(made);
+        if (made) delete made;
         return rc;
     }
     *out = made;
@@ -979,7 +1027,7 @@ int icp_batch_create(icp_ctx* c, int count, const void* moving_aos, const int64_
     if (int rc = lay_out(c, count, precision, moving_off, model_off, &b)) return rc;
     if (int rc = upload(b, moving_aos, model_aos)) {
         (void)hipStreamSynchronize(c->stream);
-        release(b);
+        delete b;
         return rc;
     }
     *out = b;
@@ -1087,14 +1135,14 @@ int icp_batch_get_offsets(icp_batch* b, int64_t* moving_off_out, int64_t* model_
 int icp_batch_get_clouds(icp_batch* b, void* moving_aos_out, void* model_aos_out)
 {
     if (int rc = ready(b)) return rc;
-    return download_clouds(b, b->P0.p, b->Q.p, moving_aos_out, model_aos_out);
+    return fetch_clouds(b, b->P0.p, b->Q.p, moving_aos_out, model_aos_out);
 }
 
 void icp_batch_destroy(icp_batch* b)
 {
     if (!b) return;
     (void)hipSetDevice(b->ctx->device);
-    release(b);
+    delete b;
 }
 
 int icp_batch_begin(icp_batch* b, const icp_params* prm)
@@ -1103,20 +1151,20 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
     if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
     if (prm->metric != ICP_POINT_TO_POINT && prm->metric != ICP_POINT_TO_PLANE && prm->metric != ICP_GENERALIZED && prm->metric != ICP_COLORED)
         return fail(ICP_ERR_INVALID, "unknown metric");
-    if (prm->metric == ICP_POINT_TO_PLANE && !b->have_normals)
+    if (prm->metric == ICP_POINT_TO_PLANE && !b->N.have[1])
         return fail(ICP_ERR_INVALID, "a point-to-plane batch needs the model normals: icp_batch_set_model_normals or icp_batch_estimate_normals first");
     if (prm->metric == ICP_GENERALIZED) {
-        if (!b->have_cov[0] || !b->have_cov[1])
+        if (!b->cov.have[0] || !b->cov.have[1])
             return fail(ICP_ERR_INVALID, std::string("a generalized batch needs covariances on both sides (icp_batch_set_covariances or icp_batch_estimate_covariances first): the ") +
-                                             (!b->have_cov[0] ? "moving clouds" : "models") + " have none");
+                                             (!b->cov.have[0] ? "moving clouds" : "models") + " have none");
         if (b->robust) return fail(ICP_ERR_INVALID, "the generalized metric takes no robust kernels (icp_batch_set_robust(NULL) first)");
         HIP_TRY(b->dist.ensure((size_t)b->p_plane * b->esize));   // (the deferred route's winning distances)
     }
     if (prm->metric == ICP_COLORED) {
-        const char* missing = !b->have_normals ? "the model normals (icp_batch_set_model_normals or icp_batch_estimate_normals)"
-                              : !b->have_int[0] ? "the intensities of the moving clouds (icp_batch_set_intensities)"
-                              : !b->have_int[1] ? "the intensities of the models (icp_batch_set_intensities)"
-                              : !b->have_grad   ? "the intensity gradients of the models (icp_batch_estimate_intensity_gradients or icp_batch_set_intensity_gradients)"
+        const char* missing = !b->N.have[1] ? "the model normals (icp_batch_set_model_normals or icp_batch_estimate_normals)"
+                              : !b->inten.have[0] ? "the intensities of the moving clouds (icp_batch_set_intensities)"
+                              : !b->inten.have[1] ? "the intensities of the models (icp_batch_set_intensities)"
+                              : !b->grad.have[1] ? "the intensity gradients of the models (icp_batch_estimate_intensity_gradients or icp_batch_set_intensity_gradients)"
                                                 : nullptr;
         if (missing) return fail(ICP_ERR_INVALID, std::string("a colored batch needs model normals, intensities on both sides and intensity gradients: it lacks ") + missing);
         if (b->robust) return fail(ICP_ERR_INVALID, "the colored metric takes no robust kernels (icp_batch_set_robust(NULL) first)");
@@ -1204,8 +1252,8 @@ int icp_diag_batch_moments(icp_batch* b, int pair, double* out32)
 {
     if (!b || !out32) return fail(ICP_ERR_INVALID, "null argument");
     if (pair < 0 || pair >= b->count) return fail(ICP_ERR_INVALID, "pair out of range");
-    if (!b->begun || !b->mom_seen[pair] || !b->h_mom) return fail(ICP_ERR_STATE, "no completed pass of this pair");
-    std::memcpy(out32, b->h_mom + (size_t)pair * ICP_NMOM, ICP_NMOM * sizeof(double));
+    if (!b->begun || !b->mom_seen[pair] || !b->h_mom.p) return fail(ICP_ERR_STATE, "no completed pass of this pair");
+    std::memcpy(out32, b->h_mom.as<double>() + (size_t)pair * ICP_NMOM, ICP_NMOM * sizeof(double));
     return ICP_OK;
 }
 
@@ -1234,7 +1282,7 @@ int icp_batch_evaluate(icp_batch* b, int metric, const double* max_dist, int* st
     if (metric != ICP_POINT_TO_POINT && metric != ICP_POINT_TO_PLANE) return fail(ICP_ERR_INVALID, "unknown metric");
     if (!b->begun) return fail(ICP_ERR_STATE, "icp_batch_begin first: an evaluation needs the clouds of a loop");
     const bool plane = metric == ICP_POINT_TO_PLANE;
-    if (plane && !b->have_normals)
+    if (plane && !b->N.have[1])
         return fail(ICP_ERR_INVALID, "a point-to-plane evaluation needs the model normals: icp_batch_set_model_normals or icp_batch_estimate_normals first");
     if (max_dist)
         for (int p = 0; p < b->count; ++p)   // (icp_batch_set_max_distance's rule: NaN fails the comparison too; -inf is <= 0)
@@ -1249,7 +1297,7 @@ int icp_batch_evaluate(icp_batch* b, int metric, const double* max_dist, int* st
     HIP_TRY(b->e_dist.ensure((size_t)b->p_plane * b->esize));
     HIP_TRY(b->e_partials.ensure((size_t)b->n_items * ICP_NMOM * sizeof(double)));
     HIP_TRY(b->e_mom.ensure(vec_bytes));
-    if (!b->h_eval) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_eval), vec_bytes, hipHostMallocDefault));
+    HIP_TRY(b->h_eval.ensure(vec_bytes));
     // every pair is evaluated where its cloud stands -- running, ended or failed -- but one whose start cloud was refused
     std::vector<int> mode((size_t)b->count);
     for (int p = 0; p < b->count; ++p) mode[p] = b->refused[p] ? 0 : icp::BATCH_MATCH;
@@ -1271,7 +1319,7 @@ int icp_batch_evaluate(icp_batch* b, int metric, const double* max_dist, int* st
     a.P_soa = b->P.p;
     a.p_plane = b->p_plane;
     a.Q_soa = b->Q.p;
-    a.N_soa = plane ? b->N.p : nullptr;
+    a.N_soa = plane ? b->N.buf[1].p : nullptr;
     a.q_plane = b->q_plane;
     a.thr = max_dist ? b->e_thr.p : nullptr;
     a.idx = (int32_t*)b->e_idx.p;
@@ -1280,7 +1328,7 @@ int icp_batch_evaluate(icp_batch* b, int metric, const double* max_dist, int* st
     a.mom = (double*)b->e_mom.p;
     std::vector<int32_t> hidx;
     hipError_t e = icp::launch_batch_evaluate(a, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b->h_eval, b->e_mom.p, vec_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b->h_eval.p, b->e_mom.p, vec_bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && (idx_out || mask_out)) {
         hidx.resize((size_t)b->p_plane);
         e = hipMemcpyAsync(hidx.data(), b->e_idx.p, hidx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
@@ -1294,7 +1342,7 @@ int icp_batch_evaluate(icp_batch* b, int metric, const double* max_dist, int* st
     }
     b->eval_seen = true;
     for (int p = 0; p < b->count; ++p) {
-        double* v = b->h_eval + (size_t)p * ICP_NMOM;
+        double* v = b->h_eval.as<double>() + (size_t)p * ICP_NMOM;
         const int n = b->pairs[p].n;
         if (b->refused[p]) std::memset(v, 0, ICP_NMOM * sizeof(double));   // (its row of the device vector was never written)
         const double cnt = v[ICP_EVAL_CNT];
@@ -1337,8 +1385,8 @@ int icp_diag_batch_eval_moments(icp_batch* b, int pair, double* out32)
 {
     if (!b || !out32) return fail(ICP_ERR_INVALID, "null argument");
     if (pair < 0 || pair >= b->count) return fail(ICP_ERR_INVALID, "pair out of range");
-    if (!b->eval_seen || !b->h_eval) return fail(ICP_ERR_STATE, "no evaluation of this batch");
-    std::memcpy(out32, b->h_eval + (size_t)pair * ICP_NMOM, ICP_NMOM * sizeof(double));
+    if (!b->eval_seen || !b->h_eval.p) return fail(ICP_ERR_STATE, "no evaluation of this batch");
+    std::memcpy(out32, b->h_eval.as<double>() + (size_t)pair * ICP_NMOM, ICP_NMOM * sizeof(double));
     return ICP_OK;
 }
 
@@ -1354,7 +1402,7 @@ int icp_batch_get_moving(icp_batch* b, void* aos_out)
 {
     if (int rc = ready(b)) return rc;
     if (!aos_out) return fail(ICP_ERR_INVALID, "aos_out == NULL");
-    return download_clouds(b, b->P.p, nullptr, aos_out, nullptr);
+    return fetch_clouds(b, b->P.p, nullptr, aos_out, nullptr);
 }
 
 int icp_batch_get_indices(icp_batch* b, int32_t* idx_out) { return download_indices(b, false, idx_out); }
@@ -1523,12 +1571,9 @@ int icp_batch_get_weights(icp_batch* b, double* w_out)
         for (size_t i = 0; i < mask.size(); ++i) w_out[i] = mask[i] ? 1.0 : 0.0;
         return ICP_OK;
     }
-    std::vector<double> h((size_t)b->p_plane);
-    HIP_TRY(hipMemcpyAsync(h.data(), b->weights.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    for (int p = 0; p < b->count; ++p)
-        std::memcpy(w_out + b->moff[p], h.data() + b->pairs[p].p_off, (size_t)b->pairs[p].n * sizeof(double));
-    return ICP_OK;
+    const void* const dev[2] = {b->weights.p, nullptr};
+    void* const out[2] = {w_out, nullptr};
+    return fetch(b, icp::Format{1, icp::PLANES, sizeof(double)}, dev, out);
 }
 
 int icp_diag_batch_reverse(icp_batch* b, int32_t* rev_out)
@@ -1613,15 +1658,11 @@ int icp_batch_set_model_normals(icp_batch* b, const void* nxyz_aos)
     const int64_t points = b->qoff[b->count];
     if (!(b->prec == ICP_F64 ? all_finite<double>(nxyz_aos, points) : all_finite<float>(nxyz_aos, points)))
         return fail(ICP_ERR_INVALID, "a normal of the batch has a NaN or an infinite component");
-    HIP_TRY(b->N.ensure(3 * (size_t)b->q_plane * b->esize));
+    const void* const given[2] = {nullptr, nxyz_aos};
+    if (int rc = attr_reserve(b, b->N, given, nullptr)) return rc;   // (scanned above: one refusal for the whole batch)
     b->begun = false;   // a loop under way is discarded: its passes so far used other normals (or none)
-    b->have_normals = false;
-    b->have_grad = false;   // (intensity gradients lie in the tangent planes of the normals they were made with)
-    std::vector<char> ns;
-    if (int rc = enqueue_planes(b, nxyz_aos, true, b->N.p, ns)) return rc;
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
-    b->have_normals = true;
-    return ICP_OK;
+    b->grad.have[1] = false;   // (intensity gradients lie in the tangent planes of the normals they were made with)
+    return attr_commit(b, b->N, given);
 }
 
 int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighbours_out)
@@ -1635,30 +1676,29 @@ int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighb
     const size_t qb = 3 * (size_t)b->q_plane * b->esize, nb = 4 * (size_t)b->q_plane * sizeof(int32_t);
     if (int rc = ensure_model_items(b)) return rc;   // BATCH_ITEM model points of one pair, cut from that pair's first model point
     HIP_TRY(b->nbr.ensure(nb));
-    HIP_TRY(b->N.ensure(qb));
+    if (int rc = attr_room(b, b->N, 1)) return rc;
     b->begun = false;   // a loop under way is discarded
-    b->have_normals = false;
-    b->have_grad = false;   // (intensity gradients lie in the tangent planes of the normals they were made with)
+    b->N.have[1] = false;
+    b->grad.have[1] = false;   // (intensity gradients lie in the tangent planes of the normals they were made with)
     HIP_TRY(hipMemsetAsync(b->nbr.p, 0, nb, c->stream));   // (the padding between the clouds: never read, never random)
-    HIP_TRY(hipMemsetAsync(b->N.p, 0, qb, c->stream));
+    HIP_TRY(hipMemsetAsync(b->N.buf[1].p, 0, qb, c->stream));
     HIP_TRY(icp::launch_batch_normals(b->prec, (const icp::BatchItem*)b->q_items.p, b->n_q_items, (const icp::BatchPair*)b->pairs_d.p, b->Q.p,
-                                      b->q_plane, (int32_t*)b->nbr.p, b->N.p, c->stream));
-    std::vector<char> raw;
+                                      b->q_plane, (int32_t*)b->nbr.p, b->N.buf[1].p, c->stream));
+    const void* const dev[2] = {nullptr, b->N.buf[1].p};
+    void* const out[2] = {nullptr, nxyz_aos_out};
+    Download d;
     std::vector<int32_t> hn;
-    if (nxyz_aos_out) {
-        raw.resize(qb);
-        HIP_TRY(hipMemcpyAsync(raw.data(), b->N.p, qb, hipMemcpyDeviceToHost, c->stream));
-    }
+    if (int rc = download(b, b->N.fmt, dev, out, d)) return rc;
     if (neighbours_out) {
         hn.resize(4 * (size_t)b->q_plane);
         HIP_TRY(hipMemcpyAsync(hn.data(), b->nbr.p, nb, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (nxyz_aos_out) planes_to_aos(b, raw, true, nxyz_aos_out);
+    deliver(b, b->N.fmt, d, out);
     if (neighbours_out)
         for (int p = 0; p < b->count; ++p)
             std::memcpy(neighbours_out + 4 * b->qoff[p], hn.data() + 4 * (size_t)b->pairs[p].q_off, 4 * (size_t)b->pairs[p].m * sizeof(int32_t));
-    b->have_normals = true;
+    b->N.have[1] = true;
     return ICP_OK;
 }
 
@@ -1678,31 +1718,11 @@ void pack_args(void* dst, const icp::ArgsLayout& lay, const icp::CloudList& cl, 
 int icp_batch_set_covariances(icp_batch* b, const double* moving_cov, const double* model_cov)
 {
     if (int rc = ready(b)) return rc;
-    const double* given[2] = {moving_cov, model_cov};
+    const void* const given[2] = {moving_cov, model_cov};
     if (!given[0] && !given[1]) return fail(ICP_ERR_INVALID, "moving_cov == NULL and model_cov == NULL");
-    for (int side = 0; side < 2; ++side) {
-        if (!given[side]) continue;
-        const int64_t* off = side ? b->qoff.data() : b->moff.data();
-        for (int p = 0; p < b->count; ++p)
-            for (int64_t i = 6 * off[p]; i < 6 * off[p + 1]; ++i)
-                if (!std::isfinite(given[side][i]))
-                    return fail(ICP_ERR_INVALID, "a covariance has a NaN or an infinite value" + where(p, side));
-    }
-    // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
-    for (int side = 0; side < 2; ++side)
-        if (given[side]) HIP_TRY(b->cov[side].ensure(6 * plane_elems(b, side) * sizeof(double)));
+    if (int rc = attr_reserve(b, b->cov, given, "a covariance")) return rc;
     b->begun = false;   // a loop under way is discarded: its passes so far used other covariances (or none)
-    std::vector<char> h[2];
-    for (int side = 0; side < 2; ++side) {
-        if (!given[side]) continue;
-        b->have_cov[side] = false;
-        to_planes<double, 6>(given[side], ::side(b, side != 0), h[side]);
-        HIP_TRY(hipMemcpyAsync(b->cov[side].p, h[side].data(), h[side].size(), hipMemcpyHostToDevice, b->ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
-    for (int side = 0; side < 2; ++side)
-        if (given[side]) b->have_cov[side] = true;
-    return ICP_OK;
+    return attr_commit(b, b->cov, given);
 }
 
 int icp_batch_estimate_covariances(icp_batch* b, const int* k_moving, const int* k_model, int regularisation, double lambda,
@@ -1720,13 +1740,8 @@ int icp_batch_estimate_covariances(icp_batch* b, const int* k_moving, const int*
     int cap = 8;
     for (int side = 0; side < 2; ++side)
         for (int p = 0; given[side] && p < count; ++p) {
-            const int kk = given[side][p];
-            if (kk < ICP_COV_MIN_NEIGHBOURS || kk > ICP_COV_MAX_NEIGHBOURS)
-                return fail(ICP_ERR_INVALID, "the neighbours (k) of a covariance must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]" + where(p, side));
-            if ((side ? b->pairs[p].m : b->pairs[p].n) < kk + 1)
-                return fail(ICP_ERR_INVALID, "covariances from k neighbours need a cloud of at least k + 1 points" + where(p, side));
-            ks[(size_t)side * count + p] = kk;
-            cap = std::max(cap, list_cap(kk));
+            if (int rc = check_k(given[side][p], side ? b->pairs[p].m : b->pairs[p].n, "a covariance", "covariances", where(p, side), cap)) return rc;
+            ks[(size_t)side * count + p] = given[side][p];
         }
     const bool want[2] = {given[0] != nullptr, given[1] != nullptr};   // work items for the sides asked for
     icp::CloudList cl;
@@ -1738,26 +1753,19 @@ int icp_batch_estimate_covariances(icp_batch* b, const int* k_moving, const int*
     // has to outlive it on the stack: the call returns without a host wait unless an output is wanted.  The allocations come
     // before the batch changes: a call refused for want of memory leaves it as it was
     const icp::ArgsLayout lay = icp::lay_out_args(cl.clouds.size(), cl.items.size(), ks.size());
-    if (b->cov_ev) HIP_TRY(hipEventSynchronize(b->cov_ev));   // (the call before has long read the host buffer: no wait in practice)
-    else HIP_TRY(hipEventCreateWithFlags(&b->cov_ev, hipEventDisableTiming));
-    if (lay.bytes > b->h_cov_cap) {
-        if (b->h_cov_args) (void)hipHostFree(b->h_cov_args);
-        b->h_cov_args = nullptr;
-        b->h_cov_cap = 0;
-        HIP_TRY(hipHostMalloc(&b->h_cov_args, lay.bytes, hipHostMallocDefault));
-        b->h_cov_cap = lay.bytes;
-    }
+    HIP_TRY(b->cov_args.wait());   // (the call before has long read the host buffer: no wait in practice)
     HIP_TRY(b->cov_args.ensure(lay.bytes));
     for (int side = 0; side < 2; ++side)
-        if (given[side]) HIP_TRY(b->cov[side].ensure(6 * plane_elems(b, side) * sizeof(double)));
+        if (given[side])
+            if (int rc = attr_room(b, b->cov, side)) return rc;
     b->begun = false;   // a loop under way is discarded
     for (int side = 0; side < 2; ++side)
-        if (given[side]) b->have_cov[side] = false;
-    pack_args(b->h_cov_args, lay, cl, &ks);
-    HIP_TRY(hipMemcpyAsync(b->cov_args.p, b->h_cov_args, lay.bytes, hipMemcpyHostToDevice, st));
+        if (given[side]) b->cov.have[side] = false;
+    pack_args(b->cov_args.host.p, lay, cl, &ks);
+    HIP_TRY(b->cov_args.copy(lay.bytes, st));
     for (int side = 0; side < 2; ++side)   // (the padding between the clouds: never read, never random)
-        if (given[side]) HIP_TRY(hipMemsetAsync(b->cov[side].p, 0, 6 * plane_elems(b, side) * sizeof(double), st));
-    const char* ds = static_cast<const char*>(b->cov_args.p);
+        if (given[side]) HIP_TRY(hipMemsetAsync(b->cov.buf[side].p, 0, attr_bytes(b, b->cov, side), st));
+    const char* ds = static_cast<const char*>(b->cov_args.dev.p);
     icp::BatchCovArgs a{};
     a.precision = b->prec;
     a.cap = cap;
@@ -1771,109 +1779,78 @@ int icp_batch_estimate_covariances(icp_batch* b, const int* k_moving, const int*
     a.src[1] = b->Q.p;
     a.src_plane[0] = b->p_plane;
     a.src_plane[1] = b->q_plane;
-    a.cov[0] = (double*)b->cov[0].p;
-    a.cov[1] = (double*)b->cov[1].p;
+    a.cov[0] = (double*)b->cov.buf[0].p;
+    a.cov[1] = (double*)b->cov.buf[1].p;
     HIP_TRY(icp::launch_batch_covariances(a, st));
-    HIP_TRY(hipEventRecord(b->cov_ev, st));
-    double* const out[2] = {given[0] ? moving_cov_out : nullptr, given[1] ? model_cov_out : nullptr};
-    if (out[0] || out[1]) {
-        if (int rc = download_planes<double, 6>(b, b->cov[0].p, b->cov[1].p, out[0], out[1])) return rc;   // (the one wait of a call that wants an output)
-    }
+    HIP_TRY(b->cov_args.record(st));
+    void* const out[2] = {given[0] ? moving_cov_out : nullptr, given[1] ? model_cov_out : nullptr};
+    if (out[0] || out[1])
+        if (int rc = fetch(b, b->cov, out)) return rc;   // (the one wait of a call that wants an output)
     for (int side = 0; side < 2; ++side)
-        if (given[side]) b->have_cov[side] = true;
+        if (given[side]) b->cov.have[side] = true;
     return ICP_OK;
 }
 
 int icp_batch_get_covariances(icp_batch* b, double* moving_cov_out, double* model_cov_out)
 {
-    if (int rc = ready(b)) return rc;
-    double* const out[2] = {moving_cov_out, model_cov_out};
-    if (!out[0] && !out[1]) return fail(ICP_ERR_INVALID, "output pointer == NULL");
-    for (int side = 0; side < 2; ++side)
-        if (out[side] && !b->have_cov[side]) return fail(ICP_ERR_STATE, std::string("the batch holds no covariances of the ") + (side ? "models" : "moving clouds"));
-    return download_planes<double, 6>(b, b->cov[0].p, b->cov[1].p, out[0], out[1]);
+    void* const out[2] = {moving_cov_out, model_cov_out};
+    return attr_get(b, b->cov, out, "");
 }
 
 int icp_batch_set_intensities(icp_batch* b, const double* moving_I, const double* model_I)
 {
     if (int rc = ready(b)) return rc;
-    const double* given[2] = {moving_I, model_I};
+    const void* const given[2] = {moving_I, model_I};
     if (!given[0] && !given[1]) return fail(ICP_ERR_INVALID, "moving_I == NULL and model_I == NULL");
-    for (int side = 0; side < 2; ++side) {
-        if (!given[side]) continue;
-        const int64_t* off = side ? b->qoff.data() : b->moff.data();
-        for (int p = 0; p < b->count; ++p)
-            for (int64_t i = off[p]; i < off[p + 1]; ++i)
-                if (!std::isfinite(given[side][i]))
-                    return fail(ICP_ERR_INVALID, "an intensity has a NaN or an infinite value" + where(p, side));
-    }
-    // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
-    for (int side = 0; side < 2; ++side)
-        if (given[side]) HIP_TRY(b->inten[side].ensure(plane_elems(b, side) * sizeof(double)));
+    if (int rc = attr_reserve(b, b->inten, given, "an intensity")) return rc;
     b->begun = false;   // a loop under way is discarded: its passes so far used other intensities (or none)
-    if (given[1]) b->have_grad = false;   // (gradients belong to the model intensities they were made from)
-    std::vector<char> h[2];
-    for (int side = 0; side < 2; ++side) {
-        if (!given[side]) continue;
-        b->have_int[side] = false;
-        to_planes<double, 1>(given[side], ::side(b, side != 0), h[side]);
-        HIP_TRY(hipMemcpyAsync(b->inten[side].p, h[side].data(), h[side].size(), hipMemcpyHostToDevice, b->ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
-    for (int side = 0; side < 2; ++side)
-        if (given[side]) b->have_int[side] = true;
-    return ICP_OK;
+    if (given[1]) b->grad.have[1] = false;   // (gradients belong to the model intensities they were made from)
+    return attr_commit(b, b->inten, given);
 }
 
 int icp_batch_estimate_intensity_gradients(icp_batch* b, const int* k_model, double* grad_out)
 {
     if (int rc = ready(b)) return rc;
     if (!k_model) return fail(ICP_ERR_INVALID, "k_model == NULL");
-    if (!b->have_int[1]) return fail(ICP_ERR_STATE, "intensity gradients need the intensities of the models: icp_batch_set_intensities first");
-    if (!b->have_normals) return fail(ICP_ERR_STATE, "intensity gradients need the model normals: icp_batch_set_model_normals or icp_batch_estimate_normals first");
+    if (!b->inten.have[1]) return fail(ICP_ERR_STATE, "intensity gradients need the intensities of the models: icp_batch_set_intensities first");
+    if (!b->N.have[1]) return fail(ICP_ERR_STATE, "intensity gradients need the model normals: icp_batch_set_model_normals or icp_batch_estimate_normals first");
     static_assert(icp::COV_MAX_K == ICP_COV_MAX_NEIGHBOURS, "the kernel's list holds the largest k");
     int cap = 8;
-    for (int p = 0; p < b->count; ++p) {
-        const int kk = k_model[p];
-        if (kk < ICP_COV_MIN_NEIGHBOURS || kk > ICP_COV_MAX_NEIGHBOURS)
-            return fail(ICP_ERR_INVALID, "the neighbours (k) of an intensity gradient must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]: pair " + std::to_string(p));
-        if (b->pairs[p].m < kk + 1)
-            return fail(ICP_ERR_INVALID, "intensity gradients from k neighbours need a model of at least k + 1 points: pair " + std::to_string(p));
-        cap = std::max(cap, list_cap(kk));
-    }
+    for (int p = 0; p < b->count; ++p)
+        if (int rc = check_k(k_model[p], b->pairs[p].m, "an intensity gradient", "intensity gradients", where(p, 1), cap)) return rc;
     icp_ctx* c = b->ctx;
     hipStream_t st = c->stream;
     ScopedPin pin(c);
     // every model's k travels through one pinned host buffer of the batch's, so that nothing has to outlive the call on the stack:
     // it returns without a host wait unless the output is wanted.  The allocations come before the batch changes
     if (int rc = ensure_model_items(b)) return rc;   // (waits once, the first time a batch needs its models' work items)
-    if (b->grad_ev) HIP_TRY(hipEventSynchronize(b->grad_ev));   // (the call before has long read the host buffer: no wait in practice)
-    else HIP_TRY(hipEventCreateWithFlags(&b->grad_ev, hipEventDisableTiming));
-    if (!b->h_grad_k) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_grad_k), (size_t)b->count * sizeof(int), hipHostMallocDefault));
-    HIP_TRY(b->grad_k.ensure((size_t)b->count * sizeof(int)));
-    HIP_TRY(b->grad.ensure(3 * (size_t)b->q_plane * sizeof(double)));
+    const size_t k_bytes = (size_t)b->count * sizeof(int);
+    HIP_TRY(b->grad_k.wait());   // (the call before has long read the host buffer: no wait in practice)
+    HIP_TRY(b->grad_k.ensure(k_bytes));
+    if (int rc = attr_room(b, b->grad, 1)) return rc;
     b->begun = false;   // a loop under way is discarded
-    b->have_grad = false;
-    std::memcpy(b->h_grad_k, k_model, (size_t)b->count * sizeof(int));
-    HIP_TRY(hipMemcpyAsync(b->grad_k.p, b->h_grad_k, (size_t)b->count * sizeof(int), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(b->grad.p, 0, 3 * (size_t)b->q_plane * sizeof(double), st));   // (the padding between the models: never read, never random)
+    b->grad.have[1] = false;
+    std::memcpy(b->grad_k.host.p, k_model, k_bytes);
+    HIP_TRY(b->grad_k.copy(k_bytes, st));
+    HIP_TRY(hipMemsetAsync(b->grad.buf[1].p, 0, attr_bytes(b, b->grad, 1), st));   // (the padding between the models: never read, never random)
     icp::BatchGradArgs a{};
     a.precision = b->prec;
     a.cap = cap;
     a.items = (const icp::BatchItem*)b->q_items.p;
     a.n_items = b->n_q_items;
     a.pairs = (const icp::BatchPair*)b->pairs_d.p;
-    a.k = (const int*)b->grad_k.p;
+    a.k = (const int*)b->grad_k.dev.p;
     a.Q_soa = b->Q.p;
-    a.N_soa = b->N.p;
+    a.N_soa = b->N.buf[1].p;
     a.q_plane = b->q_plane;
-    a.int_q = (const double*)b->inten[1].p;
-    a.grad = (double*)b->grad.p;
+    a.int_q = (const double*)b->inten.buf[1].p;
+    a.grad = (double*)b->grad.buf[1].p;
     HIP_TRY(icp::launch_batch_intensity_gradients(a, st));
-    HIP_TRY(hipEventRecord(b->grad_ev, st));
+    HIP_TRY(b->grad_k.record(st));
+    void* const out[2] = {nullptr, grad_out};
     if (grad_out)
-        if (int rc = download_planes<double, 3>(b, nullptr, b->grad.p, nullptr, grad_out)) return rc;   // (the one wait of a call that wants the output)
-    b->have_grad = true;
+        if (int rc = fetch(b, b->grad, out)) return rc;   // (the one wait of a call that wants the output)
+    b->grad.have[1] = true;
     return ICP_OK;
 }
 
@@ -1881,26 +1858,16 @@ int icp_batch_set_intensity_gradients(icp_batch* b, const double* grad)
 {
     if (int rc = ready(b)) return rc;
     if (!grad) return fail(ICP_ERR_INVALID, "grad == NULL");
-    for (int p = 0; p < b->count; ++p)
-        for (int64_t i = 3 * b->qoff[p]; i < 3 * b->qoff[p + 1]; ++i)
-            if (!std::isfinite(grad[i])) return fail(ICP_ERR_INVALID, "an intensity gradient has a NaN or an infinite value" + where(p, 1));
-    HIP_TRY(b->grad.ensure(3 * (size_t)b->q_plane * sizeof(double)));
+    const void* const given[2] = {nullptr, grad};
+    if (int rc = attr_reserve(b, b->grad, given, "an intensity gradient")) return rc;
     b->begun = false;   // a loop under way is discarded
-    b->have_grad = false;
-    std::vector<char> h;
-    to_planes<double, 3>(grad, ::side(b, true), h);
-    HIP_TRY(hipMemcpyAsync(b->grad.p, h.data(), h.size(), hipMemcpyHostToDevice, b->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vector goes)
-    b->have_grad = true;
-    return ICP_OK;
+    return attr_commit(b, b->grad, given);
 }
 
 int icp_batch_get_intensity_gradients(icp_batch* b, double* grad_out)
 {
-    if (int rc = ready(b)) return rc;
-    if (!grad_out) return fail(ICP_ERR_INVALID, "output pointer == NULL");
-    if (!b->have_grad) return fail(ICP_ERR_STATE, "the batch holds no intensity gradients");
-    return download_planes<double, 3>(b, nullptr, b->grad.p, nullptr, grad_out);
+    void* const out[2] = {nullptr, grad_out};
+    return attr_get(b, b->grad, out, "");
 }
 
 int icp_batch_set_color_weight(icp_batch* b, const double* lambda)
@@ -1988,26 +1955,6 @@ extern "C++" {
 namespace {
 
 constexpr int kRansacChunk = 4096;   // hypotheses per pair and scoring launch of icp_batch_ransac
-
-// downloads the descriptors of the sides whose output pointer is given (one wait) and lays them out as the caller's
-int download_features(icp_batch* b, double* const out[2])
-{
-    std::vector<double> h[2];
-    for (int sd = 0; sd < 2; ++sd)
-        if (out[sd]) {
-            h[sd].resize(ICP_FEATURE_BINS * plane_elems(b, sd));
-            HIP_TRY(hipMemcpyAsync(h[sd].data(), b->feat[sd].p, h[sd].size() * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
-        }
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    for (int sd = 0; sd < 2; ++sd) {
-        if (!out[sd]) continue;
-        const Side s = ::side(b, sd != 0);
-        for (size_t p = 0; p < s.dst.size(); ++p)
-            std::memcpy(out[sd] + ICP_FEATURE_BINS * s.off[p], h[sd].data() + ICP_FEATURE_BINS * (size_t)s.dst[p],
-                        ICP_FEATURE_BINS * (size_t)(s.off[p + 1] - s.off[p]) * sizeof(double));
-    }
-    return ICP_OK;
-}
 
 // the candidates of one scoring launch (count x per_pair, 12 values of the batch's precision each; valid: count x per_pair bytes or
 // NULL) against the batch's correspondence lists: upload, one launch, download of the counts (one wait)
@@ -2170,10 +2117,9 @@ int compute_features(icp_batch* b, bool stored, const int* k_moving, const int* 
     const double* nrm_given[2] = {moving_normals, model_normals};
     for (int sd = 0; sd < 2; ++sd) {
         if (!ks_given[sd]) return fail(ICP_ERR_INVALID, std::string("descriptors need a k for both sides: ") + (sd ? "k_model" : "k_moving") + " == NULL");
+        const bool asked[2] = {sd == 0, sd == 1};
         if (stored) {
-            if (!b->have_pnrm[sd])
-                return fail(ICP_ERR_STATE, std::string("the batch holds no point normals of the ") + (sd ? "models" : "moving clouds") +
-                                               " (icp_batch_estimate_point_normals or icp_batch_set_point_normals first)");
+            if (int rc = attr_held(b->pnrm, asked, kPointNormalsFirst)) return rc;
         } else if (!nrm_given[sd])
             return fail(ICP_ERR_INVALID, std::string("descriptors need normals on both sides: ") + (sd ? "model_normals" : "moving_normals") + " == NULL");
     }
@@ -2182,16 +2128,11 @@ int compute_features(icp_batch* b, bool stored, const int* k_moving, const int* 
     int cap = 8;
     for (int sd = 0; sd < 2; ++sd)
         for (int p = 0; p < count; ++p) {
-            const int kk = ks_given[sd][p];
-            if (kk < ICP_COV_MIN_NEIGHBOURS || kk > ICP_COV_MAX_NEIGHBOURS)
-                return fail(ICP_ERR_INVALID, "the neighbours (k) of a descriptor must lie in [ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS]" + where(p, sd));
-            if ((sd ? b->pairs[p].m : b->pairs[p].n) < kk + 1)
-                return fail(ICP_ERR_INVALID, "descriptors from k neighbours need a cloud of at least k + 1 points" + where(p, sd));
+            if (int rc = check_k(ks_given[sd][p], sd ? b->pairs[p].m : b->pairs[p].n, "a descriptor", "descriptors", where(p, sd), cap)) return rc;
             const int64_t* off = sd ? b->qoff.data() : b->moff.data();
             for (int64_t i = 3 * off[p]; !stored && i < 3 * off[p + 1]; ++i)
                 if (!std::isfinite(nrm_given[sd][i])) return fail(ICP_ERR_INVALID, "a normal has a NaN or an infinite value" + where(p, sd));
-            ks[(size_t)sd * count + p] = kk;
-            cap = std::max(cap, list_cap(kk));
+            ks[(size_t)sd * count + p] = ks_given[sd][p];
         }
     const bool both[2] = {true, true};
     icp::CloudList cl;
@@ -2212,17 +2153,17 @@ int compute_features(icp_batch* b, bool stored, const int* k_moving, const int* 
         if (!stored) HIP_TRY(tmp.buf[NRM + sd].ensure(3 * plane * sizeof(double)));
         HIP_TRY(tmp.buf[TAU + sd].ensure(plane * b->esize));
         HIP_TRY(tmp.buf[SPFH + sd].ensure(ICP_FEATURE_BINS * plane * sizeof(double)));
-        HIP_TRY(b->feat[sd].ensure(ICP_FEATURE_BINS * plane * sizeof(double)));
-        if (!stored) to_planes<double, 3>(nrm_given[sd], ::side(b, sd != 0), hn[sd]);
+        HIP_TRY(b->feat.buf[sd].ensure(ICP_FEATURE_BINS * plane * sizeof(double)));
+        if (!stored) icp::encode(b->pnrm.fmt, side(b, sd != 0), nrm_given[sd], hn[sd]);
     }
-    b->have_feat[0] = b->have_feat[1] = false;
+    b->feat.have[0] = b->feat.have[1] = false;
     b->have_match = false;   // (matches of other descriptors)
     HIP_TRY(hipMemcpyAsync(tmp.buf[ARGS].p, hs.data(), lay.bytes, hipMemcpyHostToDevice, st));
     for (int sd = 0; sd < 2; ++sd) {
         const size_t plane = plane_elems(b, sd);
         if (!stored) HIP_TRY(hipMemcpyAsync(tmp.buf[NRM + sd].p, hn[sd].data(), hn[sd].size(), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(tmp.buf[SPFH + sd].p, 0, ICP_FEATURE_BINS * plane * sizeof(double), st));   // (the padding between the clouds: never read, never random)
-        HIP_TRY(hipMemsetAsync(b->feat[sd].p, 0, ICP_FEATURE_BINS * plane * sizeof(double), st));
+        HIP_TRY(hipMemsetAsync(b->feat.buf[sd].p, 0, ICP_FEATURE_BINS * plane * sizeof(double), st));
         HIP_TRY(hipMemsetAsync(tmp.buf[TAU + sd].p, 0, plane * b->esize, st));
     }
     const char* ds = static_cast<const char*>(tmp.buf[ARGS].p);
@@ -2238,28 +2179,18 @@ int compute_features(icp_batch* b, bool stored, const int* k_moving, const int* 
     a.src_plane[0] = b->p_plane;
     a.src_plane[1] = b->q_plane;
     for (int sd = 0; sd < 2; ++sd) {
-        a.nrm[sd] = (const double*)(stored ? b->pnrm[sd].p : tmp.buf[NRM + sd].p);
+        a.nrm[sd] = (const double*)(stored ? b->pnrm.buf[sd].p : tmp.buf[NRM + sd].p);
         a.tau[sd] = tmp.buf[TAU + sd].p;
         a.spfh[sd] = (double*)tmp.buf[SPFH + sd].p;
-        a.feat[sd] = (double*)b->feat[sd].p;
+        a.feat[sd] = (double*)b->feat.buf[sd].p;
     }
     const hipError_t le = icp::launch_batch_features(a, st);
     const hipError_t se = hipStreamSynchronize(st);   // (the one wait: the temporaries and the host vectors go with the call)
     HIP_TRY(le);
     HIP_TRY(se);
-    b->have_feat[0] = b->have_feat[1] = true;
-    double* const out[2] = {moving_feat_out, model_feat_out};
-    if (out[0] || out[1]) return download_features(b, out);
-    return ICP_OK;
-}
-
-// room for the point normals of one side; new room is zeroed, so that the padding between the clouds is never random
-int ensure_point_normals(icp_batch* b, int sd)
-{
-    const size_t bytes = 3 * plane_elems(b, sd) * sizeof(double);
-    if (b->pnrm[sd].p && bytes <= b->pnrm[sd].cap) return ICP_OK;
-    HIP_TRY(b->pnrm[sd].ensure(bytes));
-    HIP_TRY(hipMemsetAsync(b->pnrm[sd].p, 0, bytes, b->ctx->stream));
+    b->feat.have[0] = b->feat.have[1] = true;
+    void* const out[2] = {moving_feat_out, model_feat_out};
+    if (out[0] || out[1]) return fetch(b, b->feat, out);
     return ICP_OK;
 }
 
@@ -2273,15 +2204,14 @@ int ensure_normals_args(icp_batch* b)
     if (!icp::list_clouds(b->pairs, both, cl)) return fail(ICP_ERR_INVALID, "too many work items for one batch");
     const icp::ArgsLayout lay = icp::lay_out_args(cl.clouds.size(), cl.items.size(), 0);
     const size_t view_bytes = cl.clouds.size() * 3 * sizeof(double);
-    if (!b->nrm_ev) HIP_TRY(hipEventCreateWithFlags(&b->nrm_ev, hipEventDisableTiming));
-    if (!b->h_nrm_view) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_nrm_view), view_bytes, hipHostMallocDefault));
-    if (!b->h_nrm_args) HIP_TRY(hipHostMalloc(&b->h_nrm_args, lay.bytes, hipHostMallocDefault));
+    HIP_TRY(b->nrm_view.wait());   // (makes the event)
+    HIP_TRY(b->nrm_view.host.ensure(view_bytes));
     HIP_TRY(b->nrm_args.ensure(lay.bytes));
-    HIP_TRY(b->nrm_view.ensure(view_bytes));
+    HIP_TRY(b->nrm_view.dev.ensure(view_bytes));
     HIP_TRY(b->nrm_cent.ensure(view_bytes));
-    std::memset(b->h_nrm_args, 0, lay.bytes);
-    pack_args(b->h_nrm_args, lay, cl, nullptr);
-    HIP_TRY(hipMemcpyAsync(b->nrm_args.p, b->h_nrm_args, lay.bytes, hipMemcpyHostToDevice, b->ctx->stream));   // (from a pinned buffer the batch keeps: no wait)
+    std::memset(b->nrm_args.host.p, 0, lay.bytes);
+    pack_args(b->nrm_args.host.p, lay, cl, nullptr);
+    HIP_TRY(b->nrm_args.copy(lay.bytes, b->ctx->stream));   // (from a pinned buffer the batch keeps: no wait)
     b->nrm_off_items = lay.off_items;
     b->n_nrm_items = (int)cl.items.size();
     return ICP_OK;
@@ -2307,7 +2237,7 @@ int icp_batch_estimate_point_normals(icp_batch* b, int orient, const double* mov
     if (orient != ICP_ORIENT_NONE && orient != ICP_ORIENT_VIEWPOINT && orient != ICP_ORIENT_CENTROID)
         return fail(ICP_ERR_INVALID, "unknown orientation of the point normals");
     for (int sd = 0; sd < 2; ++sd)
-        if (!b->have_cov[sd])
+        if (!b->cov.have[sd])
             return fail(ICP_ERR_STATE, std::string("point normals need the covariances of both sides: the batch holds none of the ") + (sd ? "models" : "moving clouds") +
                                            " (icp_batch_set_covariances or icp_batch_estimate_covariances first)");
     const double* views[2] = {moving_viewpoints, model_viewpoints};
@@ -2327,14 +2257,14 @@ int icp_batch_estimate_point_normals(icp_batch* b, int orient, const double* mov
     // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
     if (int rc = ensure_normals_args(b)) return rc;
     for (int sd = 0; sd < 2; ++sd)
-        if (int rc = ensure_point_normals(b, sd)) return rc;
+        if (int rc = attr_room(b, b->pnrm, sd)) return rc;
     if (orient == ICP_ORIENT_VIEWPOINT) {
-        HIP_TRY(hipEventSynchronize(b->nrm_ev));   // (the call before has long read the host buffer: no wait in practice; a new event is complete)
-        for (int sd = 0; sd < 2; ++sd) std::memcpy(b->h_nrm_view + (size_t)sd * count * 3, views[sd], (size_t)count * 3 * sizeof(double));
-        HIP_TRY(hipMemcpyAsync(b->nrm_view.p, b->h_nrm_view, (size_t)n_clouds * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(b->nrm_ev, st));
+        HIP_TRY(b->nrm_view.wait());   // (the call before has long read the host buffer: no wait in practice; a new event is complete)
+        for (int sd = 0; sd < 2; ++sd) std::memcpy(b->nrm_view.host.as<double>() + (size_t)sd * count * 3, views[sd], (size_t)count * 3 * sizeof(double));
+        HIP_TRY(b->nrm_view.copy((size_t)n_clouds * 3 * sizeof(double), st));
+        HIP_TRY(b->nrm_view.record(st));
     }
-    const char* ds = static_cast<const char*>(b->nrm_args.p);
+    const char* ds = static_cast<const char*>(b->nrm_args.dev.p);
     icp::BatchNormalsArgs a{};
     a.precision = b->prec;
     a.orient = orient;
@@ -2347,58 +2277,32 @@ int icp_batch_estimate_point_normals(icp_batch* b, int orient, const double* mov
     a.src_plane[0] = b->p_plane;
     a.src_plane[1] = b->q_plane;
     a.cent = (double*)b->nrm_cent.p;
-    a.view = orient == ICP_ORIENT_CENTROID ? (const double*)b->nrm_cent.p : orient == ICP_ORIENT_VIEWPOINT ? (const double*)b->nrm_view.p : nullptr;
+    a.view = orient == ICP_ORIENT_CENTROID ? (const double*)b->nrm_cent.p : orient == ICP_ORIENT_VIEWPOINT ? (const double*)b->nrm_view.dev.p : nullptr;
     for (int sd = 0; sd < 2; ++sd) {
-        a.cov[sd] = (const double*)b->cov[sd].p;
-        a.nrm[sd] = (double*)b->pnrm[sd].p;
+        a.cov[sd] = (const double*)b->cov.buf[sd].p;
+        a.nrm[sd] = (double*)b->pnrm.buf[sd].p;
     }
     HIP_TRY(icp::launch_batch_point_normals(a, st));
-    b->have_pnrm[0] = b->have_pnrm[1] = true;
+    b->pnrm.have[0] = b->pnrm.have[1] = true;
     if (orient == ICP_ORIENT_CENTROID) b->have_cent = true;
-    double* const out[2] = {moving_normals_out, model_normals_out};
-    if (out[0] || out[1]) return download_planes<double, 3>(b, b->pnrm[0].p, b->pnrm[1].p, out[0], out[1]);   // (the one wait of a call that wants an output)
+    void* const out[2] = {moving_normals_out, model_normals_out};
+    if (out[0] || out[1]) return fetch(b, b->pnrm, out);   // (the one wait of a call that wants an output)
     return ICP_OK;
 }
 
 int icp_batch_set_point_normals(icp_batch* b, const double* moving_normals, const double* model_normals)
 {
     if (int rc = ready(b)) return rc;
-    const double* given[2] = {moving_normals, model_normals};
+    const void* const given[2] = {moving_normals, model_normals};
     if (!given[0] && !given[1]) return fail(ICP_ERR_INVALID, "moving_normals == NULL and model_normals == NULL");
-    for (int sd = 0; sd < 2; ++sd) {
-        if (!given[sd]) continue;
-        const int64_t* off = sd ? b->qoff.data() : b->moff.data();
-        for (int p = 0; p < b->count; ++p)
-            for (int64_t i = 3 * off[p]; i < 3 * off[p + 1]; ++i)
-                if (!std::isfinite(given[sd][i])) return fail(ICP_ERR_INVALID, "a normal has a NaN or an infinite value" + where(p, sd));
-    }
-    // the allocations come before the batch changes: a call refused for want of memory leaves it as it was
-    for (int sd = 0; sd < 2; ++sd)
-        if (given[sd])
-            if (int rc = ensure_point_normals(b, sd)) return rc;
-    std::vector<char> h[2];
-    for (int sd = 0; sd < 2; ++sd) {
-        if (!given[sd]) continue;
-        b->have_pnrm[sd] = false;
-        to_planes<double, 3>(given[sd], ::side(b, sd != 0), h[sd]);
-        HIP_TRY(hipMemcpyAsync(b->pnrm[sd].p, h[sd].data(), h[sd].size(), hipMemcpyHostToDevice, b->ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
-    for (int sd = 0; sd < 2; ++sd)
-        if (given[sd]) b->have_pnrm[sd] = true;
-    return ICP_OK;
+    if (int rc = attr_reserve(b, b->pnrm, given, "a normal")) return rc;
+    return attr_commit(b, b->pnrm, given);   // (the loop does not read them: one under way goes on)
 }
 
 int icp_batch_get_point_normals(icp_batch* b, double* moving_normals_out, double* model_normals_out)
 {
-    if (int rc = ready(b)) return rc;
-    double* const out[2] = {moving_normals_out, model_normals_out};
-    if (!out[0] && !out[1]) return fail(ICP_ERR_INVALID, "output pointer == NULL");
-    for (int sd = 0; sd < 2; ++sd)
-        if (out[sd] && !b->have_pnrm[sd])
-            return fail(ICP_ERR_STATE, std::string("the batch holds no point normals of the ") + (sd ? "models" : "moving clouds") +
-                                           " (icp_batch_estimate_point_normals or icp_batch_set_point_normals first)");
-    return download_planes<double, 3>(b, b->pnrm[0].p, b->pnrm[1].p, out[0], out[1]);
+    void* const out[2] = {moving_normals_out, model_normals_out};
+    return attr_get(b, b->pnrm, out, kPointNormalsFirst);
 }
 
 int icp_diag_batch_centroids(icp_batch* b, double* out)
@@ -2413,41 +2317,24 @@ int icp_diag_batch_centroids(icp_batch* b, double* out)
 
 int icp_batch_get_features(icp_batch* b, double* moving_feat_out, double* model_feat_out)
 {
-    if (int rc = ready(b)) return rc;
-    double* const out[2] = {moving_feat_out, model_feat_out};
-    if (!out[0] && !out[1]) return fail(ICP_ERR_INVALID, "output pointer == NULL");
-    for (int sd = 0; sd < 2; ++sd)
-        if (out[sd] && !b->have_feat[sd]) return fail(ICP_ERR_STATE, std::string("the batch holds no descriptors of the ") + (sd ? "models" : "moving clouds") + " (icp_batch_compute_features first)");
-    return download_features(b, out);
+    void* const out[2] = {moving_feat_out, model_feat_out};
+    return attr_get(b, b->feat, out, " (icp_batch_compute_features first)");
 }
 
 int icp_diag_batch_set_features(icp_batch* b, const double* moving_feat, const double* model_feat)
 {
     if (int rc = ready(b)) return rc;
-    const double* given[2] = {moving_feat, model_feat};
+    const void* const given[2] = {moving_feat, model_feat};
     if (!given[0] || !given[1]) return fail(ICP_ERR_INVALID, "moving_feat == NULL or model_feat == NULL");
-    std::vector<double> h[2];
-    for (int sd = 0; sd < 2; ++sd) {
-        const Side s = ::side(b, sd != 0);
-        HIP_TRY(b->feat[sd].ensure(ICP_FEATURE_BINS * (size_t)s.plane * sizeof(double)));
-        h[sd].assign(ICP_FEATURE_BINS * (size_t)s.plane, 0.0);
-        for (size_t p = 0; p < s.dst.size(); ++p)
-            std::memcpy(h[sd].data() + ICP_FEATURE_BINS * (size_t)s.dst[p], given[sd] + ICP_FEATURE_BINS * s.off[p],
-                        ICP_FEATURE_BINS * (size_t)(s.off[p + 1] - s.off[p]) * sizeof(double));
-    }
-    b->have_feat[0] = b->have_feat[1] = false;
-    b->have_match = false;
-    for (int sd = 0; sd < 2; ++sd)
-        HIP_TRY(hipMemcpyAsync(b->feat[sd].p, h[sd].data(), h[sd].size() * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // (before the host vectors go)
-    b->have_feat[0] = b->have_feat[1] = true;
-    return ICP_OK;
+    if (int rc = attr_reserve(b, b->feat, given, nullptr)) return rc;   // (a diagnostic: nothing is scanned)
+    b->have_match = false;   // (matches of other descriptors)
+    return attr_commit(b, b->feat, given);
 }
 
 int icp_batch_match_features(icp_batch* b, int mutual, int32_t* fwd_out, int32_t* rev_out, uint8_t* kept_out)
 {
     if (int rc = ready(b)) return rc;
-    if (!b->have_feat[0] || !b->have_feat[1]) return fail(ICP_ERR_STATE, "the batch holds no descriptors (icp_batch_compute_features first)");
+    if (!b->feat.have[0] || !b->feat.have[1]) return fail(ICP_ERR_STATE, "the batch holds no descriptors (icp_batch_compute_features first)");
     icp_ctx* c = b->ctx;
     ScopedPin pin(c);
     if (int rc = ensure_model_items(b)) return rc;
@@ -2466,8 +2353,8 @@ int icp_batch_match_features(icp_batch* b, int mutual, int32_t* fwd_out, int32_t
     a.n_items[0] = b->n_items;
     a.n_items[1] = b->n_q_items;
     a.pairs = (const icp::BatchPair*)b->pairs_d.p;
-    a.feat[0] = (const double*)b->feat[0].p;
-    a.feat[1] = (const double*)b->feat[1].p;
+    a.feat[0] = (const double*)b->feat.buf[0].p;
+    a.feat[1] = (const double*)b->feat.buf[1].p;
     a.fwd = (int32_t*)b->f_fwd.p;
     a.rev = (int32_t*)b->f_rev.p;
     HIP_TRY(icp::launch_batch_feature_match(a, c->stream));
@@ -2779,7 +2666,7 @@ int icp_batch_fgr(icp_batch* b, const icp_fgr_params* prm, const uint64_t* seed,
     double sec[4] = {0.0, 0.0, 0.0, 0.0};
     if (n_items > 0) {
         const size_t ctl_bytes = (size_t)count * icp::FGR_CTL * sizeof(double), mom_bytes = (size_t)count * ICP_NMOM * sizeof(double);
-        if (!b->h_fgr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_fgr), ctl_bytes + mom_bytes, hipHostMallocDefault));
+        HIP_TRY(b->h_fgr.ensure(ctl_bytes + mom_bytes));
         HIP_TRY(b->g_ui.ensure((size_t)b->p_plane * sizeof(int32_t)));
         HIP_TRY(b->g_uj.ensure((size_t)b->p_plane * sizeof(int32_t)));
         HIP_TRY(b->g_items.ensure((size_t)n_items * sizeof(icp::BatchItem)));
@@ -2811,8 +2698,8 @@ int icp_batch_fgr(icp_batch* b, const icp_fgr_params* prm, const uint64_t* seed,
         a.partials = (double*)b->g_partials.p;
         a.mom = (double*)b->g_mom.p;
         a.weights = (double*)b->g_w.p;
-        double* ctl = b->h_fgr;
-        double* mom = b->h_fgr + (size_t)count * icp::FGR_CTL;
+        double* ctl = b->h_fgr.as<double>();
+        double* mom = ctl + (size_t)count * icp::FGR_CTL;
         std::vector<char> run((size_t)count, 0);   // the pair is still iterating
         int n_run = 0;
         for (int p = 0; p < count; ++p) n_run += (run[p] = status[p] == ICP_OK ? 1 : 0);

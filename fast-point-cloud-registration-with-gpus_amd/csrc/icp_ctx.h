@@ -34,9 +34,26 @@ constexpr int kMailSlots = 4;  // armed launches: ring of mailboxes (one is live
 constexpr size_t kMailSlotBytes = sizeof(icp::NNMailbox64);   // a slot holds a float message (one line) or a double one (two)
 inline icp::NNMailbox* mail_slot(icp::NNMailbox* base, int slot) { return reinterpret_cast<icp::NNMailbox*>(reinterpret_cast<char*>(base) + (size_t)slot * kMailSlotBytes); }
 
+// device memory, pinned host memory and an event that go with whatever holds them: none can be copied, all free in their destructor
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }   // (moved, not copied: the loop swaps its ping-pong clouds)
+    DevBuf& operator=(DevBuf&& o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p;
+            cap = o.cap;
+            o.p = nullptr;
+            o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
@@ -52,6 +69,53 @@ struct DevBuf {
         p = nullptr;
         cap = 0;
     }
+};
+
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t ensure(size_t bytes)   // (what it held is not kept)
+    {
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() { if (ev) (void)hipEventDestroy(ev); }
+    // what was recorded last has ended; the first use makes the event (a new one is complete)
+    hipError_t wait() { return ev ? hipEventSynchronize(ev) : hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+    hipError_t record(hipStream_t st) { return hipEventRecord(ev, st); }
+};
+
+// arguments of a launch that travel through a pinned buffer their owner keeps, so that nothing has to outlive the call on the
+// stack and the call waits for nothing: wait (the copy before has read the pinned side), ensure, fill host, copy, record
+struct Staged {
+    DevBuf dev;
+    PinnedBuf host;
+    Event ev;
+    hipError_t wait() { return ev.wait(); }
+    hipError_t ensure(size_t bytes)
+    {
+        hipError_t e = host.ensure(bytes);
+        return e == hipSuccess ? dev.ensure(bytes) : e;
+    }
+    hipError_t copy(size_t bytes, hipStream_t st) { return hipMemcpyAsync(dev.p, host.p, bytes, hipMemcpyHostToDevice, st); }
+    hipError_t record(hipStream_t st) { return ev.record(st); }
 };
 
 struct LoopState {

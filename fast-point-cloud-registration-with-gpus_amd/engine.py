@@ -700,6 +700,11 @@ def _batch_arrays(pairs):
     return Ds, Ms, moff, qoff, dtype
 
 
+def _ptr(a, ctype=C.c_double):
+    """an optional array -> a pointer to its first element, or None (NULL)"""
+    return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
+
+
 def _batch_normals(normals, Ms, dtype):
     """one (m, 3) array of normals per pair -> their concatenation in the models' layout"""
     normals = list(normals)
@@ -780,7 +785,7 @@ class Batch:
         out = Batch._from_handle(self._ctx, h, self.count, self._dtype)
         if not want_maps:
             return out
-        return out, self._split(mm), [qm[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
+        return out, self._split(mm), self._cut(qm, self._qoff)
 
     def _outlier_rules(self, rules, what):
         """one rule or one per pair -> a ctypes array of count icp_outlier_rule (None: NULL, copy that side)"""
@@ -826,7 +831,7 @@ class Batch:
                                                        C.byref(h)), "icp_batch_remove_outliers")
         out = Batch._from_handle(self._ctx, h, self.count, self._dtype)
         info = {"stats": stats}
-        per_model = lambda a: [a[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
+        per_model = lambda a: self._cut(a, self._qoff)
         per_moving = lambda a: [a[self._moff[b]:self._moff[b + 1]].copy() for b in range(self.count)]
         if want_maps:
             info["moving_map"], info["model_map"] = per_moving(mm), per_model(qm)
@@ -886,7 +891,7 @@ class Batch:
                                                         C.byref(h)), "icp_batch_select_keypoints")
         out = Batch._from_handle(self._ctx, h, self.count, self._dtype)
         info = {"counts": counts}
-        per_model = lambda a: [a[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
+        per_model = lambda a: self._cut(a, self._qoff)
         per_moving = lambda a: [a[self._moff[b]:self._moff[b + 1]].copy() for b in range(self.count)]
         if want_maps:
             info["moving_map"], info["model_map"] = per_moving(mm), per_model(qm)
@@ -919,7 +924,7 @@ class Batch:
         self.close()
 
     def _split(self, flat):
-        return [flat[self._moff[b]:self._moff[b + 1]].copy() for b in range(self.count)]
+        return self._cut(flat, self._moff)
 
     def set_model_normals(self, normals):
         """the unit normals of every pair's model points (one (m, 3) array per pair): what a point-to-plane begin needs"""
@@ -939,24 +944,25 @@ class Batch:
         total = int(self._qoff[-1])
         nrm = np.empty((total, 3), dtype=self._dtype)
         nbr = np.empty((total, 4), dtype=np.int32) if want_neighbours else None
-        capi.check(self._lib.icp_batch_estimate_normals(self._h, nrm.ctypes.data, nbr.ctypes.data_as(C.POINTER(C.c_int32)) if want_neighbours else None),
+        capi.check(self._lib.icp_batch_estimate_normals(self._h, nrm.ctypes.data, _ptr(nbr, C.c_int32)),
                    "icp_batch_estimate_normals")
-        cut = lambda a: [a[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
-        return (cut(nrm), cut(nbr)) if want_neighbours else cut(nrm)
+        return (self._cut(nrm, self._qoff), self._cut(nbr, self._qoff)) if want_neighbours else self._cut(nrm, self._qoff)
 
-    def _cov_side(self, covs, off, what):
-        """one (n, 6) float64 array per pair -> their concatenation in that side's layout (None: NULL)"""
-        if covs is None:
+    def _side(self, arrays, off, width, what):
+        """one float64 array per pair, (points, width) or (points,) for width None -> their concatenation in that side's layout
+        (None: NULL); what: "moving covariances", "model normals", ..."""
+        if arrays is None:
             return None
-        covs = [np.ascontiguousarray(c, dtype=np.float64) for c in covs]
-        if len(covs) != self.count:
-            raise ValueError(f"one array of {what} covariances per pair")
-        for b, c in enumerate(covs):
-            if c.shape != (int(off[b + 1] - off[b]), 6):
-                raise ValueError(f"a pair's {what} covariances must be (points, 6): xx, xy, xz, yy, yz, zz")
-        return np.ascontiguousarray(np.concatenate(covs))
+        arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in arrays]
+        if len(arrays) != self.count:
+            raise ValueError(f"one array of {what} per pair")
+        for b, a in enumerate(arrays):
+            points = int(off[b + 1] - off[b])
+            if a.shape != ((points,) if width is None else (points, width)):
+                raise ValueError(f"a pair's {what} must be (points,{'' if width is None else ' ' + str(width)})")
+        return np.ascontiguousarray(np.concatenate(arrays))
 
-    def _cut6(self, flat, off):
+    def _cut(self, flat, off):
         return [flat[off[b]:off[b + 1]].copy() for b in range(self.count)]
 
     def set_covariances(self, moving=None, model=None):
@@ -964,10 +970,8 @@ class Batch:
         pair -- xx, xy, xz, yy, yz, zz, symmetric positive semi-definite (the caller's duty; only finiteness is checked) -- or
         None: that side is left as it is.  The moving covariances belong to the clouds as uploaded, in their own frame.  Discards
         a loop under way."""
-        pd = C.POINTER(C.c_double)
-        a, q = self._cov_side(moving, self._moff, "moving"), self._cov_side(model, self._qoff, "model")
-        capi.check(self._lib.icp_batch_set_covariances(self._h, a.ctypes.data_as(pd) if a is not None else None,
-                                                       q.ctypes.data_as(pd) if q is not None else None), "icp_batch_set_covariances")
+        a, q = self._side(moving, self._moff, 6, "moving covariances"), self._side(model, self._qoff, 6, "model covariances")
+        capi.check(self._lib.icp_batch_set_covariances(self._h, _ptr(a), _ptr(q)), "icp_batch_set_covariances")
 
     def _cov_k(self, k, what):
         if k is None:
@@ -992,42 +996,24 @@ class Batch:
             regularisation is None or isinstance(regularisation, str)) else int(regularisation)
         km = self._cov_k(k, "k")
         kq = self._cov_k(k if k_model is None else k_model, "model k")
-        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
         om = np.empty((int(self._moff[-1]), 6)) if want and km is not None else None
         oq = np.empty((int(self._qoff[-1]), 6)) if want and kq is not None else None
-        capi.check(self._lib.icp_batch_estimate_covariances(self._h, km.ctypes.data_as(pi) if km is not None else None,
-                                                            kq.ctypes.data_as(pi) if kq is not None else None, reg, float(lam),
-                                                            om.ctypes.data_as(pd) if om is not None else None,
-                                                            oq.ctypes.data_as(pd) if oq is not None else None), "icp_batch_estimate_covariances")
+        capi.check(self._lib.icp_batch_estimate_covariances(self._h, _ptr(km, C.c_int), _ptr(kq, C.c_int), reg, float(lam), _ptr(om), _ptr(oq)),
+                   "icp_batch_estimate_covariances")
         if want:
-            return (self._cut6(om, self._moff) if om is not None else None, self._cut6(oq, self._qoff) if oq is not None else None)
+            return (self._cut(om, self._moff) if om is not None else None, self._cut(oq, self._qoff) if oq is not None else None)
 
     def get_covariances(self):
         """(moving, model): per pair the (points, 6) float64 covariances the batch holds (icp_batch_get_covariances)"""
-        pd = C.POINTER(C.c_double)
         om, oq = np.empty((int(self._moff[-1]), 6)), np.empty((int(self._qoff[-1]), 6))
-        capi.check(self._lib.icp_batch_get_covariances(self._h, om.ctypes.data_as(pd), oq.ctypes.data_as(pd)), "icp_batch_get_covariances")
-        return self._cut6(om, self._moff), self._cut6(oq, self._qoff)
-
-    def _scalar_side(self, vals, off, what):
-        """one (points,) float64 array per pair -> their concatenation in that side's layout (None: NULL)"""
-        if vals is None:
-            return None
-        vals = [np.ascontiguousarray(v, dtype=np.float64) for v in vals]
-        if len(vals) != self.count:
-            raise ValueError(f"one array of {what} intensities per pair")
-        for b, v in enumerate(vals):
-            if v.shape != (int(off[b + 1] - off[b]),):
-                raise ValueError(f"a pair's {what} intensities must be (points,)")
-        return np.ascontiguousarray(np.concatenate(vals))
+        capi.check(self._lib.icp_batch_get_covariances(self._h, _ptr(om), _ptr(oq)), "icp_batch_get_covariances")
+        return self._cut(om, self._moff), self._cut(oq, self._qoff)
 
     def set_intensities(self, moving=None, model=None):
         """the intensity of every point, what a colored begin needs on both sides: per side one (points,) float64 array per pair,
         or None: that side is left as it is.  New model intensities discard the gradients.  Discards a loop under way."""
-        pd = C.POINTER(C.c_double)
-        a, q = self._scalar_side(moving, self._moff, "moving"), self._scalar_side(model, self._qoff, "model")
-        capi.check(self._lib.icp_batch_set_intensities(self._h, a.ctypes.data_as(pd) if a is not None else None,
-                                                       q.ctypes.data_as(pd) if q is not None else None), "icp_batch_set_intensities")
+        a, q = self._side(moving, self._moff, None, "moving intensities"), self._side(model, self._qoff, None, "model intensities")
+        capi.check(self._lib.icp_batch_set_intensities(self._h, _ptr(a), _ptr(q)), "icp_batch_set_intensities")
 
     def estimate_intensity_gradients(self, k=8, want=False):
         """the intensity gradient of every model point from its k nearest neighbours, on the device in one launch
@@ -1037,28 +1023,20 @@ class Batch:
         the per-pair list of (m, 3) float64 gradients.  Discards a loop under way."""
         kq = self._cov_k(k, "k")
         out = np.empty((int(self._qoff[-1]), 3)) if want else None
-        capi.check(self._lib.icp_batch_estimate_intensity_gradients(self._h, kq.ctypes.data_as(C.POINTER(C.c_int)),
-                                                                    out.ctypes.data_as(C.POINTER(C.c_double)) if want else None),
-                   "icp_batch_estimate_intensity_gradients")
+        capi.check(self._lib.icp_batch_estimate_intensity_gradients(self._h, _ptr(kq, C.c_int), _ptr(out)), "icp_batch_estimate_intensity_gradients")
         if want:
-            return self._cut6(out, self._qoff)
+            return self._cut(out, self._qoff)
 
     def set_intensity_gradients(self, grads):
         """the caller's own intensity gradients: one (m, 3) float64 array per pair, in the models' frame"""
-        grads = [np.ascontiguousarray(g, dtype=np.float64) for g in grads]
-        if len(grads) != self.count:
-            raise ValueError("one array of gradients per pair")
-        for b, g in enumerate(grads):
-            if g.shape != (int(self._qoff[b + 1] - self._qoff[b]), 3):
-                raise ValueError("a pair's gradients must be (model points, 3)")
-        g = np.ascontiguousarray(np.concatenate(grads))
-        capi.check(self._lib.icp_batch_set_intensity_gradients(self._h, g.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_intensity_gradients")
+        g = self._side(list(grads), self._qoff, 3, "model gradients")
+        capi.check(self._lib.icp_batch_set_intensity_gradients(self._h, _ptr(g)), "icp_batch_set_intensity_gradients")
 
     def get_intensity_gradients(self):
         """per pair the (m, 3) float64 gradients the batch holds (icp_batch_get_intensity_gradients)"""
         out = np.empty((int(self._qoff[-1]), 3))
-        capi.check(self._lib.icp_batch_get_intensity_gradients(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_get_intensity_gradients")
-        return self._cut6(out, self._qoff)
+        capi.check(self._lib.icp_batch_get_intensity_gradients(self._h, _ptr(out)), "icp_batch_get_intensity_gradients")
+        return self._cut(out, self._qoff)
 
     def set_color_weight(self, lam=None):
         """lambda, the weight of the geometric term of the colored metric (1 - lambda weighs the photometric term): a scalar for
@@ -1081,19 +1059,6 @@ class Batch:
         capi.check(self._lib.icp_diag_batch_rotation(self._h, int(b), R.ctypes.data_as(C.POINTER(C.c_double))), "icp_diag_batch_rotation")
         return R.reshape(3, 3)
 
-    def _normals_side(self, normals, off, what):
-        """one (points, 3) float64 array per pair -> their concatenation in that side's layout"""
-        normals = [np.ascontiguousarray(a, dtype=np.float64) for a in normals]
-        if len(normals) != self.count:
-            raise ValueError(f"one array of {what} normals per pair")
-        for b, a in enumerate(normals):
-            if a.shape != (int(off[b + 1] - off[b]), 3):
-                raise ValueError(f"a pair's {what} normals must be (points, 3)")
-        return np.ascontiguousarray(np.concatenate(normals))
-
-    def _cut33(self, flat, off):
-        return [flat[off[b]:off[b + 1]].copy() for b in range(self.count)]
-
     def compute_features(self, k, normals, k_model=None, want=False):
         """a 33-bin FPFH descriptor of every point of both clouds of every pair, on the device in two launches
         (icp_batch_compute_features): k neighbours per point (a scalar or one value per pair, each in [3, 32]; k_model: the same
@@ -1103,15 +1068,13 @@ class Batch:
         (points, 33) float64 descriptors."""
         moving, model = normals
         km, kq = self._cov_k(k, "k"), self._cov_k(k if k_model is None else k_model, "model k")
-        nm, nq = self._normals_side(moving, self._moff, "moving"), self._normals_side(model, self._qoff, "model")
-        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        nm, nq = self._side(list(moving), self._moff, 3, "moving normals"), self._side(list(model), self._qoff, 3, "model normals")
         om = np.empty((int(self._moff[-1]), capi.ICP_FEATURE_BINS)) if want else None
         oq = np.empty((int(self._qoff[-1]), capi.ICP_FEATURE_BINS)) if want else None
-        capi.check(self._lib.icp_batch_compute_features(self._h, km.ctypes.data_as(pi), kq.ctypes.data_as(pi), nm.ctypes.data_as(pd), nq.ctypes.data_as(pd),
-                                                        om.ctypes.data_as(pd) if want else None, oq.ctypes.data_as(pd) if want else None),
+        capi.check(self._lib.icp_batch_compute_features(self._h, _ptr(km, C.c_int), _ptr(kq, C.c_int), _ptr(nm), _ptr(nq), _ptr(om), _ptr(oq)),
                    "icp_batch_compute_features")
         if want:
-            return self._cut33(om, self._moff), self._cut33(oq, self._qoff)
+            return self._cut(om, self._moff), self._cut(oq, self._qoff)
 
     def _viewpoints(self, viewpoints):
         """(moving, model), each (count, 3) float64: one (3,) viewpoint for every cloud, or a (moving, model) pair of per-pair arrays"""
@@ -1135,47 +1098,37 @@ class Batch:
         (points, 3) float64 normals.  One launch, two for "centroid"; a host wait only with want.  A loop under way is left alone."""
         mode = {"none": capi.ICP_ORIENT_NONE, None: capi.ICP_ORIENT_NONE, "viewpoint": capi.ICP_ORIENT_VIEWPOINT,
                 "centroid": capi.ICP_ORIENT_CENTROID}[orient] if (orient is None or isinstance(orient, str)) else int(orient)
-        pd = C.POINTER(C.c_double)
         vm = vq = None
         if mode == capi.ICP_ORIENT_VIEWPOINT and viewpoints is not None:
             vm, vq = self._viewpoints(viewpoints)
         om = np.empty((int(self._moff[-1]), 3)) if want else None
         oq = np.empty((int(self._qoff[-1]), 3)) if want else None
-        capi.check(self._lib.icp_batch_estimate_point_normals(self._h, mode, vm.ctypes.data_as(pd) if vm is not None else None,
-                                                              vq.ctypes.data_as(pd) if vq is not None else None,
-                                                              om.ctypes.data_as(pd) if want else None, oq.ctypes.data_as(pd) if want else None),
-                   "icp_batch_estimate_point_normals")
+        capi.check(self._lib.icp_batch_estimate_point_normals(self._h, mode, _ptr(vm), _ptr(vq), _ptr(om), _ptr(oq)), "icp_batch_estimate_point_normals")
         if want:
-            return self._cut33(om, self._moff), self._cut33(oq, self._qoff)
+            return self._cut(om, self._moff), self._cut(oq, self._qoff)
 
     def set_point_normals(self, moving=None, model=None):
         """point normals of the caller's own (icp_batch_set_point_normals): per side one (points, 3) float64 array per pair, or
         None: that side is left as it is.  Only finiteness is checked."""
-        pd = C.POINTER(C.c_double)
-        a = self._normals_side(moving, self._moff, "moving") if moving is not None else None
-        q = self._normals_side(model, self._qoff, "model") if model is not None else None
-        capi.check(self._lib.icp_batch_set_point_normals(self._h, a.ctypes.data_as(pd) if a is not None else None,
-                                                         q.ctypes.data_as(pd) if q is not None else None), "icp_batch_set_point_normals")
+        a, q = self._side(moving, self._moff, 3, "moving normals"), self._side(model, self._qoff, 3, "model normals")
+        capi.check(self._lib.icp_batch_set_point_normals(self._h, _ptr(a), _ptr(q)), "icp_batch_set_point_normals")
 
     def get_point_normals(self):
         """(moving, model): per pair the (points, 3) float64 point normals the batch holds (icp_batch_get_point_normals)"""
-        pd = C.POINTER(C.c_double)
         om, oq = np.empty((int(self._moff[-1]), 3)), np.empty((int(self._qoff[-1]), 3))
-        capi.check(self._lib.icp_batch_get_point_normals(self._h, om.ctypes.data_as(pd), oq.ctypes.data_as(pd)), "icp_batch_get_point_normals")
-        return self._cut33(om, self._moff), self._cut33(oq, self._qoff)
+        capi.check(self._lib.icp_batch_get_point_normals(self._h, _ptr(om), _ptr(oq)), "icp_batch_get_point_normals")
+        return self._cut(om, self._moff), self._cut(oq, self._qoff)
 
     def compute_features_stored(self, k, k_model=None, want=False):
         """compute_features from the point normals the batch holds (estimate_point_normals, set_point_normals): the same two
         launches, nothing uploaded (icp_batch_compute_features_stored)"""
         km, kq = self._cov_k(k, "k"), self._cov_k(k if k_model is None else k_model, "model k")
-        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
         om = np.empty((int(self._moff[-1]), capi.ICP_FEATURE_BINS)) if want else None
         oq = np.empty((int(self._qoff[-1]), capi.ICP_FEATURE_BINS)) if want else None
-        capi.check(self._lib.icp_batch_compute_features_stored(self._h, km.ctypes.data_as(pi), kq.ctypes.data_as(pi),
-                                                               om.ctypes.data_as(pd) if want else None, oq.ctypes.data_as(pd) if want else None),
+        capi.check(self._lib.icp_batch_compute_features_stored(self._h, _ptr(km, C.c_int), _ptr(kq, C.c_int), _ptr(om), _ptr(oq)),
                    "icp_batch_compute_features_stored")
         if want:
-            return self._cut33(om, self._moff), self._cut33(oq, self._qoff)
+            return self._cut(om, self._moff), self._cut(oq, self._qoff)
 
     def diag_centroids(self):
         """(moving, model), each (count, 3) float64: the centroids of the last estimate_point_normals("centroid")
@@ -1186,20 +1139,18 @@ class Batch:
 
     def get_features(self):
         """(moving, model): per pair the (points, 33) float64 descriptors the batch holds (icp_batch_get_features)"""
-        pd = C.POINTER(C.c_double)
         om = np.empty((int(self._moff[-1]), capi.ICP_FEATURE_BINS))
         oq = np.empty((int(self._qoff[-1]), capi.ICP_FEATURE_BINS))
-        capi.check(self._lib.icp_batch_get_features(self._h, om.ctypes.data_as(pd), oq.ctypes.data_as(pd)), "icp_batch_get_features")
-        return self._cut33(om, self._moff), self._cut33(oq, self._qoff)
+        capi.check(self._lib.icp_batch_get_features(self._h, _ptr(om), _ptr(oq)), "icp_batch_get_features")
+        return self._cut(om, self._moff), self._cut(oq, self._qoff)
 
     def diag_set_features(self, moving, model):
         """descriptors of the caller's own, per side one (points, 33) float64 array per pair (icp_diag_batch_set_features): for tests"""
-        pd = C.POINTER(C.c_double)
         a = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1, capi.ICP_FEATURE_BINS) for x in moving]))
         q = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1, capi.ICP_FEATURE_BINS) for x in model]))
         if a.shape[0] != int(self._moff[-1]) or q.shape[0] != int(self._qoff[-1]):
             raise ValueError("one (points, 33) array of descriptors per cloud")
-        capi.check(self._lib.icp_diag_batch_set_features(self._h, a.ctypes.data_as(pd), q.ctypes.data_as(pd)), "icp_diag_batch_set_features")
+        capi.check(self._lib.icp_diag_batch_set_features(self._h, _ptr(a), _ptr(q)), "icp_diag_batch_set_features")
 
     def match_features(self, mutual=True):
         """the nearest descriptor of the other cloud for every point, both ways (icp_batch_match_features): (fwd, rev, kept), per
@@ -1212,7 +1163,7 @@ class Batch:
         kept = np.zeros(int(self._moff[-1]), dtype=np.uint8)
         capi.check(self._lib.icp_batch_match_features(self._h, 1 if mutual else 0, fwd.ctypes.data_as(p32), rev.ctypes.data_as(p32),
                                                       kept.ctypes.data_as(C.POINTER(C.c_uint8))), "icp_batch_match_features")
-        return self._split(fwd), [rev[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)], self._split(kept)
+        return self._split(fwd), self._cut(rev, self._qoff), self._split(kept)
 
     def score_transforms(self, T, max_distance):
         """(count, per_pair) int32: how many correspondences of every pair lie within max_distance (a scalar, one value per pair,
@@ -1227,7 +1178,7 @@ class Batch:
         md = None if max_distance is None else self._per_pair(max_distance, "maximum distance")
         pd = C.POINTER(C.c_double)
         out = np.zeros((self.count, T.shape[1]), dtype=np.int32)
-        capi.check(self._lib.icp_batch_score_transforms(self._h, int(T.shape[1]), T.ctypes.data_as(pd), md.ctypes.data_as(pd) if md is not None else None,
+        capi.check(self._lib.icp_batch_score_transforms(self._h, int(T.shape[1]), T.ctypes.data_as(pd), _ptr(md),
                                                         out.ctypes.data_as(C.POINTER(C.c_int32))), "icp_batch_score_transforms")
         return out
 
@@ -1286,7 +1237,7 @@ class Batch:
         obj = np.zeros(self.count)
         st = np.zeros(self.count, dtype=np.intc)
         pd = C.POINTER(C.c_double)
-        capi.check(self._lib.icp_batch_fgr(self._h, C.byref(prm), sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None, T.ctypes.data_as(pd),
+        capi.check(self._lib.icp_batch_fgr(self._h, C.byref(prm), _ptr(sd, C.c_uint64), T.ctypes.data_as(pd),
                                            w.ctypes.data_as(pd), used.ctypes.data_as(C.POINTER(C.c_int32)), obj.ctypes.data_as(pd),
                                            st.ctypes.data_as(C.POINTER(C.c_int))), "icp_batch_fgr")
         self._fgr_iter, self._fgr_used = int(iterations), used.copy()
@@ -1370,7 +1321,7 @@ class Batch:
         matched since begin"""
         out = np.empty(int(self._qoff[-1]), dtype=np.int32)
         capi.check(self._lib.icp_diag_batch_reverse(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))), "icp_diag_batch_reverse")
-        return [out[self._qoff[b]:self._qoff[b + 1]].copy() for b in range(self.count)]
+        return self._cut(out, self._qoff)
 
     def set_robust(self, kind, scale=None):
         """robust kernels: kind None (none), one kernel for every pair, or one per pair -- "huber", "cauchy", "tukey", None or the
@@ -1504,7 +1455,7 @@ class Batch:
         idx = np.zeros(total, dtype=np.int32) if want_matches else None
         mask = np.zeros(total, dtype=np.uint8) if want_matches else None
         pd, pi32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        capi.check(self._lib.icp_batch_evaluate(self._h, int(metric), md.ctypes.data_as(pd) if md is not None else None,
+        capi.check(self._lib.icp_batch_evaluate(self._h, int(metric), _ptr(md),
                                                 status.ctypes.data_as(C.POINTER(C.c_int)), inl.ctypes.data_as(pi32), fit.ctypes.data_as(pd),
                                                 rmse.ctypes.data_as(pd), info.ctypes.data_as(pd),
                                                 idx.ctypes.data_as(pi32) if want_matches else None,

@@ -1,11 +1,16 @@
 // batch_clouds_check.cpp -- csrc/icp_batch_clouds.h on the CPU.  Built and run by tests/test_batch_clouds.py (with the address and
-// undefined-behaviour sanitizers); prints one line per failed check, a summary, and exits 0 when all hold.  Two things:
+// undefined-behaviour sanitizers); prints one line per failed check, a summary, and exits 0 when all hold.  Three things:
 //   * CLOUDS.  list_clouds for 1 and 3 pairs, every cloud size drawn from {1, 63, 64, 65, 129} (all combinations) and the three
 //     side masks, against a restatement by brute force: which cloud is which, the stretches of the temporaries, and a per-point
 //     count of the work items that cover it.
 //   * ARGS.  lay_out_args over a grid of cloud, item and int counts: 16-byte boundaries, regions that do not overlap, the exact total.
+//   * CODEC.  encode and decode for 1 and 3 pairs, every cloud size of a side drawn from the same five (all combinations), both
+//     sides, widths 1, 3 and 6 as planes and 33 as rows, float and double: decode(encode(x)) is x byte for byte, every value sits
+//     where a restatement of k * plane + dst[p] + i (planes) and (dst[p] + i) * width + k (rows) puts it, every other byte of the
+//     packed buffer is zero, and decode writes nothing outside the caller's array (guard values on both ends).
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "../fast-point-cloud-registration-with-gpus_amd/csrc/icp_batch_clouds.h"
@@ -141,10 +146,65 @@ static void check_args()
             }
 }
 
+template <typename E>
+static void check_codec_case(const std::vector<int>& n, const std::vector<int>& m, bool model, int width, Layout layout)
+{
+    const std::vector<BatchPair> pairs = make_pairs(n, m);
+    const std::vector<int>& len = model ? m : n;
+    std::vector<int64_t> off(len.size() + 1, 0);
+    for (size_t p = 0; p < len.size(); ++p) off[p + 1] = off[p] + len[p];
+    const BatchPair& last = pairs.back();
+    const long long plane = (model ? last.q_off : last.p_off) + (len.back() + BATCH_ALIGN - 1) / BATCH_ALIGN * BATCH_ALIGN;
+    const Side s = make_side(pairs, off.data(), plane, model);
+    const Format f{width, layout, sizeof(E)};
+    char tag[160];
+    snprintf(tag, sizeof tag, "codec %s width %d %s side %d sizes %d/%d/%d", sizeof(E) == 8 ? "f64" : "f32", width, layout == ROWS ? "rows" : "planes",
+             (int)model, len[0], len.size() > 1 ? len[1] : 0, len.size() > 2 ? len[2] : 0);
+    for (size_t p = 0; p < len.size(); ++p) check(s.dst[p] == (model ? pairs[p].q_off : pairs[p].p_off), "%s: dst[%zu] %lld", tag, p, s.dst[p]);
+    const size_t total = (size_t)off.back() * width, guard = 16;
+    const E sentinel = (E)-12345;
+    std::vector<E> own(guard + total + guard, sentinel), back(guard + total + guard, sentinel);
+    for (size_t i = 0; i < total; ++i) own[guard + i] = (E)(1 + i);   // (never 0, never the sentinel; exact in a float up to 2^24)
+    std::vector<char> raw(3, 'x');   // (a vector that is used twice starts over)
+    encode(f, s, own.data() + guard, raw);
+    if (!check(raw.size() == (size_t)width * (size_t)plane * sizeof(E) && raw.size() == f.bytes(plane), "%s: %zu packed bytes", tag, raw.size())) return;
+    std::vector<char> expect(raw.size(), 0);
+    E* e = reinterpret_cast<E*>(expect.data());
+    for (size_t p = 0; p < len.size(); ++p)
+        for (int i = 0; i < len[p]; ++i)
+            for (int k = 0; k < width; ++k) {
+                const size_t at = layout == ROWS ? (size_t)(s.dst[p] + i) * width + k : (size_t)(k * plane + s.dst[p] + i);
+                if (!check(at < (size_t)width * (size_t)plane, "%s: the restatement leaves the buffer", tag)) return;
+                e[at] = own[guard + (size_t)(off[p] + i) * width + k];
+            }
+    check(std::memcmp(raw.data(), expect.data(), raw.size()) == 0, "%s: a value is misplaced or a padding byte is not zero", tag);
+    decode(f, s, raw.data(), back.data() + guard);
+    check(std::memcmp(back.data(), own.data(), own.size() * sizeof(E)) == 0, "%s: decode(encode(x)) != x, or a guard value was written", tag);
+}
+
+static void check_codec()
+{
+    static const int widths[4] = {1, 3, 6, 33};
+    for (int w = 0; w < 4; ++w)
+        for (int model = 0; model < 2; ++model) {
+            const Layout layout = widths[w] == 33 ? ROWS : PLANES;
+            for (int a = 0; a < 5; ++a) {
+                check_codec_case<float>({kSizes[a]}, {kSizes[a]}, model != 0, widths[w], layout);
+                check_codec_case<double>({kSizes[a]}, {kSizes[a]}, model != 0, widths[w], layout);
+            }
+            for (int code = 0; code < 5 * 5 * 5; ++code) {   // the side's three sizes: all combinations; the other side's: rotated
+                const std::vector<int> own{kSizes[code % 5], kSizes[code / 5 % 5], kSizes[code / 25]}, other{own[1], own[2], own[0]};
+                check_codec_case<float>(model ? other : own, model ? own : other, model != 0, widths[w], layout);
+                check_codec_case<double>(model ? other : own, model ? own : other, model != 0, widths[w], layout);
+            }
+        }
+}
+
 int main()
 {
     check_clouds();
     check_args();
+    check_codec();
     printf("%d checks, %d failed\n", g_checks, g_failed);
     if (g_failed == 0) printf("batch_clouds_check passed\n");
     return g_failed == 0 ? 0 : 1;
