@@ -1,7 +1,8 @@
 // icp_device_batch.h -- device-side pieces shared by the batched neighbourhood kernels (icp_k_batch.hip, icp_k_gicp.hip,
 // icp_k_color.hip, icp_k_feat.hip, icp_k_keypoint.hip, icp_k_normals.hip): the list behind the k-th smallest distance and the scan
 // that fills it ("phase 1"), the block-wide walk over a cloud's tiles ("phase 2"), the neighbourhood sums behind a covariance, the
-// cyclic Jacobi of icp_eigh3, the exclusive scan of keep flags, the copy of a kept point and the kept decision of a deferred step.
+// cyclic Jacobi of icp_eigh3 with its range rule (a matrix beyond 2^+-400 is solved times an exact power of two, the eigenvalues
+// scaled back; the Frobenius regularisation forms its norm the same way), the exclusive scan of keep flags, the copy of a kept point and the kept decision of a deferred step.
 // ONE definition each: a kernel states what is its own -- its pointers, its per-chunk body, its closing arithmetic, its stores.
 // Everything here is constexpr or __device__ __forceinline__, and rounds every operation on its own (icp_device.h turns contraction
 // off).  Internal to libicp_mi355x.so.
@@ -284,7 +285,7 @@ struct NeighbourSums {
 
 // ------------------------------------------------------------------------------------------------
 // icp_eigh3's cyclic Jacobi (icp_host_math.cpp) on named doubles -- no runtime-indexed array, no scratch.  The statements and their
-// order are the host's.  The eigenvectors are formed with VECTORS alone.
+// order are the host's, the range rule in front included.  The eigenvectors are formed with VECTORS alone.
 // ------------------------------------------------------------------------------------------------
 struct EigenVectors3 {   // v[row][column], the identity before the first sweep
     double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
@@ -317,10 +318,29 @@ __device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& 
     }
 }
 
-// the sweeps over (0,1), (0,2), (1,2), at most 64, every lane under its own stop test: the eigenvalues are left on the diagonal
-template <bool VECTORS>
-__device__ __forceinline__ void jacobi_eigh3(double& a00, double& a01, double& a02, double& a11, double& a12, double& a22, EigenVectors3& v)
+// the range rule of icp_eigh3 and of the Frobenius regularisation: whatever squares the six entries of a symmetric matrix leaves the
+// double range once they pass 2^+-400 (the Jacobi's stop test then sees off = inf or 0 and ends at once, with the identity for
+// eigenvectors; the Frobenius norm is inf or 0).  With amax the largest magnitude of the six, amax > 2^400 multiplies them by 2^-600
+// and 0 < amax < 2^-400 by 2^+600: an exact power of two, which changes no rotation and no quotient.  Returns the factor that
+// scales an eigenvalue back (2^+600, 2^-600), 1.0 where the matrix is left as it is: amax within [2^-400, 2^400], amax == 0, and
+// every matrix with an entry that is not finite -- those go through bit for bit.
+__device__ __forceinline__ double range_scale6(double& a00, double& a01, double& a02, double& a11, double& a12, double& a22)
 {
+    const double amax = fmax(fmax(fmax(fabs(a00), fabs(a01)), fmax(fabs(a02), fabs(a11))), fmax(fabs(a12), fabs(a22)));   // (fmax drops a NaN)
+    if (!(amax > 0x1p+400 || (amax < 0x1p-400 && amax > 0.0))) return 1.0;
+    if (!(finite_(a00) && finite_(a01) && finite_(a02) && finite_(a11) && finite_(a12) && finite_(a22))) return 1.0;
+    const double sc = amax > 1.0 ? 0x1p-600 : 0x1p+600;
+    a00 *= sc; a01 *= sc; a02 *= sc; a11 *= sc; a12 *= sc; a22 *= sc;
+    return amax > 1.0 ? 0x1p+600 : 0x1p-600;
+}
+
+// the sweeps over (0,1), (0,2), (1,2), at most 64, every lane under its own stop test, on the matrix range_scale6 leaves: the
+// eigenvalues are left on the diagonal, to be multiplied by the factor returned once their ascending order is fixed (the
+// eigenvectors need nothing)
+template <bool VECTORS>
+__device__ __forceinline__ double jacobi_eigh3(double& a00, double& a01, double& a02, double& a11, double& a12, double& a22, EigenVectors3& v)
+{
+    const double unscale = range_scale6(a00, a01, a02, a11, a12, a22);
 #pragma unroll 1
     for (int sweep = 0; sweep < 64; ++sweep) {
         const double off = a01 * a01 + a02 * a02 + a12 * a12;
@@ -330,6 +350,7 @@ __device__ __forceinline__ void jacobi_eigh3(double& a00, double& a01, double& a
         jacobi_rotate<VECTORS>(a00, a22, a02, a01, a12, v.v00, v.v10, v.v20, v.v02, v.v12, v.v22);   // (0, 2), r = 1
         jacobi_rotate<VECTORS>(a11, a22, a12, a01, a02, v.v01, v.v11, v.v21, v.v02, v.v12, v.v22);   // (1, 2), r = 0
     }
+    return unscale;
 }
 
 // ------------------------------------------------------------------------------------------------

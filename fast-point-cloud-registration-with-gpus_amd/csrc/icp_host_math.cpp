@@ -190,15 +190,30 @@ int solve_point_to_plane(const double* mom, double* R, double* t, double* x6)
     return ICP_OK;
 }
 
-// cyclic Jacobi on the full symmetric matrix built from the upper triangle
+// cyclic Jacobi on the full symmetric matrix built from the upper triangle.  The stop test squares the entries, and the squares of
+// a matrix beyond 2^+-400 leave the range (off = inf or 0 ends the sweeps at once: the identity would come out whatever the matrix):
+// with amax the largest magnitude of the six entries, amax > 2^400 multiplies them by 2^-600 and 0 < amax < 2^-400 by 2^+600 -- an
+// exact power of two, which changes no rotation -- and the eigenvalues are multiplied back once their order is fixed.  Every other
+// matrix, and every matrix with an entry that is not finite, goes through as it is, bit for bit.
 void eigh3(const double A[9], double w[3], double Z[9])
 {
     double a[3][3], v[3][3];
+    double amax = 0.0;
+    bool finite = true;
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) {
             a[i][j] = j >= i ? A[i * 3 + j] : A[j * 3 + i];
             v[i][j] = i == j ? 1.0 : 0.0;
+            amax = std::fmax(amax, std::fabs(a[i][j]));   // (fmax drops a NaN)
+            finite = finite && std::isfinite(a[i][j]);
         }
+    double unscale = 1.0;
+    if (finite && (amax > 0x1p+400 || (amax < 0x1p-400 && amax > 0.0))) {
+        const double sc = amax > 1.0 ? 0x1p-600 : 0x1p+600;
+        unscale = amax > 1.0 ? 0x1p+600 : 0x1p-600;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) a[i][j] *= sc;
+    }
     for (int sweep = 0; sweep < 64; ++sweep) {
         const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
         const double dia = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
@@ -230,7 +245,7 @@ void eigh3(const double A[9], double w[3], double Z[9])
         for (int j = i + 1; j < 3; ++j)
             if (a[ord[j]][ord[j]] < a[ord[i]][ord[i]]) std::swap(ord[i], ord[j]);
     for (int k = 0; k < 3; ++k) {
-        w[k] = a[ord[k]][ord[k]];
+        w[k] = a[ord[k]][ord[k]] * unscale;
         for (int i = 0; i < 3; ++i) Z[i * 3 + k] = v[i][ord[k]];
     }
 }

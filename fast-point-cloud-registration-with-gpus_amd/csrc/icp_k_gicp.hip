@@ -53,6 +53,7 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_cov_kernel(const BatchCovArgs 
     double xx, xy, xz, yy, yz, zz;
     sums.covariance(xx, xy, xz, yy, yz, zz);   // (the count is >= k + 1)
     if (a.regularisation == ICP_COV_FROBENIUS) {
+        (void)range_scale6(xx, xy, xz, yy, yz, zz);   // the squares below stay in range; the quotients are scale-free
         const double f = sqrt(((xx * xx + yy * yy) + zz * zz) + 2.0 * ((xy * xy + xz * xz) + yz * yz));
         const double lam = a.lambda;
         if (f > 0.0) {

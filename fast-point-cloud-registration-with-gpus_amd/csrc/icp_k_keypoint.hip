@@ -58,11 +58,12 @@ __global__ __launch_bounds__(NN_BLOCK) void batch_iss_saliency(const BatchKeypoi
     double a00, a01, a02, a11, a12, a22;
     sums.covariance(a00, a01, a02, a11, a12, a22);
     EigenVectors3 none;
-    jacobi_eigh3<false>(a00, a01, a02, a11, a12, a22, none);
+    const double unscale = jacobi_eigh3<false>(a00, a01, a02, a11, a12, a22, none);
     double w0 = a00, w1 = a11, w2 = a22, tmp;   // ... and its ascending order: three compare-and-swaps
     if (w1 < w0) { tmp = w0; w0 = w1; w1 = tmp; }
     if (w2 < w0) { tmp = w0; w0 = w2; w2 = tmp; }
     if (w2 < w1) { tmp = w1; w1 = w2; w2 = tmp; }
+    w0 *= unscale; w1 *= unscale; w2 *= unscale;   // (the range rule: 1.0 for every matrix within 2^+-400)
     const bool salient = sums.cnt >= rule.min_neighbours && (w1 / w2) < rule.gamma_21 && (w0 / w1) < rule.gamma_32 && w0 > 0.0;   // (NaN fails each)
     sal[i] = salient ? w0 : 0.0;
 }

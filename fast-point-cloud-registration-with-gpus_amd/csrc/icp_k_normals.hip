@@ -67,7 +67,7 @@ __global__ __launch_bounds__(BATCH_ITEM) void batch_point_normals_kernel(const B
     const double* C = a.cov[c.side] + c.src_off + i;
     double a00 = C[0], a01 = C[sp], a02 = C[2 * sp], a11 = C[3 * sp], a12 = C[4 * sp], a22 = C[5 * sp];
     EigenVectors3 v;
-    jacobi_eigh3<true>(a00, a01, a02, a11, a12, a22, v);
+    (void)jacobi_eigh3<true>(a00, a01, a02, a11, a12, a22, v);   // (the factor that scales the eigenvalues back: the order needs none)
     // ... its ascending order: three compare-and-swaps with the strict <, every column with its eigenvalue
     double w0 = a00, w1 = a11, w2 = a22;
     double nx = v.v00, ny = v.v10, nz = v.v20;     // column ord[0]

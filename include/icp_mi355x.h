@@ -550,7 +550,11 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *             against the query, so a cloud far from the origin loses nothing; s_a += e_a; S_ab += e_a * e_b for the six a <= b.
  *           C_ab = (S_ab - (s_a * s_b) / (double)c) / (double)c: each operation rounded on its own, nothing fused.
  *           ICP_COV_FROBENIUS: f = sqrt(((xx*xx + yy*yy) + zz*zz) + 2.0 * ((xy*xy + xz*xz) + yz*yz)); f > 0: C'_ab = C_ab / f,
- *             plus lambda on the diagonal; f == 0: C' = lambda I exactly.  ICP_COV_NONE: the raw covariance.
+ *             plus lambda on the diagonal; f == 0: C' = lambda I exactly.  ICP_COV_NONE: the raw covariance.  f and the quotients
+ *             are formed on the matrix icp_eigh3's range rule leaves (below): with amax the largest magnitude of the six entries,
+ *             all finite, amax > 2^400 multiplies the six by 2^-600 first and 0 < amax < 2^-400 by 2^+600 -- no square leaves
+ *             the double range, the quotients are scale-free, and f == 0 is left to the zero matrix alone.  Within 2^+-400
+ *             nothing is multiplied.
  *           a cloud's result depends on that cloud, its k and the two parameters alone.
  *         cost: one launch for all clouds of the sides asked for (one block per 64 points: the k-th distance in a register list,
  *           then the sums in one pass over the cloud), no atomics, and one host wait only when an output array is wanted.
@@ -633,7 +637,9 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *                 the updates of v included -- cyclic Jacobi over (0,1), (0,2), (1,2) from v = I; at most 64 sweeps; the stop test
  *                 off <= 1e-34 * dia || off == 0.0; the same theta, t, c, s; the same three compare-and-swaps of the order with the
  *                 strict <.  n is column ord[0] of v, not renormalised.  A zero matrix gives (1, 0, 0); equal smallest
- *                 eigenvalues give whatever these statements give.
+ *                 eigenvalues give whatever these statements give.  icp_eigh3's range rule comes first: a matrix of six finite
+ *                 entries whose largest magnitude lies beyond 2^+-400 is solved times 2^-+600 -- the same rotations, so n does
+ *                 not depend on a power of two in C.
  *               non-finite rule: if any component of n is not finite, n is exactly (0.0, 0.0, 0.0) -- the kept normals are always
  *                 finite, which is what icp_batch_compute_features demands of the caller's.
  *               orientation: to_a = v_a - (double)x_a for the cloud's viewpoint v; dt = (n_x*to_x + n_y*to_y) + n_z*to_z; n is
@@ -752,7 +758,10 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *               eigenvalues: icp_eigh3's statements (below) on the symmetric matrix built from C -- cyclic Jacobi over (0,1),
  *                 (0,2), (1,2); at most 64 sweeps; the stop test off <= 1e-34 * dia || off == 0.0; the same theta, t, c, s and
  *                 update statements; the same ascending order w0 <= w1 <= w2.  The eigenvectors are not formed: the eigenvalues do
- *                 not depend on them.
+ *                 not depend on them.  icp_eigh3's range rule comes first, and w0, w1, w2 are the scaled-back eigenvalues: a
+ *                 matrix of six finite entries whose largest magnitude lies beyond 2^+-400 is solved times 2^-+600, and each
+ *                 eigenvalue is multiplied by 2^+-600 once the order is fixed -- the saliency of a cloud times 2^e is 2^(2e)
+ *                 times the cloud's own.
  *               saliency: sal_i = w0 iff c >= min_neighbours && (w1 / w2) < gamma_21 && (w0 / w1) < gamma_32 && w0 > 0, else
  *                 sal_i is exactly 0.0.  A NaN fails every comparison.  The divisions are Open3D's.
  *               selection: M_i is every j with d2(i, j) <= tn, i included.  i is a keypoint iff sal_i > 0 &&
@@ -1058,7 +1067,12 @@ int icp_host_loop_state(icp_host_loop* h, int* iterations, int* passes, double* 
  * shard_cyclic_index of the Python mirror) -- every rank simply passes its own points to icp_set_moving. */
 int icp_shard_range(int64_t n, int rank, int world, int64_t* begin, int64_t* count);
 /* symmetric 3x3 eigen-solve used for the normals (upper triangle of row-major A read);
- * w ascending, Z[i*3+k] = component i of eigenvector k */
+ * w ascending, Z[i*3+k] = component i of eigenvector k.  The range rule: the stop test of the cyclic Jacobi squares the entries, so
+ * with amax the largest magnitude of the six entries read, all of them finite, amax > 2^400 multiplies them by 2^-600 and
+ * 0 < amax < 2^-400 by 2^+600 before the first sweep -- an exact power of two, which changes no rotation -- and the three
+ * eigenvalues are multiplied by 2^+600 or 2^-600 after the ascending order is fixed: w is the scaled-back eigenvalues, and one that
+ * leaves the double range on the way back is what IEEE makes of the product (inf, a subnormal, 0).  Every matrix with amax within
+ * [2^-400, 2^400], the zero matrix, and every matrix with an entry that is not finite go through as they are, bit for bit. */
 int icp_eigh3(const double* A9, double* w3, double* Z9);
 
 /* ---- datasets: the reference's input formats --------------------------------- */

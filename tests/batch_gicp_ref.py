@@ -10,7 +10,9 @@ double.  Nothing here touches a device.
                   sum: the sum starts at +0.0 and a sum of doubles is never -0.0 unless every addend is, so np.cumsum over all j
                   behind one leading 0.0 is the rule's sequential sum.  (np.sum adds pairwise: not used.)
     covariance    C_ab = (S_ab - (s_a * s_b) / c) / c, every elementwise operation rounded separately
-    frobenius     f = sqrt(((xx*xx + yy*yy) + zz*zz) + 2.0 * ((xy*xy + xz*xz) + yz*yz)); f > 0: C / f + lam on the diagonal, else lam I
+    frobenius     f = sqrt(((xx*xx + yy*yy) + zz*zz) + 2.0 * ((xy*xy + xz*xz) + yz*yz)); f > 0: C / f + lam on the diagonal, else lam I;
+                  f and the quotients are formed on the matrix the range rule of icp_eigh3 leaves (batch_keypoint_ref.range_scale:
+                  times 2^-+600 where the largest magnitude lies beyond 2^+-400), so no square leaves the double range
 
 The per-match terms (terms()) use +, -, *, / on float64 arrays only, one numpy operation per rounding, in the order of the header;
 the device forms the same expressions, so a pass's vector is a sum of these terms up to the order of its additions.  The bound on
@@ -21,6 +23,7 @@ import math
 import numpy as np
 
 import batch_outlier_ref as orf
+from batch_keypoint_ref import range_scale
 import ref_moments as rm
 from batch_ref import hom, sq_dist
 
@@ -70,8 +73,10 @@ def covariances(X, k, regularisation=COV_FROBENIUS, lam=1e-3, rows=None):
 
 def frobenius(C, lam):
     C = np.asarray(C, dtype=np.float64)
-    xx, xy, xz, yy, yz, zz = (C[:, a] for a in range(6))
-    f = np.sqrt(((xx * xx + yy * yy) + zz * zz) + 2.0 * ((xy * xy + xz * xz) + yz * yz))
+    (xx, xy, xz, yy, yz, zz), _ = range_scale([C[:, a] for a in range(6)])   # the squares stay in range; the quotients are scale-free
+    C = np.stack([xx, xy, xz, yy, yz, zz], axis=1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = np.sqrt(((xx * xx + yy * yy) + zz * zz) + 2.0 * ((xy * xy + xz * xz) + yz * yz))
     pos = f > 0
     with np.errstate(divide="ignore", invalid="ignore"):
         out = np.where(pos[:, None], C / f[:, None], 0.0)

@@ -10,6 +10,8 @@ CPU and the GPU end-to-end tests use.  Nothing here touches a device.
     covariance  C_ab = (S_ab - (s_a * s_b) / c) / c, one numpy operation per rounding
     Jacobi      icp_eigh3's statements on six arrays a00 .. a22, every point at once: a point that has met the stop test, and a
                 rotation whose apq is exactly 0, keep their values through np.where -- elementwise IEEE operations keep the bits
+    range       a matrix whose largest magnitude lies beyond 2^+-400 is solved times 2^-+600 and its eigenvalues are scaled back
+                after the ascending order is fixed (range_scale): sal_i and the two ratio tests see the scaled-back values
     selection   integer counts and comparisons over the non-max neighbourhood
 """
 import os
@@ -70,9 +72,32 @@ def covariances(X, inside):
     return count, C
 
 
-def jacobi_eigenvalues(C):
-    """(3, n) float64, ascending per point: icp_eigh3's eigenvalues of the symmetric matrices given as (6, n) xx, xy, xz, yy, yz, zz"""
+def range_scale(a6):
+    """(the six arrays times sc, unscale (n,)): the range rule of icp_eigh3 and of the Frobenius regularisation.  amax = the largest
+    magnitude of the six entries; a matrix with six finite entries and amax > 2^400 is multiplied by 2^-600, one with
+    0 < amax < 2^-400 by 2^+600 (sc), and unscale = 1 / sc scales an eigenvalue back; sc = unscale = 1.0 for every other matrix,
+    whose bits a multiplication by 1.0 keeps"""
+    a6 = [np.asarray(a, dtype=np.float64) for a in a6]
+    amax = np.zeros(a6[0].shape)
+    finite = np.ones(a6[0].shape, dtype=bool)
+    for a in a6:
+        amax = np.fmax(amax, np.fabs(a))                          # (fmax drops a NaN)
+        finite &= np.isfinite(a)
+    big = finite & (amax > 2.0 ** 400)
+    small = finite & (amax < 2.0 ** -400) & (amax > 0.0)
+    sc = np.where(big, 2.0 ** -600, np.where(small, 2.0 ** 600, 1.0))
+    unscale = np.where(big, 2.0 ** 600, np.where(small, 2.0 ** -600, 1.0))
+    scaled = [np.where(big | small, a * sc, a) for a in a6]       # (the others: not multiplied at all)
+    return scaled, unscale
+
+
+def jacobi_eigenvalues(C, _scale=True):
+    """(3, n) float64, ascending per point: icp_eigh3's eigenvalues of the symmetric matrices given as (6, n) xx, xy, xz, yy, yz, zz.
+    _scale=False leaves the range rule out (the statements as they were before it: the anchor of tests/test_batch_range_ref.py)"""
     a00, a01, a02, a11, a12, a22 = (np.array(C[o], dtype=np.float64, copy=True) for o in range(6))
+    unscale = 1.0
+    if _scale:
+        (a00, a01, a02, a11, a12, a22), unscale = range_scale((a00, a01, a02, a11, a12, a22))
     live = np.ones(a00.shape, dtype=bool)                        # the point has not met the stop test yet
 
     def rotate(live, apq, app, aqq, arp, arq):
@@ -102,6 +127,8 @@ def jacobi_eigenvalues(C):
         w0, w2 = np.where(lt, w2, w0), np.where(lt, w0, w2)
         lt = w2 < w1
         w1, w2 = np.where(lt, w2, w1), np.where(lt, w1, w2)
+        if _scale:                                               # scaled back once the order is fixed
+            w0, w1, w2 = w0 * unscale, w1 * unscale, w2 * unscale
     return np.stack([w0, w1, w2])
 
 

@@ -12,16 +12,21 @@ of icp_batch_estimate_point_normals in numpy, bit for bit as include/icp_mi355x.
 """
 import numpy as np
 
-from batch_keypoint_ref import SWEEPS
+from batch_keypoint_ref import SWEEPS, range_scale
 
 NONE, VIEWPOINT, CENTROID = 0, 1, 2   # ICP_ORIENT_NONE, ICP_ORIENT_VIEWPOINT, ICP_ORIENT_CENTROID
 LANES = 256                            # the partial sums of the centroid
 
 
-def jacobi(C):
+def jacobi(C, _scale=True):
     """(w (3, n) ascending, n (3, n): column ord[0] of v, Z (3, 3, n): v's columns in the order of w) of the symmetric matrices given
-    as (6, n) xx, xy, xz, yy, yz, zz -- icp_eigh3's statements with the updates of v"""
+    as (6, n) xx, xy, xz, yy, yz, zz -- icp_eigh3's statements with the updates of v, behind its range rule
+    (batch_keypoint_ref.range_scale; w is scaled back).  _scale=False leaves the range rule out (the statements as they were before
+    it: the anchor of tests/test_batch_range_ref.py)"""
     a00, a01, a02, a11, a12, a22 = (np.array(C[o], dtype=np.float64, copy=True) for o in range(6))
+    unscale = 1.0
+    if _scale:
+        (a00, a01, a02, a11, a12, a22), unscale = range_scale((a00, a01, a02, a11, a12, a22))
     one, zero = np.ones(a00.shape), np.zeros(a00.shape)
     v = [[one.copy(), zero.copy(), zero.copy()], [zero.copy(), one.copy(), zero.copy()], [zero.copy(), zero.copy(), one.copy()]]   # v[row][column]
     live = np.ones(a00.shape, dtype=bool)
@@ -55,6 +60,8 @@ def jacobi(C):
             lt = w[j] < w[i]
             w[i], w[j] = np.where(lt, w[j], w[i]), np.where(lt, w[i], w[j])
             col[i], col[j] = np.where(lt[None, :], col[j], col[i]), np.where(lt[None, :], col[i], col[j])
+        if _scale:                                               # scaled back once the order is fixed
+            w = [x * unscale for x in w]
     return np.stack(w), col[0], np.stack(col, axis=1)
 
 

@@ -46,6 +46,8 @@ def test_header_states_the_rule():
                    "tau_i is the k-th smallest d2(i, j) over j != i by index", "all ties with the k-th are in", "c >= k + 1",
                    "in ascending j", "differences against the query", "C_ab = (S_ab - (s_a * s_b) / (double)c) / (double)c",
                    "f = sqrt(((xx*xx + yy*yy) + zz*zz) + 2.0 * ((xy*xy + xz*xz) + yz*yz))", "f == 0: C' = lambda I exactly",
+                   "f and the quotients are formed on the matrix icp_eigh3's range rule leaves", "multiplies the six by 2^-600 first",
+                   "f == 0 is left to the zero matrix alone", "Within 2^+-400 nothing is multiplied",
                    "weights on a Mahalanobis residual are a later change", "det = (S00*c00 + S01*c01) + S02*c02",
                    "A match whose det is not finite or not > 0 is rejected", "j0 = (0, -pz, py), j1 = (pz, 0, -px), j2 = (-py, px, 0)",
                    "Slot C(a, c) += j_a . u_c for a <= c; slot B(a) -= u_a . e", "Every dot product is (x*x' + y*y') + z*z'",

@@ -44,6 +44,8 @@ def test_header_states_the_rule():
                    "over the neighbourhood in ascending j", "e = (double)x_j - (double)x_i, s_a += e_a, S_ab += e_a * e_b",
                    "C_ab = (S_ab - (s_a * s_b) / (double)c) / (double)c", "cyclic Jacobi over (0,1), (0,2), (1,2)", "at most 64 sweeps",
                    "off <= 1e-34 * dia || off == 0.0", "the same ascending order w0 <= w1 <= w2",
+                   "w0, w1, w2 are the scaled-back eigenvalues", "multiplied by 2^+-600 once the order is fixed",
+                   "the saliency of a cloud times 2^e is 2^(2e) times the cloud's own",
                    "sal_i = w0 iff c >= min_neighbours && (w1 / w2) < gamma_21 && (w0 / w1) < gamma_32 && w0 > 0",
                    "sal_i is exactly 0.0", "A NaN fails every comparison", "M_i is every j with d2(i, j) <= tn, i included",
                    "|M_i| >= min_neighbours && sal_j <= sal_i for every j in M_i", "Equal saliencies keep each other",

@@ -51,6 +51,9 @@ def test_header_states_the_rule():
                    "A refused call leaves the previous normals and everything else as they were", "neither discards nor advances it",
                    "The normals are a snapshot", "bit for bit in numpy", "+ - * / sqrt fabs copysign",
                    "cyclic Jacobi over (0,1), (0,2), (1,2) from v = I", "at most 64 sweeps", "off <= 1e-34 * dia || off == 0.0",
+                   "icp_eigh3's range rule comes first", "largest magnitude lies beyond 2^+-400 is solved times 2^-+600",
+                   "n does not depend on a power of two in C", "amax > 2^400 multiplies them by 2^-600", "0 < amax < 2^-400 by 2^+600",
+                   "after the ascending order is fixed", "go through as they are, bit for bit",
                    "the same three compare-and-swaps of the order with the strict <", "n is column ord[0] of v, not renormalised",
                    "A zero matrix gives (1, 0, 0)", "n is exactly (0.0, 0.0, 0.0)", "to_a = v_a - (double)x_a",
                    "dt = (n_x*to_x + n_y*to_y) + n_z*to_z", "negated iff dt < 0", "With ICP_ORIENT_NONE nothing is negated",
