@@ -24,6 +24,7 @@ ICP_F32, ICP_F64 = 0, 1
 ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1
 ICP_GENERALIZED = 2   # the generalized (plane-to-plane) metric of a batch that holds covariances
 ICP_COLORED = 3       # the colored metric of a batch that holds model normals, intensities and intensity gradients
+ICP_SYMMETRIC = 4     # the symmetric metric of a batch that holds point normals on both sides
 ICP_COLOR_LAMBDA_DEFAULT = 0.968
 ICP_COV_NONE, ICP_COV_FROBENIUS = 0, 1   # icp_batch_estimate_covariances: the regularisation
 ICP_COV_MIN_NEIGHBOURS, ICP_COV_MAX_NEIGHBOURS = 3, 32
@@ -175,11 +176,13 @@ SIGNATURES = {
     "icp_lcomm_destroy": (None, [_vp]),
     "icp_solve_point_to_point": (_i, [_pd, _pd, _pd]),
     "icp_solve_point_to_plane": (_i, [_pd, _pd, _pd, _pd]),
+    "icp_solve_symmetric": (_i, [_pd, _pd, _pd, _pd]),
     "icp_host_loop_create": (_i, [C.POINTER(icp_params), C.POINTER(_vp)]),
     "icp_host_loop_destroy": (None, [_vp]),
     "icp_host_loop_advance": (_i, [_vp, _pd, _pi, _pd, _pd]),
     "icp_host_loop_note_applied": (_i, [_vp]),
     "icp_host_loop_set_weighted": (_i, [_vp, _i]),
+    "icp_host_loop_set_symmetric": (_i, [_vp, _i]),
     "icp_host_loop_state": (_i, [_vp, _pi, _pi, _pd, _i, _pd]),
     "icp_shard_range": (_i, [C.c_int64, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "icp_share_rows_plan": (_i, [_pu32, _i, _i, _i, _i, _pi32, _pu32]),

@@ -56,7 +56,15 @@
 // decision, then the geometric and the photometric terms of the 6 x 6 system into a plane pass's slots; every pair's HostLoop is
 // begun as a point-to-plane loop.  The other metrics of such a batch run the steps they ran without intensities.
 //
+// And it may hold a unit normal per point on both sides (icp_batch_estimate_point_normals, icp_batch_set_point_normals: what the
+// descriptors are computed from).  icp_batch_begin then takes a fifth metric, ICP_SYMMETRIC (Rusinkiewicz, SIGGRAPH 2019): the
+// generalized metric's route with batch_sym_moments (icp_k_sym.hip) in batch_gicp_moments' place -- the same decision, then the
+// terms of the symmetrized point-to-plane system along n_p + n_q into a plane pass's slots, the moving normal turned by the step's
+// Rc as the generalized metric turns the covariances; every pair's HostLoop is begun as a point-to-plane loop that solves by
+// icp::solve_symmetric (HostLoop::symmetric: two half rotations).  New point normals discard a symmetric loop, and no other.
+//
 //   batch kind             launches of a step
+//   symmetric metric       nn_match_batch<DEFER>, [nn_match_batch_rev,] [batch_trim_select,] batch_sym_moments<MUTUAL?>, batch_finalize_kernel
 //   colored metric         nn_match_batch<DEFER>, [nn_match_batch_rev,] [batch_trim_select,] batch_color_moments<MUTUAL?>, batch_finalize_kernel
 //   generalized metric     nn_match_batch<DEFER>, [nn_match_batch_rev,] [batch_trim_select,] batch_gicp_moments<MUTUAL?>, batch_finalize_kernel
 //   any robust pair        nn_match_batch<DEFER>, [nn_match_batch_rev,] [batch_trim_select,] batch_robust_moments<MUTUAL?>, batch_finalize_kernel
@@ -864,6 +872,7 @@ int step(icp_batch* b)
     icp_ctx* c = b->ctx;
     const int cur = (int)(b->steps & 1);
     const bool generalized = b->metric == ICP_GENERALIZED;
+    const bool rotates = generalized || b->metric == ICP_SYMMETRIC;   // the step uploads Rc: the moving covariances, or the moving point normals, turn with the cloud
     int* mode = reinterpret_cast<int*>(b->h_ctl.as<char>() + b->rt_bytes);
     for (int p = 0; p < b->count; ++p) {
         mode[p] = 0;
@@ -882,7 +891,7 @@ int step(icp_batch* b)
         if (!final_only) {
             b->last_match[p] = cur;
             mode[p] |= icp::BATCH_MATCH;
-            if (generalized) {   // Rc: the rotation of every motion applied to the cloud this pass matches on
+            if (rotates) {   // Rc: the rotation of every motion applied to the cloud this pass matches on
                 double T[16];
                 composed_T(b, p, T);
                 double* R = b->rot.data() + (size_t)p * 9;
@@ -891,8 +900,8 @@ int step(icp_batch* b)
             }
         }
     }
-    if (generalized) std::memcpy(b->h_ctl.as<char>() + b->rot_off, b->rot.data(), b->rot.size() * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(b->ctl.p, b->h_ctl.p, generalized ? b->rot_off + b->rot.size() * sizeof(double) : b->ctl_bytes, hipMemcpyHostToDevice, c->stream));
+    if (rotates) std::memcpy(b->h_ctl.as<char>() + b->rot_off, b->rot.data(), b->rot.size() * sizeof(double));
+    HIP_TRY(hipMemcpyAsync(b->ctl.p, b->h_ctl.p, rotates ? b->rot_off + b->rot.size() * sizeof(double) : b->ctl_bytes, hipMemcpyHostToDevice, c->stream));
     icp::BatchPassArgs a{};
     a.precision = b->prec;
     a.metric = b->metric;
@@ -923,10 +932,14 @@ int step(icp_batch* b)
     a.robust_k = (const double*)b->rob_k.p;
     a.robust_k2 = (const double*)b->rob_k2.p;
     a.weights = (double*)b->weights.p;
+    if (rotates) a.rot = reinterpret_cast<const double*>(static_cast<const char*>(b->ctl.p) + b->rot_off);
     if (generalized) {
         a.cov_p = (const double*)b->cov.buf[0].p;
         a.cov_q = (const double*)b->cov.buf[1].p;
-        a.rot = reinterpret_cast<const double*>(static_cast<const char*>(b->ctl.p) + b->rot_off);
+    }
+    if (b->metric == ICP_SYMMETRIC) {
+        a.nrm_p = (const double*)b->pnrm.buf[0].p;
+        a.nrm_q = (const double*)b->pnrm.buf[1].p;
     }
     if (b->metric == ICP_COLORED) {
         a.int_p = (const double*)b->inten.buf[0].p;
@@ -1149,7 +1162,8 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
 {
     if (int rc = ready(b)) return rc;
     if (!prm) return fail(ICP_ERR_INVALID, "params == NULL");
-    if (prm->metric != ICP_POINT_TO_POINT && prm->metric != ICP_POINT_TO_PLANE && prm->metric != ICP_GENERALIZED && prm->metric != ICP_COLORED)
+    if (prm->metric != ICP_POINT_TO_POINT && prm->metric != ICP_POINT_TO_PLANE && prm->metric != ICP_GENERALIZED && prm->metric != ICP_COLORED &&
+        prm->metric != ICP_SYMMETRIC)
         return fail(ICP_ERR_INVALID, "unknown metric");
     if (prm->metric == ICP_POINT_TO_PLANE && !b->N.have[1])
         return fail(ICP_ERR_INVALID, "a point-to-plane batch needs the model normals: icp_batch_set_model_normals or icp_batch_estimate_normals first");
@@ -1172,17 +1186,26 @@ int icp_batch_begin(icp_batch* b, const icp_params* prm)
         if (!b->color_w_set)
             if (int rc = upload_color_weights(b)) return rc;
     }
+    if (prm->metric == ICP_SYMMETRIC) {
+        if (!b->pnrm.have[0] || !b->pnrm.have[1])
+            return fail(ICP_ERR_INVALID, std::string("a symmetric batch needs point normals on both sides (icp_batch_estimate_point_normals or icp_batch_set_point_normals first): the ") +
+                                             (!b->pnrm.have[0] ? "moving clouds" : "models") + " have none");
+        if (b->robust) return fail(ICP_ERR_INVALID, "the symmetric metric takes no robust kernels (icp_batch_set_robust(NULL) first)");
+        HIP_TRY(b->dist.ensure((size_t)b->p_plane * b->esize));   // (the deferred route's winning distances)
+    }
     if (prm->precision != b->prec) return fail(ICP_ERR_INVALID, "params precision differs from the batch's clouds");
     if (prm->max_iter < 1) return fail(ICP_ERR_INVALID, "max_iter must be >= 1");
     b->begun = false;
     b->metric = prm->metric;
     icp_params hp = *prm;
     if (hp.metric == ICP_COLORED) hp.metric = ICP_POINT_TO_PLANE;   // (the colored metric fills a plane pass's slots: the host loops are point-to-plane loops)
+    if (hp.metric == ICP_SYMMETRIC) hp.metric = ICP_POINT_TO_PLANE;   // (so does the symmetric metric: point-to-plane loops that solve by solve_symmetric)
     for (int p = 0; p < b->count; ++p)
         if (int rc = b->H[p].begin(hp)) return fail(rc, "bad loop parameters");
+    for (int p = 0; p < b->count; ++p) b->H[p].symmetric = prm->metric == ICP_SYMMETRIC;
     // (a generalized pass may keep nothing whatever the options: a match whose det(S) is not > 0 is rejected)
     for (int p = 0; p < b->count; ++p) b->H[p].gated = b->gated || b->trimmed || b->reciprocal || prm->metric == ICP_GENERALIZED;
-    if (prm->metric == ICP_GENERALIZED) b->rot.assign((size_t)b->count * 9, 0.0);
+    if (prm->metric == ICP_GENERALIZED || prm->metric == ICP_SYMMETRIC) b->rot.assign((size_t)b->count * 9, 0.0);
     for (int p = 0; p < b->count; ++p) b->H[p].weighted = b->robust;   // (a NONE pair of a robust batch: W == CNT exactly)
     reset_loop_state(b);
     if (b->have_init) {
@@ -1894,7 +1917,8 @@ int icp_diag_batch_rotation(icp_batch* b, int pair, double* R9)
 {
     if (!b || !R9) return fail(ICP_ERR_INVALID, "null argument");
     if (pair < 0 || pair >= b->count) return fail(ICP_ERR_INVALID, "pair out of range");
-    if (!b->begun || b->metric != ICP_GENERALIZED || !b->tau_seen[pair]) return fail(ICP_ERR_STATE, "no completed matching pass of this pair in a generalized loop");
+    if (!b->begun || (b->metric != ICP_GENERALIZED && b->metric != ICP_SYMMETRIC) || !b->tau_seen[pair])
+        return fail(ICP_ERR_STATE, "no completed matching pass of this pair in a generalized or a symmetric loop");
     std::memcpy(R9, b->rot.data() + (size_t)pair * 9, 9 * sizeof(double));
     return ICP_OK;
 }
@@ -2282,6 +2306,7 @@ int icp_batch_estimate_point_normals(icp_batch* b, int orient, const double* mov
         a.cov[sd] = (const double*)b->cov.buf[sd].p;
         a.nrm[sd] = (double*)b->pnrm.buf[sd].p;
     }
+    if (b->metric == ICP_SYMMETRIC) b->begun = false;   // a symmetric loop under way is discarded: its passes so far read other normals
     HIP_TRY(icp::launch_batch_point_normals(a, st));
     b->pnrm.have[0] = b->pnrm.have[1] = true;
     if (orient == ICP_ORIENT_CENTROID) b->have_cent = true;
@@ -2296,7 +2321,8 @@ int icp_batch_set_point_normals(icp_batch* b, const double* moving_normals, cons
     const void* const given[2] = {moving_normals, model_normals};
     if (!given[0] && !given[1]) return fail(ICP_ERR_INVALID, "moving_normals == NULL and model_normals == NULL");
     if (int rc = attr_reserve(b, b->pnrm, given, "a normal")) return rc;
-    return attr_commit(b, b->pnrm, given);   // (the loop does not read them: one under way goes on)
+    if (b->metric == ICP_SYMMETRIC) b->begun = false;   // a symmetric loop under way is discarded: its passes so far read other normals
+    return attr_commit(b, b->pnrm, given);   // (no other loop reads them: one under way goes on)
 }
 
 int icp_batch_get_point_normals(icp_batch* b, double* moving_normals_out, double* model_normals_out)

@@ -82,8 +82,10 @@ int HostLoop::advance(const double* mom)
             mom = wmom;
         }
         // (the generalized metric fills a plane pass's slots with its own 6 x 6 system: the same solve)
-        const int rc = prm.metric != ICP_POINT_TO_POINT ? solve_point_to_plane(mom, R, t, nullptr)
-                                                        : solve_point_to_point(mom, R, t);
+        // (the symmetric metric fills them with the system of its two half rotations: the same Cholesky, its own rotation)
+        const int rc = prm.metric == ICP_POINT_TO_POINT ? solve_point_to_point(mom, R, t)
+                       : symmetric                      ? solve_symmetric(mom, R, t, nullptr)
+                                                        : solve_point_to_plane(mom, R, t, nullptr);
         if (rc != ICP_OK) {
             done = true;
             return rc;
@@ -142,6 +144,13 @@ int icp_host_loop_set_weighted(icp_host_loop* h, int on)
 {
     if (!h) return ICP_ERR_INVALID;
     h->H.weighted = on != 0;
+    return ICP_OK;
+}
+
+int icp_host_loop_set_symmetric(icp_host_loop* h, int on)
+{
+    if (!h) return ICP_ERR_INVALID;
+    h->H.symmetric = on != 0;
     return ICP_OK;
 }
 

@@ -17,6 +17,7 @@ struct HostLoop {
     double n_total = 0.0; // moving points that contributed to the latest matching pass (summed over ranks)
     bool gated = false;   // set after begin(): a matching pass may keep no point, which ends the loop with ICP_ERR_EMPTY
     bool weighted = false; // set after begin(): the vectors are a robust pass's -- the solve reads ICP_MOM_W where it read ICP_MOM_CNT, and a matching pass of weight sum 0 ends the loop with ICP_ERR_EMPTY
+    bool symmetric = false; // set after begin(): the vectors are a symmetric pass's -- the plane solve's system, solved by solve_symmetric (two half rotations)
     double R[9], t[3], T[16];
     std::vector<double> err;
 

@@ -147,8 +147,8 @@ int solve_rigid(const double* mom, double* R, double* t)
     return ICP_OK;
 }
 
-// Upper Cholesky C = Ut*U of the 6x6 SPD matrix given by its upper triangle (row-major packed, 21).
-int solve_point_to_plane(const double* mom, double* R, double* t, double* x6)
+// Upper Cholesky C = Ut*U of the 6x6 SPD matrix given by its upper triangle (row-major packed, 21), then Ut y = b and U x = y.
+static int cholesky6_solve(const double* mom, double x[6])
 {
     double Uc[6][6];
     {
@@ -168,7 +168,7 @@ int solve_point_to_plane(const double* mom, double* R, double* t, double* x6)
             Uc[k][c] = s / d;
         }
     }
-    double y[6], x[6];
+    double y[6];
     for (int i = 0; i < 6; ++i) {  // Ut y = b
         double s = mom[ICP_MOM_B + i];
         for (int r = 0; r < i; ++r) s -= Uc[r][i] * y[r];
@@ -179,6 +179,13 @@ int solve_point_to_plane(const double* mom, double* R, double* t, double* x6)
         for (int c = i + 1; c < 6; ++c) s -= Uc[i][c] * x[c];
         x[i] = s / Uc[i][i];
     }
+    return ICP_OK;
+}
+
+int solve_point_to_plane(const double* mom, double* R, double* t, double* x6)
+{
+    double x[6];
+    if (int rc = cholesky6_solve(mom, x)) return rc;
     if (x6) std::memcpy(x6, x, sizeof x);
     const double cx = std::cos(x[0]), cy = std::cos(x[1]), cz = std::cos(x[2]);
     const double sx = std::sin(x[0]), sy = std::sin(x[1]), sz = std::sin(x[2]);
@@ -187,6 +194,33 @@ int solve_point_to_plane(const double* mom, double* R, double* t, double* x6)
     R[3] = cy * sz; R[4] = cx * cz + sx * sy * sz; R[5] = cx * sy * sz - cz * sx;
     R[6] = -sy;     R[7] = cy * sx;                R[8] = cx * cy;
     t[0] = x[3]; t[1] = x[4]; t[2] = x[5];
+    return ICP_OK;
+}
+
+// The symmetric metric's step (include/icp_mi355x.h, "the symmetric metric"): x = (a, tt) from the plane solve's Cholesky, a the axis
+// times tan(theta), tt the translation over cos(theta); Ra the rotation by theta = atan(|a|) about a, without trigonometry and
+// without a division by |a|; the motion p -> Ra (Ra p + t'), t' = c tt, as R = Ra Ra and t = Ra t'.
+int solve_symmetric(const double* mom, double* R, double* t, double* x6)
+{
+    double x[6];
+    if (int rc = cholesky6_solve(mom, x)) return rc;
+    for (int i = 0; i < 6; ++i)
+        if (!std::isfinite(x[i])) return ICP_ERR_SINGULAR;
+    const double a[3] = {x[0], x[1], x[2]};
+    const double l2 = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
+    if (!std::isfinite(l2)) return ICP_ERR_SINGULAR;
+    if (x6) std::memcpy(x6, x, sizeof x);
+    const double c = 1.0 / std::sqrt(1.0 + l2), k = (c * c) / (1.0 + c);
+    const double E[3][3] = {{1.0, -a[2], a[1]}, {a[2], 1.0, -a[0]}, {-a[1], a[0], 1.0}};   // I + [a]x
+    double Ra[3][3], tp[3];
+    for (int r = 0; r < 3; ++r) {
+        for (int s = 0; s < 3; ++s) Ra[r][s] = c * E[r][s] + k * (a[r] * a[s]);
+        tp[r] = c * x[3 + r];
+    }
+    for (int r = 0; r < 3; ++r) {
+        for (int s = 0; s < 3; ++s) R[r * 3 + s] = (Ra[r][0] * Ra[0][s] + Ra[r][1] * Ra[1][s]) + Ra[r][2] * Ra[2][s];
+        t[r] = (Ra[r][0] * tp[0] + Ra[r][1] * tp[1]) + Ra[r][2] * tp[2];
+    }
     return ICP_OK;
 }
 
@@ -276,6 +310,11 @@ int icp_solve_point_to_plane(const double* mom, double* R9, double* t3, double* 
 {
     if (!mom || !R9 || !t3) return ICP_ERR_INVALID;
     return icp::solve_point_to_plane(mom, R9, t3, x6);
+}
+int icp_solve_symmetric(const double* mom, double* R9, double* t3, double* x6)
+{
+    if (!mom || !R9 || !t3) return ICP_ERR_INVALID;
+    return icp::solve_symmetric(mom, R9, t3, x6);
 }
 int icp_shard_range(int64_t n, int rank, int world, int64_t* begin, int64_t* count)
 {

@@ -579,10 +579,11 @@ hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st)
     if (a.trim_rank && (!a.dist || !a.tau)) return hipErrorInvalidValue;
     if (a.recip && (!a.dist || !a.rev || !a.q_items || a.n_q_items <= 0)) return hipErrorInvalidValue;
     if (a.robust_kind && (!a.robust_k || !a.robust_k2 || !a.weights || !a.dist)) return hipErrorInvalidValue;
-    if (a.metric == ICP_GENERALIZED || a.metric == ICP_COLORED) {
+    if (a.metric == ICP_GENERALIZED || a.metric == ICP_COLORED || a.metric == ICP_SYMMETRIC) {
         // the generalized metric: matching without a decision (the point-to-point instantiation), [the reverse search,] [the K-th
         // distance of every pair,] then batch_gicp_moments (icp_k_gicp.hip): the decision and the terms of the 6 x 6 system.  The
-        // colored metric: the same launches with batch_color_moments (icp_k_color.hip) in its place
+        // colored metric: the same launches with batch_color_moments (icp_k_color.hip) in its place; the symmetric metric: with
+        // batch_sym_moments (icp_k_sym.hip)
         if (a.robust_kind || !a.dist) return hipErrorInvalidValue;
 #define ICP_LAUNCH_BATCH_GICP(F)                                                                                                 \
     do {                                                                                                                         \
@@ -599,7 +600,11 @@ hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st)
         if (a.precision == ICP_F64) ICP_LAUNCH_BATCH_GICP(double); else ICP_LAUNCH_BATCH_GICP(float);
 #undef ICP_LAUNCH_BATCH_GICP
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        if (hipError_t e = a.metric == ICP_COLORED ? launch_batch_color_moments(a, st) : launch_batch_gicp_moments(a, st); e != hipSuccess) return e;
+        if (hipError_t e = a.metric == ICP_COLORED     ? launch_batch_color_moments(a, st)
+                           : a.metric == ICP_SYMMETRIC ? launch_batch_sym_moments(a, st)
+                                                       : launch_batch_gicp_moments(a, st);
+            e != hipSuccess)
+            return e;
         hipLaunchKernelGGL(batch_finalize_kernel, dim3(a.n_pairs), dim3(256), 0, st, a.pairs, a.mode, (const double*)a.partials,
                            ICP_MOM_B + 5, a.mom);
         return hipGetLastError();

@@ -376,12 +376,19 @@ struct BatchPassArgs {
     const double* int_q;       // double[q_plane]: every model point's intensity, laid out as the models
     const double* grad_q;      // double[3][q_plane]: every model point's intensity gradient
     const double* color_w;     // double[n_pairs]: lambda, the weight of the geometric term, in [0, 1]
+    // metric == ICP_SYMMETRIC (never with robust_kind): the generalized metric's launches with batch_sym_moments<.., MUTUAL = recip
+    // given> (icp_k_sym.hip) in batch_gicp_moments' place: kept as batch_trim_moments decides it, the terms of the symmetric 6 x 6
+    // system into a plane pass's slots; the reduction runs to ICP_MOM_B + 5.  rot is the generalized metric's.
+    const double* nrm_p;       // double[3][p_plane]: every moving point's unit normal, in the frame of the cloud as uploaded
+    const double* nrm_q;       // double[3][q_plane]: every model point's unit normal
 };
 hipError_t launch_batch_pass(const BatchPassArgs& a, hipStream_t st);
 // batch_gicp_moments alone, on the buffers the deferred launches of launch_batch_pass left (called by it; icp_k_gicp.hip)
 hipError_t launch_batch_gicp_moments(const BatchPassArgs& a, hipStream_t st);
 // batch_color_moments alone, likewise (icp_k_color.hip)
 hipError_t launch_batch_color_moments(const BatchPassArgs& a, hipStream_t st);
+// batch_sym_moments alone, likewise (icp_k_sym.hip)
+hipError_t launch_batch_sym_moments(const BatchPassArgs& a, hipStream_t st);
 // evaluation of every pair whose mode is BATCH_MATCH at its present pose (icp_batch_evaluate): the deferred matching launch
 // (point-to-point instantiation whatever the metric, P only read) -> idx, dist; batch_eval_moments: kept = d <= thr[pair], rejected
 // matches marked in idx, the ICP_EVAL_* terms of the kept ones -> partials; batch_finalize_kernel -> mom[pair][ICP_NMOM] (pairs of

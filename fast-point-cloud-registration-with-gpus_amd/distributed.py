@@ -48,6 +48,10 @@ class HostLoop:
     def note_applied(self):
         capi.check(self._lib.icp_host_loop_note_applied(self._h), "icp_host_loop_note_applied")
 
+    def set_symmetric(self, on):
+        """the vectors are a symmetric pass's (icp_host_loop_set_symmetric): a point-to-plane loop solves by icp_solve_symmetric"""
+        capi.check(self._lib.icp_host_loop_set_symmetric(self._h, 1 if on else 0), "icp_host_loop_set_symmetric")
+
     def set_weighted(self, on):
         """the vectors are a robust pass's (icp_host_loop_set_weighted): solve with ICP_MOM_W in the place of ICP_MOM_CNT"""
         capi.check(self._lib.icp_host_loop_set_weighted(self._h, 1 if on else 0), "icp_host_loop_set_weighted")

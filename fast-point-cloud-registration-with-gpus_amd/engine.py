@@ -388,6 +388,34 @@ class Context:
                                        options.get("max_distance"), options.get("init"), options.get("trim"), options.get("reciprocal"), None,
                                        prepare=prepare)
 
+    def register_batch_symmetric(self, pairs, k=20, orient="centroid", normals=None, **options):
+        """register_batch with the symmetric metric (Rusinkiewicz, SIGGRAPH 2019; Batch.begin with ICP_SYMMETRIC): every kept match
+        pulls along the sum of the two points' own normals and the step is split into two half rotations, so the residual vanishes
+        wherever the two points lie on a common second-order patch -- a wider basin than point-to-plane's after a rough start, and
+        no bias from the two clouds sampling the surface differently.  normals = (moving, model): per side one (points, 3) float64
+        array of unit normals per pair (Batch.set_point_normals; their signs need not agree), or None: estimated on the device
+        from the covariances of k neighbours (Batch.estimate_covariances(k): a scalar or one value per pair, both sides) and
+        oriented by orient (Batch.estimate_point_normals).  options: register_batch's, by keyword, without metric and normals;
+        robust kernels are not combined with this metric.  The same list of Result as register_batch."""
+        unknown = set(options) - {"max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal"}
+        if unknown:
+            raise TypeError(f"register_batch_symmetric: unknown option(s) {sorted(unknown)}")
+        max_iter = options.get("max_iter")
+        if max_iter is None:
+            max_iter = 50
+
+        def prepare(bt):
+            if normals is not None:
+                moving, model = normals
+                bt.set_point_normals(moving, model)
+            else:
+                bt.estimate_covariances(k)
+                bt.estimate_point_normals(orient)
+
+        return self._run_batch_options(capi.ICP_SYMMETRIC, pairs, None, max_iter, options.get("tol", 1e-6), options.get("fixed_iterations", False),
+                                       options.get("max_distance"), options.get("init"), options.get("trim"), options.get("reciprocal"), None,
+                                       prepare=prepare)
+
     def register_batch_global(self, pairs, voxel, k, hypotheses, max_distance, **options):
         """register_batch for pairs in unknown relative pose: a start pose from descriptors first, then the local loop from it.
         The pairs are uploaded once; a copy thinned at voxel (Batch.downsample; 0 or None: the clouds themselves) gets raw
@@ -543,7 +571,8 @@ class Context:
 
     def _run_batch_options(self, metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init, trim, reciprocal, robust, prepare=None):
         """... and robust: None, or (kernel, scale) for set_robust -- the results then carry extra["weights"]; prepare: None, or a
-        callable that gives the new Batch what its metric needs beyond normals (the colored metric's intensities and gradients)"""
+        callable that gives the new Batch what its metric needs beyond normals (the colored metric's intensities and gradients, the
+        symmetric metric's point normals)"""
         with Batch(self, pairs) as bt:
             if prepare is not None:
                 prepare(bt)
@@ -1053,8 +1082,8 @@ class Batch:
         capi.check(self._lib.icp_batch_set_color_weight(self._h, a.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_color_weight")
 
     def diag_rotation(self, b):
-        """(3, 3): the rotation pair b's most recent matching pass of a generalized loop rotated its moving covariances by
-        (icp_diag_batch_rotation)"""
+        """(3, 3): the rotation pair b's most recent matching pass of a generalized loop rotated its moving covariances by, or of
+        a symmetric loop its moving point normals (icp_diag_batch_rotation)"""
         R = np.zeros(9)
         capi.check(self._lib.icp_diag_batch_rotation(self._h, int(b), R.ctypes.data_as(C.POINTER(C.c_double))), "icp_diag_batch_rotation")
         return R.reshape(3, 3)
@@ -1372,7 +1401,8 @@ class Batch:
     def begin(self, max_iter=40, tol=1e-6, fixed_iterations=False, metric=capi.ICP_POINT_TO_POINT):
         """start every pair's registration from the uploaded clouds, moved by the pair's initial transform where the batch holds
         any (ICP_POINT_TO_PLANE: the batch must hold normals; ICP_GENERALIZED: covariances on both sides and no robust kernel;
-        ICP_COLORED: normals, intensities on both sides, intensity gradients and no robust kernel)"""
+        ICP_COLORED: normals, intensities on both sides, intensity gradients and no robust kernel; ICP_SYMMETRIC: point normals on
+        both sides -- estimate_point_normals or set_point_normals -- and no robust kernel; new point normals discard such a loop)"""
         prm = capi.icp_params(int(max_iter), float(tol), 1 if fixed_iterations else 0, _prec(self._dtype), int(metric))
         capi.check(self._lib.icp_batch_begin(self._h, C.byref(prm)), "icp_batch_begin")
         self._max_iter = int(max_iter)
@@ -1535,6 +1565,18 @@ def solve_point_to_plane(mom):
     pd = C.POINTER(C.c_double)
     capi.check(lib.icp_solve_point_to_plane(mom.ctypes.data_as(pd), R.ctypes.data_as(pd), t.ctypes.data_as(pd),
                                             x.ctypes.data_as(pd)), "icp_solve_point_to_plane")
+    return R.reshape(3, 3), t, x
+
+
+def solve_symmetric(mom):
+    """the symmetric metric's step from a pass's vector (icp_solve_symmetric): (R, t, x), x = (a, tt) as solved, R = Ra Ra and
+    t = Ra (c tt) with Ra the rotation by atan(|a|) about a"""
+    lib = capi.load()
+    mom = np.ascontiguousarray(mom, dtype=np.float64)
+    R, t, x = np.zeros(9), np.zeros(3), np.zeros(6)
+    pd = C.POINTER(C.c_double)
+    capi.check(lib.icp_solve_symmetric(mom.ctypes.data_as(pd), R.ctypes.data_as(pd), t.ctypes.data_as(pd),
+                                       x.ctypes.data_as(pd)), "icp_solve_symmetric")
     return R.reshape(3, 3), t, x
 
 

@@ -843,6 +843,47 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *         j2 = (-py, px, 0), j3, j4, j5 the unit vectors; G_a = dot(j_a, n), K_a = dot(j_a, m).  lg = lambda[pair], lp = 1.0 - lg.
  *         Slot C(a, c) += lg*(G_a*G_c) + lp*(K_a*K_c) for a <= c; slot B(a) -= lg*(G_a*h) + lp*(K_a*rI); ICP_MOM_CNT = 1.
  *         With lg == 1 these are the plane pass's statements.  A pair's bits depend on that pair and its options alone.
+ *   - the symmetric metric (ICP_SYMMETRIC; Rusinkiewicz, "A Symmetric Objective Function for ICP", SIGGRAPH 2019; PCL's
+ *     TransformationEstimationSymmetricPointToPlaneLLS): the point-to-plane objective made symmetric in the two clouds.  Every kept
+ *     match pulls along n_p + n_q, the sum of the two points' own normals, and the step is split into two half rotations.  The
+ *     residual then vanishes wherever the two points lie on a common second-order patch, not only on a common plane: a wider
+ *     basin after a rough global pose, and no bias from the two clouds sampling the surface differently.  It reads the point
+ *     normals the batch holds on both sides (icp_batch_estimate_point_normals, icp_batch_set_point_normals: three doubles per
+ *     point, in the frame of the cloud as uploaded) and nothing else.
+ *       icp_batch_begin with ICP_SYMMETRIC needs point normals on both sides (ICP_ERR_INVALID without; the message names the side
+ *         and the two calls that provide them), and a batch that holds robust kernels refuses this metric with ICP_ERR_INVALID,
+ *         as it refuses ICP_GENERALIZED and ICP_COLORED.  It combines with gate, trim, reciprocity and initial transforms.  Every
+ *         pair's host loop is a point-to-plane loop that solves by icp_solve_symmetric (icp_host_loop_set_symmetric).
+ *         icp_host_loop_create, icp_batch_evaluate, the single-pair loops (icp_loop_begin, icp_point_to_*) and the one-call
+ *         icp_point_to_*_batch refuse the value as any unknown metric.
+ *       while a symmetric loop is under way icp_batch_set_point_normals and icp_batch_estimate_point_normals discard it
+ *         (icp_batch_run: ICP_ERR_STATE until the next icp_batch_begin); under any other loop they leave it running, as before.
+ *       a step always runs deferred: the point-to-point matching launch, [the reverse search,] [the trim's selection,]
+ *         batch_sym_moments, the reduction up to ICP_MOM_B + 5 -- three launches, up to five, one download.  The kept decision
+ *         is the one of every deferred batch: gate, tau over all n distances, the mutual rule.  Front end, ICP_MOM_ERR (Euclidean,
+ *         over the points the previous matching pass kept), the err series, the stop rule, idx, masks, initial transforms and
+ *         the ICP_ERR_EMPTY / ICP_ERR_SINGULAR handling are those of the other metrics.  A rejected point's idx entry carries
+ *         the rejection in its top bit.
+ *       terms of a kept match of moving point i to model point j.  Every operation is one IEEE double operation, nothing is
+ *         fused, and the only functions used are + - *.  dot(a, b) = (a0*b0 + a1*b1) + a2*b2.  p is the widened moved point, q
+ *         the widened model point; m0 the stored point normal of i, in the frame of the cloud as uploaded; nq the stored point
+ *         normal of j; Rc = the 3 x 3 of the pair's composed T at this pass, what the generalized step uploads
+ *         (icp_diag_batch_rotation reads it).  np_a = dot(Rc[a], m0): on the first pass of a pair without an initial transform Rc
+ *         is the identity and np == m0 bit for bit.  s = dot(np, nq); n_a = s < 0 ? nq_a - np_a : nq_a + np_a -- the sign rule
+ *         is always on: PCA normals have no sign of their own, and ICP_ORIENT_NONE is allowed (PCL's
+ *         enforce_same_direction_normals).  e = p - q, g = p + q componentwise, h = dot(e, n).  v0 = g1*n2 - g2*n1,
+ *         v1 = g2*n0 - g0*n2, v2 = g0*n1 - g1*n0, v3..5 = n.  Slot C(a, c) += v_a*v_c for a <= c; slot B(a) -= v_a*h;
+ *         ICP_MOM_CNT = 1.  A kept match whose n is exactly zero counts and adds zeros: the stored fallback normal (0, 0, 0) on
+ *         both sides gives such a match.  The points are not centred: the cosine and sine terms of the linearization are exact
+ *         about any origin, and the dropped term depends only on p - q.  A pair's bits depend on that pair and its options
+ *         alone: no atomics, the fixed summation order of the other metrics.
+ *       solve (icp_solve_symmetric, below): x from icp_solve_point_to_plane's Cholesky of the same slots, with the same
+ *         ICP_ERR_SINGULAR; a solution that is not finite, or whose l2 is not finite, is ICP_ERR_SINGULAR too.  a = x[0..2] is the
+ *         axis times tan(theta), tt = x[3..5] the translation over cos(theta).  With no trigonometry and no division by |a|:
+ *         l2 = (a0*a0 + a1*a1) + a2*a2, c = 1.0 / sqrt(1.0 + l2), k = (c*c) / (1.0 + c); Ra_ab = c*E_ab + k*(a_a*a_b), where
+ *         E = I + [a]x holds 1, 0 or a signed component of a (E01 = -a2, E02 = a1, E10 = a2, E12 = -a0, E20 = -a1, E21 = a0);
+ *         t'_a = c*tt_a; R = Ra Ra and t = Ra t', each entry a dot of a row with a column.  Ra is the exact rotation by
+ *         theta = atan(|a|) about a: the motion is p -> Ra (Ra p + t'), and a = 0 gives the identity.
      Not gated, not trimmed and without an initial transform: the single-pair loops (icp_point_to_*, icp_loop_*) and the
  *     multi-GPU sums -- a single pair that needs any of them is a batch of one; nor do they weigh matches by a robust kernel.  Trimming is the only rejection by rank: there
  *     is no other percentile rejection (none by a multiple of the median or of the standard deviation of the distances). */
@@ -863,7 +904,8 @@ int icp_batch_set_model_normals(icp_batch* b, const void* nxyz_aos);
 int icp_batch_estimate_normals(icp_batch* b, void* nxyz_aos_out, int32_t* neighbours_out);
 /* prm->precision must be the batch's; prm->metric ICP_POINT_TO_POINT, or ICP_POINT_TO_PLANE on a batch that holds normals, or
  * ICP_GENERALIZED on a batch that holds covariances on both sides and no robust kernel, or ICP_COLORED on a batch that holds model
- * normals, intensities on both sides, intensity gradients and no robust kernel */
+ * normals, intensities on both sides, intensity gradients and no robust kernel, or ICP_SYMMETRIC on a batch that holds point
+ * normals on both sides and no robust kernel */
 int icp_batch_begin(icp_batch* b, const icp_params* prm);
 /* up to max_steps passes for every pair still running; *active (optional) = pairs not yet done */
 int icp_batch_run(icp_batch* b, int max_steps, int* steps_done, int* active);
@@ -949,6 +991,8 @@ int icp_batch_set_intensity_gradients(icp_batch* b, const double* grad);
 int icp_batch_get_intensity_gradients(icp_batch* b, double* grad_out);
 /* count doubles in [0, 1]: the weight of the geometric term; NULL: ICP_COLOR_LAMBDA_DEFAULT for every pair */
 int icp_batch_set_color_weight(icp_batch* b, const double* lambda);
+/* the symmetric metric (above): prm->metric of icp_batch_begin on a batch that holds point normals on both sides */
+#define ICP_SYMMETRIC 4                       /* fifth value of icp_metric */
 /* global registration (above).  k_*: count ints each; *_normals: 3 doubles per point, laid out as the clouds; the outputs
  * (ICP_FEATURE_BINS doubles per point) may be NULL */
 #define ICP_FEATURE_BINS 33
@@ -1046,6 +1090,10 @@ int icp_solve_rigid(const double* mom /*ICP_NMOM*/, double* R9, double* t3);
  * and LAPACKE_ssysv (CPU_ICP_point_to-plane.cpp:371); x = (alpha,beta,gamma,tx,ty,tz), then the
  * full (non-linearised) R = Rz(gamma) Ry(beta) Rx(alpha) (src/ICP_point_to_plane.cu:585-593). */
 int icp_solve_point_to_plane(const double* mom /*ICP_NMOM*/, double* R9, double* t3, double* x6);
+/* the symmetric metric's step (the rule: "the symmetric metric" above): the same Cholesky of the same slots, x = (a, tt) into x6
+ * (may be NULL) as solved, then R = Ra Ra and t = Ra (c tt) with Ra the rotation by atan(|a|) about a.  ICP_ERR_SINGULAR as
+ * icp_solve_point_to_plane, and where x or |a|^2 is not finite; ICP_ERR_INVALID where mom, R9 or t3 is NULL. */
+int icp_solve_symmetric(const double* mom /*ICP_NMOM*/, double* R9, double* t3, double* x6);
 /* The host half of the loops above as a device-free state machine (the device loop runs this very
  * code): feed it the rank-reduced ICP_NMOM vector of each pass, it returns the stop decision and the
  * next R, t; tell it when that motion has been applied.  Sequence per pass:
@@ -1060,6 +1108,10 @@ int icp_host_loop_note_applied(icp_host_loop* h);
  * not > 0 ends the loop with ICP_ERR_EMPTY.  The error, its divisor (the kept count), the stop rule and the iteration counting
  * do not change.  Off (the default): the loop is the one it always was. */
 int icp_host_loop_set_weighted(icp_host_loop* h, int on);
+/* on != 0: the vectors are those of a symmetric pass -- every advance of a point-to-plane loop from now on solves by
+ * icp_solve_symmetric where it solved by icp_solve_point_to_plane.  Everything else is unchanged.  Off (the default): the loop is
+ * the one it always was. */
+int icp_host_loop_set_symmetric(icp_host_loop* h, int on);
 int icp_host_loop_state(icp_host_loop* h, int* iterations, int* passes, double* err, int err_cap, double* T16);
 /* contiguous shard [begin, begin+count) of n moving points for `rank` of `world`.  Any partition of the moving points is the same
  * registration, and a registration is as slow as its slowest rank: where the work per point varies over a LARGE cloud (BASELINE

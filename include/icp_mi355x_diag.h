@@ -115,7 +115,8 @@ int icp_diag_batch_eval_moments(icp_batch* b, int pair, double* out32);
 /* the generalized metric (ICP_GENERALIZED): the 9 doubles, row-major, of the rotation Rc that pair `pair`'s most recent matching
  * pass rotated the moving covariances by -- the rotation part of the product of every motion applied to the cloud that pass
  * matched on, the initial transform included (the upper left 3 x 3 of icp_batch_state's T at that pass).  A host copy of what
- * the step uploaded: nothing is downloaded.  ICP_ERR_STATE unless a generalized loop is under way and the pair has completed
+ * the step uploaded: nothing is downloaded.  A symmetric loop (ICP_SYMMETRIC) answers too: its passes rotate the moving point
+ * normals by the same Rc.  ICP_ERR_STATE unless a generalized or a symmetric loop is under way and the pair has completed
  * a matching pass. */
 int icp_diag_batch_rotation(icp_batch* b, int pair, double* R9);
 

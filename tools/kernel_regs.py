@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""register / scratch / LDS use of every kernel in build/icp_k_*.s, build/gicp_k.s, build/feat_k.s, build/color_k.s, build/keypoint_k.s and build/normals_k.s
+"""register / scratch / LDS use of every kernel in build/icp_k_*.s, build/gicp_k.s, build/feat_k.s, build/color_k.s, build/keypoint_k.s, build/normals_k.s and build/sym_k.s
 (optionally filtered by a substring).
 build/feat_k.s holds the descriptor, matching and scoring kernels and those of Fast Global Registration: `kernel_regs.py fgr` lists
 batch_fgr_terms<F, false / true> and batch_fgr_finalize"""
@@ -9,7 +9,8 @@ import sys
 
 import glob
 paths = sorted(glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/icp_k_*.s") + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/gicp_k.s") + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/feat_k.s") + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/color_k.s")
-               + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/keypoint_k.s") + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/normals_k.s"))
+               + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/keypoint_k.s") + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/normals_k.s")
+               + glob.glob("fast-point-cloud-registration-with-gpus_amd/csrc/build/sym_k.s"))
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
 s = "".join(open(p).read() for p in paths)
 rows = []
