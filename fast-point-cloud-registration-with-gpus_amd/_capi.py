@@ -36,6 +36,7 @@ ICP_BATCH_MAX_POINTS = 65536   # per cloud of one pair of a batch
 ICP_OUTLIER_NONE, ICP_OUTLIER_STATISTICAL, ICP_OUTLIER_RADIUS = 0, 1, 2   # icp_outlier_rule.kind
 ICP_OUTLIER_MAX_NEIGHBOURS = 32
 ICP_KEYPOINT_NONE, ICP_KEYPOINT_ISS = 0, 1   # icp_keypoint_rule.kind
+ICP_PLANE_NONE, ICP_PLANE_DETECT, ICP_PLANE_REMOVE, ICP_PLANE_KEEP = 0, 1, 2, 3   # icp_plane_rule.kind
 ICP_ORIENT_NONE, ICP_ORIENT_VIEWPOINT, ICP_ORIENT_CENTROID = 0, 1, 2   # icp_batch_estimate_point_normals: the orientation
 # icp_diag_loop_moments: how the vector came about (include/icp_mi355x_diag.h)
 ROUTE_HOST_ROWS, ROUTE_COMPACT, ROUTE_AVX, ROUTE_FIN_LAUNCH, ROUTE_FIN_PINNED, ROUTE_FIN_KERNEL = 0x001, 0x002, 0x004, 0x008, 0x010, 0x020
@@ -64,6 +65,10 @@ class icp_outlier_rule(C.Structure):
 class icp_keypoint_rule(C.Structure):
     _fields_ = [("kind", C.c_int), ("min_neighbours", C.c_int), ("salient_radius", C.c_double), ("non_max_radius", C.c_double),
                 ("gamma_21", C.c_double), ("gamma_32", C.c_double)]
+
+
+class icp_plane_rule(C.Structure):
+    _fields_ = [("kind", C.c_int), ("hypotheses", C.c_int), ("distance", C.c_double), ("axis", C.c_double * 3), ("min_cos", C.c_double)]
 
 
 class icp_ransac_params(C.Structure):
@@ -145,6 +150,10 @@ SIGNATURES = {
     "icp_batch_get_offsets": (_i, [_vp, _pi64, _pi64]),
     "icp_batch_remove_outliers": (_i, [_vp, C.POINTER(icp_outlier_rule), C.POINTER(icp_outlier_rule), _pi32, _pi32, _pd, _pd, _pd, C.POINTER(_vp)]),
     "icp_batch_select_keypoints": (_i, [_vp, C.POINTER(icp_keypoint_rule), C.POINTER(icp_keypoint_rule), _pi32, _pi32, _pd, _pd, _pi32, C.POINTER(_vp)]),
+    "icp_batch_segment_plane": (_i, [_vp, C.POINTER(icp_plane_rule), C.POINTER(icp_plane_rule), C.POINTER(C.c_uint64), _pd, _pi32, _pi,
+                                     C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _pi32, _pi32, C.POINTER(_vp)]),
+    "icp_plane_from_points": (_i, [_pd, _pd]),
+    "icp_plane_from_moments": (_i, [_pd, _pd, _pd]),
     "icp_batch_get_clouds": (_i, [_vp, _vp, _vp]),
     "icp_batch_set_covariances": (_i, [_vp, _pd, _pd]),
     "icp_batch_estimate_covariances": (_i, [_vp, _pi, _pi, _i, C.c_double, _pd, _pd]),
@@ -199,6 +208,7 @@ SIGNATURES = {
     "icp_diag_batch_fgr": (_i, [_vp, _i, _pi32, _pd, _pd, _pd]),
     "icp_diag_batch_fgr_times": (_i, [_vp, _pd]),
     "icp_diag_batch_centroids": (_i, [_vp, _pd]),
+    "icp_diag_batch_segment": (_i, [_vp, _i, _i, _pi32, C.POINTER(C.c_uint8), _pd, _pi32]),
     "icp_solve_rigid": (_i, [_pd, _pd, _pd]),
     "icp_eigh3": (_i, [_pd, _pd, _pd]),
     "icp_synthetic_grid_f32": (_i, [_i, C.c_float, C.c_float, _vp]),

@@ -91,6 +91,10 @@
 //   icp_batch_select_keypoints  ISS keypoints (icp_k_keypoint.hip): batch_iss_saliency, batch_iss_select, batch_keypoint_rank  ->
 //                               batch_keypoint_compact (coordinates, and the kept points' descriptors where the source holds descriptors,
 //                               so that matching and RANSAC or FGR run on a few hundred points per cloud)
+//   icp_batch_segment_plane     the dominant plane of every cloud, removed or kept (icp_k_segment.hip): the hypotheses are drawn and solved
+//                               on the host from the downloaded clouds, as the RANSAC's are, and scored by batch_plane_score, kPlaneChunk
+//                               per cloud and launch; batch_plane_refit, the eigenvector on the host, batch_plane_decide  ->  the outlier
+//                               call's compaction.  Three more waits than the others: the clouds, the counts, the refit's moments
 //
 // A start pose for pairs in unknown relative pose (global registration; the rules, which numpy reproduces bit for bit, are stated in
 // include/icp_mi355x.h; kernels: icp_k_feat.hip): icp_batch_compute_features (batch_spfh_kernel -> batch_fpfh_kernel, one block
@@ -234,6 +238,12 @@ struct __attribute__((visibility("hidden"))) icp_batch {   // (the public header
     std::vector<std::vector<int32_t>> fg_used;   // ... the used list positions
     std::vector<double> fg_mu, fg_mom, fg_T; // ... and per iteration mu, the vector (ICP_NMOM) and the pose the terms were formed at (16)
     double fg_sec[4] = {0, 0, 0, 0};         // ... and the host's seconds in the iterations: enqueue (fill, upload, launches, download), wait, solve; the iterations run
+    // plane segmentation (icp_batch_segment_plane): the last call's hypotheses per cloud (2 * count, the moving clouds first; empty
+    // for a cloud that was not searched), for icp_diag_batch_segment
+    bool sg_seen = false;
+    std::vector<std::vector<int32_t>> sg_triples, sg_counts;   // 3 per hypothesis: the point indices; the count (-1: invalid)
+    std::vector<std::vector<uint8_t>> sg_valid;
+    std::vector<std::vector<double>> sg_planes;                // 4 per hypothesis
 };
 
 namespace {
@@ -581,7 +591,7 @@ int upload(icp_batch* b, const void* moving, const void* model)
 // (host vectors that its copies read or write are declared before this and so outlive it)
 struct Temps {
     hipStream_t st;
-    DevBuf buf[12];
+    DevBuf buf[16];
     explicit Temps(hipStream_t s) : st(s) {}
     ~Temps()
     {
@@ -2589,6 +2599,268 @@ int icp_diag_batch_ransac(icp_batch* b, int pair, int32_t* triples, uint8_t* val
     if (valid) std::memcpy(valid, b->rs_valid.data() + at, H);
     if (T16) std::memcpy(T16, b->rs_T.data() + at * 16, H * 16 * sizeof(double));
     if (counts) std::memcpy(counts, b->rs_counts.data() + at, H * sizeof(int32_t));
+    return ICP_OK;
+}
+
+// ---- plane segmentation (the rule: include/icp_mi355x.h; kernels: icp_k_segment.hip; the host statements: icp_host_math.cpp) ----
+extern "C++" {
+namespace {
+
+constexpr int kPlaneChunk = 4096;   // hypotheses per cloud and scoring launch of icp_batch_segment_plane: a multiple of PLANE_GROUP
+static_assert(kPlaneChunk % icp::PLANE_GROUP == 0, "whole groups per launch");
+
+// what the caller's output pointers of icp_batch_segment_plane are
+struct PlaneOut {
+    double* planes;
+    int32_t* inliers;
+    int* status;
+    uint8_t* mask[2];
+    int32_t* map[2];
+};
+
+// icp_batch_segment_plane after its argument checks.  rules: 2 * count, the moving clouds' first.  The sequence is a thinning call's
+// (thin_*), with the search in the place of the select launches:  [the clouds come down: the host draws from them]  ->  the
+// hypotheses of every searched cloud on the host  ->  per kPlaneChunk hypotheses: planes and valid bytes up, batch_plane_score, counts
+// down  ->  winners  ->  batch_plane_refit, moments down  ->  the refits on the host (icp::plane_from_moments)  ->
+// batch_plane_decide  ->  thin_counts and onwards as icp_batch_remove_outliers
+int segment_plane(icp_batch* src, const std::vector<icp_plane_rule>& rules, const uint64_t* seed, const PlaneOut& o, icp_batch** made)
+{
+    enum { MASK = T_VALUE, INLIERS = T_OWN, MOMENTS, SLICES, DIST, PLANES, VALID, COUNTS };   // (T_VALUE: this call keeps no double per point)
+    const int count = src->count;
+    const size_t n_clouds = 2 * (size_t)count;
+    hipStream_t st = src->ctx->stream;
+    // (host vectors that copies read or write: declared before th, whose temporaries wait for the stream when they go)
+    std::vector<char> raw[2];
+    std::vector<icp::PlaneJob> jobs0(n_clouds), jobs1, jobs2;
+    std::vector<icp::BatchItem> slices;
+    std::vector<double> dist(n_clouds, 0.0), hpl, hmom;
+    std::vector<uint8_t> hval, hmask;
+    std::vector<int32_t> got, hinl;
+    std::vector<std::vector<int32_t>> triples(n_clouds), counts(n_clouds);
+    std::vector<std::vector<uint8_t>> valid(n_clouds);
+    std::vector<std::vector<double>> planes(n_clouds);
+    bool any = false;
+    int Hmax = 0;
+    for (size_t k = 0; k < n_clouds; ++k) {
+        const icp_plane_rule& r = rules[k];
+        jobs0[k] = icp::PlaneJob{{0, 0, 0, 0}, {0, 0, 0, 0}, r.distance, r.kind, 0, 0, 0};
+        dist[k] = r.distance;
+        if (r.kind == ICP_PLANE_NONE) continue;
+        any = true;
+        Hmax = std::max(Hmax, r.hypotheses);
+    }
+    Thin th(src);
+    th.map_out[0] = o.map[0];
+    th.map_out[1] = o.map[1];
+    if (int rc = thin_begin(th, n_clouds * sizeof(icp::PlaneJob), false, true)) return rc;
+    const size_t tmp = (size_t)th.cl.tmp_plane;
+    HIP_TRY(th.t.buf[MASK].ensure(tmp));
+    HIP_TRY(th.t.buf[INLIERS].ensure(n_clouds * sizeof(int32_t)));
+    HIP_TRY(th.t.buf[MOMENTS].ensure(n_clouds * 9 * sizeof(double)));
+    if (int rc = thin_upload(th, jobs0.data(), n_clouds * sizeof(icp::PlaneJob))) return rc;
+    icp::BatchPlaneArgs a{};
+    thin_args(a, th);
+    a.jobs = (const icp::PlaneJob*)th.t.buf[T_RULES].p;
+    a.moments = (double*)th.t.buf[MOMENTS].p;
+    a.mask = (uint8_t*)th.t.buf[MASK].p;
+    a.inliers = (int32_t*)th.t.buf[INLIERS].p;
+    a.chosen = (int*)th.t.buf[T_FLAG].p;
+    jobs1 = jobs0;
+    if (any) {
+        // the clouds, widened: P0 and Q as the device holds them (the first wait)
+        raw[0].resize(3 * (size_t)src->p_plane * src->esize);
+        raw[1].resize(3 * (size_t)src->q_plane * src->esize);
+        HIP_TRY(hipMemcpyAsync(raw[0].data(), src->P0.p, raw[0].size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(raw[1].data(), src->Q.p, raw[1].size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        // the hypotheses of every searched cloud: draws, the plane of the three points, the axis test
+        for (size_t k = 0; k < n_clouds; ++k) {
+            const icp_plane_rule& r = rules[k];
+            if (r.kind == ICP_PLANE_NONE) continue;
+            const icp::VoxelCloud& c = th.cl.clouds[k];
+            const long long plane = c.side ? src->q_plane : src->p_plane;
+            const size_t p = k - (size_t)c.side * count;
+            const size_t H = (size_t)r.hypotheses;
+            triples[k].assign(3 * H, -1);
+            counts[k].assign(H, -1);
+            valid[k].assign(H, 0);
+            planes[k].assign(4 * H, 0.0);
+            const uint64_t s0 = ransac_mix(seed[p] + (uint64_t)c.side);
+            for (size_t h = 0; h < H; ++h) {
+                int32_t* slot = &triples[k][3 * h];
+                if (!draw_triple(s0, (int)h, (size_t)c.n, slot)) continue;
+                double abc[9];
+                for (int s = 0; s < 3; ++s)
+                    for (int d = 0; d < 3; ++d) abc[3 * s + d] = get_scalar(src, raw[c.side].data(), (size_t)(d * plane + c.src_off + slot[s]));
+                double* pl = &planes[k][4 * h];
+                if (!icp::plane_from_points(abc, abc + 3, abc + 6, pl)) continue;
+                if (!icp::plane_axis_ok(pl, r.axis, r.min_cos)) {
+                    pl[0] = pl[1] = pl[2] = pl[3] = 0.0;
+                    continue;
+                }
+                valid[k][h] = 1;
+            }
+            for (int first = 0; first < c.n; first += icp::PLANE_SLICE)
+                slices.push_back(icp::BatchItem{(int)k, first, std::min(icp::PLANE_SLICE, c.n - first), 0});
+        }
+        if (slices.size() > (size_t)INT_MAX) return fail(ICP_ERR_INVALID, "too many work items for one batch");
+        // scoring: every searched cloud's hypotheses [h0, h0 + per) in one launch; a wait per launch
+        const size_t room = (size_t)std::min(kPlaneChunk, (int)icp::round_up(Hmax, icp::PLANE_GROUP));
+        HIP_TRY(th.t.buf[SLICES].ensure(slices.size() * sizeof(icp::BatchItem)));
+        HIP_TRY(th.t.buf[DIST].ensure(n_clouds * sizeof(double)));
+        HIP_TRY(th.t.buf[PLANES].ensure(n_clouds * room * 4 * sizeof(double)));
+        HIP_TRY(th.t.buf[VALID].ensure(n_clouds * room));
+        HIP_TRY(th.t.buf[COUNTS].ensure(n_clouds * room * sizeof(int32_t)));
+        HIP_TRY(hipMemcpyAsync(th.t.buf[SLICES].p, slices.data(), slices.size() * sizeof(icp::BatchItem), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(th.t.buf[DIST].p, dist.data(), n_clouds * sizeof(double), hipMemcpyHostToDevice, st));
+        a.slices = (const icp::BatchItem*)th.t.buf[SLICES].p;
+        a.n_slices = (int)slices.size();
+        a.distance = (const double*)th.t.buf[DIST].p;
+        a.planes = (const double*)th.t.buf[PLANES].p;
+        a.valid = (const uint8_t*)th.t.buf[VALID].p;
+        a.counts = (int32_t*)th.t.buf[COUNTS].p;
+        for (int h0 = 0; h0 < Hmax; h0 += kPlaneChunk) {
+            const size_t per = (size_t)icp::round_up(std::min(kPlaneChunk, Hmax - h0), icp::PLANE_GROUP);   // <= room
+            hpl.assign(n_clouds * per * 4, 0.0);
+            hval.assign(n_clouds * per, 0);
+            got.assign(n_clouds * per, 0);
+            for (size_t k = 0; k < n_clouds; ++k) {
+                const size_t H = valid[k].size();
+                if (H <= (size_t)h0) continue;
+                const size_t len = std::min(per, H - (size_t)h0);
+                std::memcpy(&hpl[k * per * 4], &planes[k][4 * (size_t)h0], len * 4 * sizeof(double));
+                std::memcpy(&hval[k * per], &valid[k][(size_t)h0], len);
+            }
+            HIP_TRY(hipMemcpyAsync(th.t.buf[PLANES].p, hpl.data(), hpl.size() * sizeof(double), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(th.t.buf[VALID].p, hval.data(), hval.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(th.t.buf[COUNTS].p, 0, got.size() * sizeof(int32_t), st));
+            a.per = (int)per;
+            HIP_TRY(icp::launch_batch_plane_score(a, st));
+            HIP_TRY(hipMemcpyAsync(got.data(), th.t.buf[COUNTS].p, got.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (size_t k = 0; k < n_clouds; ++k)
+                for (size_t h = (size_t)h0; h < std::min(valid[k].size(), (size_t)h0 + per); ++h)
+                    if (valid[k][h]) counts[k][h] = got[k * per + (h - (size_t)h0)];
+        }
+        // winners: the largest count, the lowest h among equals
+        for (size_t k = 0; k < n_clouds; ++k) {
+            int best = -1;
+            for (size_t h = 0; h < valid[k].size(); ++h)
+                if (valid[k][h] && (best < 0 || counts[k][h] > counts[k][(size_t)best])) best = (int)h;
+            if (best < 0) continue;
+            icp::PlaneJob& j = jobs1[k];
+            std::memcpy(j.win, &planes[k][4 * (size_t)best], sizeof j.win);
+            j.has_plane = 1;
+            j.win_count = counts[k][(size_t)best];
+        }
+        // the refits: the sums on the device, the eigenvector on the host
+        hmom.resize(n_clouds * 9);
+        HIP_TRY(hipMemcpyAsync(th.t.buf[T_RULES].p, jobs1.data(), n_clouds * sizeof(icp::PlaneJob), hipMemcpyHostToDevice, st));
+        HIP_TRY(icp::launch_batch_plane_refit(a, st));
+        HIP_TRY(hipMemcpyAsync(hmom.data(), th.t.buf[MOMENTS].p, hmom.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    jobs2 = jobs1;
+    for (size_t k = 0; any && k < n_clouds; ++k) {
+        icp::PlaneJob& j = jobs2[k];
+        if (!j.has_plane || j.win_count < 3) continue;
+        if (!icp::plane_from_moments(&hmom[9 * k], &hmom[9 * k + 3], j.fit)) continue;
+        j.fit_ok = icp::plane_axis_ok(j.fit, rules[k].axis, rules[k].min_cos) ? 1 : 0;
+    }
+    HIP_TRY(hipMemcpyAsync(th.t.buf[T_RULES].p, jobs2.data(), n_clouds * sizeof(icp::PlaneJob), hipMemcpyHostToDevice, st));
+    HIP_TRY(icp::launch_batch_plane_decide(a, st));
+    if (int rc = thin_counts(th)) return rc;
+    for (int p = 0; p < count; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const size_t k = (size_t)side * count + p;
+            if (th.kept[k] < 1 && rules[k].kind == ICP_PLANE_REMOVE) return fail(ICP_ERR_EMPTY, "every point of the cloud lies on its plane" + where(p, side));
+            if (th.kept[k] < 1 && !jobs2[k].has_plane) return fail(ICP_ERR_EMPTY, "the cloud has no plane to keep" + where(p, side));
+            if (th.kept[k] < 1) return fail(ICP_ERR_EMPTY, "the cloud's plane keeps no point" + where(p, side));
+            if (th.kept[k] > th.cl.clouds[k].n) return fail(ICP_ERR_HIP, "icp_batch_segment_plane: a cloud's kept count is out of range");   // (cannot happen)
+        }
+    if (int rc = thin_allocate(th, made)) return rc;
+    icp::BatchOutlierArgs ca{};   // the compaction is the outlier call's: the same clouds, items, map and planes
+    thin_args(ca, th);
+    HIP_TRY(icp::launch_batch_outlier_compact(ca, st));
+    if (int rc = thin_download(th)) return rc;
+    hinl.resize(n_clouds);
+    HIP_TRY(hipMemcpyAsync(hinl.data(), th.t.buf[INLIERS].p, n_clouds * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (o.mask[0] || o.mask[1]) {
+        hmask.resize(tmp);
+        HIP_TRY(hipMemcpyAsync(hmask.data(), th.t.buf[MASK].p, tmp, hipMemcpyDeviceToHost, st));
+    }
+    if (int rc = thin_finish(th)) return rc;
+    for (size_t k = 0; k < n_clouds; ++k) {
+        const icp::VoxelCloud& c = th.cl.clouds[k];
+        const size_t p = k - (size_t)c.side * count;
+        const icp::PlaneJob& j = jobs2[k];
+        const bool searched = rules[k].kind != ICP_PLANE_NONE;
+        if (o.planes) {
+            const double zero[4] = {0, 0, 0, 0};
+            std::memcpy(o.planes + 4 * k, !j.has_plane ? zero : th.flag[k] == 1 ? j.fit : j.win, 4 * sizeof(double));
+        }
+        if (o.inliers) o.inliers[k] = hinl[k];
+        if (o.status) o.status[k] = searched && !j.has_plane ? ICP_ERR_EMPTY : ICP_OK;
+        if (o.mask[c.side]) std::memcpy(o.mask[c.side] + (c.side ? src->qoff[p] : src->moff[p]), hmask.data() + c.tmp_off, (size_t)c.n);
+    }
+    src->sg_seen = true;
+    src->sg_triples.swap(triples);
+    src->sg_valid.swap(valid);
+    src->sg_planes.swap(planes);
+    src->sg_counts.swap(counts);
+    return ICP_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int icp_batch_segment_plane(icp_batch* src, const icp_plane_rule* moving, const icp_plane_rule* model, const uint64_t* seed, double* planes_out,
+                            int32_t* inliers_out, int* status_out, uint8_t* moving_mask_out, uint8_t* model_mask_out, int32_t* moving_map_out,
+                            int32_t* model_map_out, icp_batch** out)
+{
+    if (!out) return fail(ICP_ERR_INVALID, "out == NULL");
+    *out = nullptr;
+    if (int rc = ready(src)) return rc;
+    static_assert(sizeof(icp_plane_rule) == 48, "the layout of icp_plane_rule");
+    std::vector<icp_plane_rule> rules(2 * (size_t)src->count, icp_plane_rule{ICP_PLANE_NONE, 0, 0.0, {0.0, 0.0, 0.0}, 0.0});   // the moving clouds', then the models'
+    for (int p = 0; p < src->count; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const icp_plane_rule* given = side ? model : moving;
+            if (!given) continue;
+            const icp_plane_rule& r = given[p];
+            const int n = side ? src->pairs[p].m : src->pairs[p].n;
+            const std::string at = where(p, side);
+            if (r.kind == ICP_PLANE_NONE) continue;
+            if (r.kind != ICP_PLANE_DETECT && r.kind != ICP_PLANE_REMOVE && r.kind != ICP_PLANE_KEEP) return fail(ICP_ERR_INVALID, "unknown plane rule kind" + at);
+            if (!seed) return fail(ICP_ERR_INVALID, "seed == NULL with a rule that searches" + at);
+            if (r.hypotheses < 1 || r.hypotheses > 65536) return fail(ICP_ERR_INVALID, "a plane rule's hypotheses must lie in [1, 65536]" + at);
+            if (!(std::isfinite(r.distance) && r.distance >= 0.0))   // (NaN fails both)
+                return fail(ICP_ERR_INVALID, "a plane rule's distance must be finite and >= 0" + at);
+            if (!(std::isfinite(r.axis[0]) && std::isfinite(r.axis[1]) && std::isfinite(r.axis[2])))
+                return fail(ICP_ERR_INVALID, "a plane rule's axis must be finite" + at);
+            if (!(r.min_cos >= 0.0 && r.min_cos <= 1.0)) return fail(ICP_ERR_INVALID, "a plane rule's min_cos must lie in [0, 1]" + at);
+            if (n < 3) return fail(ICP_ERR_INVALID, "a plane needs a cloud of at least 3 points" + at);
+            rules[(size_t)side * src->count + p] = r;
+        }
+    ScopedPin pin(src->ctx);
+    icp_batch* made = nullptr;
+    const PlaneOut o{planes_out, inliers_out, status_out, {moving_mask_out, model_mask_out}, {moving_map_out, model_map_out}};
+    const int rc = segment_plane(src, rules, seed, o, &made);
+    return hand_over(src, rc, made, out);
+}
+
+int icp_diag_batch_segment(icp_batch* b, int pair, int side, int32_t* triples, uint8_t* valid, double* planes, int32_t* counts)
+{
+    if (!b) return fail(ICP_ERR_INVALID, "null batch");
+    if (pair < 0 || pair >= b->count) return fail(ICP_ERR_INVALID, "pair out of range");
+    if (side != 0 && side != 1) return fail(ICP_ERR_INVALID, "side must be 0 (the moving cloud) or 1 (the model)");
+    if (!b->sg_seen) return fail(ICP_ERR_STATE, "no icp_batch_segment_plane call on this batch");
+    const size_t k = (size_t)side * b->count + pair, H = b->sg_valid[k].size();
+    if (H == 0) return fail(ICP_ERR_STATE, "the last icp_batch_segment_plane call did not search this cloud");
+    if (triples) std::memcpy(triples, b->sg_triples[k].data(), H * 3 * sizeof(int32_t));
+    if (valid) std::memcpy(valid, b->sg_valid[k].data(), H);
+    if (planes) std::memcpy(planes, b->sg_planes[k].data(), H * 4 * sizeof(double));
+    if (counts) std::memcpy(counts, b->sg_counts[k].data(), H * sizeof(int32_t));
     return ICP_OK;
 }
 

@@ -284,6 +284,62 @@ void eigh3(const double A[9], double w[3], double Z[9])
     }
 }
 
+// ---- plane segmentation (icp_batch_segment_plane): every statement is the header's, one IEEE double operation each (this unit is
+// compiled with contraction off)
+namespace {
+// all three components negated iff the component of largest magnitude is negative; the lowest index decides among equal magnitudes
+void plane_sign(double n[3])
+{
+    int k = 0;
+    for (int a = 1; a < 3; ++a)
+        if (std::fabs(n[a]) > std::fabs(n[k])) k = a;
+    if (n[k] < 0.0)
+        for (int a = 0; a < 3; ++a) n[a] = -n[a];
+}
+}  // namespace
+
+bool plane_from_points(const double* a, const double* b, const double* c, double plane4[4])
+{
+    plane4[0] = plane4[1] = plane4[2] = plane4[3] = 0.0;
+    const double ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
+    const double vx = c[0] - a[0], vy = c[1] - a[1], vz = c[2] - a[2];
+    const double wx = uy * vz - uz * vy, wy = uz * vx - ux * vz, wz = ux * vy - uy * vx;
+    const double l = std::sqrt((wx * wx + wy * wy) + wz * wz);
+    if (!(l > 0.0 && std::isfinite(l))) return false;   // (NaN fails both)
+    double n[3] = {wx / l, wy / l, wz / l};
+    plane_sign(n);
+    plane4[0] = n[0];
+    plane4[1] = n[1];
+    plane4[2] = n[2];
+    plane4[3] = -((n[0] * a[0] + n[1] * a[1]) + n[2] * a[2]);
+    return true;
+}
+
+bool plane_from_moments(const double centroid[3], const double cov6[6], double plane4[4])
+{
+    plane4[0] = plane4[1] = plane4[2] = plane4[3] = 0.0;
+    const double A[9] = {cov6[0], cov6[1], cov6[2], cov6[1], cov6[3], cov6[4], cov6[2], cov6[4], cov6[5]};
+    double w[3], Z[9];
+    eigh3(A, w, Z);
+    double n[3] = {Z[0], Z[3], Z[6]};   // column 0: the smallest eigenvalue's, not renormalised
+    if (!(std::isfinite(n[0]) && std::isfinite(n[1]) && std::isfinite(n[2]))) return false;
+    if (n[0] == 0.0 && n[1] == 0.0 && n[2] == 0.0) return false;
+    plane_sign(n);
+    plane4[0] = n[0];
+    plane4[1] = n[1];
+    plane4[2] = n[2];
+    plane4[3] = -((n[0] * centroid[0] + n[1] * centroid[1]) + n[2] * centroid[2]);
+    return true;
+}
+
+bool plane_axis_ok(const double plane4[4], const double axis[3], double min_cos)
+{
+    if (axis[0] == 0.0 && axis[1] == 0.0 && axis[2] == 0.0) return true;
+    const double la = std::sqrt((axis[0] * axis[0] + axis[1] * axis[1]) + axis[2] * axis[2]);
+    const double hx = axis[0] / la, hy = axis[1] / la, hz = axis[2] / la;
+    return std::fabs((plane4[0] * hx + plane4[1] * hy) + plane4[2] * hz) >= min_cos;
+}
+
 int shard_range(int64_t n, int rank, int world, int64_t* begin, int64_t* count)
 {
     if (n < 0 || world <= 0 || rank < 0 || rank >= world) return ICP_ERR_INVALID;
@@ -320,6 +376,16 @@ int icp_shard_range(int64_t n, int rank, int world, int64_t* begin, int64_t* cou
 {
     if (!begin || !count) return ICP_ERR_INVALID;
     return icp::shard_range(n, rank, world, begin, count);
+}
+int icp_plane_from_points(const double* abc9, double* plane4)
+{
+    if (!abc9 || !plane4) return ICP_ERR_INVALID;
+    return icp::plane_from_points(abc9, abc9 + 3, abc9 + 6, plane4) ? ICP_OK : ICP_ERR_EMPTY;
+}
+int icp_plane_from_moments(const double* centroid3, const double* cov6, double* plane4)
+{
+    if (!centroid3 || !cov6 || !plane4) return ICP_ERR_INVALID;
+    return icp::plane_from_moments(centroid3, cov6, plane4) ? ICP_OK : ICP_ERR_EMPTY;
 }
 int icp_eigh3(const double* A9, double* w3, double* Z9)
 {

@@ -651,6 +651,55 @@ struct BatchNormalsArgs {
 // [batch_centroid_kernel (one block per cloud: cent), ICP_ORIENT_CENTROID only ->] batch_point_normals_kernel (one wave per work
 // item: nrm).  One launch, or two.
 hipError_t launch_batch_point_normals(const BatchNormalsArgs& a, hipStream_t st);
+// the dominant plane of every cloud of a batch (icp_batch_segment_plane; the rule: include/icp_mi355x.h; icp_k_segment.hip).  The
+// clouds, their numbering, their stretches of the per-point temporaries and the work items are the outlier call's.  The host draws
+// and solves the hypotheses; the device counts their inliers, sums the winner's moments and decides every point.
+constexpr int PLANE_GROUP = 32;            // hypotheses per block of batch_plane_score: one integer counter each, in registers
+constexpr int PLANE_SLICE = 4096;          // points per block of batch_plane_score: a large cloud is cut over several blocks
+struct PlaneJob {                          // one per cloud
+    double win[4];                         // the winning hypothesis: nx, ny, nz, d (zeros: none)
+    double fit[4];                         // its refit (read where fit_ok)
+    double distance;
+    int kind;                              // ICP_PLANE_*
+    int has_plane;                         // a valid hypothesis exists
+    int win_count;                         // the winner's inliers
+    int fit_ok;                            // the refit exists and passed the axis test
+};
+struct BatchPlaneArgs {
+    int precision;             // ICP_F32 / ICP_F64
+    const VoxelCloud* clouds;  // [2 * n_pairs]
+    int n_clouds;
+    const BatchItem* items;    // the work items of all clouds, in cloud order (the compaction's)
+    int n_items;
+    const void* src[2];        // P0 and Q of the source batch (read only)
+    long long src_plane[2];
+    long long tmp_plane;       // elements of every per-point temporary
+    int32_t* map;              // [tmp]: the index of a kept point in its new cloud, -1 for a removed one
+    int32_t* count;            // int32[n_clouds]: kept points
+    void* dst[2];              // P0 and Q of the new batch (the compaction)
+    long long dst_plane[2];
+    // batch_plane_score
+    const BatchItem* slices;   // PLANE_SLICE points of one searched cloud each (BatchItem::pair = the cloud's number)
+    int n_slices;
+    int per;                   // hypotheses per cloud of this launch: a multiple of PLANE_GROUP
+    const double* planes;      // double[n_clouds][per][4]
+    const uint8_t* valid;      // uint8[n_clouds][per]: 0 = the hypothesis is not counted
+    const double* distance;    // double[n_clouds]
+    int32_t* counts;           // int32[n_clouds][per], zero before the launch: the blocks of a cloud add their integers
+    // batch_plane_refit, batch_plane_decide
+    const PlaneJob* jobs;      // [n_clouds]
+    double* moments;           // double[n_clouds][9]: the centroid, then xx, xy, xz, yy, yz, zz of the winner's inliers
+    uint8_t* mask;             // uint8[tmp]: 1 = the point lies on the returned plane
+    int32_t* inliers;          // int32[n_clouds]: the returned plane's count
+    int* chosen;               // int[n_clouds]: 1 = the refit is returned, 0 = the winner, -1 = no plane
+};
+// batch_plane_score<F>: grid (n_slices, per / PLANE_GROUP).  One launch.
+hipError_t launch_batch_plane_score(const BatchPlaneArgs& a, hipStream_t st);
+// batch_plane_refit<F>: one block per cloud -> moments.  One launch.
+hipError_t launch_batch_plane_refit(const BatchPlaneArgs& a, hipStream_t st);
+// batch_plane_decide<F>: one block per cloud -> chosen, inliers, mask, map, count.  One launch.  The compaction is the outlier
+// call's (launch_batch_outlier_compact: the same clouds, items, map and planes).
+hipError_t launch_batch_plane_decide(const BatchPlaneArgs& a, hipStream_t st);
 
 // soa2 (optional): a second copy of the result (the pristine moving cloud); enc (optional, fp32): the cloud's bounding cube as six
 // ordered-integer words {~ord(min xyz), ord(max xyz)}, zero before the launch

@@ -435,8 +435,13 @@ class Context:
         device_normals=True (the default is False) makes the normals on the device from the covariances
         (Batch.estimate_point_normals, facing the centroids, or viewpoint where given) and describes from them
         (Batch.compute_features_stored): no clouds and no covariances come down, no normals go up.  The Jacobi's and LAPACK's
-        vectors differ in the last bits, so descriptors and poses can differ from the default route's."""
-        known = {"viewpoint", "edge_similarity", "seed", "mutual", "gate", "metric", "normals", "max_iter", "tol", "fixed_iterations", "trim", "reciprocal",
+        vectors differ in the last bits, so descriptors and poses can differ from the default route's.
+        planes=rule (Batch.segment_plane's rule, one for all pairs or one per pair; the default is None) applies the rule to both
+        clouds of every pair before downsampling -- ("remove", distance) takes the dominant plane out, so that a floor or a wall
+        neither fills the match list with ties nor lets the pose slide; seed is handed on.  The start pose is found on those
+        clouds; the local loop runs on the full pairs as before.  extra["global"] gains "planes": the (2, 4) planes of the pair's
+        moving cloud and model, and "plane_inliers": their two counts."""
+        known = {"planes", "viewpoint", "edge_similarity", "seed", "mutual", "gate", "metric", "normals", "max_iter", "tol", "fixed_iterations", "trim", "reciprocal",
                  "method", "iterations", "division_factor", "decrease_every", "tuple_similarity", "keypoints", "device_normals"}
         unknown = set(options) - known
         if unknown:
@@ -447,7 +452,15 @@ class Context:
         pairs = list(pairs)
         v = 0.0 if voxel is None else float(voxel)
         with Batch(self, pairs) as full:
-            bt = full if v == 0.0 else full.downsample(v)
+            cut, cut_info = full, None
+            if options.get("planes") is not None:
+                cut, cut_info = full.segment_plane(moving=options["planes"], model=options["planes"], seed=options.get("seed", 0))
+            try:
+                bt = cut if v == 0.0 else cut.downsample(v)
+            except Exception:
+                if cut is not full:
+                    cut.close()
+                raise
             try:
                 view = options.get("viewpoint")
                 if options.get("device_normals", False):   # nothing comes down, nothing goes up
@@ -478,9 +491,15 @@ class Context:
                 if kept is not None:
                     for r, c in zip(start, kept):
                         r["keypoints"] = c
+                if cut_info is not None:
+                    for b, r in enumerate(start):
+                        r["planes"] = cut_info["planes"][[b, full.count + b]].copy()
+                        r["plane_inliers"] = (int(cut_info["inliers"][b]), int(cut_info["inliers"][full.count + b]))
             finally:
-                if bt is not full:
+                if bt is not cut:
                     bt.close()
+                if cut is not full:
+                    cut.close()
         T0 = np.stack([r["T"] for r in start])
         rest = {o: options[o] for o in ("metric", "normals", "max_iter", "tol", "fixed_iterations", "trim", "reciprocal") if o in options}
         out = self.register_batch(pairs, max_distance=options.get("gate"), init=T0, **rest)
@@ -867,6 +886,94 @@ class Batch:
         if want_scores:
             info["moving_score"], info["model_score"] = per_moving(ms), per_model(qs)
         return out, info
+
+    def _plane_rules(self, rules, what):
+        """one rule or one per pair -> (a ctypes array of count icp_plane_rule, the hypotheses of each); None: (NULL, zeros), copy
+        that side.  A rule is a tuple (kind, distance, hypotheses=1000, axis=(0, 0, 0), min_cos=0.0) or a dict of those names, kind
+        one of "detect", "remove", "keep"; None copies"""
+        if rules is None:
+            return None, [0] * self.count
+        one = isinstance(rules, dict) or (isinstance(rules, tuple) and len(rules) > 0 and isinstance(rules[0], str))
+        rules = [rules] * self.count if one else list(rules)
+        if len(rules) != self.count:
+            raise ValueError(f"one {what} plane rule per pair (or a single rule)")
+        names = ("kind", "distance", "hypotheses", "axis", "min_cos")
+        kinds = {"detect": capi.ICP_PLANE_DETECT, "remove": capi.ICP_PLANE_REMOVE, "keep": capi.ICP_PLANE_KEEP}
+        arr = (capi.icp_plane_rule * self.count)()
+        hyp = []
+        for b, r in enumerate(rules):
+            if r is None:
+                arr[b] = capi.icp_plane_rule(capi.ICP_PLANE_NONE, 0, 0.0, (C.c_double * 3)(0.0, 0.0, 0.0), 0.0)
+                hyp.append(0)
+                continue
+            if isinstance(r, dict):
+                if set(r) - set(names) or "kind" not in r or "distance" not in r:
+                    raise ValueError(f"a plane rule needs kind and distance, and may hold {names[2:]}")
+                r = (r["kind"], r["distance"]) + tuple(r.get(k, d) for k, d in zip(names[2:], (1000, (0.0, 0.0, 0.0), 0.0)))
+            r = tuple(r)
+            if not 2 <= len(r) <= 5:
+                raise ValueError("a plane rule is (kind, distance, hypotheses=1000, axis=(0, 0, 0), min_cos=0.0)")
+            r = r + (1000, (0.0, 0.0, 0.0), 0.0)[len(r) - 2:]
+            if r[0] not in kinds:
+                raise ValueError(f"unknown plane rule kind {r[0]!r}: 'detect', 'remove', 'keep' or None")
+            ax = [float(x) for x in r[3]]
+            if len(ax) != 3:
+                raise ValueError("a plane rule's axis has three components")
+            arr[b] = capi.icp_plane_rule(kinds[r[0]], int(r[2]), float(r[1]), (C.c_double * 3)(*ax), float(r[4]))
+            hyp.append(int(r[2]))
+        return arr, hyp
+
+    def segment_plane(self, moving=None, model=None, seed=0, want_masks=False, want_maps=False):
+        """a new Batch on the same context whose clouds are this batch's clouds as uploaded without their dominant plane, or
+        reduced to it, found by RANSAC on the device (icp_batch_segment_plane; the rule is stated in include/icp_mi355x.h).  moving,
+        model: one rule or one per pair -- (kind, distance, hypotheses=1000, axis=(0, 0, 0), min_cos=0.0) or a dict of those
+        names; kind "detect" copies the cloud and reports its plane, "remove" keeps the points farther than distance from the
+        plane, "keep" those within; a non-zero axis admits only planes whose normal n has |n . axis| / |axis| >= min_cos; None:
+        copy, nothing is searched.  seed: a scalar for every pair, or one per pair.  Kept points are copied, in the source order.
+        Zero lidar returns are the caller's to drop: a plane through the origin counts every one of them.  This batch is only
+        read, and its loop does not notice.  Returns (Batch, info): info["planes"] (2 * count, 4) float64 -- nx, ny, nz, d, the
+        moving clouds first -- info["inliers"] (2 * count,) int32 and info["status"] (2 * count,) (ICP_OK; ICP_ERR_EMPTY where a
+        cloud has no valid hypothesis: it is copied); want_masks adds "moving_mask" and "model_mask" (per pair, uint8: 1 = on
+        the plane), want_maps "moving_map" and "model_map" (per pair, int32: the new index of a kept point, -1 for a removed one)."""
+        (rm, hm), (rq, hq) = self._plane_rules(moving, "moving"), self._plane_rules(model, "model")
+        sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seed, dtype=np.uint64), (self.count,)))
+        pd, p32, p8 = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        n, m = int(self._moff[-1]), int(self._qoff[-1])
+        mk = np.empty(n, dtype=np.uint8) if want_masks else None
+        qk = np.empty(m, dtype=np.uint8) if want_masks else None
+        mm = np.empty(n, dtype=np.int32) if want_maps else None
+        qm = np.empty(m, dtype=np.int32) if want_maps else None
+        planes = np.zeros((2 * self.count, 4), dtype=np.float64)
+        inl = np.zeros(2 * self.count, dtype=np.int32)
+        st = np.zeros(2 * self.count, dtype=np.intc)
+        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        h = C.c_void_p()
+        capi.check(self._lib.icp_batch_segment_plane(self._h, rm, rq, sd.ctypes.data_as(C.POINTER(C.c_uint64)), ptr(planes, pd), ptr(inl, p32),
+                                                     st.ctypes.data_as(C.POINTER(C.c_int)), ptr(mk, p8), ptr(qk, p8), ptr(mm, p32), ptr(qm, p32),
+                                                     C.byref(h)), "icp_batch_segment_plane")
+        self._segment_hyp = hm + hq
+        out = Batch._from_handle(self._ctx, h, self.count, self._dtype)
+        info = {"planes": planes, "inliers": inl, "status": st}
+        per_model = lambda a: self._cut(a, self._qoff)
+        per_moving = lambda a: [a[self._moff[b]:self._moff[b + 1]].copy() for b in range(self.count)]
+        if want_masks:
+            info["moving_mask"], info["model_mask"] = per_moving(mk), per_model(qk)
+        if want_maps:
+            info["moving_map"], info["model_map"] = per_moving(mm), per_model(qm)
+        return out, info
+
+    def diag_segment(self, b, side):
+        """the last segment_plane call's hypotheses of pair b, side 0 (the moving cloud) or 1 (the model)
+        (icp_diag_batch_segment): dict of triples (H, 3) int32 -- point indices, -1 for an empty slot -- valid (H,) uint8, planes
+        (H, 4) and counts (H,) int32 (-1: invalid)"""
+        hyp = getattr(self, "_segment_hyp", None)
+        H = int(hyp[int(side) * self.count + int(b)]) if hyp is not None and 0 <= int(b) < self.count and int(side) in (0, 1) else 0
+        tr, va = np.zeros((max(H, 1), 3), dtype=np.int32), np.zeros(max(H, 1), dtype=np.uint8)
+        pl, cn = np.zeros((max(H, 1), 4)), np.zeros(max(H, 1), dtype=np.int32)
+        p32 = C.POINTER(C.c_int32)
+        capi.check(self._lib.icp_diag_batch_segment(self._h, int(b), int(side), tr.ctypes.data_as(p32), va.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                    pl.ctypes.data_as(C.POINTER(C.c_double)), cn.ctypes.data_as(p32)), "icp_diag_batch_segment")
+        return dict(triples=tr[:H], valid=va[:H], planes=pl[:H], counts=cn[:H])
 
     def _keypoint_rules(self, rules, what):
         """one rule or one per pair -> a ctypes array of count icp_keypoint_rule (None: NULL, copy that side).  A rule is a tuple
@@ -1606,6 +1713,36 @@ def eigh3(A):
     pd = C.POINTER(C.c_double)
     capi.check(lib.icp_eigh3(A.ctypes.data_as(pd), w.ctypes.data_as(pd), Z.ctypes.data_as(pd)), "icp_eigh3")
     return w, Z.reshape(3, 3)
+
+
+def plane_from_points(abc):
+    """the plane (nx, ny, nz, d) of three points (3, 3) by icp_batch_segment_plane's rule (icp_plane_from_points), or None where
+    the hypothesis is invalid: coincident or collinear points, or a cross product outside the double range"""
+    lib = capi.load()
+    abc = np.ascontiguousarray(abc, dtype=np.float64).reshape(9)
+    out = np.zeros(4)
+    pd = C.POINTER(C.c_double)
+    rc = lib.icp_plane_from_points(abc.ctypes.data_as(pd), out.ctypes.data_as(pd))
+    if rc == capi.ICP_ERR_EMPTY:
+        return None
+    capi.check(rc, "icp_plane_from_points")
+    return out
+
+
+def plane_from_moments(centroid, cov6):
+    """the plane (nx, ny, nz, d) through centroid (3,) whose normal is the eigenvector of the smallest eigenvalue of the second
+    moments cov6 (xx, xy, xz, yy, yz, zz): the last step of icp_batch_segment_plane's refit (icp_plane_from_moments), or None where
+    that vector is zero or not finite"""
+    lib = capi.load()
+    c = np.ascontiguousarray(centroid, dtype=np.float64).reshape(3)
+    v = np.ascontiguousarray(cov6, dtype=np.float64).reshape(6)
+    out = np.zeros(4)
+    pd = C.POINTER(C.c_double)
+    rc = lib.icp_plane_from_moments(c.ctypes.data_as(pd), v.ctypes.data_as(pd), out.ctypes.data_as(pd))
+    if rc == capi.ICP_ERR_EMPTY:
+        return None
+    capi.check(rc, "icp_plane_from_moments")
+    return out
 
 
 class LocalComm:

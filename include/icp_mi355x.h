@@ -790,6 +790,72 @@ int icp_loop_indices(icp_ctx* ctx, int32_t* idx_out);
  *             one for the kept count of every cloud, which the new batch's layout needs, one at the end with the optional
  *             outputs.  Both scans are brute force, n^2 distances per cloud.  LDS per block: 24 KiB (saliency), 42 KiB in fp32
  *             and 34 KiB in fp64 (selection), 16 bytes (rank), none (compaction).  No atomics.
+ *   - plane segmentation (icp_batch_segment_plane; Open3D's segment_plane, PCL's SACSegmentation): a floor or a wall holds a large
+ *     share of a scan's points, fixes only three of the six unknowns and gives descriptors that are all alike.  The call finds the
+ *     dominant plane of every cloud by RANSAC -- points x hypotheses plane tests per cloud, counted on the device -- and makes a new
+ *     batch without it, or of it alone.  Each cloud has a rule of its own (icp_plane_rule).  Where the two overlap the call behaves
+ *     as icp_batch_remove_outliers.  The rule is restated in numpy, bit for bit (tests/batch_segment_ref.py).
+ *       inputs: moving and model hold count rules each; a NULL array copies that side; kind ICP_PLANE_NONE copies the cloud, its
+ *         bytes and its order, and nothing is searched (its status is ICP_OK, its plane four zeros).  The other kinds read
+ *         hypotheses, distance, axis and min_cos.  seed holds one word per pair.
+ *       source: P0 and Q, the clouds as uploaded or as made by an earlier call -- never the moved cloud.  The options, the normals
+ *         and the loop of src are not read.  The loop does not notice.
+ *       the rule for a cloud of n points whose kind is not ICP_PLANE_NONE.  Everything is in IEEE double on coordinates widened
+ *         once; every operation is rounded on its own, nothing is fused, nothing is multiplied by a reciprocal, and the only
+ *         functions used are + - * / sqrt fabs.
+ *           draws: icp_batch_ransac's generator, unchanged: draw(h, r) = mix(mix(mix(seed_p + side) + h) + r) % n, side 0 for the
+ *             moving cloud and 1 for the model, sums modulo 2^64.  Slots 0, 1, 2 take the draws r = 0, 1, ...; a draw equal to an
+ *             earlier slot is skipped; at most 16 draws are used; fewer than three distinct indices make the hypothesis invalid.
+ *           plane of three points a, b, c (icp_plane_from_points): u = b - a, v = c - a;
+ *             w = (uy*vz - uz*vy, uz*vx - ux*vz, ux*vy - uy*vx); l = sqrt((wx*wx + wy*wy) + wz*wz).  The hypothesis is invalid unless
+ *             l > 0 and l is finite: coincident and collinear picks end here, and so do the zero returns of a lidar -- a triple
+ *             out of the heap at the origin is invalid, while a plane through the origin still counts every point of the heap;
+ *             dropping zero returns is the caller's job.  n = w / l, three divisions.  sign rule: all three components are
+ *             negated iff the component of largest magnitude is negative; the lowest index decides among equal magnitudes.
+ *             d = -((nx*ax + ny*ay) + nz*az).
+ *           range: the products of w are squares of the cloud's extent and l squares them again: l leaves the double range
+ *             (overflows to +INFINITY) once the triangle's edges pass about 2^255, and is exactly 0 once they fall below about
+ *             2^-269.  Such hypotheses are invalid, not wrong.  (Between 2^-269 and 2^-255 the squares are subnormal and n is
+ *             what these statements give.)
+ *           axis constraint: axis == (0, 0, 0) means none.  Otherwise ahat = axis / sqrt((ax*ax + ay*ay) + az*az), three divisions,
+ *             and the hypothesis is valid iff fabs((nx*ahx + ny*ahy) + nz*ahz) >= min_cos (PCL's perpendicular-plane model without
+ *             its trigonometry: what lets a caller ask for the floor and not the larger wall).
+ *           score: s_i = ((nx*x + ny*y) + nz*z) + d; point i is an inlier iff fabs(s_i) <= distance.  A point on the threshold is
+ *             in, a NaN is out.  Counts are integers: exact whatever order the device adds them in.
+ *           winner: the largest count, the lowest h among equals.  With no valid hypothesis the cloud's status is ICP_ERR_EMPTY, its
+ *             plane four zeros, its count 0, its mask all 0; under ICP_PLANE_DETECT and ICP_PLANE_REMOVE such a cloud is copied.
+ *           refit over the winner's k >= 3 inliers (k < 3: no refit): S = the sum of the inlier coordinates in the outlier call's
+ *             order -- granules of 64 consecutive points from the cloud's first point, each granule added from 0.0 in ascending
+ *             index, the granule sums added from 0.0 in ascending order; c = S / (double)k; the six sums of ex*ex, ex*ey, ex*ez,
+ *             ey*ey, ey*ez, ez*ez with e = x - c in the same order, each divided once by (double)k.  icp_plane_from_moments:
+ *             icp_eigh3's eigenvector of the smallest eigenvalue (column 0 of Z, as icp_batch_estimate_point_normals chooses it,
+ *             not renormalised); the refit is dropped if that vector is zero or not finite; the sign rule;
+ *             d = -((nx*cx + ny*cy) + nz*cz); the axis test again -- a refit that fails it is dropped.  The refit is scored once
+ *             more, and the call returns the refit if its count is at least the winner's, else the winner (icp_batch_ransac's
+ *             rule).  The mask is the returned plane's.
+ *       outputs, all optional (NULL: not wanted): planes_out 4 doubles per cloud (nx, ny, nz, d), inliers_out and status_out
+ *         (ICP_OK or ICP_ERR_EMPTY) one per cloud -- 2 * count clouds, the moving clouds first.  The masks hold one byte per source
+ *         point in src's layout: 1 = the point lies on its cloud's plane.  The maps follow the outlier call: the index of a kept
+ *         point within its new cloud, -1 for a removed point, 0 .. n-1 for a copied cloud.  Kept points are copied, not computed,
+ *         in the source order: a -0.0 survives.  ICP_PLANE_DETECT copies the cloud; ICP_PLANE_REMOVE keeps the points off the
+ *         plane, ICP_PLANE_KEEP those on it.
+ *       refusals: on any refusal *out is NULL, nothing of src changes and no output array is written; where a pair is at fault
+ *         the message names the first offending pair and the side.  ICP_ERR_INVALID: a null src or a null out; null seeds where
+ *         any rule searches; an unknown kind; hypotheses outside [1, 65536]; a distance that is not finite or not >= 0; an axis
+ *         that is not finite; min_cos outside [0, 1]; a searched cloud of n < 3.  ICP_ERR_STATE: a pass pending on the context.
+ *         ICP_ERR_EMPTY for the whole call (known at the first host wait of the new batch's layout, before the new batch exists):
+ *         an ICP_PLANE_REMOVE cloud whose every point is an inlier; an ICP_PLANE_KEEP cloud with no plane, or with no inlier.
+ *       independence: a cloud's outputs depend on that cloud, its rule, its pair's seed and its side alone -- not on the other
+ *         pairs, their order or the batch size.
+ *       new batch: *out is a complete batch, as if icp_batch_create had been called with the output clouds: no options, no
+ *         normals, no descriptors, no loop under way.  Several planes are peeled by calling again on the result.
+ *       cost: the host draws and solves the hypotheses (three points each); the device scores them, 4096 per cloud and launch
+ *         (batch_plane_score: one block of 256 threads per 4096 points of a cloud and per 32 hypotheses, the planes read at a
+ *         uniform address, one integer counter per hypothesis and lane, integer adds of the blocks' counts), then
+ *         batch_plane_refit and batch_plane_decide (one block per cloud each; 48 KiB and 16 bytes of LDS) and the outlier call's
+ *         compaction.  Host waits: one for the clouds the host draws from, one per scoring launch (ceil(H / 4096)), one for the
+ *         refit's moments, and the outlier call's two around the layout of the new batch -- five for up to 4096 hypotheses; two
+ *         when nothing is searched.  No floating-point atomics.
  *   - the colored metric (ICP_COLORED; Park, Zhou, Koltun, ICCV 2017; Open3D's registration_colored_icp): a flat or gently curved
  *     textured surface leaves geometry alone three unknowns free; a scalar intensity per point (a reflectivity, the mean of an
  *     RGB colour) fixes them.  Every kept match pulls with two residuals, the point-to-plane distance weighed by lambda and the
@@ -964,6 +1030,23 @@ int icp_batch_remove_outliers(icp_batch* src,
         double* moving_score_out, double* model_score_out,                  /* 1 per source point; may be NULL */
         double* stats_out,                                                  /* 2*count x 4, moving clouds first; may be NULL */
         icp_batch** out);
+/* a new batch on src's context: same count and precision, every pair's clouds without their dominant plane, or reduced to it (the
+ * rule: above).  seed: one word per pair (may be NULL where no rule searches); every output may be NULL */
+#define ICP_PLANE_NONE   0   /* copy the cloud: its bytes, its order; nothing is searched */
+#define ICP_PLANE_DETECT 1   /* copy the cloud; report its plane and inlier mask */
+#define ICP_PLANE_REMOVE 2   /* new cloud = the points off the plane */
+#define ICP_PLANE_KEEP   3   /* new cloud = the points on the plane */
+typedef struct icp_plane_rule { int kind; int hypotheses; double distance; double axis[3]; double min_cos; } icp_plane_rule;   /* 48 bytes */
+int icp_batch_segment_plane(icp_batch* src, const icp_plane_rule* moving, const icp_plane_rule* model, const uint64_t* seed /*count*/,
+                            double* planes_out /*2*count x 4, moving clouds first*/, int32_t* inliers_out /*2*count*/, int* status_out /*2*count*/,
+                            uint8_t* moving_mask_out, uint8_t* model_mask_out, int32_t* moving_map_out, int32_t* model_map_out,
+                            icp_batch** out);
+/* host: three points (9 doubles: a, b, c) -> plane4 = (nx, ny, nz, d) by the rule above.  ICP_ERR_EMPTY, and four zeros, where the
+ * hypothesis is invalid (l is not > 0 or not finite); ICP_ERR_INVALID on a NULL pointer */
+int icp_plane_from_points(const double* abc9, double* plane4);
+/* host: the refit's last step -- the centroid and the six second moments (xx, xy, xz, yy, yz, zz) -> plane4.  ICP_ERR_EMPTY, and
+ * four zeros, where the eigenvector is zero or not finite; ICP_ERR_INVALID on a NULL pointer */
+int icp_plane_from_moments(const double* centroid3, const double* cov6, double* plane4);
 /* the generalized metric (above): prm->metric of icp_batch_begin on a batch that holds covariances on both sides */
 #define ICP_GENERALIZED 2                 /* third value of icp_metric */
 #define ICP_COV_NONE 0                    /* the raw covariance */

@@ -144,6 +144,13 @@ int icp_diag_batch_fgr_times(icp_batch* b, double* seconds4);
 /* the centroids batch_centroid_kernel made in the last icp_batch_estimate_point_normals call with ICP_ORIENT_CENTROID: 3 doubles
  * per cloud, 2 * count clouds, the moving clouds first.  One download, one wait.  ICP_ERR_STATE after no such call. */
 int icp_diag_batch_centroids(icp_batch* b, double* out /* 2 * count * 3 */);
+/* the last icp_batch_segment_plane call's hypotheses of one cloud of src -- pair `pair`, side 0 (the moving cloud) or 1 (the
+ * model) -- H = that cloud's rule's hypotheses: triples 3 x H int32 (the point indices that slots 0, 1, 2 took; -1 for a slot left
+ * empty), valid H bytes (three distinct picks, l > 0 and finite, the axis test passed), planes 4 x H doubles (nx, ny, nz, d; zeros
+ * for an invalid hypothesis), counts H int32 (the inliers batch_plane_score counted; -1 for an invalid hypothesis).  Host copies:
+ * nothing is downloaded.  Every output may be NULL.  ICP_ERR_STATE before the first call and for a cloud whose kind was
+ * ICP_PLANE_NONE; a refused call leaves the hypotheses of the call before it. */
+int icp_diag_batch_segment(icp_batch* b, int pair, int side, int32_t* triples, uint8_t* valid, double* planes, int32_t* counts);
 #ifdef __cplusplus
 }
 #endif
