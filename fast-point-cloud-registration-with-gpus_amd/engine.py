@@ -299,8 +299,7 @@ class Context:
         point_to_point_batch takes them, and reciprocal (None: off; a bool for every pair; or one flag per pair): a reciprocal
         pair keeps only mutual nearest neighbours (Batch.set_reciprocal).  Always runs through a Batch; a list of Result in pair
         order with extra["status"], extra["inliers"] (the mask of the last contributing pass) and extra["fitness"]."""
-        if max_iter is None:
-            max_iter = 50 if metric == capi.ICP_POINT_TO_PLANE else 40
+        max_iter = _default_max_iter("register_batch", metric, max_iter)
         return self._run_batch_gated(metric, pairs, normals, max_iter, tol, fixed_iterations, max_distance, init, trim, reciprocal)
 
     def register_batch_robust(self, pairs, kernel, scale, **options):
@@ -309,16 +308,8 @@ class Context:
         weight in [0, 1] that falls smoothly with its residual; the loop is iteratively re-weighted least squares.  options:
         register_batch's, by keyword.  The same list of Result, with extra["weights"] added: the (n,) float64 weights of each
         pair's most recent matching pass (0.0 where the match was rejected)."""
-        unknown = set(options) - {"metric", "normals", "max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal"}
-        if unknown:
-            raise TypeError(f"register_batch_robust: unknown option(s) {sorted(unknown)}")
-        metric = options.get("metric", capi.ICP_POINT_TO_POINT)
-        max_iter = options.get("max_iter")
-        if max_iter is None:
-            max_iter = 50 if metric == capi.ICP_POINT_TO_PLANE else 40
-        return self._run_batch_options(metric, pairs, options.get("normals"), max_iter, options.get("tol", 1e-6),
-                                       options.get("fixed_iterations", False), options.get("max_distance"), options.get("init"),
-                                       options.get("trim"), options.get("reciprocal"), (kernel, scale))
+        _known_options("register_batch_robust", options)
+        return self._run_batch_keywords("register_batch_robust", options.get("metric", capi.ICP_POINT_TO_POINT), pairs, options, (kernel, scale))
 
     def register_batch_generalized(self, pairs, k=20, regularisation="frobenius", lam=1e-3, covariances=None, **options):
         """register_batch with the generalized (plane-to-plane) metric: every kept match pulls with the inverse of the summed
@@ -328,35 +319,16 @@ class Context:
         one (m, 6) float64 array per pair (Batch.set_covariances; covariances_from_normals makes them from good normals).
         options: register_batch's, by keyword, without metric and normals; robust kernels are not combined with this metric.  The
         same list of Result as register_batch."""
-        unknown = set(options) - {"max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal"}
-        if unknown:
-            raise TypeError(f"register_batch_generalized: unknown option(s) {sorted(unknown)}")
-        max_iter = options.get("max_iter")
-        if max_iter is None:
-            max_iter = 50
-        with Batch(self, pairs) as bt:
+        _known_options("register_batch_generalized", options)
+
+        def prepare(bt):
             if covariances is not None:
                 moving, model = covariances
                 bt.set_covariances(moving, model)
             else:
-                km, kq = k if isinstance(k, tuple) else (k, None)
-                bt.estimate_covariances(km, kq, regularisation=regularisation, lam=lam)
-            bt.set_max_distance(options.get("max_distance"))
-            bt.set_initial_transforms(options.get("init"))
-            if options.get("trim") is not None:
-                bt.set_trim(options["trim"])
-            if options.get("reciprocal") is not None:
-                bt.set_reciprocal(options["reciprocal"])
-            bt.begin(max_iter=max_iter, tol=options.get("tol", 1e-6), fixed_iterations=options.get("fixed_iterations", False), metric=capi.ICP_GENERALIZED)
-            while bt.run(1 << 20)[1] > 0:
-                pass
-            idx, inl, moved = bt.loop_indices(), bt.loop_inliers(), bt.get_moving()
-            out = []
-            for b in range(bt.count):
-                st = bt.state(b)
-                out.append(Result(T=st["T"].copy(), iterations=st["iterations"], passes=st["passes"], err=st["err"], idx=idx[b], moved=moved[b],
-                                  extra={"status": st["status"], "inliers": inl[b], "fitness": float(inl[b].sum()) / inl[b].size}))
-            return out
+                bt._estimate_covariances_k(k, regularisation, lam)
+
+        return self._run_batch_keywords("register_batch_generalized", capi.ICP_GENERALIZED, pairs, options, prepare=prepare)
 
     def register_batch_colored(self, pairs, intensities, k=8, lam=capi.ICP_COLOR_LAMBDA_DEFAULT, normals=None, **options):
         """register_batch with the colored metric (Park, Zhou, Koltun, ICCV 2017; Batch.begin with ICP_COLORED): every kept match
@@ -367,26 +339,16 @@ class Context:
         or one per pair; lam: a scalar or one per pair, in [0, 1]; normals: one (m, 3) array per pair, or None: estimated on the
         device.  options: register_batch's, by keyword, without metric and normals; robust kernels are not combined with this
         metric.  The same list of Result as register_batch."""
-        unknown = set(options) - {"max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal"}
-        if unknown:
-            raise TypeError(f"register_batch_colored: unknown option(s) {sorted(unknown)}")
-        max_iter = options.get("max_iter")
-        if max_iter is None:
-            max_iter = 50
+        _known_options("register_batch_colored", options)
         moving, model = intensities
 
         def prepare(bt):
-            if normals is not None:
-                bt.set_model_normals(normals)
-            else:
-                bt.estimate_normals()
+            bt._model_normals(normals)
             bt.set_intensities(moving, model)
             bt.estimate_intensity_gradients(k)
             bt.set_color_weight(lam)
 
-        return self._run_batch_options(capi.ICP_COLORED, pairs, None, max_iter, options.get("tol", 1e-6), options.get("fixed_iterations", False),
-                                       options.get("max_distance"), options.get("init"), options.get("trim"), options.get("reciprocal"), None,
-                                       prepare=prepare)
+        return self._run_batch_keywords("register_batch_colored", capi.ICP_COLORED, pairs, options, prepare=prepare)
 
     def register_batch_symmetric(self, pairs, k=20, orient="centroid", normals=None, **options):
         """register_batch with the symmetric metric (Rusinkiewicz, SIGGRAPH 2019; Batch.begin with ICP_SYMMETRIC): every kept match
@@ -397,12 +359,7 @@ class Context:
         from the covariances of k neighbours (Batch.estimate_covariances(k): a scalar or one value per pair, both sides) and
         oriented by orient (Batch.estimate_point_normals).  options: register_batch's, by keyword, without metric and normals;
         robust kernels are not combined with this metric.  The same list of Result as register_batch."""
-        unknown = set(options) - {"max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal"}
-        if unknown:
-            raise TypeError(f"register_batch_symmetric: unknown option(s) {sorted(unknown)}")
-        max_iter = options.get("max_iter")
-        if max_iter is None:
-            max_iter = 50
+        _known_options("register_batch_symmetric", options)
 
         def prepare(bt):
             if normals is not None:
@@ -412,9 +369,7 @@ class Context:
                 bt.estimate_covariances(k)
                 bt.estimate_point_normals(orient)
 
-        return self._run_batch_options(capi.ICP_SYMMETRIC, pairs, None, max_iter, options.get("tol", 1e-6), options.get("fixed_iterations", False),
-                                       options.get("max_distance"), options.get("init"), options.get("trim"), options.get("reciprocal"), None,
-                                       prepare=prepare)
+        return self._run_batch_keywords("register_batch_symmetric", capi.ICP_SYMMETRIC, pairs, options, prepare=prepare)
 
     def register_batch_global(self, pairs, voxel, k, hypotheses, max_distance, **options):
         """register_batch for pairs in unknown relative pose: a start pose from descriptors first, then the local loop from it.
@@ -441,11 +396,7 @@ class Context:
         neither fills the match list with ties nor lets the pose slide; seed is handed on.  The start pose is found on those
         clouds; the local loop runs on the full pairs as before.  extra["global"] gains "planes": the (2, 4) planes of the pair's
         moving cloud and model, and "plane_inliers": their two counts."""
-        known = {"planes", "viewpoint", "edge_similarity", "seed", "mutual", "gate", "metric", "normals", "max_iter", "tol", "fixed_iterations", "trim", "reciprocal",
-                 "method", "iterations", "division_factor", "decrease_every", "tuple_similarity", "keypoints", "device_normals"}
-        unknown = set(options) - known
-        if unknown:
-            raise TypeError(f"register_batch_global: unknown option(s) {sorted(unknown)}")
+        _known_options("register_batch_global", options)
         method = options.get("method", "ransac")
         if method not in ("ransac", "fgr"):
             raise ValueError(f"register_batch_global: method must be 'ransac' or 'fgr', not {method!r}")
@@ -519,11 +470,7 @@ class Context:
         status, iterations and T.
         metric ICP_GENERALIZED: every level estimates the covariances of its own clouds on the device; the options k,
         regularisation and lam are then read as register_batch_generalized takes them."""
-        known = {"metric", "normals", "max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal", "kernel", "scale",
-                 "k", "regularisation", "lam"}
-        unknown = set(options) - known
-        if unknown:
-            raise TypeError(f"register_batch_multiscale: unknown option(s) {sorted(unknown)}")
+        _known_options("register_batch_multiscale", options)
         voxels = [0.0 if v is None else float(v) for v in voxels]
         if not voxels:
             raise ValueError("register_batch_multiscale needs at least one level")
@@ -531,11 +478,10 @@ class Context:
         normals = options.get("normals")
         if normals is not None and any(v != 0.0 for v in voxels):
             raise ValueError("caller-given normals cannot follow a downsampled model: every level estimates its own")
-        max_iter = options.get("max_iter")
-        if max_iter is None:
-            max_iter = 40 if metric == capi.ICP_POINT_TO_POINT else 50
+        max_iter = _default_max_iter("register_batch_multiscale", metric, options.get("max_iter"))
         gate = options.get("max_distance")
         per_level = isinstance(gate, (list, tuple)) and len(gate) == len(voxels)
+        robust = (options["kernel"], options.get("scale")) if options.get("kernel") is not None else None
         with Batch(self, pairs) as full:
             T = options.get("init")
             levels = [[] for _ in range(full.count)]
@@ -544,40 +490,19 @@ class Context:
                 bt = full if v == 0.0 else full.downsample(v)
                 try:
                     if metric == capi.ICP_POINT_TO_PLANE:
-                        if normals is not None:
-                            bt.set_model_normals(normals)
-                        else:
-                            bt.estimate_normals()
+                        bt._model_normals(normals)
                     if metric == capi.ICP_GENERALIZED:
-                        k = options.get("k", 20)
-                        km, kq = k if isinstance(k, tuple) else (k, None)
-                        bt.estimate_covariances(km, kq, regularisation=options.get("regularisation", "frobenius"), lam=options.get("lam", 1e-3))
-                    bt.set_max_distance(gate[l] if per_level else gate)
-                    bt.set_initial_transforms(T)
-                    if options.get("trim") is not None:
-                        bt.set_trim(options["trim"])
-                    if options.get("reciprocal") is not None:
-                        bt.set_reciprocal(options["reciprocal"])
-                    if options.get("kernel") is not None:
-                        bt.set_robust(options["kernel"], options.get("scale"))
-                    bt.begin(max_iter=max_iter, tol=options.get("tol", 1e-6), fixed_iterations=options.get("fixed_iterations", False), metric=metric)
-                    while bt.run(1 << 20)[1] > 0:
-                        pass
-                    states = [bt.state(b) for b in range(bt.count)]
+                        bt._estimate_covariances_k(options.get("k", 20), options.get("regularisation", "frobenius"), options.get("lam", 1e-3))
+                    states = bt._drive(metric, max_iter, options.get("tol", 1e-6), options.get("fixed_iterations", False),
+                                       gate[l] if per_level else gate, T, options.get("trim"), options.get("reciprocal"), robust)
                     T = np.stack([st["T"] for st in states])
                     for b, st in enumerate(states):
                         levels[b].append({"voxel": v, "n": int(bt._moff[b + 1] - bt._moff[b]), "m": int(bt._qoff[b + 1] - bt._qoff[b]),
                                           "status": st["status"], "iterations": st["iterations"], "T": st["T"].copy()})
                     if l == len(voxels) - 1:
-                        idx, inl, moved = bt.loop_indices(), bt.loop_inliers(), bt.get_moving()
-                        wts = bt.get_weights() if options.get("kernel") is not None else None
-                        out = []
-                        for b, st in enumerate(states):
-                            out.append(Result(T=st["T"].copy(), iterations=st["iterations"], passes=st["passes"], err=st["err"], idx=idx[b], moved=moved[b],
-                                              extra={"status": st["status"], "inliers": inl[b], "fitness": float(inl[b].sum()) / inl[b].size,
-                                                     "levels": levels[b]}))
-                            if wts is not None:
-                                out[-1].extra["weights"] = wts[b]
+                        out = bt._results(states, robust is not None)
+                        for b, res in enumerate(out):
+                            res.extra["levels"] = levels[b]
                 finally:
                     if bt is not full:
                         bt.close()
@@ -596,31 +521,15 @@ class Context:
             if prepare is not None:
                 prepare(bt)
             if metric == capi.ICP_POINT_TO_PLANE:
-                if normals is not None:
-                    bt.set_model_normals(normals)
-                else:
-                    bt.estimate_normals()
-            bt.set_max_distance(max_distance)
-            bt.set_initial_transforms(init)
-            if trim is not None:
-                bt.set_trim(trim)
-            if reciprocal is not None:
-                bt.set_reciprocal(reciprocal)
-            if robust is not None:
-                bt.set_robust(*robust)
-            bt.begin(max_iter=max_iter, tol=tol, fixed_iterations=fixed_iterations, metric=metric)
-            while bt.run(1 << 20)[1] > 0:
-                pass
-            idx, inl, moved = bt.loop_indices(), bt.loop_inliers(), bt.get_moving()
-            wts = bt.get_weights() if robust is not None else None
-            out = []
-            for b in range(bt.count):
-                st = bt.state(b)
-                out.append(Result(T=st["T"].copy(), iterations=st["iterations"], passes=st["passes"], err=st["err"], idx=idx[b], moved=moved[b],
-                                  extra={"status": st["status"], "inliers": inl[b], "fitness": float(inl[b].sum()) / inl[b].size}))
-                if wts is not None:
-                    out[-1].extra["weights"] = wts[b]
-            return out
+                bt._model_normals(normals)
+            states = bt._drive(metric, max_iter, tol, fixed_iterations, max_distance, init, trim, reciprocal, robust)
+            return bt._results(states, robust is not None)
+
+    def _run_batch_keywords(self, where, metric, pairs, options, robust=None, prepare=None):
+        """_run_batch_options from the **options of the entry point `where`, with that entry point's default max_iter"""
+        return self._run_batch_options(metric, pairs, options.get("normals"), _default_max_iter(where, metric, options.get("max_iter")),
+                                       options.get("tol", 1e-6), options.get("fixed_iterations", False), options.get("max_distance"),
+                                       options.get("init"), options.get("trim"), options.get("reciprocal"), robust, prepare=prepare)
 
     def _run_batch(self, metric, pairs, normals, max_iter, tol, fixed_iterations):
         Ds, Ms, moff, qoff, dtype = _batch_arrays(pairs)
@@ -636,7 +545,7 @@ class Context:
         outs = (T.ctypes.data_as(pd), it.ctypes.data_as(pi), ps.ctypes.data_as(pi), err.ctypes.data_as(pd),
                 idx.ctypes.data_as(C.POINTER(C.c_int32)), moved.ctypes.data, st.ctypes.data_as(pi))
         if metric == capi.ICP_POINT_TO_PLANE:
-            N = _batch_normals(normals, Ms, dtype) if normals is not None else None
+            N = _batch_normals(normals, [M.shape for M in Ms], dtype) if normals is not None else None
             rc = self._lib.icp_point_to_plane_batch(self._h, count, D.ctypes.data, moff.ctypes.data_as(p64), M.ctypes.data, qoff.ctypes.data_as(p64),
                                                     N.ctypes.data if N is not None else None, C.byref(prm), *outs)
             capi.check(rc, "icp_point_to_plane_batch")
@@ -753,20 +662,80 @@ def _ptr(a, ctype=C.c_double):
     return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
 
 
-def _batch_normals(normals, Ms, dtype):
-    """one (m, 3) array of normals per pair -> their concatenation in the models' layout"""
+def _batch_normals(normals, shapes, dtype):
+    """one (m, 3) array of normals per pair -> their concatenation in the layout of the models, whose shapes are `shapes`"""
     normals = list(normals)
-    if len(normals) != len(Ms):
+    if len(normals) != len(shapes):
         raise ValueError("one array of normals per pair")
     Ns = [_as_cloud(N, dtype) for N in normals]
-    for N, M in zip(Ns, Ms):
-        if N.shape != M.shape:
+    for N, shape in zip(Ns, shapes):
+        if N.shape != shape:
             raise ValueError("a pair's normals must have the shape of its model")
     return np.concatenate(Ns)
 
 
+# the batch entry points that take **options: the names each accepts ...
+_LOOP_OPTIONS = {"max_iter", "tol", "fixed_iterations", "max_distance", "init", "trim", "reciprocal"}
+_OPTIONS = {
+    "register_batch_robust": _LOOP_OPTIONS | {"metric", "normals"},
+    "register_batch_generalized": _LOOP_OPTIONS,
+    "register_batch_colored": _LOOP_OPTIONS,
+    "register_batch_symmetric": _LOOP_OPTIONS,
+    "register_batch_multiscale": _LOOP_OPTIONS | {"metric", "normals", "kernel", "scale", "k", "regularisation", "lam"},
+    "register_batch_global": (_LOOP_OPTIONS - {"max_distance", "init"}) | {
+        "metric", "normals", "gate", "planes", "viewpoint", "edge_similarity", "seed", "mutual", "method", "iterations", "division_factor",
+        "decrease_every", "tuple_similarity", "keypoints", "device_normals"},
+}
+# ... and the max_iter of a caller who gives none: by metric, under None for every other metric.  register_batch follows the
+# one-call functions (50 is point_to_plane_batch's), the multiscale runs read it the other way round: they part at ICP_GENERALIZED
+_MAX_ITER = {
+    "register_batch": {capi.ICP_POINT_TO_PLANE: 50, None: 40},
+    "register_batch_robust": {capi.ICP_POINT_TO_PLANE: 50, None: 40},
+    "register_batch_multiscale": {capi.ICP_POINT_TO_POINT: 40, None: 50},
+    "register_batch_generalized": {None: 50},
+    "register_batch_colored": {None: 50},
+    "register_batch_symmetric": {None: 50},
+}
+
+
+def _known_options(where, options):
+    unknown = set(options) - _OPTIONS[where]
+    if unknown:
+        raise TypeError(f"{where}: unknown option(s) {sorted(unknown)}")
+
+
+def _default_max_iter(where, metric, max_iter):
+    if max_iter is not None:
+        return max_iter
+    return _MAX_ITER[where].get(metric, _MAX_ITER[where][None])
+
+
 _ROBUST_KINDS = {None: capi.ICP_ROBUST_NONE, "none": capi.ICP_ROBUST_NONE, "huber": capi.ICP_ROBUST_HUBER,
                  "cauchy": capi.ICP_ROBUST_CAUCHY, "tukey": capi.ICP_ROBUST_TUKEY}
+
+
+def _plane_rule(r):
+    if r[0] not in _PLANE_KINDS:
+        raise ValueError(f"unknown plane rule kind {r[0]!r}: 'detect', 'remove', 'keep' or None")
+    ax = [float(x) for x in r[3]]
+    if len(ax) != 3:
+        raise ValueError("a plane rule's axis has three components")
+    return capi.icp_plane_rule(_PLANE_KINDS[r[0]], int(r[2]), float(r[1]), (C.c_double * 3)(*ax), float(r[4]))
+
+
+def _keypoint_rule(r):
+    return capi.icp_keypoint_rule(capi.ICP_KEYPOINT_ISS, int(r[4]), float(r[0]), float(r[1]), float(r[2]), float(r[3]))
+
+
+_PLANE_KINDS = {"detect": capi.ICP_PLANE_DETECT, "remove": capi.ICP_PLANE_REMOVE, "keep": capi.ICP_PLANE_KEEP}
+# Batch._coded_rules: the struct, its NONE kind, what the first element of a single rule's tuple is, the fields of a rule as the
+# caller writes it -- (name, default), the first two are required -- and the struct of such a tuple
+_RULES = {
+    "plane": (capi.icp_plane_rule, capi.ICP_PLANE_NONE, lambda x: isinstance(x, str),
+              (("kind", None), ("distance", None), ("hypotheses", 1000), ("axis", (0, 0, 0)), ("min_cos", 0.0)), _plane_rule),
+    "keypoint": (capi.icp_keypoint_rule, capi.ICP_KEYPOINT_NONE, np.isscalar,
+                 (("salient_radius", None), ("non_max_radius", None), ("gamma_21", 0.975), ("gamma_32", 0.975), ("min_neighbours", 5)), _keypoint_rule),
+}
 
 
 class Batch:
@@ -775,41 +744,40 @@ class Batch:
     for it alone.  Outputs are split per pair."""
 
     def __init__(self, ctx, pairs):
-        self._ctx = ctx   # (keeps the context alive: a batch must go before it)
-        self._lib = ctx._lib
-        Ds, Ms, self._moff, qoff, self._dtype = _batch_arrays(pairs)
-        self._qoff = qoff
-        self._model_shapes = [M.shape for M in Ms]
-        self.count = len(Ds)
+        Ds, Ms, moff, qoff, dtype = _batch_arrays(pairs)
         D, M = np.concatenate(Ds), np.concatenate(Ms)
         h = C.c_void_p()
-        p64 = C.POINTER(C.c_int64)
-        capi.check(self._lib.icp_batch_create(ctx._h, self.count, D.ctypes.data, self._moff.ctypes.data_as(p64), M.ctypes.data,
-                                              qoff.ctypes.data_as(p64), _prec(self._dtype), C.byref(h)), "icp_batch_create")
-        self._h = h
-        self._max_iter = 0
+        capi.check(ctx._lib.icp_batch_create(ctx._h, len(Ds), D.ctypes.data, _ptr(moff, C.c_int64), M.ctypes.data, _ptr(qoff, C.c_int64),
+                                             _prec(dtype), C.byref(h)), "icp_batch_create")
+        self._adopt(ctx, h, dtype, moff, qoff)
 
     @classmethod
     def _from_handle(cls, ctx, h, count, dtype):
         """a Batch around a ready icp_batch handle (Batch.downsample): its layout is read back with icp_batch_get_offsets"""
         self = cls.__new__(cls)
-        self._ctx = ctx
+        moff, qoff = np.zeros(int(count) + 1, dtype=np.int64), np.zeros(int(count) + 1, dtype=np.int64)
+        capi.check(ctx._lib.icp_batch_get_offsets(h, _ptr(moff, C.c_int64), _ptr(qoff, C.c_int64)), "icp_batch_get_offsets")
+        self._adopt(ctx, h, dtype, moff, qoff)
+        return self
+
+    def _adopt(self, ctx, h, dtype, moff, qoff):
+        """the fields of a Batch around the handle h, whose clouds lie at the int64 offsets moff and qoff"""
+        self._ctx = ctx   # (keeps the context alive: a batch must go before it)
         self._lib = ctx._lib
         self._h = h
         self._max_iter = 0
         self._dtype = dtype
-        self.count = int(count)
-        self._moff = np.zeros(self.count + 1, dtype=np.int64)
-        self._qoff = np.zeros(self.count + 1, dtype=np.int64)
-        p64 = C.POINTER(C.c_int64)
-        capi.check(self._lib.icp_batch_get_offsets(h, self._moff.ctypes.data_as(p64), self._qoff.ctypes.data_as(p64)), "icp_batch_get_offsets")
-        self._model_shapes = [(int(self._qoff[b + 1] - self._qoff[b]), 3) for b in range(self.count)]
-        return self
+        self._moff, self._qoff = moff, qoff
+        self.count = len(moff) - 1
+        self._model_shapes = [(int(qoff[b + 1] - qoff[b]), 3) for b in range(self.count)]
 
-    def _per_pair(self, v, what):
-        a = np.asarray(v, dtype=np.float64)
+    def _per_pair(self, v, what, dtype=np.float64):
+        """a scalar for every pair, or one value per pair -> a contiguous (count,) array of dtype; None stays None (NULL)"""
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=dtype)
         if a.ndim == 0:
-            a = np.full(self.count, float(a))
+            a = np.full(self.count, a, dtype=dtype)
         a = np.ascontiguousarray(a)
         if a.shape != (self.count,):
             raise ValueError(f"one {what} per pair (or a scalar)")
@@ -824,27 +792,41 @@ class Batch:
         to its output point: (Batch, moving_maps, model_maps)."""
         vm = self._per_pair(voxel, "voxel edge")
         vq = vm if voxel_model is None else self._per_pair(voxel_model, "model voxel edge")
-        pd, p32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        mm = np.empty(int(self._moff[-1]), dtype=np.int32) if want_maps else None
-        qm = np.empty(int(self._qoff[-1]), dtype=np.int32) if want_maps else None
+        out, info = self._thin("icp_batch_downsample", (_ptr(vm), _ptr(vq)), [("map", C.c_int32, want_maps)])
+        return (out, info["moving_map"], info["model_map"]) if want_maps else out
+
+    def _thin(self, name, lead, outputs, tail=()):
+        """what downsample, remove_outliers, keypoints and segment_plane share: the C call `name`(handle, *lead, the optional
+        per-point outputs, *tail, &new handle) -> (the new Batch, info).  outputs: (key, element type, wanted) in the call's
+        order; a wanted one is a flat array per side, the moving clouds' before the models', cut per pair into
+        info["moving_" + key] and info["model_" + key]; one not wanted goes as two NULLs"""
+        flat, ptrs = [], []
+        for _, ctype, wanted in outputs:
+            for off in (self._moff, self._qoff):
+                flat.append(np.empty(int(off[-1]), dtype=ctype) if wanted else None)
+                ptrs.append(_ptr(flat[-1], ctype))
         h = C.c_void_p()
-        capi.check(self._lib.icp_batch_downsample(self._h, vm.ctypes.data_as(pd), vq.ctypes.data_as(pd), mm.ctypes.data_as(p32) if want_maps else None,
-                                                  qm.ctypes.data_as(p32) if want_maps else None, C.byref(h)), "icp_batch_downsample")
+        capi.check(getattr(self._lib, name)(self._h, *lead, *ptrs, *tail, C.byref(h)), name)
         out = Batch._from_handle(self._ctx, h, self.count, self._dtype)
-        if not want_maps:
-            return out
-        return out, self._split(mm), self._cut(qm, self._qoff)
+        info = {}
+        for (key, _, wanted), a, q in zip(outputs, flat[0::2], flat[1::2]):
+            if wanted:
+                info["moving_" + key], info["model_" + key] = self._split(a), self._cut(q, self._qoff)
+        return out, info
+
+    def _rule_list(self, rules, what, one):
+        """one rule (then `one` is true) or one per pair -> a list of count rules; what: "moving", "model plane", ..."""
+        rules = [rules] * self.count if one else list(rules)
+        if len(rules) != self.count:
+            raise ValueError(f"one {what} rule per pair (or a single rule)")
+        return rules
 
     def _outlier_rules(self, rules, what):
         """one rule or one per pair -> a ctypes array of count icp_outlier_rule (None: NULL, copy that side)"""
         if rules is None:
             return None
-        one = isinstance(rules, tuple) and len(rules) == 3 and isinstance(rules[0], str)
-        rules = [rules] * self.count if one else list(rules)
-        if len(rules) != self.count:
-            raise ValueError(f"one {what} rule per pair (or a single rule)")
         arr = (capi.icp_outlier_rule * self.count)()
-        for b, r in enumerate(rules):
+        for b, r in enumerate(self._rule_list(rules, what, isinstance(rules, tuple) and len(rules) == 3 and isinstance(rules[0], str))):
             if r is None:
                 arr[b] = capi.icp_outlier_rule(capi.ICP_OUTLIER_NONE, 0, 0.0)
             elif r[0] == "statistical":   # ("statistical", k, ratio)
@@ -865,63 +847,35 @@ class Batch:
         moving clouds first; want_maps adds "moving_map" and "model_map" (per pair, int32: the new index of a kept point, -1 for
         a removed one), want_scores "moving_score" and "model_score" (per pair, float64: the mean neighbour distance, or the
         neighbour count of a radius rule)."""
-        rm, rq = self._outlier_rules(moving, "moving"), self._outlier_rules(model, "model")
-        pd, p32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        n, m = int(self._moff[-1]), int(self._qoff[-1])
-        mm = np.empty(n, dtype=np.int32) if want_maps else None
-        qm = np.empty(m, dtype=np.int32) if want_maps else None
-        ms = np.empty(n, dtype=np.float64) if want_scores else None
-        qs = np.empty(m, dtype=np.float64) if want_scores else None
         stats = np.empty((2 * self.count, 4), dtype=np.float64)
-        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
-        h = C.c_void_p()
-        capi.check(self._lib.icp_batch_remove_outliers(self._h, rm, rq, ptr(mm, p32), ptr(qm, p32), ptr(ms, pd), ptr(qs, pd), ptr(stats, pd),
-                                                       C.byref(h)), "icp_batch_remove_outliers")
-        out = Batch._from_handle(self._ctx, h, self.count, self._dtype)
-        info = {"stats": stats}
-        per_model = lambda a: self._cut(a, self._qoff)
-        per_moving = lambda a: [a[self._moff[b]:self._moff[b + 1]].copy() for b in range(self.count)]
-        if want_maps:
-            info["moving_map"], info["model_map"] = per_moving(mm), per_model(qm)
-        if want_scores:
-            info["moving_score"], info["model_score"] = per_moving(ms), per_model(qs)
-        return out, info
+        out, info = self._thin("icp_batch_remove_outliers", (self._outlier_rules(moving, "moving"), self._outlier_rules(model, "model")),
+                               [("map", C.c_int32, want_maps), ("score", C.c_double, want_scores)], (_ptr(stats),))
+        return out, {"stats": stats, **info}
 
-    def _plane_rules(self, rules, what):
-        """one rule or one per pair -> (a ctypes array of count icp_plane_rule, the hypotheses of each); None: (NULL, zeros), copy
-        that side.  A rule is a tuple (kind, distance, hypotheses=1000, axis=(0, 0, 0), min_cos=0.0) or a dict of those names, kind
-        one of "detect", "remove", "keep"; None copies"""
+    def _coded_rules(self, rules, what, label):
+        """the codec of the plane and the keypoint rules (_RULES[label]): one rule or one per pair -> a ctypes array of count rule
+        structs (None: NULL, copy that side).  A rule is None (the NONE rule), a tuple of the table's first two fields or more, the
+        rest padded with the table's defaults, or a dict of the table's names; a single rule is a dict, or a tuple whose first
+        element passes the table's test"""
         if rules is None:
-            return None, [0] * self.count
-        one = isinstance(rules, dict) or (isinstance(rules, tuple) and len(rules) > 0 and isinstance(rules[0], str))
-        rules = [rules] * self.count if one else list(rules)
-        if len(rules) != self.count:
-            raise ValueError(f"one {what} plane rule per pair (or a single rule)")
-        names = ("kind", "distance", "hypotheses", "axis", "min_cos")
-        kinds = {"detect": capi.ICP_PLANE_DETECT, "remove": capi.ICP_PLANE_REMOVE, "keep": capi.ICP_PLANE_KEEP}
-        arr = (capi.icp_plane_rule * self.count)()
-        hyp = []
-        for b, r in enumerate(rules):
+            return None
+        struct, none, first, fields, make = _RULES[label]
+        names = tuple(name for name, _ in fields)
+        one = isinstance(rules, dict) or (isinstance(rules, tuple) and len(rules) > 0 and first(rules[0]))
+        arr = (struct * self.count)()
+        for b, r in enumerate(self._rule_list(rules, f"{what} {label}", one)):
             if r is None:
-                arr[b] = capi.icp_plane_rule(capi.ICP_PLANE_NONE, 0, 0.0, (C.c_double * 3)(0.0, 0.0, 0.0), 0.0)
-                hyp.append(0)
+                arr[b] = struct(none)   # (every other field 0)
                 continue
             if isinstance(r, dict):
-                if set(r) - set(names) or "kind" not in r or "distance" not in r:
-                    raise ValueError(f"a plane rule needs kind and distance, and may hold {names[2:]}")
-                r = (r["kind"], r["distance"]) + tuple(r.get(k, d) for k, d in zip(names[2:], (1000, (0.0, 0.0, 0.0), 0.0)))
+                if set(r) - set(names) or names[0] not in r or names[1] not in r:
+                    raise ValueError(f"a {label} rule needs {names[0]} and {names[1]}, and may hold {names[2:]}")
+                r = tuple(r.get(name, default) for name, default in fields)
             r = tuple(r)
-            if not 2 <= len(r) <= 5:
-                raise ValueError("a plane rule is (kind, distance, hypotheses=1000, axis=(0, 0, 0), min_cos=0.0)")
-            r = r + (1000, (0.0, 0.0, 0.0), 0.0)[len(r) - 2:]
-            if r[0] not in kinds:
-                raise ValueError(f"unknown plane rule kind {r[0]!r}: 'detect', 'remove', 'keep' or None")
-            ax = [float(x) for x in r[3]]
-            if len(ax) != 3:
-                raise ValueError("a plane rule's axis has three components")
-            arr[b] = capi.icp_plane_rule(kinds[r[0]], int(r[2]), float(r[1]), (C.c_double * 3)(*ax), float(r[4]))
-            hyp.append(int(r[2]))
-        return arr, hyp
+            if not 2 <= len(r) <= len(fields):
+                raise ValueError(f"a {label} rule is ({', '.join(names[:2] + tuple(f'{n}={d}' for n, d in fields[2:]))})")
+            arr[b] = make(r + tuple(default for _, default in fields[len(r):]))
+        return arr
 
     def segment_plane(self, moving=None, model=None, seed=0, want_masks=False, want_maps=False):
         """a new Batch on the same context whose clouds are this batch's clouds as uploaded without their dominant plane, or
@@ -935,32 +889,15 @@ class Batch:
         moving clouds first -- info["inliers"] (2 * count,) int32 and info["status"] (2 * count,) (ICP_OK; ICP_ERR_EMPTY where a
         cloud has no valid hypothesis: it is copied); want_masks adds "moving_mask" and "model_mask" (per pair, uint8: 1 = on
         the plane), want_maps "moving_map" and "model_map" (per pair, int32: the new index of a kept point, -1 for a removed one)."""
-        (rm, hm), (rq, hq) = self._plane_rules(moving, "moving"), self._plane_rules(model, "model")
+        rm, rq = self._coded_rules(moving, "moving", "plane"), self._coded_rules(model, "model", "plane")
         sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seed, dtype=np.uint64), (self.count,)))
-        pd, p32, p8 = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
-        n, m = int(self._moff[-1]), int(self._qoff[-1])
-        mk = np.empty(n, dtype=np.uint8) if want_masks else None
-        qk = np.empty(m, dtype=np.uint8) if want_masks else None
-        mm = np.empty(n, dtype=np.int32) if want_maps else None
-        qm = np.empty(m, dtype=np.int32) if want_maps else None
         planes = np.zeros((2 * self.count, 4), dtype=np.float64)
         inl = np.zeros(2 * self.count, dtype=np.int32)
         st = np.zeros(2 * self.count, dtype=np.intc)
-        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
-        h = C.c_void_p()
-        capi.check(self._lib.icp_batch_segment_plane(self._h, rm, rq, sd.ctypes.data_as(C.POINTER(C.c_uint64)), ptr(planes, pd), ptr(inl, p32),
-                                                     st.ctypes.data_as(C.POINTER(C.c_int)), ptr(mk, p8), ptr(qk, p8), ptr(mm, p32), ptr(qm, p32),
-                                                     C.byref(h)), "icp_batch_segment_plane")
-        self._segment_hyp = hm + hq
-        out = Batch._from_handle(self._ctx, h, self.count, self._dtype)
-        info = {"planes": planes, "inliers": inl, "status": st}
-        per_model = lambda a: self._cut(a, self._qoff)
-        per_moving = lambda a: [a[self._moff[b]:self._moff[b + 1]].copy() for b in range(self.count)]
-        if want_masks:
-            info["moving_mask"], info["model_mask"] = per_moving(mk), per_model(qk)
-        if want_maps:
-            info["moving_map"], info["model_map"] = per_moving(mm), per_model(qm)
-        return out, info
+        out, info = self._thin("icp_batch_segment_plane", (rm, rq, _ptr(sd, C.c_uint64), _ptr(planes), _ptr(inl, C.c_int32), _ptr(st, C.c_int)),
+                               [("mask", C.c_uint8, want_masks), ("map", C.c_int32, want_maps)])
+        self._segment_hyp = [0 if side is None else side[b].hypotheses for side in (rm, rq) for b in range(self.count)]   # (diag_segment)
+        return out, {"planes": planes, "inliers": inl, "status": st, **info}
 
     def diag_segment(self, b, side):
         """the last segment_plane call's hypotheses of pair b, side 0 (the moving cloud) or 1 (the model)
@@ -975,33 +912,6 @@ class Batch:
                                                     pl.ctypes.data_as(C.POINTER(C.c_double)), cn.ctypes.data_as(p32)), "icp_diag_batch_segment")
         return dict(triples=tr[:H], valid=va[:H], planes=pl[:H], counts=cn[:H])
 
-    def _keypoint_rules(self, rules, what):
-        """one rule or one per pair -> a ctypes array of count icp_keypoint_rule (None: NULL, copy that side).  A rule is a tuple
-        (salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbours=5) or a dict of those names; None copies"""
-        if rules is None:
-            return None
-        one = isinstance(rules, dict) or (isinstance(rules, tuple) and len(rules) > 0 and np.isscalar(rules[0]))
-        rules = [rules] * self.count if one else list(rules)
-        if len(rules) != self.count:
-            raise ValueError(f"one {what} keypoint rule per pair (or a single rule)")
-        names = ("salient_radius", "non_max_radius", "gamma_21", "gamma_32", "min_neighbours")
-        arr = (capi.icp_keypoint_rule * self.count)()
-        for b, r in enumerate(rules):
-            if r is None:
-                arr[b] = capi.icp_keypoint_rule(capi.ICP_KEYPOINT_NONE, 0, 0.0, 0.0, 0.0, 0.0)
-                continue
-            if isinstance(r, dict):
-                unknown = set(r) - set(names)
-                if unknown or "salient_radius" not in r or "non_max_radius" not in r:
-                    raise ValueError(f"a keypoint rule needs salient_radius and non_max_radius, and may hold {names[2:]}")
-                r = tuple(r[k] for k in names[:2]) + tuple(r.get(k, d) for k, d in zip(names[2:], (0.975, 0.975, 5)))
-            r = tuple(r)
-            if not 2 <= len(r) <= 5:
-                raise ValueError("a keypoint rule is (salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbours=5)")
-            r = r + (0.975, 0.975, 5)[len(r) - 2:]
-            arr[b] = capi.icp_keypoint_rule(capi.ICP_KEYPOINT_ISS, int(r[4]), float(r[0]), float(r[1]), float(r[2]), float(r[3]))
-        return arr
-
     def keypoints(self, moving=None, model=None, want_maps=False, want_saliency=False):
         """a new Batch on the same context whose clouds are the ISS keypoints of this batch's clouds as uploaded, made on the
         device (icp_batch_select_keypoints; the rule is stated in include/icp_mi355x.h).  moving, model: one rule or one per pair
@@ -1013,27 +923,10 @@ class Batch:
         are.  This batch is only read, and its loop does not notice.  Returns (Batch, info): info["counts"] is a (2 * count,) int32
         array of the kept points, the moving clouds first; want_maps adds "moving_map" and "model_map" (per pair, int32: the new
         index of a kept point, -1 for a dropped one), want_saliency "moving_saliency" and "model_saliency" (per pair, float64)."""
-        rm, rq = self._keypoint_rules(moving, "moving"), self._keypoint_rules(model, "model")
-        pd, p32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        n, m = int(self._moff[-1]), int(self._qoff[-1])
-        mm = np.empty(n, dtype=np.int32) if want_maps else None
-        qm = np.empty(m, dtype=np.int32) if want_maps else None
-        ms = np.empty(n, dtype=np.float64) if want_saliency else None
-        qs = np.empty(m, dtype=np.float64) if want_saliency else None
         counts = np.empty(2 * self.count, dtype=np.int32)
-        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
-        h = C.c_void_p()
-        capi.check(self._lib.icp_batch_select_keypoints(self._h, rm, rq, ptr(mm, p32), ptr(qm, p32), ptr(ms, pd), ptr(qs, pd), ptr(counts, p32),
-                                                        C.byref(h)), "icp_batch_select_keypoints")
-        out = Batch._from_handle(self._ctx, h, self.count, self._dtype)
-        info = {"counts": counts}
-        per_model = lambda a: self._cut(a, self._qoff)
-        per_moving = lambda a: [a[self._moff[b]:self._moff[b + 1]].copy() for b in range(self.count)]
-        if want_maps:
-            info["moving_map"], info["model_map"] = per_moving(mm), per_model(qm)
-        if want_saliency:
-            info["moving_saliency"], info["model_saliency"] = per_moving(ms), per_model(qs)
-        return out, info
+        out, info = self._thin("icp_batch_select_keypoints", (self._coded_rules(moving, "moving", "keypoint"), self._coded_rules(model, "model", "keypoint")),
+                               [("map", C.c_int32, want_maps), ("saliency", C.c_double, want_saliency)], (_ptr(counts, C.c_int32),))
+        return out, {"counts": counts, **info}
 
     def get_clouds(self):
         """the clouds the batch holds as uploaded (or as Batch.downsample made them; never the moved cloud): a list of (D, M)"""
@@ -1064,15 +957,15 @@ class Batch:
 
     def set_model_normals(self, normals):
         """the unit normals of every pair's model points (one (m, 3) array per pair): what a point-to-plane begin needs"""
-        normals = list(normals)
-        if len(normals) != self.count:
-            raise ValueError("one array of normals per pair")
-        Ns = [_as_cloud(N, self._dtype) for N in normals]
-        for N, shape in zip(Ns, self._model_shapes):
-            if N.shape != shape:
-                raise ValueError("a pair's normals must have the shape of its model")
-        N = np.concatenate(Ns)
+        N = _batch_normals(normals, self._model_shapes, self._dtype)
         capi.check(self._lib.icp_batch_set_model_normals(self._h, N.ctypes.data), "icp_batch_set_model_normals")
+
+    def _model_normals(self, normals):
+        """the caller's model normals, or None: estimated on the device"""
+        if normals is not None:
+            self.set_model_normals(normals)
+        else:
+            self.estimate_normals()
 
     def estimate_normals(self, want_neighbours=False):
         """kNN(4) + PCA normals of every pair's model on the device (one neighbour launch + one normals launch for all pairs);
@@ -1109,16 +1002,10 @@ class Batch:
         a, q = self._side(moving, self._moff, 6, "moving covariances"), self._side(model, self._qoff, 6, "model covariances")
         capi.check(self._lib.icp_batch_set_covariances(self._h, _ptr(a), _ptr(q)), "icp_batch_set_covariances")
 
-    def _cov_k(self, k, what):
-        if k is None:
-            return None
-        a = np.asarray(k)
-        if a.ndim == 0:
-            a = np.full(self.count, int(a))
-        a = np.ascontiguousarray(a, dtype=np.intc)
-        if a.shape != (self.count,):
-            raise ValueError(f"one {what} per pair (or a scalar)")
-        return a
+    def _estimate_covariances_k(self, k, regularisation, lam):
+        """estimate_covariances as the entry points take k: one value for both sides, or (k_moving, k_model)"""
+        km, kq = k if isinstance(k, tuple) else (k, None)
+        self.estimate_covariances(km, kq, regularisation=regularisation, lam=lam)
 
     def estimate_covariances(self, k=20, k_model=None, regularisation="frobenius", lam=1e-3, want=False):
         """the covariance of every point from its k nearest neighbours, on the device in one launch (icp_batch_estimate_covariances):
@@ -1130,8 +1017,7 @@ class Batch:
         Discards a loop under way."""
         reg = {"frobenius": capi.ICP_COV_FROBENIUS, "none": capi.ICP_COV_NONE, None: capi.ICP_COV_NONE}[regularisation] if (
             regularisation is None or isinstance(regularisation, str)) else int(regularisation)
-        km = self._cov_k(k, "k")
-        kq = self._cov_k(k if k_model is None else k_model, "model k")
+        km, kq = self._per_pair(k, "k", np.intc), self._per_pair(k if k_model is None else k_model, "model k", np.intc)
         om = np.empty((int(self._moff[-1]), 6)) if want and km is not None else None
         oq = np.empty((int(self._qoff[-1]), 6)) if want and kq is not None else None
         capi.check(self._lib.icp_batch_estimate_covariances(self._h, _ptr(km, C.c_int), _ptr(kq, C.c_int), reg, float(lam), _ptr(om), _ptr(oq)),
@@ -1157,7 +1043,7 @@ class Batch:
         other point no farther than the k-th nearest, ties included -- in the tangent plane of the point's normal.  The batch
         must hold model intensities and model normals.  k: a scalar or one value per pair, each in [3, 32].  want: also return
         the per-pair list of (m, 3) float64 gradients.  Discards a loop under way."""
-        kq = self._cov_k(k, "k")
+        kq = self._per_pair(k, "k", np.intc)
         out = np.empty((int(self._qoff[-1]), 3)) if want else None
         capi.check(self._lib.icp_batch_estimate_intensity_gradients(self._h, _ptr(kq, C.c_int), _ptr(out)), "icp_batch_estimate_intensity_gradients")
         if want:
@@ -1177,16 +1063,7 @@ class Batch:
     def set_color_weight(self, lam=None):
         """lambda, the weight of the geometric term of the colored metric (1 - lambda weighs the photometric term): a scalar for
         every pair, one value per pair, each in [0, 1], or None: ICP_COLOR_LAMBDA_DEFAULT.  Discards a loop under way."""
-        if lam is None:
-            capi.check(self._lib.icp_batch_set_color_weight(self._h, None), "icp_batch_set_color_weight")
-            return
-        a = np.asarray(lam, dtype=np.float64)
-        if a.ndim == 0:
-            a = np.full(self.count, float(a))
-        a = np.ascontiguousarray(a)
-        if a.shape != (self.count,):
-            raise ValueError("one lambda per pair (or a scalar)")
-        capi.check(self._lib.icp_batch_set_color_weight(self._h, a.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_color_weight")
+        capi.check(self._lib.icp_batch_set_color_weight(self._h, _ptr(self._per_pair(lam, "lambda"))), "icp_batch_set_color_weight")
 
     def diag_rotation(self, b):
         """(3, 3): the rotation pair b's most recent matching pass of a generalized loop rotated its moving covariances by, or of
@@ -1203,7 +1080,7 @@ class Batch:
         holds as uploaded, never the moved ones; a loop under way is left alone.  want: also return (moving, model), per pair the
         (points, 33) float64 descriptors."""
         moving, model = normals
-        km, kq = self._cov_k(k, "k"), self._cov_k(k if k_model is None else k_model, "model k")
+        km, kq = self._per_pair(k, "k", np.intc), self._per_pair(k if k_model is None else k_model, "model k", np.intc)
         nm, nq = self._side(list(moving), self._moff, 3, "moving normals"), self._side(list(model), self._qoff, 3, "model normals")
         om = np.empty((int(self._moff[-1]), capi.ICP_FEATURE_BINS)) if want else None
         oq = np.empty((int(self._qoff[-1]), capi.ICP_FEATURE_BINS)) if want else None
@@ -1258,7 +1135,7 @@ class Batch:
     def compute_features_stored(self, k, k_model=None, want=False):
         """compute_features from the point normals the batch holds (estimate_point_normals, set_point_normals): the same two
         launches, nothing uploaded (icp_batch_compute_features_stored)"""
-        km, kq = self._cov_k(k, "k"), self._cov_k(k if k_model is None else k_model, "model k")
+        km, kq = self._per_pair(k, "k", np.intc), self._per_pair(k if k_model is None else k_model, "model k", np.intc)
         om = np.empty((int(self._moff[-1]), capi.ICP_FEATURE_BINS)) if want else None
         oq = np.empty((int(self._qoff[-1]), capi.ICP_FEATURE_BINS)) if want else None
         capi.check(self._lib.icp_batch_compute_features_stored(self._h, _ptr(km, C.c_int), _ptr(kq, C.c_int), _ptr(om), _ptr(oq)),
@@ -1311,7 +1188,7 @@ class Batch:
         if T.ndim != 4 or T.shape[0] != self.count or T.shape[2:] != (4, 4) or T.shape[1] < 1:
             raise ValueError("candidate transforms must be (count, per_pair, 4, 4)")
         T = np.ascontiguousarray(T)
-        md = None if max_distance is None else self._per_pair(max_distance, "maximum distance")
+        md = self._per_pair(max_distance, "maximum distance")
         pd = C.POINTER(C.c_double)
         out = np.zeros((self.count, T.shape[1]), dtype=np.int32)
         capi.check(self._lib.icp_batch_score_transforms(self._h, int(T.shape[1]), T.ctypes.data_as(pd), _ptr(md),
@@ -1324,16 +1201,13 @@ class Batch:
         check, solved on the host and scored on the device; the best is refitted on its inliers.  Per pair a dict of T (4, 4: maps
         the moving cloud as uploaded into the model's frame -- what set_initial_transforms takes), inliers, correspondences and
         status (ICP_OK, or ICP_ERR_EMPTY where fewer than three correspondences or no valid hypothesis exist: T is then the identity)."""
-        sd = np.asarray(seed)
-        sd = np.full(self.count, int(sd), dtype=np.uint64) if sd.ndim == 0 else np.ascontiguousarray(sd, dtype=np.uint64)
-        if sd.shape != (self.count,):
-            raise ValueError("one seed per pair (or a scalar)")
+        sd = self._per_pair(seed, "seed", np.uint64)
         prm = capi.icp_ransac_params(int(hypotheses), float(max_distance), float(edge_similarity))
         T = np.zeros((self.count, 4, 4))
         inl, cor = np.zeros(self.count, dtype=np.int32), np.zeros(self.count, dtype=np.int32)
         st = np.zeros(self.count, dtype=np.intc)
         p32 = C.POINTER(C.c_int32)
-        capi.check(self._lib.icp_batch_ransac(self._h, C.byref(prm), sd.ctypes.data_as(C.POINTER(C.c_uint64)), T.ctypes.data_as(C.POINTER(C.c_double)),
+        capi.check(self._lib.icp_batch_ransac(self._h, C.byref(prm), _ptr(sd, C.c_uint64), T.ctypes.data_as(C.POINTER(C.c_double)),
                                               inl.ctypes.data_as(p32), cor.ctypes.data_as(p32), st.ctypes.data_as(C.POINTER(C.c_int))), "icp_batch_ransac")
         self._ransac_hyp = int(hypotheses)
         return [dict(T=T[b].copy(), inliers=int(inl[b]), correspondences=int(cor[b]), status=int(st[b])) for b in range(self.count)]
@@ -1360,12 +1234,7 @@ class Batch:
         that was not used -- used (how many correspondences were), objective and status (ICP_OK; ICP_ERR_EMPTY where fewer than
         three correspondences are used: T is then the identity; ICP_ERR_SINGULAR where a step's system was not positive definite:
         T is then the pose reached so far)."""
-        sd = None
-        if int(tuples) > 0:
-            sd = np.asarray(seed)
-            sd = np.full(self.count, int(sd), dtype=np.uint64) if sd.ndim == 0 else np.ascontiguousarray(sd, dtype=np.uint64)
-            if sd.shape != (self.count,):
-                raise ValueError("one seed per pair (or a scalar)")
+        sd = self._per_pair(seed, "seed", np.uint64) if int(tuples) > 0 else None
         prm = capi.icp_fgr_params(int(iterations), float(max_distance), float(division_factor), int(decrease_every), int(tuples), float(tuple_similarity))
         T = np.zeros((self.count, 4, 4))
         w = np.zeros(int(self._moff[-1]))
@@ -1403,31 +1272,13 @@ class Batch:
     def set_max_distance(self, v):
         """the maximum correspondence distance: a scalar for every pair, one value per pair (inf: that pair is not gated), or
         None (no gate).  A match farther away than that enters no sum of its pass.  Discards a loop under way."""
-        if v is None:
-            capi.check(self._lib.icp_batch_set_max_distance(self._h, None), "icp_batch_set_max_distance")
-            return
-        a = np.asarray(v, dtype=np.float64)
-        if a.ndim == 0:
-            a = np.full(self.count, float(a))
-        a = np.ascontiguousarray(a)
-        if a.shape != (self.count,):
-            raise ValueError("one maximum distance per pair (or a scalar)")
-        capi.check(self._lib.icp_batch_set_max_distance(self._h, a.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_max_distance")
+        capi.check(self._lib.icp_batch_set_max_distance(self._h, _ptr(self._per_pair(v, "maximum distance"))), "icp_batch_set_max_distance")
 
     def set_trim(self, v):
         """the share of every moving cloud to keep: a scalar for every pair, one value per pair (1.0: that pair is not trimmed), or
         None (no trimming).  Each in (0, 1].  A pair keeps the K = ceil(share * n) closest matches of every pass and every match
         tied with the K-th; the others enter no sum.  Discards a loop under way."""
-        if v is None:
-            capi.check(self._lib.icp_batch_set_trim(self._h, None), "icp_batch_set_trim")
-            return
-        a = np.asarray(v, dtype=np.float64)
-        if a.ndim == 0:
-            a = np.full(self.count, float(a))
-        a = np.ascontiguousarray(a)
-        if a.shape != (self.count,):
-            raise ValueError("one share to keep per pair (or a scalar)")
-        capi.check(self._lib.icp_batch_set_trim(self._h, a.ctypes.data_as(C.POINTER(C.c_double))), "icp_batch_set_trim")
+        capi.check(self._lib.icp_batch_set_trim(self._h, _ptr(self._per_pair(v, "share to keep"))), "icp_batch_set_trim")
 
     def diag_trim(self, b):
         """(tau_sq, K) of pair b (icp_diag_batch_trim): the squared-distance threshold of its most recent matching pass (inf for a
@@ -1472,16 +1323,7 @@ class Batch:
         if len(kinds) != self.count:
             raise ValueError("one robust kernel per pair (or one for every pair, or None)")
         k = np.ascontiguousarray([_ROBUST_KINDS[x] if (x is None or isinstance(x, str)) else int(x) for x in kinds], dtype=np.intc)
-        sp = None
-        if scale is not None:
-            a = np.asarray(scale, dtype=np.float64)
-            if a.ndim == 0:
-                a = np.full(self.count, float(a))
-            a = np.ascontiguousarray(a)
-            if a.shape != (self.count,):
-                raise ValueError("one scale per pair (or a scalar)")
-            sp = a.ctypes.data_as(C.POINTER(C.c_double))
-        capi.check(self._lib.icp_batch_set_robust(self._h, k.ctypes.data_as(C.POINTER(C.c_int)), sp), "icp_batch_set_robust")
+        capi.check(self._lib.icp_batch_set_robust(self._h, _ptr(k, C.c_int), _ptr(self._per_pair(scale, "scale"))), "icp_batch_set_robust")
 
     def get_weights(self):
         """per pair, (n,) float64: the weight of every moving point's match in the pair's most recent matching pass
@@ -1519,6 +1361,35 @@ class Batch:
         k, a = C.c_int(0), C.c_int(0)
         capi.check(self._lib.icp_batch_run(self._h, int(steps), C.byref(k), C.byref(a)), "icp_batch_run")
         return k.value, a.value
+
+    def _drive(self, metric, max_iter, tol, fixed_iterations, max_distance, init, trim, reciprocal, robust):
+        """what every batch entry point does with a prepared batch: the per-pair options (the gate and the start poses always, None
+        too, which clears them; trim, reciprocity and robust -- (kernel, scale) -- only where given), begin, run to the end.
+        Returns every pair's state"""
+        self.set_max_distance(max_distance)
+        self.set_initial_transforms(init)
+        if trim is not None:
+            self.set_trim(trim)
+        if reciprocal is not None:
+            self.set_reciprocal(reciprocal)
+        if robust is not None:
+            self.set_robust(*robust)
+        self.begin(max_iter=max_iter, tol=tol, fixed_iterations=fixed_iterations, metric=metric)
+        while self.run(1 << 20)[1] > 0:
+            pass
+        return [self.state(b) for b in range(self.count)]
+
+    def _results(self, states, weights):
+        """the list of Result of a finished loop from _drive's states; weights: also extra["weights"] (a robust run)"""
+        idx, inl, moved = self.loop_indices(), self.loop_inliers(), self.get_moving()
+        wts = self.get_weights() if weights else None
+        out = []
+        for b, st in enumerate(states):
+            out.append(Result(T=st["T"].copy(), iterations=st["iterations"], passes=st["passes"], err=st["err"], idx=idx[b], moved=moved[b],
+                              extra={"status": st["status"], "inliers": inl[b], "fitness": float(inl[b].sum()) / inl[b].size}))
+            if wts is not None:
+                out[-1].extra["weights"] = wts[b]
+        return out
 
     def state(self, b):
         st, it, ps = C.c_int(0), C.c_int(0), C.c_int(0)
@@ -1578,14 +1449,7 @@ class Batch:
         that pair counts), or None (every match counts) -- the evaluation's own distance, not the batch's gate.  One dict per pair:
         status, inliers, fitness (inliers / n), rmse (over the inliers), information (6 x 6 float64, order rx ry rz tx ty tz: the
         metric's Gauss-Newton matrix over the inliers); with want_matches also idx and inliers_mask (bool)."""
-        md = None
-        if max_distance is not None:
-            a = np.asarray(max_distance, dtype=np.float64)
-            if a.ndim == 0:
-                a = np.full(self.count, float(a))
-            md = np.ascontiguousarray(a)
-            if md.shape != (self.count,):
-                raise ValueError("one evaluation distance per pair (or a scalar)")
+        md = self._per_pair(max_distance, "evaluation distance")
         total = int(self._moff[-1])
         status, inl = np.zeros(self.count, dtype=np.intc), np.zeros(self.count, dtype=np.int32)
         fit, rmse, info = np.zeros(self.count), np.zeros(self.count), np.zeros((self.count, 6, 6))
@@ -1595,8 +1459,7 @@ class Batch:
         capi.check(self._lib.icp_batch_evaluate(self._h, int(metric), _ptr(md),
                                                 status.ctypes.data_as(C.POINTER(C.c_int)), inl.ctypes.data_as(pi32), fit.ctypes.data_as(pd),
                                                 rmse.ctypes.data_as(pd), info.ctypes.data_as(pd),
-                                                idx.ctypes.data_as(pi32) if want_matches else None,
-                                                mask.ctypes.data_as(C.POINTER(C.c_uint8)) if want_matches else None), "icp_batch_evaluate")
+                                                _ptr(idx, C.c_int32), _ptr(mask, C.c_uint8)), "icp_batch_evaluate")
         out = [dict(status=int(status[b]), inliers=int(inl[b]), fitness=float(fit[b]), rmse=float(rmse[b]), information=info[b].copy())
                for b in range(self.count)]
         if want_matches:
